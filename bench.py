@@ -2,7 +2,7 @@
 """Headline benchmark: ELBO-Hessian builds/sec (+ LRVB-covariance solve time) at
 N = 1e6 observations x D = 1024 free parameters (BASELINE.json `metric`), synthetic data.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 One "step" = one Hessian build: (theta, w) resident in HBM -> dense free-coordinate Hessian
 (both triangles) in HBM, including the pass over all observations (weights are an input, so
@@ -48,7 +48,41 @@ def parse(argv=None):
                     help='h = the headline metric (default, what the driver runs; at N = 1 its line also carries short runs of '
                          'c2..c5 under `configs`); c2..c5 = the other BASELINE.json configurations, one line each with its own '
                          'roofline, observations sharded over --gpus ranks')
-    return ap.parse_args(argv)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy '
+                         '(float64, at most 64 MB in all; a larger result is written as a fixed, seeded sample of its entries)')
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+NPY_HEADER_BYTES = 4096          # room left in each share for the .npy header
+
+
+def dump_outputs(path, arrays):
+    """Writes {name: array} as path/<name>.npy and returns {name: {shape, sampled}} for the JSON line.  Each array gets an equal
+    share of DUMP_BUDGET_BYTES; one over its share is written as the entries at a fixed set of flat indices (drawn from a
+    seeded generator and sorted), so that two builds of the project are compared on the same entries.  A directory created
+    here gets a .gitignore of its own, so that a dump inside the repository leaves `git status` clean."""
+    import numpy as np
+    if not os.path.isdir(path):
+        os.makedirs(path)
+        with open(os.path.join(path, '.gitignore'), 'w') as fh:
+            fh.write('*\n')
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    info = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64, copy=False)
+        shape, sampled = list(a.shape), a.nbytes > share - NPY_HEADER_BYTES
+        if sampled:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=(share - NPY_HEADER_BYTES) // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + '.npy'), a)
+        info[name] = {'shape': shape, 'sampled': bool(sampled)}
+    return info
 
 
 def _free_port():
@@ -452,6 +486,8 @@ def run_config(args, cfg=None, steps=None, warmup=None, env=None):
     per_rank = _gather_floats(torch, dist, [kernel_ms, prof['reduce_ms'] / steps, prof['reduce_calls'] / steps], dev, backend, use_dist)
     scale = 1e9 if unit == 'GB/s' else 1e12
     achieved = alg / (kernel_ms * 1e-3) / scale if kernel_ms > 0 else 0.0
+    # a step leaves its result in HBM; final() is the same call chain at the same point with the copy back (every rank takes part)
+    H_final = final()
     out = {
         'metric': metric, 'value': steps / elapsed, 'unit': 'builds/s', 'n_gpus': world, 'steps': steps, 'warmup': warmup,
         'ms_per_step': ms_per_step, 'higher_is_better': True, 'scaling': 'strong', 'vs_baseline': None,
@@ -460,7 +496,7 @@ def run_config(args, cfg=None, steps=None, warmup=None, env=None):
                    'ranks_seen': dist.get_world_size() if use_dist else 1,
                    'backend': (backend + (' (in-library communicator)' if native else '')) if use_dist else 'none (single process)',
                    'parallelism': 'observation shards x{} + 1 device all-reduce per statistics call'.format(world),
-                   'result_fingerprint': _fingerprint(np, final())},
+                   'result_fingerprint': _fingerprint(np, H_final)},
         'roofline': {'bound': bound, 'achieved': achieved, 'peak': peak, 'unit': unit, 'frac': achieved / peak, 'traffic': None,
                      'kernel': 'ALL statistics kernels of one step on this rank (library profile marks: {} launch groups per step)'.format(
                          prof['wsyrk_calls'] // max(steps, 1)),
@@ -468,6 +504,8 @@ def run_config(args, cfg=None, steps=None, warmup=None, env=None):
                      'step_frac': alg / (ms_per_step * 1e-3) / scale / peak},
     }
     out['roofline'].update(extra)
+    if own_group and rank == 0 and args.dump_outputs:
+        out['dumped_outputs'] = dump_outputs(args.dump_outputs, {'hessian': H_final})
     out['exchange'] = {'per_rank_kernel_ms': [r[0] for r in per_rank], 'allreduce_ms': [r[1] for r in per_rank],
                        'allreduce_calls_per_step': per_rank[0][2],
                        'note': 'HIP events on each rank\'s stream: all statistics kernels of a step / around the sum-over-ranks hook '
@@ -660,6 +698,8 @@ def main(args):
     elapsed = time.perf_counter() - t0
     prof = ctx.profile_get()
     ctx.profile_enable(False)
+    # the Hessian of the last timed step, copied now: the legs below factor H in place and build into it again
+    H_last = Hout.detach().cpu().numpy() if args.dump_outputs and rank == 0 else None
     # the three phases of a sharded build on this rank's stream: statistics kernels | exchange | N-independent assembly
     phases = None
     if sharded is not None:
@@ -863,6 +903,8 @@ def main(args):
                 out['parity'] = {'skipped': 'the strong-numpy leg did not reach all rows within its time budget'}
     if configs_out is not None:
         out['configs'] = configs_out
+    if H_last is not None:
+        out['dumped_outputs'] = dump_outputs(args.dump_outputs, {'hessian': H_last})
     if use_dist:
         dist.destroy_process_group()
     return out if rank == 0 else None

@@ -123,3 +123,33 @@ def test_stdout_carries_only_the_result_line(monkeypatch, capfd):
     finally:
         os.dup2(saved, 1)
         os.close(saved)
+
+
+def test_steps_flag_is_validated_and_dump_outputs_parsed():
+    bench = _bench()
+    assert bench.parse([]).dump_outputs is None
+    assert bench.parse(['--steps', '7', '--dump-outputs', 'out']).dump_outputs == 'out'
+    import pytest
+    with pytest.raises(SystemExit):
+        bench.parse(['--steps', '0'])
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    """Small results are written whole; a result over its share of the 64 MB budget becomes the same seeded sample of entries
+    in every run; a directory the dump creates ignores itself."""
+    bench = _bench()
+    rng = np.random.default_rng(1)
+    small = rng.normal(size=(64, 64))
+    big = rng.normal(size=(4096, 4096))                      # 128 MB in float64
+    d = tmp_path / 'dump'
+    info = bench.dump_outputs(str(d), {'small': small, 'big': big})
+    assert info == {'small': {'shape': [64, 64], 'sampled': False}, 'big': {'shape': [4096, 4096], 'sampled': True}}
+    assert (d / '.gitignore').read_text() == '*\n'
+    s, b = np.load(d / 'small.npy'), np.load(d / 'big.npy')
+    assert s.dtype == np.float64 and np.array_equal(s, small)
+    assert b.dtype == np.float64 and b.size > 0 and np.all(np.isin(b[:100], big))
+    assert sum(f.stat().st_size for f in d.iterdir()) <= bench.DUMP_BUDGET_BYTES
+    bench.dump_outputs(str(d), {'small': small, 'big': big})
+    assert np.array_equal(np.load(d / 'big.npy'), b)
+    i32 = bench.dump_outputs(str(tmp_path / 'f'), {'h': np.arange(6, dtype=np.int32)})
+    assert i32['h']['sampled'] is False and np.load(tmp_path / 'f' / 'h.npy').dtype == np.float64

@@ -318,6 +318,23 @@ int lrvb_gh_logistic(lrvb_ctx* ctx, int64_t n, const double* z_mean, const doubl
  * derivatives of the quadrature sum as weights.  The context must hold X and y (any GLM loss).                       */
 int lrvb_logitnormal_terms(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* gh_x,
                            const double* gh_w, int32_t n_nodes, double* value_out, double* grad_out, double* H_blocks_out);
+/* The same model with a full-covariance posterior q(beta) = N(mean, cov), P = n_cols <= 64 (LRVB_ERR_UNSUPPORTED above:
+ * the Sigma-Sigma block is the packed-triangle Kronecker SYRK, whose stage holds 64 columns).  Data term
+ *   sum_n w_n ( psi(x_n . mean, x_n^T cov x_n) - y_n x_n . mean ),   psi(mu, s) = E log(1 + e^z), z ~ N(mu, s)  (Gauss-Hermite)
+ * in the D = P + P (P + 1) / 2 coordinates (mean, vech cov), vech = row-major lower triangle, an off-diagonal coordinate
+ * standing for both entries: value, gradient (D, nullable) and Hessian (D x D, row-major, nullable).  Derivatives in the
+ * variance s are Stein's identity on the same nodes (d_s E g = E g'' / 2, ...), so a zero design row is regular.       */
+int lrvb_logitnormal_mvn_terms(lrvb_ctx* ctx, const double* mean, const double* cov, int64_t P, const double* gh_x,
+                               const double* gh_w, int32_t n_nodes, double* value_out, double* grad_out, double* H_out);
+/* Matrix-free product of that data-term Hessian with v (D, coordinates (mean, vech cov)) -> out (D): two row passes, one
+ * gemv and one weighted SYRK of X; no D x D matrix is formed.                                                          */
+int lrvb_logitnormal_mvn_hvp(lrvb_ctx* ctx, const double* mean, const double* cov, int64_t P, const double* gh_x,
+                             const double* gh_w, int32_t n_nodes, const double* v, double* out);
+/* Chain of a Hessian H_in (D x D) in (mean, vech Sigma) to (mean, vech Lambda), Lambda = Sigma^-1, on the device:
+ *   H_out = J^T H_in J + [0, 0; 0, 2 symkron(M, Sigma) - 1/2 symkron(Sigma, Sigma)],  J = d vech Sigma / d vech Lambda,
+ * where M = Sigma G Sigma for the symmetric matrix gradient G of the objective in Sigma (the second-order term of
+ * Lambda -> Lambda^-1) and the last term is the Hessian of +1/2 log det Lambda (minus the entropy).  No observations are involved.          */
+int lrvb_logitnormal_mvn_chain(lrvb_ctx* ctx, int64_t P, const double* cov, const double* M, const double* H_in, double* H_out);
 
 /* ---- objectives that are quadratic in the data ------------------------------------------
  * S = Z^T diag(w) Z (n_cols x n_cols, both triangles) with the context's current weights: the

@@ -81,6 +81,9 @@ _SIGNATURES = {
     'lrvb_obs_loss': [_VP, _VP, c_i64, ctypes.c_int, c_i64, c_i64, _VP],
     'lrvb_gh_logistic': [_VP, c_i64, _VP, _VP, _VP, _VP, ctypes.c_int32, ctypes.c_int32, _VP, _VP, _VP],
     'lrvb_logitnormal_terms': [_VP, _VP, _VP, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, _VP],
+    'lrvb_logitnormal_mvn_terms': [_VP, _VP, _VP, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, _VP],
+    'lrvb_logitnormal_mvn_hvp': [_VP, _VP, _VP, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP],
+    'lrvb_logitnormal_mvn_chain': [_VP, c_i64, _VP, _VP, _VP, _VP],
     'lrvb_hvec_begin': [_VP],
     'lrvb_hvec_add_block': [_VP, _VP, c_i64, c_i64, c_i64, c_i64, ctypes.c_int],
     'lrvb_hvec_add_indexed': [_VP, _VP, c_i64, c_i64, _VP, _VP],

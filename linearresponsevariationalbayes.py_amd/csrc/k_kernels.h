@@ -113,3 +113,18 @@ void cg_multi_tail_kernel(i64 D, double sq, const double* __restrict__ quadA /* 
                           const double* __restrict__ j2, const double* __restrict__ g, const double* __restrict__ W,
                           const double* __restrict__ U, const double* __restrict__ Pm, double* __restrict__ X,
                           double* __restrict__ R, const double* __restrict__ s, i64 Q);
+
+// k_logitmvn.hip
+__global__ __launch_bounds__(256)
+void lmvn_coef_kernel(i64 n, const double* __restrict__ mu, const double* __restrict__ s, const double* __restrict__ y,
+                      const double* __restrict__ w, const double* __restrict__ gx, const double* __restrict__ gw, int K,
+                      double* __restrict__ a1, double* __restrict__ a2, double* __restrict__ c11, double* __restrict__ c12,
+                      double* __restrict__ c22, double* __restrict__ vpart);
+__global__ void lmvn_dup_scale_kernel(i64 total, i64 Pv, int P, double* __restrict__ H, i64 ld);
+__global__ void lmvn_vech_grad_kernel(i64 total, int P, const double* __restrict__ G, double* __restrict__ g);
+__global__ void lmvn_mirror_kernel(i64 total, i64 Pv, int P, double* __restrict__ H, i64 ld);
+__global__ void lmvn_copy_block_kernel(i64 total, i64 C, const double* __restrict__ src, i64 lds, double* __restrict__ dst, i64 ldd);
+__global__ void lmvn_jac_rows_kernel(i64 total, i64 Pv, double* __restrict__ S);
+__global__ void lmvn_hvp_coef_kernel(i64 n, const double* __restrict__ c11, const double* __restrict__ c12, const double* __restrict__ c22,
+                                     const double* __restrict__ dmu, const double* __restrict__ ds, double* __restrict__ em,
+                                     double* __restrict__ es);

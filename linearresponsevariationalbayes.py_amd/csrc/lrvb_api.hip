@@ -225,7 +225,7 @@ extern "C" int lrvb_ctx_destroy(lrvb_ctx* c) {
     DevBuf* all[] = { &c->X, &c->y, &c->w, &c->quadA, &c->quadM, &c->quadB, &c->theta, &c->eta, &c->j1, &c->j2,
                       &c->vtmp, &c->vtmp2, &c->vtmp3, &c->g_eta, &c->g_free, &c->lp, &c->cw, &c->zbuf,
                       &c->part_vec, &c->part_val, &c->stats, &c->tile_part, &c->Heta, &c->Hfree, &c->Jdense,
-                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->Hres, &c->hres_theta, &c->qstats };
+                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->Hres, &c->hres_theta, &c->qstats, &c->lmvn };
     for (DevBuf* b : all) buf_free(*b);
     if (c->host_pinned) (void)hipHostFree(c->host_pinned);
     if (c->up_ring) { for (int k = 0; k < lrvb_ctx::UP_SLOTS; ++k) if (c->up_ev[k]) (void)hipEventDestroy(c->up_ev[k]); (void)hipHostFree(c->up_ring); }
@@ -2512,6 +2512,155 @@ extern "C" int lrvb_logitnormal_terms(lrvb_ctx* c, const double* mean, const dou
     if (want_g) LRVB_TRY(d2h(c, grad_out, gred, (size_t)(2 * P)));
     if (want_H) LRVB_TRY(d2h(c, H_blocks_out, Hb, (size_t)(3 * P * P)));
     return LRVB_OK;
+}
+
+// ---- logistic regression with a full-covariance Gaussian posterior q(beta) = N(m, Sigma) ----------------------------------
+// Device layout of c->lmvn for N rows, P columns (NP = N + 64: the coefficient vectors carry zero padding past N):
+//   [nodes 256 | m P | Sigma P^2 | V P^2 | b P | Tmp P^2 | mu N | s N | a1 a2 c11 c12 c22 ds em es (8 NP) | partials]
+struct LmvnBufs { double *g, *m, *S, *V, *b, *T, *mu, *s, *a1, *a2, *c11, *c12, *c22, *ds, *em, *es, *vpart; i64 nblk; };
+
+static int lmvn_check(lrvb_ctx* c, int64_t P_in, int32_t n_nodes) {
+    if (n_nodes < 1 || n_nodes > 128) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 128 quadrature nodes");
+    if (c->loss == LRVB_LOSS_NONE || c->data_only || !(c->have_X && c->have_y))
+        LRVB_FAIL(LRVB_ERR_STATE, "the context needs a design matrix and responses: lrvb_set_data for LRVB_SLOT_X and LRVB_SLOT_Y");
+    LRVB_TRY(check_len(P_in, c->P, "mean"));
+    if (c->P > 64)
+        LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "full-covariance logistic regression needs P <= 64 (got %lld): the Sigma-Sigma Hessian block is "
+                  "the packed-triangle Kronecker SYRK, whose on-chip stage holds 64 columns", (long long)c->P);
+    return LRVB_OK;
+}
+
+static int lmvn_reserve(lrvb_ctx* c, LmvnBufs& B) {
+    const i64 N = c->N, P = c->P, NP = ((N + 64 + 7) / 8) * 8;
+    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };            // every segment starts on a 64-byte boundary
+    B.nblk = (N + 255) / 256;
+    LRVB_TRY(buf_reserve(c, c->lmvn, (size_t)(256 + 3 * up(P) + 3 * up(P * P) + 2 * up(N) + 8 * NP + B.nblk)));
+    double* p = c->lmvn.p;
+    auto take = [&](i64 n) { double* q = p; p += up(n); return q; };
+    B.g = take(256); B.m = take(P); B.S = take(P * P); B.V = take(P * P); B.b = take(P); B.T = take(P * P);
+    B.mu = take(N); B.s = take(N);
+    B.a1 = take(NP); B.a2 = take(NP); B.c11 = take(NP); B.c12 = take(NP); B.c22 = take(NP);
+    B.ds = take(NP); B.em = take(NP); B.es = take(NP); B.vpart = p;
+    HIP_TRY(hipMemsetAsync(B.a1, 0, (size_t)(8 * NP) * sizeof(double), c->stream));
+    return LRVB_OK;
+}
+
+// the point (m, Sigma) and the nodes to the device, (mu, s) by the row pass, the five coefficient vectors and the value partials
+static int lmvn_point(lrvb_ctx* c, const LmvnBufs& B, const double* mean, const double* cov, const double* gh_x, const double* gh_w,
+                      int32_t n_nodes) {
+    const i64 N = c->N, P = c->P;
+    LRVB_TRY(h2d(c, B.m, mean, (size_t)P));
+    LRVB_TRY(h2d(c, B.S, cov, (size_t)(P * P)));
+    LRVB_TRY(h2d(c, B.g, gh_x, (size_t)n_nodes));
+    LRVB_TRY(h2d(c, B.g + 128, gh_w, (size_t)n_nodes));
+    LRVB_TRY(launch_lmvn_rowpass(c, B.S, B.m, B.s, B.mu));          // s_n = x_n^T Sigma x_n, mu_n = x_n . m
+    EW(lmvn_coef_kernel, N, (const double*)B.mu, (const double*)B.s, (const double*)c->y.p, (const double*)c->w.p, (const double*)B.g,
+       (const double*)(B.g + 128), (int)n_nodes, B.a1, B.a2, B.c11, B.c12, B.c22, B.vpart);
+    return LRVB_OK;
+}
+
+extern "C" int lrvb_logitnormal_mvn_terms(lrvb_ctx* c, const double* mean, const double* cov, int64_t P_in, const double* gh_x,
+                                          const double* gh_w, int32_t n_nodes, double* value_out, double* grad_out, double* H_out) {
+    LRVB_TRY(ctx_bind(c));
+    if (!mean || !cov || !gh_x || !gh_w || !value_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    LRVB_TRY(lmvn_check(c, P_in, n_nodes));
+    const i64 N = c->N, P = c->P, Pv = P * (P + 1) / 2, D = P + Pv;
+    LmvnBufs B;
+    LRVB_TRY(lmvn_reserve(c, B));
+    const bool want_g = grad_out != nullptr, want_H = H_out != nullptr;
+    // every sum over observations of this call in ONE buffer [H (D x D) | gradient (D) | value], reduced once (the suffix asked for)
+    LRVB_TRY(buf_reserve(c, c->Hfree, (size_t)(D * D + D + 1)));
+    double* Hb = c->Hfree.p;
+    double* gred = Hb + D * D;
+    double* vred = gred + D;
+    const int nbk = (int)((Pv + WS_TILE - 1) / WS_TILE);
+    if (want_H) LRVB_TRY(buf_reserve(c, c->Tdense, (size_t)nbk * (nbk + 1) / 2 * WS_TILE * WS_TILE));      // before any launch
+    LRVB_TRY(lmvn_point(c, B, mean, cov, gh_x, gh_w, n_nodes));
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, c->stream, (const double*)B.vpart, B.nblk, vred);
+    HIP_TRY(hipGetLastError());
+    if (want_g) {
+        LRVB_TRY(launch_gemv(c, true, N, P, 1.0, c->X.p, P, B.a1, 0.0, gred));                       // X^T w (psi_mu - y)
+        LRVB_TRY(weighted_tn(c, c->X.p, c->X.p, P, N, B.a2, B.T, c->mx_A));                          // X^T diag(w psi_s) X
+        EW(lmvn_vech_grad_kernel, Pv, (int)P, (const double*)B.T, gred + P);
+    }
+    if (want_H) {
+        HIP_TRY(hipMemsetAsync(Hb, 0, (size_t)(D * D) * sizeof(double), c->stream));
+        LRVB_TRY(weighted_tn(c, c->X.p, c->X.p, P, N, B.c11, B.T, c->mx_A));                         // H_mm
+        EW(lmvn_copy_block_kernel, P * P, P, (const double*)B.T, P, Hb, D);
+        // H_mSigma = X^T diag(c12) U with U generated on chip (lmvn_cross_kernel), both triangles
+        LRVB_TRY(launch_lmvn_cross(c, B.c12, Hb, D));
+        // H_SigmaSigma = sum_n c22_n u_n u_n^T (packed lower triangle u_n of x_n x_n^T) on the Kronecker SYRK, then the
+        // duplication weights of vech coordinates
+        LRVB_TRY(launch_wsyrk_kron(c, B.c22, c->Tdense.p));
+        LRVB_TRY(launch_tiles_to_dense(c, c->Tdense.p, Pv, Hb, D, P, P, false));
+        EW(lmvn_dup_scale_kernel, Pv * Pv, Pv, (int)P, Hb, D);
+        if (!want_g) HIP_TRY(hipMemsetAsync(gred, 0, (size_t)D * sizeof(double), c->stream));
+    }
+    double* first = want_H ? Hb : (want_g ? gred : vred);
+    LRVB_TRY(obs_reduce(c, first, (i64)(vred + 1 - first)));
+    LRVB_TRY(d2h(c, value_out, vred, 1));
+    if (want_g) LRVB_TRY(d2h(c, grad_out, gred, (size_t)D));
+    if (want_H) LRVB_TRY(d2h(c, H_out, Hb, (size_t)(D * D)));
+    return LRVB_OK;
+}
+
+extern "C" int lrvb_logitnormal_mvn_hvp(lrvb_ctx* c, const double* mean, const double* cov, int64_t P_in, const double* gh_x,
+                                        const double* gh_w, int32_t n_nodes, const double* v_in, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    if (!mean || !cov || !gh_x || !gh_w || !v_in || !out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    LRVB_TRY(lmvn_check(c, P_in, n_nodes));
+    const i64 N = c->N, P = c->P, Pv = P * (P + 1) / 2, D = P + Pv;
+    LmvnBufs B;
+    LRVB_TRY(lmvn_reserve(c, B));
+    // the direction's Sigma part as a symmetric matrix: ds_n = sum_v delta_v u_nv v_v = x_n^T V x_n
+    std::vector<double> Vh((size_t)(P * P));
+    for (i64 a = 0; a < P; ++a)
+        for (i64 b = 0; b <= a; ++b) Vh[(size_t)(a * P + b)] = Vh[(size_t)(b * P + a)] = v_in[P + a * (a + 1) / 2 + b];
+    LRVB_TRY(buf_reserve(c, c->vtmp3, (size_t)D));
+    LRVB_TRY(lmvn_point(c, B, mean, cov, gh_x, gh_w, n_nodes));
+    LRVB_TRY(h2d(c, B.V, Vh.data(), (size_t)(P * P)));
+    LRVB_TRY(h2d(c, B.b, v_in, (size_t)P));
+    LRVB_TRY(launch_lmvn_rowpass(c, B.V, B.b, B.ds, B.a1));        // ds; dmu -> a1 (a1 is not needed by the product)
+    EW(lmvn_hvp_coef_kernel, N, (const double*)B.c11, (const double*)B.c12, (const double*)B.c22, (const double*)B.a1,
+       (const double*)B.ds, B.em, B.es);
+    double* o = c->vtmp3.p;
+    LRVB_TRY(launch_gemv(c, true, N, P, 1.0, c->X.p, P, B.em, 0.0, o));                              // X^T e_m
+    LRVB_TRY(weighted_tn(c, c->X.p, c->X.p, P, N, B.es, B.T, c->mx_A));                              // X^T diag(e_s) X
+    EW(lmvn_vech_grad_kernel, Pv, (int)P, (const double*)B.T, o + P);
+    LRVB_TRY(obs_reduce(c, o, D));
+    return d2h(c, out, o, (size_t)D);
+}
+
+extern "C" int lrvb_logitnormal_mvn_chain(lrvb_ctx* c, int64_t P, const double* cov, const double* M, const double* H_in, double* H_out) {
+    LRVB_TRY(ctx_bind(c));
+    if (!cov || !M || !H_in || !H_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    if (P < 1 || P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "full-covariance logistic regression needs 1 <= P <= 64 (got %lld)", (long long)P);
+    const i64 Pv = P * (P + 1) / 2, D = P + Pv;
+    // [Sigma | M] (2 P^2), J (Pv^2), H_SigmaSigma J (Pv^2), H_in and H_out (D^2 each)
+    LRVB_TRY(buf_reserve(c, c->vtmp3, (size_t)(2 * P * P)));
+    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(2 * Pv * Pv)));
+    LRVB_TRY(buf_reserve(c, c->Hfree, (size_t)(D * D)));
+    LRVB_TRY(buf_reserve(c, c->Heta, (size_t)(D * D)));
+    double* Sg = c->vtmp3.p; double* Md = Sg + P * P;
+    double* J = c->work1.p; double* T1 = J + Pv * Pv;
+    double* Hi = c->Hfree.p; double* Ho = c->Heta.p;
+    LRVB_TRY(h2d(c, Sg, cov, (size_t)(P * P)));
+    LRVB_TRY(h2d(c, Md, M, (size_t)(P * P)));
+    LRVB_TRY(h2d(c, Hi, H_in, (size_t)(D * D)));
+    // J = d vech Sigma / d vech Lambda = -diag(1 / delta) symkron(Sigma, Sigma)
+    HIP_TRY(hipMemsetAsync(J, 0, (size_t)(Pv * Pv) * sizeof(double), c->stream));
+    HIP_TRY(hipMemsetAsync(Ho, 0, (size_t)(D * D) * sizeof(double), c->stream));
+    EW(hvec_symkron_kernel, Pv * Pv, Pv, (int)P, (const double*)Sg, (const double*)Sg, 1.0, J, Pv, (i64)0, (i64)0, 0);
+    EW(lmvn_jac_rows_kernel, Pv * Pv, Pv, J);
+    EW(lmvn_copy_block_kernel, P * P, P, (const double*)Hi, D, Ho, D);
+    LRVB_TRY(launch_gemm(c, false, false, P, Pv, Pv, 1.0, Hi + P, D, J, Pv, 0.0, Ho + P, D));              // H_m,Lambda = H_m,Sigma J
+    LRVB_TRY(launch_gemm(c, false, false, Pv, Pv, Pv, 1.0, Hi + P * D + P, D, J, Pv, 0.0, T1, Pv));       // H_Sigma,Sigma J
+    LRVB_TRY(launch_gemm(c, true, false, Pv, Pv, Pv, 1.0, J, Pv, T1, Pv, 0.0, Ho + P * D + P, D));        // J^T (...)
+    // second order of Lambda -> Lambda^-1 against the matrix gradient G (M = Sigma G Sigma), and +1/2 log det Lambda
+    EW(hvec_symkron_kernel, Pv * Pv, Pv, (int)P, (const double*)Md, (const double*)Sg, 2.0, Ho, D, P, P, 0);
+    EW(hvec_symkron_kernel, Pv * Pv, Pv, (int)P, (const double*)Sg, (const double*)Sg, -0.5, Ho, D, P, P, 0);
+    EW(lmvn_mirror_kernel, P * Pv, Pv, (int)P, Ho, D);
+    return d2h(c, H_out, Ho, (size_t)(D * D));
 }
 
 extern "C" int lrvb_dk_grad_vec(lrvb_ctx* c, const double* vec_in, int64_t V, int32_t order, const double* U,

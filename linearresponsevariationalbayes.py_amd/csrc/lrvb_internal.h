@@ -101,6 +101,7 @@ struct lrvb_ctx {
     std::vector<double> hvp_pt; bool hvp_pt_valid = false; bool hvp_pt_free = false;
     bool hvp_pt_prepared = false;   // the dense packing Jacobian / third-order matrix of general layouts are built too
     DevBuf dkw;                    // lrvb_dk_grad_vec: the caller's weight direction (N)
+    DevBuf lmvn;                   // lrvb_logitnormal_mvn_*: parameters, row pass, per-observation coefficients
     DevBuf opt;                    // trust-region Newton-CG: 12 D-vectors (+ the D x D preconditioner)
     DevBuf cgm[9];                 // blocked CG: B, X, R, P, Q, Z (Q x D), U, W (Q x V), R^T (P x Q)
     DevBuf cgT;                    // N x Q products X U^T of the blocked HVP
@@ -177,6 +178,10 @@ int  launch_atb_kron32(lrvb_ctx* c, const double* X31, const double* B, i64 N, c
 int  launch_wsyrk_kron(lrvb_ctx* c, const double* cvec_dev, double* tiles_out_dev /* nb = ceil(q (q + 1) / 2 / 128) tile rows */);
 int  launch_tiles_to_dense(lrvb_ctx* c, const double* tiles_dev, i64 P, double* dense_dev, i64 ld,
                            i64 row_off, i64 col_off, bool accumulate);
+
+// k_logitmvn.hip (P = n_cols <= 64)
+int  launch_lmvn_rowpass(lrvb_ctx* c, const double* A, const double* b, double* r, double* t);   // r_n = x_n^T A x_n, t_n = x_n . b
+int  launch_lmvn_cross(lrvb_ctx* c, const double* cvec, double* H, i64 ld);    // H[a, P + v] = H[P + v, a] = delta_v (X^T diag(c) U)[a, v]
 
 // k_lmm.hip
 struct LmmIdx { int p, ms, ls, iem, iim, iay, iby, iam, ibm; i64 ld; };    // vector-coordinate positions of the global parameters

@@ -448,14 +448,29 @@ void logitnormal_coef_kernel(i64 n, const double* __restrict__ mu, const double*
         const double m = mu[i], var = vv[i], sd = sqrt(var), wi = w[i];
         double v, dm, ds, dmm, dms, dss;
         gh_logistic_point(m, sd, sx, sw, K, v, dm, ds, dmm, dms, dss);
-        // chain sd = sqrt(var): sd' = 1 / (2 sd), sd'' = -1 / (4 sd^3)
-        const double s1 = 0.5 / sd, s2 = -0.25 / (sd * var);
         contrib = wi * (v - y[i] * m);
         a1[i] = wi * (dm - y[i]);
-        a2[i] = wi * ds * s1;
         c11[i] = wi * dmm;
-        c12[i] = wi * dms * s1;
-        c22[i] = wi * (dss * s1 * s1 + ds * s2);
+        if (sd > 0.0) {
+            // chain sd = sqrt(var): sd' = 1 / (2 sd), sd'' = -1 / (4 sd^3)
+            const double s1 = 0.5 / sd, s2 = -0.25 / (sd * var);
+            a2[i] = wi * ds * s1;
+            c12[i] = wi * dms * s1;
+            c22[i] = wi * (dss * s1 * s1 + ds * s2);
+        } else {
+            // var = 0 (an all-zero design row): the limits of the same quadrature sum as sd -> 0.  phi_sd is odd in sd, so
+            // phi_sd / (2 sd) -> M2 g''(m) / 2, phi_msd / (2 sd) -> M2 g'''(m) / 2 and d_var (phi_sd / (2 sd)) -> M4 g''''(m) / 12,
+            // M_j = sum_k p_k z_k^j the moments of the rule (M2 = 0 for one node, where phi does not depend on sd)
+            const double ispi = 0.5641895835477563;                   // z_k = sqrt(2) x_k, p_k = w_k / sqrt(pi)
+            double M2 = 0.0, M4 = 0.0;
+            for (int k = 0; k < K; ++k) { const double z2 = 2.0 * sx[k] * sx[k], p = sw[k] * ispi; M2 += p * z2; M4 += p * z2 * z2; }
+            const double e = exp(-fabs(m)), ie = 1.0 / (1.0 + e);
+            const double g2 = e * ie * ie, om = (1.0 - e) * ie;       // sigma (1 - sigma), |1 - 2 sigma|
+            const double g3 = m >= 0.0 ? -g2 * om : g2 * om;
+            a2[i] = wi * 0.5 * M2 * g2;
+            c12[i] = wi * 0.5 * M2 * g3;
+            c22[i] = wi * M4 * g2 * (1.0 - 6.0 * g2) / 12.0;
+        }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) contrib += __shfl_xor(contrib, off);

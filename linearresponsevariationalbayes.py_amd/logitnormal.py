@@ -160,9 +160,13 @@ class LogitNormalRegressionObjective(object):
         var = 1.0 / info
         x = self._x
         mu, v = x @ mean, (x * x) @ var
-        _, d1 = self.ctx.gh_logistic(mu, np.sqrt(v), self.gh_x, self.gh_w, order=1)
+        sd = np.sqrt(v)
+        _, d1, d2 = self.ctx.gh_logistic(mu, sd, self.gh_x, self.gh_w, order=2)
         y = self._y
-        G = np.hstack([(d1[:, 0] - y)[:, None] * x, (d1[:, 1] * 0.5 / np.sqrt(v))[:, None] * (x * x) * (-var * var)[None, :]])
+        # psi_var = phi_sd / (2 sd); at sd = 0 (an all-zero design row) its limit, phi_sdsd / 2 (phi_sd is odd in sd)
+        pos = sd > 0
+        psi_var = np.where(pos, 0.5 * d1[:, 1] / np.where(pos, sd, 1.0), 0.5 * d2[:, 2])
+        G = np.hstack([(d1[:, 0] - y)[:, None] * x, psi_var[:, None] * (x * x) * (-var * var)[None, :]])
         if val1_is_free:
             G = G @ self.ctx.free_to_vector_jac(val1)
         return np.ascontiguousarray(G.T)

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from lmvn_reference import kl_vec, kl_free, problem, psi
+from lmvn_reference import coefs_f64, coefs_mp, kl_free, kl_mean_field, kl_vec, problem, psi, std_nodes, terms_from_coefs
 
 
 def _import():
@@ -99,6 +99,44 @@ def test_free_coordinate_product_pieces_match_autograd(P):
         out = np.concatenate([hv[:P], lm.psd_free_vjp_hvp(free[P:], u[P:], hv[P:], g_vec[P:], P)])
         ref = H_ref @ u
         assert np.max(np.abs(out - ref)) <= 1e-10 * np.max(np.abs(ref))
+
+
+@pytest.mark.parametrize('P', [1, 3])
+def test_edge_references_agree_with_autograd(P):
+    """The per-row coefficients of tests/lmvn_reference.py (fp64, assembled with an explicit U) against autograd of the data
+    term, and against mpmath row by row, at a point with an all-zero row and a row with |mu| ~ 300."""
+    x, y, w, free, Lam = problem(40, P, seed=P)
+    y[3] = 0.3
+    m, S = free[:P], np.linalg.inv(Lam)
+    S = 0.5 * (S + S.T)
+    nodes, weights = std_nodes(20)
+    c = coefs_f64(x, y, w, m, S, nodes, weights)
+    _, g, H = terms_from_coefs(x, c)
+    g_ref, H_ref = _sig_derivs(x, y, w, m, S, 20)
+    assert np.max(np.abs(g - g_ref)) <= 1e-13 * np.max(np.abs(g_ref))
+    assert np.max(np.abs(H - H_ref)) <= 1e-13 * np.max(np.abs(H_ref))
+    mu, s = x @ m, np.einsum('ni,ij,nj->n', x, S, x)
+    for n in range(0, 40, 7):
+        cm = coefs_mp(mu[n], max(s[n], 0.0), y[n], w[n], nodes, weights)
+        for k, v in cm.items():
+            assert abs(c[k][n] - v) <= 1e-15 * w[n] * (1 + abs(mu[n])) + 1e-13 * abs(v)
+
+
+def test_mean_field_reference_matches_oracle():
+    """kl_mean_field (the mean-field model's KL for the GPU edge tests) against the numpy oracle of the model."""
+    from oracle import logitnormal as ol
+    from test_logitnormal_host_math import problem as mf_problem
+    x, y, w, eta = mf_problem(50, 4, seed=1)
+    gx, gw = np.polynomial.hermite.hermgauss(20)
+    o_val, o_g, o_H = ol.kl_terms(eta, x, y, w, 0.7, gx, gw)
+    args = (torch.tensor(x), torch.tensor(y), torch.tensor(w), 0.7, 20)
+    et = torch.tensor(eta, requires_grad=True)
+    val = kl_mean_field(et, *args)
+    g = torch.autograd.grad(val, et)[0].numpy()
+    H = torch.autograd.functional.hessian(lambda t: kl_mean_field(t, *args), torch.tensor(eta)).numpy()
+    assert abs(val.item() - o_val) <= 1e-13 * abs(o_val)
+    assert np.max(np.abs(g - o_g)) <= 1e-13 * np.max(np.abs(o_g))
+    assert np.max(np.abs(H - o_H)) <= 1e-13 * np.max(np.abs(o_H))
 
 
 def test_refusals_before_any_device_call():

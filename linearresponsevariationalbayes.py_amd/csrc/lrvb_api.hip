@@ -59,9 +59,15 @@ static void comm_release(lrvb_ctx* c);      // destroys the context's RCCL commu
 
 static int ctx_bind(lrvb_ctx* c) {
     if (!c) LRVB_FAIL(LRVB_ERR_INVALID, "null context");
-    c->hvp_pt_valid = false;
+    c->pt.invalidate();
     HIP_TRY(hipSetDevice(c->device));
     return LRVB_OK;
+}
+
+// What a setter leaves stale: the point state always, the resident Hessian when the objective itself changed.
+static void invalidate_caches(lrvb_ctx* c, bool objective_changed) {
+    c->pt.invalidate();
+    if (objective_changed) c->hres.invalidate();
 }
 
 static int pinned_reserve(lrvb_ctx* c, size_t n) {
@@ -225,7 +231,7 @@ extern "C" int lrvb_ctx_destroy(lrvb_ctx* c) {
     DevBuf* all[] = { &c->X, &c->y, &c->w, &c->quadA, &c->quadM, &c->quadB, &c->theta, &c->eta, &c->j1, &c->j2,
                       &c->vtmp, &c->vtmp2, &c->vtmp3, &c->g_eta, &c->g_free, &c->lp, &c->cw, &c->zbuf,
                       &c->part_vec, &c->part_val, &c->stats, &c->tile_part, &c->Heta, &c->Hfree, &c->Jdense,
-                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->Hres, &c->hres_theta, &c->qstats, &c->lmvn };
+                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn };
     for (DevBuf* b : all) buf_free(*b);
     if (c->host_pinned) (void)hipHostFree(c->host_pinned);
     if (c->up_ring) { for (int k = 0; k < lrvb_ctx::UP_SLOTS; ++k) if (c->up_ev[k]) (void)hipEventDestroy(c->up_ev[k]); (void)hipHostFree(c->up_ring); }
@@ -319,7 +325,7 @@ extern "C" int lrvb_set_data(lrvb_ctx* c, int slot, const double* host, int64_t 
     LRVB_TRY(h2d(c, b->p, host, n));
     if (slot == LRVB_SLOT_X) { c->have_X = true; c->x2_ready = false; c->gstats_valid = false; c->zs_valid = false; }
     if (slot == LRVB_SLOT_Y) c->have_y = true;
-    c->hres_valid = false;
+    invalidate_caches(c, true);
     return LRVB_OK;
 }
 
@@ -332,7 +338,7 @@ extern "C" int lrvb_set_data_dev(lrvb_ctx* c, int slot, const double* data_dev, 
     b->p = const_cast<double*>(data_dev); b->n = n; b->owned = false; ++c->buf_epoch;
     if (slot == LRVB_SLOT_X) { c->have_X = true; c->x2_ready = false; c->gstats_valid = false; c->zs_valid = false; }
     if (slot == LRVB_SLOT_Y) c->have_y = true;
-    c->hres_valid = false;
+    invalidate_caches(c, true);
     return LRVB_OK;
 }
 
@@ -341,7 +347,7 @@ extern "C" int lrvb_set_weights(lrvb_ctx* c, const double* w, int64_t n) {
     if (c->loss == LRVB_LOSS_NONE) LRVB_FAIL(LRVB_ERR_STATE, "model has no data term");
     if (!w || n != c->N) LRVB_FAIL(LRVB_ERR_SIZE, "weights must have %lld entries (got %lld)", (long long)c->N, (long long)n);
     if (!c->w.owned) { c->w.p = nullptr; c->w.n = 0; c->w.owned = true; }
-    c->gstats_valid = false; c->ws_valid = false; c->hres_valid = false;
+    c->gstats_valid = false; c->ws_valid = false; invalidate_caches(c, true);
     LRVB_TRY(buf_reserve(c, c->w, (size_t)n));
     return h2d(c, c->w.p, w, (size_t)n);
 }
@@ -352,25 +358,24 @@ extern "C" int lrvb_set_weights_dev(lrvb_ctx* c, const double* w_dev, int64_t n)
     if (!w_dev || n != c->N) LRVB_FAIL(LRVB_ERR_SIZE, "weights must have %lld entries (got %lld)", (long long)c->N, (long long)n);
     if (c->w.p && c->w.owned) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->w.p)); }
     c->w.p = const_cast<double*>(w_dev); c->w.n = (size_t)n; c->w.owned = false; ++c->buf_epoch;
-    c->gstats_valid = false; c->ws_valid = false; c->hres_valid = false;
+    c->gstats_valid = false; c->ws_valid = false; invalidate_caches(c, true);
     return LRVB_OK;
 }
 
 extern "C" int lrvb_set_quad_scale(lrvb_ctx* c, double scale) {
-    if (c) c->hvp_pt_valid = false;
     if (!c) LRVB_FAIL(LRVB_ERR_INVALID, "null context");
-    if (scale != c->quad_scale) c->hres_valid = false;
+    invalidate_caches(c, scale != c->quad_scale);
     c->quad_scale = scale;
     return LRVB_OK;
 }
 
 extern "C" int lrvb_set_lik_info(lrvb_ctx* c, double lik_info) {
     if (!c) LRVB_FAIL(LRVB_ERR_INVALID, "null context");
-    c->hvp_pt_valid = false;
+    invalidate_caches(c, false);
     if (c->loss != LRVB_LOSS_GAUSSIAN) LRVB_FAIL(LRVB_ERR_STATE, "lik_info is the precision of the Gaussian loss");
     if (!(lik_info > 0.0) || !std::isfinite(lik_info)) LRVB_FAIL(LRVB_ERR_INVALID, "lik_info must be positive and finite");
     c->lik_info = lik_info;
-    c->hres_valid = false;
+    invalidate_caches(c, true);
     return LRVB_OK;
 }
 
@@ -378,7 +383,7 @@ extern "C" int lrvb_set_tuning(lrvb_ctx* c, int n_splits, int reserved) {
     if (!c) LRVB_FAIL(LRVB_ERR_INVALID, "null context");
     if (n_splits < 0 || n_splits > 1024) LRVB_FAIL(LRVB_ERR_INVALID, "n_splits out of range");
     if (reserved & ~15) LRVB_FAIL(LRVB_ERR_INVALID, "reserved = %d: only bits 0-3 are defined (include/lrvb_hip.h)", reserved);
-    c->hvp_pt_valid = false;
+    invalidate_caches(c, false);
     c->no_resident = (reserved & 8) != 0;      // (the resident matrix itself stays: it is the Hessian whichever kernels would form it)
     c->n_splits_user = n_splits;
     c->force_generic_wsyrk = (reserved & 1) != 0;
@@ -395,6 +400,15 @@ static int data_ready(lrvb_ctx* c) {
     return LRVB_OK;
 }
 
+static int check_len(i64 got, i64 want, const char* what) {
+    if (got != want) LRVB_FAIL(LRVB_ERR_SIZE, "Wrong size for %s.  Expected %lld, got %lld", what, (long long)want, (long long)got);
+    return LRVB_OK;
+}
+// a point has D entries in free coordinates, V in vector coordinates
+static int check_point_len(const lrvb_ctx* c, i64 got, bool is_free) {
+    return check_len(got, is_free ? c->D : c->V, is_free ? "free vector" : "vector");
+}
+
 // ---- small elementwise kernels used only by the orchestration -------------------------
 static inline unsigned nb256(i64 n) { return (unsigned)((n + 255) / 256); }
 #define EW(kernel, n, ...) do { if ((n) > 0) { hipLaunchKernelGGL(kernel, dim3(nb256(n)), dim3(256), 0, c->stream, n, __VA_ARGS__); HIP_TRY(hipGetLastError()); } } while (0)
@@ -409,6 +423,11 @@ static int set_point(lrvb_ctx* c, const double* point_dev, bool is_free) {
     }
     return LRVB_OK;
 }
+// a host point into c->theta (which doubles as the vector-coordinate input), then set_point
+static int load_point(lrvb_ctx* c, const double* point, bool is_free) {
+    LRVB_TRY(h2d(c, c->theta.p, point, (size_t)(is_free ? c->D : c->V)));
+    return set_point(c, c->theta.p, is_free);
+}
 
 // Sum of a device buffer of observation sums over the ranks of the job (no-op in a single process).
 static int obs_reduce(lrvb_ctx* c, double* buf_dev, i64 n) {
@@ -421,7 +440,7 @@ static int obs_reduce(lrvb_ctx* c, double* buf_dev, i64 n) {
 }
 extern "C" int lrvb_set_reduce_hook(lrvb_ctx* c, lrvb_reduce_fn fn, void* user) {
     if (!c) LRVB_FAIL(LRVB_ERR_INVALID, "null context");
-    c->hvp_pt_valid = false; c->hres_valid = false;
+    invalidate_caches(c, true);
     c->reduce_fn = fn; c->reduce_user = fn ? user : nullptr;
     return LRVB_OK;
 }
@@ -485,7 +504,7 @@ extern "C" int lrvb_comm_init(lrvb_ctx* c, int world_size, int rank, const lrvb_
     RCCL_TRY(g_rccl.CommInitRank(&c->comm, world_size, *id, rank));
     c->comm_world = world_size; c->comm_rank = rank;
     c->reduce_fn = native_reduce; c->reduce_user = c;              // every observation sum now goes through RCCL
-    c->hres_valid = false;
+    invalidate_caches(c, true);
     return LRVB_OK;
 }
 extern "C" int lrvb_comm_destroy(lrvb_ctx* c) {
@@ -496,7 +515,7 @@ extern "C" int lrvb_comm_destroy(lrvb_ctx* c) {
     if (c->reduce_fn == native_reduce) { c->reduce_fn = nullptr; c->reduce_user = nullptr; }
     RCCL_TRY(g_rccl.CommDestroy(c->comm));
     c->comm = nullptr; c->comm_world = 1; c->comm_rank = 0;
-    c->hvp_pt_valid = false; c->hres_valid = false;
+    invalidate_caches(c, true);
     return LRVB_OK;
 }
 extern "C" int lrvb_allreduce_hessian(lrvb_ctx* c, double* stats_dev, int64_t n) {
@@ -535,21 +554,8 @@ static int grad_to_free(lrvb_ctx* c, const double* theta_dev, double* g_free_dev
     return launch_gemv(c, true, c->V, c->D, 1.0, c->Jdense.p, c->D, c->g_eta.p, 0.0, g_free_dev);
 }
 
-// out_eta (V) = H_eta u   using the cached per-observation curvature cw
-static int heta_apply(lrvb_ctx* c, const double* u_vec, double* out_vec) {
-    if (c->loss != LRVB_LOSS_NONE) {
-        LRVB_TRY(buf_reserve(c, c->vtmp3, (size_t)(c->V > c->P ? c->V : c->P)));
-        LRVB_TRY(launch_glm_pass(c, PASS_HVP_C, nullptr, u_vec + c->glm_off, c->vtmp3.p, nullptr, false));
-        LRVB_TRY(obs_reduce(c, c->vtmp3.p, c->P));
-        // vtmp3 holds the P-vector; scatter into out_vec
-        LRVB_TRY(launch_scatter_glm(c, c->vtmp3.p, out_vec));
-    } else {
-        LRVB_TRY(launch_scatter_glm(c, nullptr, out_vec));
-    }
-    return launch_quad_hvp(c, u_vec, out_vec);
-}
-
-// the same pass with whatever per-observation coefficient sits in c->cw, quadratic term optional
+// out_eta (V) = X^T (cw o (X u)) scattered into the vector layout (+ the quadratic term's A u): H_eta u when c->cw holds the
+// cached per-observation curvature, another derivative when it holds another coefficient
 static int heta_apply_coef(lrvb_ctx* c, const double* u_vec, double* out_vec, bool with_quad) {
     if (c->loss != LRVB_LOSS_NONE) {
         LRVB_TRY(buf_reserve(c, c->vtmp3, (size_t)(c->V > c->P ? c->V : c->P)));
@@ -564,16 +570,16 @@ static int heta_apply_coef(lrvb_ctx* c, const double* u_vec, double* out_vec, bo
 
 // full HVP at the current point.  Requires set_point + eval_grad_eta done (g_eta, cw valid).
 static int hvp_apply(lrvb_ctx* c, const double* theta_dev, bool is_free, const double* v_dev, double* out_dev) {
-    if (!is_free) return heta_apply(c, v_dev, out_dev);
+    if (!is_free) return heta_apply_coef(c, v_dev, out_dev, true);
     if (c->all_box) {
         EW(mul_kernel, c->D, c->j1.p, v_dev, c->vtmp.p);                   // u = J v
-        LRVB_TRY(heta_apply(c, c->vtmp.p, c->vtmp2.p));                   // H_eta u
+        LRVB_TRY(heta_apply_coef(c, c->vtmp.p, c->vtmp2.p, true));                   // H_eta u
         EW(fma3_kernel, c->D, c->g_eta.p, c->j2.p, v_dev, c->j1.p, c->vtmp2.p, out_dev);
         return LRVB_OK;
     }
     // general layouts: dense J and dense third-order matrix (built by the caller once per point)
     LRVB_TRY(launch_gemv(c, false, c->V, c->D, 1.0, c->Jdense.p, c->D, v_dev, 0.0, c->vtmp.p));
-    LRVB_TRY(heta_apply(c, c->vtmp.p, c->vtmp2.p));
+    LRVB_TRY(heta_apply_coef(c, c->vtmp.p, c->vtmp2.p, true));
     LRVB_TRY(launch_gemv(c, true, c->V, c->D, 1.0, c->Jdense.p, c->D, c->vtmp2.p, 0.0, out_dev));
     LRVB_TRY(launch_gemv(c, false, c->D, c->D, 1.0, c->Tdense.p, c->D, v_dev, 1.0, out_dev));
     return LRVB_OK;
@@ -588,39 +594,44 @@ static int prepare_general_hvp(lrvb_ctx* c, const double* theta_dev) {
 }
 
 // ---- the resident Hessian ------------------------------------------------------------------------------------------
+// c->hres.H holds the Hessian at a point given on the host (theta_host) or, failing that, on the device (theta_dev)
+static int hres_set_point(lrvb_ctx* c, const double* theta_dev, const double* theta_host) {
+    const i64 D = c->D;
+    if (theta_host) { c->hres.pt.assign(theta_host, theta_host + D); c->hres.pt_host = true; }
+    else {
+        LRVB_TRY(buf_reserve(c, c->hres.theta_dev, (size_t)D));
+        HIP_TRY(hipMemcpyAsync(c->hres.theta_dev.p, theta_dev, (size_t)D * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        c->hres.pt_host = false;
+    }
+    c->hres.valid = true;
+    return LRVB_OK;
+}
 static int hres_capture(lrvb_ctx* c, const double* H_dev, i64 ld, const double* theta_dev, const double* theta_host) {
     const i64 D = c->D;
-    c->hres_valid = false;
-    LRVB_TRY(buf_reserve(c, c->Hres, (size_t)D * (size_t)D));
-    HIP_TRY(hipMemcpy2DAsync(c->Hres.p, (size_t)D * 8, H_dev, (size_t)ld * 8, (size_t)D * 8, (size_t)D, hipMemcpyDeviceToDevice, c->stream));
-    if (theta_host) { c->hres_pt.assign(theta_host, theta_host + D); c->hres_pt_host = true; }
-    else {
-        LRVB_TRY(buf_reserve(c, c->hres_theta, (size_t)D));
-        HIP_TRY(hipMemcpyAsync(c->hres_theta.p, theta_dev, (size_t)D * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        c->hres_pt_host = false;
-    }
-    c->hres_valid = true;
-    return LRVB_OK;
+    c->hres.invalidate();
+    LRVB_TRY(buf_reserve(c, c->hres.H, (size_t)D * (size_t)D));
+    HIP_TRY(hipMemcpy2DAsync(c->hres.H.p, (size_t)D * 8, H_dev, (size_t)ld * 8, (size_t)D * 8, (size_t)D, hipMemcpyDeviceToDevice, c->stream));
+    return hres_set_point(c, theta_dev, theta_host);
 }
 // Is `free_in` (host) the point of the resident Hessian?  A build through a `_dev` entry point left its point on the device
 // only: the first question costs one small comparison kernel and a flag read-back, after which the host copy answers.
 static int hres_matches(lrvb_ctx* c, const double* free_in, i64 D, bool* match) {
     *match = false;
-    if (!c->hres_valid || c->no_resident || !free_in || D != c->D) return LRVB_OK;
-    if (!c->hres_pt_host) {
+    if (!c->hres.valid || c->no_resident || !free_in || D != c->D) return LRVB_OK;
+    if (!c->hres.pt_host) {
         LRVB_TRY(h2d(c, c->theta.p, free_in, (size_t)D));
         int* flag = reinterpret_cast<int*>(c->scal.p);
         HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int), c->stream));
-        EW(vec_differs_kernel, D, (const double*)c->theta.p, (const double*)c->hres_theta.p, flag);
+        EW(vec_differs_kernel, D, (const double*)c->theta.p, (const double*)c->hres.theta_dev.p, flag);
         int differs = 0;
         HIP_TRY(hipMemcpyAsync(&differs, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (differs) return LRVB_OK;                  // (the resident matrix stays: its own point may come back)
-        c->hres_pt.assign(free_in, free_in + D); c->hres_pt_host = true;
+        c->hres.pt.assign(free_in, free_in + D); c->hres.pt_host = true;
         *match = true;
         return LRVB_OK;
     }
-    *match = (i64)c->hres_pt.size() == D && memcmp(c->hres_pt.data(), free_in, (size_t)D * sizeof(double)) == 0;
+    *match = (i64)c->hres.pt.size() == D && memcmp(c->hres.pt.data(), free_in, (size_t)D * sizeof(double)) == 0;
     return LRVB_OK;
 }
 
@@ -678,45 +689,35 @@ static int hessian_finish(lrvb_ctx* c, const double* point_dev, bool is_free, co
     const double* tiles = (c->loss != LRVB_LOSS_NONE) ? stats_dev + 1 + c->P : nullptr;
     LRVB_TRY(launch_scatter_glm(c, (c->loss != LRVB_LOSS_NONE) ? stats_dev + 1 : nullptr, c->g_eta.p));
     LRVB_TRY(launch_quad_grad_value(c, c->eta.p, c->g_eta.p, nullptr));
-    if (!is_free) {
-        if (ld == c->V) return launch_build_Heta(c, tiles, H_dev);
-        LRVB_TRY(buf_reserve(c, c->Heta, (size_t)c->V * (size_t)c->V));
-        LRVB_TRY(launch_build_Heta(c, tiles, c->Heta.p));
-        HIP_TRY(hipMemcpy2DAsync(H_dev, (size_t)ld * 8, c->Heta.p, (size_t)c->V * 8, (size_t)c->V * 8, (size_t)c->V, hipMemcpyDeviceToDevice, c->stream));
-        return LRVB_OK;
-    }
-    if (c->all_box)
+    if (is_free && c->all_box)
         return launch_finish_box(c, tiles, c->g_eta.p, c->j1.p, c->j2.p, true, H_dev, ld);
-    // general: H = J^T H_eta J + T
-    LRVB_TRY(buf_reserve(c, c->Heta, (size_t)c->V * (size_t)c->V));
-    LRVB_TRY(buf_reserve(c, c->work1, (size_t)c->V * (size_t)c->D));
-    LRVB_TRY(launch_build_Heta(c, tiles, c->Heta.p));
-    if (c->jt_rows > 0) {
-        // box and log-Cholesky blocks: two structured products instead of the dense Jacobian and two V^2 D products
-        LRVB_TRY(launch_jt_apply(c, point_dev, c->Heta.p, c->V, c->V, c->work1.p, c->V, false));      // W = J^T H_eta (D x V)
-        if (ld == c->D) {
-            LRVB_TRY(launch_jt_apply(c, point_dev, c->work1.p, c->V, c->D, H_dev, ld, true));         // J^T W^T
-            return launch_third_order(c, point_dev, c->g_eta.p, H_dev);
+    // the other forms write a dense n x n matrix: straight into H_dev, or into scratch that is copied out when ld > n
+    DevBuf& scratch = is_free ? c->Tdense : c->Heta;
+    double* H = H_dev;
+    if (ld != n) { LRVB_TRY(buf_reserve(c, scratch, (size_t)n * (size_t)n)); H = scratch.p; }
+    if (!is_free) {
+        LRVB_TRY(launch_build_Heta(c, tiles, H));
+    } else {
+        // general: H = J^T H_eta J + T
+        LRVB_TRY(buf_reserve(c, c->Heta, (size_t)c->V * (size_t)c->V));
+        LRVB_TRY(buf_reserve(c, c->work1, (size_t)c->V * (size_t)c->D));
+        LRVB_TRY(launch_build_Heta(c, tiles, c->Heta.p));
+        if (c->jt_rows > 0) {
+            // box and log-Cholesky blocks: two structured products instead of the dense Jacobian and two V^2 D products
+            LRVB_TRY(launch_jt_apply(c, point_dev, c->Heta.p, c->V, c->V, c->work1.p, c->V, false));  // W = J^T H_eta (D x V)
+            LRVB_TRY(launch_jt_apply(c, point_dev, c->work1.p, c->V, c->D, H, n, true));               // J^T W^T
+            LRVB_TRY(launch_third_order(c, point_dev, c->g_eta.p, H));
+        } else {
+            LRVB_TRY(ensure_dense_J(c, point_dev));
+            LRVB_TRY(launch_gemm(c, false, false, c->V, c->D, c->V, 1.0, c->Heta.p, c->V, c->Jdense.p, c->D, 0.0, c->work1.p, c->D));
+            // T into H, then H += J^T work1
+            HIP_TRY(hipMemsetAsync(H, 0, (size_t)n * (size_t)n * sizeof(double), c->stream));
+            LRVB_TRY(launch_third_order(c, point_dev, c->g_eta.p, H));
+            LRVB_TRY(launch_gemm(c, true, false, c->D, c->D, c->V, 1.0, c->Jdense.p, c->D, c->work1.p, c->D, 1.0, H, n));
         }
-        LRVB_TRY(buf_reserve(c, c->Tdense, (size_t)c->D * (size_t)c->D));
-        LRVB_TRY(launch_jt_apply(c, point_dev, c->work1.p, c->V, c->D, c->Tdense.p, c->D, true));
-        LRVB_TRY(launch_third_order(c, point_dev, c->g_eta.p, c->Tdense.p));
-        HIP_TRY(hipMemcpy2DAsync(H_dev, (size_t)ld * 8, c->Tdense.p, (size_t)c->D * 8, (size_t)c->D * 8, (size_t)c->D, hipMemcpyDeviceToDevice, c->stream));
-        return LRVB_OK;
     }
-    LRVB_TRY(ensure_dense_J(c, point_dev));
-    LRVB_TRY(launch_gemm(c, false, false, c->V, c->D, c->V, 1.0, c->Heta.p, c->V, c->Jdense.p, c->D, 0.0, c->work1.p, c->D));
-    // T into H_dev (respecting ld), then H += J^T work1
-    if (ld == c->D) {
-        HIP_TRY(hipMemsetAsync(H_dev, 0, (size_t)c->D * (size_t)c->D * sizeof(double), c->stream));
-        LRVB_TRY(launch_third_order(c, point_dev, c->g_eta.p, H_dev));
-        return launch_gemm(c, true, false, c->D, c->D, c->V, 1.0, c->Jdense.p, c->D, c->work1.p, c->D, 1.0, H_dev, ld);
-    }
-    LRVB_TRY(buf_reserve(c, c->Tdense, (size_t)c->D * (size_t)c->D));
-    HIP_TRY(hipMemsetAsync(c->Tdense.p, 0, (size_t)c->D * (size_t)c->D * sizeof(double), c->stream));
-    LRVB_TRY(launch_third_order(c, point_dev, c->g_eta.p, c->Tdense.p));
-    LRVB_TRY(launch_gemm(c, true, false, c->D, c->D, c->V, 1.0, c->Jdense.p, c->D, c->work1.p, c->D, 1.0, c->Tdense.p, c->D));
-    HIP_TRY(hipMemcpy2DAsync(H_dev, (size_t)ld * 8, c->Tdense.p, (size_t)c->D * 8, (size_t)c->D * 8, (size_t)c->D, hipMemcpyDeviceToDevice, c->stream));
+    if (H != H_dev)
+        HIP_TRY(hipMemcpy2DAsync(H_dev, (size_t)ld * 8, H, (size_t)n * 8, (size_t)n * 8, (size_t)n, hipMemcpyDeviceToDevice, c->stream));
     return LRVB_OK;
 }
 
@@ -726,6 +727,13 @@ static int stats_reduce(lrvb_ctx* c) {
     int64_t n = 0;
     LRVB_TRY(lrvb_stats_size(c, &n));
     return obs_reduce(c, c->stats.p, n);
+}
+
+// partial statistics, one sum over ranks, finish: the Hessian at point_dev into H (leading dimension ld)
+static int build_hessian(lrvb_ctx* c, const double* point_dev, bool is_free, double* H, i64 ld) {
+    LRVB_TRY(hessian_partial(c, point_dev, is_free, c->stats.p));
+    LRVB_TRY(stats_reduce(c));
+    return hessian_finish(c, point_dev, is_free, c->stats.p, H, ld);
 }
 
 extern "C" int lrvb_hessian_partial_dev(lrvb_ctx* c, const double* free_dev, double* stats_dev) {
@@ -743,16 +751,9 @@ extern "C" int lrvb_hessian_dev(lrvb_ctx* c, const double* free_dev, double* H_d
     LRVB_TRY(ctx_bind(c));
     if (!free_dev || !H_dev) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
     if (c->prof_on) LRVB_TRY(prof_mark(c, PROF_BUILD));
-    LRVB_TRY(hessian_partial(c, free_dev, true, c->stats.p));
-    LRVB_TRY(stats_reduce(c));
-    LRVB_TRY(hessian_finish(c, free_dev, true, c->stats.p, H_dev, ld));
+    LRVB_TRY(build_hessian(c, free_dev, true, H_dev, ld));
     LRVB_TRY(hres_capture(c, H_dev, ld, free_dev, nullptr));
     if (c->prof_on) LRVB_TRY(prof_mark(c, PROF_BUILD));
-    return LRVB_OK;
-}
-
-static int check_len(i64 got, i64 want, const char* what) {
-    if (got != want) LRVB_FAIL(LRVB_ERR_SIZE, "Wrong size for %s.  Expected %lld, got %lld", what, (long long)want, (long long)got);
     return LRVB_OK;
 }
 
@@ -760,13 +761,11 @@ static int hessian_host(lrvb_ctx* c, const double* point, i64 n_in, bool is_free
     LRVB_TRY(ctx_bind(c));
     if (!point || !H_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
     const i64 n = is_free ? c->D : c->V;
-    LRVB_TRY(check_len(n_in, n, is_free ? "free vector" : "vector"));
+    LRVB_TRY(check_point_len(c, n_in, is_free));
     if (ld < n) LRVB_FAIL(LRVB_ERR_SIZE, "leading dimension too small");
     LRVB_TRY(h2d(c, c->theta.p, point, (size_t)n));           // theta buffer doubles as the vector-mode input
     LRVB_TRY(buf_reserve(c, c->Hfree, (size_t)n * (size_t)n));
-    LRVB_TRY(hessian_partial(c, c->theta.p, is_free, c->stats.p));
-    LRVB_TRY(stats_reduce(c));
-    LRVB_TRY(hessian_finish(c, c->theta.p, is_free, c->stats.p, c->Hfree.p, n));
+    LRVB_TRY(build_hessian(c, c->theta.p, is_free, c->Hfree.p, n));
     if (is_free) LRVB_TRY(hres_capture(c, c->Hfree.p, n, c->theta.p, point));
     HIP_TRY(hipMemcpy2DAsync(H_out, (size_t)ld * 8, c->Hfree.p, (size_t)n * 8, (size_t)n * 8, (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -779,39 +778,57 @@ extern "C" int lrvb_hessian_vec(lrvb_ctx* c, const double* vec_in, int64_t V, do
     return hessian_host(c, vec_in, V, false, H_out, ld);
 }
 
-// ---- value / gradient ------------------------------------------------------------------
-// Is (point, is_free) the point whose state the last value / gradient / HVP call left in place?  Must be asked
-// BEFORE ctx_bind, which clears the flag for every entry point.
-static bool same_point(const lrvb_ctx* c, const double* point, i64 n_in, bool is_free) {
-    return c && point && c->hvp_pt_valid && c->hvp_pt_free == is_free && (i64)c->hvp_pt.size() == n_in &&
-           memcmp(c->hvp_pt.data(), point, (size_t)n_in * sizeof(double)) == 0;
+// ---- the point state ----------------------------------------------------------------------------------------------
+// An entry point evaluating at the host point x, against the point state (eta, J, d f / d eta, curvature) in c->pt.
+struct AtPoint {
+    const double* x; i64 n; bool is_free;
+    bool current;          // the point state is that of x
+    bool prepared;         // ... with the general-layout HVP operands (prepare_general_hvp)
+};
+// Binds the context, checks the point's length and the data, and notes whether the state the last value / gradient / product
+// call left is that of x (and no other entry point ran since).  That question comes first: ctx_bind invalidates the state.
+static int bind_point(lrvb_ctx* c, const double* x, i64 n, bool is_free, AtPoint* at) {
+    const bool same = c && x && c->pt.is(x, n, is_free);
+    *at = AtPoint{ x, n, is_free, same, same && c->pt.prepared };
+    LRVB_TRY(ctx_bind(c));
+    LRVB_TRY(check_point_len(c, n, is_free));
+    return data_ready(c);
 }
-static void remember_point(lrvb_ctx* c, const double* point, i64 n, bool is_free, bool prepared) {
-    c->hvp_pt.assign(point, point + n);
-    c->hvp_pt_free = is_free;
-    c->hvp_pt_prepared = prepared;
-    c->hvp_pt_valid = true;
+// Makes the point state that of at.x: a new point is uploaded, evaluated (d f / d eta with the quadratic term, curvature)
+// and starts a new count of matrix-free products; `prepare` adds the dense Jacobian and third-order matrix of general layouts.
+static int enter_point(lrvb_ctx* c, AtPoint& at, bool prepare) {
+    if (!at.current) {
+        LRVB_TRY(load_point(c, at.x, at.is_free));
+        LRVB_TRY(eval_grad_eta(c, c->stats.p, true));
+        c->pt.products = 0;
+        at.current = true;
+    }
+    if (prepare && !at.prepared) {
+        if (at.is_free) LRVB_TRY(prepare_general_hvp(c, c->theta.p));
+        at.prepared = true;
+    }
+    return LRVB_OK;
+}
+// the epilogue of a call that leaves the state of at.x in place for the next one
+static void remember_point(lrvb_ctx* c, const AtPoint& at) {
+    c->pt.x.assign(at.x, at.x + at.n);
+    c->pt.is_free = at.is_free;
+    c->pt.prepared = at.prepared;
+    c->pt.valid = true;
 }
 
+// ---- value / gradient ------------------------------------------------------------------
 static int grad_host(lrvb_ctx* c, const double* point, i64 n_in, bool is_free, double* value_out, double* g_out) {
-    const bool reuse = same_point(c, point, n_in, is_free);          // fun(x) then jac(x), as scipy calls them
-    const bool prepared = reuse && c->hvp_pt_prepared;
-    LRVB_TRY(ctx_bind(c));
+    AtPoint at;                                                      // fun(x) then jac(x), as scipy calls them
+    LRVB_TRY(bind_point(c, point, n_in, is_free, &at));
     if (!point) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
-    const i64 n = is_free ? c->D : c->V;
-    LRVB_TRY(check_len(n_in, n, is_free ? "free vector" : "vector"));
-    LRVB_TRY(data_ready(c));
-    if (!reuse) {
-        LRVB_TRY(h2d(c, c->theta.p, point, (size_t)n));
-        LRVB_TRY(set_point(c, c->theta.p, is_free));
-        LRVB_TRY(eval_grad_eta(c, c->stats.p, true));
-    }
+    LRVB_TRY(enter_point(c, at, false));
     if (g_out) {
-        if (is_free) { LRVB_TRY(grad_to_free(c, c->theta.p, c->g_free.p)); LRVB_TRY(d2h(c, g_out, c->g_free.p, (size_t)n)); }
-        else LRVB_TRY(d2h(c, g_out, c->g_eta.p, (size_t)n));
+        if (is_free) { LRVB_TRY(grad_to_free(c, c->theta.p, c->g_free.p)); LRVB_TRY(d2h(c, g_out, c->g_free.p, (size_t)n_in)); }
+        else LRVB_TRY(d2h(c, g_out, c->g_eta.p, (size_t)n_in));
     }
     if (value_out) LRVB_TRY(d2h(c, value_out, c->stats.p, 1));
-    remember_point(c, point, n, is_free, prepared);       // (grad_to_free rebuilds the same dense Jacobian)
+    remember_point(c, at);                                 // (grad_to_free rebuilds the same dense Jacobian)
     return LRVB_OK;
 }
 extern "C" int lrvb_value(lrvb_ctx* c, const double* free_in, int64_t D, double* out) {
@@ -846,65 +863,50 @@ extern "C" int lrvb_hvp_dev(lrvb_ctx* c, const double* free_dev, const double* v
 }
 // Many products at ONE point (scipy's trust-ncg or cg driving lrvb_hvp, right-hand sides solved one by one): a pass over X per
 // product is the cheaper route for a handful; a build of the point's Hessian costs about D / 86 passes and makes every further
-// product a D x D matrix-vector product.  Past max(8, D / 64) matrix-free products at the remembered point the Hessian is
-// built into the resident slot (as lrvb_hessian would leave it) and *resident set.  The point state must be current
-// (c->theta on the device, set_point + eval_grad_eta done); every rank counts the same products, so a sharded run builds
-// on all ranks at the same product.
-static int maybe_build_resident(lrvb_ctx* c, const double* point_host, i64 D, bool* resident) {
-    if (*resident || c->no_resident || c->loss == LRVB_LOSS_NONE || D < 256 || D > 8192) return LRVB_OK;
-    const i64 thr = D / 64 > 8 ? D / 64 : 8;
-    if (c->pt_products <= thr) return LRVB_OK;
-    c->hres_valid = false;
-    LRVB_TRY(buf_reserve(c, c->Hres, (size_t)D * (size_t)D));
-    LRVB_TRY(hessian_partial(c, c->theta.p, true, c->stats.p));
-    LRVB_TRY(stats_reduce(c));
-    LRVB_TRY(hessian_finish(c, c->theta.p, true, c->stats.p, c->Hres.p, D));
-    c->hres_pt.assign(point_host, point_host + D); c->hres_pt_host = true;
-    c->hres_valid = true;
+// product a D x D matrix-vector product.  A build may happen where the model has a data term, the resident route is not
+// switched off (tuning bit 3) and D lies in [256, 8192] (below, a pass and a build are both a handful of launches) ...
+static bool resident_build_allowed(const lrvb_ctx* c, i64 D) {
+    return c->loss != LRVB_LOSS_NONE && !c->no_resident && D >= 256 && D <= 8192;
+}
+// ... past this many matrix-free products at one point
+static i64 resident_build_threshold(i64 D) { return D / 64 > 8 ? D / 64 : 8; }
+// Counts one more matrix-free product at the current point (c->theta on the device, its state entered); past the threshold
+// the Hessian is built into the resident slot (as lrvb_hessian would leave it) and *resident set.  Every rank counts the same
+// products, so a sharded run builds on all ranks at the same product.
+static int maybe_build_resident(lrvb_ctx* c, const double* point_host, bool* resident) {
+    if (*resident) return LRVB_OK;
+    const i64 D = c->D;
+    if (++c->pt.products <= resident_build_threshold(D) || !resident_build_allowed(c, D)) return LRVB_OK;
+    c->hres.invalidate();
+    LRVB_TRY(buf_reserve(c, c->hres.H, (size_t)D * (size_t)D));
+    LRVB_TRY(build_hessian(c, c->theta.p, true, c->hres.H.p, D));
+    LRVB_TRY(hres_set_point(c, nullptr, point_host));
     *resident = true;
     return LRVB_OK;
 }
 
 static int hvp_host(lrvb_ctx* c, const double* point, const double* v, i64 n_in, bool is_free, double* out) {
-    // same point as the previous call, nothing else in between: its eta / J / g_eta / curvature are still in place
-    const bool reuse = same_point(c, point, n_in, is_free);
-    const bool prepared = reuse && c->hvp_pt_prepared;
-    LRVB_TRY(ctx_bind(c));
+    AtPoint at;
+    LRVB_TRY(bind_point(c, point, n_in, is_free, &at));
     if (!point || !v || !out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
-    const i64 n = is_free ? c->D : c->V;
-    LRVB_TRY(check_len(n_in, n, is_free ? "free vector" : "vector"));
-    LRVB_TRY(data_ready(c));
+    const i64 n = n_in;
     LRVB_TRY(buf_reserve(c, c->cgp, (size_t)n));
     LRVB_TRY(buf_reserve(c, c->cgq, (size_t)n));
-    if (is_free) {                                        // the Hessian of this very point is resident: one D x D product
-        bool resident = false;
-        LRVB_TRY(hres_matches(c, point, n_in, &resident));
-        if (resident) {
-            LRVB_TRY(h2d(c, c->cgp.p, v, (size_t)n));
-            LRVB_TRY(launch_gemv(c, false, n, n, 1.0, c->Hres.p, n, c->cgp.p, 0.0, c->cgq.p));
-            return d2h(c, out, c->cgq.p, (size_t)n);
-        }
-    }
+    bool resident = false;                                // the Hessian of this very point is resident: one D x D product
+    if (is_free) LRVB_TRY(hres_matches(c, point, n, &resident));
     LRVB_TRY(h2d(c, c->cgp.p, v, (size_t)n));
-    if (!reuse) {
-        LRVB_TRY(h2d(c, c->theta.p, point, (size_t)n));
-        LRVB_TRY(set_point(c, c->theta.p, is_free));
-        LRVB_TRY(eval_grad_eta(c, c->stats.p, true));
-        c->pt_products = 0;
+    if (!resident) {
+        LRVB_TRY(enter_point(c, at, false));
+        if (is_free) LRVB_TRY(maybe_build_resident(c, point, &resident));
     }
-    if (is_free) {
-        ++c->pt_products;
-        bool built = false;
-        LRVB_TRY(maybe_build_resident(c, point, n, &built));
-        if (built) {
-            LRVB_TRY(launch_gemv(c, false, n, n, 1.0, c->Hres.p, n, c->cgp.p, 0.0, c->cgq.p));
-            return d2h(c, out, c->cgq.p, (size_t)n);
-        }
+    if (resident) {
+        LRVB_TRY(launch_gemv(c, false, n, n, 1.0, c->hres.H.p, n, c->cgp.p, 0.0, c->cgq.p));
+        return d2h(c, out, c->cgq.p, (size_t)n);
     }
-    if (!prepared && is_free) LRVB_TRY(prepare_general_hvp(c, c->theta.p));
+    LRVB_TRY(enter_point(c, at, true));
     LRVB_TRY(hvp_apply(c, c->theta.p, is_free, c->cgp.p, c->cgq.p));
     LRVB_TRY(d2h(c, out, c->cgq.p, (size_t)n));
-    remember_point(c, point, n, is_free, true);
+    remember_point(c, at);
     return LRVB_OK;
 }
 extern "C" int lrvb_hvp(lrvb_ctx* c, const double* free_in, const double* v, int64_t D, double* out) {
@@ -1326,12 +1328,11 @@ static int obs_grad_impl(lrvb_ctx* c, const double* point, i64 n_in, bool is_fre
     LRVB_TRY(ctx_bind(c));
     if (!point || !G_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
     const i64 width = is_free ? c->D : c->V;
-    LRVB_TRY(check_len(n_in, width, is_free ? "free vector" : "vector"));
+    LRVB_TRY(check_point_len(c, n_in, is_free));
     if (c->loss == LRVB_LOSS_NONE) LRVB_FAIL(LRVB_ERR_STATE, "model has no data term");
     if (n0 < 0 || n1 > c->N || n0 > n1) LRVB_FAIL(LRVB_ERR_INVALID, "row range [%lld, %lld) outside [0, %lld)", (long long)n0, (long long)n1, (long long)c->N);
     LRVB_TRY(data_ready(c));
-    LRVB_TRY(h2d(c, c->theta.p, point, (size_t)width));
-    LRVB_TRY(set_point(c, c->theta.p, is_free));
+    LRVB_TRY(load_point(c, point, is_free));
     LRVB_TRY(eval_grad_eta(c, c->stats.p, false, false));        // per-observation l' only: rank-local
     const bool diag_path = !is_free || c->all_box;
     if (!is_free) EW(fill_kernel, c->V, 1.0, c->vtmp.p);
@@ -1405,10 +1406,8 @@ static int hyper_point(lrvb_ctx* c, int kind, const double* point, i64 n_in, boo
     int64_t Ph = 0;
     LRVB_TRY(lrvb_hyper_size(c, kind, &Ph));
     LRVB_TRY(check_len(n_hyper, Ph, "hyper-parameter"));
-    const i64 n = is_free ? c->D : c->V;
-    LRVB_TRY(check_len(n_in, n, is_free ? "free vector" : "vector"));
-    LRVB_TRY(h2d(c, c->theta.p, point, (size_t)n));
-    LRVB_TRY(set_point(c, c->theta.p, is_free));
+    LRVB_TRY(check_point_len(c, n_in, is_free));
+    LRVB_TRY(load_point(c, point, is_free));
     if (need_J && is_free && !c->all_box) LRVB_TRY(ensure_dense_J(c, c->theta.p));
     if (kind == LRVB_HYPER_LIK_INFO) {
         LRVB_TRY(data_ready(c));
@@ -1647,7 +1646,6 @@ extern "C" int lrvb_group_sums(lrvb_ctx* c, double* out) {
 // ---- hierarchical LMM (config 4): statistics resident on the device, group effects eliminated there ---------------
 // [S (q x q) | group sums (G x (q + 1))] in ONE device buffer, handed to the sum-over-ranks hook once and kept
 // resident for lrvb_lmm_group_terms; both host copies are optional.
-static int grouped_stats_device(lrvb_ctx* c);
 extern "C" int lrvb_grouped_stats(lrvb_ctx* c, double* S_out, double* gs_out) {
     LRVB_TRY(ctx_bind(c));
     LRVB_TRY(grouped_stats_device(c));
@@ -1693,7 +1691,6 @@ static int grouped_stats_device(lrvb_ctx* c) {
 // 128 + (p + 5)^2): the sums of lmm_group_kernel, then M = sum_g c_e c_e^T / dfe + c_i c_i^T / dfi -- the Schur
 // complement of the 2 G local parameters onto the coupled global rows, in vector coordinates of the globals and free
 // coordinates of the locals (H_gl diag(H_ll)^-1 H_lg; the G independent 2 x 2 local blocks of this model are diagonal).
-static int lmm_group_terms_device(lrvb_ctx* c, const double* par, int64_t n_par, const double* f_local, int64_t n_local, double** sums_dev);
 extern "C" int lrvb_lmm_group_terms(lrvb_ctx* c, const double* par, int64_t n_par, const double* f_local, int64_t n_local, double* out) {
     LRVB_TRY(ctx_bind(c));
     if (!par || !f_local || !out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
@@ -2101,6 +2098,57 @@ static int quadform_gram_impl(lrvb_ctx* c, const double* M, const WishartGen* ge
     return LRVB_OK;
 }
 
+// Preconditioned conjugate gradients driven from the host, the loop of lrvb_cg_solve and lrvb_cg_solve_matrix: b in c->rhs,
+// the preconditioner (if any) in c->Hfree, product(v, out) queues out = H v.  Stops when ||r|| < tol ||b||.
+template <class Product>
+static int pcg_host(lrvb_ctx* c, i64 D, const double* x0, bool precond, double tol, i64 maxiter, Product&& product,
+                    double* x_out, int* info_out, int64_t* iters_out) {
+    double* s = c->scal.p;                     // s[0] = ||b||^2, s[1] = ||r||^2, s[2] = r.z, s[3] = p.q
+    double hs[4];
+    LRVB_TRY(launch_dot(c, c->rhs.p, c->rhs.p, D, s + 0));
+    if (x0) {
+        LRVB_TRY(h2d(c, c->cgx.p, x0, (size_t)D));
+        LRVB_TRY(product(c->cgx.p, c->cgq.p));
+        LRVB_TRY(launch_axpby(c, D, 1.0, c->rhs.p, 0.0, c->cgr.p));
+        LRVB_TRY(launch_axpby(c, D, -1.0, c->cgq.p, 1.0, c->cgr.p));
+    } else {
+        HIP_TRY(hipMemsetAsync(c->cgx.p, 0, (size_t)D * sizeof(double), c->stream));
+        LRVB_TRY(launch_axpby(c, D, 1.0, c->rhs.p, 0.0, c->cgr.p));
+    }
+    LRVB_TRY(d2h(c, hs, s, 1));
+    const double bnorm = sqrt(hs[0]);
+    const double atol = tol * bnorm;
+    int info = 0; i64 it = 0;
+    double rho_prev = 0.0;
+    if (bnorm == 0.0) {
+        HIP_TRY(hipMemsetAsync(c->cgx.p, 0, (size_t)D * sizeof(double), c->stream));
+    } else {
+        info = (int)maxiter;
+        for (it = 0; it < maxiter; ++it) {
+            if (precond) LRVB_TRY(launch_gemv(c, false, D, D, 1.0, c->Hfree.p, D, c->cgr.p, 0.0, c->cgz.p));
+            const double* z = precond ? c->cgz.p : c->cgr.p;
+            LRVB_TRY(launch_dot(c, c->cgr.p, c->cgr.p, D, s + 1));
+            LRVB_TRY(launch_dot(c, c->cgr.p, z, D, s + 2));
+            LRVB_TRY(d2h(c, hs + 1, s + 1, 2));
+            if (sqrt(hs[1]) < atol) { info = 0; break; }
+            const double rho = hs[2];
+            if (it > 0) LRVB_TRY(launch_axpby(c, D, 1.0, z, rho / rho_prev, c->cgp.p));
+            else        LRVB_TRY(launch_axpby(c, D, 1.0, z, 0.0, c->cgp.p));
+            LRVB_TRY(product(c->cgp.p, c->cgq.p));
+            LRVB_TRY(launch_dot(c, c->cgp.p, c->cgq.p, D, s + 3));
+            LRVB_TRY(d2h(c, hs + 3, s + 3, 1));
+            const double alpha = rho / hs[3];
+            LRVB_TRY(launch_axpby(c, D, alpha, c->cgp.p, 1.0, c->cgx.p));
+            LRVB_TRY(launch_axpby(c, D, -alpha, c->cgq.p, 1.0, c->cgr.p));
+            rho_prev = rho;
+        }
+    }
+    LRVB_TRY(d2h(c, x_out, c->cgx.p, (size_t)D));
+    if (info_out) *info_out = info;
+    if (iters_out) *iters_out = it;
+    return LRVB_OK;
+}
+
 // Conjugate gradients on a dense symmetric matrix held on the device (objectives whose Hessian is
 // assembled from sufficient statistics: the HVP is a D x D matrix-vector product).  H == NULL reuses
 // the matrix of the previous call.  Same stopping rule as lrvb_cg_solve.
@@ -2121,50 +2169,8 @@ extern "C" int lrvb_cg_solve_matrix(lrvb_ctx* c, const double* H, const double* 
     for (DevBuf* v : vecs) LRVB_TRY(buf_reserve(c, *v, (size_t)D));
     if (Minv) { LRVB_TRY(buf_reserve(c, c->Hfree, (size_t)D * (size_t)D)); LRVB_TRY(h2d(c, c->Hfree.p, Minv, (size_t)D * (size_t)D)); }
     LRVB_TRY(h2d(c, c->rhs.p, b, (size_t)D));
-    double* s = c->scal.p;
-    double hs[4];
-    LRVB_TRY(launch_dot(c, c->rhs.p, c->rhs.p, D, s + 0));
-    if (x0) {
-        LRVB_TRY(h2d(c, c->cgx.p, x0, (size_t)D));
-        LRVB_TRY(launch_gemv(c, false, D, D, 1.0, c->cgH.p, D, c->cgx.p, 0.0, c->cgq.p));
-        LRVB_TRY(launch_axpby(c, D, 1.0, c->rhs.p, 0.0, c->cgr.p));
-        LRVB_TRY(launch_axpby(c, D, -1.0, c->cgq.p, 1.0, c->cgr.p));
-    } else {
-        HIP_TRY(hipMemsetAsync(c->cgx.p, 0, (size_t)D * sizeof(double), c->stream));
-        LRVB_TRY(launch_axpby(c, D, 1.0, c->rhs.p, 0.0, c->cgr.p));
-    }
-    LRVB_TRY(d2h(c, hs, s, 1));
-    const double bnorm = sqrt(hs[0]);
-    const double atol = tol * bnorm;
-    int info = 0; i64 it = 0;
-    double rho_prev = 0.0;
-    if (bnorm == 0.0) {
-        HIP_TRY(hipMemsetAsync(c->cgx.p, 0, (size_t)D * sizeof(double), c->stream));
-    } else {
-        info = (int)maxiter;
-        for (it = 0; it < maxiter; ++it) {
-            if (Minv) LRVB_TRY(launch_gemv(c, false, D, D, 1.0, c->Hfree.p, D, c->cgr.p, 0.0, c->cgz.p));
-            const double* z = Minv ? c->cgz.p : c->cgr.p;
-            LRVB_TRY(launch_dot(c, c->cgr.p, c->cgr.p, D, s + 1));
-            LRVB_TRY(launch_dot(c, c->cgr.p, z, D, s + 2));
-            LRVB_TRY(d2h(c, hs + 1, s + 1, 2));
-            if (sqrt(hs[1]) < atol) { info = 0; break; }
-            const double rho = hs[2];
-            if (it > 0) LRVB_TRY(launch_axpby(c, D, 1.0, z, rho / rho_prev, c->cgp.p));
-            else        LRVB_TRY(launch_axpby(c, D, 1.0, z, 0.0, c->cgp.p));
-            LRVB_TRY(launch_gemv(c, false, D, D, 1.0, c->cgH.p, D, c->cgp.p, 0.0, c->cgq.p));
-            LRVB_TRY(launch_dot(c, c->cgp.p, c->cgq.p, D, s + 3));
-            LRVB_TRY(d2h(c, hs + 3, s + 3, 1));
-            const double alpha = rho / hs[3];
-            LRVB_TRY(launch_axpby(c, D, alpha, c->cgp.p, 1.0, c->cgx.p));
-            LRVB_TRY(launch_axpby(c, D, -alpha, c->cgq.p, 1.0, c->cgr.p));
-            rho_prev = rho;
-        }
-    }
-    LRVB_TRY(d2h(c, x_out, c->cgx.p, (size_t)D));
-    if (info_out) *info_out = info;
-    if (iters_out) *iters_out = it;
-    return LRVB_OK;
+    auto product = [&](const double* vin, double* vout) { return launch_gemv(c, false, D, D, 1.0, c->cgH.p, D, vin, 0.0, vout); };
+    return pcg_host(c, D, x0, Minv != nullptr, tol, maxiter, product, x_out, info_out, iters_out);
 }
 
 // ---- Cholesky / linear response ------------------------------------------------------------
@@ -2213,7 +2219,6 @@ extern "C" int lrvb_chol_solve(lrvb_ctx* c, const double* B, int64_t D, int64_t 
     LRVB_TRY(launch_potrs_lower(c, c->chol.p, D, D, c->rhs.p, nrhs, nrhs));
     return d2h(c, X_out, c->rhs.p, (size_t)D * (size_t)nrhs);
 }
-static int gemm_tn(lrvb_ctx* c, i64 K, i64 PA, i64 PB, const double* A, const double* B, double* C);
 static int lrvb_cov_dev_impl(lrvb_ctx* c, const double* M_dev, i64 Q, i64 D, double* cov_dev) {
     if (!c->chol_valid || c->chol_n != D) LRVB_FAIL(LRVB_ERR_STATE, "no Cholesky factor of size %lld: call lrvb_chol_factor first", (long long)D);
     LRVB_TRY(buf_reserve(c, c->rhs, (size_t)D * (size_t)Q));
@@ -2246,13 +2251,12 @@ static int obs_influence_impl(lrvb_ctx* c, const double* point, i64 n_in, bool i
     LRVB_TRY(ctx_bind(c));
     if (!point || !M || !out || Q <= 0) LRVB_FAIL(LRVB_ERR_INVALID, "bad argument");
     const i64 width = is_free ? c->D : c->V;
-    LRVB_TRY(check_len(n_in, width, is_free ? "free vector" : "vector"));
+    LRVB_TRY(check_point_len(c, n_in, is_free));
     if (c->loss == LRVB_LOSS_NONE || c->data_only) LRVB_FAIL(LRVB_ERR_STATE, "model has no declared data term");
     if (n0 < 0 || n1 > c->N || n0 > n1) LRVB_FAIL(LRVB_ERR_INVALID, "row range [%lld, %lld) outside [0, %lld)", (long long)n0, (long long)n1, (long long)c->N);
     if (!c->chol_valid || c->chol_n != width) LRVB_FAIL(LRVB_ERR_STATE, "no Cholesky factor of size %lld: call lrvb_chol_factor first", (long long)width);
     LRVB_TRY(data_ready(c));
-    LRVB_TRY(h2d(c, c->theta.p, point, (size_t)width));
-    LRVB_TRY(set_point(c, c->theta.p, is_free));
+    LRVB_TRY(load_point(c, point, is_free));
     LRVB_TRY(eval_grad_eta(c, c->stats.p, false, false));          // leaves l'_n in c->lp (rank-local rows)
     // W = H^-1 M^T
     LRVB_TRY(buf_reserve(c, c->work1, (size_t)Q * (size_t)width));
@@ -2315,12 +2319,9 @@ extern "C" int lrvb_obs_influence_vec(lrvb_ctx* c, const double* vec_in, int64_t
 extern "C" int lrvb_cg_solve(lrvb_ctx* c, const double* free_in, const double* b, const double* x0,
                              const double* Minv, double tol, int64_t maxiter, int64_t D,
                              double* x_out, int* info_out, int64_t* iters_out) {
-    const bool reuse = same_point(c, free_in, D, true);          // many right-hand sides at one point: the state stays
-    const bool prepared = reuse && c->hvp_pt_prepared;
-    LRVB_TRY(ctx_bind(c));
+    AtPoint at;                                            // many right-hand sides at one point: the state stays
+    LRVB_TRY(bind_point(c, free_in, D, true, &at));
     if (!free_in || !b || !x_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
-    LRVB_TRY(check_len(D, c->D, "free vector"));
-    LRVB_TRY(data_ready(c));
     if (maxiter <= 0) maxiter = 10 * D;
     DevBuf* vecs[] = { &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz };
     for (DevBuf* v : vecs) LRVB_TRY(buf_reserve(c, *v, (size_t)D));
@@ -2328,68 +2329,13 @@ extern "C" int lrvb_cg_solve(lrvb_ctx* c, const double* free_in, const double* b
     bool resident = false;                                 // the Hessian of this point is resident: products are D x D gemv's
     LRVB_TRY(hres_matches(c, free_in, D, &resident));
     LRVB_TRY(h2d(c, c->rhs.p, b, (size_t)D));
-    // point state once: eta, J, g_eta, cached curvature
-    if (!resident) {
-        if (!reuse) {
-            LRVB_TRY(h2d(c, c->theta.p, free_in, (size_t)D));
-            LRVB_TRY(set_point(c, c->theta.p, true));
-            LRVB_TRY(eval_grad_eta(c, c->stats.p, true));
-            c->pt_products = 0;
-        }
-        if (!prepared) LRVB_TRY(prepare_general_hvp(c, c->theta.p));
-    }
+    if (!resident) LRVB_TRY(enter_point(c, at, true));    // point state once: eta, J, g_eta, cached curvature
     auto product = [&](const double* vin, double* vout) -> int {
-        if (!resident) {                                   // (the right-hand sides of one point, solved one by one: see maybe_build_resident)
-            ++c->pt_products;
-            LRVB_TRY(maybe_build_resident(c, free_in, D, &resident));
-        }
-        return resident ? launch_gemv(c, false, D, D, 1.0, c->Hres.p, D, vin, 0.0, vout) : hvp_apply(c, c->theta.p, true, vin, vout);
+        LRVB_TRY(maybe_build_resident(c, free_in, &resident));   // (the right-hand sides of one point, solved one by one)
+        return resident ? launch_gemv(c, false, D, D, 1.0, c->hres.H.p, D, vin, 0.0, vout) : hvp_apply(c, c->theta.p, true, vin, vout);
     };
-
-    double* s = c->scal.p;                     // s[0] = ||b||^2, s[1] = ||r||^2, s[2] = r.z, s[3] = p.q
-    double hs[4];
-    LRVB_TRY(launch_dot(c, c->rhs.p, c->rhs.p, D, s + 0));
-    if (x0) {
-        LRVB_TRY(h2d(c, c->cgx.p, x0, (size_t)D));
-        LRVB_TRY(product(c->cgx.p, c->cgq.p));
-        LRVB_TRY(launch_axpby(c, D, 1.0, c->rhs.p, 0.0, c->cgr.p));
-        LRVB_TRY(launch_axpby(c, D, -1.0, c->cgq.p, 1.0, c->cgr.p));
-    } else {
-        HIP_TRY(hipMemsetAsync(c->cgx.p, 0, (size_t)D * sizeof(double), c->stream));
-        LRVB_TRY(launch_axpby(c, D, 1.0, c->rhs.p, 0.0, c->cgr.p));
-    }
-    LRVB_TRY(d2h(c, hs, s, 1));
-    const double bnorm = sqrt(hs[0]);
-    const double atol = tol * bnorm;
-    int info = 0; i64 it = 0;
-    double rho_prev = 0.0;
-    if (bnorm == 0.0) {
-        HIP_TRY(hipMemsetAsync(c->cgx.p, 0, (size_t)D * sizeof(double), c->stream));
-    } else {
-        info = (int)maxiter;
-        for (it = 0; it < maxiter; ++it) {
-            if (Minv) LRVB_TRY(launch_gemv(c, false, D, D, 1.0, c->Hfree.p, D, c->cgr.p, 0.0, c->cgz.p));
-            const double* z = Minv ? c->cgz.p : c->cgr.p;
-            LRVB_TRY(launch_dot(c, c->cgr.p, c->cgr.p, D, s + 1));
-            LRVB_TRY(launch_dot(c, c->cgr.p, z, D, s + 2));
-            LRVB_TRY(d2h(c, hs + 1, s + 1, 2));
-            if (sqrt(hs[1]) < atol) { info = 0; break; }
-            const double rho = hs[2];
-            if (it > 0) LRVB_TRY(launch_axpby(c, D, 1.0, z, rho / rho_prev, c->cgp.p));
-            else        LRVB_TRY(launch_axpby(c, D, 1.0, z, 0.0, c->cgp.p));
-            LRVB_TRY(product(c->cgp.p, c->cgq.p));
-            LRVB_TRY(launch_dot(c, c->cgp.p, c->cgq.p, D, s + 3));
-            LRVB_TRY(d2h(c, hs + 3, s + 3, 1));
-            const double alpha = rho / hs[3];
-            LRVB_TRY(launch_axpby(c, D, alpha, c->cgp.p, 1.0, c->cgx.p));
-            LRVB_TRY(launch_axpby(c, D, -alpha, c->cgq.p, 1.0, c->cgr.p));
-            rho_prev = rho;
-        }
-    }
-    LRVB_TRY(d2h(c, x_out, c->cgx.p, (size_t)D));
-    if (info_out) *info_out = info;
-    if (iters_out) *iters_out = it;
-    if (!resident) remember_point(c, free_in, D, true, true);
+    LRVB_TRY(pcg_host(c, D, x0, Minv != nullptr, tol, maxiter, product, x_out, info_out, iters_out));
+    if (!resident) remember_point(c, at);
     return LRVB_OK;
 }
 
@@ -2401,14 +2347,13 @@ extern "C" int lrvb_obs_loss(lrvb_ctx* c, const double* point, int64_t n_in, int
     LRVB_TRY(ctx_bind(c));
     if (!point || !out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
     const i64 width = is_free ? c->D : c->V;
-    LRVB_TRY(check_len(n_in, width, is_free ? "free vector" : "vector"));
+    LRVB_TRY(check_point_len(c, n_in, is_free));
     if (c->loss == LRVB_LOSS_NONE || c->data_only) LRVB_FAIL(LRVB_ERR_STATE, "model has no declared data term");
     if (n0 < 0 || n1 > c->N || n0 > n1) LRVB_FAIL(LRVB_ERR_INVALID, "row range [%lld, %lld) outside [0, %lld)", (long long)n0, (long long)n1, (long long)c->N);
     LRVB_TRY(data_ready(c));
     const i64 rows = n1 - n0, P = c->P;
     if (rows == 0) return LRVB_OK;
-    LRVB_TRY(h2d(c, c->theta.p, point, (size_t)width));
-    LRVB_TRY(set_point(c, c->theta.p, is_free != 0));
+    LRVB_TRY(load_point(c, point, is_free != 0));
     // z = X[n0:n1] beta: the one-vector case of the skinny row product
     LRVB_TRY(buf_reserve(c, c->work1, (size_t)rows * 2));
     double* z = c->work1.p; double* lv = c->work1.p + rows;
@@ -2672,8 +2617,7 @@ extern "C" int lrvb_dk_grad_vec(lrvb_ctx* c, const double* vec_in, int64_t V, in
     LRVB_TRY(data_ready(c));
     const i64 N = c->N, P = c->P;
     const bool glm = c->loss != LRVB_LOSS_NONE;
-    LRVB_TRY(h2d(c, c->theta.p, vec_in, (size_t)V));
-    LRVB_TRY(set_point(c, c->theta.p, false));
+    LRVB_TRY(load_point(c, vec_in, false));
     // weights of this evaluation: the context's, or the caller's direction in weight space
     const double* wsrc = c->w.p;
     if (w_override && glm) {
@@ -2735,9 +2679,7 @@ struct TrustNcg {
     // products at a point -- or at once, if the previous point needed that many -- the Hessian is built and used.
     double* Hm = nullptr; bool h_ready = false; i64 n_here = 0, prev_here = 0, thr = 0;
     int build_H() {
-        LRVB_TRY(hessian_partial(c, x, true, c->stats.p));
-        LRVB_TRY(stats_reduce(c));
-        LRVB_TRY(hessian_finish(c, x, true, c->stats.p, Hm, D));
+        LRVB_TRY(build_hessian(c, x, true, Hm, D));
         h_ready = true; ++nbuild;
         return LRVB_OK;
     }
@@ -2810,16 +2752,15 @@ extern "C" int lrvb_minimize_trust_ncg(lrvb_ctx* c, const double* y0, int64_t D,
     if (!(eta >= 0.0 && eta < 0.25)) LRVB_FAIL(LRVB_ERR_INVALID, "eta must lie in [0, 0.25)");
     if (maxiter <= 0) maxiter = 200 * D;
     const size_t nA = precond ? (size_t)D * (size_t)D : 0;
-    // the point's Hessian may be built inside the CG runs (TrustNcg::h_apply) where the model has a data term and the
-    // resident-Hessian route is not switched off (tuning bit 3)
-    // (from 256 parameters on: below, a pass and a build are both a handful of launches and the run keeps scipy's exact path)
-    const bool can_build = c->loss != LRVB_LOSS_NONE && !c->no_resident && D >= 256 && D <= 8192;
+    // the point's Hessian may be built inside the CG runs (TrustNcg::h_apply) where the resident route may build; below 256
+    // parameters the run keeps scipy's exact path
+    const bool can_build = resident_build_allowed(c, D);
     const size_t nH = can_build ? (size_t)D * (size_t)D : 0;
     LRVB_TRY(buf_reserve(c, c->opt, 12 * (size_t)D + nA + nH));
     TrustNcg o;
     o.c = c; o.D = D;
     o.Hm = can_build ? c->opt.p + 12 * (size_t)D + nA : nullptr;
-    o.thr = D / 64 > 8 ? D / 64 : 8;
+    o.thr = resident_build_threshold(D);
     double* base = c->opt.p;
     o.y = base; o.x = base + D; o.g = base + 2 * D; o.p = base + 4 * D; o.z = base + 5 * D; o.r = base + 6 * D;
     o.d = base + 7 * D; o.Bd = base + 8 * D; o.t1 = base + 9 * D; o.t2 = base + 10 * D; o.yp = base + 11 * D;
@@ -2998,7 +2939,7 @@ static int cg_multi_fused_loop(lrvb_ctx* c, i64 Q, i64 D, double tol, i64 maxite
         HIP_TRY(hipMemcpyAsync(status + (it & 1) * 1024, s + (5 + (it & 1)) * Q, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, c->aux_stream));
         if (resident) {
             // W = U H: the whole block against the resident matrix (H symmetric), identical on every rank -- no reduction
-            LRVB_TRY(launch_symm_block(c, Q, D, U, c->Hres.p, W));
+            LRVB_TRY(launch_symm_block(c, Q, D, U, c->hres.H.p, W));
         } else {
         HIP_TRY(hipMemsetAsync(W, 0, (size_t)(Q * D) * sizeof(double), c->stream));
         for (i64 q0 = 0; q0 < Q; q0 += 16) {
@@ -3048,12 +2989,9 @@ extern "C" int lrvb_cg_solve_multi(lrvb_ctx* c, const double* free_in, const dou
     // d f / d eta and the per-observation curvature are still in place (the reference's ConjugateGradientSolver is built
     // for ONE point x0 and solves for many right-hand sides there, LRVB/ConjugateGradient.py:63-105) -- no second
     // gradient pass over X.
-    const bool reuse = same_point(c, free_in, D, true);
-    const bool prepared = reuse && c->hvp_pt_prepared;
-    LRVB_TRY(ctx_bind(c));
+    AtPoint at;
+    LRVB_TRY(bind_point(c, free_in, D, true, &at));
     if (!free_in || !B || !X_out || Q <= 0) LRVB_FAIL(LRVB_ERR_INVALID, "bad argument");
-    LRVB_TRY(check_len(D, c->D, "free vector"));
-    LRVB_TRY(data_ready(c));
     if (maxiter <= 0) maxiter = 10 * D;
     const i64 V = c->V, Qp = Q + (Q & 1);
     const size_t qd = (size_t)Q * (size_t)D, qv = (size_t)Q * (size_t)V;
@@ -3070,16 +3008,9 @@ extern "C" int lrvb_cg_solve_multi(lrvb_ctx* c, const double* free_in, const dou
     double *Bd = c->cgm[0].p, *Xd = c->cgm[1].p, *Rd = c->cgm[2].p, *Pd = c->cgm[3].p, *Qd = c->cgm[4].p, *Zd = c->cgm[5].p;
     if (Minv) { LRVB_TRY(buf_reserve(c, c->Hfree, (size_t)D * (size_t)D)); LRVB_TRY(h2d(c, c->Hfree.p, Minv, (size_t)D * (size_t)D)); }
     LRVB_TRY(h2d(c, Bd, B, qd));
-    if (!resident) {
-        if (!reuse) {
-            LRVB_TRY(h2d(c, c->theta.p, free_in, (size_t)D));
-            LRVB_TRY(set_point(c, c->theta.p, true));
-            LRVB_TRY(eval_grad_eta(c, c->stats.p, true));
-        }
-        if (!prepared) LRVB_TRY(prepare_general_hvp(c, c->theta.p));
-    }
+    if (!resident) LRVB_TRY(enter_point(c, at, true));
     auto block_product = [&](const double* Vb, double* Out) -> int {
-        return resident ? launch_symm_block(c, Q, D, Vb, c->Hres.p, Out) : hvp_apply_multi(c, Q, Vb, Out);
+        return resident ? launch_symm_block(c, Q, D, Vb, c->hres.H.p, Out) : hvp_apply_multi(c, Q, Vb, Out);
     };
     // scalars: s[0..Q) = ||b||^2 | rr | rz | pq | alpha | beta | minus_alpha | one
     LRVB_TRY(buf_reserve(c, c->scal, (size_t)(8 * Q + 16)));
@@ -3110,7 +3041,7 @@ extern "C" int lrvb_cg_solve_multi(lrvb_ctx* c, const double* free_in, const dou
         LRVB_TRY(cg_multi_fused_loop(c, Q, D, tol, maxiter, Xd, Rd, Pd, info, iters, resident));
         LRVB_TRY(d2h(c, X_out, Xd, qd));
         for (i64 q = 0; q < Q; ++q) { if (info_out) info_out[q] = info[q]; if (iters_out) iters_out[q] = iters[q]; }
-        if (!resident) remember_point(c, free_in, D, true, true);
+        if (!resident) remember_point(c, at);
         return LRVB_OK;
     }
     for (i64 it = 0; it < maxiter && n_active > 0; ++it) {
@@ -3142,7 +3073,7 @@ extern "C" int lrvb_cg_solve_multi(lrvb_ctx* c, const double* free_in, const dou
     }
     LRVB_TRY(d2h(c, X_out, Xd, qd));
     for (i64 q = 0; q < Q; ++q) { if (info_out) info_out[q] = info[q]; if (iters_out) iters_out[q] = iters[q]; }
-    if (!resident) remember_point(c, free_in, D, true, true);
+    if (!resident) remember_point(c, at);
     return LRVB_OK;
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 #include <string>
 #include <vector>
 #include "../../include/lrvb_hip.h"
@@ -79,7 +80,12 @@ struct lrvb_ctx {
     DevBuf cgH; i64 cgH_n = 0;     // dense matrix of lrvb_cg_solve_matrix
     // the free-coordinate Hessian of the last build, kept by the library: products at the SAME point with the SAME data, weights
     // and hyper-parameters (lrvb_hvp, lrvb_cg_solve, lrvb_cg_solve_multi) are D x D matrix products instead of passes over X
-    DevBuf Hres, hres_theta; bool hres_valid = false; bool hres_pt_host = false; std::vector<double> hres_pt;
+    struct ResidentHessian {
+        DevBuf H, theta_dev;           // the D x D matrix; its point, when a `_dev` entry point built it
+        bool valid = false;
+        bool pt_host = false; std::vector<double> pt;   // its point on the host (known once asked for, see hres_matches)
+        void invalidate() { valid = false; }
+    } hres;
     bool no_resident = false;      // tuning/testing: always take the matrix-free products
     // captured launch chains (hipGraph): the device part of a one-call step is a dozen dependent launches of 3-15 us; replayed as
     // a graph the gaps between them go.  A slot is valid for one shape, one set of buffer addresses (buf_epoch moves whenever a
@@ -87,19 +93,25 @@ struct lrvb_ctx {
     struct GraphSlot { hipGraphExec_t exec = nullptr; i64 key[6] = {0, 0, 0, 0, 0, 0}; unsigned long long epoch = 0; hipStream_t stream = nullptr; bool warmed = false, broken = false; };
     GraphSlot mv_graph;            // lrvb_mvnreg_hessian
     unsigned long long buf_epoch = 1;
-    i64 pt_products = 0;           // matrix-free products made at the remembered point (lrvb_hvp / lrvb_cg_solve): past
-                                   // max(8, D / 64) of them the point's Hessian is built and made resident (lrvb_api.hip)
     DevBuf chol, cholW;            // D x D Cholesky factor (lower); inverses of its 64 x 64 diagonal blocks
     DevBuf hprog;                  // operands of an lrvb_hvec_program call
     bool chol_valid = false;
     bool hvec_open = false;        // between lrvb_hvec_begin and lrvb_hvec_finish
     i64 chol_n = 0;
     DevBuf rhs, cgx, cgr, cgp, cgq, cgz, scal;
-    // host-callback optimisers call lrvb_hvp many times at ONE point: the point state (eta, J, g_eta, curvature)
-    // of the last lrvb_hvp / lrvb_hvp_vec call is reused when the next call names the same point and no other
-    // entry point ran in between (every entry point clears the flag in ctx_bind)
-    std::vector<double> hvp_pt; bool hvp_pt_valid = false; bool hvp_pt_free = false;
-    bool hvp_pt_prepared = false;   // the dense packing Jacobian / third-order matrix of general layouts are built too
+    // host-callback optimisers call lrvb_value / lrvb_grad / lrvb_hvp many times at ONE point: the point state (eta, J, g_eta,
+    // curvature) the last of them left is reused when the next call names the same point and no other entry point ran in
+    // between (every entry point invalidates it in ctx_bind)
+    struct PointState {
+        std::vector<double> x; bool valid = false, is_free = false;
+        bool prepared = false;     // the dense packing Jacobian / third-order matrix of general layouts are built too
+        i64 products = 0;          // matrix-free products made at this point: past max(8, D / 64) of them the point's
+                                   // Hessian is built and made resident (lrvb_api.hip)
+        bool is(const double* p, i64 n, bool free_coords) const {
+            return valid && is_free == free_coords && (i64)x.size() == n && memcmp(x.data(), p, (size_t)n * sizeof(double)) == 0;
+        }
+        void invalidate() { valid = false; }
+    } pt;
     DevBuf dkw;                    // lrvb_dk_grad_vec: the caller's weight direction (N)
     DevBuf lmvn;                   // lrvb_logitnormal_mvn_*: parameters, row pass, per-observation coefficients
     DevBuf opt;                    // trust-region Newton-CG: 12 D-vectors (+ the D x D preconditioner)

@@ -309,6 +309,45 @@ def test_many_products_at_one_point_build_the_hessian(vb):
     assert prof['wsyrk_calls'] == 1
 
 
+def test_product_count_starts_again_at_every_new_point(vb):
+    """The count of matrix-free products behind the automatic build belongs to the point: every call that sets up a new point
+    starts it again, whichever entry point that is.  scipy's trust-ncg calls fun, jac, then a few hessp at each iterate
+    (`lrvb_value`, `lrvb_grad`, `lrvb_hvp`): a handful of products per point never adds up to a build, also after a
+    `lrvb_cg_solve_multi` run has set up the point; max(8, D / 64) + 1 products at one point build exactly once."""
+    rng = np.random.default_rng(79)
+    N, P = 4000, 320
+    par, lay = make_par(vb, [('box', 'a', P - 64, -np.inf, np.inf), ('box', 'b', 64, 0.0, np.inf)])
+    x, y, w = glm_data(rng, N, P, om.LOGISTIC)
+    fun = vb.DeviceObjective(par, x=x, y=y, loss='logistic', quad_A=np.full(P, 0.5), weights=w)
+    fun._push_state()
+    ctx = fun.ctx
+    model = om.DeclaredModel(lay, loss=om.LOGISTIC, x=x, y=y, w=w, quad_A=np.full(P, 0.5))
+    points = [rng.normal(size=P) * 0.1 for _ in range(8)]
+    hessians = [model.hessian(theta) for theta in points]
+    ctx.profile_enable(True); ctx.profile_reset()
+    for theta, H in zip(points[:6], hessians[:6]):             # 18 products in all, three per point
+        ctx.value(theta)
+        ctx.grad(theta)
+        for k in range(3):
+            v = rng.normal(size=P)
+            assert rel_err(ctx.hvp(theta, v), H @ v) < 1e-11
+    assert ctx.profile_get()['wsyrk_calls'] == 0
+    theta, H = points[6], hessians[6]
+    X, info, iters = ctx.cg_solve_multi(theta, rng.normal(size=(2, P)))
+    assert np.all(info == 0)
+    for k in range(3):
+        v = rng.normal(size=P)
+        assert rel_err(ctx.hvp(theta, v), H @ v) < 1e-11
+    assert ctx.profile_get()['wsyrk_calls'] == 0
+    theta, H = points[7], hessians[7]
+    for k in range(12):
+        v = rng.normal(size=P)
+        assert rel_err(ctx.hvp(theta, v), H @ v) < 1e-11
+    prof = ctx.profile_get()
+    ctx.profile_enable(False)
+    assert prof['wsyrk_calls'] == 1
+
+
 def test_automatic_build_under_a_reduce_hook(vb):
     """With a sum-over-ranks hook installed (a one-rank identity hook that records what it is handed), the automatic build
     of the point's Hessian inside a run of `lrvb_cg_solve` calls reduces its statistics buffer exactly once -- every rank

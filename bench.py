@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Headline benchmark: ELBO-Hessian builds/sec (+ LRVB-covariance solve time) at
+"""Headline benchmark: ELBO-Hessian builds/sec (+ with --full, LRVB-covariance solve time) at
 N = 1e6 observations x D = 1024 free parameters (BASELINE.json `metric`), synthetic data.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one Hessian build: (theta, w) resident in HBM -> dense free-coordinate Hessian
 (both triangles) in HBM, including the pass over all observations (weights are an input, so
@@ -13,9 +13,13 @@ X^T (c o y), from which the gradient of the data term follows without a separate
 
 The total N is FIXED as --gpus grows (observations shard over ranks): "scaling": "strong".
 Rank 0 prints ONE JSON line with the contract keys plus `roofline` (dominant kernel = the
-weighted SYRK, timed with HIP events on the context's stream inside the timed region) and,
-at N = 1, `cpu_baseline` (the numpy oracle timed on this box's host cores on a bounded
-sample) and `lrvb_solve_ms`.
+weighted SYRK, timed with HIP events on the context's stream inside the timed region).
+
+A plain run does only that: set up, warm up, time the steps, dump (--dump-outputs) and print.
+With --full it also measures, at N = 1, the short runs of configurations c2..c5 (`configs`, before
+the headline), `lrvb_solve_ms`, `config.logistic_build_ms`, `ms_per_step_host_inputs`,
+`cpu_baseline` (the numpy oracle timed on this box's host cores on a bounded sample) and `parity`
+(the built matrix against the oracle's over all rows).
 """
 import argparse
 import json
@@ -38,14 +42,18 @@ def parse(argv=None):
     ap.add_argument('--n-obs', type=float, default=1e6)
     ap.add_argument('--n-free', type=int, default=1024)
     ap.add_argument('--loss', default='gaussian', choices=['gaussian', 'logistic', 'poisson'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='headline run: also measure and check what lies beyond the headline figure (at N = 1: short runs '
+                         'of configurations c2..c5 before the timed steps; after them LRVB solve times, the logistic build, '
+                         'host-copied inputs, CPU baselines and parity against the oracle)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the cpu_baseline and parity legs')
     ap.add_argument('--cpu-budget-s', type=float, default=30.0,
                     help='rough bound on the CPU work of the cpu_baseline leg (seconds)')
     ap.add_argument('--n-splits', type=int, default=0)
     ap.add_argument('--no-configs', action='store_true',
-                    help='headline run only: skip the short embedded runs of configurations c2..c5 (the `configs` object)')
+                    help='with --full: skip the short embedded runs of configurations c2..c5 (the `configs` object)')
     ap.add_argument('--config', default='h', choices=['h', 'c2', 'c3', 'c4', 'c5'],
-                    help='h = the headline metric (default, what the driver runs; at N = 1 its line also carries short runs of '
+                    help='h = the headline metric (default; with --full at N = 1 its line also carries short runs of '
                          'c2..c5 under `configs`); c2..c5 = the other BASELINE.json configurations, one line each with its own '
                          'roofline, observations sharded over --gpus ranks')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
@@ -277,8 +285,8 @@ def cpu_baseline(fetch_rows, n_total, D, n_pos, loss, lik_info, prior_info, thet
 # ---- the other BASELINE.json configurations -------------------------------------------------------
 # `python bench.py --config cN [--gpus G]`: one JSON line for configuration N, observations sharded over the G ranks (strong
 # scaling on the configuration's N; every sum over observations is reduced ON THE DEVICE inside the library's statistics
-# call, once per call).  The headline run (`--config h`, what the driver runs) also embeds a short run of c2..c5 at N = 1 in
-# its line (`configs`), so that all five rooflines are in the driver's record.
+# call, once per call).  The headline run with --full (`--config h --full`) also embeds a short run of c2..c5 at N = 1 in
+# its line (`configs`), so that all five rooflines are in one record.
 def _timed_steps(step, warmup, steps, ctx, fence):
     """EXACTLY `steps` steps between two fences, timed WITHOUT the library's profile marks (under them a one-call step runs its
     launch chain as plain launches instead of the captured graph); the marks -- HIP-event time of the statistics kernels and of
@@ -604,7 +612,7 @@ def main(args):
     # their steps are a few dozen small kernels and host round trips each, and measured after the headline phase (8 GB of
     # tensors freed, a 30 s numpy leg on 64 BLAS threads) the same steps came out 2-7 x slower than in a process of their own.
     configs_out = None
-    if world == 1 and rank == 0 and not args.no_configs:
+    if args.full and world == 1 and rank == 0 and not args.no_configs:
         import gc
         configs_out = embedded_configs(args, (world, rank, dev, backend, use_dist))
         gc.collect()
@@ -776,7 +784,7 @@ def main(args):
                                            'sum_abs_64x64': float(Hout[:64, :64].abs().sum().item()),
                                            'last_row_sum': float(Hout[D - 1].sum().item())}
 
-    if world == 1:
+    if args.full and world == 1:
         # LRVB-covariance solve time: cho_factor(H) + M H^-1 M^T with Q = D moments (worst case)
         M = torch.eye(D, dtype=torch.float64, device=dev)
         cov = torch.empty((D, D), dtype=torch.float64, device=dev)

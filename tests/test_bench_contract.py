@@ -125,6 +125,14 @@ def test_stdout_carries_only_the_result_line(monkeypatch, capfd):
         os.close(saved)
 
 
+def test_full_flag_is_off_by_default():
+    """A plain run measures the headline figure only; everything beyond it (configs, CPU baselines, parity, solve times)
+    waits for --full."""
+    bench = _bench()
+    assert bench.parse([]).full is False
+    assert bench.parse(['--gpus', '1', '--steps', '5', '--warmup', '2', '--full']).full is True
+
+
 def test_steps_flag_is_validated_and_dump_outputs_parsed():
     bench = _bench()
     assert bench.parse([]).dump_outputs is None

@@ -263,6 +263,26 @@ def test_bench_gpus_2_starts_two_ranks_and_builds_the_same_matrix():
     assert 'N=200000 obs x D=256' in two['metric'] and two['scaling'] == 'strong'
 
 
+def test_bench_full_adds_the_legs_beyond_the_headline():
+    """A plain one-rank line carries the headline keys and nothing that takes runs of its own; --full adds the legs beyond
+    it (two of the embedded configurations, to keep the test short), and both lines build the same matrix."""
+    common = ['--gpus', '1', '--steps', '2', '--warmup', '1', '--n-obs', '200000', '--n-free', '256']
+    plain = _bench_line(common, {})
+    full = _bench_line(common + ['--full', '--cpu-budget-s', '4'], {'LRVB_EMBED_ORDER': 'c2,c4'})
+    extras = ('configs', 'lrvb_solve_ms', 'ms_per_step_host_inputs', 'cpu_baseline', 'parity')
+    assert [k for k in extras if k in plain] == [] and 'logistic_build_ms' not in plain['config']
+    assert all(k in full for k in extras) and 'logistic_build_ms' in full['config']
+    for key in ('metric', 'unit', 'higher_is_better', 'dtype', 'steps', 'warmup'):
+        assert plain[key] == full[key], key
+    assert plain['ms_per_step'] > 0 and plain['roofline']['kernel_ms'] > 0
+    assert sorted(k for k in full['configs'] if k != 'seconds') == ['c2', 'c4']
+    assert all('metric' in full['configs'][c] for c in ('c2', 'c4')), full['configs']
+    assert full['parity']['max_rel_err_hessian'] < 1e-11
+    for key, a in plain['config']['hessian_fingerprint'].items():
+        b = full['config']['hessian_fingerprint'][key]
+        assert abs(a - b) <= 1e-11 * max(abs(a), 1.0), key
+
+
 def test_bench_gpus_2_without_a_second_gpu_fails_loudly():
     import torch
     if torch.cuda.device_count() >= 2:

@@ -4,8 +4,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 import numpy as np
 import bench
-args = bench.parse(['--steps', '3', '--warmup', '1', '--cpu-budget-s', '6', '--no-configs'])
-out = bench.main(args)                       # headline + cpu baseline, as the default run does
+args = bench.parse(['--steps', '3', '--warmup', '1', '--full', '--cpu-budget-s', '6', '--no-configs'])
+out = bench.main(args)                       # headline + cpu baseline, as a --full run does
 import torch
 dev = torch.device('cuda', 0)
 for rep in range(2):

@@ -336,6 +336,35 @@ int lrvb_logitnormal_mvn_hvp(lrvb_ctx* ctx, const double* mean, const double* co
  * Lambda -> Lambda^-1) and the last term is the Hessian of +1/2 log det Lambda (minus the entropy).  No observations are involved.          */
 int lrvb_logitnormal_mvn_chain(lrvb_ctx* ctx, int64_t P, const double* cov, const double* M, const double* H_in, double* H_out);
 
+/* ---- multinomial (softmax) regression ---------------------------------------------------------
+ * K classes (2 <= K <= 17), labels y_n in {0 .. K-1}, class 0 the reference; coefficients beta ((K-1) x P, row-major, row a
+ * belongs to class a + 1, P = n_cols <= 1024), z_na = x_n . beta_a, z_n0 = 0, p_n = softmax(z_n).  The data term
+ *   f(beta) = sum_n w_n [ log sum_k exp(z_nk) - z_{n,y_n} ]
+ * in vector coordinates eta = vec(beta) (D = (K-1) P entries).  Any context with a design matrix holds it
+ * (LRVB_LOSS_DATA_ONLY is the natural choice: X and the weights, no GLM term); the existing entry points of that context keep
+ * their meaning.  Every call runs on the context's stream and returns with its results on the host.
+ * K > 17 or P > 1024: LRVB_ERR_UNSUPPORTED.  A softmax call before lrvb_softmax_set_labels: LRVB_ERR_STATE.
+ * Reduce hook (lrvb_set_reduce_hook / lrvb_comm_init): every sum over observations of one call goes through the hook exactly
+ * once, in one device buffer -- lrvb_softmax_terms: [H (D x D, only when hess is asked for) | gradient (D) | value (1)];
+ * lrvb_softmax_hvp: the product (D).  lrvb_softmax_obs_influence forms per-row results only and makes no hook call.
+ * The class probabilities of the last point are kept in the context (N x (K-1)); any change of data, weights, labels or hook
+ * drops them, and a product or influence call at another point forms them again first (one more pass over X).           */
+/* Uploads the labels (n = n_obs int32), checks 0 <= y < K (else LRVB_ERR_INVALID) and fixes K for the context.           */
+int lrvb_softmax_set_labels(lrvb_ctx* ctx, const int32_t* labels, int64_t n, int32_t K);
+/* Value, gradient (D, nullable) and Hessian (D x D, leading dimension ldh >= D, nullable) of the data term at beta.  One fused
+ * pass over X (value, gradient, p), then K(K-1)/2 weighted SYRKs X^T diag(w p_a (delta_ab - p_b)) X, block (a, b) at rows
+ * a P, columns b P, mirrored.                                                                                             */
+int lrvb_softmax_terms(lrvb_ctx* ctx, const double* beta, int64_t K, int64_t P, double* value_out, double* grad_out,
+                       double* hess_out, int64_t ldh);
+/* out = H v (D) at beta, matrix-free: (H v)_a = sum_n w_n p_na (t_na - sum_b p_nb t_nb) x_n, t_nb = x_n . v_b; one pass over X
+ * (two at a point whose p the context does not hold).                                                                    */
+int lrvb_softmax_hvp(lrvb_ctx* ctx, const double* beta, int64_t K, int64_t P, const double* v, double* out);
+/* Streamed weight-sensitivity rows: out[n - n0][q] = sum_a (p_na - [y_n = a + 1]) (A[q, a P : (a + 1) P] . x_n) for
+ * n0 <= n < n1, i.e. A times d2 f / d beta d w_n (column n of the cross Hessian, never formed); A is Q x D row-major (host),
+ * out (n1 - n0) x Q.  Step A of the pass with up to 16 columns per launch, then a per-row contraction over the classes.     */
+int lrvb_softmax_obs_influence(lrvb_ctx* ctx, const double* beta, int64_t K, int64_t P, const double* A, int64_t Q,
+                               int64_t n0, int64_t n1, double* out);
+
 /* ---- objectives that are quadratic in the data ------------------------------------------
  * S = Z^T diag(w) Z (n_cols x n_cols, both triangles) with the context's current weights: the
  * weighted sufficient statistics sum_n w_n z_n z_n^T that `np.einsum('ni,ij,nj,n', ...)` at

@@ -46,6 +46,7 @@ from .hierarchical import LMMObjective
 from .mixture import MixtureObjective
 from .logitnormal import LogitNormalRegressionObjective
 from .logitnormal_mvn import LogitNormalMVNRegressionObjective
+from .softmax import SoftmaxRegressionObjective
 from .torch_closure import TorchObjective
 from . import regression as regression_utils
 from . import packing as ProjectionParams

@@ -219,8 +219,8 @@ constexpr int WS_BUF = 2 * WS_PANEL + 64;                // A panel, B panel, 32
 #define WS_GLDS4_S(sbase, voff, ldsaddr) asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dword %0, %1" \
     :: "v"(voff), "s"(sbase), "s"(ldsaddr) : "memory")
 
-__global__ __launch_bounds__(WS_THREADS, 2)
-void wsyrk_glds_kernel(const double* __restrict__ X, i64 ldx, i64 N, int P,
+// the body of wsyrk_glds_kernel and of its block-batched form below (inlined into both: one copy of the code)
+__device__ __forceinline__ void wsyrk_glds_body(const double* __restrict__ X, i64 ldx, i64 N, int P,
                        const double* __restrict__ cpad, int n_splits, int nb, i64 rows_per_split,
                        double* __restrict__ partial,
                        const double* __restrict__ cypad /* nullable */, double* __restrict__ rpart /* n_splits x nb*128 */)
@@ -456,6 +456,27 @@ void wsyrk_glds_kernel(const double* __restrict__ X, i64 ldx, i64 N, int P,
                 out[(rb1 * 16 + l4 + 4 * r) * WS_TILE + n * 16 + l15] = v1;
             }
     }
+}
+
+__global__ __launch_bounds__(WS_THREADS, 2)
+void wsyrk_glds_kernel(const double* __restrict__ X, i64 ldx, i64 N, int P,
+                       const double* __restrict__ cpad, int n_splits, int nb, i64 rows_per_split,
+                       double* __restrict__ partial,
+                       const double* __restrict__ cypad /* nullable */, double* __restrict__ rpart /* n_splits x nb*128 */)
+{
+    wsyrk_glds_body(X, ldx, N, P, cpad, n_splits, nb, rows_per_split, partial, cypad, rpart);
+}
+
+// Several weighted SYRKs of the same X in ONE launch (multinomial regression: one per Hessian block):
+// blockIdx.y = the product, each with its own padded weight column (cpad + y * cstride) and split partials
+// (partial + y * pstride).  Small P leaves few tiles per product; one launch per product then ends every launch on a
+// ragged tail, one launch for all of them fills the chip until the last product.
+__global__ __launch_bounds__(WS_THREADS, 2)
+void wsyrk_glds_batched_kernel(const double* __restrict__ X, i64 ldx, i64 N, int P, const double* __restrict__ cpad, i64 cstride,
+                               int n_splits, int nb, i64 rows_per_split, double* __restrict__ partial, i64 pstride)
+{
+    wsyrk_glds_body(X, ldx, N, P, cpad + (i64)blockIdx.y * cstride, n_splits, nb, rows_per_split,
+                    partial + (i64)blockIdx.y * pstride, nullptr, nullptr);
 }
 
 // ---- narrow matrices (P <= 64): the sufficient-statistics shape of configs 2, 4, 5 --------------
@@ -1403,6 +1424,51 @@ int launch_tiles_to_dense(lrvb_ctx* c, const double* tiles_dev, i64 P, double* d
     dim3 grid((unsigned)((P + 255) / 256), (unsigned)P);
     hipLaunchKernelGGL(tiles_to_dense_kernel, grid, dim3(256), 0, c->stream,
                        tiles_dev, P, dense_dev, ld, row_off, col_off, accumulate ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    return LRVB_OK;
+}
+
+// tiles[g][e] = sum over the splits of partial[g][s][e] (fixed order), one grid row per product
+__global__ __launch_bounds__(256)
+void wsyrk_batched_reduce_kernel(const double* __restrict__ partial, int n_splits, i64 tile_elems, double* __restrict__ tiles)
+{
+    const i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= tile_elems) return;
+    const i64 g = blockIdx.y;
+    const double* src = partial + g * (i64)n_splits * tile_elems + e;
+    double s = 0.0;
+    for (int k = 0; k < n_splits; ++k) s += __builtin_nontemporal_load(src + (i64)k * tile_elems);
+    tiles[g * tile_elems + e] = s;
+}
+
+bool wsyrk_batched_supported(const lrvb_ctx* c) { return wsyrk_fast_path(c); }
+
+// G weighted SYRKs X^T diag(c_g) X in one launch: c_g = cols + g * cstride (each with >= 32 zeros past N), the packed
+// lower tiles of product g to tiles_out + g * T * 128 * 128.  The split count is chosen for all G T tiles together.
+int launch_wsyrk_batched(lrvb_ctx* c, const double* cols, i64 cstride, int G, double* tiles_out) {
+    if (!wsyrk_batched_supported(c)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "batched SYRK: even P > 64, 16-byte aligned X");
+    if (G <= 0) return LRVB_OK;
+    const int T = wsyrk_num_tiles(c->P);
+    const i64 Teff = (i64)T * G;
+    i64 S = (4608 + Teff / 2) / Teff;                    // ~18 work items per CU over all products (wsyrk_auto_splits)
+    S = ((S + 7) / 8) * 8;
+    i64 max_by_rows = (c->N / 1900 / 8) * 8;
+    if (S > max_by_rows) S = max_by_rows;
+    if (S > 128) S = 128;
+    if (S < 8) S = 8;
+    i64 rps = (c->N + S - 1) / S;
+    rps = ((rps + WS_KC - 1) / WS_KC) * WS_KC;
+    if (rps < WS_KC) rps = WS_KC;
+    const i64 tile_elems = (i64)T * WS_TILE * WS_TILE;
+    LRVB_TRY(buf_reserve(c, c->tile_part, (size_t)(tile_elems * S * G)));
+    const int nbt = (int)((c->P + WS_TILE - 1) / WS_TILE);
+    if (c->prof_on) LRVB_TRY(prof_mark(c, PROF_WSYRK));
+    hipLaunchKernelGGL(wsyrk_glds_batched_kernel, dim3((unsigned)(S * T), (unsigned)G), dim3(WS_THREADS), 0, c->stream,
+                       c->X.p, c->P, c->N, (int)c->P, cols, cstride, (int)S, nbt, rps, c->tile_part.p, tile_elems * S);
+    HIP_TRY(hipGetLastError());
+    if (c->prof_on) LRVB_TRY(prof_mark(c, PROF_WSYRK));
+    hipLaunchKernelGGL(wsyrk_batched_reduce_kernel, dim3((unsigned)((tile_elems + 255) / 256), (unsigned)G), dim3(256), 0, c->stream,
+                       (const double*)c->tile_part.p, (int)S, tile_elems, tiles_out);
     HIP_TRY(hipGetLastError());
     return LRVB_OK;
 }

@@ -67,7 +67,7 @@ static int ctx_bind(lrvb_ctx* c) {
 // What a setter leaves stale: the point state always, the resident Hessian when the objective itself changed.
 static void invalidate_caches(lrvb_ctx* c, bool objective_changed) {
     c->pt.invalidate();
-    if (objective_changed) c->hres.invalidate();
+    if (objective_changed) { c->hres.invalidate(); c->sm.p_valid = false; }
 }
 
 static int pinned_reserve(lrvb_ctx* c, size_t n) {
@@ -231,7 +231,8 @@ extern "C" int lrvb_ctx_destroy(lrvb_ctx* c) {
     DevBuf* all[] = { &c->X, &c->y, &c->w, &c->quadA, &c->quadM, &c->quadB, &c->theta, &c->eta, &c->j1, &c->j2,
                       &c->vtmp, &c->vtmp2, &c->vtmp3, &c->g_eta, &c->g_free, &c->lp, &c->cw, &c->zbuf,
                       &c->part_vec, &c->part_val, &c->stats, &c->tile_part, &c->Heta, &c->Hfree, &c->Jdense,
-                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn };
+                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn,
+                      &c->sm.labels, &c->sm.p, &c->sm.wpad, &c->sm.work, &c->sm.col, &c->sm.tiles, &c->sm.rows };
     for (DevBuf* b : all) buf_free(*b);
     if (c->host_pinned) (void)hipHostFree(c->host_pinned);
     if (c->up_ring) { for (int k = 0; k < lrvb_ctx::UP_SLOTS; ++k) if (c->up_ev[k]) (void)hipEventDestroy(c->up_ev[k]); (void)hipHostFree(c->up_ring); }
@@ -3123,4 +3124,164 @@ extern "C" int lrvb_profile_reset(lrvb_ctx* c) {
     LRVB_TRY(prof_collect(c));
     c->prof = lrvb_prof{};
     return LRVB_OK;
+}
+
+// ---- multinomial (softmax) regression (k_softmax.hip) ----------------------------------------------------
+extern "C" int lrvb_softmax_set_labels(lrvb_ctx* c, const int32_t* labels, int64_t n, int32_t K) {
+    LRVB_TRY(ctx_bind(c));
+    if (!labels) LRVB_FAIL(LRVB_ERR_INVALID, "null labels");
+    if (c->loss == LRVB_LOSS_NONE) LRVB_FAIL(LRVB_ERR_STATE, "model has no data term");
+    if (K < 2) LRVB_FAIL(LRVB_ERR_INVALID, "softmax regression needs K >= 2 classes (got %d)", (int)K);
+    if (!softmax_supported(K, c->P))
+        LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "softmax regression is built for 2 <= K <= 17 classes and 1 <= n_cols <= 1024 (got K = %d, n_cols = %lld)",
+                  (int)K, (long long)c->P);
+    if (n != c->N) LRVB_FAIL(LRVB_ERR_SIZE, "labels must have %lld entries (got %lld)", (long long)c->N, (long long)n);
+    for (i64 i = 0; i < n; ++i)
+        if (labels[i] < 0 || labels[i] >= K) LRVB_FAIL(LRVB_ERR_INVALID, "label %lld is %d, outside [0, %d)", (long long)i, (int)labels[i], (int)K);
+    const size_t nd = (size_t)((n + 64 + 1) / 2);             // int32 entries, 64 of them zero past N
+    LRVB_TRY(buf_reserve(c, c->sm.labels, nd));
+    std::vector<int32_t> h((size_t)(2 * nd), 0);
+    memcpy(h.data(), labels, (size_t)n * sizeof(int32_t));
+    HIP_TRY(hipMemcpyAsync(c->sm.labels.p, h.data(), nd * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->sm.K = (int)K;
+    invalidate_caches(c, true);
+    return LRVB_OK;
+}
+
+static int sm_check(lrvb_ctx* c, int64_t K, int64_t P_in) {
+    if (c->loss == LRVB_LOSS_NONE || !c->have_X) LRVB_FAIL(LRVB_ERR_STATE, "the context needs a design matrix: lrvb_set_data for LRVB_SLOT_X");
+    if (!softmax_supported(K, P_in)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "softmax regression is built for 2 <= K <= 17 classes and 1 <= P <= 1024");
+    if (c->sm.K == 0) LRVB_FAIL(LRVB_ERR_STATE, "no labels: call lrvb_softmax_set_labels first");
+    if (K != c->sm.K) LRVB_FAIL(LRVB_ERR_SIZE, "K = %lld, but the labels were set for %d classes", (long long)K, c->sm.K);
+    LRVB_TRY(check_len(P_in, c->P, "P (n_cols)"));
+    // the chunk staging reads 8 weights at a time: a zero-padded copy of the current weights
+    LRVB_TRY(reserve_obs_vec(c, c->sm.wpad));
+    HIP_TRY(hipMemcpyAsync(c->sm.wpad.p, c->w.p, (size_t)c->N * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    const size_t np = (size_t)(c->N * (K - 1) + 16 * 8 + 64);     // the DMA of a chunk's p rows reads up to 8 (K - 1) past N (K - 1)
+    if (c->sm.p.n < np) { LRVB_TRY(buf_reserve(c, c->sm.p, np)); HIP_TRY(hipMemsetAsync(c->sm.p.p, 0, np * sizeof(double), c->stream)); c->sm.p_valid = false; }
+    return LRVB_OK;
+}
+
+// p at beta (uploaded to beta_dev) unless the context holds it already; the pass's sums go to scratch (no reduction: p is per row)
+static int sm_refresh_p(lrvb_ctx* c, const double* beta, const double* beta_dev, int Km, double* g_scratch, double* v_scratch) {
+    const i64 D = (i64)Km * c->P;
+    if (c->sm.p_valid && (i64)c->sm.p_beta.size() == D && memcmp(c->sm.p_beta.data(), beta, (size_t)D * sizeof(double)) == 0)
+        return LRVB_OK;
+    LRVB_TRY(launch_softmax_pass(c, 0, Km, beta_dev, c->sm.wpad.p, (const int*)c->sm.labels.p, c->sm.p.p, g_scratch, v_scratch));
+    c->sm.p_beta.assign(beta, beta + D); c->sm.p_valid = true;
+    return LRVB_OK;
+}
+
+extern "C" int lrvb_softmax_terms(lrvb_ctx* c, const double* beta, int64_t K, int64_t P_in, double* value_out, double* grad_out,
+                                  double* hess_out, int64_t ldh) {
+    LRVB_TRY(ctx_bind(c));
+    if (!beta || !value_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    LRVB_TRY(sm_check(c, K, P_in));
+    const int Km = (int)(K - 1);
+    const i64 P = c->P, D = (i64)Km * P, N = c->N;
+    const bool want_H = hess_out != nullptr;
+    if (want_H && ldh < D) LRVB_FAIL(LRVB_ERR_SIZE, "ldh = %lld < (K - 1) P = %lld", (long long)ldh, (long long)D);
+    // [beta D | H (D x D, if asked) | gradient D | value]: the sums of this call in one buffer, summed over the ranks once
+    LRVB_TRY(buf_reserve(c, c->sm.work, (size_t)(D + (want_H ? D * D : 0) + D + 1)));
+    double* bdev = c->sm.work.p;
+    double* H = bdev + D;
+    double* g = H + (want_H ? D * D : 0);
+    double* val = g + D;
+    LRVB_TRY(h2d(c, bdev, beta, (size_t)D));
+    LRVB_TRY(launch_softmax_pass(c, 0, Km, bdev, c->sm.wpad.p, (const int*)c->sm.labels.p, c->sm.p.p, g, val));
+    c->sm.p_beta.assign(beta, beta + D); c->sm.p_valid = true;
+    if (want_H) {
+        // block (a, b), a <= b: X^T diag(w p_a (delta_ab - p_b)) X by the weighted SYRK, placed at (a P, b P) and mirrored.
+        // Below 16 tiles per product (P <= 640) on the LDS-DMA SYRK path the blocks go in batches, one launch each (grid:
+        // product x tile x split): a launch per block fills the chip for fewer than four rounds of workgroups and ends on a
+        // ragged tail.  Measured: P = 256, K = 10 SYRK kernels 68 -> 54 ms batched; P = 1024, K = 4
+        // 90 ms per block against 97-101 ms batched, so the tuned per-block launch stays there.
+        const i64 tile_elems = (i64)wsyrk_num_tiles(P) * WS_TILE * WS_TILE;
+        const int nprod = Km * (Km + 1) / 2;
+        const i64 cst = N + 64;                              // weight columns, zero past N
+        int G = 1;
+        if (wsyrk_batched_supported(c) && nprod > 1 && wsyrk_num_tiles(P) < 16) {
+            i64 g = ((i64)1 << 27) / cst;                    // at most 1 GiB of weight columns per batch
+            if (g > 64) g = 64;
+            G = (int)(g < nprod ? (g < 1 ? 1 : g) : nprod);
+        }
+        LRVB_TRY(buf_reserve(c, c->sm.col, (size_t)(G * cst)));
+        HIP_TRY(hipMemsetAsync(c->sm.col.p, 0, (size_t)(G * cst) * sizeof(double), c->stream));
+        LRVB_TRY(buf_reserve(c, c->sm.tiles, (size_t)(G * tile_elems)));
+        std::vector<std::pair<int, int>> blk;
+        for (int a = 0; a < Km; ++a)
+            for (int b = a; b < Km; ++b) blk.emplace_back(a, b);
+        for (int k0 = 0; k0 < nprod; k0 += G) {
+            const int g = (nprod - k0) < G ? (nprod - k0) : G;
+            for (int j = 0; j < g; ++j)
+                LRVB_TRY(launch_softmax_hess_coef(c, Km, blk[k0 + j].first, blk[k0 + j].second, c->sm.wpad.p, c->sm.p.p, c->sm.col.p + j * cst));
+            if (G > 1) LRVB_TRY(launch_wsyrk_batched(c, c->sm.col.p, cst, g, c->sm.tiles.p));
+            else       LRVB_TRY(launch_wsyrk(c, c->sm.col.p, c->sm.tiles.p));
+            for (int j = 0; j < g; ++j) {
+                const int a = blk[k0 + j].first, b = blk[k0 + j].second;
+                const double* t = c->sm.tiles.p + j * tile_elems;
+                LRVB_TRY(launch_tiles_to_dense(c, t, P, H, D, a * P, b * P, false));
+                if (b != a) LRVB_TRY(launch_tiles_to_dense(c, t, P, H, D, b * P, a * P, false));
+            }
+        }
+    }
+    (void)N;
+    double* first = want_H ? H : g;
+    LRVB_TRY(obs_reduce(c, first, (i64)(val + 1 - first)));
+    LRVB_TRY(d2h(c, value_out, val, 1));
+    if (grad_out) LRVB_TRY(d2h(c, grad_out, g, (size_t)D));
+    if (want_H) {
+        HIP_TRY(hipMemcpy2DAsync(hess_out, (size_t)ldh * sizeof(double), H, (size_t)D * sizeof(double), (size_t)D * sizeof(double),
+                                 (size_t)D, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return LRVB_OK;
+}
+
+extern "C" int lrvb_softmax_hvp(lrvb_ctx* c, const double* beta, int64_t K, int64_t P_in, const double* v, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    if (!beta || !v || !out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    LRVB_TRY(sm_check(c, K, P_in));
+    const int Km = (int)(K - 1);
+    const i64 D = (i64)Km * c->P;
+    // [beta D | v D | scratch gradient D | scratch value 8 | product D]
+    LRVB_TRY(buf_reserve(c, c->sm.work, (size_t)(4 * D + 8)));
+    double* bdev = c->sm.work.p; double* vdev = bdev + D; double* gs = vdev + D; double* vs = gs + D; double* o = vs + 8;
+    LRVB_TRY(h2d(c, bdev, beta, (size_t)D));
+    LRVB_TRY(h2d(c, vdev, v, (size_t)D));
+    LRVB_TRY(sm_refresh_p(c, beta, bdev, Km, gs, vs));
+    LRVB_TRY(launch_softmax_pass(c, 1, Km, vdev, c->sm.wpad.p, (const int*)c->sm.labels.p, c->sm.p.p, o, nullptr));
+    LRVB_TRY(obs_reduce(c, o, D));
+    return d2h(c, out, o, (size_t)D);
+}
+
+extern "C" int lrvb_softmax_obs_influence(lrvb_ctx* c, const double* beta, int64_t K, int64_t P_in, const double* A, int64_t Q,
+                                          int64_t n0, int64_t n1, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    if (!beta || !A || !out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    LRVB_TRY(sm_check(c, K, P_in));
+    if (Q < 1) LRVB_FAIL(LRVB_ERR_INVALID, "Q must be positive");
+    if (n0 < 0 || n1 < n0 || n1 > c->N) LRVB_FAIL(LRVB_ERR_INVALID, "row range [%lld, %lld) outside [0, %lld)", (long long)n0, (long long)n1, (long long)c->N);
+    const int Km = (int)(K - 1);
+    const i64 P = c->P, D = (i64)Km * P, rows = n1 - n0;
+    LRVB_TRY(buf_reserve(c, c->sm.work, (size_t)(2 * D + 8)));
+    double* bdev = c->sm.work.p; double* gs = bdev + D; double* vs = gs + D;
+    LRVB_TRY(h2d(c, bdev, beta, (size_t)D));
+    LRVB_TRY(sm_refresh_p(c, beta, bdev, Km, gs, vs));
+    if (rows == 0) return LRVB_OK;
+    // [A (Q x D) | row products (rows x 16) | out (rows x Q)]
+    LRVB_TRY(buf_reserve(c, c->sm.rows, (size_t)(Q * D + rows * 16 + rows * Q)));
+    double* Ad = c->sm.rows.p; double* T = Ad + Q * D; double* od = T + rows * 16;
+    LRVB_TRY(h2d(c, Ad, A, (size_t)(Q * D)));
+    LRVB_TRY(reserve_obs_vec(c, c->sm.col));                  // unit row scale (zero past N): the cross Hessian has no w_n factor
+    EW(fill_kernel, c->N, 1.0, c->sm.col.p);
+    // G outputs per launch: their G (K - 1) vectors A[q, a P : (a + 1) P] are G (K - 1) consecutive rows of stride P
+    const int G = 16 / Km;
+    for (i64 q0 = 0; q0 < Q; q0 += G) {
+        const int g = (int)((Q - q0) < G ? (Q - q0) : G);
+        LRVB_TRY(launch_softmax_rows(c, n0, n1, g * Km, Ad + q0 * D, P, c->sm.col.p, T, 16));
+        LRVB_TRY(launch_softmax_influence_contract(c, n0, rows, g, Km, c->sm.p.p, (const int*)c->sm.labels.p, T, 16, od, Q, q0));
+    }
+    return d2h(c, out, od, (size_t)(rows * Q));
 }

@@ -113,6 +113,18 @@ struct lrvb_ctx {
         void invalidate() { valid = false; }
     } pt;
     DevBuf dkw;                    // lrvb_dk_grad_vec: the caller's weight direction (N)
+    // multinomial (softmax) regression (k_softmax.hip): labels fixed by lrvb_softmax_set_labels, the class probabilities p
+    // (N x (K - 1)) of the last pass and the point beta they belong to (dropped with every change of the objective)
+    struct Softmax {
+        int K = 0;
+        DevBuf labels;                 // N + 64 int32 (zero padding past N), stored in doubles
+        DevBuf p;                      // N (K - 1) + padding: p of the point p_beta
+        DevBuf wpad;                   // the weights, N + 64 (zero padding past N: the chunk staging reads 8 rows at a time)
+        DevBuf work;                   // beta | v | pass output [H | grad | value] / influence operands
+        DevBuf col, tiles;             // one Hessian weight column (N + 64), the tiles of one block's SYRK
+        DevBuf rows;                   // lrvb_softmax_obs_influence: [A (Q x D) | row products (rows x 16) | out (rows x Q)]
+        bool p_valid = false; std::vector<double> p_beta;
+    } sm;
     DevBuf lmvn;                   // lrvb_logitnormal_mvn_*: parameters, row pass, per-observation coefficients
     DevBuf opt;                    // trust-region Newton-CG: 12 D-vectors (+ the D x D preconditioner)
     DevBuf cgm[9];                 // blocked CG: B, X, R, P, Q, Z (Q x D), U, W (Q x V), R^T (P x Q)
@@ -176,6 +188,8 @@ int launch_obs_grad(lrvb_ctx* c, i64 n0, i64 n1, double* G_dev, int mode, const 
 int  wsyrk_num_tiles(i64 P);
 int  wsyrk_auto_splits(const lrvb_ctx* c);
 int  launch_wsyrk(lrvb_ctx* c, const double* cvec_dev, double* tiles_out_dev /* T*128*128 */);
+bool wsyrk_batched_supported(const lrvb_ctx* c);
+int  launch_wsyrk_batched(lrvb_ctx* c, const double* cols, i64 cstride, int G, double* tiles_out /* G x T*128*128 */);
 bool wsyrk_fast_path(const lrvb_ctx* c);
 int  launch_wsyrk_r(lrvb_ctx* c, const double* cvec_dev, double* tiles_out_dev, const double* cy_dev /* nullable */, double* r_out_dev /* P */);
 int  launch_gram_small_on(lrvb_ctx* c, const double* Z, i64 N, i64 P, const double* cvec_dev, double* tiles_out_dev,
@@ -190,6 +204,16 @@ int  launch_atb_kron32(lrvb_ctx* c, const double* X31, const double* B, i64 N, c
 int  launch_wsyrk_kron(lrvb_ctx* c, const double* cvec_dev, double* tiles_out_dev /* nb = ceil(q (q + 1) / 2 / 128) tile rows */);
 int  launch_tiles_to_dense(lrvb_ctx* c, const double* tiles_dev, i64 P, double* dense_dev, i64 ld,
                            i64 row_off, i64 col_off, bool accumulate);
+
+// k_softmax.hip (2 <= K <= 17, 1 <= P <= 1024)
+bool softmax_supported(i64 K, i64 P);
+int  launch_softmax_pass(lrvb_ctx* c, int mode /* 0 value + gradient, 1 product */, int Km, const double* U_dev, const double* cw_pad,
+                         const int* labels_pad, double* pbuf, double* out_dev, double* value_dev);
+int  launch_softmax_rows(lrvb_ctx* c, i64 n0, i64 n1, int Q, const double* Zt_dev, i64 ldz, const double* cw_pad,
+                         double* Tout_dev, i64 ldt);
+int  launch_softmax_hess_coef(lrvb_ctx* c, int Km, int a, int b, const double* w, const double* p, double* col);
+int  launch_softmax_influence_contract(lrvb_ctx* c, i64 n0, i64 rows, int G, int Km, const double* p, const int* labels,
+                                       const double* T, i64 ldt, double* out, i64 ldo, i64 q0);
 
 // k_logitmvn.hip (P = n_cols <= 64)
 int  launch_lmvn_rowpass(lrvb_ctx* c, const double* A, const double* b, double* r, double* t);   // r_n = x_n^T A x_n, t_n = x_n . b

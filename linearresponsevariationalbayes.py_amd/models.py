@@ -322,6 +322,40 @@ class DeviceContext(object):
                                                     _hip.ptr(val), _hip.ptr(g), _hip.ptr(Hb)))
         return float(val[0]), g, (None if Hb is None else (Hb[0], Hb[1], Hb[2]))
 
+    # ---- multinomial (softmax) regression: beta is (K - 1) x n_cols, D = (K - 1) n_cols (lrvb_softmax_*) --------------------
+    def softmax_set_labels(self, labels, n_classes):
+        y = np.ascontiguousarray(np.asarray(labels).ravel(), dtype=np.int32)
+        self._check(self._lib.lrvb_softmax_set_labels(self._h, y.ctypes.data, y.size, int(n_classes)))
+
+    def softmax_terms(self, beta, n_classes, want_grad=True, want_hess=True):
+        """Data term value, gradient (D) and Hessian (D x D) at beta (lrvb_softmax_terms)."""
+        b = _hip.as_f64(beta).ravel()
+        D = b.size
+        val = np.empty(1)
+        g = np.empty(D) if want_grad else None
+        H = np.empty((D, D)) if want_hess else None
+        self._check(self._lib.lrvb_softmax_terms(self._h, _hip.ptr(b), int(n_classes), self.n_cols, _hip.ptr(val), _hip.ptr(g),
+                                                 _hip.ptr(H), D))
+        return float(val[0]), g, H
+
+    def softmax_hvp(self, beta, n_classes, v):
+        b, v = _hip.as_f64(beta).ravel(), _hip.as_f64(v).ravel()
+        out = np.empty(b.size)
+        self._check(self._lib.lrvb_softmax_hvp(self._h, _hip.ptr(b), int(n_classes), self.n_cols, _hip.ptr(v), _hip.ptr(out)))
+        return out
+
+    def softmax_obs_influence(self, beta, n_classes, A, n0=0, n1=None):
+        """(n1 - n0) x Q rows: row n is A d2 f / d beta d w_n (lrvb_softmax_obs_influence)."""
+        b = _hip.as_f64(beta).ravel()
+        A = np.ascontiguousarray(_hip.as_f64(A))
+        if A.ndim != 2 or A.shape[1] != b.size:
+            raise ValueError('A must have {} columns'.format(b.size))
+        n1 = self.n_obs if n1 is None else int(n1)
+        out = np.empty((max(n1 - int(n0), 0), A.shape[0]))
+        self._check(self._lib.lrvb_softmax_obs_influence(self._h, _hip.ptr(b), int(n_classes), self.n_cols, _hip.ptr(A), A.shape[0],
+                                                         int(n0), n1, _hip.ptr(out)))
+        return out
+
     def obs_influence(self, x, moment_jac, n0=0, n1=None, is_free=True):
         """d moments / d weights for observations n0..n1 ((n1 - n0) x Q), from the resident factor."""
         x = _hip.as_f64(x).ravel()

@@ -141,6 +141,8 @@ class ParametricSensitivityLinearApproximation(object):
             raise NotImplementedError('row streaming is defined for hyper_par = observation weights of a declared objective')
         self.set_par_to_base_values()
         fun._push_state()
+        if hasattr(fun, 'obs_influence'):           # a model with its own streamed rows (softmax.py)
+            return fun.obs_influence(self.input_val0, moment_jac, n0=n0, n1=n1, is_free=self.input_is_free, chol=self.hess0_chol)
         self.hess0_chol.ensure_resident(fun.ctx)
         return fun.ctx.obs_influence(self.input_val0, moment_jac, n0=n0, n1=n1, is_free=self.input_is_free)
 

@@ -336,6 +336,41 @@ int lrvb_logitnormal_mvn_hvp(lrvb_ctx* ctx, const double* mean, const double* co
  * Lambda -> Lambda^-1) and the last term is the Hessian of +1/2 log det Lambda (minus the entropy).  No observations are involved.          */
 int lrvb_logitnormal_mvn_chain(lrvb_ctx* ctx, int64_t P, const double* cov, const double* M, const double* H_in, double* H_out);
 
+/* ---- logistic mixed model with a random intercept ------------------------------------------------
+ * y_n ~ Bernoulli(sigma(x_n . beta + u_g(n))), q(beta_j) = N(mean_j, var_j), q(u_g) = N(e_g, r_g).  The context holds X
+ * (n_obs x P, P <= 64), y, the weights and the groups (lrvb_set_groups, G groups).  Data term
+ *   f = sum_n w_n ( psi(rho_n, s_n) - y_n rho_n ),  rho_n = x_n . mean + e_g(n),  s_n = (x_n o x_n) . var + r_g(n),
+ * psi(rho, s) = E log(1 + e^z), z ~ N(rho, s), by Gauss-Hermite; derivatives in s by Stein's identity on the same nodes
+ * (d_s = 1/2 E g2, d_rho d_s = 1/2 E g3, d_s^2 = 1/4 E g4, gk the k-th derivative of log(1 + e^t)), as
+ * lrvb_logitnormal_mvn_terms.  Per observation a1 = w (psi_rho - y), a2 = w psi_s, c11 = w psi_rhorho, c12 = w psi_rhos,
+ * c22 = w psi_ss.  Coordinates (mean, var, e, r).
+ * One pass over the group-sorted rows forms the coefficients and, per group, the fixed-order sums (no atomics: two calls at
+ * one point return bitwise equal results)
+ *   [sum a1, sum a2 | sum c11, sum c12, sum c22 | sum c11 x | sum c12 x | sum c12 x o x | sum c22 x o x]   (5 + 4 P numbers);
+ * the global gradient [X^T a1 | (X o X)^T a2] and the blocks X^T D11 X, X^T D12 (X o X), (X o X)^T D22 (X o X) follow on the
+ * kernels of lrvb_logitnormal_terms.  Outputs (host; all but value_out nullable): value, grad_global (2 P), grad_local
+ * (G x 2: sum a1, sum a2), H_blocks (3 P^2), border (G x 4 P: the four P-vectors above) and local (G x 3: sum c11, c12, c22).
+ * Reduce hook: every sum over observations of the call lies in ONE device buffer
+ *   [H blocks (3 P^2, only when asked for) | group sums (G x (5 + 4 P)) | gradient (2 P) | value (1)]
+ * and goes through the hook exactly once (groups may straddle ranks: their sums add).  The group sums stay resident in the
+ * context for lrvb_glmm_schur until the next lrvb_glmm_terms or lrvb_set_groups.
+ * P > 64 or more than 128 nodes: LRVB_ERR_UNSUPPORTED; groups, X or y not set: LRVB_ERR_STATE; var_j <= 0 or r_g <= 0:
+ * LRVB_ERR_INVALID.                                                                                                     */
+int lrvb_glmm_terms(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r, int64_t G,
+                    const double* gh_x, const double* gh_w, int32_t n_nodes, double* value_out, double* grad_global_out,
+                    double* grad_local_out, double* H_blocks_out, double* border_out, double* local_out);
+/* Elimination of the 2 G local parameters on the device, from the group sums of the last lrvb_glmm_terms (the border is not
+ * copied to the host).  Per group the host sends the COMPLETE 2 x 2 local block in the coordinates it eliminates in
+ * (local_2x2, G x 3: [a11, a12, a22] -- data part, N-independent terms and chain terms added by the host), the two chain
+ * factors of those coordinates (border_scale, G x 2: d e / d coordinate, d r / d coordinate) and the closed-form border
+ * rows of the three scalar parameters (closed_rows, G x 6: rows [e_mu, a, b] against e_g, then against r_g).  With
+ *   C_g = [ f_e [sum c11 x | sum c12 x o x | closed_e] ; f_r [sum c12 x | sum c22 x o x | closed_r] ]      (2 x (2 P + 3))
+ * M_out ((2 P + 3)^2, row-major) = sum_g C_g^T A_g^-1 C_g over the coupled coordinates [mean (P) | var (P) | e_mu, a, b]:
+ * rows scaled by the 2 x 2 Cholesky factors, then one Gram over 2 G rows.  A block that is not positive definite:
+ * LRVB_ERR_NOT_POSDEF; no resident group sums: LRVB_ERR_STATE.                                                           */
+int lrvb_glmm_schur(lrvb_ctx* ctx, const double* local_2x2, const double* border_scale, const double* closed_rows, int64_t G,
+                    double* M_out);
+
 /* ---- multinomial (softmax) regression ---------------------------------------------------------
  * K classes (2 <= K <= 17), labels y_n in {0 .. K-1}, class 0 the reference; coefficients beta ((K-1) x P, row-major, row a
  * belongs to class a + 1, P = n_cols <= 1024), z_na = x_n . beta_a, z_n0 = 0, p_n = softmax(z_n).  The data term
@@ -546,7 +581,8 @@ int lrvb_hessian_dev(lrvb_ctx* ctx, const double* free_dev, double* H_dev, int64
  * lrvb_weighted_gram (S), lrvb_group_sums, lrvb_grouped_stats ([S | group sums]), lrvb_mixture_rows /
  * lrvb_mixture_stats ([S64 | val2 | count of indefinite rows | packed Schur operand]: every rank fails together when
  * any rank has an indefinite row), lrvb_quadform_gram ([K4 tiles | s | observation count]) and
- * lrvb_logitnormal_terms ([Hessian blocks | gradient | value], the part that was asked for).  A call must therefore
+ * lrvb_logitnormal_terms ([Hessian blocks | gradient | value], the part that was asked for), lrvb_glmm_terms
+ * ([Hessian blocks | group sums | gradient | value]).  A call must therefore
  * be made by ALL ranks, with the same arguments apart from the rows they hold.  lrvb_hessian_partial_dev and the
  * per-observation row outputs (lrvb_obs_*, the gradient rows of lrvb_mixture_rows) stay rank-local by contract.
  * fn == NULL removes the hook.                                                                                */

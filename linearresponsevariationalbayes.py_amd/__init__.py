@@ -47,6 +47,7 @@ from .mixture import MixtureObjective
 from .logitnormal import LogitNormalRegressionObjective
 from .logitnormal_mvn import LogitNormalMVNRegressionObjective
 from .softmax import SoftmaxRegressionObjective
+from .glmm import LogisticGLMMObjective
 from .torch_closure import TorchObjective
 from . import regression as regression_utils
 from . import packing as ProjectionParams

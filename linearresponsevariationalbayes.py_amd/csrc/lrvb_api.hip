@@ -1624,6 +1624,7 @@ extern "C" int lrvb_set_groups(lrvb_ctx* c, const int32_t* gid, int64_t n, int64
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->n_groups = n_groups;
     c->gstats_valid = false;
+    c->glmm_valid = false;
     c->zs_valid = false; c->ws_valid = false;
     return LRVB_OK;
 }
@@ -2458,6 +2459,106 @@ extern "C" int lrvb_logitnormal_terms(lrvb_ctx* c, const double* mean, const dou
     if (want_g) LRVB_TRY(d2h(c, grad_out, gred, (size_t)(2 * P)));
     if (want_H) LRVB_TRY(d2h(c, H_blocks_out, Hb, (size_t)(3 * P * P)));
     return LRVB_OK;
+}
+
+// ---- logistic mixed model with a random intercept (k_glmm.hip) ----------------------------------------------------------------
+// c->glmm: [H blocks (3 P^2) | group sums (G x (5 + 4 P)) | gradient (2 P) | value] -- every sum over observations of the call,
+// adjacent, so that the part that was formed goes through the reduce hook in one piece.  c->work1 holds the scratch:
+// [nodes 256 | m, v (2 up(P)) | e, r (2 up(G)) | five coefficient vectors (5 NP, original order, zero past N) | tile partials]
+extern "C" int lrvb_glmm_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc, const double* r_loc,
+                               int64_t G_in, const double* gh_x, const double* gh_w, int32_t n_nodes, double* value_out,
+                               double* grad_global_out, double* grad_local_out, double* H_blocks_out, double* border_out, double* local_out) {
+    LRVB_TRY(ctx_bind(c));
+    if (!mean || !var || !e_loc || !r_loc || !gh_x || !gh_w || !value_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    if (n_nodes < 1 || n_nodes > 128) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 128 quadrature nodes");
+    if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the logistic mixed model needs P <= 64 (got %lld)", (long long)c->P);
+    if (c->loss == LRVB_LOSS_NONE || c->data_only || !(c->have_X && c->have_y))
+        LRVB_FAIL(LRVB_ERR_STATE, "the context needs a design matrix and responses: lrvb_set_data for LRVB_SLOT_X and LRVB_SLOT_Y");
+    if (c->n_groups <= 0) LRVB_FAIL(LRVB_ERR_STATE, "no groups: call lrvb_set_groups first");
+    const i64 N = c->N, P = c->P, G = c->n_groups, ncol = 5 + 4 * P;
+    LRVB_TRY(check_len(P_in, P, "mean / var"));
+    LRVB_TRY(check_len(G_in, G, "e / r"));
+    for (i64 j = 0; j < P; ++j) if (!(var[j] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "var[%lld] is not positive", (long long)j);
+    for (i64 g = 0; g < G; ++g) if (!(r_loc[g] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "r[%lld] is not positive", (long long)g);
+    c->glmm_valid = false;
+    const bool want_g = grad_global_out != nullptr, want_H = H_blocks_out != nullptr;
+    DevBuf& X2 = c->mx_Xk;
+    if ((want_g || want_H) && (!c->x2_ready || X2.n < (size_t)(N * P))) {
+        LRVB_TRY(buf_reserve(c, X2, (size_t)(N * P)));
+        EW(square_kernel, N * P, (const double*)c->X.p, X2.p);
+        c->x2_ready = true;
+    }
+    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
+    const i64 NP = up(N + 64), n_tiles = glmm_num_tiles(N);
+    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(256 + 2 * up(P) + 2 * up(G) + 5 * NP + n_tiles * 2 * ncol + n_tiles)));
+    LRVB_TRY(buf_reserve(c, c->glmm, (size_t)(3 * P * P + G * ncol + 2 * P + 1)));
+    double* g = c->work1.p; double* dm = g + 256; double* dv = dm + up(P); double* de = dv + up(P); double* dr = de + up(G);
+    double* coef = dr + up(G); double* part = coef + 5 * NP; double* vpart = part + n_tiles * 2 * ncol;
+    double* Hb = c->glmm.p; double* gsum = Hb + 3 * P * P; double* gred = gsum + G * ncol; double* vred = gred + 2 * P;
+    LRVB_TRY(h2d(c, g, gh_x, (size_t)n_nodes));
+    LRVB_TRY(h2d(c, g + 128, gh_w, (size_t)n_nodes));
+    LRVB_TRY(h2d(c, dm, mean, (size_t)P));
+    LRVB_TRY(h2d(c, dv, var, (size_t)P));
+    LRVB_TRY(h2d(c, de, e_loc, (size_t)G));
+    LRVB_TRY(h2d(c, dr, r_loc, (size_t)G));
+    HIP_TRY(hipMemsetAsync(coef, 0, (size_t)(5 * NP) * sizeof(double), c->stream));
+    HIP_TRY(hipMemsetAsync(gsum, 0, (size_t)(G * ncol + 2 * P + 1) * sizeof(double), c->stream));
+    LRVB_TRY(launch_glmm_rows(c, dm, dv, de, dr, g, g + 128, (int)n_nodes, coef, NP, gsum, part, vpart));
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, c->stream, (const double*)vpart, n_tiles, vred);
+    HIP_TRY(hipGetLastError());
+    if (want_g) {
+        LRVB_TRY(launch_gemv(c, true, N, P, 1.0, c->X.p, P, coef, 0.0, gred));
+        LRVB_TRY(launch_gemv(c, true, N, P, 1.0, X2.p, P, coef + NP, 0.0, gred + P));
+    }
+    if (want_H) {
+        LRVB_TRY(weighted_tn(c, c->X.p, c->X.p, P, N, coef + 2 * NP, Hb, c->mx_A));
+        LRVB_TRY(weighted_tn(c, c->X.p, X2.p, P, N, coef + 3 * NP, Hb + P * P, c->mx_A));
+        LRVB_TRY(weighted_tn(c, X2.p, X2.p, P, N, coef + 4 * NP, Hb + 2 * P * P, c->mx_A));
+    }
+    double* first = want_H ? Hb : gsum;
+    LRVB_TRY(obs_reduce(c, first, (i64)(vred + 1 - first)));
+    c->glmm_valid = true;
+    LRVB_TRY(d2h(c, value_out, vred, 1));
+    if (want_g) LRVB_TRY(d2h(c, grad_global_out, gred, (size_t)(2 * P)));
+    if (want_H) LRVB_TRY(d2h(c, H_blocks_out, Hb, (size_t)(3 * P * P)));
+    if (grad_local_out || border_out || local_out) {
+        std::vector<double> host((size_t)(G * ncol));
+        LRVB_TRY(d2h(c, host.data(), gsum, host.size()));
+        for (i64 gi = 0; gi < G; ++gi) {
+            const double* row = host.data() + gi * ncol;
+            if (grad_local_out) { grad_local_out[2 * gi] = row[0]; grad_local_out[2 * gi + 1] = row[1]; }
+            if (local_out) { local_out[3 * gi] = row[2]; local_out[3 * gi + 1] = row[3]; local_out[3 * gi + 2] = row[4]; }
+            if (border_out) memcpy(border_out + gi * 4 * P, row + 5, (size_t)(4 * P) * sizeof(double));
+        }
+    }
+    return LRVB_OK;
+}
+
+extern "C" int lrvb_glmm_schur(lrvb_ctx* c, const double* local_2x2, const double* border_scale, const double* closed_rows, int64_t G_in,
+                               double* M_out) {
+    LRVB_TRY(ctx_bind(c));
+    if (!local_2x2 || !border_scale || !closed_rows || !M_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    if (c->n_groups <= 0 || !c->glmm_valid) LRVB_FAIL(LRVB_ERR_STATE, "no group sums resident: call lrvb_glmm_terms first");
+    const i64 P = c->P, G = c->n_groups, ncol = 5 + 4 * P, R = 2 * P + 3;
+    LRVB_TRY(check_len(G_in, G, "local blocks"));
+    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
+    const int ldu = (int)up(R);
+    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(8 + up(3 * G) + up(2 * G) + up(6 * G) + 2 * G * ldu + R * R)));
+    double* flag = c->work1.p; double* loc = flag + 8; double* sc = loc + up(3 * G); double* cl = sc + up(2 * G);
+    double* U = cl + up(6 * G); double* Md = U + 2 * G * ldu;
+    LRVB_TRY(h2d(c, loc, local_2x2, (size_t)(3 * G)));
+    LRVB_TRY(h2d(c, sc, border_scale, (size_t)(2 * G)));
+    LRVB_TRY(h2d(c, cl, closed_rows, (size_t)(6 * G)));
+    HIP_TRY(hipMemsetAsync(flag, 0, sizeof(double), c->stream));
+    const double* gsum = c->glmm.p + 3 * P * P;
+    LRVB_TRY(launch_glmm_schur_rows(c, gsum, loc, sc, cl, U, ldu, reinterpret_cast<int*>(flag)));
+    LRVB_TRY(launch_gemm(c, true, false, R, R, 2 * G, 1.0, U, ldu, U, ldu, 0.0, Md, R));
+    double fh = 0.0;
+    LRVB_TRY(d2h(c, &fh, flag, 1));
+    int bad = 0;
+    memcpy(&bad, &fh, sizeof(int));
+    if (bad) LRVB_FAIL(LRVB_ERR_NOT_POSDEF, "a 2 x 2 local block of the logistic mixed model is not positive definite");
+    return d2h(c, M_out, Md, (size_t)(R * R));
 }
 
 // ---- logistic regression with a full-covariance Gaussian posterior q(beta) = N(m, Sigma) ----------------------------------

@@ -126,6 +126,7 @@ struct lrvb_ctx {
         bool p_valid = false; std::vector<double> p_beta;
     } sm;
     DevBuf lmvn;                   // lrvb_logitnormal_mvn_*: parameters, row pass, per-observation coefficients
+    DevBuf glmm; bool glmm_valid = false;   // lrvb_glmm_terms: [H blocks (3 P^2) | group sums (G x (5 + 4 P)) | gradient (2 P) | value], summed over ranks; the group sums stay resident for lrvb_glmm_schur
     DevBuf opt;                    // trust-region Newton-CG: 12 D-vectors (+ the D x D preconditioner)
     DevBuf cgm[9];                 // blocked CG: B, X, R, P, Q, Z (Q x D), U, W (Q x V), R^T (P x Q)
     DevBuf cgT;                    // N x Q products X U^T of the blocked HVP
@@ -218,6 +219,14 @@ int  launch_softmax_influence_contract(lrvb_ctx* c, i64 n0, i64 rows, int G, int
 // k_logitmvn.hip (P = n_cols <= 64)
 int  launch_lmvn_rowpass(lrvb_ctx* c, const double* A, const double* b, double* r, double* t);   // r_n = x_n^T A x_n, t_n = x_n . b
 int  launch_lmvn_cross(lrvb_ctx* c, const double* cvec, double* H, i64 ld);    // H[a, P + v] = H[P + v, a] = delta_v (X^T diag(c) U)[a, v]
+
+// k_glmm.hip (P = n_cols <= 64; groups set)
+i64  glmm_num_tiles(i64 N);               // tiles of the rows pass: `part` holds 2 (5 + 4 P) doubles per tile, `vpart` one
+int  launch_glmm_rows(lrvb_ctx* c, const double* m, const double* vb, const double* eg, const double* rg, const double* gx,
+                      const double* gw, int K, double* coef /* 5 x NP, original row order */, i64 NP,
+                      double* gsum /* G x (5 + 4 P), zeroed by the caller */, double* part, double* vpart);
+int  launch_glmm_schur_rows(lrvb_ctx* c, const double* gsum, const double* loc, const double* scale, const double* closed,
+                            double* U /* 2 G x ldu */, int ldu, int* bad);
 
 // k_lmm.hip
 struct LmmIdx { int p, ms, ls, iem, iim, iay, iby, iam, ibm; i64 ld; };    // vector-coordinate positions of the global parameters

@@ -322,6 +322,37 @@ class DeviceContext(object):
                                                     _hip.ptr(val), _hip.ptr(g), _hip.ptr(Hb)))
         return float(val[0]), g, (None if Hb is None else (Hb[0], Hb[1], Hb[2]))
 
+    def glmm_terms(self, mean, var, e, r, gh_x, gh_w, want_grad=True, want_hess=True, want_border=True):
+        """Data term of the logistic mixed model in the coordinates (mean, var, e, r) (lrvb_glmm_terms): value, global gradient
+        (2 P), local gradient (G x 2), the Hessian blocks (3 x P x P), the border (G x 4 P) and the local sums (G x 3).  The group
+        sums stay resident for `glmm_schur`; want_border=False leaves the border there and returns None for it."""
+        m, v = _hip.as_f64(mean).ravel(), _hip.as_f64(var).ravel()
+        e, r = _hip.as_f64(e).ravel(), _hip.as_f64(r).ravel()
+        gx, gw = _hip.as_f64(gh_x).ravel(), _hip.as_f64(gh_w).ravel()
+        P, G = self.n_cols, e.size
+        if m.size != P or v.size != P or r.size != G or gx.size != gw.size:
+            raise ValueError('expected mean and var of length {}, e and r of one length and as many weights as nodes'.format(P))
+        val = np.empty(1)
+        gg = np.empty(2 * P) if want_grad else None
+        gl = np.empty((G, 2)) if want_grad else None
+        Hb = np.empty((3, P, P)) if want_hess else None
+        B = np.empty((G, 4 * P)) if (want_hess and want_border) else None
+        L = np.empty((G, 3)) if want_hess else None
+        self._check(self._lib.lrvb_glmm_terms(self._h, _hip.ptr(m), _hip.ptr(v), P, _hip.ptr(e), _hip.ptr(r), G, _hip.ptr(gx), _hip.ptr(gw),
+                                             gx.size, _hip.ptr(val), _hip.ptr(gg), _hip.ptr(gl), _hip.ptr(Hb), _hip.ptr(B), _hip.ptr(L)))
+        return float(val[0]), gg, gl, Hb, B, L
+
+    def glmm_schur(self, local_2x2, border_scale, closed_rows):
+        """M ((2 P + 3)^2) = sum_g C_g^T A_g^-1 C_g from the resident group sums of the last `glmm_terms` (lrvb_glmm_schur)."""
+        A, sc, cl = _hip.as_f64(local_2x2), _hip.as_f64(border_scale), _hip.as_f64(closed_rows)
+        G = A.shape[0]
+        if A.shape != (G, 3) or sc.shape != (G, 2) or cl.shape != (G, 6):
+            raise ValueError('expected G x 3 local blocks, G x 2 chain factors and G x 6 closed-form rows')
+        R = 2 * self.n_cols + 3
+        M = np.empty((R, R))
+        self._check(self._lib.lrvb_glmm_schur(self._h, _hip.ptr(A), _hip.ptr(sc), _hip.ptr(cl), G, _hip.ptr(M)))
+        return M
+
     # ---- multinomial (softmax) regression: beta is (K - 1) x n_cols, D = (K - 1) n_cols (lrvb_softmax_*) --------------------
     def softmax_set_labels(self, labels, n_classes):
         y = np.ascontiguousarray(np.asarray(labels).ravel(), dtype=np.int32)

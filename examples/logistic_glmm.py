@@ -3,8 +3,9 @@
     y_n ~ Bernoulli(sigma(x_n . beta + u_g(n))),  u_g ~ N(mu, 1 / tau)
 
 Simulates data, fits the mean-field posterior with scipy's trust-ncg on the arrow products, prints the LRVB standard errors of
-beta, mu and log tau (through the Schur complement of the arrow Hessian) next to the mean-field ones, predicts a refit under
-a changed prior on tau by linear response and compares with the refit, and prints wall times.
+beta, mu and log tau (through the Schur complement of the arrow Hessian) next to the mean-field ones, ranks the groups by their
+influence on one coefficient (streamed on the device), drops the top group, refits and prints the predicted change next to the
+actual one, predicts a refit under a changed prior on tau by linear response and compares with the refit, and prints wall times.
 
     python examples/logistic_glmm.py [--small]
 """
@@ -98,6 +99,23 @@ def main():
     print('%-10s %12s %12s' % ('', 'mean-field se', 'LRVB se'))
     for k in list(range(min(P, 4))) + [P, P + 1]:
         print('%-10s %12.5f %12.5f' % (names[k], se_mf[k], se_lr[k]))
+
+    # leave one cluster out: groups ranked by their streamed influence on beta[0], the top one dropped and refitted
+    Mb = np.zeros((1, ng))
+    Mb[0, 0] = 1.0
+    t0 = time.perf_counter()
+    gi = fun.group_influence(th, Mb)[:, 0]                               # d beta[0] / d (multiplier on the group's weights)
+    t_gi = time.perf_counter() - t0
+    top = np.argsort(-np.abs(gi))[:5]
+    print('group influence on beta[0] (%.3f s): top groups %s, influence %s' % (t_gi, top.tolist(), np.array2string(gi[top], precision=5)))
+    g = int(top[0])
+    w = np.ones(N)
+    w[gid == g] = 0.0
+    fun.weights_par.set_vector(w)
+    th_drop = fit(objective, fun, th)
+    fun.weights_par.set_vector(np.ones(N))
+    print('drop group %d (%d rows): beta[0] predicted change %.4e, actual change %.4e'
+          % (g, int(np.sum(gid == g)), -gi[g], th_drop[0] - th[0]))
 
     # a changed prior on tau: linear-response prediction against the refit
     hp = fun.tau_prior_par

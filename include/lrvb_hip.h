@@ -371,6 +371,39 @@ int lrvb_glmm_terms(lrvb_ctx* ctx, const double* mean, const double* var, int64_
 int lrvb_glmm_schur(lrvb_ctx* ctx, const double* local_2x2, const double* border_scale, const double* closed_rows, int64_t G,
                     double* M_out);
 
+/* Streamed weight influence of the logistic mixed model.  Point arguments as lrvb_glmm_terms.  Per observation, PER UNIT WEIGHT,
+ *   a1' = psi_rho(rho_n, s_n) - y_n,   a2' = psi_s(rho_n, s_n)
+ * and the gradient of row n's term in (mean, var, e, r) is [a1' x_n | a2' x_n o x_n | at g(n): a1', a2'].  For an operand A
+ * (Q x (2 P + 2 G), columns [A_m | A_v | A_e | A_r]) given as
+ *   A_global (Q x 2 P, row-major: row q = [A_m[q] | A_v[q]])   and
+ *   A_local  (G x 2 Q, row-major: row g = [A_e[0..Q-1, g] | A_r[0..Q-1, g]] -- one contiguous read per observation)
+ * the entry writes, for n0 <= n < n1,
+ *   out[n - n0][q] = a1' (x_n . A_m[q] + A_e[q, g(n)]) + a2' ((x_n o x_n) . A_v[q] + A_r[q, g(n)])        ((n1 - n0) x Q, host)
+ * i.e. A times column n of the weight cross Hessian, which is never formed.  The weights do not enter: a row of weight zero
+ * gets the influence of adding it.  ONE pass over the rows of the window in their original order for any Q >= 1: a tile of 64
+ * rows is staged on chip, the quadrature (two of the five derivative sums of lrvb_glmm_terms) is done once per row, and the
+ * two contractions run on the fp64 matrix cores in blocks of 16 outputs inside the tile (x o x is formed on chip).  A window
+ * equals the same rows of the full result bitwise.  Per-observation rows: rank-local, NO reduce-hook call.
+ * Memory: nothing is chunked inside the call.  The device holds the (n1 - n0) x Q result and the G x 2 Q operand in one piece
+ * each, so "any Q" is bounded by (n1 - n0) Q + 2 G Q doubles of free device memory (N = 1e6, G = 1e4, Q = 16: 128 MB + 2.6 MB;
+ * Q = D = 20132 needs 3.2 GB for A_local alone and 161 GB for all rows at once): a caller with a wide operand walks row
+ * windows, and one whose A_local does not fit walks blocks of outputs.  A device allocation that fails is LRVB_ERR_HIP.
+ * Errors as lrvb_glmm_terms (P > 64 or more than 128 nodes: LRVB_ERR_UNSUPPORTED; groups, X or y not set: LRVB_ERR_STATE;
+ * var_j <= 0 or r_g <= 0: LRVB_ERR_INVALID); n0 > n1 or n1 > n_obs: LRVB_ERR_INVALID, as lrvb_obs_influence.                */
+int lrvb_glmm_obs_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                            int64_t G, const double* gh_x, const double* gh_w, int32_t n_nodes, const double* A_global,
+                            const double* A_local, int64_t Q, int64_t n0, int64_t n1, double* out);
+/* Group influence: out[g][q] = sum over the rows n of group g of w_n * (the row of lrvb_glmm_obs_influence)   (G x Q, host) --
+ * the derivative with respect to a common multiplier on the weights of group g's rows (leave one cluster out).  The group's
+ * own prior term on u_g is NOT part of it.  One pass over the group-sorted rows forms, per group and in a fixed order (no
+ * atomics: two calls at one point are bitwise equal), [sum w a1', sum w a2' | sum w a1' x | sum w a2' x o x] (2 + 2 P numbers);
+ * the contraction with A is a (G x 2 P)(2 P x Q) product and does not touch the observations again.  An empty group gives a
+ * zero row.  Reduce hook: the G x Q result is a sum over observations (a group may straddle ranks) and goes through the hook
+ * exactly once, as one buffer of G Q doubles.  Errors as lrvb_glmm_obs_influence.                                          */
+int lrvb_glmm_group_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                              int64_t G, const double* gh_x, const double* gh_w, int32_t n_nodes, const double* A_global,
+                              const double* A_local, int64_t Q, double* out);
+
 /* ---- multinomial (softmax) regression ---------------------------------------------------------
  * K classes (2 <= K <= 17), labels y_n in {0 .. K-1}, class 0 the reference; coefficients beta ((K-1) x P, row-major, row a
  * belongs to class a + 1, P = n_cols <= 1024), z_na = x_n . beta_a, z_n0 = 0, p_n = softmax(z_n).  The data term
@@ -582,7 +615,7 @@ int lrvb_hessian_dev(lrvb_ctx* ctx, const double* free_dev, double* H_dev, int64
  * lrvb_mixture_stats ([S64 | val2 | count of indefinite rows | packed Schur operand]: every rank fails together when
  * any rank has an indefinite row), lrvb_quadform_gram ([K4 tiles | s | observation count]) and
  * lrvb_logitnormal_terms ([Hessian blocks | gradient | value], the part that was asked for), lrvb_glmm_terms
- * ([Hessian blocks | group sums | gradient | value]).  A call must therefore
+ * ([Hessian blocks | group sums | gradient | value]) and lrvb_glmm_group_influence (the G x Q result).  A call must therefore
  * be made by ALL ranks, with the same arguments apart from the rows they hold.  lrvb_hessian_partial_dev and the
  * per-observation row outputs (lrvb_obs_*, the gradient rows of lrvb_mixture_rows) stay rank-local by contract.
  * fn == NULL removes the hook.                                                                                */

@@ -208,3 +208,249 @@ int launch_glmm_schur_rows(lrvb_ctx* c, const double* gsum, const double* loc, c
     HIP_TRY(hipGetLastError());
     return LRVB_OK;
 }
+
+// ---- streamed weight influence (lrvb_glmm_obs_influence) ----------------------------------------------------------------------
+// out[n - n0][q] = a1' (x_n . A_m[q] + A_e[q, g(n)]) + a2' ((x_n o x_n) . A_v[q] + A_r[q, g(n)]),  a1' = psi_rho - y_n, a2' = psi_s
+// PER UNIT WEIGHT (w_n does not enter: a row of weight zero gets the influence of adding it).  ONE pass over the rows n0..n1 in
+// their original order, X read once for any Q.  A workgroup (4 waves) walks tiles of GL_T = 64 rows:
+//   1. the tile (contiguous in X) is staged in LDS, row stride GI_XS; the columns P .. 4 ceil(P / 4) hold zeros;
+//   2. four lanes share a row for the two dot products and the quadrature, as in glmm_rows_kernel, but only the two sums E g1
+//      and E g2 are formed (no value, no second derivatives), and a1', a2' go to LDS;
+//   3. wave w owns the rows 16 w .. 16 w + 15 of the tile.  Per block of 16 outputs it runs the two contractions
+//      X A_m^T and (X o X) A_v^T as 16 x 16 x 4 fp64 MFMA tiles (A operand: lane (i = l & 15, k = l >> 4) reads one staged x and
+//      squares it in a register -- X o X is never read from memory; B operand: A_global, zero past Q and past P), two
+//      accumulator chains each, then combines them with a1', a2' and the gathered 2 Q-row of A_local in the D layout
+//      (register r <-> row (l >> 4) + 4 r, column l & 15) and writes 16 consecutive doubles per row.
+// With Q <= 16 the B fragments are loaded once per workgroup and stay in registers; with more outputs the blocks of 16 are a
+// loop INSIDE the tile (the quadrature is shared, the fragments come from L2).  No atomics, no group walk.
+constexpr int GI_XS = 66;                // LDS row stride: lanes (i, k) of an MFMA operand read banks 2 i + k
+
+typedef double gi_d4 __attribute__((ext_vector_type(4)));
+
+// The per-row part both influence kernels share (glmm_rows_kernel keeps its own five-sum loop): four lanes share the staged row
+// xr -- each a quarter of the two dot products, then a quarter of the nodes -- and every one of them returns e1 = psi_rho and
+// e2 = E g2 = 2 psi_s of group g's row.  Called by all lanes (xor shuffles); a lane whose row is not live returns zeros.
+__device__ __forceinline__ void gi_psi_derivs(const double* xr, bool live, int g, int q4, int P, int K, const double* ms,
+                                              const double* vs, const double* __restrict__ eg, const double* __restrict__ rg,
+                                              const double* sx, const double* sw, double& e1, double& e2)
+{
+    double rho = 0.0, s = 0.0;
+    if (live) for (int j = q4; j < P; j += 4) { const double x = xr[j]; rho += x * ms[j]; s += x * x * vs[j]; }
+    rho += __shfl_xor(rho, 1); s += __shfl_xor(s, 1);
+    rho += __shfl_xor(rho, 2); s += __shfl_xor(s, 2);
+    e1 = 0.0; e2 = 0.0;
+    if (live) {
+        rho += eg[g]; s += rg[g];
+        const double sd = sqrt(fmax(s, 0.0));
+        for (int k = q4; k < K; k += 4) {
+            const double t = rho + sd * sx[k], wk = sw[k];
+            const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
+            const double sg = t >= 0.0 ? ie : e * ie;
+            e1 += wk * sg; e2 += wk * e * ie * ie;
+        }
+    }
+    e1 += __shfl_xor(e1, 1); e2 += __shfl_xor(e2, 1);
+    e1 += __shfl_xor(e1, 2); e2 += __shfl_xor(e2, 2);
+}
+
+__global__ __launch_bounds__(256)
+void glmm_infl_rows_kernel(i64 n0, i64 R /* rows of the window */, int P, const double* __restrict__ X, const double* __restrict__ y,
+                           const int* __restrict__ gid, const double* __restrict__ m, const double* __restrict__ vb,
+                           const double* __restrict__ eg, const double* __restrict__ rg, const double* __restrict__ gx,
+                           const double* __restrict__ gw, int K, const double* __restrict__ Ag /* Q x 2 P */,
+                           const double* __restrict__ Al /* G x 2 Q */, int Q, double* __restrict__ out /* R x Q */)
+{
+    __shared__ double xs[GL_T * GI_XS], a1s[GL_T], a2s[GL_T], ms[64], vs[64], sx[128], sw[128];
+    __shared__ int s_gid[GL_T];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, l4 = lane >> 4;
+    const double r2 = 1.4142135623730951, ispi = 0.5641895835477563;     // sqrt(2), 1 / sqrt(pi)
+    if (tid < K) { sx[tid] = r2 * gx[tid]; sw[tid] = ispi * gw[tid]; }
+    if (tid < 64) { ms[tid] = tid < P ? m[tid] : 0.0; vs[tid] = tid < P ? vb[tid] : 0.0; }
+    for (int e = tid; e < GL_T * GI_XS; e += 256) xs[e] = 0.0;           // the padding columns stay zero for the whole kernel
+    const int KS = (P + 3) >> 2;                                         // k-steps of the contractions
+    const int nqb = (Q + 15) >> 4;
+    double bm[16], bv[16];
+    auto load_b = [&](int qb) {
+        const int q = 16 * qb + l15;
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk) {
+            const int k = 4 * kk + l4;
+            const bool ok = q < Q && k < P;
+            bm[kk] = ok ? Ag[(i64)q * 2 * P + k] : 0.0;
+            bv[kk] = ok ? Ag[(i64)q * 2 * P + P + k] : 0.0;
+        }
+    };
+    if (nqb == 1) load_b(0);
+    const i64 n_tiles = (R + GL_T - 1) / GL_T;
+    const int row = tid >> 2, q4 = tid & 3;
+    for (i64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const i64 t0 = tile * GL_T;
+        const int rows = (int)(R - t0 < GL_T ? R - t0 : GL_T);
+        __syncthreads();                                                 // the previous tile is consumed (and the nodes are in place)
+        if (tid < GL_T) s_gid[tid] = tid < rows ? gid[n0 + t0 + tid] : 0;
+        {
+            const double* src = X + (n0 + t0) * (i64)P;
+            for (int e = tid; e < rows * P; e += 256) { const int rr = e / P, cc = e - rr * P; xs[rr * GI_XS + cc] = src[e]; }
+        }
+        __syncthreads();
+        double e1, e2;
+        gi_psi_derivs(xs + row * GI_XS, row < rows, s_gid[row], q4, P, K, ms, vs, eg, rg, sx, sw, e1, e2);
+        if (q4 == 0) {
+            double k1 = 0.0, k2 = 0.0;
+            if (row < rows) { k1 = e1 - y[n0 + t0 + row]; k2 = 0.5 * e2; }
+            a1s[row] = k1; a2s[row] = k2;
+        }
+        __syncthreads();
+        // the two contractions of this wave's 16 rows
+        const double* xa = xs + (16 * wave + l15) * GI_XS + l4;
+        for (int qb = 0; qb < nqb; ++qb) {
+            if (nqb > 1) load_b(qb);
+            gi_d4 am0 = {0.0, 0.0, 0.0, 0.0}, am1 = am0, av0 = am0, av1 = am0;
+#pragma unroll
+            for (int kk = 0; kk < 16; kk += 2) {
+                if (kk < KS) {
+                    const double x = xa[4 * kk];
+                    am0 = __builtin_amdgcn_mfma_f64_16x16x4f64(x, bm[kk], am0, 0, 0, 0);
+                    av0 = __builtin_amdgcn_mfma_f64_16x16x4f64(x * x, bv[kk], av0, 0, 0, 0);
+                }
+                if (kk + 1 < KS) {
+                    const double x = xa[4 * kk + 4];
+                    am1 = __builtin_amdgcn_mfma_f64_16x16x4f64(x, bm[kk + 1], am1, 0, 0, 0);
+                    av1 = __builtin_amdgcn_mfma_f64_16x16x4f64(x * x, bv[kk + 1], av1, 0, 0, 0);
+                }
+            }
+            const int q = 16 * qb + l15;
+            if (q < Q) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int rr = 16 * wave + l4 + 4 * r;
+                    if (rr < rows) {
+                        const double* al = Al + (i64)s_gid[rr] * 2 * Q;
+                        out[(t0 + rr) * (i64)Q + q] = a1s[rr] * ((am0[r] + am1[r]) + al[q]) + a2s[rr] * ((av0[r] + av1[r]) + al[Q + q]);
+                    }
+                }
+            }
+        }
+    }
+}
+
+int launch_glmm_infl_rows(lrvb_ctx* c, i64 n0, i64 n1, const int* gid, const double* m, const double* vb, const double* eg,
+                          const double* rg, const double* gx, const double* gw, int K, const double* Ag, const double* Al, i64 Q,
+                          double* out) {
+    if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "logistic mixed model: P <= 64");
+    const i64 R = n1 - n0;
+    if (R <= 0) return LRVB_OK;
+    const i64 n_tiles = (R + GL_T - 1) / GL_T;
+    const unsigned grid = (unsigned)(n_tiles < 2048 ? n_tiles : 2048);
+    hipLaunchKernelGGL(glmm_infl_rows_kernel, dim3(grid), dim3(256), 0, c->stream, n0, R, (int)c->P, (const double*)c->X.p,
+                       (const double*)c->y.p, gid, m, vb, eg, rg, gx, gw, K, Ag, Al, (int)Q, out);
+    HIP_TRY(hipGetLastError());
+    return LRVB_OK;
+}
+
+// ---- group influence (lrvb_glmm_group_influence) ------------------------------------------------------------------------------
+// Per group the WEIGHTED sums  [sum a1, sum a2 | sum a1 x (P) | sum a2 x o x (P)],  a1 = w (psi_rho - y), a2 = w psi_s  (2 + 2 P
+// columns), by the pass of glmm_rows_kernel cut down to them: group-sorted rows, two quadrature sums, the same in-order walk of
+// the tile with the pieces of a cut group in the tile's two partial rows, added by glmm_fixup_kernel in tile order.  The
+// contraction with the operand is N-independent: a (G x 2 P) (2 P x Q) product on the library's GEMM and glmm_infl_local_kernel
+// for the two local columns.  Fixed order everywhere, no atomics.
+__global__ __launch_bounds__(256)
+void glmm_infl_gsum_kernel(i64 N, int P, i64 G, const double* __restrict__ X, const double* __restrict__ y, const double* __restrict__ w,
+                           const i64* __restrict__ perm, const i64* __restrict__ offs, const double* __restrict__ m,
+                           const double* __restrict__ vb, const double* __restrict__ eg, const double* __restrict__ rg,
+                           const double* __restrict__ gx, const double* __restrict__ gw, int K, double* __restrict__ gsum,
+                           double* __restrict__ part)
+{
+    __shared__ double xs[GL_T * GL_XS], cf[2 * GL_T], ms[64], vs[64], sx[128], sw[128];
+    __shared__ i64 s_row[GL_T];
+    __shared__ int s_gid[GL_T], s_whole[GL_T];
+    const int tid = threadIdx.x;
+    const int ncol = 2 + 2 * P;
+    const double r2 = 1.4142135623730951, ispi = 0.5641895835477563;
+    if (tid < K) { sx[tid] = r2 * gx[tid]; sw[tid] = ispi * gw[tid]; }
+    if (tid < P) { ms[tid] = m[tid]; vs[tid] = vb[tid]; }
+    const i64 n_tiles = (N + GL_T - 1) / GL_T;
+    const int row = tid >> 2, q4 = tid & 3;
+    const bool has_col = tid < 2 * P;                                    // output column 2 + tid; threads 0, 1 also a scalar column
+    const bool sq = tid >= P;
+    const int jc = sq ? tid - P : tid;
+    for (i64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const i64 t0 = tile * GL_T;
+        const int rows = (int)(N - t0 < GL_T ? N - t0 : GL_T);
+        __syncthreads();
+        if (tid < GL_T) {
+            int g = 0, whole = 0;
+            i64 pr = 0;
+            if (tid < rows) {
+                const i64 i = t0 + tid;
+                pr = perm[i];
+                i64 lo = 0, hi = G;                                      // the last g with offs[g] <= i (its offs[g + 1] > i)
+                while (hi - lo > 1) { const i64 mid = (lo + hi) >> 1; if (offs[mid] <= i) lo = mid; else hi = mid; }
+                g = (int)lo;
+                whole = (offs[lo] >= t0 && offs[lo + 1] <= t0 + GL_T) ? 1 : 0;
+            }
+            s_row[tid] = pr; s_gid[tid] = g; s_whole[tid] = whole;
+        }
+        __syncthreads();
+        for (int e = tid; e < rows * P; e += 256) { const int rr = e / P, cc = e - rr * P; xs[rr * GL_XS + cc] = X[s_row[rr] * P + cc]; }
+        __syncthreads();
+        double e1, e2;
+        gi_psi_derivs(xs + row * GL_XS, row < rows, s_gid[row], q4, P, K, ms, vs, eg, rg, sx, sw, e1, e2);
+        if (q4 == 0) {
+            double k1 = 0.0, k2 = 0.0;
+            if (row < rows) { const i64 pr = s_row[row]; const double wi = w[pr]; k1 = wi * (e1 - y[pr]); k2 = wi * 0.5 * e2; }
+            cf[row] = k1; cf[GL_T + row] = k2;
+        }
+        __syncthreads();
+        if (has_col || tid < 2) {
+            double acc = 0.0, accs = 0.0;
+            int run_start = 0;
+            for (int rr = 0; rr < rows; ++rr) {
+                if (has_col) { double x = xs[rr * GL_XS + jc]; if (sq) x *= x; acc += cf[(sq ? GL_T : 0) + rr] * x; }
+                if (tid < 2) accs += cf[tid * GL_T + rr];
+                const int g = s_gid[rr];
+                if (rr == rows - 1 || s_gid[rr + 1] != g) {
+                    double* dst = s_whole[rr] ? gsum + (i64)g * ncol : part + (tile * 2 + (run_start == 0 ? 0 : 1)) * ncol;
+                    if (has_col) dst[2 + tid] = acc;
+                    if (tid < 2) dst[tid] = accs;
+                    acc = 0.0; accs = 0.0; run_start = rr + 1;
+                }
+            }
+        }
+    }
+}
+
+// out[g][q] += S[g][0] A_e[q, g] + S[g][1] A_r[q, g]   (S: the group sums, leading dimension ncol; A_local: G x 2 Q)
+__global__ __launch_bounds__(256)
+void glmm_infl_local_kernel(i64 G, int Q, int ncol, const double* __restrict__ S, const double* __restrict__ Al, double* __restrict__ out)
+{
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= G * Q) return;
+    const i64 g = i / Q;
+    const int q = (int)(i - g * Q);
+    out[i] += S[g * ncol] * Al[g * 2 * Q + q] + S[g * ncol + 1] * Al[g * 2 * Q + Q + q];
+}
+
+int launch_glmm_infl_gsum(lrvb_ctx* c, const double* m, const double* vb, const double* eg, const double* rg, const double* gx,
+                          const double* gw, int K, double* gsum, double* part) {
+    const i64 N = c->N, G = c->n_groups;
+    if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "logistic mixed model: P <= 64");
+    const int ncol = 2 + 2 * (int)c->P;
+    const i64* gdev = reinterpret_cast<const i64*>(c->groups.p);
+    const i64 n_tiles = (N + GL_T - 1) / GL_T;
+    const unsigned grid = (unsigned)(n_tiles < 2048 ? (n_tiles < 1 ? 1 : n_tiles) : 2048);
+    hipLaunchKernelGGL(glmm_infl_gsum_kernel, dim3(grid), dim3(256), 0, c->stream, N, (int)c->P, G, (const double*)c->X.p,
+                       (const double*)c->y.p, (const double*)c->w.p, gdev, gdev + N, m, vb, eg, rg, gx, gw, K, gsum, part);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(glmm_fixup_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, G, ncol, gdev + N, (const double*)part, gsum);
+    HIP_TRY(hipGetLastError());
+    return LRVB_OK;
+}
+
+int launch_glmm_infl_local(lrvb_ctx* c, i64 Q, const double* S, const double* Al, double* out) {
+    const i64 G = c->n_groups, n = G * Q;
+    hipLaunchKernelGGL(glmm_infl_local_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, G, (int)Q,
+                       2 + 2 * (int)c->P, S, Al, out);
+    HIP_TRY(hipGetLastError());
+    return LRVB_OK;
+}

@@ -227,6 +227,13 @@ int  launch_glmm_rows(lrvb_ctx* c, const double* m, const double* vb, const doub
                       double* gsum /* G x (5 + 4 P), zeroed by the caller */, double* part, double* vpart);
 int  launch_glmm_schur_rows(lrvb_ctx* c, const double* gsum, const double* loc, const double* scale, const double* closed,
                             double* U /* 2 G x ldu */, int ldu, int* bad);
+int  launch_glmm_infl_rows(lrvb_ctx* c, i64 n0, i64 n1, const int* gid /* original row order */, const double* m, const double* vb,
+                           const double* eg, const double* rg, const double* gx, const double* gw, int K, const double* Ag /* Q x 2 P */,
+                           const double* Al /* G x 2 Q */, i64 Q, double* out /* (n1 - n0) x Q */);
+int  launch_glmm_infl_gsum(lrvb_ctx* c, const double* m, const double* vb, const double* eg, const double* rg, const double* gx,
+                           const double* gw, int K, double* gsum /* G x (2 + 2 P), zeroed by the caller */,
+                           double* part /* 2 (2 + 2 P) doubles per tile of glmm_num_tiles */);
+int  launch_glmm_infl_local(lrvb_ctx* c, i64 Q, const double* S, const double* Al, double* out /* G x Q, += */);
 
 // k_lmm.hip
 struct LmmIdx { int p, ms, ls, iem, iim, iay, iby, iam, ibm; i64 ld; };    // vector-coordinate positions of the global parameters

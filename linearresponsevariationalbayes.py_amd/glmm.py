@@ -21,6 +21,7 @@ blocks (NOT diagonal: psi_rho_s couples e_g and i_g) and a border of 2 P + 3 cou
 import numpy as np
 from scipy import special
 from scipy import sparse as sp_sparse
+from scipy import linalg as sp_linalg
 
 from . import _hip
 from .models import DeviceContext, DeclaredHypers, refuse_double_reduction
@@ -164,6 +165,37 @@ def arrow_local_solve(loc, be, bi):
     """A_g^-1 [be_g; bi_g] for every group."""
     det = loc[:, 0] * loc[:, 2] - loc[:, 1] ** 2
     return (loc[:, 2] * be - loc[:, 1] * bi) / det, (loc[:, 0] * bi - loc[:, 1] * be) / det
+
+
+def arrow_solve(Hgg, rows, Hx, loc, R, schur_solve=None):
+    """H^-1 R for the arrow (R: D x Q or a D-vector, D = n_global + 2 G) without the dense matrix: the G local 2 x 2 blocks are
+    solved, the result is reduced onto the coupled global rows, the Schur complement Hgg - `arrow_schur_term` is factored and
+    solved, and the local parameters are back-substituted -- O(P G Q + n_global^3).  `schur_solve` (n_global x Q -> n_global x Q)
+    replaces the host factorisation of the Schur complement, e.g. by the factor resident on the global context after
+    `global_hessian(..., want_host=False)` + `chol_factor_last`.  A local block or a Schur complement that is not positive
+    definite raises `np.linalg.LinAlgError`."""
+    ng, G = Hgg.shape[0], loc.shape[0]
+    R = np.asarray(R, dtype=np.float64)
+    vec = R.ndim == 1
+    R2 = R.reshape(ng + 2 * G, -1)
+    det = loc[:, 0] * loc[:, 2] - loc[:, 1] ** 2
+    if not (np.all(loc[:, 0] > 0) and np.all(det > 0)):
+        raise np.linalg.LinAlgError('a 2 x 2 local block is not positive definite')
+    i11, i12, i22 = (loc[:, 2] / det)[:, None], (-loc[:, 1] / det)[:, None], (loc[:, 0] / det)[:, None]
+    Rg, Re, Ri = R2[:ng], R2[ng:ng + G], R2[ng + G:]
+    te, ti = i11 * Re + i12 * Ri, i12 * Re + i22 * Ri                    # H_ll^-1 R_l
+    rhs = Rg.copy()
+    rhs[rows] -= Hx[:, :G] @ te + Hx[:, G:] @ ti
+    if schur_solve is None:
+        S = Hgg.copy()
+        S[np.ix_(rows, rows)] -= arrow_schur_term(rows, Hx, loc)
+        L = np.linalg.cholesky(0.5 * (S + S.T))                          # LinAlgError where it is not positive definite
+        xg = sp_linalg.cho_solve((L, True), rhs)
+    else:
+        xg = np.asarray(schur_solve(np.ascontiguousarray(rhs)), dtype=np.float64).reshape(ng, -1)
+    ce, ci = Hx[:, :G].T @ xg[rows], Hx[:, G:].T @ xg[rows]              # H_lg x_g
+    out = np.vstack([xg, te - (i11 * ce + i12 * ci), ti - (i12 * ce + i22 * ci)])
+    return out.ravel() if vec else out
 
 
 class LogisticGLMMObjective(DeclaredHypers):
@@ -405,7 +437,76 @@ class LogisticGLMMObjective(DeclaredHypers):
         gc = self._ensure_gctx()
         gc.hvec_begin()
         gc.hvec_add_block(Hgg, 0, 0)
-        return gc.hvec_finish(fv[:ng], g[:ng], True, want_host=want_host)
+        out = gc.hvec_finish(fv[:ng], g[:ng], True, want_host=want_host)
+        self._schur_key = self._resident_key(fv)
+        return out
+
+    def _resident_key(self, fv):
+        """What the Schur complement resident on the global context was built at: point, weights, hyper-parameters."""
+        return (np.asarray(fv, dtype=np.float64).tobytes(), self._w_res.key, self._hyper_state_key(),
+                None if self._external is None else id(self._external))
+
+    # ---- the whole arrow: solve, covariance of any moment, weight influence --------------------------------------------------
+    @_hip.host_blas
+    def solve(self, x, R, is_free=True, resident_factor=False):
+        """H^-1 R at x (R: D x Q or a D-vector, local rows allowed) by `arrow_solve`.  resident_factor=True solves the Schur
+        complement with the factor on the global context: call `global_hessian(x, want_host=False)` and
+        `_ensure_gctx().chol_factor_last()` at the same point first (free coordinates).  A factor built at another point,
+        or under other weights or hyper-parameters, is refused with a ValueError."""
+        _, Hgg, rows, Hx, loc = self._arrow(x, is_free)
+        if resident_factor and (not is_free or getattr(self, '_schur_key', None) != self._resident_key(_hip.as_f64(x).ravel())):
+            raise ValueError('resident_factor=True needs global_hessian(x, want_host=False) and chol_factor_last() at this point, '
+                             'with these weights and hyper-parameters, in free coordinates')
+        schur_solve = self._ensure_gctx().chol_solve if resident_factor else None
+        return arrow_solve(Hgg, rows, Hx, loc, R, schur_solve=schur_solve)
+
+    def _moment_jac(self, moment_jac):
+        M = np.atleast_2d(_hip.as_f64(moment_jac))
+        D = self.n_global + 2 * self.G
+        if M.ndim != 2 or M.shape[1] not in (D, self.n_global):
+            raise ValueError('moment Jacobian must have {} (all parameters) or {} (global parameters) columns'.format(D, self.n_global))
+        if M.shape[1] != D:
+            M = np.hstack([M, np.zeros((M.shape[0], D - M.shape[1]))])
+        return M
+
+    def lrvb_cov(self, x, moment_jac, is_free=True):
+        """M H^-1 M^T (Q x Q): the linear-response covariance of the moments M theta, M = moment_jac being Q x D (columns of the
+        group effects allowed) or Q x n_global (zero-padded)."""
+        M = self._moment_jac(moment_jac)
+        return M @ self.solve(x, np.ascontiguousarray(M.T), is_free)
+
+    def _influence_operand(self, x, moment_jac, is_free, chol):
+        """A = -M H^-1 J (Q x (2 P + 2 G)) in the coordinates (m, v, e, r) of the device entries, and the point in them."""
+        self._push_state()
+        M = self._moment_jac(moment_jac)
+        P, G, ng = self.P, self.G, self.n_global
+        if chol is None:
+            S = self.solve(x, np.ascontiguousarray(M.T), is_free)
+        else:
+            S = np.asarray(chol.solve(np.ascontiguousarray(M.T))).reshape(ng + 2 * G, -1)
+        eta = self._eta(x, is_free)
+        j1 = self._jac(eta)[0] if is_free else np.ones(eta.size)
+        v, r = 1.0 / eta[P:2 * P], 1.0 / eta[ng + G:]
+        chain = np.concatenate([j1[:P], -v * v * j1[P:2 * P], j1[ng:ng + G], -r * r * j1[ng + G:]])
+        keep = np.concatenate([np.arange(2 * P), np.arange(ng, ng + 2 * G)])
+        A = -(S[keep] * chain[:, None]).T
+        return np.ascontiguousarray(A), (eta[:P], v, eta[ng:ng + G], r, self.gh_x, self.gh_w)
+
+    def obs_influence(self, x, moment_jac, n0=0, n1=None, is_free=True, chol=None):
+        """Rows n0..n1 of (moment_jac @ d par / d w)^T ((n1 - n0) x Q), streamed over the observations on the device
+        (`lrvb_glmm_obs_influence`); the N x D cross Hessian is never formed.  A = -moment_jac H^-1 J comes from the dense factor
+        `chol` where one is given (ParametricSensitivityLinearApproximation holds it), otherwise from `arrow_solve` -- the route
+        for large G, where no dense factor exists.  Per unit weight: a row of weight zero gets the influence of adding it."""
+        A, pt = self._influence_operand(x, moment_jac, is_free, chol)
+        return self.ctx.glmm_obs_influence(*pt, A, n0=n0, n1=n1)
+
+    def group_influence(self, x, moment_jac, is_free=True, chol=None):
+        """G x Q: row g is the derivative of the moments with respect to a common multiplier on the weights of group g's rows,
+        sum_{n in g} w_n * (row n of `obs_influence`) -- minus it is the linear prediction of leaving the cluster out.  The
+        group's own prior term on u_g stays in the model and is not part of it.  Fixed summation order on the device
+        (`lrvb_glmm_group_influence`); an empty group gives a zero row."""
+        A, pt = self._influence_operand(x, moment_jac, is_free, chol)
+        return self.ctx.glmm_group_influence(*pt, A)
 
     # ---- hyper-parameters ---------------------------------------------------------------------------------------------
     def _prior_hyper(self, kind, eta_g, want):

@@ -371,6 +371,48 @@ int lrvb_glmm_terms(lrvb_ctx* ctx, const double* mean, const double* var, int64_
 int lrvb_glmm_schur(lrvb_ctx* ctx, const double* local_2x2, const double* border_scale, const double* closed_rows, int64_t G,
                     double* M_out);
 
+/* Logistic mixed model with K <= 4 independent random effects per group (random slopes):
+ *   y_n ~ Bernoulli(sigma(x_n . beta + z_n . u_g(n))),  q(beta_j) = N(mean_j, var_j),  q(u_gk) = N(e_gk, r_gk).
+ * The group design z (n x K, row-major: a column of ones for an intercept, columns of X for slopes) lives in its own device
+ * buffer.  It is replaced by the next call and dropped by a later lrvb_set_groups whose row count differs from n.
+ * z == NULL: LRVB_ERR_INVALID; K < 1 or K > 4: LRVB_ERR_UNSUPPORTED; n < 1: LRVB_ERR_SIZE.                                */
+int lrvb_set_group_design(lrvb_ctx* ctx, const double* z, int64_t n, int64_t K);
+/* Data term of that model at (mean, var (P each), e, r (G x K each, row-major: group-major)):
+ *   rho_n = x_n . mean + z_n . e_g(n),  s_n = (x_n o x_n) . var + (z_n o z_n) . r_g(n),  sum_n w_n [psi(rho_n, s_n) - y_n rho_n]
+ * with psi and the per-row coefficients a1, a2, c11, c12, c22 of lrvb_glmm_terms (same nodes, same derivative rule).
+ *   value_out (1), grad_global_out (2 P: d/d mean, d/d var; may be NULL), H_blocks_out (3 P^2: mean-mean, mean-var, var-var;
+ *   may be NULL) as lrvb_glmm_terms.
+ *   group_sums_out (may be NULL): per group the ncol = nsc + 4 K P sums, nsc = 2 K + K (2 K + 1),
+ *     [ sum a1 z (K) | sum a2 z o z (K) |
+ *       upper triangle, row-major, of the 2 K x 2 K local block  sum c q q^T,  q = [z | z o z],  c = c11 on the z-z quarter,
+ *       c12 on the z-(z o z) quarter, c22 on the (z o z)-(z o z) quarter  (K (2 K + 1)) |
+ *       border, four blocks of K x P, entry (b K + k) P + j:
+ *         b = 0: sum c11 z_k x_j,  b = 1: sum c12 z_k^2 x_j,  b = 2: sum c12 z_k x_j^2,  b = 3: sum c22 z_k^2 x_j^2 ]
+ *   want_border != 0: G x ncol doubles; want_border == 0: G x nsc doubles (the scalar columns; the border is not copied to
+ *   the host).  At K = 1 with z = 1 these are the columns of lrvb_glmm_terms in its order.
+ * Fixed summation order, no atomics: two calls at one point are bitwise equal.
+ * Reduce hook: every sum over observations of the call lies in ONE device buffer
+ *   [H blocks (3 P^2, only when asked for) | group sums (G x ncol) | gradient (2 P) | value (1)]
+ * and goes through the hook exactly once.  The group sums stay resident for lrvb_glmm_slopes_schur until the next
+ * lrvb_glmm_slopes_terms, lrvb_set_group_design or lrvb_set_groups.
+ * P > 64, K < 1, K > 4 or more than 128 nodes: LRVB_ERR_UNSUPPORTED; groups, the group design, X or y not set, or a group
+ * design that is not n_obs x K: LRVB_ERR_STATE; var_j <= 0 or r_gk <= 0: LRVB_ERR_INVALID; G is not the number of groups:
+ * LRVB_ERR_SIZE.                                                                                                          */
+int lrvb_glmm_slopes_terms(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r, int64_t G,
+                           int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes, double* value_out,
+                           double* grad_global_out, double* H_blocks_out, double* group_sums_out, int32_t want_border);
+/* Elimination of the 2 K G local parameters on the device from the group sums of the last lrvb_glmm_slopes_terms.  Per group
+ * the host sends the COMPLETE local block in the coordinates it eliminates in, ordered [e_g0 .. e_g,K-1 | r_g0 .. r_g,K-1]
+ * (local_blocks, G x K (2 K + 1): upper triangle, row-major), the 2 K chain factors of those coordinates (border_scale,
+ * G x 2 K) and the closed-form border entries of every local coordinate against [e_mu_k, a_k, b_k] of its own component k
+ * (closed_rows, G x 2 K x 3; the entries against the other components are zero).
+ * M_out (R x R, R = 2 P + 3 K, row-major) = sum_g C_g^T A_g^-1 C_g over the coupled coordinates
+ * [mean (P) | var (P) | e_mu_0, a_0, b_0, .., e_mu_{K-1}, a_{K-1}, b_{K-1}]: each block is factored A_g = L L^T, the rows
+ * U_g = L^-1 C_g are written, then one Gram over 2 K G rows.  A block that is not positive definite: LRVB_ERR_NOT_POSDEF;
+ * no resident group sums of K effects: LRVB_ERR_STATE; K < 1 or K > 4: LRVB_ERR_UNSUPPORTED.  No reduce-hook call.          */
+int lrvb_glmm_slopes_schur(lrvb_ctx* ctx, const double* local_blocks, const double* border_scale, const double* closed_rows,
+                           int64_t G, int64_t K, double* M_out);
+
 /* Streamed weight influence of the logistic mixed model.  Point arguments as lrvb_glmm_terms.  Per observation, PER UNIT WEIGHT,
  *   a1' = psi_rho(rho_n, s_n) - y_n,   a2' = psi_s(rho_n, s_n)
  * and the gradient of row n's term in (mean, var, e, r) is [a1' x_n | a2' x_n o x_n | at g(n): a1', a2'].  For an operand A
@@ -614,8 +656,8 @@ int lrvb_hessian_dev(lrvb_ctx* ctx, const double* free_dev, double* H_dev, int64
  * lrvb_weighted_gram (S), lrvb_group_sums, lrvb_grouped_stats ([S | group sums]), lrvb_mixture_rows /
  * lrvb_mixture_stats ([S64 | val2 | count of indefinite rows | packed Schur operand]: every rank fails together when
  * any rank has an indefinite row), lrvb_quadform_gram ([K4 tiles | s | observation count]) and
- * lrvb_logitnormal_terms ([Hessian blocks | gradient | value], the part that was asked for), lrvb_glmm_terms
- * ([Hessian blocks | group sums | gradient | value]) and lrvb_glmm_group_influence (the G x Q result).  A call must therefore
+ * lrvb_logitnormal_terms ([Hessian blocks | gradient | value], the part that was asked for), lrvb_glmm_terms and
+ * lrvb_glmm_slopes_terms ([Hessian blocks | group sums | gradient | value]) and lrvb_glmm_group_influence (the G x Q result).  A call must therefore
  * be made by ALL ranks, with the same arguments apart from the rows they hold.  lrvb_hessian_partial_dev and the
  * per-observation row outputs (lrvb_obs_*, the gradient rows of lrvb_mixture_rows) stay rank-local by contract.
  * fn == NULL removes the hook.                                                                                */

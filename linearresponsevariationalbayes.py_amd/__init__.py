@@ -48,6 +48,7 @@ from .logitnormal import LogitNormalRegressionObjective
 from .logitnormal_mvn import LogitNormalMVNRegressionObjective
 from .softmax import SoftmaxRegressionObjective
 from .glmm import LogisticGLMMObjective
+from .glmm_slopes import LogisticGLMMSlopesObjective
 from .torch_closure import TorchObjective
 from . import regression as regression_utils
 from . import packing as ProjectionParams

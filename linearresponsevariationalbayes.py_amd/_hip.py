@@ -86,6 +86,9 @@ _SIGNATURES = {
     'lrvb_logitnormal_mvn_chain': [_VP, c_i64, _VP, _VP, _VP, _VP],
     'lrvb_glmm_terms': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, _VP, _VP, _VP, _VP],
     'lrvb_glmm_schur': [_VP, _VP, _VP, _VP, c_i64, _VP],
+    'lrvb_set_group_design': [_VP, _VP, c_i64, c_i64],
+    'lrvb_glmm_slopes_terms': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, _VP, _VP, ctypes.c_int32],
+    'lrvb_glmm_slopes_schur': [_VP, _VP, _VP, _VP, c_i64, c_i64, _VP],
     'lrvb_glmm_obs_influence': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, c_i64, c_i64, c_i64, _VP],
     'lrvb_glmm_group_influence': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, c_i64, _VP],
     'lrvb_softmax_set_labels': [_VP, _VP, c_i64, ctypes.c_int32],

@@ -1,0 +1,290 @@
+// k_glmm_slopes.hip -- logistic mixed model with K <= 4 independent random effects per group:
+//   y_n ~ Bernoulli(sigma(x_n . beta + z_n . u_g(n))),   q(beta_j) = N(m_j, v_j),   q(u_gk) = N(e_gk, r_gk).
+// Per observation rho_n = x_n . m + z_n . e_g, s_n = (x_n o x_n) . v + (z_n o z_n) . r_g and the five quadrature coefficients
+// a1, a2, c11, c12, c22 of k_glmm.hip (same nodes, same Stein-rule derivatives).  With K = 1 and z = 1 it is that model.
+//
+// glmm_slopes_rows_kernel is ONE pass over the rows in group-sorted order, built like glmm_rows_kernel: a workgroup (4 waves) walks
+// tiles of GS_T = 64 sorted rows.
+//   1. the tile's rows of X are gathered through the permutation into LDS, and the row's K values of z behind them (columns
+//      P .. P + K - 1 of the same LDS row, stride GS_XS);
+//   2. four lanes share a row for the four dot products (lane q4 takes the x columns q4, q4 + 4, .. and the z column q4) and for
+//      the quadrature nodes; xor shuffles add the quarters;
+//   3. lane 0 of the four writes the five coefficients to the ORIGINAL row position (global block and gradient by the library's
+//      weighted products, unchanged) and to LDS;
+//   4. the 4 K products of a row that P border columns each share,
+//        d[0 K + k] = c11 z_k,  d[1 K + k] = c12 z_k^2,  d[2 K + k] = c12 z_k,  d[3 K + k] = c22 z_k^2,
+//      are formed ONCE per row into LDS (GS_DS doubles per row);
+//   5. segmented sums from the tile still in LDS over the ncol = nsc + 4 K P columns of a group,
+//        [ sum a1 z (K) | sum a2 z o z (K) | upper triangle, row-major, of the 2 K x 2 K block  sum c q q^T  (K (2 K + 1)) |
+//          border: column nsc + (b K + k) P + j = sum d[b K + k] x_j (b = 0, 1) or d[b K + k] x_j^2 (b = 2, 3) ],
+//      nsc = 2 K + K (2 K + 1), q = [z | z o z] and c = c11 / c12 / c22 by the halves the pair lies in.  Thread t owns the
+//      border columns t, t + 256, t + 512, t + 768 (consecutive threads read consecutive LDS words of the staged row; the
+//      factor d is a broadcast) and, for t < nsc, scalar column t.  The tile's rows are walked in order, flushing at every change
+//      of group: a group inside one tile goes to its row of the result, the piece of a group cut by a tile boundary to one of
+//      the tile's two partial rows, which glmm_fixup_kernel (k_glmm.hip) adds in tile order.
+// No atomics anywhere: the result is a fixed-order sum, bitwise reproducible.  Empty groups keep the zeros the caller wrote.
+#include "lrvb_internal.h"
+#include "k_kernels.h"
+#include <math.h>
+
+constexpr int GS_T = 64;                 // sorted rows per tile (= GL_T of k_glmm.hip: glmm_fixup_kernel and glmm_num_tiles are shared)
+constexpr int GS_XS = 68;                // LDS row stride in doubles: 64 columns of x + 4 of z; 68 = 4 mod 32, so the 8 rows x 4 lanes
+                                         // of a 32-lane half read 32 different 8-byte bank pairs in the dot products
+constexpr int GS_DS = 16;                // the 4 K shared products of a row
+constexpr int GS_OWN = 4;                // border columns per thread: 4 K P <= 1024 = 4 x 256
+
+__global__ __launch_bounds__(256)
+void glmm_slopes_rows_kernel(i64 N, int P, int Kz, i64 G, const double* __restrict__ X, const double* __restrict__ Z,
+                             const double* __restrict__ y, const double* __restrict__ w, const i64* __restrict__ perm,
+                             const i64* __restrict__ offs, const double* __restrict__ m, const double* __restrict__ vb,
+                             const double* __restrict__ eg, const double* __restrict__ rg, const double* __restrict__ gx,
+                             const double* __restrict__ gw, int nq, double* __restrict__ coef, i64 NP, double* __restrict__ gsum,
+                             double* __restrict__ part, double* __restrict__ vpart)
+{
+    __shared__ double xs[GS_T * GS_XS], dk[GS_T * GS_DS], cf[5 * GS_T], ms[64], vs[64], sx[128], sw[128], red[4];
+    __shared__ i64 s_row[GS_T];
+    __shared__ int s_gid[GS_T], s_whole[GS_T];
+    const int tid = threadIdx.x;
+    const int K2 = 2 * Kz, K4 = 4 * Kz;
+    const int nsc = K2 + Kz * (K2 + 1), nbord = K4 * P, ncol = nsc + nbord;
+    const double r2 = 1.4142135623730951, ispi = 0.5641895835477563;     // sqrt(2), 1 / sqrt(pi)
+    if (tid < nq) { sx[tid] = r2 * gx[tid]; sw[tid] = ispi * gw[tid]; }
+    if (tid < P) { ms[tid] = m[tid]; vs[tid] = vb[tid]; }
+    const i64 n_tiles = (N + GS_T - 1) / GS_T;
+    const int row = tid >> 2, q4 = tid & 3;
+    // the border columns of this thread: column t = tid + 256 i is block bk = t / P (d[bk]) and x column j = t - bk P
+    int o_x[GS_OWN], o_d[GS_OWN];
+    bool o_has[GS_OWN], o_sq[GS_OWN];
+#pragma unroll
+    for (int i = 0; i < GS_OWN; ++i) {
+        const int t = tid + 256 * i;
+        o_has[i] = t < nbord;
+        const int bk = o_has[i] ? t / P : 0;
+        o_d[i] = bk; o_x[i] = o_has[i] ? t - bk * P : 0; o_sq[i] = bk >= K2;
+    }
+    // the scalar column of this thread (tid < nsc): cf[s_c] q[s_i] q[s_j] with q = [z | z o z | 1]
+    const bool has_sc = tid < nsc;
+    int s_c = 0, s_i = K2, s_j = K2;
+    if (tid < Kz) { s_c = 0; s_i = tid; }
+    else if (tid < K2) { s_c = 1; s_i = tid; }
+    else if (has_sc) {
+        int u = tid - K2, i = 0;
+        while (u >= K2 - i) { u -= K2 - i; ++i; }
+        s_i = i; s_j = i + u;
+        s_c = s_j < Kz ? 2 : (s_i >= Kz ? 4 : 3);
+    }
+    const int zi = P + (s_i < Kz ? s_i : s_i - Kz), zj = P + (s_j < Kz ? s_j : s_j - Kz);    // unused where the factor is 1
+    const bool i_one = s_i >= K2, i_sq = s_i >= Kz, j_one = s_j >= K2, j_sq = s_j >= Kz;
+    for (i64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const i64 t0 = tile * GS_T;
+        const int rows = (int)(N - t0 < GS_T ? N - t0 : GS_T);
+        __syncthreads();                                                 // the previous tile is consumed (and the nodes are in place)
+        if (tid < GS_T) {
+            int g = 0, whole = 0;
+            i64 pr = 0;
+            if (tid < rows) {
+                const i64 i = t0 + tid;
+                pr = perm[i];
+                i64 lo = 0, hi = G;                                      // the last g with offs[g] <= i (its offs[g + 1] > i)
+                while (hi - lo > 1) { const i64 mid = (lo + hi) >> 1; if (offs[mid] <= i) lo = mid; else hi = mid; }
+                g = (int)lo;
+                whole = (offs[lo] >= t0 && offs[lo + 1] <= t0 + GS_T) ? 1 : 0;
+            }
+            s_row[tid] = pr; s_gid[tid] = g; s_whole[tid] = whole;
+        }
+        __syncthreads();
+        for (int e = tid; e < rows * P; e += 256) { const int rr = e / P, cc = e - rr * P; xs[rr * GS_XS + cc] = X[s_row[rr] * P + cc]; }
+        for (int e = tid; e < rows * Kz; e += 256) { const int rr = e / Kz, cc = e - rr * Kz; xs[rr * GS_XS + P + cc] = Z[s_row[rr] * Kz + cc]; }
+        __syncthreads();
+        double rho = 0.0, s = 0.0;
+        if (row < rows) {
+            const double* xr = xs + row * GS_XS;
+            for (int j = q4; j < P; j += 4) { const double x = xr[j]; rho += x * ms[j]; s += x * x * vs[j]; }
+            if (q4 < Kz) {
+                const i64 gk = (i64)s_gid[row] * Kz + q4;
+                const double z = xr[P + q4];
+                rho += z * eg[gk]; s += z * z * rg[gk];
+            }
+        }
+        rho += __shfl_xor(rho, 1); s += __shfl_xor(s, 1);
+        rho += __shfl_xor(rho, 2); s += __shfl_xor(s, 2);
+        double v = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0, e4 = 0.0;
+        if (row < rows) {
+            const double sd = sqrt(fmax(s, 0.0));
+            for (int k = q4; k < nq; k += 4) {
+                const double t = rho + sd * sx[k], wk = sw[k];
+                const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
+                const double sp = (t > 0.0 ? t : 0.0) + log1p(e);
+                const double sg = t >= 0.0 ? ie : e * ie;
+                const double g2 = e * ie * ie;
+                const double om = (1.0 - e) * ie;                        // |1 - 2 sigma|
+                const double g3 = t >= 0.0 ? -g2 * om : g2 * om;
+                v += wk * sp; e1 += wk * sg; e2 += wk * g2; e3 += wk * g3; e4 += wk * g2 * (1.0 - 6.0 * g2);
+            }
+        }
+#pragma unroll
+        for (int off = 1; off <= 2; off <<= 1) {
+            v += __shfl_xor(v, off); e1 += __shfl_xor(e1, off); e2 += __shfl_xor(e2, off);
+            e3 += __shfl_xor(e3, off); e4 += __shfl_xor(e4, off);
+        }
+        double contrib = 0.0;
+        if (q4 == 0) {
+            double k1 = 0.0, k2 = 0.0, k11 = 0.0, k12 = 0.0, k22 = 0.0;
+            if (row < rows) {
+                const i64 pr = s_row[row];
+                const double wi = w[pr], yi = y[pr];
+                contrib = wi * (v - yi * rho);
+                k1 = wi * (e1 - yi); k2 = wi * 0.5 * e2; k11 = wi * e2; k12 = wi * 0.5 * e3; k22 = wi * 0.25 * e4;
+                coef[pr] = k1; coef[NP + pr] = k2; coef[2 * NP + pr] = k11; coef[3 * NP + pr] = k12; coef[4 * NP + pr] = k22;
+            }
+            cf[row] = k1; cf[GS_T + row] = k2; cf[2 * GS_T + row] = k11; cf[3 * GS_T + row] = k12; cf[4 * GS_T + row] = k22;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) contrib += __shfl_xor(contrib, off);
+        if ((tid & 63) == 0) red[tid >> 6] = contrib;
+        __syncthreads();
+        if (tid == 0) vpart[tile] = (red[0] + red[1]) + (red[2] + red[3]);
+        // the 4 K products of a row that its border columns share
+        for (int e = tid; e < rows * K4; e += 256) {
+            const int rr = e / K4, bk = e - rr * K4, b = bk / Kz, k = bk - b * Kz;
+            const double z = xs[rr * GS_XS + P + k];
+            dk[rr * GS_DS + bk] = cf[(b == 0 ? 2 : (b == 3 ? 4 : 3)) * GS_T + rr] * ((b & 1) ? z * z : z);
+        }
+        __syncthreads();
+        // segmented sums over the tile's rows, in row order
+        if (o_has[0] || has_sc) {
+            double acc[GS_OWN] = {0.0, 0.0, 0.0, 0.0}, accs = 0.0;
+            int run_start = 0;
+            for (int rr = 0; rr < rows; ++rr) {
+                const double* xr = xs + rr * GS_XS;
+                const double* dr = dk + rr * GS_DS;
+#pragma unroll
+                for (int i = 0; i < GS_OWN; ++i)
+                    if (o_has[i]) { double x = xr[o_x[i]]; if (o_sq[i]) x *= x; acc[i] += dr[o_d[i]] * x; }
+                if (has_sc) {
+                    double fi = 1.0, fj = 1.0;
+                    if (!i_one) { fi = xr[zi]; if (i_sq) fi *= fi; }
+                    if (!j_one) { fj = xr[zj]; if (j_sq) fj *= fj; }
+                    accs += cf[s_c * GS_T + rr] * (fi * fj);
+                }
+                const int g = s_gid[rr];
+                if (rr == rows - 1 || s_gid[rr + 1] != g) {
+                    double* dst = s_whole[rr] ? gsum + (i64)g * ncol : part + (tile * 2 + (run_start == 0 ? 0 : 1)) * ncol;
+#pragma unroll
+                    for (int i = 0; i < GS_OWN; ++i)
+                        if (o_has[i]) { dst[nsc + tid + 256 * i] = acc[i]; acc[i] = 0.0; }
+                    if (has_sc) dst[tid] = accs;
+                    accs = 0.0; run_start = rr + 1;
+                }
+            }
+        }
+    }
+}
+
+int launch_glmm_slopes_rows(lrvb_ctx* c, int Kz, const double* Z, const double* m, const double* vb, const double* eg, const double* rg,
+                            const double* gx, const double* gw, int nq, double* coef, i64 NP, double* gsum, double* part, double* vpart) {
+    const i64 N = c->N, G = c->n_groups;
+    if (c->P > 64 || Kz < 1 || Kz > 4 || nq < 1 || nq > 128)
+        LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "logistic mixed model with slopes: P <= 64, 1 <= K <= 4, at most 128 nodes");
+    const int ncol = glmm_slopes_ncol((int)c->P, Kz);
+    const i64* gdev = reinterpret_cast<const i64*>(c->groups.p);
+    const i64 n_tiles = glmm_num_tiles(N);
+    const unsigned grid = (unsigned)(n_tiles < 2048 ? (n_tiles < 1 ? 1 : n_tiles) : 2048);
+    hipLaunchKernelGGL(glmm_slopes_rows_kernel, dim3(grid), dim3(256), 0, c->stream, N, (int)c->P, Kz, G, (const double*)c->X.p, Z,
+                       (const double*)c->y.p, (const double*)c->w.p, gdev, gdev + N, m, vb, eg, rg, gx, gw, nq, coef, NP, gsum, part, vpart);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(glmm_fixup_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, G, ncol, gdev + N, (const double*)part, gsum);
+    HIP_TRY(hipGetLastError());
+    return LRVB_OK;
+}
+int glmm_slopes_ncol(int P, int Kz) { return 2 * Kz + Kz * (2 * Kz + 1) + 4 * Kz * P; }
+
+// ---- elimination of the 2 K G local parameters ---------------------------------------------------------------------------------
+// Per group g: A_g (2 K x 2 K, the complete local block in the coordinates that are eliminated, its K (2 K + 1) upper-triangle
+// entries row-major from the host) = L L^T, and the 2 K border rows over the R = 2 P + 3 K coupled global coordinates
+// [m (P) | v (P) | e_mu_0, a_0, b_0, .., e_mu_{K-1}, a_{K-1}, b_{K-1}]:
+//   row e_gk = f_ek [sum c11 z_k x | sum c12 z_k x o x | closed (3) in the columns of k, zero in those of the other components]
+//   row r_gk = f_rk [sum c12 z_k^2 x | sum c22 z_k^2 x o x | closed (3) ...]
+// from the RESIDENT group sums.  Thread 0 factors A_g into LDS; thread c then takes column c through the forward substitution
+// and writes U_g = L^-1 C_g (2 K x R), so that sum_g C_g^T A_g^-1 C_g = U^T U is one Gram over 2 K G rows.  A pivot that is not
+// positive raises the flag.
+template <int KZ>
+__global__ __launch_bounds__(256)
+void glmm_slopes_schur_rows_kernel(i64 G, int P, const double* __restrict__ gsum, const double* __restrict__ loc /* G x K (2 K + 1) */,
+                                   const double* __restrict__ scale /* G x 2 K */, const double* __restrict__ closed /* G x 2 K x 3 */,
+                                   double* __restrict__ U, int ldu, int* __restrict__ bad)
+{
+    constexpr int K2 = 2 * KZ, NT = KZ * (K2 + 1), nsc = K2 + NT;
+    __shared__ double Ls[K2 * K2], fs[K2], cs[K2 * 3];
+    const i64 g = blockIdx.x;
+    if (g >= G) return;
+    const int ncol = nsc + 4 * KZ * P, R = 2 * P + 3 * KZ;
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        double A[K2][K2];
+        const double* a = loc + g * NT;
+        int t = 0;
+#pragma unroll
+        for (int i = 0; i < K2; ++i)
+#pragma unroll
+            for (int j = i; j < K2; ++j) A[i][j] = a[t++];
+        bool ok = true;
+#pragma unroll
+        for (int j = 0; j < K2; ++j) {                                   // column j of L, kept in A[j][j ..] (L_ij = A[j][i], i >= j)
+            double d = A[j][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) d -= A[k][j] * A[k][j];
+            if (!(d > 0.0)) { ok = false; d = 1.0; }
+            const double l = sqrt(d);
+            A[j][j] = l;
+#pragma unroll
+            for (int i = j + 1; i < K2; ++i) {
+                double sij = A[j][i];
+#pragma unroll
+                for (int k = 0; k < j; ++k) sij -= A[k][i] * A[k][j];
+                A[j][i] = sij / l;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < K2; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) Ls[i * K2 + j] = A[j][i];
+        if (!ok) *bad = 1;
+    }
+    if (tid >= 64 && tid < 64 + K2) fs[tid - 64] = scale[g * K2 + (tid - 64)];
+    if (tid >= 128 && tid < 128 + K2 * 3) cs[tid - 128] = closed[g * K2 * 3 + (tid - 128)];
+    __syncthreads();
+    const double* gs = gsum + g * ncol + nsc;
+    for (int c = tid; c < R; c += 256) {
+        double u[K2];
+#pragma unroll
+        for (int i = 0; i < K2; ++i) {
+            const int k = i < KZ ? i : i - KZ;
+            double ce;
+            if (c < P) ce = gs[((i < KZ ? 0 : KZ) + k) * P + c];
+            else if (c < 2 * P) ce = gs[((i < KZ ? K2 : 3 * KZ) + k) * P + (c - P)];
+            else { const int q = c - 2 * P, kc = q / 3; ce = kc == k ? cs[i * 3 + (q - 3 * kc)] : 0.0; }
+            double t = fs[i] * ce;
+#pragma unroll
+            for (int j = 0; j < i; ++j) t -= Ls[i * K2 + j] * u[j];
+            u[i] = t / Ls[i * K2 + i];
+            U[(g * K2 + i) * ldu + c] = u[i];
+        }
+    }
+}
+
+int launch_glmm_slopes_schur_rows(lrvb_ctx* c, int Kz, const double* gsum, const double* loc, const double* scale, const double* closed,
+                                  double* U, int ldu, int* bad) {
+    const i64 G = c->n_groups;
+    const dim3 grid((unsigned)G), block(256);
+    const int P = (int)c->P;
+    switch (Kz) {
+    case 1: hipLaunchKernelGGL(glmm_slopes_schur_rows_kernel<1>, grid, block, 0, c->stream, G, P, gsum, loc, scale, closed, U, ldu, bad); break;
+    case 2: hipLaunchKernelGGL(glmm_slopes_schur_rows_kernel<2>, grid, block, 0, c->stream, G, P, gsum, loc, scale, closed, U, ldu, bad); break;
+    case 3: hipLaunchKernelGGL(glmm_slopes_schur_rows_kernel<3>, grid, block, 0, c->stream, G, P, gsum, loc, scale, closed, U, ldu, bad); break;
+    case 4: hipLaunchKernelGGL(glmm_slopes_schur_rows_kernel<4>, grid, block, 0, c->stream, G, P, gsum, loc, scale, closed, U, ldu, bad); break;
+    default: LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "logistic mixed model with slopes: 1 <= K <= 4");
+    }
+    HIP_TRY(hipGetLastError());
+    return LRVB_OK;
+}

@@ -128,3 +128,7 @@ __global__ void lmvn_jac_rows_kernel(i64 total, i64 Pv, double* __restrict__ S);
 __global__ void lmvn_hvp_coef_kernel(i64 n, const double* __restrict__ c11, const double* __restrict__ c12, const double* __restrict__ c22,
                                      const double* __restrict__ dmu, const double* __restrict__ ds, double* __restrict__ em,
                                      double* __restrict__ es);
+
+// k_glmm.hip
+__global__ __launch_bounds__(256)
+void glmm_fixup_kernel(i64 G, int ncol, const i64* __restrict__ offs, const double* __restrict__ part, double* __restrict__ gsum);

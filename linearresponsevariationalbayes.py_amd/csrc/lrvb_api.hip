@@ -231,7 +231,7 @@ extern "C" int lrvb_ctx_destroy(lrvb_ctx* c) {
     DevBuf* all[] = { &c->X, &c->y, &c->w, &c->quadA, &c->quadM, &c->quadB, &c->theta, &c->eta, &c->j1, &c->j2,
                       &c->vtmp, &c->vtmp2, &c->vtmp3, &c->g_eta, &c->g_free, &c->lp, &c->cw, &c->zbuf,
                       &c->part_vec, &c->part_val, &c->stats, &c->tile_part, &c->Heta, &c->Hfree, &c->Jdense,
-                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn,
+                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn, &c->glmm, &c->gz, &c->glmms,
                       &c->sm.labels, &c->sm.p, &c->sm.wpad, &c->sm.work, &c->sm.col, &c->sm.tiles, &c->sm.rows };
     for (DevBuf* b : all) buf_free(*b);
     if (c->host_pinned) (void)hipHostFree(c->host_pinned);
@@ -1627,6 +1627,8 @@ extern "C" int lrvb_set_groups(lrvb_ctx* c, const int32_t* gid, int64_t n, int64
     c->n_groups = n_groups;
     c->gstats_valid = false;
     c->glmm_valid = false;
+    c->glmms_valid = false;
+    if (c->gz_n != n) { c->gz_n = 0; c->gz_K = 0; }      // a group design of another row count is dropped
     c->zs_valid = false; c->ws_valid = false;
     return LRVB_OK;
 }
@@ -2560,6 +2562,124 @@ extern "C" int lrvb_glmm_schur(lrvb_ctx* c, const double* local_2x2, const doubl
     int bad = 0;
     memcpy(&bad, &fh, sizeof(int));
     if (bad) LRVB_FAIL(LRVB_ERR_NOT_POSDEF, "a 2 x 2 local block of the logistic mixed model is not positive definite");
+    return d2h(c, M_out, Md, (size_t)(R * R));
+}
+
+// ---- logistic mixed model with K <= 4 random effects per group (k_glmm_slopes.hip) ---------------------------------------------
+extern "C" int lrvb_set_group_design(lrvb_ctx* c, const double* z, int64_t n, int64_t K) {
+    LRVB_TRY(ctx_bind(c));
+    if (!z) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    if (K < 1 || K > 4) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 4 random effects per group (got %lld)", (long long)K);
+    if (n < 1) LRVB_FAIL(LRVB_ERR_SIZE, "the group design needs at least one row");
+    c->glmms_valid = false;
+    c->gz_n = 0; c->gz_K = 0;
+    LRVB_TRY(buf_reserve(c, c->gz, (size_t)(n * K)));
+    HIP_TRY(hipMemcpyAsync(c->gz.p, z, (size_t)(n * K) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->gz_n = n; c->gz_K = (int)K;
+    return LRVB_OK;
+}
+
+// c->glmms: [H blocks (3 P^2) | group sums (G x ncol) | gradient (2 P) | value], adjacent as in lrvb_glmm_terms.  c->work1:
+// [nodes 256 | m, v (2 up(P)) | e, r (2 up(G K)) | five coefficient vectors (5 NP, original order, zero past N) | tile partials]
+extern "C" int lrvb_glmm_slopes_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                      const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
+                                      double* value_out, double* grad_global_out, double* H_blocks_out, double* group_sums_out,
+                                      int32_t want_border) {
+    LRVB_TRY(ctx_bind(c));
+    if (!mean || !var || !e_loc || !r_loc || !gh_x || !gh_w || !value_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    if (n_nodes < 1 || n_nodes > 128) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 128 quadrature nodes");
+    if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the logistic mixed model needs P <= 64 (got %lld)", (long long)c->P);
+    if (K < 1 || K > 4) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 4 random effects per group (got %lld)", (long long)K);
+    if (c->loss == LRVB_LOSS_NONE || c->data_only || !(c->have_X && c->have_y))
+        LRVB_FAIL(LRVB_ERR_STATE, "the context needs a design matrix and responses: lrvb_set_data for LRVB_SLOT_X and LRVB_SLOT_Y");
+    if (c->n_groups <= 0) LRVB_FAIL(LRVB_ERR_STATE, "no groups: call lrvb_set_groups first");
+    if (c->gz_K <= 0) LRVB_FAIL(LRVB_ERR_STATE, "no group design: call lrvb_set_group_design first");
+    if (c->gz_n != c->N || c->gz_K != K)
+        LRVB_FAIL(LRVB_ERR_STATE, "the group design is %lld x %d, the model needs %lld x %lld", (long long)c->gz_n, c->gz_K, (long long)c->N, (long long)K);
+    const i64 N = c->N, P = c->P, G = c->n_groups, ncol = glmm_slopes_ncol((int)P, (int)K), nsc = ncol - 4 * K * P;
+    LRVB_TRY(check_len(P_in, P, "mean / var"));
+    LRVB_TRY(check_len(G_in, G, "groups of e / r"));
+    for (i64 j = 0; j < P; ++j) if (!(var[j] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "var[%lld] is not positive", (long long)j);
+    for (i64 g = 0; g < G * K; ++g) if (!(r_loc[g] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "r[%lld] is not positive", (long long)g);
+    c->glmms_valid = false;
+    const bool want_g = grad_global_out != nullptr, want_H = H_blocks_out != nullptr;
+    DevBuf& X2 = c->mx_Xk;
+    if ((want_g || want_H) && (!c->x2_ready || X2.n < (size_t)(N * P))) {
+        LRVB_TRY(buf_reserve(c, X2, (size_t)(N * P)));
+        EW(square_kernel, N * P, (const double*)c->X.p, X2.p);
+        c->x2_ready = true;
+    }
+    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
+    const i64 NP = up(N + 64), n_tiles = glmm_num_tiles(N), GK = G * K;
+    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(256 + 2 * up(P) + 2 * up(GK) + 5 * NP + n_tiles * 2 * ncol + n_tiles)));
+    LRVB_TRY(buf_reserve(c, c->glmms, (size_t)(3 * P * P + G * ncol + 2 * P + 1)));
+    double* g = c->work1.p; double* dm = g + 256; double* dv = dm + up(P); double* de = dv + up(P); double* dr = de + up(GK);
+    double* coef = dr + up(GK); double* part = coef + 5 * NP; double* vpart = part + n_tiles * 2 * ncol;
+    double* Hb = c->glmms.p; double* gsum = Hb + 3 * P * P; double* gred = gsum + G * ncol; double* vred = gred + 2 * P;
+    LRVB_TRY(h2d(c, g, gh_x, (size_t)n_nodes));
+    LRVB_TRY(h2d(c, g + 128, gh_w, (size_t)n_nodes));
+    LRVB_TRY(h2d(c, dm, mean, (size_t)P));
+    LRVB_TRY(h2d(c, dv, var, (size_t)P));
+    LRVB_TRY(h2d(c, de, e_loc, (size_t)GK));
+    LRVB_TRY(h2d(c, dr, r_loc, (size_t)GK));
+    HIP_TRY(hipMemsetAsync(coef, 0, (size_t)(5 * NP) * sizeof(double), c->stream));
+    HIP_TRY(hipMemsetAsync(gsum, 0, (size_t)(G * ncol + 2 * P + 1) * sizeof(double), c->stream));
+    LRVB_TRY(launch_glmm_slopes_rows(c, (int)K, c->gz.p, dm, dv, de, dr, g, g + 128, (int)n_nodes, coef, NP, gsum, part, vpart));
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, c->stream, (const double*)vpart, n_tiles, vred);
+    HIP_TRY(hipGetLastError());
+    if (want_g) {
+        LRVB_TRY(launch_gemv(c, true, N, P, 1.0, c->X.p, P, coef, 0.0, gred));
+        LRVB_TRY(launch_gemv(c, true, N, P, 1.0, X2.p, P, coef + NP, 0.0, gred + P));
+    }
+    if (want_H) {
+        LRVB_TRY(weighted_tn(c, c->X.p, c->X.p, P, N, coef + 2 * NP, Hb, c->mx_A));
+        LRVB_TRY(weighted_tn(c, c->X.p, X2.p, P, N, coef + 3 * NP, Hb + P * P, c->mx_A));
+        LRVB_TRY(weighted_tn(c, X2.p, X2.p, P, N, coef + 4 * NP, Hb + 2 * P * P, c->mx_A));
+    }
+    double* first = want_H ? Hb : gsum;
+    LRVB_TRY(obs_reduce(c, first, (i64)(vred + 1 - first)));
+    c->glmms_valid = true; c->glmms_K = (int)K;
+    LRVB_TRY(d2h(c, value_out, vred, 1));
+    if (want_g) LRVB_TRY(d2h(c, grad_global_out, gred, (size_t)(2 * P)));
+    if (want_H) LRVB_TRY(d2h(c, H_blocks_out, Hb, (size_t)(3 * P * P)));
+    if (group_sums_out) {
+        if (want_border) LRVB_TRY(d2h(c, group_sums_out, gsum, (size_t)(G * ncol)));
+        else {                                                           // the scalar columns of every group; the border stays
+            HIP_TRY(hipMemcpy2DAsync(group_sums_out, (size_t)nsc * sizeof(double), gsum, (size_t)ncol * sizeof(double),
+                                     (size_t)nsc * sizeof(double), (size_t)G, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+    }
+    return LRVB_OK;
+}
+
+extern "C" int lrvb_glmm_slopes_schur(lrvb_ctx* c, const double* local_blocks, const double* border_scale, const double* closed_rows,
+                                      int64_t G_in, int64_t K, double* M_out) {
+    LRVB_TRY(ctx_bind(c));
+    if (!local_blocks || !border_scale || !closed_rows || !M_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    if (K < 1 || K > 4) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 4 random effects per group (got %lld)", (long long)K);
+    if (c->n_groups <= 0 || !c->glmms_valid || c->glmms_K != K)
+        LRVB_FAIL(LRVB_ERR_STATE, "no group sums of %lld effects resident: call lrvb_glmm_slopes_terms first", (long long)K);
+    const i64 P = c->P, G = c->n_groups, R = 2 * P + 3 * K, K2 = 2 * K, NT = K * (K2 + 1);
+    LRVB_TRY(check_len(G_in, G, "local blocks"));
+    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
+    const int ldu = (int)up(R);
+    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(8 + up(NT * G) + up(K2 * G) + up(3 * K2 * G) + K2 * G * ldu + R * R)));
+    double* flag = c->work1.p; double* loc = flag + 8; double* sc = loc + up(NT * G); double* cl = sc + up(K2 * G);
+    double* U = cl + up(3 * K2 * G); double* Md = U + K2 * G * ldu;
+    LRVB_TRY(h2d(c, loc, local_blocks, (size_t)(NT * G)));
+    LRVB_TRY(h2d(c, sc, border_scale, (size_t)(K2 * G)));
+    LRVB_TRY(h2d(c, cl, closed_rows, (size_t)(3 * K2 * G)));
+    HIP_TRY(hipMemsetAsync(flag, 0, sizeof(double), c->stream));
+    const double* gsum = c->glmms.p + 3 * P * P;
+    LRVB_TRY(launch_glmm_slopes_schur_rows(c, (int)K, gsum, loc, sc, cl, U, ldu, reinterpret_cast<int*>(flag)));
+    LRVB_TRY(launch_gemm(c, true, false, R, R, K2 * G, 1.0, U, ldu, U, ldu, 0.0, Md, R));
+    double fh = 0.0;
+    LRVB_TRY(d2h(c, &fh, flag, 1));
+    int bad = 0;
+    memcpy(&bad, &fh, sizeof(int));
+    if (bad) LRVB_FAIL(LRVB_ERR_NOT_POSDEF, "a local block of the logistic mixed model with slopes is not positive definite");
     return d2h(c, M_out, Md, (size_t)(R * R));
 }
 

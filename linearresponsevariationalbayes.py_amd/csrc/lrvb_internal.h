@@ -127,6 +127,11 @@ struct lrvb_ctx {
     } sm;
     DevBuf lmvn;                   // lrvb_logitnormal_mvn_*: parameters, row pass, per-observation coefficients
     DevBuf glmm; bool glmm_valid = false;   // lrvb_glmm_terms: [H blocks (3 P^2) | group sums (G x (5 + 4 P)) | gradient (2 P) | value], summed over ranks; the group sums stay resident for lrvb_glmm_schur
+    // lrvb_glmm_slopes_terms (K <= 4 effects per group): the group design z (gz_n x gz_K, row-major; lrvb_set_group_design) and
+    // [H blocks (3 P^2) | group sums (G x glmm_slopes_ncol) | gradient (2 P) | value] of the last call with glmms_K effects,
+    // summed over ranks; the group sums stay resident for lrvb_glmm_slopes_schur
+    DevBuf gz; i64 gz_n = 0; int gz_K = 0;
+    DevBuf glmms; bool glmms_valid = false; int glmms_K = 0;
     DevBuf opt;                    // trust-region Newton-CG: 12 D-vectors (+ the D x D preconditioner)
     DevBuf cgm[9];                 // blocked CG: B, X, R, P, Q, Z (Q x D), U, W (Q x V), R^T (P x Q)
     DevBuf cgT;                    // N x Q products X U^T of the blocked HVP
@@ -234,6 +239,16 @@ int  launch_glmm_infl_gsum(lrvb_ctx* c, const double* m, const double* vb, const
                            const double* gw, int K, double* gsum /* G x (2 + 2 P), zeroed by the caller */,
                            double* part /* 2 (2 + 2 P) doubles per tile of glmm_num_tiles */);
 int  launch_glmm_infl_local(lrvb_ctx* c, i64 Q, const double* S, const double* Al, double* out /* G x Q, += */);
+
+// k_glmm_slopes.hip (P = n_cols <= 64, 1 <= K <= 4; groups and the group design set)
+int  glmm_slopes_ncol(int P, int K);      // columns of one group's sums: 2 K + K (2 K + 1) + 4 K P
+int  launch_glmm_slopes_rows(lrvb_ctx* c, int K, const double* Z /* N x K */, const double* m, const double* vb,
+                             const double* eg /* G x K */, const double* rg /* G x K */, const double* gx, const double* gw, int n_nodes,
+                             double* coef /* 5 x NP, original row order */, i64 NP, double* gsum /* G x ncol, zeroed by the caller */,
+                             double* part /* 2 ncol doubles per tile of glmm_num_tiles */, double* vpart);
+int  launch_glmm_slopes_schur_rows(lrvb_ctx* c, int K, const double* gsum, const double* loc /* G x K (2 K + 1) */,
+                                   const double* scale /* G x 2 K */, const double* closed /* G x 2 K x 3 */,
+                                   double* U /* 2 K G x ldu */, int ldu, int* bad);
 
 // k_lmm.hip
 struct LmmIdx { int p, ms, ls, iem, iim, iay, iby, iam, ibm; i64 ld; };    // vector-coordinate positions of the global parameters

@@ -1,0 +1,601 @@
+"""Logistic mixed model with K <= 4 independent random effects per group -- random slopes:
+
+    y_n ~ Bernoulli(sigma(x_n . beta + z_n . u_{g(n)})),   z_n in R^K,   u_gk ~ N(mu_k, 1 / tau_k) independently over k
+
+with beta_j ~ N(0, 1 / tau_beta), mu_k ~ N(mu0, 1 / kappa0), tau_k ~ Gamma(a0, b0) (the K components share the hyper-parameters)
+and q(beta) = UVNParamVector(P), q(mu) = UVNParamVector(K), q(tau_k) = K GammaParams, q(u) = UVNParamArray (G, K), pushed in this
+order.  `z` is its own N x K array: a column of ones for an intercept, `x[:, cols]` for slopes.  Vector coordinates
+
+    eta = [m (P) | i_beta (P) | e_mu (K) | i_mu (K) | a_0, b_0, .., a_{K-1}, b_{K-1} | e (G K, group-major) | i (G K)]
+
+n_global = 2 P + 4 K, D = 2 P + 4 K + 2 G K (the order the parameter classes themselves give: ArrayParam flattens in C order).
+
+    KL(eta) =  sum_n w_n [ psi(rho_n, s_n) - y_n rho_n ]     rho_n = x_n . m + z_n . e_g,  s_n = (x_n o x_n) . v + (z_n o z_n) . r_g
+             + sum_k { 1/2 E tau_k ( sum_g [(e_gk - e_mu_k)^2 + 1 / i_gk] + G / i_mu_k ) - 1/2 G E log tau_k
+                       + 1/2 kappa0 ((e_mu_k - mu0)^2 + 1 / i_mu_k) - (a0 - 1) E log tau_k + b0 E tau_k
+                       + 1/2 log i_mu_k + 1/2 sum_g log i_gk - gamma_entropy(a_k, b_k) }
+             + 1/2 tau_beta sum_j (m_j^2 + 1 / i_beta_j) + 1/2 sum_j log i_beta_j            (v = 1 / i_beta, r = 1 / i)
+
+The O(N) work is `lrvb_glmm_slopes_terms` (csrc/k_glmm_slopes.hip); everything N-independent is `glmm_slopes_closed_forms`
+below, plain numpy on the data pieces.  The Hessian is a block arrow: a dense global block, G local 2 K x 2 K blocks in the
+coordinates [e_g0 .. e_g,K-1 | i_g0 .. i_g,K-1] and a border of R = 2 P + 3 K coupled global rows
+[m | i_beta | e_mu_0, a_0, b_0, .., e_mu_{K-1}, a_{K-1}, b_{K-1}] (the i_mu_k do not couple).  At K = 1 with z = 1 the model is
+`LogisticGLMMObjective`.  The observation weights are data of this class, not a hyper-parameter.
+"""
+import numpy as np
+from scipy import special
+from scipy import sparse as sp_sparse
+from scipy import linalg as sp_linalg
+
+from . import _hip
+from .models import DeviceContext, DeclaredHypers, refuse_double_reduction
+from .packing import HyperVectorParam
+from .quadform import gamma_prior_hyper_grad, gamma_prior_hyper_cross
+from .hierarchical import _gamma_block, _gamma_entropy
+
+
+def group_sums_ncol(P, K):
+    """(scalar columns, all columns) of one group's sums (include/lrvb_hip.h, lrvb_glmm_slopes_terms)."""
+    nsc = 2 * K + K * (2 * K + 1)
+    return nsc, nsc + 4 * K * P
+
+
+def unpack_group_sums(gs, P, K):
+    """The G x ncol (or G x nsc, without the border) group sums of the device as the data pieces of `glmm_slopes_closed_forms`:
+    (g_loc G x 2 K, loc G x 2 K x 2 K symmetric, border G x 4 K x P or None)."""
+    gs = np.asarray(gs, dtype=np.float64)
+    G = gs.shape[0]
+    K2 = 2 * K
+    nsc, ncol = group_sums_ncol(P, K)
+    iu = np.triu_indices(K2)
+    loc = np.zeros((G, K2, K2))
+    loc[:, iu[0], iu[1]] = gs[:, K2:nsc]
+    loc[:, iu[1], iu[0]] = gs[:, K2:nsc]
+    border = gs[:, nsc:].reshape(G, 4 * K, P) if gs.shape[1] == ncol else None
+    return gs[:, :K2], loc, border
+
+
+def pack_group_sums(g_loc, loc, border):
+    """Inverse of `unpack_group_sums` (with the border)."""
+    G, K2 = g_loc.shape
+    iu = np.triu_indices(K2)
+    return np.hstack([g_loc, loc[:, iu[0], iu[1]], np.asarray(border).reshape(G, -1)])
+
+
+def _split_eta(eta, P, K, G):
+    ng = 2 * P + 4 * K
+    m, ib = eta[:P], eta[P:2 * P]
+    e_mu, i_mu = eta[2 * P:2 * P + K], eta[2 * P + K:2 * P + 2 * K]
+    a, b = eta[2 * P + 2 * K:ng:2], eta[2 * P + 2 * K + 1:ng:2]
+    e, ig = eta[ng:ng + G * K].reshape(G, K), eta[ng + G * K:].reshape(G, K)
+    return m, ib, e_mu, i_mu, a, b, e, ig
+
+
+def glmm_slopes_closed_forms(P, K, G, eta, data, tau_beta, mu0, kappa0, a0, b0, want_hess=True):
+    """The N-independent part of the model, in VECTOR coordinates, from the data-dependent pieces.
+
+    data: dict of the data term in the coordinates (m, v = 1 / i_beta, e, r = 1 / i): 'value', 'g_glob' (2 P: d/dm, d/dv),
+    'g_loc' (G x 2 K: [sum a1 z | sum a2 z o z]), and for the Hessian 'Hb' (3 x P x P: mm, mv, vv), 'loc' (G x 2 K x 2 K: the
+    blocks sum c q q^T, q = [z | z o z]) and 'border' (G x 4 K x P, row b K + k: sum c11 z_k x | sum c12 z_k^2 x |
+    sum c12 z_k x o x | sum c22 z_k^2 x o x for b = 0..3; None where it stayed on the device).
+
+    Returns dict: 'value', 'grad' (D), and with want_hess 'Hgg' (n_global x n_global), 'rows' (the R = 2 P + 3 K coupled global
+    coordinates, [m | i_beta | e_mu_k, a_k, b_k per k]), 'Hx' (R x 2 G K, columns in the order of eta's local part; None without
+    the border) and 'loc' (G x 2 K x 2 K, coordinates [e_g. | i_g.])."""
+    eta = np.asarray(eta, dtype=np.float64)
+    ng, GK = 2 * P + 4 * K, G * K
+    m, ib, e_mu, i_mu, a, b, e, ig = _split_eta(eta, P, K, G)
+    v, r = 1.0 / ib, 1.0 / ig
+    Et, EL = a / b, special.digamma(a) - np.log(b)
+    d = e - e_mu[None, :]
+    Am = np.sum(d * d + r, axis=0) + G / i_mu                  # (K)
+    value = (data['value'] + np.sum(0.5 * Et * Am - 0.5 * G * EL + 0.5 * kappa0 * ((e_mu - mu0) ** 2 + 1.0 / i_mu)
+                                    - (a0 - 1.0) * EL + b0 * Et + 0.5 * np.log(i_mu) - _gamma_entropy(a, b))
+             + 0.5 * np.sum(np.log(ig)) + 0.5 * tau_beta * (np.sum(m * m) + np.sum(v)) + 0.5 * np.sum(np.log(ib)))
+    out = dict(value=float(value))
+    if data.get('g_glob') is None:
+        return out
+    gd, gl = np.asarray(data['g_glob']), np.asarray(data['g_loc'])
+    dv, dr = -v * v, -r * r                                    # d v / d i_beta, d r / d i
+    g_v = gd[P:] + 0.5 * tau_beta
+    g_r = gl[:, K:] + 0.5 * Et[None, :]
+    dsum = np.sum(d, axis=0)
+    iem, iim = 2 * P + np.arange(K), 2 * P + K + np.arange(K)
+    ia = 2 * P + 2 * K + 2 * np.arange(K)
+    ibb = ia + 1
+    g = np.empty(ng + 2 * GK)
+    g[:P] = gd[:P] + tau_beta * m
+    g[P:2 * P] = g_v * dv + 0.5 / ib
+    g[iem] = -Et * dsum + kappa0 * (e_mu - mu0)
+    g[iim] = -0.5 * (Et * G + kappa0) / i_mu ** 2 + 0.5 / i_mu
+    Hab = []
+    for k in range(K):
+        gab, H2 = _gamma_block(a[k], b[k], 0.5 * Am[k] + b0, -0.5 * G - (a0 - 1.0))
+        g[ia[k]], g[ibb[k]] = gab
+        Hab.append(H2)
+    g[ng:ng + GK] = (gl[:, :K] + Et[None, :] * d).ravel()
+    g[ng + GK:] = (g_r * dr + 0.5 / ig).ravel()
+    out['grad'] = g
+    if not want_hess:
+        return out
+    Hb, B, L = np.asarray(data['Hb']), data.get('border'), np.asarray(data['loc'])
+    ta, tb = 1.0 / b, -a / b ** 2                              # d E tau / d a, d E tau / d b
+    Hgg = np.zeros((ng, ng))
+    Hgg[:P, :P] = Hb[0] + tau_beta * np.eye(P)
+    Hgg[:P, P:2 * P] = Hb[1] * dv[None, :]
+    Hgg[P:2 * P, :P] = Hgg[:P, P:2 * P].T
+    Hgg[P:2 * P, P:2 * P] = Hb[2] * dv[:, None] * dv[None, :] + np.diag(g_v * 2.0 * v ** 3 - 0.5 / ib ** 2)
+    for k in range(K):
+        em, im, ka, kb = iem[k], iim[k], ia[k], ibb[k]
+        Hgg[em, em] = Et[k] * G + kappa0
+        Hgg[em, ka] = Hgg[ka, em] = -dsum[k] * ta[k]
+        Hgg[em, kb] = Hgg[kb, em] = -dsum[k] * tb[k]
+        Hgg[im, im] = (Et[k] * G + kappa0) / i_mu[k] ** 3 - 0.5 / i_mu[k] ** 2
+        Hgg[im, ka] = Hgg[ka, im] = -0.5 * G / i_mu[k] ** 2 * ta[k]
+        Hgg[im, kb] = Hgg[kb, im] = -0.5 * G / i_mu[k] ** 2 * tb[k]
+        Hgg[ka:kb + 1, ka:kb + 1] = Hab[k]
+    rows = np.concatenate([np.arange(2 * P), np.stack([iem, ia, ibb], axis=1).ravel()])
+    jl = np.concatenate([np.ones((G, K)), dr], axis=1)          # chain of the local coordinates [e | r(i)]
+    loc = L * jl[:, :, None] * jl[:, None, :]
+    kk = np.arange(K)
+    loc[:, kk, kk] += Et[None, :]
+    loc[:, K + kk, K + kk] += g_r * 2.0 * r ** 3 - 0.5 / ig ** 2
+    out.update(Hgg=Hgg, rows=rows, Hx=None, loc=loc)
+    if B is None:                                              # the border stayed on the device (global_hessian)
+        return out
+    B = np.asarray(B).reshape(G, 4, K, P)
+    R = 2 * P + 3 * K
+    Hx = np.zeros((R, 2, G, K))                                 # [row, e or i, g, k]
+    Hx[:P, 0] = B[:, 0].transpose(2, 0, 1)
+    Hx[:P, 1] = B[:, 1].transpose(2, 0, 1) * dr[None]
+    Hx[P:2 * P, 0] = B[:, 2].transpose(2, 0, 1) * dv[:, None, None]
+    Hx[P:2 * P, 1] = B[:, 3].transpose(2, 0, 1) * dv[:, None, None] * dr[None]
+    for k in range(K):
+        o = 2 * P + 3 * k
+        Hx[o, 0, :, k] = -Et[k]
+        Hx[o + 1, 0, :, k] = d[:, k] * ta[k]
+        Hx[o + 2, 0, :, k] = d[:, k] * tb[k]
+        Hx[o + 1, 1, :, k] = 0.5 * ta[k] * dr[:, k]
+        Hx[o + 2, 1, :, k] = 0.5 * tb[k] * dr[:, k]
+    out['Hx'] = Hx.reshape(R, 2 * GK)
+    return out
+
+
+# ---- the block arrow: global block Hgg, border Hx (R x 2 G K) on the coupled rows, G local 2 K x 2 K blocks ------------------------
+def _to_groups(x, G, K):
+    """Local part (2 G K [x Q], order [e (G K) | i (G K)]) -> G x 2 K x Q."""
+    x = np.asarray(x, dtype=np.float64).reshape(2, G, K, -1)
+    return np.concatenate([x[0], x[1]], axis=1)
+
+
+def _from_groups(x, G, K):
+    """G x 2 K x Q -> 2 G K x Q in the order of the local part."""
+    return np.concatenate([x[:, :K].reshape(G * K, -1), x[:, K:].reshape(G * K, -1)], axis=0)
+
+
+def _local_chol(loc):
+    try:
+        return np.linalg.cholesky(loc)
+    except np.linalg.LinAlgError:
+        raise np.linalg.LinAlgError('a 2 K x 2 K local block is not positive definite')
+
+
+def block_arrow_to_free(cf, j1, j2, n_global, G, K):
+    """The pieces of `glmm_slopes_closed_forms` in FREE coordinates for an element-wise packing (j1 = d eta / d theta, j2 = its
+    second derivative, both D-vectors): (grad, Hgg, rows, Hx, loc)."""
+    g, ng = cf['grad'], n_global
+    jg = j1[:ng]
+    Hgg = cf['Hgg'] * jg[:, None] * jg[None, :] + np.diag(g[:ng] * j2[:ng])
+    rows = cf['rows']
+    Hx = None if cf['Hx'] is None else cf['Hx'] * jg[rows][:, None] * j1[ng:][None, :]
+    jl = _to_groups(j1[ng:], G, K)[:, :, 0]
+    dl = _to_groups(g[ng:] * j2[ng:], G, K)[:, :, 0]
+    loc = cf['loc'] * jl[:, :, None] * jl[:, None, :]
+    kk = np.arange(2 * K)
+    loc[:, kk, kk] += dl
+    return g * j1, Hgg, rows, Hx, loc
+
+
+def block_arrow_matvec(Hgg, rows, Hx, loc, v):
+    """H v for the block arrow: O(n_global^2 + P G K + G K^2)."""
+    ng, G, K = Hgg.shape[0], loc.shape[0], loc.shape[1] // 2
+    v = np.asarray(v, dtype=np.float64).ravel()
+    vg, vl = v[:ng], v[ng:]
+    og = Hgg @ vg
+    og[rows] += Hx @ vl
+    ol = Hx.T @ vg[rows] + _from_groups(np.einsum('gij,gjq->giq', loc, _to_groups(vl, G, K)), G, K)[:, 0]
+    return np.concatenate([og, ol])
+
+
+def _local_index(G, K):
+    """Position, in the local part of the vector, of coordinate i of group g's block: G x 2 K."""
+    gk = np.arange(G * K).reshape(G, K)
+    return np.concatenate([gk, G * K + gk], axis=1)
+
+
+def block_arrow_dense(Hgg, rows, Hx, loc):
+    ng, G, K = Hgg.shape[0], loc.shape[0], loc.shape[1] // 2
+    D = ng + 2 * G * K
+    H = np.zeros((D, D))
+    H[:ng, :ng] = Hgg
+    H[rows, ng:] = Hx
+    H[ng:, rows] = Hx.T
+    li = ng + _local_index(G, K)
+    H[li[:, :, None], li[:, None, :]] = loc
+    return H
+
+
+def _border_blocks(Hx, G, K):
+    """Hx (R x 2 G K) as G x 2 K x R: C_g^T per group."""
+    return _to_groups(Hx.T, G, K)
+
+
+def block_arrow_schur_term(rows, Hx, loc):
+    """M = sum_g C_g A_g^-1 C_g^T on the coupled rows (host route; the device route is lrvb_glmm_slopes_schur)."""
+    G, K = loc.shape[0], loc.shape[1] // 2
+    _local_chol(loc)
+    Ct = _border_blocks(Hx, G, K)
+    return np.einsum('gir,gis->rs', Ct, np.linalg.solve(loc, Ct))
+
+
+def block_arrow_local_solve(loc, B):
+    """A_g^-1 B_g for every group (B: G x 2 K [x Q])."""
+    B = np.asarray(B, dtype=np.float64)
+    return np.linalg.solve(loc, B.reshape(B.shape[0], B.shape[1], -1)).reshape(B.shape)
+
+
+def block_arrow_solve(Hgg, rows, Hx, loc, R, schur_solve=None):
+    """H^-1 R for the block arrow (R: D x Q or a D-vector) without the dense matrix: the G local blocks are solved (batched),
+    the result is reduced onto the coupled global rows, the Schur complement is factored and solved, and the local parameters
+    are back-substituted -- O(P G K Q + G K^3 + n_global^3).  `schur_solve` (n_global x Q -> n_global x Q) replaces the host
+    factorisation of the Schur complement.  A local block or a Schur complement that is not positive definite raises
+    `np.linalg.LinAlgError`."""
+    ng, G, K = Hgg.shape[0], loc.shape[0], loc.shape[1] // 2
+    R = np.asarray(R, dtype=np.float64)
+    vec = R.ndim == 1
+    R2 = R.reshape(ng + 2 * G * K, -1)
+    _local_chol(loc)
+    Ct = _border_blocks(Hx, G, K)                                        # G x 2 K x R
+    tl = np.linalg.solve(loc, _to_groups(R2[ng:], G, K))                 # H_ll^-1 R_l, G x 2 K x Q
+    rhs = R2[:ng].copy()
+    rhs[rows] -= np.einsum('gir,giq->rq', Ct, tl)
+    if schur_solve is None:
+        S = Hgg.copy()
+        S[np.ix_(rows, rows)] -= np.einsum('gir,gis->rs', Ct, np.linalg.solve(loc, Ct))
+        L = np.linalg.cholesky(0.5 * (S + S.T))                          # LinAlgError where it is not positive definite
+        xg = sp_linalg.cho_solve((L, True), rhs)
+    else:
+        xg = np.asarray(schur_solve(np.ascontiguousarray(rhs)), dtype=np.float64).reshape(ng, -1)
+    cl = np.einsum('gir,rq->giq', Ct, xg[rows])                          # H_lg x_g
+    out = np.vstack([xg, _from_groups(tl - np.linalg.solve(loc, cl), G, K)])
+    return out.ravel() if vec else out
+
+
+class LogisticGLMMSlopesObjective(DeclaredHypers):
+    _lrvb_device_functor = True
+
+    def __init__(self, par, x, y, z, groups, n_groups, beta_prior_info=1.0, mu_prior=(0.0, 1.0), tau_prior=(1.0, 1.0), gh_deg=20,
+                 names=('beta', 'mu', 'tau', 'u'), weights=None, device=0):
+        """names: the parameters of q(beta), q(mu), q(tau_k) -- named names[2] + str(k), k = 0..K-1 -- and q(u)."""
+        self.par = par
+        x, z = _hip.as_f64(x), _hip.as_f64(z)
+        self.n_obs, self.P = x.shape
+        if z.ndim != 2 or z.shape[0] != self.n_obs or not 1 <= z.shape[1] <= 4:
+            raise ValueError('z must be N x K with 1 <= K <= 4')
+        self.K = z.shape[1]
+        self.G = int(n_groups)
+        self._names = tuple(names)
+        self._index(par, names)
+        self.gh_x, self.gh_w = np.polynomial.hermite.hermgauss(int(gh_deg))
+        self._declare_hyper('beta_prior_info', HyperVectorParam('beta_prior_info', 1, lb=0.0, val=np.array([float(beta_prior_info)])))
+        self._declare_hyper('mu_prior', HyperVectorParam('mu_prior', 2, val=np.array(list(map(float, mu_prior)))))
+        self._declare_hyper('tau_prior', HyperVectorParam('tau_prior', 2, lb=0.0, val=np.array(list(map(float, tau_prior)))))
+        self.ctx = DeviceContext(par.layout_blocks(), loss='logistic', n_obs=self.n_obs, n_cols=self.P, device=device)
+        self.ctx.set_data(_hip.SLOT_X, x)
+        self.ctx.set_data(_hip.SLOT_Y, _hip.as_f64(y).ravel().copy())
+        self.ctx.set_groups(np.ascontiguousarray(np.asarray(groups).ravel(), dtype=np.int32), self.G)
+        self.ctx.set_group_design(z)
+        self.ctx.set_weights(np.ones(self.n_obs) if weights is None else _hip.as_f64(weights).ravel().copy())
+        self._external = None
+        self._point_key = None
+
+    tau_beta = property(lambda self: float(self._hyper_vec('beta_prior_info')[0]))
+    mu0 = property(lambda self: float(self._hyper_vec('mu_prior')[0]))
+    kappa0 = property(lambda self: float(self._hyper_vec('mu_prior')[1]))
+    a0 = property(lambda self: float(self._hyper_vec('tau_prior')[0]))
+    b0 = property(lambda self: float(self._hyper_vec('tau_prior')[1]))
+
+    def _index(self, par, names):
+        """The layout must be the canonical one of the module docstring in both vector and free coordinates, every coordinate
+        packed element-wise (identity, or lb + exp)."""
+        P, K, G = self.P, self.K, self.G
+        self.n_global = ng = 2 * P + 4 * K
+        GK = G * K
+        vi, fi = par.vector_indices_dict, par.free_indices_dict
+        want = [(names[0], 'mean', 0, P), (names[0], 'info', P, 2 * P), (names[1], 'mean', 2 * P, 2 * P + K),
+                (names[1], 'info', 2 * P + K, 2 * P + 2 * K)]
+        for k in range(K):
+            o = 2 * P + 2 * K + 2 * k
+            want += [(names[2] + str(k), 'shape', o, o + 1), (names[2] + str(k), 'rate', o + 1, o + 2)]
+        want += [(names[3], 'mean', ng, ng + GK), (names[3], 'info', ng + GK, ng + 2 * GK)]
+        msg = ('the parameter must be [UVNParamVector {} ({}) | UVNParamVector {} ({}) | GammaParam {}0 .. {}{} | UVNParamArray {} ({}, {})] '
+               'in this order, the group effects pushed last'.format(names[0], P, names[1], K, names[2], names[2], K - 1, names[3], G, K))
+        for name, field, lo, hi in want:
+            if name not in vi:
+                raise ValueError(msg)
+            sub = par[name]
+            for top, inner in ((vi, sub.vector_indices_dict), (fi, sub.free_indices_dict)):
+                if top[name].start + inner[field].start != lo or top[name].start + inner[field].stop != hi:
+                    raise ValueError(msg)
+        if par.vector_size() != ng + 2 * GK or par.free_size() != ng + 2 * GK:
+            raise ValueError('the parameter holds more than the blocks of the model')
+        lb = []
+        for blk in par.layout_blocks():
+            if blk['kind'] != _hip.BLOCK_BOX or np.isfinite(blk['ub']) or blk['free_size'] != blk['vec_size']:
+                raise ValueError('every coordinate must be unconstrained or bounded below only')
+            lb.extend([blk['lb']] * blk['vec_size'])
+        self._lb = np.asarray(lb, dtype=np.float64)
+        self._bounded = np.isfinite(self._lb)
+
+    # ---- the point --------------------------------------------------------------------------------------------------
+    def _eta(self, x, is_free):
+        """Vector coordinates of x; `par` holds the evaluation point afterwards (the side-effect contract of the functors)."""
+        x = _hip.as_f64(x).ravel()
+        if is_free:
+            self.par.set_free(x)
+            return np.asarray(self.par.get_vector(), dtype=np.float64).ravel()
+        self.par.set_vector(x)
+        return x
+
+    def _jac(self, eta):
+        """Element-wise packing: d eta / d theta and d2 eta / d theta2."""
+        j1 = np.where(self._bounded, eta - np.where(self._bounded, self._lb, 0.0), 1.0)
+        return j1, np.where(self._bounded, j1, 0.0)
+
+    # ---- data pieces (GPU) ------------------------------------------------------------------------------------------
+    def _pieces_of(self, val, gg, Hb, gs):
+        if gs is None:
+            return dict(value=val, g_glob=None)
+        gl, loc, border = unpack_group_sums(gs, self.P, self.K)
+        return dict(value=val, g_glob=gg, g_loc=gl, Hb=Hb, loc=loc, border=border)
+
+    def _device_terms(self, eta, want_grad, want_hess, want_border=True):
+        P, K, G = self.P, self.K, self.G
+        _, ib, _, _, _, _, e, ig = _split_eta(eta, P, K, G)
+        out = self.ctx.glmm_slopes_terms(eta[:P], 1.0 / ib, e, 1.0 / ig, self.gh_x, self.gh_w, want_grad=want_grad or want_hess,
+                                         want_hess=want_hess, want_border=want_border)
+        return self._pieces_of(*out)
+
+    def stats_size(self):
+        return 1 + 2 * self.P + 3 * self.P ** 2 + self.G * group_sums_ncol(self.P, self.K)[1]
+
+    def local_stats(self, eta):
+        """[value | global gradient (2 P) | H blocks (3 P^2) | group sums (G x ncol)] of THIS process's rows in the coordinates
+        (m, v, e, r) at the vector-coordinate point eta: the buffer of one host-side sum over shards (a group may straddle
+        shards: its sums add).  With a reduce hook on the context it is already the sum over the ranks."""
+        eta = _hip.as_f64(eta).ravel()
+        _, ib, _, _, _, _, e, ig = _split_eta(eta, self.P, self.K, self.G)
+        val, gg, Hb, gs = self.ctx.glmm_slopes_terms(eta[:self.P], 1.0 / ib, e, 1.0 / ig, self.gh_x, self.gh_w)
+        return np.concatenate([[val], gg, Hb.ravel(), gs.ravel()])
+
+    def set_reduced_stats(self, flat, eta=None):
+        """Install statistics summed over all shards for the point eta (None = use this process's own rows again)."""
+        refuse_double_reduction(getattr(self, 'ctx', None), flat)
+        self._point_key = None
+        if flat is None:
+            self._external = None
+            return
+        flat = np.asarray(flat, dtype=np.float64).ravel()
+        if flat.size != self.stats_size() or eta is None:
+            raise ValueError('expected {} statistics and the point they were formed at'.format(self.stats_size()))
+        self._external = (np.asarray(eta, dtype=np.float64).copy(), flat.copy())
+
+    def _data(self, eta, want_grad, want_hess, want_border=True):
+        if self._external is None:
+            return self._device_terms(eta, want_grad, want_hess, want_border)
+        if not np.array_equal(self._external[0], eta):
+            raise ValueError('the installed statistics were formed at another point')
+        P, G = self.P, self.G
+        f = self._external[1]
+        o = 1 + 2 * P
+        return self._pieces_of(float(f[0]), f[1:o], f[o:o + 3 * P * P].reshape(3, P, P), f[o + 3 * P * P:].reshape(G, -1))
+
+    def _closed(self, eta, want_grad=True, want_hess=True, want_border=True):
+        d = self._data(eta, want_grad, want_hess, want_border)
+        if not (want_grad or want_hess):
+            d = dict(value=d['value'])
+        return glmm_slopes_closed_forms(self.P, self.K, self.G, eta, d, self.tau_beta, self.mu0, self.kappa0, self.a0, self.b0,
+                                        want_hess=want_hess)
+
+    def _arrow(self, x, is_free):
+        """(grad, Hgg, rows, Hx, loc) at x in its own coordinates, cached per point and hyper-parameters."""
+        key = (bool(is_free), np.asarray(x, dtype=np.float64).tobytes(), self._hyper_state_key(),
+               None if self._external is None else id(self._external))
+        if self._point_key != key:
+            eta = self._eta(x, is_free)
+            cf = self._closed(eta)
+            if is_free:
+                j1, j2 = self._jac(eta)
+                self._pieces = block_arrow_to_free(cf, j1, j2, self.n_global, self.G, self.K)
+            else:
+                self._pieces = (cf['grad'], cf['Hgg'], cf['rows'], cf['Hx'], cf['loc'])
+            self._point_key = key
+        else:
+            self._eta(x, is_free)
+        return self._pieces
+
+    # ---- functor protocol -------------------------------------------------------------------------------------------
+    def __call__(self):
+        return self.value(np.asarray(self.par.get_free(), dtype=np.float64), True)
+
+    @_hip.host_blas
+    def value(self, x, is_free=True):
+        return self._closed(self._eta(x, is_free), False, False)['value']
+
+    @_hip.host_blas
+    def grad(self, x, is_free=True):
+        eta = self._eta(x, is_free)
+        g = self._closed(eta, True, False)['grad']
+        return g * self._jac(eta)[0] if is_free else g
+
+    jacobian = grad
+
+    @_hip.host_blas
+    def hessian(self, x, is_free=True):
+        if self.par.vector_size() > 8192:
+            raise MemoryError('dense Hessian of {} parameters: use global_hessian() (Schur complement) or hvp()'.format(self.par.vector_size()))
+        _, Hgg, rows, Hx, loc = self._arrow(x, is_free)
+        return block_arrow_dense(Hgg, rows, Hx, loc)
+
+    @_hip.host_blas
+    def hvp(self, x, v, is_free=True):
+        _, Hgg, rows, Hx, loc = self._arrow(x, is_free)
+        return block_arrow_matvec(Hgg, rows, Hx, loc, v)
+
+    @_hip.host_blas
+    def sparse_hessian(self, free_val):
+        """The free-coordinate Hessian as a scipy CSR block arrow: global block, border and 2 K x 2 K local blocks."""
+        from .objectives import get_sparse_sub_hessian, get_sparse_sub_matrix
+        _, Hgg, rows, Hx, loc = self._arrow(free_val, True)
+        ng, G, K = self.n_global, self.G, self.K
+        D = ng + 2 * G * K
+        gi, li = np.arange(ng), np.arange(ng, D)
+        H = get_sparse_sub_hessian(Hgg, gi, D)
+        H = H + get_sparse_sub_matrix(Hx, rows, li, D, D) + get_sparse_sub_matrix(Hx.T, li, rows, D, D)
+        idx = ng + _local_index(G, K)
+        ri = np.broadcast_to(idx[:, :, None], loc.shape).ravel()
+        ci = np.broadcast_to(idx[:, None, :], loc.shape).ravel()
+        H = H + sp_sparse.coo_matrix((loc.ravel(), (ri, ci)), shape=(D, D))
+        return H.tocsr()
+
+    # ---- Schur complement onto the global block -----------------------------------------------------------------------
+    def _ensure_gctx(self):
+        if not hasattr(self, '_gctx'):
+            blocks, size = [], 0
+            for b in self.par.layout_blocks():
+                if size >= self.n_global:
+                    break
+                blocks.append(b)
+                size += b['vec_size']
+            assert size == self.n_global
+            self._gctx = DeviceContext(blocks, quad_kind=_hip.QUAD_DIAG, device=self.ctx.device)
+        return self._gctx
+
+    @_hip.host_blas
+    def global_hessian(self, free_val, want_host=True):
+        """H_S = H_gg - H_gl H_ll^-1 H_lg in FREE coordinates (n_global x n_global): its inverse is the linear-response
+        covariance of the global parameters.  Device route: the border formed by `lrvb_glmm_slopes_terms` stays on the GPU and
+        `lrvb_glmm_slopes_schur` eliminates the 2 G K local parameters there; the host adds the N-independent terms to the G local
+        blocks (free coordinates) and sends their upper triangles with the chain factors and the closed-form border entries.
+        The result stays resident on the global context for `chol_factor_last`."""
+        fv = _hip.as_f64(free_val).ravel()
+        P, K, G, ng = self.P, self.K, self.G, self.n_global
+        eta = self._eta(fv, True)
+        j1, j2 = self._jac(eta)
+        cf = self._closed(eta, want_border=False)    # the group sums of the point stay resident; the border is not copied back
+        g, Hgg, rows = cf['grad'], cf['Hgg'].copy(), cf['rows']
+        loc_f = block_arrow_to_free(cf, j1, j2, ng, G, K)[4]
+        if self._external is None:
+            _, ib, e_mu, _, a, b, e, ig = _split_eta(eta, P, K, G)
+            r = 1.0 / ig
+            d = e - e_mu[None, :]
+            ta, tb = 1.0 / b, -a / b ** 2
+            closed = np.zeros((G, 2 * K, 3))
+            closed[:, :K, 0], closed[:, :K, 1], closed[:, :K, 2] = -(a / b)[None, :], d * ta[None, :], d * tb[None, :]
+            closed[:, K:, 1], closed[:, K:, 2] = 0.5 * ta[None, :], 0.5 * tb[None, :]
+            jl = _to_groups(j1[ng:], G, K)[:, :, 0]
+            scale = np.concatenate([jl[:, :K], -r * r * jl[:, K:]], axis=1)
+            iu = np.triu_indices(2 * K)
+            M = self.ctx.glmm_slopes_schur(loc_f[:, iu[0], iu[1]], scale, closed)     # coordinates [m | v | e_mu_k, a_k, b_k]
+            dv = np.concatenate([np.ones(P), -1.0 / ib ** 2, np.ones(3 * K)])
+            M = M * dv[:, None] * dv[None, :]
+        else:
+            M = block_arrow_schur_term(rows, cf['Hx'] * j1[ng:][None, :], loc_f)
+        Hgg[np.ix_(rows, rows)] -= M
+        gc = self._ensure_gctx()
+        gc.hvec_begin()
+        gc.hvec_add_block(Hgg, 0, 0)
+        out = gc.hvec_finish(fv[:ng], g[:ng], True, want_host=want_host)
+        self._schur_key = self._resident_key(fv)
+        return out
+
+    def _resident_key(self, fv):
+        """What the Schur complement resident on the global context was built at: point and hyper-parameters."""
+        return (np.asarray(fv, dtype=np.float64).tobytes(), self._hyper_state_key(),
+                None if self._external is None else id(self._external))
+
+    # ---- the whole arrow: solve, covariance of any moment ----------------------------------------------------------------
+    @_hip.host_blas
+    def solve(self, x, R, is_free=True, resident_factor=False):
+        """H^-1 R at x (R: D x Q or a D-vector, local rows allowed) by `block_arrow_solve`.  resident_factor=True solves the
+        Schur complement with the factor on the global context: call `global_hessian(x, want_host=False)` and
+        `_ensure_gctx().chol_factor_last()` at the same point first (free coordinates); a factor built at another point or
+        under other hyper-parameters is refused with a ValueError."""
+        _, Hgg, rows, Hx, loc = self._arrow(x, is_free)
+        if resident_factor and (not is_free or getattr(self, '_schur_key', None) != self._resident_key(_hip.as_f64(x).ravel())):
+            raise ValueError('resident_factor=True needs global_hessian(x, want_host=False) and chol_factor_last() at this point, '
+                             'with these hyper-parameters, in free coordinates')
+        schur_solve = self._ensure_gctx().chol_solve if resident_factor else None
+        return block_arrow_solve(Hgg, rows, Hx, loc, R, schur_solve=schur_solve)
+
+    def lrvb_cov(self, x, moment_jac, is_free=True):
+        """M H^-1 M^T (Q x Q): the linear-response covariance of the moments M theta, M = moment_jac being Q x D (columns of the
+        group effects allowed) or Q x n_global (zero-padded)."""
+        M = np.atleast_2d(_hip.as_f64(moment_jac))
+        D = self.n_global + 2 * self.G * self.K
+        if M.ndim != 2 or M.shape[1] not in (D, self.n_global):
+            raise ValueError('moment Jacobian must have {} (all parameters) or {} (global parameters) columns'.format(D, self.n_global))
+        if M.shape[1] != D:
+            M = np.hstack([M, np.zeros((M.shape[0], D - M.shape[1]))])
+        return M @ self.solve(x, np.ascontiguousarray(M.T), is_free)
+
+    # ---- hyper-parameters ---------------------------------------------------------------------------------------------
+    def _prior_hyper(self, kind, eta_g, want):
+        P, K, ng = self.P, self.K, self.n_global
+        m, ib = eta_g[:P], eta_g[P:2 * P]
+        e_mu, i_mu = eta_g[2 * P:2 * P + K], eta_g[2 * P + K:2 * P + 2 * K]
+        if kind == 'beta_prior_info':
+            if want == 'grad':
+                return np.array([0.5 * (np.sum(m * m) + np.sum(1.0 / ib))])
+            C = np.zeros((ng, 1))
+            C[:P, 0], C[P:2 * P, 0] = m, -0.5 / ib ** 2
+            return C
+        if kind == 'mu_prior':
+            if want == 'grad':
+                return np.array([-self.kappa0 * np.sum(e_mu - self.mu0), 0.5 * np.sum((e_mu - self.mu0) ** 2 + 1.0 / i_mu)])
+            C = np.zeros((ng, 2))
+            C[2 * P:2 * P + K, 0], C[2 * P:2 * P + K, 1] = -self.kappa0, e_mu - self.mu0
+            C[2 * P + K:2 * P + 2 * K, 1] = -0.5 / i_mu ** 2
+            return C
+        if kind != 'tau_prior':
+            raise NotImplementedError(kind)
+        out = np.zeros(2) if want == 'grad' else np.zeros((ng, 2))
+        for k in range(K):
+            ia = 2 * P + 2 * K + 2 * k
+            a, b = eta_g[ia], eta_g[ia + 1]
+            out = out + (gamma_prior_hyper_grad(a, b, special) if want == 'grad' else gamma_prior_hyper_cross(ng, ia, ia + 1, a, b, special))
+        return out
+
+    def hyper_grad(self, hyper_par, val1, val1_is_free):
+        return self._prior_hyper(self.hyper_kind(hyper_par), self._eta(val1, val1_is_free)[:self.n_global], 'grad')
+
+    def global_cross_hessian(self, hyper_par, val, is_free=True):
+        """The n_global rows of the cross Hessian with a prior hyper-parameter (its 2 G K local rows are zero)."""
+        eta = self._eta(val, is_free)
+        C = self._prior_hyper(self.hyper_kind(hyper_par), eta[:self.n_global], 'cross')
+        return C * self._jac(eta)[0][:self.n_global, None] if is_free else C
+
+    def cross_hessian(self, hyper_par, val1, val1_is_free):
+        """d2 f / d par d hyper^T, all rows (dense protocol): the priors do not touch the local rows."""
+        val1 = _hip.as_f64(val1).ravel()
+        Cg = self.global_cross_hessian(hyper_par, val1, is_free=val1_is_free)
+        return np.vstack([Cg, np.zeros((val1.size - self.n_global, Cg.shape[1]))])
+
+    def global_sensitivity(self, hyper_par, free_val):
+        """d theta_global / d hyper^T = -H_S^-1 C_g (n_global x Ph) for a prior hyper-parameter: its cross Hessian has no local
+        rows, so the local parameters enter through the Schur complement only."""
+        Cg = self.global_cross_hessian(hyper_par, free_val)
+        gc = self._ensure_gctx()
+        self.global_hessian(free_val, want_host=False)
+        gc.chol_factor_last()
+        return -gc.chol_solve(Cg)

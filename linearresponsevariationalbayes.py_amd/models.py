@@ -353,6 +353,48 @@ class DeviceContext(object):
         self._check(self._lib.lrvb_glmm_schur(self._h, _hip.ptr(A), _hip.ptr(sc), _hip.ptr(cl), G, _hip.ptr(M)))
         return M
 
+    def set_group_design(self, z):
+        """The group design z (N x K, 1 <= K <= 4) of the logistic mixed model with slopes (lrvb_set_group_design)."""
+        z = _hip.as_f64(z)
+        if z.ndim != 2:
+            raise ValueError('the group design is N x K')
+        self._check(self._lib.lrvb_set_group_design(self._h, _hip.ptr(z), z.shape[0], z.shape[1]))
+
+    def glmm_slopes_terms(self, mean, var, e, r, gh_x, gh_w, want_grad=True, want_hess=True, want_border=True):
+        """Data term of the logistic mixed model with K effects per group in the coordinates (mean, var, e, r), e and r being G x K
+        (lrvb_glmm_slopes_terms): value, global gradient (2 P), the Hessian blocks (3 x P x P) and the group sums in the column
+        layout of include/lrvb_hip.h -- G x ncol, or G x nsc (no border) with want_border=False, or None where neither the
+        gradient nor the Hessian is asked for.  The group sums stay resident for `glmm_slopes_schur`."""
+        m, v = _hip.as_f64(mean).ravel(), _hip.as_f64(var).ravel()
+        e, r = _hip.as_f64(e), _hip.as_f64(r)
+        gx, gw = _hip.as_f64(gh_x).ravel(), _hip.as_f64(gh_w).ravel()
+        P = self.n_cols
+        if e.ndim != 2 or r.shape != e.shape or m.size != P or v.size != P or gx.size != gw.size:
+            raise ValueError('expected mean and var of length {}, e and r of one shape G x K and as many weights as nodes'.format(P))
+        G, K = e.shape
+        nsc = 2 * K + K * (2 * K + 1)
+        val = np.empty(1)
+        gg = np.empty(2 * P) if want_grad else None
+        Hb = np.empty((3, P, P)) if want_hess else None
+        border = bool(want_hess and want_border)
+        gs = np.empty((G, nsc + (4 * K * P if border else 0))) if (want_grad or want_hess) else None
+        self._check(self._lib.lrvb_glmm_slopes_terms(self._h, _hip.ptr(m), _hip.ptr(v), P, _hip.ptr(e), _hip.ptr(r), G, K, _hip.ptr(gx),
+                                                    _hip.ptr(gw), gx.size, _hip.ptr(val), _hip.ptr(gg), _hip.ptr(Hb), _hip.ptr(gs),
+                                                    1 if border else 0))
+        return float(val[0]), gg, Hb, gs
+
+    def glmm_slopes_schur(self, local_blocks, border_scale, closed_rows):
+        """M ((2 P + 3 K)^2) = sum_g C_g^T A_g^-1 C_g from the resident group sums of the last `glmm_slopes_terms`
+        (lrvb_glmm_slopes_schur): G x K (2 K + 1) upper triangles, G x 2 K chain factors, G x 2 K x 3 closed-form entries."""
+        A, sc, cl = _hip.as_f64(local_blocks), _hip.as_f64(border_scale), _hip.as_f64(closed_rows)
+        G, K = sc.shape[0], sc.shape[1] // 2
+        if sc.shape != (G, 2 * K) or A.shape != (G, K * (2 * K + 1)) or cl.shape != (G, 2 * K, 3):
+            raise ValueError('expected G x K (2 K + 1) local blocks, G x 2 K chain factors and G x 2 K x 3 closed-form entries')
+        R = 2 * self.n_cols + 3 * K
+        M = np.empty((R, R))
+        self._check(self._lib.lrvb_glmm_slopes_schur(self._h, _hip.ptr(A), _hip.ptr(sc), _hip.ptr(cl), G, K, _hip.ptr(M)))
+        return M
+
     def _glmm_influence_args(self, mean, var, e, r, gh_x, gh_w, A):
         """The point and the operand A (Q x (2 P + 2 G), columns [A_m | A_v | A_e | A_r]) in the layout of the C entries:
         A_global (Q x 2 P) and A_local (G x 2 Q, row g = [A_e[:, g] | A_r[:, g]])."""

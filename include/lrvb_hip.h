@@ -446,6 +446,40 @@ int lrvb_glmm_group_influence(lrvb_ctx* ctx, const double* mean, const double* v
                               int64_t G, const double* gh_x, const double* gh_w, int32_t n_nodes, const double* A_global,
                               const double* A_local, int64_t Q, double* out);
 
+/* Streamed weight influence of the logistic mixed model with K <= 4 effects per group.  Point arguments as
+ * lrvb_glmm_slopes_terms (e, r: G x K, group-major).  Per observation, PER UNIT WEIGHT, with a1', a2' as above at
+ *   rho_n = x_n . mean + z_n . e_g(n),   s_n = (x_n o x_n) . var + (z_n o z_n) . r_g(n),
+ * the gradient of row n's term in (mean, var, e, r) is [a1' x_n | a2' x_n o x_n | at g(n): a1' z_n (K), a2' z_n o z_n (K)].
+ * For an operand A (Q x (2 P + 2 G K), columns [A_m | A_v | A_e (G K, group-major) | A_r (G K)]) given as
+ *   A_global (Q x 2 P, row-major: row q = [A_m[q] | A_v[q]])   and
+ *   A_local  (G x 2 K x Q, row-major: group g holds 2 K vectors of Q contiguous outputs in the order
+ *             [A_e[., g, 0] .. A_e[., g, K-1] | A_r[., g, 0] .. A_r[., g, K-1]]; at K = 1 the G x 2 Q layout above)
+ * the entry writes, for n0 <= n < n1,
+ *   out[n - n0][q] = a1' (x_n . A_m[q] + sum_k z_nk A_e[q, g(n), k]) + a2' ((x_n o x_n) . A_v[q] + sum_k z_nk^2 A_r[q, g(n), k])
+ * ((n1 - n0) x Q, host).  At K = 1 with z = 1 this is the row of lrvb_glmm_obs_influence.  The weights do not enter.  ONE pass
+ * over the rows of the window in their original order for any Q >= 1, the quadrature once per row, the two global contractions
+ * on the fp64 matrix cores in blocks of 16 outputs; the 2 K local values of a row are gathered (16 consecutive doubles per
+ * coordinate and block) and added behind the matrix product, because the rows of one tile belong to different groups.  A window
+ * equals the same rows of the full result bitwise.  Per-observation rows: rank-local, NO reduce-hook call.
+ * Memory: nothing is chunked inside the call; Q is bounded by (n1 - n0) Q + 2 G K Q doubles of free device memory (N = 1e6,
+ * G = 1e4, K = 4, Q = 16: 128 MB + 10 MB): a caller with a wide operand walks row windows or blocks of outputs.
+ * Errors as lrvb_glmm_slopes_terms (P > 64, K < 1, K > 4 or more than 128 nodes: LRVB_ERR_UNSUPPORTED; groups, the group design,
+ * X or y not set, or a group design that is not n_obs x K: LRVB_ERR_STATE; var_j <= 0 or r_gk <= 0: LRVB_ERR_INVALID; G is not
+ * the number of groups: LRVB_ERR_SIZE); n0 > n1 or n1 > n_obs: LRVB_ERR_INVALID, as lrvb_glmm_obs_influence.                 */
+int lrvb_glmm_slopes_obs_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                                   int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
+                                   const double* A_global, const double* A_local, int64_t Q, int64_t n0, int64_t n1, double* out);
+/* Group influence of that model: out[g][q] = sum over the rows n of group g of w_n * (the row of lrvb_glmm_slopes_obs_influence)
+ * (G x Q, host): leave one cluster out; the group's own prior terms on u_g. are NOT part of it.  One pass over the group-sorted
+ * rows forms, per group and in a fixed order (no atomics: two calls at one point are bitwise equal),
+ *   [sum w a1' z (K) | sum w a2' z o z (K) | sum w a1' x (P) | sum w a2' x o x (P)]        (2 K + 2 P numbers);
+ * the contraction with A is a (G x 2 P)(2 P x Q) product plus the 2 K local columns and does not touch the observations again.
+ * An empty group gives an exact zero row.  Reduce hook: the G x Q result is a sum over observations (a group may straddle
+ * ranks) and goes through the hook exactly once, as one buffer of G Q doubles.  Errors as lrvb_glmm_slopes_obs_influence.     */
+int lrvb_glmm_slopes_group_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e,
+                                     const double* r, int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
+                                     const double* A_global, const double* A_local, int64_t Q, double* out);
+
 /* ---- multinomial (softmax) regression ---------------------------------------------------------
  * K classes (2 <= K <= 17), labels y_n in {0 .. K-1}, class 0 the reference; coefficients beta ((K-1) x P, row-major, row a
  * belongs to class a + 1, P = n_cols <= 1024), z_na = x_n . beta_a, z_n0 = 0, p_n = softmax(z_n).  The data term
@@ -657,7 +691,7 @@ int lrvb_hessian_dev(lrvb_ctx* ctx, const double* free_dev, double* H_dev, int64
  * lrvb_mixture_stats ([S64 | val2 | count of indefinite rows | packed Schur operand]: every rank fails together when
  * any rank has an indefinite row), lrvb_quadform_gram ([K4 tiles | s | observation count]) and
  * lrvb_logitnormal_terms ([Hessian blocks | gradient | value], the part that was asked for), lrvb_glmm_terms and
- * lrvb_glmm_slopes_terms ([Hessian blocks | group sums | gradient | value]) and lrvb_glmm_group_influence (the G x Q result).  A call must therefore
+ * lrvb_glmm_slopes_terms ([Hessian blocks | group sums | gradient | value]) and lrvb_glmm_group_influence / lrvb_glmm_slopes_group_influence (the G x Q result).  A call must therefore
  * be made by ALL ranks, with the same arguments apart from the rows they hold.  lrvb_hessian_partial_dev and the
  * per-observation row outputs (lrvb_obs_*, the gradient rows of lrvb_mixture_rows) stay rank-local by contract.
  * fn == NULL removes the hook.                                                                                */

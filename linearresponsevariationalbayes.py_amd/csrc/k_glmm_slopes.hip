@@ -288,3 +288,290 @@ int launch_glmm_slopes_schur_rows(lrvb_ctx* c, int Kz, const double* gsum, const
     HIP_TRY(hipGetLastError());
     return LRVB_OK;
 }
+
+// ---- streamed weight influence (lrvb_glmm_slopes_obs_influence) -------------------------------------------
+// out[n - n0][q] = a1' (x_n . A_m[q] + sum_k z_nk A_e[q, g(n), k]) + a2' ((x_n o x_n) . A_v[q] + sum_k z_nk^2 A_r[q, g(n), k]),
+// a1' = psi_rho - y_n, a2' = psi_s PER UNIT WEIGHT (w_n does not enter).  Built like glmm_infl_rows_kernel (k_glmm.hip): ONE pass
+// over the rows n0..n1 in their original order, X and Z read once for any Q; a workgroup (4 waves) walks tiles of GS_T = 64 rows:
+//   1. the tile (contiguous in X) is staged in LDS, row stride GSI_XS, the row's K values of z behind its x columns (columns
+//      P .. P + K - 1, as glmm_slopes_rows_kernel stages them);
+//   2. four lanes share a row for the two dot products (lane q4 also takes the z column q4) and the quadrature; only E g1 and
+//      E g2 are formed, and a1', a2' go to LDS;
+//   3. wave w owns the rows 16 w .. 16 w + 15.  Per block of 16 outputs the contractions X A_m^T and (X o X) A_v^T run as
+//      16 x 16 x 4 fp64 MFMA tiles, two accumulator chains each, x o x squared in a register.  The B operand is zero past Q and
+//      past P, so the staged z columns (and whatever lies behind them) that the last k-step reads meet zeros;
+//   4. epilogue, in the D layout (register r <-> row (l >> 4) + 4 r, column l & 15): the 2 K gathered values of A_local
+//      (G x 2 K x Q: 16 consecutive doubles for the 16 lanes of a block), weighted by z_nk and z_nk^2 from the staged row, are
+//      added, the two halves are combined with a1', a2', and 16 consecutive doubles per row are written.
+// The group-dependent term CANNOT go through the matrix cores: the B operand of an MFMA tile is shared by its 16 rows, and those
+// rows belong to different groups.  K is a runtime value: the epilogue is a loop over scalars, no indexed register array.
+// With Q <= 16 the B fragments are loaded once per workgroup and stay in registers; with more outputs the blocks of 16 are a
+// loop INSIDE the tile.  No atomics, no group walk.
+//
+// GSI_XS.  Bank of a double at index a: a mod 32 (ds_read_b64: 64 dword banks, the two 32-lane halves separately).
+//   (a) MFMA operand: lane (i = l & 15, k = l >> 4) reads row i, column 4 kk + k; a half holds i = 0..15, k in {0, 1} (or
+//       {2, 3}): banks i S + k (+ const) must be 32 different values, so S mod 32 = 2 x an odd number: i S runs through the
+//       16 even residues.  Stride 66 of k_glmm.hip is too short for 64 + 4 columns; 68 puts rows i and i + 8 on one bank (2-way).
+//   (b) dot products: a half holds 8 rows x 4 lanes.  With lane q4 on the columns q4, q4 + 4, .. (k_glmm.hip) the banks are
+//       row S + q4: different only if S = 4 mod 8 -- never together with (a) (stride 66 is 2-way there).
+//   S = 70 = 6 mod 32 meets (a); the row offsets 6 row mod 32, row = 0..7, are {0, 6, 12, 18, 24, 30, 4, 10}: all even, and no
+//   two of them 16 apart.  So the four lanes of a row take the columns c0 + 2 t + 32 h, c0 = {0, 1, 16, 17}[q4], t = 0..7,
+//   h = 0, 1: at every step the 32 lanes read row S + {0, 1, 16, 17} + 2 t -- 32 different banks.  Both patterns are free of
+//   conflicts.  (The single read of z, column P + q4, may be 2-way; it happens once per row.)
+constexpr int GSI_XS = 70;
+
+typedef double gsi_d4 __attribute__((ext_vector_type(4)));
+
+// The per-row part both influence kernels share, the sibling of gi_psi_derivs (k_glmm.hip) with the z terms and the column map
+// of GSI_XS: every one of the four lanes of the staged row xr returns e1 = psi_rho and e2 = E g2 = 2 psi_s.  Called by all lanes.
+__device__ __forceinline__ void gsi_psi_derivs(const double* xr, bool live, int g, int q4, int P, int Kz, int nq, const double* ms,
+                                               const double* vs, const double* __restrict__ eg, const double* __restrict__ rg,
+                                               const double* sx, const double* sw, double& e1, double& e2)
+{
+    double rho = 0.0, s = 0.0;
+    if (live) {
+        for (int h = (q4 & 1) + 16 * (q4 >> 1); h < P; h += 32)
+            for (int j = h; j < h + 16 && j < P; j += 2) { const double x = xr[j]; rho += x * ms[j]; s += x * x * vs[j]; }
+        if (q4 < Kz) {
+            const i64 gk = (i64)g * Kz + q4;
+            const double z = xr[P + q4];
+            rho += z * eg[gk]; s += z * z * rg[gk];
+        }
+    }
+    rho += __shfl_xor(rho, 1); s += __shfl_xor(s, 1);
+    rho += __shfl_xor(rho, 2); s += __shfl_xor(s, 2);
+    e1 = 0.0; e2 = 0.0;
+    if (live) {
+        const double sd = sqrt(fmax(s, 0.0));
+        for (int k = q4; k < nq; k += 4) {
+            const double t = rho + sd * sx[k], wk = sw[k];
+            const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
+            const double sg = t >= 0.0 ? ie : e * ie;
+            e1 += wk * sg; e2 += wk * e * ie * ie;
+        }
+    }
+    e1 += __shfl_xor(e1, 1); e2 += __shfl_xor(e2, 1);
+    e1 += __shfl_xor(e1, 2); e2 += __shfl_xor(e2, 2);
+}
+
+__global__ __launch_bounds__(256)
+void glmm_slopes_infl_rows_kernel(i64 n0, i64 R /* rows of the window */, int P, int Kz, const double* __restrict__ X,
+                                  const double* __restrict__ Z, const double* __restrict__ y, const int* __restrict__ gid,
+                                  const double* __restrict__ m, const double* __restrict__ vb, const double* __restrict__ eg,
+                                  const double* __restrict__ rg, const double* __restrict__ gx, const double* __restrict__ gw, int nq,
+                                  const double* __restrict__ Ag /* Q x 2 P */, const double* __restrict__ Al /* G x 2 K x Q */, int Q,
+                                  double* __restrict__ out /* R x Q */)
+{
+    __shared__ double xs[GS_T * GSI_XS], a1s[GS_T], a2s[GS_T], ms[64], vs[64], sx[128], sw[128];
+    __shared__ int s_gid[GS_T];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, l4 = lane >> 4;
+    const double r2 = 1.4142135623730951, ispi = 0.5641895835477563;     // sqrt(2), 1 / sqrt(pi)
+    if (tid < nq) { sx[tid] = r2 * gx[tid]; sw[tid] = ispi * gw[tid]; }
+    if (tid < 64) { ms[tid] = tid < P ? m[tid] : 0.0; vs[tid] = tid < P ? vb[tid] : 0.0; }
+    for (int e = tid; e < GS_T * GSI_XS; e += 256) xs[e] = 0.0;          // what no tile writes stays zero (finite) for the whole kernel
+    const int KS = (P + 3) >> 2;                                         // k-steps of the contractions
+    const int nqb = (Q + 15) >> 4;
+    const int K2 = 2 * Kz;
+    double bm[16], bv[16];
+    auto load_b = [&](int qb) {
+        const int q = 16 * qb + l15;
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk) {
+            const int k = 4 * kk + l4;
+            const bool ok = q < Q && k < P;
+            bm[kk] = ok ? Ag[(i64)q * 2 * P + k] : 0.0;
+            bv[kk] = ok ? Ag[(i64)q * 2 * P + P + k] : 0.0;
+        }
+    };
+    if (nqb == 1) load_b(0);
+    const i64 n_tiles = (R + GS_T - 1) / GS_T;
+    const int row = tid >> 2, q4 = tid & 3;
+    for (i64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const i64 t0 = tile * GS_T;
+        const int rows = (int)(R - t0 < GS_T ? R - t0 : GS_T);
+        __syncthreads();                                                 // the previous tile is consumed (and the nodes are in place)
+        if (tid < GS_T) s_gid[tid] = tid < rows ? gid[n0 + t0 + tid] : 0;
+        {
+            const double* src = X + (n0 + t0) * (i64)P;
+            for (int e = tid; e < rows * P; e += 256) { const int rr = e / P, cc = e - rr * P; xs[rr * GSI_XS + cc] = src[e]; }
+            const double* zsrc = Z + (n0 + t0) * (i64)Kz;
+            for (int e = tid; e < rows * Kz; e += 256) { const int rr = e / Kz, cc = e - rr * Kz; xs[rr * GSI_XS + P + cc] = zsrc[e]; }
+        }
+        __syncthreads();
+        double e1, e2;
+        gsi_psi_derivs(xs + row * GSI_XS, row < rows, s_gid[row], q4, P, Kz, nq, ms, vs, eg, rg, sx, sw, e1, e2);
+        if (q4 == 0) {
+            double k1 = 0.0, k2 = 0.0;
+            if (row < rows) { k1 = e1 - y[n0 + t0 + row]; k2 = 0.5 * e2; }
+            a1s[row] = k1; a2s[row] = k2;
+        }
+        __syncthreads();
+        // the two contractions of this wave's 16 rows
+        const double* xa = xs + (16 * wave + l15) * GSI_XS + l4;
+        for (int qb = 0; qb < nqb; ++qb) {
+            if (nqb > 1) load_b(qb);
+            gsi_d4 am0 = {0.0, 0.0, 0.0, 0.0}, am1 = am0, av0 = am0, av1 = am0;
+#pragma unroll
+            for (int kk = 0; kk < 16; kk += 2) {
+                if (kk < KS) {
+                    const double x = xa[4 * kk];
+                    am0 = __builtin_amdgcn_mfma_f64_16x16x4f64(x, bm[kk], am0, 0, 0, 0);
+                    av0 = __builtin_amdgcn_mfma_f64_16x16x4f64(x * x, bv[kk], av0, 0, 0, 0);
+                }
+                if (kk + 1 < KS) {
+                    const double x = xa[4 * kk + 4];
+                    am1 = __builtin_amdgcn_mfma_f64_16x16x4f64(x, bm[kk + 1], am1, 0, 0, 0);
+                    av1 = __builtin_amdgcn_mfma_f64_16x16x4f64(x * x, bv[kk + 1], av1, 0, 0, 0);
+                }
+            }
+            const int q = 16 * qb + l15;
+            if (q < Q) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int rr = 16 * wave + l4 + 4 * r;
+                    if (rr < rows) {
+                        const double* zr = xs + rr * GSI_XS + P;
+                        const double* al = Al + (i64)s_gid[rr] * K2 * Q + q;
+                        double le = 0.0, lr = 0.0;
+                        for (int k = 0; k < Kz; ++k) {
+                            const double z = zr[k];
+                            le += z * al[(i64)k * Q]; lr += z * z * al[(i64)(Kz + k) * Q];
+                        }
+                        out[(t0 + rr) * (i64)Q + q] = a1s[rr] * ((am0[r] + am1[r]) + le) + a2s[rr] * ((av0[r] + av1[r]) + lr);
+                    }
+                }
+            }
+        }
+    }
+}
+
+int launch_glmm_slopes_infl_rows(lrvb_ctx* c, int Kz, const double* Z, i64 n0, i64 n1, const int* gid, const double* m, const double* vb,
+                                 const double* eg, const double* rg, const double* gx, const double* gw, int nq, const double* Ag,
+                                 const double* Al, i64 Q, double* out) {
+    if (c->P > 64 || Kz < 1 || Kz > 4 || nq < 1 || nq > 128)
+        LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "logistic mixed model with slopes: P <= 64, 1 <= K <= 4, at most 128 nodes");
+    const i64 R = n1 - n0;
+    if (R <= 0) return LRVB_OK;
+    const i64 n_tiles = (R + GS_T - 1) / GS_T;
+    const unsigned grid = (unsigned)(n_tiles < 2048 ? n_tiles : 2048);
+    hipLaunchKernelGGL(glmm_slopes_infl_rows_kernel, dim3(grid), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
+                       (const double*)c->y.p, gid, m, vb, eg, rg, gx, gw, nq, Ag, Al, (int)Q, out);
+    HIP_TRY(hipGetLastError());
+    return LRVB_OK;
+}
+
+// ---- group influence (lrvb_glmm_slopes_group_influence) ---------------------------------------------------------------------------
+// Per group the WEIGHTED sums  [sum a1 z (K) | sum a2 z o z (K) | sum a1 x (P) | sum a2 x o x (P)],  a1 = w (psi_rho - y),
+// a2 = w psi_s  (2 K + 2 P columns): glmm_slopes_rows_kernel cut down to them -- group-sorted rows, two quadrature sums, the same
+// in-order walk of the tile (thread t owns column t), the pieces of a cut group in the tile's two partial rows, added by
+// glmm_fixup_kernel in tile order.  The staging and the column map of the dot products are those of the row kernel above.  The
+// contraction with the operand is N-independent: a (G x 2 P) (2 P x Q) product on the library's GEMM and
+// glmm_slopes_infl_local_kernel for the 2 K local columns.  Fixed order everywhere, no atomics.
+__global__ __launch_bounds__(256)
+void glmm_slopes_infl_gsum_kernel(i64 N, int P, int Kz, i64 G, const double* __restrict__ X, const double* __restrict__ Z,
+                                  const double* __restrict__ y, const double* __restrict__ w, const i64* __restrict__ perm,
+                                  const i64* __restrict__ offs, const double* __restrict__ m, const double* __restrict__ vb,
+                                  const double* __restrict__ eg, const double* __restrict__ rg, const double* __restrict__ gx,
+                                  const double* __restrict__ gw, int nq, double* __restrict__ gsum, double* __restrict__ part)
+{
+    __shared__ double xs[GS_T * GSI_XS], cf[2 * GS_T], ms[64], vs[64], sx[128], sw[128];
+    __shared__ i64 s_row[GS_T];
+    __shared__ int s_gid[GS_T], s_whole[GS_T];
+    const int tid = threadIdx.x;
+    const int K2 = 2 * Kz, ncol = K2 + 2 * P;
+    const double r2 = 1.4142135623730951, ispi = 0.5641895835477563;
+    if (tid < nq) { sx[tid] = r2 * gx[tid]; sw[tid] = ispi * gw[tid]; }
+    if (tid < P) { ms[tid] = m[tid]; vs[tid] = vb[tid]; }
+    const i64 n_tiles = (N + GS_T - 1) / GS_T;
+    const int row = tid >> 2, q4 = tid & 3;
+    // output column tid (< ncol): a1 z_k | a2 z_k^2 | a1 x_j | a2 x_j^2 -- the staged column jc, squared or not
+    const bool has_col = tid < ncol;
+    const bool sq = has_col && (tid < K2 ? tid >= Kz : tid >= K2 + P);
+    const int jc = !has_col ? 0 : (tid < Kz ? P + tid : (tid < K2 ? P + tid - Kz : (tid < K2 + P ? tid - K2 : tid - K2 - P)));
+    for (i64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const i64 t0 = tile * GS_T;
+        const int rows = (int)(N - t0 < GS_T ? N - t0 : GS_T);
+        __syncthreads();
+        if (tid < GS_T) {
+            int g = 0, whole = 0;
+            i64 pr = 0;
+            if (tid < rows) {
+                const i64 i = t0 + tid;
+                pr = perm[i];
+                i64 lo = 0, hi = G;                                      // the last g with offs[g] <= i (its offs[g + 1] > i)
+                while (hi - lo > 1) { const i64 mid = (lo + hi) >> 1; if (offs[mid] <= i) lo = mid; else hi = mid; }
+                g = (int)lo;
+                whole = (offs[lo] >= t0 && offs[lo + 1] <= t0 + GS_T) ? 1 : 0;
+            }
+            s_row[tid] = pr; s_gid[tid] = g; s_whole[tid] = whole;
+        }
+        __syncthreads();
+        for (int e = tid; e < rows * P; e += 256) { const int rr = e / P, cc = e - rr * P; xs[rr * GSI_XS + cc] = X[s_row[rr] * P + cc]; }
+        for (int e = tid; e < rows * Kz; e += 256) { const int rr = e / Kz, cc = e - rr * Kz; xs[rr * GSI_XS + P + cc] = Z[s_row[rr] * Kz + cc]; }
+        __syncthreads();
+        double e1, e2;
+        gsi_psi_derivs(xs + row * GSI_XS, row < rows, s_gid[row], q4, P, Kz, nq, ms, vs, eg, rg, sx, sw, e1, e2);
+        if (q4 == 0) {
+            double k1 = 0.0, k2 = 0.0;
+            if (row < rows) { const i64 pr = s_row[row]; const double wi = w[pr]; k1 = wi * (e1 - y[pr]); k2 = wi * 0.5 * e2; }
+            cf[row] = k1; cf[GS_T + row] = k2;
+        }
+        __syncthreads();
+        if (has_col) {
+            double acc = 0.0;
+            int run_start = 0;
+            for (int rr = 0; rr < rows; ++rr) {
+                double x = xs[rr * GSI_XS + jc];
+                if (sq) x *= x;
+                acc += cf[(sq ? GS_T : 0) + rr] * x;
+                const int g = s_gid[rr];
+                if (rr == rows - 1 || s_gid[rr + 1] != g) {
+                    double* dst = s_whole[rr] ? gsum + (i64)g * ncol : part + (tile * 2 + (run_start == 0 ? 0 : 1)) * ncol;
+                    dst[tid] = acc;
+                    acc = 0.0; run_start = rr + 1;
+                }
+            }
+        }
+    }
+}
+
+// out[g][q] += sum_c S[g][c] A_local[g][c][q], c = 0 .. 2 K - 1   (S: the group sums, leading dimension ncol)
+__global__ __launch_bounds__(256)
+void glmm_slopes_infl_local_kernel(i64 G, int Q, int K2, int ncol, const double* __restrict__ S, const double* __restrict__ Al,
+                                   double* __restrict__ out)
+{
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= G * Q) return;
+    const i64 g = i / Q;
+    const int q = (int)(i - g * Q);
+    const double* s = S + g * ncol;
+    const double* al = Al + g * K2 * Q + q;
+    double acc = 0.0;
+    for (int c = 0; c < K2; ++c) acc += s[c] * al[(i64)c * Q];
+    out[i] += acc;
+}
+
+int launch_glmm_slopes_infl_gsum(lrvb_ctx* c, int Kz, const double* Z, const double* m, const double* vb, const double* eg,
+                                 const double* rg, const double* gx, const double* gw, int nq, double* gsum, double* part) {
+    const i64 N = c->N, G = c->n_groups;
+    if (c->P > 64 || Kz < 1 || Kz > 4 || nq < 1 || nq > 128)
+        LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "logistic mixed model with slopes: P <= 64, 1 <= K <= 4, at most 128 nodes");
+    const int ncol = 2 * Kz + 2 * (int)c->P;
+    const i64* gdev = reinterpret_cast<const i64*>(c->groups.p);
+    const i64 n_tiles = glmm_num_tiles(N);
+    const unsigned grid = (unsigned)(n_tiles < 2048 ? (n_tiles < 1 ? 1 : n_tiles) : 2048);
+    hipLaunchKernelGGL(glmm_slopes_infl_gsum_kernel, dim3(grid), dim3(256), 0, c->stream, N, (int)c->P, Kz, G, (const double*)c->X.p, Z,
+                       (const double*)c->y.p, (const double*)c->w.p, gdev, gdev + N, m, vb, eg, rg, gx, gw, nq, gsum, part);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(glmm_fixup_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, G, ncol, gdev + N, (const double*)part, gsum);
+    HIP_TRY(hipGetLastError());
+    return LRVB_OK;
+}
+
+int launch_glmm_slopes_infl_local(lrvb_ctx* c, int Kz, i64 Q, const double* S, const double* Al, double* out) {
+    const i64 G = c->n_groups, n = G * Q;
+    hipLaunchKernelGGL(glmm_slopes_infl_local_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, G, (int)Q, 2 * Kz,
+                       2 * Kz + 2 * (int)c->P, S, Al, out);
+    HIP_TRY(hipGetLastError());
+    return LRVB_OK;
+}

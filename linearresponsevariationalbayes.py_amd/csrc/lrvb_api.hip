@@ -2751,6 +2751,81 @@ extern "C" int lrvb_glmm_group_influence(lrvb_ctx* c, const double* mean, const 
     return d2h(c, out, od, (size_t)(G * Q));
 }
 
+// ---- weight influence of the logistic mixed model with slopes (k_glmm_slopes.hip) -------------------------------------------------
+// The checks of lrvb_glmm_slopes_terms, in its order, then the operand.  c->work1 holds
+//   [nodes 256 | m, v (2 up(P)) | e, r (2 up(G K)) | A_global (Q x 2 P) | A_local (G x 2 K x Q) | call-specific scratch]
+static int glmm_slopes_infl_setup(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                  const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
+                                  const double* A_global, const double* A_local, int64_t Q, const void* out, size_t extra,
+                                  GlmmInflBufs& b) {
+    if (!mean || !var || !e_loc || !r_loc || !gh_x || !gh_w || !A_global || !A_local || !out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    if (n_nodes < 1 || n_nodes > 128) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 128 quadrature nodes");
+    if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the logistic mixed model needs P <= 64 (got %lld)", (long long)c->P);
+    if (K < 1 || K > 4) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 4 random effects per group (got %lld)", (long long)K);
+    if (c->loss == LRVB_LOSS_NONE || c->data_only || !(c->have_X && c->have_y))
+        LRVB_FAIL(LRVB_ERR_STATE, "the context needs a design matrix and responses: lrvb_set_data for LRVB_SLOT_X and LRVB_SLOT_Y");
+    if (c->n_groups <= 0) LRVB_FAIL(LRVB_ERR_STATE, "no groups: call lrvb_set_groups first");
+    if (c->gz_K <= 0) LRVB_FAIL(LRVB_ERR_STATE, "no group design: call lrvb_set_group_design first");
+    if (c->gz_n != c->N || c->gz_K != K)
+        LRVB_FAIL(LRVB_ERR_STATE, "the group design is %lld x %d, the model needs %lld x %lld", (long long)c->gz_n, c->gz_K, (long long)c->N, (long long)K);
+    const i64 P = c->P, G = c->n_groups, GK = G * K;
+    LRVB_TRY(check_len(P_in, P, "mean / var"));
+    LRVB_TRY(check_len(G_in, G, "groups of e / r"));
+    for (i64 j = 0; j < P; ++j) if (!(var[j] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "var[%lld] is not positive", (long long)j);
+    for (i64 g = 0; g < GK; ++g) if (!(r_loc[g] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "r[%lld] is not positive", (long long)g);
+    if (Q < 1) LRVB_FAIL(LRVB_ERR_INVALID, "Q must be positive");
+    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
+    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(256 + 2 * up(P) + 2 * up(GK) + up(Q * 2 * P) + up(GK * 2 * Q)) + extra));
+    b.g = c->work1.p; b.m = b.g + 256; b.v = b.m + up(P); b.e = b.v + up(P); b.r = b.e + up(GK);
+    b.Ag = b.r + up(GK); b.Al = b.Ag + up(Q * 2 * P); b.extra = b.Al + up(GK * 2 * Q);
+    LRVB_TRY(h2d(c, b.g, gh_x, (size_t)n_nodes));
+    LRVB_TRY(h2d(c, b.g + 128, gh_w, (size_t)n_nodes));
+    LRVB_TRY(h2d(c, b.m, mean, (size_t)P));
+    LRVB_TRY(h2d(c, b.v, var, (size_t)P));
+    LRVB_TRY(h2d(c, b.e, e_loc, (size_t)GK));
+    LRVB_TRY(h2d(c, b.r, r_loc, (size_t)GK));
+    LRVB_TRY(h2d(c, b.Ag, A_global, (size_t)(Q * 2 * P)));
+    LRVB_TRY(h2d(c, b.Al, A_local, (size_t)(GK * 2 * Q)));
+    return LRVB_OK;
+}
+
+extern "C" int lrvb_glmm_slopes_obs_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                              const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                              int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, int64_t n0,
+                                              int64_t n1, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    GlmmInflBufs b;
+    LRVB_TRY(glmm_slopes_infl_setup(c, mean, var, P_in, e_loc, r_loc, G_in, K, gh_x, gh_w, n_nodes, A_global, A_local, Q, out, 0, b));
+    if (n0 < 0 || n1 > c->N || n0 > n1) LRVB_FAIL(LRVB_ERR_INVALID, "row range [%lld, %lld) outside [0, %lld)", (long long)n0, (long long)n1, (long long)c->N);
+    const i64 rows = n1 - n0;
+    if (rows == 0) return LRVB_OK;
+    LRVB_TRY(buf_reserve(c, c->cgT, (size_t)(rows * Q)));
+    const i64 NW = (c->N + grouped_rows_per_wave(c->N) - 1) / grouped_rows_per_wave(c->N);
+    const int* gid = reinterpret_cast<const int*>(reinterpret_cast<const i64*>(c->groups.p) + c->N + c->n_groups + 1 + NW);
+    LRVB_TRY(launch_glmm_slopes_infl_rows(c, (int)K, c->gz.p, n0, n1, gid, b.m, b.v, b.e, b.r, b.g, b.g + 128, (int)n_nodes, b.Ag, b.Al, Q,
+                                          c->cgT.p));
+    return d2h(c, out, c->cgT.p, (size_t)(rows * Q));       // per-observation rows: rank-local, no hook call
+}
+
+extern "C" int lrvb_glmm_slopes_group_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                                const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                                int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    GlmmInflBufs b;
+    const i64 Kc = K < 1 ? 1 : (K > 4 ? 4 : K);               // the setup refuses K outside 1..4 before the scratch is used
+    const i64 ncol = 2 * Kc + 2 * c->P, n_tiles = glmm_num_tiles(c->N), G = c->n_groups > 0 ? c->n_groups : 0;
+    // scratch: [group sums (G x (2 K + 2 P)) | tile partials | out (G x Q)]
+    const size_t extra = (size_t)(G * ncol + n_tiles * 2 * ncol + G * (Q > 0 ? Q : 0));
+    LRVB_TRY(glmm_slopes_infl_setup(c, mean, var, P_in, e_loc, r_loc, G_in, K, gh_x, gh_w, n_nodes, A_global, A_local, Q, out, extra, b));
+    double* gsum = b.extra; double* part = gsum + G * ncol; double* od = part + n_tiles * 2 * ncol;
+    HIP_TRY(hipMemsetAsync(gsum, 0, (size_t)(G * ncol) * sizeof(double), c->stream));       // empty groups keep the zeros
+    LRVB_TRY(launch_glmm_slopes_infl_gsum(c, (int)K, c->gz.p, b.m, b.v, b.e, b.r, b.g, b.g + 128, (int)n_nodes, gsum, part));
+    LRVB_TRY(launch_gemm(c, false, true, G, Q, 2 * c->P, 1.0, gsum + 2 * K, ncol, b.Ag, 2 * c->P, 0.0, od, Q));
+    LRVB_TRY(launch_glmm_slopes_infl_local(c, (int)K, Q, gsum, b.Al, od));
+    LRVB_TRY(obs_reduce(c, od, G * Q));                       // a sum over observations; a group may straddle ranks
+    return d2h(c, out, od, (size_t)(G * Q));
+}
+
 // ---- logistic regression with a full-covariance Gaussian posterior q(beta) = N(m, Sigma) ----------------------------------
 // Device layout of c->lmvn for N rows, P columns (NP = N + 64: the coefficient vectors carry zero padding past N):
 //   [nodes 256 | m P | Sigma P^2 | V P^2 | b P | Tmp P^2 | mu N | s N | a1 a2 c11 c12 c22 ds em es (8 NP) | partials]

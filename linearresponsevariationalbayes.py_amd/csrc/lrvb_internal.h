@@ -249,6 +249,15 @@ int  launch_glmm_slopes_rows(lrvb_ctx* c, int K, const double* Z /* N x K */, co
 int  launch_glmm_slopes_schur_rows(lrvb_ctx* c, int K, const double* gsum, const double* loc /* G x K (2 K + 1) */,
                                    const double* scale /* G x 2 K */, const double* closed /* G x 2 K x 3 */,
                                    double* U /* 2 K G x ldu */, int ldu, int* bad);
+int  launch_glmm_slopes_infl_rows(lrvb_ctx* c, int K, const double* Z, i64 n0, i64 n1, const int* gid /* original row order */,
+                                  const double* m, const double* vb, const double* eg, const double* rg, const double* gx,
+                                  const double* gw, int n_nodes, const double* Ag /* Q x 2 P */, const double* Al /* G x 2 K x Q */,
+                                  i64 Q, double* out /* (n1 - n0) x Q */);
+int  launch_glmm_slopes_infl_gsum(lrvb_ctx* c, int K, const double* Z, const double* m, const double* vb, const double* eg,
+                                  const double* rg, const double* gx, const double* gw, int n_nodes,
+                                  double* gsum /* G x (2 K + 2 P), zeroed by the caller */,
+                                  double* part /* 2 (2 K + 2 P) doubles per tile of glmm_num_tiles */);
+int  launch_glmm_slopes_infl_local(lrvb_ctx* c, int K, i64 Q, const double* S, const double* Al, double* out /* G x Q, += */);
 
 // k_lmm.hip
 struct LmmIdx { int p, ms, ls, iem, iim, iay, iby, iam, ibm; i64 ld; };    // vector-coordinate positions of the global parameters

@@ -20,7 +20,9 @@ The O(N) work is `lrvb_glmm_slopes_terms` (csrc/k_glmm_slopes.hip); everything N
 below, plain numpy on the data pieces.  The Hessian is a block arrow: a dense global block, G local 2 K x 2 K blocks in the
 coordinates [e_g0 .. e_g,K-1 | i_g0 .. i_g,K-1] and a border of R = 2 P + 3 K coupled global rows
 [m | i_beta | e_mu_0, a_0, b_0, .., e_mu_{K-1}, a_{K-1}, b_{K-1}] (the i_mu_k do not couple).  At K = 1 with z = 1 the model is
-`LogisticGLMMObjective`.  The observation weights are data of this class, not a hyper-parameter.
+`LogisticGLMMObjective`.  The observation weights are the hyper-parameter `weights_par` (the constructor's `weights=` is its
+initial value); `obs_influence`, `group_influence` and `ParametricSensitivityLinearApproximation(..., stream_hyper=True)` stream
+the sensitivity of any moment to them (`lrvb_glmm_slopes_obs_influence`, `lrvb_glmm_slopes_group_influence`).
 """
 import numpy as np
 from scipy import special
@@ -29,7 +31,7 @@ from scipy import linalg as sp_linalg
 
 from . import _hip
 from .models import DeviceContext, DeclaredHypers, refuse_double_reduction
-from .packing import HyperVectorParam
+from .packing import HyperVectorParam, ResidentVector
 from .quadform import gamma_prior_hyper_grad, gamma_prior_hyper_cross
 from .hierarchical import _gamma_block, _gamma_entropy
 
@@ -271,6 +273,19 @@ def block_arrow_solve(Hgg, rows, Hx, loc, R, schur_solve=None):
     return out.ravel() if vec else out
 
 
+def split_influence_operand(A, P, K, G):
+    """The operand A (Q x (2 P + 2 G K), columns [A_m | A_v | A_e (G K, group-major) | A_r (G K)]) of the influence entries in
+    their two layouts (include/lrvb_hip.h): A_global (Q x 2 P) and A_local (G x 2 K x Q: group g holds the Q-vectors of
+    [e_g0 .. e_g,K-1 | r_g0 .. r_g,K-1])."""
+    A = np.atleast_2d(np.asarray(A, dtype=np.float64))
+    Q, GK = A.shape[0], G * K
+    if A.ndim != 2 or A.shape[1] != 2 * P + 2 * GK:
+        raise ValueError('A must have {} columns [A_m | A_v | A_e | A_r]'.format(2 * P + 2 * GK))
+    Ae = A[:, 2 * P:2 * P + GK].reshape(Q, G, K).transpose(1, 2, 0)
+    Ar = A[:, 2 * P + GK:].reshape(Q, G, K).transpose(1, 2, 0)
+    return np.ascontiguousarray(A[:, :2 * P]), np.ascontiguousarray(np.concatenate([Ae, Ar], axis=1))
+
+
 class LogisticGLMMSlopesObjective(DeclaredHypers):
     _lrvb_device_functor = True
 
@@ -292,12 +307,19 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
         self._declare_hyper('tau_prior', HyperVectorParam('tau_prior', 2, lb=0.0, val=np.array(list(map(float, tau_prior)))))
         self.ctx = DeviceContext(par.layout_blocks(), loss='logistic', n_obs=self.n_obs, n_cols=self.P, device=device)
         self.ctx.set_data(_hip.SLOT_X, x)
-        self.ctx.set_data(_hip.SLOT_Y, _hip.as_f64(y).ravel().copy())
-        self.ctx.set_groups(np.ascontiguousarray(np.asarray(groups).ravel(), dtype=np.int32), self.G)
+        self._y = _hip.as_f64(y).ravel().copy()
+        self.ctx.set_data(_hip.SLOT_Y, self._y)
+        self._groups = np.ascontiguousarray(np.asarray(groups).ravel(), dtype=np.int32)
+        self.ctx.set_groups(self._groups, self.G)
         self.ctx.set_group_design(z)
-        self.ctx.set_weights(np.ones(self.n_obs) if weights is None else _hip.as_f64(weights).ravel().copy())
+        w0 = np.ones(self.n_obs) if weights is None else _hip.as_f64(weights).ravel().copy()
+        self._declare_hyper('weights', HyperVectorParam('weights', self.n_obs, val=w0))
+        self.tilt_par = None
+        self._w_res = ResidentVector()
+        self._x, self._z = x, z
         self._external = None
         self._point_key = None
+        self._push_state()                           # the initial weights on the device: direct calls on `ctx` see them from the start
 
     tau_beta = property(lambda self: float(self._hyper_vec('beta_prior_info')[0]))
     mu0 = property(lambda self: float(self._hyper_vec('mu_prior')[0]))
@@ -352,6 +374,12 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
         j1 = np.where(self._bounded, eta - np.where(self._bounded, self._lb, 0.0), 1.0)
         return j1, np.where(self._bounded, j1, 0.0)
 
+    def _push_state(self):
+        w = self._w_res.changed(self.weights_par)
+        if w is not None:
+            self.ctx.set_weights(w)
+            self._point_key = None
+
     # ---- data pieces (GPU) ------------------------------------------------------------------------------------------
     def _pieces_of(self, val, gg, Hb, gs):
         if gs is None:
@@ -362,6 +390,7 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
     def _device_terms(self, eta, want_grad, want_hess, want_border=True):
         P, K, G = self.P, self.K, self.G
         _, ib, _, _, _, _, e, ig = _split_eta(eta, P, K, G)
+        self._push_state()
         out = self.ctx.glmm_slopes_terms(eta[:P], 1.0 / ib, e, 1.0 / ig, self.gh_x, self.gh_w, want_grad=want_grad or want_hess,
                                          want_hess=want_hess, want_border=want_border)
         return self._pieces_of(*out)
@@ -375,6 +404,7 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
         shards: its sums add).  With a reduce hook on the context it is already the sum over the ranks."""
         eta = _hip.as_f64(eta).ravel()
         _, ib, _, _, _, _, e, ig = _split_eta(eta, self.P, self.K, self.G)
+        self._push_state()
         val, gg, Hb, gs = self.ctx.glmm_slopes_terms(eta[:self.P], 1.0 / ib, e, 1.0 / ig, self.gh_x, self.gh_w)
         return np.concatenate([[val], gg, Hb.ravel(), gs.ravel()])
 
@@ -408,8 +438,9 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
                                         want_hess=want_hess)
 
     def _arrow(self, x, is_free):
-        """(grad, Hgg, rows, Hx, loc) at x in its own coordinates, cached per point and hyper-parameters."""
-        key = (bool(is_free), np.asarray(x, dtype=np.float64).tobytes(), self._hyper_state_key(),
+        """(grad, Hgg, rows, Hx, loc) at x in its own coordinates, cached per point, weights and hyper-parameters."""
+        self._push_state()
+        key = (bool(is_free), np.asarray(x, dtype=np.float64).tobytes(), self._w_res.key, self._hyper_state_key(),
                None if self._external is None else id(self._external))
         if self._point_key != key:
             eta = self._eta(x, is_free)
@@ -490,6 +521,7 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
         The result stays resident on the global context for `chol_factor_last`."""
         fv = _hip.as_f64(free_val).ravel()
         P, K, G, ng = self.P, self.K, self.G, self.n_global
+        self._push_state()
         eta = self._eta(fv, True)
         j1, j2 = self._jac(eta)
         cf = self._closed(eta, want_border=False)    # the group sums of the point stay resident; the border is not copied back
@@ -520,8 +552,8 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
         return out
 
     def _resident_key(self, fv):
-        """What the Schur complement resident on the global context was built at: point and hyper-parameters."""
-        return (np.asarray(fv, dtype=np.float64).tobytes(), self._hyper_state_key(),
+        """What the Schur complement resident on the global context was built at: point, weights, hyper-parameters."""
+        return (np.asarray(fv, dtype=np.float64).tobytes(), self._w_res.key, self._hyper_state_key(),
                 None if self._external is None else id(self._external))
 
     # ---- the whole arrow: solve, covariance of any moment ----------------------------------------------------------------
@@ -529,25 +561,66 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
     def solve(self, x, R, is_free=True, resident_factor=False):
         """H^-1 R at x (R: D x Q or a D-vector, local rows allowed) by `block_arrow_solve`.  resident_factor=True solves the
         Schur complement with the factor on the global context: call `global_hessian(x, want_host=False)` and
-        `_ensure_gctx().chol_factor_last()` at the same point first (free coordinates); a factor built at another point or
-        under other hyper-parameters is refused with a ValueError."""
+        `_ensure_gctx().chol_factor_last()` at the same point first (free coordinates); a factor built at another point, or
+        under other weights or hyper-parameters, is refused with a ValueError."""
         _, Hgg, rows, Hx, loc = self._arrow(x, is_free)
         if resident_factor and (not is_free or getattr(self, '_schur_key', None) != self._resident_key(_hip.as_f64(x).ravel())):
             raise ValueError('resident_factor=True needs global_hessian(x, want_host=False) and chol_factor_last() at this point, '
-                             'with these hyper-parameters, in free coordinates')
+                             'with these weights and hyper-parameters, in free coordinates')
         schur_solve = self._ensure_gctx().chol_solve if resident_factor else None
         return block_arrow_solve(Hgg, rows, Hx, loc, R, schur_solve=schur_solve)
 
-    def lrvb_cov(self, x, moment_jac, is_free=True):
-        """M H^-1 M^T (Q x Q): the linear-response covariance of the moments M theta, M = moment_jac being Q x D (columns of the
-        group effects allowed) or Q x n_global (zero-padded)."""
+    def _moment_jac(self, moment_jac):
         M = np.atleast_2d(_hip.as_f64(moment_jac))
         D = self.n_global + 2 * self.G * self.K
         if M.ndim != 2 or M.shape[1] not in (D, self.n_global):
             raise ValueError('moment Jacobian must have {} (all parameters) or {} (global parameters) columns'.format(D, self.n_global))
         if M.shape[1] != D:
             M = np.hstack([M, np.zeros((M.shape[0], D - M.shape[1]))])
+        return M
+
+    def lrvb_cov(self, x, moment_jac, is_free=True):
+        """M H^-1 M^T (Q x Q): the linear-response covariance of the moments M theta, M = moment_jac being Q x D (columns of the
+        group effects allowed) or Q x n_global (zero-padded)."""
+        M = self._moment_jac(moment_jac)
         return M @ self.solve(x, np.ascontiguousarray(M.T), is_free)
+
+    def _influence_operand(self, x, moment_jac, is_free, chol):
+        """A = -M H^-1 J (Q x (2 P + 2 G K)) in the coordinates (m, v, e, r) of the device entries -- the element-wise chain from
+        eta's (m, i_beta, e, i), the columns of mu and tau dropped -- and the point in those coordinates."""
+        self._push_state()
+        M = self._moment_jac(moment_jac)
+        P, K, G, ng = self.P, self.K, self.G, self.n_global
+        GK = G * K
+        if chol is None:
+            S = self.solve(x, np.ascontiguousarray(M.T), is_free)
+        else:
+            S = np.asarray(chol.solve(np.ascontiguousarray(M.T))).reshape(ng + 2 * GK, -1)
+        eta = self._eta(x, is_free)
+        j1 = self._jac(eta)[0] if is_free else np.ones(eta.size)
+        _, ib, _, _, _, _, e, ig = _split_eta(eta, P, K, G)
+        v, r = 1.0 / ib, 1.0 / ig
+        chain = np.concatenate([j1[:P], -v * v * j1[P:2 * P], j1[ng:ng + GK], -(r * r).ravel() * j1[ng + GK:]])
+        keep = np.concatenate([np.arange(2 * P), np.arange(ng, ng + 2 * GK)])
+        A = -(S[keep] * chain[:, None]).T
+        return np.ascontiguousarray(A), (eta[:P], v, e, r, self.gh_x, self.gh_w)
+
+    def obs_influence(self, x, moment_jac, n0=0, n1=None, is_free=True, chol=None):
+        """Rows n0..n1 of (moment_jac @ d par / d w)^T ((n1 - n0) x Q), streamed over the observations on the device
+        (`lrvb_glmm_slopes_obs_influence`); the N x D cross Hessian is never formed.  A = -moment_jac H^-1 J comes from the dense
+        factor `chol` where one is given (ParametricSensitivityLinearApproximation holds it), otherwise from `block_arrow_solve`
+        -- the route for large G, where no dense factor exists.  Per unit weight: a row of weight zero gets the influence of
+        adding it."""
+        A, pt = self._influence_operand(x, moment_jac, is_free, chol)
+        return self.ctx.glmm_slopes_obs_influence(*pt, A, n0=n0, n1=n1)
+
+    def group_influence(self, x, moment_jac, is_free=True, chol=None):
+        """G x Q: row g is the derivative of the moments with respect to a common multiplier on the weights of group g's rows,
+        sum_{n in g} w_n * (row n of `obs_influence`) -- minus it is the linear prediction of leaving the cluster out.  The
+        group's own prior terms on u_g stay in the model and are not part of it.  Fixed summation order on the device
+        (`lrvb_glmm_slopes_group_influence`); an empty group gives a zero row."""
+        A, pt = self._influence_operand(x, moment_jac, is_free, chol)
+        return self.ctx.glmm_slopes_group_influence(*pt, A)
 
     # ---- hyper-parameters ---------------------------------------------------------------------------------------------
     def _prior_hyper(self, kind, eta_g, want):
@@ -577,19 +650,52 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
         return out
 
     def hyper_grad(self, hyper_par, val1, val1_is_free):
-        return self._prior_hyper(self.hyper_kind(hyper_par), self._eta(val1, val1_is_free)[:self.n_global], 'grad')
+        kind = self.hyper_kind(hyper_par)
+        if kind == 'weights':
+            raise NotImplementedError('d f / d weights is not declared')
+        return self._prior_hyper(kind, self._eta(val1, val1_is_free)[:self.n_global], 'grad')
 
     def global_cross_hessian(self, hyper_par, val, is_free=True):
-        """The n_global rows of the cross Hessian with a prior hyper-parameter (its 2 G K local rows are zero)."""
+        """The n_global rows of the cross Hessian with a PRIOR hyper-parameter (its 2 G K local rows are zero)."""
+        kind = self.hyper_kind(hyper_par)
+        if kind == 'weights':
+            raise NotImplementedError('the weight cross Hessian has local rows: use cross_hessian')
         eta = self._eta(val, is_free)
-        C = self._prior_hyper(self.hyper_kind(hyper_par), eta[:self.n_global], 'cross')
+        C = self._prior_hyper(kind, eta[:self.n_global], 'cross')
         return C * self._jac(eta)[0][:self.n_global, None] if is_free else C
 
+    @_hip.host_blas
     def cross_hessian(self, hyper_par, val1, val1_is_free):
-        """d2 f / d par d hyper^T, all rows (dense protocol): the priors do not touch the local rows."""
+        """d2 f / d par d hyper^T, all rows (dense protocol: small N and G).  Weights: column n is the gradient of row n's term
+        per unit weight, [(psi_rho - y) x_n | psi_s x_n o x_n chained to i_beta | 0 | at g(n): (psi_rho - y) z_n, psi_s z_n o z_n
+        chained to i_g.] -- its local rows are NOT zero.  Priors: the local rows are zero."""
+        kind = self.hyper_kind(hyper_par)
         val1 = _hip.as_f64(val1).ravel()
-        Cg = self.global_cross_hessian(hyper_par, val1, is_free=val1_is_free)
-        return np.vstack([Cg, np.zeros((val1.size - self.n_global, Cg.shape[1]))])
+        if kind != 'weights':
+            Cg = self.global_cross_hessian(hyper_par, val1, is_free=val1_is_free)
+            return np.vstack([Cg, np.zeros((val1.size - self.n_global, Cg.shape[1]))])
+        eta = self._eta(val1, val1_is_free)
+        P, K, G, ng, N = self.P, self.K, self.G, self.n_global, self.n_obs
+        GK = G * K
+        x, z, gid = self._x, self._z, self._groups
+        _, ib, _, _, _, _, e, ig = _split_eta(eta, P, K, G)
+        v, r = 1.0 / ib, 1.0 / ig
+        rho = x @ eta[:P] + np.sum(z * e[gid], axis=1)
+        s = (x * x) @ v + np.sum(z * z * r[gid], axis=1)
+        sd = np.sqrt(s)
+        _, d1, _ = self.ctx.gh_logistic(rho, sd, self.gh_x, self.gh_w, order=2)
+        p_rho = d1[:, 0] - self._y
+        p_s = 0.5 * d1[:, 1] / sd                            # s_n > 0 wherever a row has a non-zero x or z
+        C = np.zeros((N, ng + 2 * GK))
+        C[:, :P] = p_rho[:, None] * x
+        C[:, P:2 * P] = p_s[:, None] * (x * x) * (-v * v)[None, :]
+        n = np.arange(N)[:, None]
+        cols = gid[:, None] * K + np.arange(K)[None, :]
+        C[n, ng + cols] = p_rho[:, None] * z
+        C[n, ng + GK + cols] = p_s[:, None] * z * z * (-r * r)[gid]
+        if val1_is_free:
+            C = C * self._jac(eta)[0][None, :]
+        return np.ascontiguousarray(C.T)
 
     def global_sensitivity(self, hyper_par, free_val):
         """d theta_global / d hyper^T = -H_S^-1 C_g (n_global x Ph) for a prior hyper-parameter: its cross Hessian has no local

@@ -432,6 +432,44 @@ class DeviceContext(object):
                                                        _hip.ptr(gx), _hip.ptr(gw), gx.size, _hip.ptr(Ag), _hip.ptr(Al), Q, _hip.ptr(out)))
         return out
 
+    def _glmm_slopes_influence_args(self, mean, var, e, r, gh_x, gh_w, A):
+        """The point (e, r: G x K) and the operand A (Q x (2 P + 2 G K), columns [A_m | A_v | A_e (G K, group-major) | A_r (G K)])
+        in the layout of the C entries: A_global (Q x 2 P) and A_local (G x 2 K x Q), by `glmm_slopes.split_influence_operand`."""
+        from .glmm_slopes import split_influence_operand
+        m, v = _hip.as_f64(mean).ravel(), _hip.as_f64(var).ravel()
+        e, r = _hip.as_f64(e), _hip.as_f64(r)
+        gx, gw = _hip.as_f64(gh_x).ravel(), _hip.as_f64(gh_w).ravel()
+        P = self.n_cols
+        if e.ndim != 2 or r.shape != e.shape or m.size != P or v.size != P or gx.size != gw.size:
+            raise ValueError('expected mean and var of length {}, e and r of one shape G x K and as many weights as nodes'.format(P))
+        G, K = e.shape
+        Ag, Al = split_influence_operand(A, P, K, G)                     # a wrong width is its ValueError
+        return (m, v, e, r, gx, gw, Ag, Al), Ag.shape[0]
+
+    def glmm_slopes_obs_influence(self, mean, var, e, r, gh_x, gh_w, A, n0=0, n1=None):
+        """(n1 - n0) x Q rows, row n = A times column n of the weight cross Hessian of the logistic mixed model with K effects per
+        group in the coordinates (mean, var, e, r), per unit weight (lrvb_glmm_slopes_obs_influence).  A: Q x (2 P + 2 G K),
+        columns [A_m | A_v | A_e | A_r], the local parts group-major as e and r."""
+        (m, v, e, r, gx, gw, Ag, Al), Q = self._glmm_slopes_influence_args(mean, var, e, r, gh_x, gh_w, A)
+        n0 = int(n0)
+        n1 = self.n_obs if n1 is None else int(n1)
+        out = np.empty((max(n1 - n0, 0), Q))
+        self._check(self._lib.lrvb_glmm_slopes_obs_influence(self._h, _hip.ptr(m), _hip.ptr(v), self.n_cols, _hip.ptr(e), _hip.ptr(r),
+                                                            e.shape[0], e.shape[1], _hip.ptr(gx), _hip.ptr(gw), gx.size, _hip.ptr(Ag),
+                                                            _hip.ptr(Al), Q, n0, n1, _hip.ptr(out)))
+        return out
+
+    def glmm_slopes_group_influence(self, mean, var, e, r, gh_x, gh_w, A):
+        """G x Q: row g = sum over the rows of group g of w_n times the row of `glmm_slopes_obs_influence`
+        (lrvb_glmm_slopes_group_influence): the derivative with respect to a common multiplier on the weights of the group's rows.
+        The group's own prior terms on u_g are not part of it."""
+        (m, v, e, r, gx, gw, Ag, Al), Q = self._glmm_slopes_influence_args(mean, var, e, r, gh_x, gh_w, A)
+        out = np.empty((e.shape[0], Q))
+        self._check(self._lib.lrvb_glmm_slopes_group_influence(self._h, _hip.ptr(m), _hip.ptr(v), self.n_cols, _hip.ptr(e), _hip.ptr(r),
+                                                              e.shape[0], e.shape[1], _hip.ptr(gx), _hip.ptr(gw), gx.size, _hip.ptr(Ag),
+                                                              _hip.ptr(Al), Q, _hip.ptr(out)))
+        return out
+
     # ---- multinomial (softmax) regression: beta is (K - 1) x n_cols, D = (K - 1) n_cols (lrvb_softmax_*) --------------------
     def softmax_set_labels(self, labels, n_classes):
         y = np.ascontiguousarray(np.asarray(labels).ravel(), dtype=np.int32)

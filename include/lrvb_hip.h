@@ -624,7 +624,10 @@ int lrvb_wishart_gram(lrvb_ctx* ctx, int64_t d, const int64_t* offsets, double n
 
 /* ---- linear-response solve ------------------------------------------------------------ */
 /* scipy.linalg.cho_factor at LRVB/ModelSensitivity.py:594 / SparseObjectives.py:539.
- * The factor stays on the device inside the context.                                        */
+ * The factor stays on the device inside the context.  Only the lower triangle of H (row-major, j <= i) is read: whatever
+ * lies above the diagonal -- NaN included -- has no effect, which is what lrvb_chol_factor_last relies on for resident
+ * Hessians whose builders write lower tiles only.  A pivot that is not a positive finite number (<= 0, NaN, +Inf) fails with
+ * LRVB_ERR_NOT_POSDEF and its 1-based position; after a failed call the context holds no factor.  */
 int lrvb_chol_factor(lrvb_ctx* ctx, const double* H, int64_t D);
 /* Factor the Hessian the context last built on the device (no host round trip).            */
 int lrvb_chol_factor_last(lrvb_ctx* ctx);

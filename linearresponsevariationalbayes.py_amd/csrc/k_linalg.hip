@@ -129,6 +129,11 @@ __device__ __forceinline__ double lane_bcast(double v, int src_lane) {
     return __hiloint2double(hi, lo);
 }
 
+// A pivot must be a positive FINITE number.  NaN compares false; +Inf passed a bare `> 0` test, gave rsqrt = 0 and a diagonal
+// entry Inf * 0 = NaN that no later pivot sees (the column it scales becomes 0, not NaN): the factorisation reported success
+// and every solve returned NaN.
+__device__ __forceinline__ bool pivot_ok(double d) { return d > 0.0 && d < __builtin_inf(); }
+
 constexpr int CH_LS = CH_NB + 2;          // LDS row stride of the diagonal block (even: 16-byte pair reads)
 
 constexpr int CH_WS = CH_NB + 1;          // LDS row stride of W
@@ -202,10 +207,10 @@ __device__ __forceinline__ void potrf_inv_diag_body(double* __restrict__ Ls, dou
             const double d3 = fma(-l32, l32, fma(-l31, l31, fma(-l30, l30, p33)));
             const double rs3 = rsqrt(d3);
             if (bad == 0) {
-                if (!(d0 > 0.0)) bad = j + 1;
-                else if (!(d1 > 0.0)) bad = j + 2;
-                else if (!(d2 > 0.0)) bad = j + 3;
-                else if (!(d3 > 0.0)) bad = j + 4;
+                if (!pivot_ok(d0)) bad = j + 1;
+                else if (!pivot_ok(d1)) bad = j + 2;
+                else if (!pivot_ok(d2)) bad = j + 3;
+                else if (!pivot_ok(d3)) bad = j + 4;
             }
             // this lane's row of L in columns j..j+3
             const double y0 = a[j] * rs0;

@@ -7,7 +7,10 @@ solve), prints the LRVB standard errors of beta and mu (through the Schur comple
 mean-field ones, ranks the groups by their influence on beta[0] (streamed on the device), drops the top group, refits and prints
 the predicted change next to the actual one.
 
-    python examples/logistic_glmm_slopes.py [--small]
+    python examples/logistic_glmm_slopes.py [--small] [--device-solve]
+
+--device-solve takes the Newton polish and the operand of the group influence through the device-resident block-arrow solve
+(`on_device=True`): the border of the Hessian never reaches the host.
 """
 import os
 import sys
@@ -20,7 +23,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import lrvb_amd as vb                                                     # noqa: E402
 
 
-def fit(objective, fun, th0):
+def fit(objective, fun, th0, on_device=False):
     opt = scipy.optimize.minimize(objective.fun_free, jac=objective.fun_free_grad, hessp=objective.fun_free_hvp, x0=th0,
                                   method='trust-ncg', options={'gtol': 1e-6, 'maxiter': 200})
     th = opt.x
@@ -28,12 +31,13 @@ def fit(objective, fun, th0):
         g = fun.grad(th, True)
         if np.max(np.abs(g)) < 1e-7:
             break
-        th = th - fun.solve(th, g)
+        th = th - fun.solve(th, g, on_device=on_device)
     return th
 
 
 def main():
     small = '--small' in sys.argv
+    device_solve = '--device-solve' in sys.argv
     N, P, G = (20000, 8, 200) if small else (1000000, 64, 10000)
     K = 2
     rng = np.random.default_rng(0)
@@ -55,7 +59,7 @@ def main():
     ng = fun.n_global
 
     t0 = time.perf_counter()
-    th = fit(objective, fun, np.zeros(par.free_size()))
+    th = fit(objective, fun, np.zeros(par.free_size()), device_solve)
     print('fit: %.2f s, max |free gradient| %.2e' % (time.perf_counter() - t0, np.max(np.abs(fun.grad(th, True)))))
 
     # LRVB standard errors of beta and mu next to the mean-field ones
@@ -77,7 +81,7 @@ def main():
     Mb = np.zeros((1, ng))
     Mb[0, 0] = 1.0
     t0 = time.perf_counter()
-    gi = fun.group_influence(th, Mb)[:, 0]                               # d beta[0] / d (multiplier on the group's weights)
+    gi = fun.group_influence(th, Mb, on_device=device_solve)[:, 0]       # d beta[0] / d (multiplier on the group's weights)
     t_gi = time.perf_counter() - t0
     top = np.argsort(-np.abs(gi))[:5]
     print('group influence on beta[0] (%.3f s): top groups %s, influence %s' % (t_gi, top.tolist(), np.array2string(gi[top], precision=5)))
@@ -85,7 +89,7 @@ def main():
     w = np.ones(N)
     w[gid == g] = 0.0
     fun.weights_par.set_vector(w)
-    th_drop = fit(objective, fun, th)
+    th_drop = fit(objective, fun, th, device_solve)
     fun.weights_par.set_vector(np.ones(N))
     print('drop group %d (%d rows): beta[0] predicted change %.4e, actual change %.4e'
           % (g, int(np.sum(gid == g)), -gi[g], th_drop[0] - th[0]))

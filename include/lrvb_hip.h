@@ -409,9 +409,32 @@ int lrvb_glmm_slopes_terms(lrvb_ctx* ctx, const double* mean, const double* var,
  * M_out (R x R, R = 2 P + 3 K, row-major) = sum_g C_g^T A_g^-1 C_g over the coupled coordinates
  * [mean (P) | var (P) | e_mu_0, a_0, b_0, .., e_mu_{K-1}, a_{K-1}, b_{K-1}]: each block is factored A_g = L L^T, the rows
  * U_g = L^-1 C_g are written, then one Gram over 2 K G rows.  A block that is not positive definite: LRVB_ERR_NOT_POSDEF;
- * no resident group sums of K effects: LRVB_ERR_STATE; K < 1 or K > 4: LRVB_ERR_UNSUPPORTED.  No reduce-hook call.          */
+ * no resident group sums of K effects: LRVB_ERR_STATE; K < 1 or K > 4: LRVB_ERR_UNSUPPORTED.  No reduce-hook call.
+ * On success the uploaded blocks and U stay resident for lrvb_glmm_slopes_solve_forward / _back (below).                   */
 int lrvb_glmm_slopes_schur(lrvb_ctx* ctx, const double* local_blocks, const double* border_scale, const double* closed_rows,
                            int64_t G, int64_t K, double* M_out);
+/* The block-arrow solve H^-1 [R_g ; R_l] with the local half on the device.  A successful lrvb_glmm_slopes_schur leaves its
+ * factor resident in a buffer of its own: the local blocks as uploaded (L_g is re-derived from them on chip, by the same
+ * operations in the same order, wherever it is needed) and U_g = L_g^-1 C_g.  The factor is dropped by the next
+ * lrvb_glmm_slopes_terms, lrvb_set_group_design or lrvb_set_groups, and replaced by the next lrvb_glmm_slopes_schur.  With
+ * S = H_gg - M on the host (M scaled to the caller's coordinates; s below is that scaling of the coupled rows):
+ *   forward:  T_g = L_g^-1 R_local,g  (kept resident),   red_out (R x Q, row-major) = sum_g U_g^T T_g;
+ *   host:     rhs = R_g,  rhs[coupled rows] -= s o red,  x = S^-1 rhs;
+ *   back:     X_local_out,g = L_g^-T (T_g - U_g x_coupled),   x_coupled (R x Q, row-major) = s o x[coupled rows].
+ * R_local and X_local_out are G x 2 K x Q, row-major: group g holds 2 K vectors of Q contiguous values in the order
+ * [e_g0 .. e_g,K-1 | r_g0 .. r_g,K-1] -- the layout of A_local of lrvb_glmm_slopes_obs_influence; the coupled rows are in the
+ * order of M_out.  One workgroup per group runs the triangular substitution, one thread per column q (any Q >= 1); the
+ * contractions U^T T (over 2 K G rows) and U x (over R) are GEMMs on the fp64 matrix cores.  Fixed summation order, no
+ * atomics: two calls with the same inputs are bitwise equal.  No reduce-hook call: after lrvb_glmm_slopes_terms every rank
+ * holds the complete group sums, so the solve is replicated, as the elimination is.
+ * Memory: the factor holds 2 K G x ld(R) doubles of U, ld(R) = R rounded up to a multiple of 8 (G = 1e4, K = 4, P = 64:
+ * 8e4 x 144 doubles = 92 MB), and K (2 K + 1) G doubles of blocks; a forward pass adds 2 K G x Q doubles of T, a back pass
+ * as many of scratch.
+ * No resident factor of K effects, or lrvb_glmm_slopes_solve_back without a forward pass since the factor was built:
+ * LRVB_ERR_STATE; back with another Q than the forward pass before it, or G not the number of groups: LRVB_ERR_SIZE; K < 1 or
+ * K > 4: LRVB_ERR_UNSUPPORTED; Q < 1 or a null pointer: LRVB_ERR_INVALID.                                                    */
+int lrvb_glmm_slopes_solve_forward(lrvb_ctx* ctx, const double* R_local, int64_t G, int64_t K, int64_t Q, double* red_out);
+int lrvb_glmm_slopes_solve_back(lrvb_ctx* ctx, const double* x_coupled, int64_t G, int64_t K, int64_t Q, double* X_local_out);
 
 /* Streamed weight influence of the logistic mixed model.  Point arguments as lrvb_glmm_terms.  Per observation, PER UNIT WEIGHT,
  *   a1' = psi_rho(rho_n, s_n) - y_n,   a2' = psi_s(rho_n, s_n)

@@ -89,6 +89,8 @@ _SIGNATURES = {
     'lrvb_set_group_design': [_VP, _VP, c_i64, c_i64],
     'lrvb_glmm_slopes_terms': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, _VP, _VP, ctypes.c_int32],
     'lrvb_glmm_slopes_schur': [_VP, _VP, _VP, _VP, c_i64, c_i64, _VP],
+    'lrvb_glmm_slopes_solve_forward': [_VP, _VP, c_i64, c_i64, c_i64, _VP],
+    'lrvb_glmm_slopes_solve_back': [_VP, _VP, c_i64, c_i64, c_i64, _VP],
     'lrvb_glmm_obs_influence': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, c_i64, c_i64, c_i64, _VP],
     'lrvb_glmm_group_influence': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, c_i64, _VP],
     'lrvb_glmm_slopes_obs_influence': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, c_i64, c_i64, c_i64, _VP],

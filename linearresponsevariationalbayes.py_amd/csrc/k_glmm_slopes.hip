@@ -199,6 +199,42 @@ int launch_glmm_slopes_rows(lrvb_ctx* c, int Kz, const double* Z, const double* 
 }
 int glmm_slopes_ncol(int P, int Kz) { return 2 * Kz + Kz * (2 * Kz + 1) + 4 * Kz * P; }
 
+// A = L L^T of one local block from its upper triangle a (row-major), L row-major into Ls; false where a pivot is not positive
+// (the factor then continues with 1 in its place).  One thread; shared by the elimination and by the two substitution kernels
+// of the solve below, so that all three see the same L bit for bit.
+template <int K2>
+__device__ __forceinline__ bool gs_local_chol(const double* __restrict__ a, double* __restrict__ Ls)
+{
+    double A[K2][K2];
+    int t = 0;
+#pragma unroll
+    for (int i = 0; i < K2; ++i)
+#pragma unroll
+        for (int j = i; j < K2; ++j) A[i][j] = a[t++];
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < K2; ++j) {                                       // column j of L, kept in A[j][j ..] (L_ij = A[j][i], i >= j)
+        double d = A[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d -= A[k][j] * A[k][j];
+        if (!(d > 0.0)) { ok = false; d = 1.0; }
+        const double l = sqrt(d);
+        A[j][j] = l;
+#pragma unroll
+        for (int i = j + 1; i < K2; ++i) {
+            double sij = A[j][i];
+#pragma unroll
+            for (int k = 0; k < j; ++k) sij -= A[k][i] * A[k][j];
+            A[j][i] = sij / l;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < K2; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) Ls[i * K2 + j] = A[j][i];
+    return ok;
+}
+
 // ---- elimination of the 2 K G local parameters ---------------------------------------------------------------------------------
 // Per group g: A_g (2 K x 2 K, the complete local block in the coordinates that are eliminated, its K (2 K + 1) upper-triangle
 // entries row-major from the host) = L L^T, and the 2 K border rows over the R = 2 P + 3 K coupled global coordinates
@@ -220,37 +256,7 @@ void glmm_slopes_schur_rows_kernel(i64 G, int P, const double* __restrict__ gsum
     if (g >= G) return;
     const int ncol = nsc + 4 * KZ * P, R = 2 * P + 3 * KZ;
     const int tid = threadIdx.x;
-    if (tid == 0) {
-        double A[K2][K2];
-        const double* a = loc + g * NT;
-        int t = 0;
-#pragma unroll
-        for (int i = 0; i < K2; ++i)
-#pragma unroll
-            for (int j = i; j < K2; ++j) A[i][j] = a[t++];
-        bool ok = true;
-#pragma unroll
-        for (int j = 0; j < K2; ++j) {                                   // column j of L, kept in A[j][j ..] (L_ij = A[j][i], i >= j)
-            double d = A[j][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) d -= A[k][j] * A[k][j];
-            if (!(d > 0.0)) { ok = false; d = 1.0; }
-            const double l = sqrt(d);
-            A[j][j] = l;
-#pragma unroll
-            for (int i = j + 1; i < K2; ++i) {
-                double sij = A[j][i];
-#pragma unroll
-                for (int k = 0; k < j; ++k) sij -= A[k][i] * A[k][j];
-                A[j][i] = sij / l;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < K2; ++i)
-#pragma unroll
-            for (int j = 0; j <= i; ++j) Ls[i * K2 + j] = A[j][i];
-        if (!ok) *bad = 1;
-    }
+    if (tid == 0 && !gs_local_chol<K2>(loc + g * NT, Ls)) *bad = 1;
     if (tid >= 64 && tid < 64 + K2) fs[tid - 64] = scale[g * K2 + (tid - 64)];
     if (tid >= 128 && tid < 128 + K2 * 3) cs[tid - 128] = closed[g * K2 * 3 + (tid - 128)];
     __syncthreads();
@@ -285,6 +291,84 @@ int launch_glmm_slopes_schur_rows(lrvb_ctx* c, int Kz, const double* gsum, const
     case 4: hipLaunchKernelGGL(glmm_slopes_schur_rows_kernel<4>, grid, block, 0, c->stream, G, P, gsum, loc, scale, closed, U, ldu, bad); break;
     default: LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "logistic mixed model with slopes: 1 <= K <= 4");
     }
+    HIP_TRY(hipGetLastError());
+    return LRVB_OK;
+}
+
+// ---- the two substitution passes of the device-resident block-arrow solve ---------------------------------
+// One workgroup per group.  Thread 0 re-derives L_g from the resident copy of the uploaded block (gs_local_chol: the L that
+// U_g = L_g^-1 C_g was formed with) into LDS; thread t then owns the columns q = t, t + blockDim.x, .. of the group's 2 K x Q
+// slab (row-major: consecutive threads touch consecutive doubles of each of its 2 K rows), keeps the 2 K values of a column
+// in registers and runs one triangular substitution on them.  The contractions over the groups (U^T T) and over the coupled
+// rows (U x) are the library's GEMM on the fp64 matrix cores, launched by the entry points.  Only blocks whose factorisation
+// succeeded get here (the entry points ask for a valid resident factor).  No atomics; every output has one writer.
+template <int KZ>
+__global__ __launch_bounds__(256)
+void glmm_slopes_solve_forward_kernel(i64 G, i64 Q, const double* __restrict__ loc /* G x K (2 K + 1) */,
+                                      double* __restrict__ T /* G x 2 K x Q: R_local in, L^-1 R_local out */)
+{
+    constexpr int K2 = 2 * KZ, NT = KZ * (K2 + 1);
+    __shared__ double Ls[K2 * K2];
+    const i64 g = blockIdx.x;
+    if (g >= G) return;
+    if (threadIdx.x == 0) gs_local_chol<K2>(loc + g * NT, Ls);
+    __syncthreads();
+    double* tg = T + g * K2 * Q;
+    for (i64 q = threadIdx.x; q < Q; q += blockDim.x) {
+        double t[K2];
+#pragma unroll
+        for (int i = 0; i < K2; ++i) {
+            double v = tg[i * Q + q];
+#pragma unroll
+            for (int j = 0; j < i; ++j) v -= Ls[i * K2 + j] * t[j];
+            t[i] = v / Ls[i * K2 + i];
+            tg[i * Q + q] = t[i];
+        }
+    }
+}
+
+template <int KZ>
+__global__ __launch_bounds__(256)
+void glmm_slopes_solve_back_kernel(i64 G, i64 Q, const double* __restrict__ loc, const double* __restrict__ T /* G x 2 K x Q */,
+                                   double* __restrict__ W /* G x 2 K x Q: U_g x in, L^-T (T_g - U_g x) out */)
+{
+    constexpr int K2 = 2 * KZ, NT = KZ * (K2 + 1);
+    __shared__ double Ls[K2 * K2];
+    const i64 g = blockIdx.x;
+    if (g >= G) return;
+    if (threadIdx.x == 0) gs_local_chol<K2>(loc + g * NT, Ls);
+    __syncthreads();
+    const double* tg = T + g * K2 * Q;
+    double* wg = W + g * K2 * Q;
+    for (i64 q = threadIdx.x; q < Q; q += blockDim.x) {
+        double x[K2];
+#pragma unroll
+        for (int i = 0; i < K2; ++i) x[i] = tg[i * Q + q] - wg[i * Q + q];
+#pragma unroll
+        for (int i = K2 - 1; i >= 0; --i) {
+            double v = x[i];
+#pragma unroll
+            for (int j = i + 1; j < K2; ++j) v -= Ls[j * K2 + i] * x[j];
+            x[i] = v / Ls[i * K2 + i];
+            wg[i * Q + q] = x[i];
+        }
+    }
+}
+
+int launch_glmm_slopes_solve(lrvb_ctx* c, int Kz, bool back, i64 Q, const double* loc, double* T, double* W) {
+    const i64 G = c->n_groups;
+    const dim3 grid((unsigned)G), block(Q <= 64 ? 64 : (Q <= 128 ? 128 : 256));
+#define GS_SOLVE(KK) do {                                                                                                        \
+        if (back) hipLaunchKernelGGL(glmm_slopes_solve_back_kernel<KK>, grid, block, 0, c->stream, G, Q, loc, (const double*)T, W); \
+        else hipLaunchKernelGGL(glmm_slopes_solve_forward_kernel<KK>, grid, block, 0, c->stream, G, Q, loc, T); } while (0)
+    switch (Kz) {
+    case 1: GS_SOLVE(1); break;
+    case 2: GS_SOLVE(2); break;
+    case 3: GS_SOLVE(3); break;
+    case 4: GS_SOLVE(4); break;
+    default: LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "logistic mixed model with slopes: 1 <= K <= 4");
+    }
+#undef GS_SOLVE
     HIP_TRY(hipGetLastError());
     return LRVB_OK;
 }

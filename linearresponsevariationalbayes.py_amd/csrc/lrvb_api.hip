@@ -231,7 +231,7 @@ extern "C" int lrvb_ctx_destroy(lrvb_ctx* c) {
     DevBuf* all[] = { &c->X, &c->y, &c->w, &c->quadA, &c->quadM, &c->quadB, &c->theta, &c->eta, &c->j1, &c->j2,
                       &c->vtmp, &c->vtmp2, &c->vtmp3, &c->g_eta, &c->g_free, &c->lp, &c->cw, &c->zbuf,
                       &c->part_vec, &c->part_val, &c->stats, &c->tile_part, &c->Heta, &c->Hfree, &c->Jdense,
-                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn, &c->glmm, &c->gz, &c->glmms,
+                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn, &c->glmm, &c->gz, &c->glmms, &c->glmms_fac, &c->glmms_T,
                       &c->sm.labels, &c->sm.p, &c->sm.wpad, &c->sm.work, &c->sm.col, &c->sm.tiles, &c->sm.rows };
     for (DevBuf* b : all) buf_free(*b);
     if (c->host_pinned) (void)hipHostFree(c->host_pinned);
@@ -1627,7 +1627,7 @@ extern "C" int lrvb_set_groups(lrvb_ctx* c, const int32_t* gid, int64_t n, int64
     c->n_groups = n_groups;
     c->gstats_valid = false;
     c->glmm_valid = false;
-    c->glmms_valid = false;
+    c->glmms_drop();
     if (c->gz_n != n) { c->gz_n = 0; c->gz_K = 0; }      // a group design of another row count is dropped
     c->zs_valid = false; c->ws_valid = false;
     return LRVB_OK;
@@ -2571,7 +2571,7 @@ extern "C" int lrvb_set_group_design(lrvb_ctx* c, const double* z, int64_t n, in
     if (!z) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
     if (K < 1 || K > 4) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 4 random effects per group (got %lld)", (long long)K);
     if (n < 1) LRVB_FAIL(LRVB_ERR_SIZE, "the group design needs at least one row");
-    c->glmms_valid = false;
+    c->glmms_drop();
     c->gz_n = 0; c->gz_K = 0;
     LRVB_TRY(buf_reserve(c, c->gz, (size_t)(n * K)));
     HIP_TRY(hipMemcpyAsync(c->gz.p, z, (size_t)(n * K) * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -2602,7 +2602,7 @@ extern "C" int lrvb_glmm_slopes_terms(lrvb_ctx* c, const double* mean, const dou
     LRVB_TRY(check_len(G_in, G, "groups of e / r"));
     for (i64 j = 0; j < P; ++j) if (!(var[j] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "var[%lld] is not positive", (long long)j);
     for (i64 g = 0; g < G * K; ++g) if (!(r_loc[g] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "r[%lld] is not positive", (long long)g);
-    c->glmms_valid = false;
+    c->glmms_drop();
     const bool want_g = grad_global_out != nullptr, want_H = H_blocks_out != nullptr;
     DevBuf& X2 = c->mx_Xk;
     if ((want_g || want_H) && (!c->x2_ready || X2.n < (size_t)(N * P))) {
@@ -2665,9 +2665,12 @@ extern "C" int lrvb_glmm_slopes_schur(lrvb_ctx* c, const double* local_blocks, c
     LRVB_TRY(check_len(G_in, G, "local blocks"));
     auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
     const int ldu = (int)up(R);
-    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(8 + up(NT * G) + up(K2 * G) + up(3 * K2 * G) + K2 * G * ldu + R * R)));
-    double* flag = c->work1.p; double* loc = flag + 8; double* sc = loc + up(NT * G); double* cl = sc + up(K2 * G);
-    double* U = cl + up(3 * K2 * G); double* Md = U + K2 * G * ldu;
+    c->glmms_fac_valid = false; c->glmms_T_Q = 0;
+    // the uploaded blocks and U outlive the call in a buffer of their own (lrvb_glmm_slopes_solve_forward / _back)
+    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(8 + up(K2 * G) + up(3 * K2 * G) + R * R)));
+    LRVB_TRY(buf_reserve(c, c->glmms_fac, (size_t)(up(NT * G) + K2 * G * ldu)));
+    double* flag = c->work1.p; double* sc = flag + 8; double* cl = sc + up(K2 * G); double* Md = cl + up(3 * K2 * G);
+    double* loc = c->glmms_fac.p; double* U = loc + up(NT * G);
     LRVB_TRY(h2d(c, loc, local_blocks, (size_t)(NT * G)));
     LRVB_TRY(h2d(c, sc, border_scale, (size_t)(K2 * G)));
     LRVB_TRY(h2d(c, cl, closed_rows, (size_t)(3 * K2 * G)));
@@ -2680,7 +2683,54 @@ extern "C" int lrvb_glmm_slopes_schur(lrvb_ctx* c, const double* local_blocks, c
     int bad = 0;
     memcpy(&bad, &fh, sizeof(int));
     if (bad) LRVB_FAIL(LRVB_ERR_NOT_POSDEF, "a local block of the logistic mixed model with slopes is not positive definite");
-    return d2h(c, M_out, Md, (size_t)(R * R));
+    LRVB_TRY(d2h(c, M_out, Md, (size_t)(R * R)));
+    c->glmms_fac_valid = true; c->glmms_fac_K = (int)K;
+    return LRVB_OK;
+}
+
+// The two device passes of the block-arrow solve around the host's Schur solve.  c->glmms_fac holds the
+// blocks as uploaded and U = L^-1 C of the last lrvb_glmm_slopes_schur; c->glmms_T keeps T = L^-1 R_local between the passes.
+static int glmm_slopes_solve_check(lrvb_ctx* c, const void* in, const void* out, int64_t G_in, int64_t K, int64_t Q) {
+    if (!in || !out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    if (K < 1 || K > 4) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 4 random effects per group (got %lld)", (long long)K);
+    if (Q < 1) LRVB_FAIL(LRVB_ERR_INVALID, "Q must be positive");
+    if (c->n_groups <= 0 || !c->glmms_valid || !c->glmms_fac_valid || c->glmms_fac_K != K)
+        LRVB_FAIL(LRVB_ERR_STATE, "no factor of %lld effects resident: call lrvb_glmm_slopes_schur first", (long long)K);
+    return check_len(G_in, c->n_groups, "groups of the right-hand side");
+}
+
+extern "C" int lrvb_glmm_slopes_solve_forward(lrvb_ctx* c, const double* R_local, int64_t G_in, int64_t K, int64_t Q, double* red_out) {
+    LRVB_TRY(ctx_bind(c));
+    LRVB_TRY(glmm_slopes_solve_check(c, R_local, red_out, G_in, K, Q));
+    const i64 P = c->P, G = c->n_groups, R = 2 * P + 3 * K, K2 = 2 * K, NT = K * (K2 + 1);
+    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
+    const i64 ldu = up(R);
+    c->glmms_T_Q = 0;
+    LRVB_TRY(buf_reserve(c, c->glmms_T, (size_t)(K2 * G * Q)));
+    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(R * Q)));
+    double* loc = c->glmms_fac.p; double* U = loc + up(NT * G); double* T = c->glmms_T.p; double* red = c->work1.p;
+    LRVB_TRY(h2d(c, T, R_local, (size_t)(K2 * G * Q)));
+    LRVB_TRY(launch_glmm_slopes_solve(c, (int)K, false, Q, loc, T, nullptr));
+    LRVB_TRY(launch_gemm(c, true, false, R, Q, K2 * G, 1.0, U, ldu, T, Q, 0.0, red, Q));      // red = sum_g U_g^T T_g
+    LRVB_TRY(d2h(c, red_out, red, (size_t)(R * Q)));
+    c->glmms_T_Q = Q;
+    return LRVB_OK;
+}
+
+extern "C" int lrvb_glmm_slopes_solve_back(lrvb_ctx* c, const double* x_coupled, int64_t G_in, int64_t K, int64_t Q, double* X_local_out) {
+    LRVB_TRY(ctx_bind(c));
+    LRVB_TRY(glmm_slopes_solve_check(c, x_coupled, X_local_out, G_in, K, Q));
+    if (c->glmms_T_Q == 0) LRVB_FAIL(LRVB_ERR_STATE, "no forward pass resident: call lrvb_glmm_slopes_solve_forward first");
+    LRVB_TRY(check_len(Q, c->glmms_T_Q, "columns (those of the forward pass)"));
+    const i64 P = c->P, G = c->n_groups, R = 2 * P + 3 * K, K2 = 2 * K, NT = K * (K2 + 1);
+    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
+    const i64 ldu = up(R);
+    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(up(R * Q) + K2 * G * Q)));
+    double* loc = c->glmms_fac.p; double* U = loc + up(NT * G); double* xs = c->work1.p; double* W = xs + up(R * Q);
+    LRVB_TRY(h2d(c, xs, x_coupled, (size_t)(R * Q)));
+    LRVB_TRY(launch_gemm(c, false, false, K2 * G, Q, R, 1.0, U, ldu, xs, Q, 0.0, W, Q));      // W_g = U_g x
+    LRVB_TRY(launch_glmm_slopes_solve(c, (int)K, true, Q, loc, c->glmms_T.p, W));
+    return d2h(c, X_local_out, W, (size_t)(K2 * G * Q));
 }
 
 // ---- weight influence of the logistic mixed model (k_glmm.hip) -------------------------------------------------------------------

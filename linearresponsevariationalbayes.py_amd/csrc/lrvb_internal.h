@@ -132,6 +132,10 @@ struct lrvb_ctx {
     // summed over ranks; the group sums stay resident for lrvb_glmm_slopes_schur
     DevBuf gz; i64 gz_n = 0; int gz_K = 0;
     DevBuf glmms; bool glmms_valid = false; int glmms_K = 0;
+    // what lrvb_glmm_slopes_schur leaves for lrvb_glmm_slopes_solve_forward / _back: [uploaded local blocks (up(K (2 K + 1) G)) |
+    // U (2 K G x ld(R))] of glmms_fac_K effects, and T = L^-1 R_local (2 K G x glmms_T_Q; 0 = no forward pass yet)
+    DevBuf glmms_fac, glmms_T; bool glmms_fac_valid = false; int glmms_fac_K = 0; i64 glmms_T_Q = 0;
+    void glmms_drop() { glmms_valid = false; glmms_fac_valid = false; glmms_T_Q = 0; }
     DevBuf opt;                    // trust-region Newton-CG: 12 D-vectors (+ the D x D preconditioner)
     DevBuf cgm[9];                 // blocked CG: B, X, R, P, Q, Z (Q x D), U, W (Q x V), R^T (P x Q)
     DevBuf cgT;                    // N x Q products X U^T of the blocked HVP
@@ -249,6 +253,8 @@ int  launch_glmm_slopes_rows(lrvb_ctx* c, int K, const double* Z /* N x K */, co
 int  launch_glmm_slopes_schur_rows(lrvb_ctx* c, int K, const double* gsum, const double* loc /* G x K (2 K + 1) */,
                                    const double* scale /* G x 2 K */, const double* closed /* G x 2 K x 3 */,
                                    double* U /* 2 K G x ldu */, int ldu, int* bad);
+int  launch_glmm_slopes_solve(lrvb_ctx* c, int K, bool back, i64 Q, const double* loc /* the blocks as uploaded */,
+                              double* T /* G x 2 K x Q: forward in place; read by back */, double* W /* back only, in place */);
 int  launch_glmm_slopes_infl_rows(lrvb_ctx* c, int K, const double* Z, i64 n0, i64 n1, const int* gid /* original row order */,
                                   const double* m, const double* vb, const double* eg, const double* rg, const double* gx,
                                   const double* gw, int n_nodes, const double* Ag /* Q x 2 P */, const double* Al /* G x 2 K x Q */,

@@ -23,6 +23,8 @@ coordinates [e_g0 .. e_g,K-1 | i_g0 .. i_g,K-1] and a border of R = 2 P + 3 K co
 `LogisticGLMMObjective`.  The observation weights are the hyper-parameter `weights_par` (the constructor's `weights=` is its
 initial value); `obs_influence`, `group_influence` and `ParametricSensitivityLinearApproximation(..., stream_hyper=True)` stream
 the sensitivity of any moment to them (`lrvb_glmm_slopes_obs_influence`, `lrvb_glmm_slopes_group_influence`).
+`solve`, `lrvb_cov` and the two influence methods take `on_device=True`: the block-arrow solve then runs on the factors the
+elimination left on the device (`block_arrow_solve_by_phases`) and the border never reaches the host.
 """
 import numpy as np
 from scipy import special
@@ -62,6 +64,12 @@ def pack_group_sums(g_loc, loc, border):
     G, K2 = g_loc.shape
     iu = np.triu_indices(K2)
     return np.hstack([g_loc, loc[:, iu[0], iu[1]], np.asarray(border).reshape(G, -1)])
+
+
+def coupled_rows(P, K):
+    """The R = 2 P + 3 K global coordinates the border couples to: [m | i_beta | e_mu_k, a_k, b_k per k]."""
+    iem, ia = 2 * P + np.arange(K), 2 * P + 2 * K + 2 * np.arange(K)
+    return np.concatenate([np.arange(2 * P), np.stack([iem, ia, ia + 1], axis=1).ravel()])
 
 
 def _split_eta(eta, P, K, G):
@@ -136,7 +144,7 @@ def glmm_slopes_closed_forms(P, K, G, eta, data, tau_beta, mu0, kappa0, a0, b0, 
         Hgg[im, ka] = Hgg[ka, im] = -0.5 * G / i_mu[k] ** 2 * ta[k]
         Hgg[im, kb] = Hgg[kb, im] = -0.5 * G / i_mu[k] ** 2 * tb[k]
         Hgg[ka:kb + 1, ka:kb + 1] = Hab[k]
-    rows = np.concatenate([np.arange(2 * P), np.stack([iem, ia, ibb], axis=1).ravel()])
+    rows = coupled_rows(P, K)
     jl = np.concatenate([np.ones((G, K)), dr], axis=1)          # chain of the local coordinates [e | r(i)]
     loc = L * jl[:, :, None] * jl[:, None, :]
     kk = np.arange(K)
@@ -273,6 +281,33 @@ def block_arrow_solve(Hgg, rows, Hx, loc, R, schur_solve=None):
     return out.ravel() if vec else out
 
 
+def block_arrow_solve_by_phases(R, n_global, rows, s, forward, schur_solve, back):
+    """H^-1 R for the block arrow (R: D x Q or a D-vector) where the local blocks and the border are held by somebody else -- the
+    device (lrvb_glmm_slopes_solve_forward / _back) or a numpy restatement of it -- as L_g (A_g = L_g L_g^T) and U_g = L_g^-1 C_g,
+    C_g (2 K x R) being group g's border with its coupled side in the coordinates of the holder: Hx[r, l] = s_r C_g[l, r].
+
+        forward(R_local: G x 2 K x Q) -> sum_g U_g^T L_g^-1 R_local,g   (R x Q; the holder keeps T_g = L_g^-1 R_local,g)
+        schur_solve(rhs: n_global x Q) -> S^-1 rhs                      (S = Hgg - Hx H_ll^-1 Hx^T)
+        back(x_coupled: R x Q, = s o x_g[rows]) -> L_g^-T (T_g - U_g x_coupled)   (G x 2 K x Q)
+
+    This function packs the local rows into groups (`_to_groups`), does the n_global-sized step in between and unpacks."""
+    R = np.asarray(R, dtype=np.float64)
+    vec = R.ndim == 1
+    rows, s = np.asarray(rows), np.asarray(s, dtype=np.float64)
+    ng, K = int(n_global), int(n_global) - len(rows)               # n_global = 2 P + 4 K, len(rows) = 2 P + 3 K
+    R2 = R.reshape(R.shape[0], -1)
+    if K < 1 or (R2.shape[0] - ng) % (2 * K) or R2.shape[0] <= ng:
+        raise ValueError('R must have n_global + 2 G K rows')
+    G = (R2.shape[0] - ng) // (2 * K)
+    red = np.asarray(forward(np.ascontiguousarray(_to_groups(R2[ng:], G, K)))).reshape(len(rows), -1)
+    rhs = R2[:ng].copy()
+    rhs[rows] -= s[:, None] * red
+    xg = np.asarray(schur_solve(np.ascontiguousarray(rhs)), dtype=np.float64).reshape(ng, -1)
+    xl = np.asarray(back(np.ascontiguousarray(s[:, None] * xg[rows]))).reshape(G, 2 * K, -1)
+    out = np.vstack([xg, _from_groups(xl, G, K)])
+    return out.ravel() if vec else out
+
+
 def split_influence_operand(A, P, K, G):
     """The operand A (Q x (2 P + 2 G K), columns [A_m | A_v | A_e (G K, group-major) | A_r (G K)]) of the influence entries in
     their two layouts (include/lrvb_hip.h): A_global (Q x 2 P) and A_local (G x 2 K x Q: group g holds the Q-vectors of
@@ -319,6 +354,7 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
         self._x, self._z = x, z
         self._external = None
         self._point_key = None
+        self._dev_factor_key = None                  # what the factors of solve(on_device=True) were built at
         self._push_state()                           # the initial weights on the device: direct calls on `ctx` see them from the start
 
     tau_beta = property(lambda self: float(self._hyper_vec('beta_prior_info')[0]))
@@ -391,6 +427,7 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
         P, K, G = self.P, self.K, self.G
         _, ib, _, _, _, _, e, ig = _split_eta(eta, P, K, G)
         self._push_state()
+        self._dev_factor_key = None                  # lrvb_glmm_slopes_terms drops the factor on the device
         out = self.ctx.glmm_slopes_terms(eta[:P], 1.0 / ib, e, 1.0 / ig, self.gh_x, self.gh_w, want_grad=want_grad or want_hess,
                                          want_hess=want_hess, want_border=want_border)
         return self._pieces_of(*out)
@@ -405,6 +442,7 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
         eta = _hip.as_f64(eta).ravel()
         _, ib, _, _, _, _, e, ig = _split_eta(eta, self.P, self.K, self.G)
         self._push_state()
+        self._dev_factor_key = None
         val, gg, Hb, gs = self.ctx.glmm_slopes_terms(eta[:self.P], 1.0 / ib, e, 1.0 / ig, self.gh_x, self.gh_w)
         return np.concatenate([[val], gg, Hb.ravel(), gs.ravel()])
 
@@ -522,6 +560,7 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
         fv = _hip.as_f64(free_val).ravel()
         P, K, G, ng = self.P, self.K, self.G, self.n_global
         self._push_state()
+        self._dev_factor_key = None
         eta = self._eta(fv, True)
         j1, j2 = self._jac(eta)
         cf = self._closed(eta, want_border=False)    # the group sums of the point stay resident; the border is not copied back
@@ -557,12 +596,43 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
                 None if self._external is None else id(self._external))
 
     # ---- the whole arrow: solve, covariance of any moment ----------------------------------------------------------------
+    def _device_factors(self, x, is_free):
+        """on_device=True: the Schur factor on the global context and the local factor (L_g, U_g) on `ctx` at the free point x,
+        built here (`global_hessian(x, want_host=False)`, `chol_factor_last()`: the border never reaches the host) unless both
+        are those of this point, weights and hyper-parameters.  Returns the scaling s of the coupled rows: the border in free
+        coordinates is Hx[r, l] = s_r C_g[l, r] for the device's C_g."""
+        if not is_free:
+            raise ValueError('on_device=True solves in free coordinates')
+        if self._external is not None:
+            raise ValueError('on_device=True uses the group sums resident on this device, not installed statistics')
+        fv = _hip.as_f64(x).ravel()
+        self._push_state()
+        key = self._resident_key(fv)
+        if getattr(self, '_schur_key', None) != key or self._dev_factor_key != key:
+            self.global_hessian(fv, want_host=False)
+            self._ensure_gctx().chol_factor_last()
+            self._dev_factor_key = key
+        eta = self._eta(fv, True)
+        dv = np.concatenate([np.ones(self.P), -1.0 / eta[self.P:2 * self.P] ** 2, np.ones(3 * self.K)])
+        return self._jac(eta)[0][coupled_rows(self.P, self.K)] * dv
+
     @_hip.host_blas
-    def solve(self, x, R, is_free=True, resident_factor=False):
+    def solve(self, x, R, is_free=True, resident_factor=False, on_device=False):
         """H^-1 R at x (R: D x Q or a D-vector, local rows allowed) by `block_arrow_solve`.  resident_factor=True solves the
         Schur complement with the factor on the global context: call `global_hessian(x, want_host=False)` and
         `_ensure_gctx().chol_factor_last()` at the same point first (free coordinates); a factor built at another point, or
-        under other weights or hyper-parameters, is refused with a ValueError."""
+        under other weights or hyper-parameters, is refused with a ValueError.
+        on_device=True (free coordinates, this process's own rows): the local blocks and the border stay on the device
+        (`block_arrow_solve_by_phases` around lrvb_glmm_slopes_solve_forward / _back); the factors are
+        built here when they are not those of this point and reused otherwise."""
+        if on_device:
+            s = self._device_factors(x, is_free)
+            D = self.n_global + 2 * self.G * self.K
+            if np.shape(R)[0] != D:
+                raise ValueError('R must have {} rows'.format(D))
+            return block_arrow_solve_by_phases(R, self.n_global, coupled_rows(self.P, self.K), s, self.ctx.glmm_slopes_solve_forward,
+                                               self._ensure_gctx().chol_solve,
+                                               lambda xc: self.ctx.glmm_slopes_solve_back(xc, self.G, self.K))
         _, Hgg, rows, Hx, loc = self._arrow(x, is_free)
         if resident_factor and (not is_free or getattr(self, '_schur_key', None) != self._resident_key(_hip.as_f64(x).ravel())):
             raise ValueError('resident_factor=True needs global_hessian(x, want_host=False) and chol_factor_last() at this point, '
@@ -579,21 +649,23 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
             M = np.hstack([M, np.zeros((M.shape[0], D - M.shape[1]))])
         return M
 
-    def lrvb_cov(self, x, moment_jac, is_free=True):
+    def lrvb_cov(self, x, moment_jac, is_free=True, on_device=False):
         """M H^-1 M^T (Q x Q): the linear-response covariance of the moments M theta, M = moment_jac being Q x D (columns of the
-        group effects allowed) or Q x n_global (zero-padded)."""
+        group effects allowed) or Q x n_global (zero-padded).  on_device: as `solve`."""
         M = self._moment_jac(moment_jac)
-        return M @ self.solve(x, np.ascontiguousarray(M.T), is_free)
+        return M @ self.solve(x, np.ascontiguousarray(M.T), is_free, on_device=on_device)
 
-    def _influence_operand(self, x, moment_jac, is_free, chol):
+    def _influence_operand(self, x, moment_jac, is_free, chol, on_device=False):
         """A = -M H^-1 J (Q x (2 P + 2 G K)) in the coordinates (m, v, e, r) of the device entries -- the element-wise chain from
         eta's (m, i_beta, e, i), the columns of mu and tau dropped -- and the point in those coordinates."""
         self._push_state()
         M = self._moment_jac(moment_jac)
         P, K, G, ng = self.P, self.K, self.G, self.n_global
         GK = G * K
+        if on_device and chol is not None:
+            raise ValueError('on_device=True does not use a dense factor: pass one of the two')
         if chol is None:
-            S = self.solve(x, np.ascontiguousarray(M.T), is_free)
+            S = self.solve(x, np.ascontiguousarray(M.T), is_free, on_device=on_device)
         else:
             S = np.asarray(chol.solve(np.ascontiguousarray(M.T))).reshape(ng + 2 * GK, -1)
         eta = self._eta(x, is_free)
@@ -605,21 +677,22 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
         A = -(S[keep] * chain[:, None]).T
         return np.ascontiguousarray(A), (eta[:P], v, e, r, self.gh_x, self.gh_w)
 
-    def obs_influence(self, x, moment_jac, n0=0, n1=None, is_free=True, chol=None):
+    def obs_influence(self, x, moment_jac, n0=0, n1=None, is_free=True, chol=None, on_device=False):
         """Rows n0..n1 of (moment_jac @ d par / d w)^T ((n1 - n0) x Q), streamed over the observations on the device
         (`lrvb_glmm_slopes_obs_influence`); the N x D cross Hessian is never formed.  A = -moment_jac H^-1 J comes from the dense
         factor `chol` where one is given (ParametricSensitivityLinearApproximation holds it), otherwise from `block_arrow_solve`
-        -- the route for large G, where no dense factor exists.  Per unit weight: a row of weight zero gets the influence of
-        adding it."""
-        A, pt = self._influence_operand(x, moment_jac, is_free, chol)
+        -- the route for large G, where no dense factor exists; with on_device=True from the device-resident solve (`solve`), so
+        that no N- or G-sized host arithmetic lies between the fit and the streamed rows.  Per unit weight: a row of weight zero
+        gets the influence of adding it."""
+        A, pt = self._influence_operand(x, moment_jac, is_free, chol, on_device)
         return self.ctx.glmm_slopes_obs_influence(*pt, A, n0=n0, n1=n1)
 
-    def group_influence(self, x, moment_jac, is_free=True, chol=None):
+    def group_influence(self, x, moment_jac, is_free=True, chol=None, on_device=False):
         """G x Q: row g is the derivative of the moments with respect to a common multiplier on the weights of group g's rows,
         sum_{n in g} w_n * (row n of `obs_influence`) -- minus it is the linear prediction of leaving the cluster out.  The
         group's own prior terms on u_g stay in the model and are not part of it.  Fixed summation order on the device
-        (`lrvb_glmm_slopes_group_influence`); an empty group gives a zero row."""
-        A, pt = self._influence_operand(x, moment_jac, is_free, chol)
+        (`lrvb_glmm_slopes_group_influence`); an empty group gives a zero row.  on_device: as `obs_influence`."""
+        A, pt = self._influence_operand(x, moment_jac, is_free, chol, on_device)
         return self.ctx.glmm_slopes_group_influence(*pt, A)
 
     # ---- hyper-parameters ---------------------------------------------------------------------------------------------

@@ -395,6 +395,28 @@ class DeviceContext(object):
         self._check(self._lib.lrvb_glmm_slopes_schur(self._h, _hip.ptr(A), _hip.ptr(sc), _hip.ptr(cl), G, K, _hip.ptr(M)))
         return M
 
+    def glmm_slopes_solve_forward(self, R_local):
+        """red (R x Q, R = 2 P + 3 K) = sum_g U_g^T L_g^-1 R_local,g with the factor the last `glmm_slopes_schur` left resident
+        (lrvb_glmm_slopes_solve_forward); R_local is G x 2 K x Q, group g = the Q-vectors of [e_g. | r_g.].  T = L^-1 R_local stays
+        on the device for `glmm_slopes_solve_back`."""
+        Rl = _hip.as_f64(R_local)
+        if Rl.ndim != 3 or Rl.shape[1] % 2:
+            raise ValueError('expected a G x 2 K x Q right-hand side')
+        G, K, Q = Rl.shape[0], Rl.shape[1] // 2, Rl.shape[2]
+        red = np.empty((2 * self.n_cols + 3 * K, Q))
+        self._check(self._lib.lrvb_glmm_slopes_solve_forward(self._h, _hip.ptr(Rl), G, K, Q, _hip.ptr(red)))
+        return red
+
+    def glmm_slopes_solve_back(self, x_coupled, G, K):
+        """X_local (G x 2 K x Q) = L_g^-T (T_g - U_g x_coupled) after `glmm_slopes_solve_forward` with as many columns
+        (lrvb_glmm_slopes_solve_back); x_coupled is R x Q, already multiplied by the scaling of the coupled rows."""
+        xc = _hip.as_f64(x_coupled)
+        if xc.ndim != 2 or xc.shape[0] != 2 * self.n_cols + 3 * K:
+            raise ValueError('expected the {} coupled rows x Q'.format(2 * self.n_cols + 3 * K))
+        X = np.empty((G, 2 * K, xc.shape[1]))
+        self._check(self._lib.lrvb_glmm_slopes_solve_back(self._h, _hip.ptr(xc), G, K, xc.shape[1], _hip.ptr(X)))
+        return X
+
     def _glmm_influence_args(self, mean, var, e, r, gh_x, gh_w, A):
         """The point and the operand A (Q x (2 P + 2 G), columns [A_m | A_v | A_e | A_r]) in the layout of the C entries:
         A_global (Q x 2 P) and A_local (G x 2 Q, row g = [A_e[:, g] | A_r[:, g]])."""

@@ -25,13 +25,17 @@ initial value); `obs_influence`, `group_influence` and `ParametricSensitivityLin
 the sensitivity of any moment to them (`lrvb_glmm_slopes_obs_influence`, `lrvb_glmm_slopes_group_influence`).
 `solve`, `lrvb_cov` and the two influence methods take `on_device=True`: the block-arrow solve then runs on the factors the
 elimination left on the device (`block_arrow_solve_by_phases`) and the border never reaches the host.
+
+The host algebra of the block arrow is `block_arrow.py` (re-exported here); everything of the objective that is not a device
+entry is `_LogisticMixedModel`, which `LogisticGLMMObjective` (glmm.py) instantiates at K = 1.
 """
 import numpy as np
 from scipy import special
-from scipy import sparse as sp_sparse
-from scipy import linalg as sp_linalg
 
 from . import _hip
+from .block_arrow import (block_arrow_to_free, block_arrow_matvec, block_arrow_dense, block_arrow_sparse,    # noqa: F401 (re-exported)
+                          block_arrow_schur_term, block_arrow_local_solve, block_arrow_solve, block_arrow_solve_by_phases,
+                          _to_groups, _from_groups, _local_index, _local_chol)
 from .models import DeviceContext, DeclaredHypers, refuse_double_reduction
 from .packing import HyperVectorParam, ResidentVector
 from .quadform import gamma_prior_hyper_grad, gamma_prior_hyper_cross
@@ -171,143 +175,6 @@ def glmm_slopes_closed_forms(P, K, G, eta, data, tau_beta, mu0, kappa0, a0, b0, 
     return out
 
 
-# ---- the block arrow: global block Hgg, border Hx (R x 2 G K) on the coupled rows, G local 2 K x 2 K blocks ------------------------
-def _to_groups(x, G, K):
-    """Local part (2 G K [x Q], order [e (G K) | i (G K)]) -> G x 2 K x Q."""
-    x = np.asarray(x, dtype=np.float64).reshape(2, G, K, -1)
-    return np.concatenate([x[0], x[1]], axis=1)
-
-
-def _from_groups(x, G, K):
-    """G x 2 K x Q -> 2 G K x Q in the order of the local part."""
-    return np.concatenate([x[:, :K].reshape(G * K, -1), x[:, K:].reshape(G * K, -1)], axis=0)
-
-
-def _local_chol(loc):
-    try:
-        return np.linalg.cholesky(loc)
-    except np.linalg.LinAlgError:
-        raise np.linalg.LinAlgError('a 2 K x 2 K local block is not positive definite')
-
-
-def block_arrow_to_free(cf, j1, j2, n_global, G, K):
-    """The pieces of `glmm_slopes_closed_forms` in FREE coordinates for an element-wise packing (j1 = d eta / d theta, j2 = its
-    second derivative, both D-vectors): (grad, Hgg, rows, Hx, loc)."""
-    g, ng = cf['grad'], n_global
-    jg = j1[:ng]
-    Hgg = cf['Hgg'] * jg[:, None] * jg[None, :] + np.diag(g[:ng] * j2[:ng])
-    rows = cf['rows']
-    Hx = None if cf['Hx'] is None else cf['Hx'] * jg[rows][:, None] * j1[ng:][None, :]
-    jl = _to_groups(j1[ng:], G, K)[:, :, 0]
-    dl = _to_groups(g[ng:] * j2[ng:], G, K)[:, :, 0]
-    loc = cf['loc'] * jl[:, :, None] * jl[:, None, :]
-    kk = np.arange(2 * K)
-    loc[:, kk, kk] += dl
-    return g * j1, Hgg, rows, Hx, loc
-
-
-def block_arrow_matvec(Hgg, rows, Hx, loc, v):
-    """H v for the block arrow: O(n_global^2 + P G K + G K^2)."""
-    ng, G, K = Hgg.shape[0], loc.shape[0], loc.shape[1] // 2
-    v = np.asarray(v, dtype=np.float64).ravel()
-    vg, vl = v[:ng], v[ng:]
-    og = Hgg @ vg
-    og[rows] += Hx @ vl
-    ol = Hx.T @ vg[rows] + _from_groups(np.einsum('gij,gjq->giq', loc, _to_groups(vl, G, K)), G, K)[:, 0]
-    return np.concatenate([og, ol])
-
-
-def _local_index(G, K):
-    """Position, in the local part of the vector, of coordinate i of group g's block: G x 2 K."""
-    gk = np.arange(G * K).reshape(G, K)
-    return np.concatenate([gk, G * K + gk], axis=1)
-
-
-def block_arrow_dense(Hgg, rows, Hx, loc):
-    ng, G, K = Hgg.shape[0], loc.shape[0], loc.shape[1] // 2
-    D = ng + 2 * G * K
-    H = np.zeros((D, D))
-    H[:ng, :ng] = Hgg
-    H[rows, ng:] = Hx
-    H[ng:, rows] = Hx.T
-    li = ng + _local_index(G, K)
-    H[li[:, :, None], li[:, None, :]] = loc
-    return H
-
-
-def _border_blocks(Hx, G, K):
-    """Hx (R x 2 G K) as G x 2 K x R: C_g^T per group."""
-    return _to_groups(Hx.T, G, K)
-
-
-def block_arrow_schur_term(rows, Hx, loc):
-    """M = sum_g C_g A_g^-1 C_g^T on the coupled rows (host route; the device route is lrvb_glmm_slopes_schur)."""
-    G, K = loc.shape[0], loc.shape[1] // 2
-    _local_chol(loc)
-    Ct = _border_blocks(Hx, G, K)
-    return np.einsum('gir,gis->rs', Ct, np.linalg.solve(loc, Ct))
-
-
-def block_arrow_local_solve(loc, B):
-    """A_g^-1 B_g for every group (B: G x 2 K [x Q])."""
-    B = np.asarray(B, dtype=np.float64)
-    return np.linalg.solve(loc, B.reshape(B.shape[0], B.shape[1], -1)).reshape(B.shape)
-
-
-def block_arrow_solve(Hgg, rows, Hx, loc, R, schur_solve=None):
-    """H^-1 R for the block arrow (R: D x Q or a D-vector) without the dense matrix: the G local blocks are solved (batched),
-    the result is reduced onto the coupled global rows, the Schur complement is factored and solved, and the local parameters
-    are back-substituted -- O(P G K Q + G K^3 + n_global^3).  `schur_solve` (n_global x Q -> n_global x Q) replaces the host
-    factorisation of the Schur complement.  A local block or a Schur complement that is not positive definite raises
-    `np.linalg.LinAlgError`."""
-    ng, G, K = Hgg.shape[0], loc.shape[0], loc.shape[1] // 2
-    R = np.asarray(R, dtype=np.float64)
-    vec = R.ndim == 1
-    R2 = R.reshape(ng + 2 * G * K, -1)
-    _local_chol(loc)
-    Ct = _border_blocks(Hx, G, K)                                        # G x 2 K x R
-    tl = np.linalg.solve(loc, _to_groups(R2[ng:], G, K))                 # H_ll^-1 R_l, G x 2 K x Q
-    rhs = R2[:ng].copy()
-    rhs[rows] -= np.einsum('gir,giq->rq', Ct, tl)
-    if schur_solve is None:
-        S = Hgg.copy()
-        S[np.ix_(rows, rows)] -= np.einsum('gir,gis->rs', Ct, np.linalg.solve(loc, Ct))
-        L = np.linalg.cholesky(0.5 * (S + S.T))                          # LinAlgError where it is not positive definite
-        xg = sp_linalg.cho_solve((L, True), rhs)
-    else:
-        xg = np.asarray(schur_solve(np.ascontiguousarray(rhs)), dtype=np.float64).reshape(ng, -1)
-    cl = np.einsum('gir,rq->giq', Ct, xg[rows])                          # H_lg x_g
-    out = np.vstack([xg, _from_groups(tl - np.linalg.solve(loc, cl), G, K)])
-    return out.ravel() if vec else out
-
-
-def block_arrow_solve_by_phases(R, n_global, rows, s, forward, schur_solve, back):
-    """H^-1 R for the block arrow (R: D x Q or a D-vector) where the local blocks and the border are held by somebody else -- the
-    device (lrvb_glmm_slopes_solve_forward / _back) or a numpy restatement of it -- as L_g (A_g = L_g L_g^T) and U_g = L_g^-1 C_g,
-    C_g (2 K x R) being group g's border with its coupled side in the coordinates of the holder: Hx[r, l] = s_r C_g[l, r].
-
-        forward(R_local: G x 2 K x Q) -> sum_g U_g^T L_g^-1 R_local,g   (R x Q; the holder keeps T_g = L_g^-1 R_local,g)
-        schur_solve(rhs: n_global x Q) -> S^-1 rhs                      (S = Hgg - Hx H_ll^-1 Hx^T)
-        back(x_coupled: R x Q, = s o x_g[rows]) -> L_g^-T (T_g - U_g x_coupled)   (G x 2 K x Q)
-
-    This function packs the local rows into groups (`_to_groups`), does the n_global-sized step in between and unpacks."""
-    R = np.asarray(R, dtype=np.float64)
-    vec = R.ndim == 1
-    rows, s = np.asarray(rows), np.asarray(s, dtype=np.float64)
-    ng, K = int(n_global), int(n_global) - len(rows)               # n_global = 2 P + 4 K, len(rows) = 2 P + 3 K
-    R2 = R.reshape(R.shape[0], -1)
-    if K < 1 or (R2.shape[0] - ng) % (2 * K) or R2.shape[0] <= ng:
-        raise ValueError('R must have n_global + 2 G K rows')
-    G = (R2.shape[0] - ng) // (2 * K)
-    red = np.asarray(forward(np.ascontiguousarray(_to_groups(R2[ng:], G, K)))).reshape(len(rows), -1)
-    rhs = R2[:ng].copy()
-    rhs[rows] -= s[:, None] * red
-    xg = np.asarray(schur_solve(np.ascontiguousarray(rhs)), dtype=np.float64).reshape(ng, -1)
-    xl = np.asarray(back(np.ascontiguousarray(s[:, None] * xg[rows]))).reshape(G, 2 * K, -1)
-    out = np.vstack([xg, _from_groups(xl, G, K)])
-    return out.ravel() if vec else out
-
-
 def split_influence_operand(A, P, K, G):
     """The operand A (Q x (2 P + 2 G K), columns [A_m | A_v | A_e (G K, group-major) | A_r (G K)]) of the influence entries in
     their two layouts (include/lrvb_hip.h): A_global (Q x 2 P) and A_local (G x 2 K x Q: group g holds the Q-vectors of
@@ -316,23 +183,27 @@ def split_influence_operand(A, P, K, G):
     Q, GK = A.shape[0], G * K
     if A.ndim != 2 or A.shape[1] != 2 * P + 2 * GK:
         raise ValueError('A must have {} columns [A_m | A_v | A_e | A_r]'.format(2 * P + 2 * GK))
-    Ae = A[:, 2 * P:2 * P + GK].reshape(Q, G, K).transpose(1, 2, 0)
-    Ar = A[:, 2 * P + GK:].reshape(Q, G, K).transpose(1, 2, 0)
-    return np.ascontiguousarray(A[:, :2 * P]), np.ascontiguousarray(np.concatenate([Ae, Ar], axis=1))
+    Al = A[:, 2 * P:].reshape(Q, 2, G, K).transpose(2, 1, 3, 0)            # [g, e or r, k, q]: one pass over the operand
+    return np.ascontiguousarray(A[:, :2 * P]), np.ascontiguousarray(Al).reshape(G, 2 * K, Q)
 
 
-class LogisticGLMMSlopesObjective(DeclaredHypers):
+class _LogisticMixedModel(DeclaredHypers):
+    """What the logistic mixed models share -- everything but the parameter layout and the device entries, for K effects per
+    group.  A model gives `_layout` and the four device hooks `_terms`, `_schur`, `_obs_influence` and `_group_influence`, which
+    speak the K-generic layouts of include/lrvb_hip.h (group sums G x ncol, closed-form entries G x 2 K x 3, e and r as G x K);
+    `_solve_on_device` where it has a device-resident block-arrow solve."""
     _lrvb_device_functor = True
 
-    def __init__(self, par, x, y, z, groups, n_groups, beta_prior_info=1.0, mu_prior=(0.0, 1.0), tau_prior=(1.0, 1.0), gh_deg=20,
-                 names=('beta', 'mu', 'tau', 'u'), weights=None, device=0):
-        """names: the parameters of q(beta), q(mu), q(tau_k) -- named names[2] + str(k), k = 0..K-1 -- and q(u)."""
+    def __init__(self, par, x, y, z, groups, n_groups, beta_prior_info, mu_prior, tau_prior, gh_deg, names, weights, device):
+        """z: the N x K group design, or None for one effect per group with the unit design (nothing is sent to the device)."""
         self.par = par
-        x, z = _hip.as_f64(x), _hip.as_f64(z)
+        x = _hip.as_f64(x)
         self.n_obs, self.P = x.shape
-        if z.ndim != 2 or z.shape[0] != self.n_obs or not 1 <= z.shape[1] <= 4:
-            raise ValueError('z must be N x K with 1 <= K <= 4')
-        self.K = z.shape[1]
+        if z is not None:
+            z = _hip.as_f64(z)
+            if z.ndim != 2 or z.shape[0] != self.n_obs or not 1 <= z.shape[1] <= 4:
+                raise ValueError('z must be N x K with 1 <= K <= 4')
+        self.K = 1 if z is None else z.shape[1]
         self.G = int(n_groups)
         self._names = tuple(names)
         self._index(par, names)
@@ -346,7 +217,8 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
         self.ctx.set_data(_hip.SLOT_Y, self._y)
         self._groups = np.ascontiguousarray(np.asarray(groups).ravel(), dtype=np.int32)
         self.ctx.set_groups(self._groups, self.G)
-        self.ctx.set_group_design(z)
+        if z is not None:
+            self.ctx.set_group_design(z)
         w0 = np.ones(self.n_obs) if weights is None else _hip.as_f64(weights).ravel().copy()
         self._declare_hyper('weights', HyperVectorParam('weights', self.n_obs, val=w0))
         self.tilt_par = None
@@ -364,29 +236,20 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
     b0 = property(lambda self: float(self._hyper_vec('tau_prior')[1]))
 
     def _index(self, par, names):
-        """The layout must be the canonical one of the module docstring in both vector and free coordinates, every coordinate
-        packed element-wise (identity, or lb + exp)."""
-        P, K, G = self.P, self.K, self.G
-        self.n_global = ng = 2 * P + 4 * K
-        GK = G * K
+        """The layout must be the canonical one, in vector and in free coordinates, every coordinate packed element-wise
+        (identity, or lb + exp).  `_layout` gives it: the (parameter, field, first, last coordinate) of every block, the message
+        for a layout that differs, and the message for a parameter that holds more than these blocks."""
+        self.n_global = ng = 2 * self.P + 4 * self.K
+        D = ng + 2 * self.G * self.K
         vi, fi = par.vector_indices_dict, par.free_indices_dict
-        want = [(names[0], 'mean', 0, P), (names[0], 'info', P, 2 * P), (names[1], 'mean', 2 * P, 2 * P + K),
-                (names[1], 'info', 2 * P + K, 2 * P + 2 * K)]
-        for k in range(K):
-            o = 2 * P + 2 * K + 2 * k
-            want += [(names[2] + str(k), 'shape', o, o + 1), (names[2] + str(k), 'rate', o + 1, o + 2)]
-        want += [(names[3], 'mean', ng, ng + GK), (names[3], 'info', ng + GK, ng + 2 * GK)]
-        msg = ('the parameter must be [UVNParamVector {} ({}) | UVNParamVector {} ({}) | GammaParam {}0 .. {}{} | UVNParamArray {} ({}, {})] '
-               'in this order, the group effects pushed last'.format(names[0], P, names[1], K, names[2], names[2], K - 1, names[3], G, K))
+        want, msg, msg_more = self._layout(par, names)
         for name, field, lo, hi in want:
-            if name not in vi:
-                raise ValueError(msg)
             sub = par[name]
             for top, inner in ((vi, sub.vector_indices_dict), (fi, sub.free_indices_dict)):
                 if top[name].start + inner[field].start != lo or top[name].start + inner[field].stop != hi:
                     raise ValueError(msg)
-        if par.vector_size() != ng + 2 * GK or par.free_size() != ng + 2 * GK:
-            raise ValueError('the parameter holds more than the blocks of the model')
+        if par.vector_size() != D or par.free_size() != D:
+            raise ValueError(msg_more)
         lb = []
         for blk in par.layout_blocks():
             if blk['kind'] != _hip.BLOCK_BOX or np.isfinite(blk['ub']) or blk['free_size'] != blk['vec_size']:
@@ -423,14 +286,19 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
         gl, loc, border = unpack_group_sums(gs, self.P, self.K)
         return dict(value=val, g_glob=gg, g_loc=gl, Hb=Hb, loc=loc, border=border)
 
-    def _device_terms(self, eta, want_grad, want_hess, want_border=True):
-        P, K, G = self.P, self.K, self.G
-        _, ib, _, _, _, _, e, ig = _split_eta(eta, P, K, G)
+    def _point(self, eta):
+        """The arguments of the terms entry at eta, the weights pushed: (m, v, e, r: G x K, nodes, weights)."""
+        _, ib, _, _, _, _, e, ig = _split_eta(eta, self.P, self.K, self.G)
         self._push_state()
-        self._dev_factor_key = None                  # lrvb_glmm_slopes_terms drops the factor on the device
-        out = self.ctx.glmm_slopes_terms(eta[:P], 1.0 / ib, e, 1.0 / ig, self.gh_x, self.gh_w, want_grad=want_grad or want_hess,
-                                         want_hess=want_hess, want_border=want_border)
-        return self._pieces_of(*out)
+        self._dev_factor_key = None                  # the terms entry drops the factor on the device
+        return eta[:self.P], 1.0 / ib, e, 1.0 / ig, self.gh_x, self.gh_w
+
+    def _group_sums(self, eta, want_grad=True, want_hess=True, want_border=True):
+        """(value, global gradient, H blocks, group sums G x ncol) of this process's rows, as the terms entry gives them."""
+        return self._terms(*self._point(eta), want_grad=want_grad or want_hess, want_hess=want_hess, want_border=want_border)
+
+    def _device_terms(self, eta, want_grad, want_hess, want_border=True):
+        return self._pieces_of(*self._group_sums(eta, want_grad, want_hess, want_border))
 
     def stats_size(self):
         return 1 + 2 * self.P + 3 * self.P ** 2 + self.G * group_sums_ncol(self.P, self.K)[1]
@@ -439,11 +307,7 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
         """[value | global gradient (2 P) | H blocks (3 P^2) | group sums (G x ncol)] of THIS process's rows in the coordinates
         (m, v, e, r) at the vector-coordinate point eta: the buffer of one host-side sum over shards (a group may straddle
         shards: its sums add).  With a reduce hook on the context it is already the sum over the ranks."""
-        eta = _hip.as_f64(eta).ravel()
-        _, ib, _, _, _, _, e, ig = _split_eta(eta, self.P, self.K, self.G)
-        self._push_state()
-        self._dev_factor_key = None
-        val, gg, Hb, gs = self.ctx.glmm_slopes_terms(eta[:self.P], 1.0 / ib, e, 1.0 / ig, self.gh_x, self.gh_w)
+        val, gg, Hb, gs = self._group_sums(_hip.as_f64(eta).ravel())
         return np.concatenate([[val], gg, Hb.ravel(), gs.ravel()])
 
     def set_reduced_stats(self, flat, eta=None):
@@ -513,29 +377,16 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
     def hessian(self, x, is_free=True):
         if self.par.vector_size() > 8192:
             raise MemoryError('dense Hessian of {} parameters: use global_hessian() (Schur complement) or hvp()'.format(self.par.vector_size()))
-        _, Hgg, rows, Hx, loc = self._arrow(x, is_free)
-        return block_arrow_dense(Hgg, rows, Hx, loc)
+        return block_arrow_dense(*self._arrow(x, is_free)[1:])
 
     @_hip.host_blas
     def hvp(self, x, v, is_free=True):
-        _, Hgg, rows, Hx, loc = self._arrow(x, is_free)
-        return block_arrow_matvec(Hgg, rows, Hx, loc, v)
+        return block_arrow_matvec(*self._arrow(x, is_free)[1:], v)
 
     @_hip.host_blas
     def sparse_hessian(self, free_val):
         """The free-coordinate Hessian as a scipy CSR block arrow: global block, border and 2 K x 2 K local blocks."""
-        from .objectives import get_sparse_sub_hessian, get_sparse_sub_matrix
-        _, Hgg, rows, Hx, loc = self._arrow(free_val, True)
-        ng, G, K = self.n_global, self.G, self.K
-        D = ng + 2 * G * K
-        gi, li = np.arange(ng), np.arange(ng, D)
-        H = get_sparse_sub_hessian(Hgg, gi, D)
-        H = H + get_sparse_sub_matrix(Hx, rows, li, D, D) + get_sparse_sub_matrix(Hx.T, li, rows, D, D)
-        idx = ng + _local_index(G, K)
-        ri = np.broadcast_to(idx[:, :, None], loc.shape).ravel()
-        ci = np.broadcast_to(idx[:, None, :], loc.shape).ravel()
-        H = H + sp_sparse.coo_matrix((loc.ravel(), (ri, ci)), shape=(D, D))
-        return H.tocsr()
+        return block_arrow_sparse(*self._arrow(free_val, True)[1:])
 
     # ---- Schur complement onto the global block -----------------------------------------------------------------------
     def _ensure_gctx(self):
@@ -553,10 +404,10 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
     @_hip.host_blas
     def global_hessian(self, free_val, want_host=True):
         """H_S = H_gg - H_gl H_ll^-1 H_lg in FREE coordinates (n_global x n_global): its inverse is the linear-response
-        covariance of the global parameters.  Device route: the border formed by `lrvb_glmm_slopes_terms` stays on the GPU and
-        `lrvb_glmm_slopes_schur` eliminates the 2 G K local parameters there; the host adds the N-independent terms to the G local
-        blocks (free coordinates) and sends their upper triangles with the chain factors and the closed-form border entries.
-        The result stays resident on the global context for `chol_factor_last`."""
+        covariance of the global parameters.  Device route: the border formed by the terms entry stays on the GPU and the Schur
+        entry (lrvb_glmm_slopes_schur, lrvb_glmm_schur) eliminates the 2 G K local parameters there; the host adds the
+        N-independent terms to the G local blocks (free coordinates) and sends their upper triangles with the chain factors and
+        the closed-form border entries.  The result stays resident on the global context for `chol_factor_last`."""
         fv = _hip.as_f64(free_val).ravel()
         P, K, G, ng = self.P, self.K, self.G, self.n_global
         self._push_state()
@@ -577,7 +428,7 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
             jl = _to_groups(j1[ng:], G, K)[:, :, 0]
             scale = np.concatenate([jl[:, :K], -r * r * jl[:, K:]], axis=1)
             iu = np.triu_indices(2 * K)
-            M = self.ctx.glmm_slopes_schur(loc_f[:, iu[0], iu[1]], scale, closed)     # coordinates [m | v | e_mu_k, a_k, b_k]
+            M = self._schur(loc_f[:, iu[0], iu[1]], scale, closed)                    # coordinates [m | v | e_mu_k, a_k, b_k]
             dv = np.concatenate([np.ones(P), -1.0 / ib ** 2, np.ones(3 * K)])
             M = M * dv[:, None] * dv[None, :]
         else:
@@ -595,26 +446,9 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
         return (np.asarray(fv, dtype=np.float64).tobytes(), self._w_res.key, self._hyper_state_key(),
                 None if self._external is None else id(self._external))
 
-    # ---- the whole arrow: solve, covariance of any moment ----------------------------------------------------------------
-    def _device_factors(self, x, is_free):
-        """on_device=True: the Schur factor on the global context and the local factor (L_g, U_g) on `ctx` at the free point x,
-        built here (`global_hessian(x, want_host=False)`, `chol_factor_last()`: the border never reaches the host) unless both
-        are those of this point, weights and hyper-parameters.  Returns the scaling s of the coupled rows: the border in free
-        coordinates is Hx[r, l] = s_r C_g[l, r] for the device's C_g."""
-        if not is_free:
-            raise ValueError('on_device=True solves in free coordinates')
-        if self._external is not None:
-            raise ValueError('on_device=True uses the group sums resident on this device, not installed statistics')
-        fv = _hip.as_f64(x).ravel()
-        self._push_state()
-        key = self._resident_key(fv)
-        if getattr(self, '_schur_key', None) != key or self._dev_factor_key != key:
-            self.global_hessian(fv, want_host=False)
-            self._ensure_gctx().chol_factor_last()
-            self._dev_factor_key = key
-        eta = self._eta(fv, True)
-        dv = np.concatenate([np.ones(self.P), -1.0 / eta[self.P:2 * self.P] ** 2, np.ones(3 * self.K)])
-        return self._jac(eta)[0][coupled_rows(self.P, self.K)] * dv
+    # ---- the whole arrow: solve, covariance of any moment, weight influence --------------------------------------------------
+    def _solve_on_device(self, x, R, is_free):
+        raise ValueError('on_device=True: this model has no block-arrow solve resident on the device')
 
     @_hip.host_blas
     def solve(self, x, R, is_free=True, resident_factor=False, on_device=False):
@@ -622,17 +456,11 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
         Schur complement with the factor on the global context: call `global_hessian(x, want_host=False)` and
         `_ensure_gctx().chol_factor_last()` at the same point first (free coordinates); a factor built at another point, or
         under other weights or hyper-parameters, is refused with a ValueError.
-        on_device=True (free coordinates, this process's own rows): the local blocks and the border stay on the device
-        (`block_arrow_solve_by_phases` around lrvb_glmm_slopes_solve_forward / _back); the factors are
-        built here when they are not those of this point and reused otherwise."""
+        on_device=True (the slopes model only; free coordinates, this process's own rows): the local blocks and the border stay
+        on the device (`block_arrow_solve_by_phases` around lrvb_glmm_slopes_solve_forward / _back); the
+        factors are built here when they are not those of this point and reused otherwise."""
         if on_device:
-            s = self._device_factors(x, is_free)
-            D = self.n_global + 2 * self.G * self.K
-            if np.shape(R)[0] != D:
-                raise ValueError('R must have {} rows'.format(D))
-            return block_arrow_solve_by_phases(R, self.n_global, coupled_rows(self.P, self.K), s, self.ctx.glmm_slopes_solve_forward,
-                                               self._ensure_gctx().chol_solve,
-                                               lambda xc: self.ctx.glmm_slopes_solve_back(xc, self.G, self.K))
+            return self._solve_on_device(x, R, is_free)
         _, Hgg, rows, Hx, loc = self._arrow(x, is_free)
         if resident_factor and (not is_free or getattr(self, '_schur_key', None) != self._resident_key(_hip.as_f64(x).ravel())):
             raise ValueError('resident_factor=True needs global_hessian(x, want_host=False) and chol_factor_last() at this point, '
@@ -679,21 +507,22 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
 
     def obs_influence(self, x, moment_jac, n0=0, n1=None, is_free=True, chol=None, on_device=False):
         """Rows n0..n1 of (moment_jac @ d par / d w)^T ((n1 - n0) x Q), streamed over the observations on the device
-        (`lrvb_glmm_slopes_obs_influence`); the N x D cross Hessian is never formed.  A = -moment_jac H^-1 J comes from the dense
-        factor `chol` where one is given (ParametricSensitivityLinearApproximation holds it), otherwise from `block_arrow_solve`
-        -- the route for large G, where no dense factor exists; with on_device=True from the device-resident solve (`solve`), so
-        that no N- or G-sized host arithmetic lies between the fit and the streamed rows.  Per unit weight: a row of weight zero
-        gets the influence of adding it."""
+        (lrvb_glmm_slopes_obs_influence, lrvb_glmm_obs_influence); the N x D cross Hessian is never formed.  A = -moment_jac H^-1 J
+        comes from the dense factor `chol` where one is given (ParametricSensitivityLinearApproximation holds it), otherwise from
+        `block_arrow_solve` -- the route for large G, where no dense factor exists; with on_device=True from the device-resident
+        solve (`solve`), so that no N- or G-sized host arithmetic lies between the fit and the streamed rows.  Per unit weight: a
+        row of weight zero gets the influence of adding it."""
         A, pt = self._influence_operand(x, moment_jac, is_free, chol, on_device)
-        return self.ctx.glmm_slopes_obs_influence(*pt, A, n0=n0, n1=n1)
+        return self._obs_influence(*pt, A, n0=n0, n1=n1)
 
     def group_influence(self, x, moment_jac, is_free=True, chol=None, on_device=False):
         """G x Q: row g is the derivative of the moments with respect to a common multiplier on the weights of group g's rows,
         sum_{n in g} w_n * (row n of `obs_influence`) -- minus it is the linear prediction of leaving the cluster out.  The
         group's own prior terms on u_g stay in the model and are not part of it.  Fixed summation order on the device
-        (`lrvb_glmm_slopes_group_influence`); an empty group gives a zero row.  on_device: as `obs_influence`."""
+        (lrvb_glmm_slopes_group_influence, lrvb_glmm_group_influence); an empty group gives a zero row.  on_device: as
+        `obs_influence`."""
         A, pt = self._influence_operand(x, moment_jac, is_free, chol, on_device)
-        return self.ctx.glmm_slopes_group_influence(*pt, A)
+        return self._group_influence(*pt, A)
 
     # ---- hyper-parameters ---------------------------------------------------------------------------------------------
     def _prior_hyper(self, kind, eta_g, want):
@@ -750,7 +579,8 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
         eta = self._eta(val1, val1_is_free)
         P, K, G, ng, N = self.P, self.K, self.G, self.n_global, self.n_obs
         GK = G * K
-        x, z, gid = self._x, self._z, self._groups
+        x, gid = self._x, self._groups
+        z = np.ones((N, 1)) if self._z is None else self._z
         _, ib, _, _, _, _, e, ig = _split_eta(eta, P, K, G)
         v, r = 1.0 / ib, 1.0 / ig
         rho = x @ eta[:P] + np.sum(z * e[gid], axis=1)
@@ -778,3 +608,70 @@ class LogisticGLMMSlopesObjective(DeclaredHypers):
         self.global_hessian(free_val, want_host=False)
         gc.chol_factor_last()
         return -gc.chol_solve(Cg)
+
+
+class LogisticGLMMSlopesObjective(_LogisticMixedModel):
+    def __init__(self, par, x, y, z, groups, n_groups, beta_prior_info=1.0, mu_prior=(0.0, 1.0), tau_prior=(1.0, 1.0), gh_deg=20,
+                 names=('beta', 'mu', 'tau', 'u'), weights=None, device=0):
+        """names: the parameters of q(beta), q(mu), q(tau_k) -- named names[2] + str(k), k = 0..K-1 -- and q(u)."""
+        if z is None:
+            raise ValueError('z must be N x K with 1 <= K <= 4')
+        super().__init__(par, x, y, z, groups, n_groups, beta_prior_info, mu_prior, tau_prior, gh_deg, names, weights, device)
+
+    def _layout(self, par, names):
+        P, K, G = self.P, self.K, self.G
+        ng, GK = 2 * P + 4 * K, G * K
+        want = [(names[0], 'mean', 0, P), (names[0], 'info', P, 2 * P), (names[1], 'mean', 2 * P, 2 * P + K),
+                (names[1], 'info', 2 * P + K, 2 * P + 2 * K)]
+        for k in range(K):
+            o = 2 * P + 2 * K + 2 * k
+            want += [(names[2] + str(k), 'shape', o, o + 1), (names[2] + str(k), 'rate', o + 1, o + 2)]
+        want += [(names[3], 'mean', ng, ng + GK), (names[3], 'info', ng + GK, ng + 2 * GK)]
+        msg = ('the parameter must be [UVNParamVector {} ({}) | UVNParamVector {} ({}) | GammaParam {}0 .. {}{} | UVNParamArray {} ({}, {})] '
+               'in this order, the group effects pushed last'.format(names[0], P, names[1], K, names[2], names[2], K - 1, names[3], G, K))
+        if any(name not in par.vector_indices_dict for name, _, _, _ in want):
+            raise ValueError(msg)
+        return want, msg, 'the parameter holds more than the blocks of the model'
+
+    # ---- the device entries -------------------------------------------------------------------------------------------------
+    def _terms(self, *point, **want):
+        return self.ctx.glmm_slopes_terms(*point, **want)
+
+    def _schur(self, local_blocks, border_scale, closed_rows):
+        return self.ctx.glmm_slopes_schur(local_blocks, border_scale, closed_rows)
+
+    def _obs_influence(self, *point_and_operand, **window):
+        return self.ctx.glmm_slopes_obs_influence(*point_and_operand, **window)
+
+    def _group_influence(self, *point_and_operand):
+        return self.ctx.glmm_slopes_group_influence(*point_and_operand)
+
+    # ---- the block-arrow solve resident on the device ------------------------------------------------------------------------
+    def _device_factors(self, x, is_free):
+        """on_device=True: the Schur factor on the global context and the local factor (L_g, U_g) on `ctx` at the free point x,
+        built here (`global_hessian(x, want_host=False)`, `chol_factor_last()`: the border never reaches the host) unless both
+        are those of this point, weights and hyper-parameters.  Returns the scaling s of the coupled rows: the border in free
+        coordinates is Hx[r, l] = s_r C_g[l, r] for the device's C_g."""
+        if not is_free:
+            raise ValueError('on_device=True solves in free coordinates')
+        if self._external is not None:
+            raise ValueError('on_device=True uses the group sums resident on this device, not installed statistics')
+        fv = _hip.as_f64(x).ravel()
+        self._push_state()
+        key = self._resident_key(fv)
+        if getattr(self, '_schur_key', None) != key or self._dev_factor_key != key:
+            self.global_hessian(fv, want_host=False)
+            self._ensure_gctx().chol_factor_last()
+            self._dev_factor_key = key
+        eta = self._eta(fv, True)
+        dv = np.concatenate([np.ones(self.P), -1.0 / eta[self.P:2 * self.P] ** 2, np.ones(3 * self.K)])
+        return self._jac(eta)[0][coupled_rows(self.P, self.K)] * dv
+
+    def _solve_on_device(self, x, R, is_free):
+        s = self._device_factors(x, is_free)
+        D = self.n_global + 2 * self.G * self.K
+        if np.shape(R)[0] != D:
+            raise ValueError('R must have {} rows'.format(D))
+        return block_arrow_solve_by_phases(R, self.n_global, coupled_rows(self.P, self.K), s, self.ctx.glmm_slopes_solve_forward,
+                                           self._ensure_gctx().chol_solve,
+                                           lambda xc: self.ctx.glmm_slopes_solve_back(xc, self.G, self.K))

@@ -418,24 +418,27 @@ class DeviceContext(object):
         return X
 
     def _glmm_influence_args(self, mean, var, e, r, gh_x, gh_w, A):
-        """The point and the operand A (Q x (2 P + 2 G), columns [A_m | A_v | A_e | A_r]) in the layout of the C entries:
-        A_global (Q x 2 P) and A_local (G x 2 Q, row g = [A_e[:, g] | A_r[:, g]])."""
+        """The point (e, r: G x K) and the operand A (Q x (2 P + 2 G K), columns [A_m | A_v | A_e (G K, group-major) | A_r (G K)])
+        in the layout of the C entries: A_global (Q x 2 P) and A_local (G x 2 K x Q), by `glmm_slopes.split_influence_operand`.
+        The entries of the intercept model pass e and r as G x 1: their A_local (G x 2 Q, row g = [A_e[:, g] | A_r[:, g]]) is
+        the same memory."""
+        from .glmm_slopes import split_influence_operand
         m, v = _hip.as_f64(mean).ravel(), _hip.as_f64(var).ravel()
-        e, r = _hip.as_f64(e).ravel(), _hip.as_f64(r).ravel()
+        e, r = _hip.as_f64(e), _hip.as_f64(r)
         gx, gw = _hip.as_f64(gh_x).ravel(), _hip.as_f64(gh_w).ravel()
-        P, G = self.n_cols, e.size
-        if m.size != P or v.size != P or r.size != G or gx.size != gw.size:
-            raise ValueError('expected mean and var of length {}, e and r of one length and as many weights as nodes'.format(P))
-        A = np.atleast_2d(_hip.as_f64(A))
-        if A.ndim != 2 or A.shape[0] < 1 or A.shape[1] != 2 * P + 2 * G:
-            raise ValueError('A must have {} columns [A_m | A_v | A_e | A_r]'.format(2 * P + 2 * G))
-        Ag = np.ascontiguousarray(A[:, :2 * P])
-        Al = np.ascontiguousarray(np.hstack([A[:, 2 * P:2 * P + G].T, A[:, 2 * P + G:].T]))
-        return (m, v, e, r, gx, gw, Ag, Al), A.shape[0]
+        P = self.n_cols
+        if e.ndim != 2 or r.shape != e.shape or m.size != P or v.size != P or gx.size != gw.size:
+            raise ValueError('expected mean and var of length {}, e and r of one shape G x K and as many weights as nodes'.format(P))
+        G, K = e.shape
+        Ag, Al = split_influence_operand(A, P, K, G)                     # a wrong width is its ValueError
+        if Ag.shape[0] < 1:
+            raise ValueError('A must have at least one row')
+        return (m, v, e, r, gx, gw, Ag, Al), Ag.shape[0]
 
     def glmm_obs_influence(self, mean, var, e, r, gh_x, gh_w, A, n0=0, n1=None):
         """(n1 - n0) x Q rows, row n = A times column n of the weight cross Hessian of the logistic mixed model in the coordinates
         (mean, var, e, r), per unit weight (lrvb_glmm_obs_influence).  A: Q x (2 P + 2 G), columns [A_m | A_v | A_e | A_r]."""
+        e, r = _hip.as_f64(e).reshape(-1, 1), _hip.as_f64(r).reshape(-1, 1)        # G x 1: one effect per group
         (m, v, e, r, gx, gw, Ag, Al), Q = self._glmm_influence_args(mean, var, e, r, gh_x, gh_w, A)
         n0 = int(n0)
         n1 = self.n_obs if n1 is None else int(n1)
@@ -448,31 +451,18 @@ class DeviceContext(object):
         """G x Q: row g = sum over the rows of group g of w_n times the row of `glmm_obs_influence` (lrvb_glmm_group_influence):
         the derivative with respect to a common multiplier on the weights of the group's rows.  The group's own prior term on
         u_g is not part of it."""
+        e, r = _hip.as_f64(e).reshape(-1, 1), _hip.as_f64(r).reshape(-1, 1)        # G x 1: one effect per group
         (m, v, e, r, gx, gw, Ag, Al), Q = self._glmm_influence_args(mean, var, e, r, gh_x, gh_w, A)
         out = np.empty((e.size, Q))
         self._check(self._lib.lrvb_glmm_group_influence(self._h, _hip.ptr(m), _hip.ptr(v), self.n_cols, _hip.ptr(e), _hip.ptr(r), e.size,
                                                        _hip.ptr(gx), _hip.ptr(gw), gx.size, _hip.ptr(Ag), _hip.ptr(Al), Q, _hip.ptr(out)))
         return out
 
-    def _glmm_slopes_influence_args(self, mean, var, e, r, gh_x, gh_w, A):
-        """The point (e, r: G x K) and the operand A (Q x (2 P + 2 G K), columns [A_m | A_v | A_e (G K, group-major) | A_r (G K)])
-        in the layout of the C entries: A_global (Q x 2 P) and A_local (G x 2 K x Q), by `glmm_slopes.split_influence_operand`."""
-        from .glmm_slopes import split_influence_operand
-        m, v = _hip.as_f64(mean).ravel(), _hip.as_f64(var).ravel()
-        e, r = _hip.as_f64(e), _hip.as_f64(r)
-        gx, gw = _hip.as_f64(gh_x).ravel(), _hip.as_f64(gh_w).ravel()
-        P = self.n_cols
-        if e.ndim != 2 or r.shape != e.shape or m.size != P or v.size != P or gx.size != gw.size:
-            raise ValueError('expected mean and var of length {}, e and r of one shape G x K and as many weights as nodes'.format(P))
-        G, K = e.shape
-        Ag, Al = split_influence_operand(A, P, K, G)                     # a wrong width is its ValueError
-        return (m, v, e, r, gx, gw, Ag, Al), Ag.shape[0]
-
     def glmm_slopes_obs_influence(self, mean, var, e, r, gh_x, gh_w, A, n0=0, n1=None):
         """(n1 - n0) x Q rows, row n = A times column n of the weight cross Hessian of the logistic mixed model with K effects per
         group in the coordinates (mean, var, e, r), per unit weight (lrvb_glmm_slopes_obs_influence).  A: Q x (2 P + 2 G K),
         columns [A_m | A_v | A_e | A_r], the local parts group-major as e and r."""
-        (m, v, e, r, gx, gw, Ag, Al), Q = self._glmm_slopes_influence_args(mean, var, e, r, gh_x, gh_w, A)
+        (m, v, e, r, gx, gw, Ag, Al), Q = self._glmm_influence_args(mean, var, e, r, gh_x, gh_w, A)
         n0 = int(n0)
         n1 = self.n_obs if n1 is None else int(n1)
         out = np.empty((max(n1 - n0, 0), Q))
@@ -485,7 +475,7 @@ class DeviceContext(object):
         """G x Q: row g = sum over the rows of group g of w_n times the row of `glmm_slopes_obs_influence`
         (lrvb_glmm_slopes_group_influence): the derivative with respect to a common multiplier on the weights of the group's rows.
         The group's own prior terms on u_g are not part of it."""
-        (m, v, e, r, gx, gw, Ag, Al), Q = self._glmm_slopes_influence_args(mean, var, e, r, gh_x, gh_w, A)
+        (m, v, e, r, gx, gw, Ag, Al), Q = self._glmm_influence_args(mean, var, e, r, gh_x, gh_w, A)
         out = np.empty((e.shape[0], Q))
         self._check(self._lib.lrvb_glmm_slopes_group_influence(self._h, _hip.ptr(m), _hip.ptr(v), self.n_cols, _hip.ptr(e), _hip.ptr(r),
                                                               e.shape[0], e.shape[1], _hip.ptr(gx), _hip.ptr(gw), gx.size, _hip.ptr(Ag),

@@ -265,6 +265,14 @@ int lrvb_obs_influence(lrvb_ctx* ctx, const double* free_in, int64_t D, const do
                        int64_t n0, int64_t n1, double* out);
 int lrvb_obs_influence_vec(lrvb_ctx* ctx, const double* vec_in, int64_t V, const double* M, int64_t Q,
                            int64_t n0, int64_t n1, double* out);
+/* The row product inside lrvb_obs_influence and lrvb_obs_loss on its own:
+ *   out[n - n0, q] = rowscale[n] * x_n . Zt[q]                  ((n1 - n0) x Q, row-major)
+ * for the rows n0 <= n < n1 of the observation matrix; Zt is Q x n_cols row-major, rowscale has n_obs entries
+ * (NULL = ones).  Where the fused multi-vector pass applies (even n_cols <= 1024, 16-byte aligned rows) the rows stream
+ * through it 16 columns of the result at a time; otherwise, or with tuning bit 0 set, a GEMM and a row scaling.
+ * Row range and data checks as lrvb_obs_loss.                                                */
+int lrvb_rows_times_matrix(lrvb_ctx* ctx, const double* Zt, int64_t Q, const double* rowscale /*nullable*/,
+                           int64_t n0, int64_t n1, double* out);
 /* D x V cross Hessian w.r.t. the linear tilt b of the quadratic term
  * (the `hyper_param @ theta` term of LRVB/test_model_sensitivity.py:56-66).                 */
 int lrvb_cross_hessian_tilt(lrvb_ctx* ctx, const double* free_in, int64_t D, double* C_out);
@@ -679,6 +687,11 @@ int lrvb_cg_solve(lrvb_ctx* ctx, const double* free_in, const double* b, const d
 int lrvb_cg_solve_multi(lrvb_ctx* ctx, const double* free_in, const double* B, const double* X0 /*nullable*/,
                         const double* Minv /*nullable D x D*/, double tol, int64_t maxiter, int64_t D, int64_t Q,
                         double* X_out, int* info_out, int64_t* iters_out);
+/* The block product of lrvb_cg_solve_multi on its own: row q of out (Q x D) = H(theta) Vb[q], computed exactly as the
+ * warm-start product of that solver (the fused multi-vector pass 16 rows at a time; the two-GEMM route with tuning bit 0,
+ * four waves per workgroup with bit 2; the resident Hessian of this point when there is one and bit 3 is clear).  Any
+ * Q >= 1.  Keeps and reuses the point state like the solvers.                                 */
+int lrvb_hvp_multi(lrvb_ctx* ctx, const double* free_in, int64_t D, const double* Vb, int64_t Q, double* out);
 
 /* The same conjugate-gradient loop on a dense symmetric D x D matrix kept on the device (Hessians
  * assembled from sufficient statistics).  H == NULL reuses the matrix of the previous call.   */

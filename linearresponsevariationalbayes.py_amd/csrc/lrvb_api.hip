@@ -2252,6 +2252,48 @@ extern "C" int lrvb_lrvb_cov(lrvb_ctx* c, const double* M, int64_t Q, int64_t D,
 }
 
 // ---- weight sensitivity of moments, streamed over the observations ------------
+// c->work1 ((n1 - n0) x Q) = diag(c->zbuf[n0 .. n1)) X[n0 .. n1) Zt^T, Zt (Q x P) on the device: the fused multi-vector
+// pass in its row form, 16 columns of the result per launch.  c->zbuf holds the row scale with its zero padding.
+static int rows_times_matrix_streamed(lrvb_ctx* c, i64 n0, i64 n1, i64 Q, const double* Zt_dev) {
+    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(n1 - n0) * (size_t)Q));
+    for (i64 q0 = 0; q0 < Q; q0 += 16) {
+        const i64 qn = (Q - q0 < 16) ? Q - q0 : 16;
+        LRVB_TRY(launch_rows_times_matrix(c, n0, n1, qn, Zt_dev + q0 * c->P, c->P, c->zbuf.p, c->work1.p + q0, Q));
+    }
+    return LRVB_OK;
+}
+// out[n - n0][q] = rowscale[n] x_n . Zt[q]: the row form of the fused multi-vector pass on its own (the product inside
+// lrvb_obs_influence and lrvb_obs_loss); the generic GEMM and a row scaling where that kernel does not apply.
+extern "C" int lrvb_rows_times_matrix(lrvb_ctx* c, const double* Zt, int64_t Q, const double* rowscale, int64_t n0, int64_t n1,
+                                      double* out) {
+    LRVB_TRY(ctx_bind(c));
+    if (!Zt || !out || Q <= 0) LRVB_FAIL(LRVB_ERR_INVALID, "bad argument");
+    if (c->loss == LRVB_LOSS_NONE || c->data_only) LRVB_FAIL(LRVB_ERR_STATE, "model has no declared data term");
+    if (n0 < 0 || n1 > c->N || n0 > n1) LRVB_FAIL(LRVB_ERR_INVALID, "row range [%lld, %lld) outside [0, %lld)", (long long)n0, (long long)n1, (long long)c->N);
+    LRVB_TRY(data_ready(c));
+    const i64 rows = n1 - n0, P = c->P;
+    if (rows == 0) return LRVB_OK;
+    LRVB_TRY(buf_reserve(c, c->vtmp3, (size_t)Q * (size_t)P));
+    LRVB_TRY(h2d(c, c->vtmp3.p, Zt, (size_t)Q * (size_t)P));
+    LRVB_TRY(reserve_obs_vec(c, c->zbuf));                                       // the row scale with zero padding past N
+    if (rowscale) { LRVB_TRY(h2d(c, c->zbuf.p, rowscale, (size_t)c->N)); }
+    else { EW(fill_kernel, c->N, 1.0, c->zbuf.p); }
+    if (hvp_multi_supported(c, 1) && !c->force_generic_wsyrk) {
+        LRVB_TRY(rows_times_matrix_streamed(c, n0, n1, Q, c->vtmp3.p));
+        return d2h(c, out, c->work1.p, (size_t)rows * (size_t)Q);
+    }
+    const i64 chunk = 65536;
+    for (i64 a = n0; a < n1; a += chunk) {
+        const i64 b = (a + chunk < n1) ? a + chunk : n1;
+        const i64 r = b - a;
+        LRVB_TRY(buf_reserve(c, c->work1, (size_t)r * (size_t)Q));
+        LRVB_TRY(launch_gemm(c, false, true, r, Q, P, 1.0, c->X.p + a * P, P, c->vtmp3.p, P, 0.0, c->work1.p, Q));
+        EW(row_scale_rows_kernel, r * Q, Q, c->zbuf.p + a, 1.0, c->work1.p);
+        LRVB_TRY(d2h(c, out + (a - n0) * Q, c->work1.p, (size_t)r * (size_t)Q));
+    }
+    return LRVB_OK;
+}
+
 static int obs_influence_impl(lrvb_ctx* c, const double* point, i64 n_in, bool is_free, const double* M, i64 Q,
                               i64 n0, i64 n1, double* out) {
     LRVB_TRY(ctx_bind(c));
@@ -2294,11 +2336,7 @@ static int obs_influence_impl(lrvb_ctx* c, const double* point, i64 n_in, bool i
             hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, c->stream, c->P, Q, c->Heta.p, c->vtmp3.p);
             HIP_TRY(hipGetLastError());
         }
-        LRVB_TRY(buf_reserve(c, c->work1, (size_t)rows * (size_t)Q));
-        for (i64 q0 = 0; q0 < Q; q0 += 16) {
-            const i64 qn = (Q - q0 < 16) ? Q - q0 : 16;
-            LRVB_TRY(launch_rows_times_matrix(c, n0, n1, qn, c->vtmp3.p + q0 * c->P, c->P, c->zbuf.p, c->work1.p + q0, Q));
-        }
+        LRVB_TRY(rows_times_matrix_streamed(c, n0, n1, Q, c->vtmp3.p));
         return d2h(c, out, c->work1.p, (size_t)rows * (size_t)Q);
     }
     const i64 chunk = 65536;
@@ -3490,6 +3528,33 @@ extern "C" int lrvb_cg_solve_multi(lrvb_ctx* c, const double* free_in, const dou
     }
     LRVB_TRY(d2h(c, X_out, Xd, qd));
     for (i64 q = 0; q < Q; ++q) { if (info_out) info_out[q] = info[q]; if (iters_out) iters_out[q] = iters[q]; }
+    if (!resident) remember_point(c, at);
+    return LRVB_OK;
+}
+
+// Row q of out = H(theta) Vb[q]: the block product of lrvb_cg_solve_multi (its warm start) on its own.
+extern "C" int lrvb_hvp_multi(lrvb_ctx* c, const double* free_in, int64_t D, const double* Vb, int64_t Q, double* out) {
+    AtPoint at;
+    LRVB_TRY(bind_point(c, free_in, D, true, &at));
+    if (!free_in || !Vb || !out || Q <= 0) LRVB_FAIL(LRVB_ERR_INVALID, "bad argument");
+    const i64 V = c->V, Qp = Q + (Q & 1);
+    const size_t qd = (size_t)Q * (size_t)D, qv = (size_t)Q * (size_t)V;
+    LRVB_TRY(buf_reserve(c, c->cgm[1], qd));
+    LRVB_TRY(buf_reserve(c, c->cgm[4], qd));
+    LRVB_TRY(buf_reserve(c, c->cgm[6], qv));
+    LRVB_TRY(buf_reserve(c, c->cgm[7], qv));
+    LRVB_TRY(buf_reserve(c, c->cgm[8], (size_t)((c->P > 0 ? c->P : 1) * Qp)));
+    bool resident = false;
+    LRVB_TRY(hres_matches(c, free_in, D, &resident));
+    if (c->loss != LRVB_LOSS_NONE && !resident) {
+        LRVB_TRY(buf_reserve(c, c->cgT, (size_t)(c->N * Qp)));
+        HIP_TRY(hipMemsetAsync(c->cgT.p, 0, (size_t)(c->N * Qp) * sizeof(double), c->stream));     // keeps the padding column zero
+    }
+    double *Xd = c->cgm[1].p, *Qd = c->cgm[4].p;
+    LRVB_TRY(h2d(c, Xd, Vb, qd));
+    if (!resident) LRVB_TRY(enter_point(c, at, true));
+    LRVB_TRY(resident ? launch_symm_block(c, Q, D, Xd, c->hres.H.p, Qd) : hvp_apply_multi(c, Q, Xd, Qd));
+    LRVB_TRY(d2h(c, out, Qd, qd));
     if (!resident) remember_point(c, at);
     return LRVB_OK;
 }

@@ -918,6 +918,30 @@ class DeviceContext(object):
                                                  info.ctypes.data_as(ctypes.c_void_p), iters.ctypes.data_as(ctypes.c_void_p)))
         return X, info, iters
 
+    def hvp_multi(self, free, V):
+        """Rows of V are vectors; returns H(free) V[q] row by row (Q x D): the block product of `cg_solve_multi`."""
+        f, V = _hip.as_f64(free).ravel(), _hip.as_f64(V)
+        if V.ndim != 2 or V.shape[1] != self.D:
+            raise ValueError('Wrong size for the vectors.  Expected (Q, {}), got {}'.format(self.D, V.shape))
+        out = np.empty((V.shape[0], self.D))
+        self._check(self._lib.lrvb_hvp_multi(self._h, _hip.ptr(f), f.size, _hip.ptr(V), V.shape[0], _hip.ptr(out)))
+        return out
+
+    def rows_times_matrix(self, Zt, rowscale=None, n0=0, n1=None):
+        """out[n - n0, q] = rowscale[n] x_n . Zt[q] for the observations n0..n1 ((n1 - n0) x Q); rowscale None = ones."""
+        Zt = _hip.as_f64(Zt)
+        if Zt.ndim != 2 or Zt.shape[1] != self.n_cols:
+            raise ValueError('Zt must have {} columns'.format(self.n_cols))
+        if rowscale is not None:
+            rowscale = _hip.as_f64(rowscale).ravel()
+            if rowscale.size != self.n_obs:
+                raise ValueError('rowscale must have {} entries'.format(self.n_obs))
+        n1 = self.n_obs if n1 is None else int(n1)
+        out = np.empty((max(n1 - int(n0), 0), Zt.shape[0]))
+        self._check(self._lib.lrvb_rows_times_matrix(self._h, _hip.ptr(Zt), Zt.shape[0], _hip.ptr(rowscale), int(n0), n1,
+                                                    _hip.ptr(out)))
+        return out
+
     # -- device-resident / multi-GPU -------------------------------------------------------
     def stats_size(self):
         n = ctypes.c_int64(0)

@@ -652,6 +652,21 @@ int lrvb_quadform_gram(lrvb_ctx* ctx, const double* M, const double* c, int64_t 
  * cvec (V) the constants c_k of the per-observation gradient, as for lrvb_quadform_gram.                                  */
 int lrvb_wishart_gram(lrvb_ctx* ctx, int64_t d, const int64_t* offsets, double nu, const double* m, const double* v,
                       const double* cvec, const double* free_in, double* GtG_out, int64_t ld);
+/* The Kronecker SYRK behind both on its own: K4 = sum_n c_n u_n u_n^T (Pv x Pv, Pv = n_cols (n_cols + 1) / 2, leading dimension
+ * ld >= Pv, both triangles), u_n the packed lower triangle of z_n z_n^T (column a (a + 1) / 2 + b <-> z_na z_nb, b <= a), z the
+ * context's data matrix.  cvec: n_obs weights, NULL = ones.  Rank-local (no sum over ranks); n_cols <= 64.  The split of the
+ * observation axis is the kernel's own (lrvb_set_tuning does not reach it).                                                  */
+int lrvb_kron_gram(lrvb_ctx* ctx, const double* cvec /*n_obs entries, NULL = ones*/, double* K4_out, int64_t ld);
+/* C = A^T diag(c) B over N rows from host operands (row-major; cvec NULL = ones), on the two-operand matrix-core kernel the
+ * models use, whatever the shape (no dispatch to the small-product kernels).  The context only lends its stream and scratch.
+ *   mode 0  A (N x PA), B (N x PB), PA and PB even; C is PA x PB.
+ *   mode 1  the same with 16 zero rows kept behind both operands on the device: at PA = PB = 528 the 16-column slivers ride on
+ *           the 16 interior workgroups and the edge entries are sums of four k-quarters.
+ *   mode 2  A is the N x 31 matrix x (PA = 31), B is N x 528: C (528 x 528) = sum_n c_n tri([1, x_n][1, x_n]^T) B[n, :], the
+ *           left operand (the packed lower triangle, column a (a + 1) / 2 + b) generated on chip.
+ * Odd widths, a mode-2 shape other than (31, 528) and N < 1 are errors (LRVB_ERR_UNSUPPORTED / LRVB_ERR_SIZE).              */
+int lrvb_weighted_atb(lrvb_ctx* ctx, const double* A, int64_t PA, const double* B, int64_t PB, int64_t N,
+                      const double* cvec /*nullable*/, int32_t mode, double* C_out);
 
 /* ---- linear-response solve ------------------------------------------------------------ */
 /* scipy.linalg.cho_factor at LRVB/ModelSensitivity.py:594 / SparseObjectives.py:539.

@@ -131,6 +131,8 @@ _SIGNATURES = {
     'lrvb_lmm_global_hessian': [_VP, _VP, _VP, c_i64, _VP, c_i64, _VP, ctypes.c_double, _VP, _VP],
     'lrvb_quadform_gram': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64],
     'lrvb_wishart_gram': [_VP, c_i64, _VP, ctypes.c_double, _VP, _VP, _VP, _VP, _VP, c_i64],
+    'lrvb_kron_gram': [_VP, _VP, _VP, c_i64],
+    'lrvb_weighted_atb': [_VP, _VP, c_i64, _VP, c_i64, c_i64, _VP, ctypes.c_int32, _VP],
     'lrvb_cg_solve_matrix': [_VP, _VP, _VP, _VP, _VP, ctypes.c_double, c_i64, c_i64, _VP,
                              ctypes.POINTER(ctypes.c_int), ctypes.POINTER(c_i64)],
     'lrvb_chol_factor': [_VP, _VP, c_i64],

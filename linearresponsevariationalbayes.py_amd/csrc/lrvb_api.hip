@@ -1973,6 +1973,12 @@ static int gemm_tn(lrvb_ctx* c, i64 K, i64 PA, i64 PB, const double* A, const do
 
 static int quadform_gram_impl(lrvb_ctx* c, const double* M, const WishartGen* gen, const double* cvec, int64_t K,
                               const double* free_in, double* GtG_out, int64_t ld);
+// what every caller of the Kronecker SYRK on the context's data matrix checks first
+static int kron_ready(lrvb_ctx* c) {
+    if (c->loss == LRVB_LOSS_NONE || !c->have_X) LRVB_FAIL(LRVB_ERR_STATE, "no data matrix: call lrvb_set_data(LRVB_SLOT_X) first");
+    if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "Kronecker Gram kernel supports n_cols <= 64 (got %lld)", (long long)c->P);
+    return LRVB_OK;
+}
 extern "C" int lrvb_quadform_gram(lrvb_ctx* c, const double* M, const double* cvec, int64_t K,
                                   const double* free_in, double* GtG_out, int64_t ld) {
     LRVB_TRY(ctx_bind(c));
@@ -2004,9 +2010,8 @@ extern "C" int lrvb_wishart_gram(lrvb_ctx* c, int64_t d, const int64_t* offsets,
 }
 static int quadform_gram_impl(lrvb_ctx* c, const double* M, const WishartGen* gen, const double* cvec, int64_t K,
                               const double* free_in, double* GtG_out, int64_t ld) {
-    if (c->loss == LRVB_LOSS_NONE || !c->have_X) LRVB_FAIL(LRVB_ERR_STATE, "no data matrix: call lrvb_set_data(LRVB_SLOT_X) first");
+    LRVB_TRY(kron_ready(c));
     if (K != c->V) LRVB_FAIL(LRVB_ERR_SIZE, "expected one matrix per vector coordinate (%lld), got %lld", (long long)c->V, (long long)K);
-    if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "Kronecker Gram kernel supports n_cols <= 64");
     if (ld < c->D) LRVB_FAIL(LRVB_ERR_SIZE, "leading dimension too small");
     const int q = (int)c->P;
     const i64 V = c->V, D = c->D, Pv = (i64)q * (q + 1) / 2;      // packed lower triangle of z z^T
@@ -2102,6 +2107,57 @@ static int quadform_gram_impl(lrvb_ctx* c, const double* M, const WishartGen* ge
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return LRVB_OK;
+}
+
+// K4 = sum_n c_n u_n u_n^T on its own (the Kronecker SYRK and the tile unpacking, nothing behind them): dense, both triangles
+extern "C" int lrvb_kron_gram(lrvb_ctx* c, const double* cvec, double* K4_out, int64_t ld) {
+    LRVB_TRY(ctx_bind(c));
+    if (!K4_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    LRVB_TRY(kron_ready(c));
+    const i64 q = c->P, Pv = q * (q + 1) / 2;
+    if (ld < Pv) LRVB_FAIL(LRVB_ERR_SIZE, "leading dimension too small");
+    const i64 nbk = (Pv + WS_TILE - 1) / WS_TILE;
+    LRVB_TRY(reserve_obs_vec(c, c->zbuf));
+    LRVB_TRY(buf_reserve(c, c->Tdense, (size_t)(nbk * (nbk + 1) / 2) * WS_TILE * WS_TILE));
+    LRVB_TRY(buf_reserve(c, c->Heta, (size_t)Pv * (size_t)Pv));
+    if (cvec) { LRVB_TRY(h2d(c, c->zbuf.p, cvec, (size_t)c->N)); }
+    else { EW(fill_kernel, c->N, 1.0, c->zbuf.p); }
+    LRVB_TRY(launch_wsyrk_kron(c, c->zbuf.p, c->Tdense.p));
+    LRVB_TRY(launch_tiles_to_dense(c, c->Tdense.p, Pv, c->Heta.p, Pv, 0, 0, false));
+    HIP_TRY(hipMemcpy2DAsync(K4_out, (size_t)ld * 8, c->Heta.p, (size_t)Pv * 8, (size_t)Pv * 8, (size_t)Pv, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return LRVB_OK;
+}
+
+// C = A^T diag(c) B from host operands: launch_atb / launch_atb_kron32 on copies in c->gpad, laid out as their callers lay
+// theirs out -- [A | B | weights | C], every piece at an even offset (16-byte aligned rows), 16 zero rows behind A and B in
+// the padded modes, 64 zeros behind the weights
+extern "C" int lrvb_weighted_atb(lrvb_ctx* c, const double* A, int64_t PA, const double* B, int64_t PB, int64_t N,
+                                 const double* cvec, int32_t mode, double* C_out) {
+    LRVB_TRY(ctx_bind(c));
+    if (!A || !B || !C_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    if (mode < 0 || mode > 2) LRVB_FAIL(LRVB_ERR_INVALID, "mode must be 0, 1 or 2 (got %d)", (int)mode);
+    if (N < 1 || PA < 1 || PB < 1) LRVB_FAIL(LRVB_ERR_SIZE, "empty operand");
+    const i64 W = 4 * WS_TILE + 16;
+    if (mode == 2) {
+        if (PA != 31 || PB != W) LRVB_FAIL(LRVB_ERR_SIZE, "mode 2: A must be N x 31 and B N x %lld (got %lld and %lld columns)", (long long)W, (long long)PA, (long long)PB);
+    } else if ((PA % 2) || (PB % 2)) {
+        LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "atb: operands must have even widths (got %lld and %lld)", (long long)PA, (long long)PB);
+    }
+    auto even = [](i64 n) { return n + (n & 1); };
+    const i64 padA = mode == 1 ? 16 : 0, padB = mode ? 16 : 0;
+    const i64 rowsC = mode == 2 ? W : PA;
+    const i64 nA = even((N + padA) * PA), nB = even((N + padB) * PB), nW = even(N + 64);
+    LRVB_TRY(buf_reserve(c, c->gpad, (size_t)(nA + nB + nW + rowsC * PB)));
+    double* Ad = c->gpad.p; double* Bd = Ad + nA; double* Wd = Bd + nB; double* Cd = Wd + nW;
+    HIP_TRY(hipMemsetAsync(Ad, 0, (size_t)(nA + nB + nW) * sizeof(double), c->stream));
+    LRVB_TRY(h2d(c, Ad, A, (size_t)(N * PA)));
+    LRVB_TRY(h2d(c, Bd, B, (size_t)(N * PB)));
+    if (cvec) { LRVB_TRY(h2d(c, Wd, cvec, (size_t)N)); }
+    else { EW(fill_kernel, N, 1.0, Wd); }
+    if (mode == 2) LRVB_TRY(launch_atb_kron32(c, Ad, Bd, N, Wd, Cd));
+    else LRVB_TRY(launch_atb(c, Ad, PA, Bd, PB, N, Wd, Cd, mode == 1));
+    return d2h(c, C_out, Cd, (size_t)(rowsC * PB));
 }
 
 // Preconditioned conjugate gradients driven from the host, the loop of lrvb_cg_solve and lrvb_cg_solve_matrix: b in c->rhs,

@@ -798,6 +798,35 @@ class DeviceContext(object):
                                                 _hip.ptr(out), self.D))
         return out
 
+    def kron_gram(self, c=None):
+        """K4 = sum_n c_n u_n u_n^T (Pv x Pv, Pv = n_cols (n_cols + 1) / 2), u_n the packed lower triangle of z_n z_n^T: the
+        Kronecker SYRK of `quadform_gram` on its own.  c None = ones."""
+        if c is not None:
+            c = _hip.as_f64(c).ravel()
+            if c.size != self.n_obs:
+                raise ValueError('c must have {} entries'.format(self.n_obs))
+        pv = self.n_cols * (self.n_cols + 1) // 2
+        out = np.empty((pv, pv))
+        self._check(self._lib.lrvb_kron_gram(self._h, _hip.ptr(c), _hip.ptr(out), pv))
+        return out
+
+    def weighted_atb(self, A, B, c=None, mode=0):
+        """C = A^T diag(c) B on the two-operand matrix-core kernel (`lrvb_weighted_atb`): mode 0 plain, mode 1 with 16 zero
+        rows behind the operands (the sliver kernel at 528 x 528), mode 2 with A = x (N x 31) and the left operand
+        tri([1, x][1, x]^T) generated on chip (C is 528 x 528).  c None = ones."""
+        A, B = _hip.as_f64(A), _hip.as_f64(B)
+        if A.ndim != 2 or B.ndim != 2 or A.shape[0] != B.shape[0]:
+            raise ValueError('A and B must be matrices with the same number of rows')
+        N = A.shape[0]
+        if c is not None:
+            c = _hip.as_f64(c).ravel()
+            if c.size != N:
+                raise ValueError('c must have {} entries'.format(N))
+        out = np.empty((528 if mode == 2 else A.shape[1], B.shape[1]))
+        self._check(self._lib.lrvb_weighted_atb(self._h, _hip.ptr(A), A.shape[1], _hip.ptr(B), B.shape[1], N, _hip.ptr(c),
+                                                int(mode), _hip.ptr(out)))
+        return out
+
     def wishart_gram(self, d, offsets, nu, m, v, c, free, want_host=True):
         """G^T G of the Wishart + MVN model with the per-coordinate matrices generated on the device (lrvb_wishart_gram);
         want_host=False leaves the result in HBM (for `chol_factor_last`) and returns None."""

@@ -511,6 +511,44 @@ int lrvb_glmm_slopes_group_influence(lrvb_ctx* ctx, const double* mean, const do
                                      const double* r, int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
                                      const double* A_global, const double* A_local, int64_t Q, double* out);
 
+/* ---- Poisson mixed model with K <= 4 independent random effects per group ---------------------------
+ *   y_n ~ Poisson(exp(o_n + x_n . beta + z_n . u_g(n))),  q(beta_j) = N(mean_j, var_j),  q(u_gk) = N(e_gk, r_gk).
+ * The per-row offset o (log exposure; n doubles) lives in one device buffer of its own.  offset == NULL clears it (the offset is
+ * then zero); it is replaced by the next call.  Only the three lrvb_glmm_poisson_* entries read it: no other entry looks at
+ * it.  The call drops the resident group sums and factor (they were formed under another offset).  A length other than n_obs
+ * is found when a Poisson entry runs: LRVB_ERR_STATE there.  n < 1 with a non-null offset: LRVB_ERR_SIZE.                   */
+int lrvb_set_offset(lrvb_ctx* ctx, const double* offset, int64_t n);
+/* Data term of that model at (mean, var (P each), e, r (G x K each, group-major)), the group design of lrvb_set_group_design:
+ *   rho_n = o_n + x_n . mean + z_n . e_g(n),  s_n = (x_n o x_n) . var + (z_n o z_n) . r_g(n),  psi_n = exp(rho_n + s_n / 2)
+ *   value = sum_n w_n [psi_n - y_n rho_n]          (E exp(t), t ~ N(rho, s), is exact: no quadrature; log y! is dropped)
+ * and, with h = w psi, the per-row coefficients a1 = h - w y, a2 = h / 2, c11 = h, c12 = h / 2, c22 = h / 4.  Outputs, the
+ * column layout of group_sums_out, want_border, the fixed summation order (two calls at one point are bitwise equal) and the
+ * reduce-hook contract (ONE buffer [H blocks, when asked for | group sums | gradient | value], one hook call) are those of
+ * lrvb_glmm_slopes_terms.  The group sums stay resident exactly as that entry leaves them: lrvb_glmm_slopes_schur,
+ * lrvb_glmm_slopes_solve_forward and lrvb_glmm_slopes_solve_back work on them unchanged.
+ * Errors as lrvb_glmm_slopes_terms without the node count (P > 64, K < 1 or K > 4: LRVB_ERR_UNSUPPORTED; groups, the group
+ * design, X or y not set, a group design that is not n_obs x K, or an offset whose length is not n_obs: LRVB_ERR_STATE;
+ * var_j <= 0 or r_gk <= 0: LRVB_ERR_INVALID; G is not the number of groups: LRVB_ERR_SIZE).  The kernel does not clamp: where
+ * exp(rho + s / 2) overflows, the value after the reduction is not finite and the call returns LRVB_ERR_INVALID; the other
+ * outputs are then unspecified and no sums stay resident.  y is not validated here (the Python layer asks for y >= 0).      */
+int lrvb_glmm_poisson_terms(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                            int64_t G, int64_t K, double* value_out, double* grad_global_out, double* H_blocks_out,
+                            double* group_sums_out, int32_t want_border);
+/* Streamed weight influence of the Poisson mixed model: lrvb_glmm_slopes_obs_influence with, per unit weight,
+ *   a1' = psi_n - y_n,   a2' = psi_n / 2
+ * from one exp per row.  Operand layouts, the row window [n0, n1), the output, "a window equals the same rows of the full
+ * result bitwise" and "no reduce-hook call" as there; errors as lrvb_glmm_poisson_terms, and n0 > n1 or n1 > n_obs:
+ * LRVB_ERR_INVALID.                                                                                                          */
+int lrvb_glmm_poisson_obs_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                                    int64_t G, int64_t K, const double* A_global, const double* A_local, int64_t Q, int64_t n0,
+                                    int64_t n1, double* out);
+/* Group influence of that model: out[g][q] = sum over the rows n of group g of w_n * (the row of lrvb_glmm_poisson_obs_influence)
+ * (G x Q, host), as lrvb_glmm_slopes_group_influence: a fixed-order sum of 2 K + 2 P columns per group, an exact zero row for
+ * an empty group, ONE reduce-hook call on the G x Q result.  Errors as lrvb_glmm_poisson_obs_influence.                       */
+int lrvb_glmm_poisson_group_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e,
+                                      const double* r, int64_t G, int64_t K, const double* A_global, const double* A_local,
+                                      int64_t Q, double* out);
+
 /* ---- multinomial (softmax) regression ---------------------------------------------------------
  * K classes (2 <= K <= 17), labels y_n in {0 .. K-1}, class 0 the reference; coefficients beta ((K-1) x P, row-major, row a
  * belongs to class a + 1, P = n_cols <= 1024), z_na = x_n . beta_a, z_n0 = 0, p_n = softmax(z_n).  The data term

@@ -49,6 +49,7 @@ from .logitnormal_mvn import LogitNormalMVNRegressionObjective
 from .softmax import SoftmaxRegressionObjective
 from .glmm import LogisticGLMMObjective
 from .glmm_slopes import LogisticGLMMSlopesObjective
+from .glmm_poisson import PoissonGLMMObjective
 from .torch_closure import TorchObjective
 from . import regression as regression_utils
 from . import packing as ProjectionParams

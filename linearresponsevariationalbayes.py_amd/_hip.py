@@ -95,6 +95,10 @@ _SIGNATURES = {
     'lrvb_glmm_group_influence': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, c_i64, _VP],
     'lrvb_glmm_slopes_obs_influence': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, c_i64, c_i64, c_i64, _VP],
     'lrvb_glmm_slopes_group_influence': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, c_i64, _VP],
+    'lrvb_set_offset': [_VP, _VP, c_i64],
+    'lrvb_glmm_poisson_terms': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, _VP, _VP, ctypes.c_int32],
+    'lrvb_glmm_poisson_obs_influence': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, c_i64, c_i64, c_i64, _VP],
+    'lrvb_glmm_poisson_group_influence': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, c_i64, _VP],
     'lrvb_softmax_set_labels': [_VP, _VP, c_i64, ctypes.c_int32],
     'lrvb_softmax_terms': [_VP, _VP, c_i64, c_i64, _VP, _VP, _VP, c_i64],
     'lrvb_softmax_hvp': [_VP, _VP, c_i64, c_i64, _VP, _VP],

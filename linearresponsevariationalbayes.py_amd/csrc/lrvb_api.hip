@@ -231,7 +231,7 @@ extern "C" int lrvb_ctx_destroy(lrvb_ctx* c) {
     DevBuf* all[] = { &c->X, &c->y, &c->w, &c->quadA, &c->quadM, &c->quadB, &c->theta, &c->eta, &c->j1, &c->j2,
                       &c->vtmp, &c->vtmp2, &c->vtmp3, &c->g_eta, &c->g_free, &c->lp, &c->cw, &c->zbuf,
                       &c->part_vec, &c->part_val, &c->stats, &c->tile_part, &c->Heta, &c->Hfree, &c->Jdense,
-                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn, &c->glmm, &c->gz, &c->glmms, &c->glmms_fac, &c->glmms_T,
+                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn, &c->glmm, &c->gz, &c->goff, &c->glmms, &c->glmms_fac, &c->glmms_T,
                       &c->sm.labels, &c->sm.p, &c->sm.wpad, &c->sm.work, &c->sm.col, &c->sm.tiles, &c->sm.rows };
     for (DevBuf* b : all) buf_free(*b);
     if (c->host_pinned) (void)hipHostFree(c->host_pinned);
@@ -2964,6 +2964,161 @@ extern "C" int lrvb_glmm_slopes_group_influence(lrvb_ctx* c, const double* mean,
     double* gsum = b.extra; double* part = gsum + G * ncol; double* od = part + n_tiles * 2 * ncol;
     HIP_TRY(hipMemsetAsync(gsum, 0, (size_t)(G * ncol) * sizeof(double), c->stream));       // empty groups keep the zeros
     LRVB_TRY(launch_glmm_slopes_infl_gsum(c, (int)K, c->gz.p, b.m, b.v, b.e, b.r, b.g, b.g + 128, (int)n_nodes, gsum, part));
+    LRVB_TRY(launch_gemm(c, false, true, G, Q, 2 * c->P, 1.0, gsum + 2 * K, ncol, b.Ag, 2 * c->P, 0.0, od, Q));
+    LRVB_TRY(launch_glmm_slopes_infl_local(c, (int)K, Q, gsum, b.Al, od));
+    LRVB_TRY(obs_reduce(c, od, G * Q));                       // a sum over observations; a group may straddle ranks
+    return d2h(c, out, od, (size_t)(G * Q));
+}
+
+// ---- Poisson mixed model with K <= 4 random effects per group (k_glmm_poisson.hip) -------------------------
+extern "C" int lrvb_set_offset(lrvb_ctx* c, const double* offset, int64_t n) {
+    LRVB_TRY(ctx_bind(c));
+    c->glmms_drop();                                                     // sums formed under another offset are not those of the model
+    c->goff_n = 0;
+    if (!offset) return LRVB_OK;
+    if (n < 1) LRVB_FAIL(LRVB_ERR_SIZE, "the offset needs at least one entry");
+    LRVB_TRY(buf_reserve(c, c->goff, (size_t)n));
+    HIP_TRY(hipMemcpyAsync(c->goff.p, offset, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->goff_n = n;
+    return LRVB_OK;
+}
+
+// The state checks the three Poisson entries share, in the order of lrvb_glmm_slopes_terms, then the offset.
+static int glmm_poisson_check(lrvb_ctx* c, const double* var, int64_t P_in, const double* r_loc, int64_t G_in, int64_t K) {
+    if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the Poisson mixed model needs P <= 64 (got %lld)", (long long)c->P);
+    if (K < 1 || K > 4) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 4 random effects per group (got %lld)", (long long)K);
+    if (c->loss == LRVB_LOSS_NONE || c->data_only || !(c->have_X && c->have_y))
+        LRVB_FAIL(LRVB_ERR_STATE, "the context needs a design matrix and responses: lrvb_set_data for LRVB_SLOT_X and LRVB_SLOT_Y");
+    if (c->n_groups <= 0) LRVB_FAIL(LRVB_ERR_STATE, "no groups: call lrvb_set_groups first");
+    if (c->gz_K <= 0) LRVB_FAIL(LRVB_ERR_STATE, "no group design: call lrvb_set_group_design first");
+    if (c->gz_n != c->N || c->gz_K != K)
+        LRVB_FAIL(LRVB_ERR_STATE, "the group design is %lld x %d, the model needs %lld x %lld", (long long)c->gz_n, c->gz_K, (long long)c->N, (long long)K);
+    if (c->goff_n != 0 && c->goff_n != c->N)
+        LRVB_FAIL(LRVB_ERR_STATE, "the offset has %lld entries, the model has %lld observations", (long long)c->goff_n, (long long)c->N);
+    LRVB_TRY(check_len(P_in, c->P, "mean / var"));
+    LRVB_TRY(check_len(G_in, c->n_groups, "groups of e / r"));
+    for (i64 j = 0; j < c->P; ++j) if (!(var[j] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "var[%lld] is not positive", (long long)j);
+    for (i64 g = 0; g < c->n_groups * K; ++g) if (!(r_loc[g] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "r[%lld] is not positive", (long long)g);
+    return LRVB_OK;
+}
+
+// c->glmms: [H blocks (3 P^2) | group sums (G x ncol) | gradient (2 P) | value], as lrvb_glmm_slopes_terms leaves them.  c->work1:
+// [m, v (2 up(P)) | e, r (2 up(G K)) | two coefficient vectors a1, h (2 NP, original order, zero past N) | tile partials]
+extern "C" int lrvb_glmm_poisson_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                       const double* r_loc, int64_t G_in, int64_t K, double* value_out, double* grad_global_out,
+                                       double* H_blocks_out, double* group_sums_out, int32_t want_border) {
+    LRVB_TRY(ctx_bind(c));
+    if (!mean || !var || !e_loc || !r_loc || !value_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    LRVB_TRY(glmm_poisson_check(c, var, P_in, r_loc, G_in, K));
+    const i64 N = c->N, P = c->P, G = c->n_groups, ncol = glmm_slopes_ncol((int)P, (int)K), nsc = ncol - 4 * K * P;
+    c->glmms_drop();
+    const bool want_g = grad_global_out != nullptr, want_H = H_blocks_out != nullptr;
+    DevBuf& X2 = c->mx_Xk;
+    if ((want_g || want_H) && (!c->x2_ready || X2.n < (size_t)(N * P))) {
+        LRVB_TRY(buf_reserve(c, X2, (size_t)(N * P)));
+        EW(square_kernel, N * P, (const double*)c->X.p, X2.p);
+        c->x2_ready = true;
+    }
+    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
+    const i64 NP = up(N + 64), n_tiles = glmm_num_tiles(N), GK = G * K;
+    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(2 * up(P) + 2 * up(GK) + 2 * NP + n_tiles * 2 * ncol + n_tiles)));
+    LRVB_TRY(buf_reserve(c, c->glmms, (size_t)(3 * P * P + G * ncol + 2 * P + 1)));
+    double* dm = c->work1.p; double* dv = dm + up(P); double* de = dv + up(P); double* dr = de + up(GK);
+    double* coef = dr + up(GK); double* part = coef + 2 * NP; double* vpart = part + n_tiles * 2 * ncol;
+    double* Hb = c->glmms.p; double* gsum = Hb + 3 * P * P; double* gred = gsum + G * ncol; double* vred = gred + 2 * P;
+    LRVB_TRY(h2d(c, dm, mean, (size_t)P));
+    LRVB_TRY(h2d(c, dv, var, (size_t)P));
+    LRVB_TRY(h2d(c, de, e_loc, (size_t)GK));
+    LRVB_TRY(h2d(c, dr, r_loc, (size_t)GK));
+    HIP_TRY(hipMemsetAsync(coef, 0, (size_t)(2 * NP) * sizeof(double), c->stream));
+    HIP_TRY(hipMemsetAsync(gsum, 0, (size_t)(G * ncol + 2 * P + 1) * sizeof(double), c->stream));
+    const double* off = c->goff_n ? c->goff.p : nullptr;
+    LRVB_TRY(launch_glmm_poisson_rows(c, (int)K, c->gz.p, off, dm, dv, de, dr, coef, NP, gsum, part, vpart));
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, c->stream, (const double*)vpart, n_tiles, vred);
+    HIP_TRY(hipGetLastError());
+    if (want_g) {                                                        // a1 = coef[0], a2 = h / 2 = coef[NP] / 2
+        LRVB_TRY(launch_gemv(c, true, N, P, 1.0, c->X.p, P, coef, 0.0, gred));
+        LRVB_TRY(launch_gemv(c, true, N, P, 0.5, X2.p, P, coef + NP, 0.0, gred + P));
+    }
+    if (want_H) {                                                        // c11 = h, c12 = h / 2, c22 = h / 4: one vector, scaled blocks
+        LRVB_TRY(weighted_tn(c, c->X.p, c->X.p, P, N, coef + NP, Hb, c->mx_A));
+        LRVB_TRY(weighted_tn(c, c->X.p, X2.p, P, N, coef + NP, Hb + P * P, c->mx_A));
+        LRVB_TRY(weighted_tn(c, X2.p, X2.p, P, N, coef + NP, Hb + 2 * P * P, c->mx_A));
+        LRVB_TRY(launch_glmm_poisson_scale_blocks(c, Hb));
+    }
+    double* first = want_H ? Hb : gsum;
+    LRVB_TRY(obs_reduce(c, first, (i64)(vred + 1 - first)));
+    LRVB_TRY(d2h(c, value_out, vred, 1));
+    if (!std::isfinite(*value_out))
+        LRVB_FAIL(LRVB_ERR_INVALID, "the Poisson data term is not finite at this point: exp(rho + s / 2) overflows for some row (the kernel does not clamp)");
+    c->glmms_valid = true; c->glmms_K = (int)K;
+    if (want_g) LRVB_TRY(d2h(c, grad_global_out, gred, (size_t)(2 * P)));
+    if (want_H) LRVB_TRY(d2h(c, H_blocks_out, Hb, (size_t)(3 * P * P)));
+    if (group_sums_out) {
+        if (want_border) LRVB_TRY(d2h(c, group_sums_out, gsum, (size_t)(G * ncol)));
+        else {                                                           // the scalar columns of every group; the border stays
+            HIP_TRY(hipMemcpy2DAsync(group_sums_out, (size_t)nsc * sizeof(double), gsum, (size_t)ncol * sizeof(double),
+                                     (size_t)nsc * sizeof(double), (size_t)G, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+    }
+    return LRVB_OK;
+}
+
+// ---- weight influence of the Poisson mixed model -------------------------------------------------------------------------------------
+// c->work1 holds [m, v (2 up(P)) | e, r (2 up(G K)) | A_global (Q x 2 P) | A_local (G x 2 K x Q) | call-specific scratch]
+static int glmm_poisson_infl_setup(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                   const double* r_loc, int64_t G_in, int64_t K, const double* A_global, const double* A_local,
+                                   int64_t Q, const void* out, size_t extra, GlmmInflBufs& b) {
+    if (!mean || !var || !e_loc || !r_loc || !A_global || !A_local || !out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    LRVB_TRY(glmm_poisson_check(c, var, P_in, r_loc, G_in, K));
+    if (Q < 1) LRVB_FAIL(LRVB_ERR_INVALID, "Q must be positive");
+    const i64 P = c->P, GK = c->n_groups * K;
+    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
+    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(2 * up(P) + 2 * up(GK) + up(Q * 2 * P) + up(GK * 2 * Q)) + extra));
+    b.g = nullptr; b.m = c->work1.p; b.v = b.m + up(P); b.e = b.v + up(P); b.r = b.e + up(GK);
+    b.Ag = b.r + up(GK); b.Al = b.Ag + up(Q * 2 * P); b.extra = b.Al + up(GK * 2 * Q);
+    LRVB_TRY(h2d(c, b.m, mean, (size_t)P));
+    LRVB_TRY(h2d(c, b.v, var, (size_t)P));
+    LRVB_TRY(h2d(c, b.e, e_loc, (size_t)GK));
+    LRVB_TRY(h2d(c, b.r, r_loc, (size_t)GK));
+    LRVB_TRY(h2d(c, b.Ag, A_global, (size_t)(Q * 2 * P)));
+    LRVB_TRY(h2d(c, b.Al, A_local, (size_t)(GK * 2 * Q)));
+    return LRVB_OK;
+}
+
+extern "C" int lrvb_glmm_poisson_obs_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                               const double* r_loc, int64_t G_in, int64_t K, const double* A_global,
+                                               const double* A_local, int64_t Q, int64_t n0, int64_t n1, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    GlmmInflBufs b;
+    LRVB_TRY(glmm_poisson_infl_setup(c, mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out, 0, b));
+    if (n0 < 0 || n1 > c->N || n0 > n1) LRVB_FAIL(LRVB_ERR_INVALID, "row range [%lld, %lld) outside [0, %lld)", (long long)n0, (long long)n1, (long long)c->N);
+    const i64 rows = n1 - n0;
+    if (rows == 0) return LRVB_OK;
+    LRVB_TRY(buf_reserve(c, c->cgT, (size_t)(rows * Q)));
+    const i64 NW = (c->N + grouped_rows_per_wave(c->N) - 1) / grouped_rows_per_wave(c->N);
+    const int* gid = reinterpret_cast<const int*>(reinterpret_cast<const i64*>(c->groups.p) + c->N + c->n_groups + 1 + NW);
+    const double* off = c->goff_n ? c->goff.p : nullptr;
+    LRVB_TRY(launch_glmm_poisson_infl_rows(c, (int)K, c->gz.p, off, n0, n1, gid, b.m, b.v, b.e, b.r, b.Ag, b.Al, Q, c->cgT.p));
+    return d2h(c, out, c->cgT.p, (size_t)(rows * Q));       // per-observation rows: rank-local, no hook call
+}
+
+extern "C" int lrvb_glmm_poisson_group_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                                 const double* r_loc, int64_t G_in, int64_t K, const double* A_global,
+                                                 const double* A_local, int64_t Q, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    GlmmInflBufs b;
+    const i64 Kc = K < 1 ? 1 : (K > 4 ? 4 : K);               // the setup refuses K outside 1..4 before the scratch is used
+    const i64 ncol = 2 * Kc + 2 * c->P, n_tiles = glmm_num_tiles(c->N), G = c->n_groups > 0 ? c->n_groups : 0;
+    // scratch: [group sums (G x (2 K + 2 P)) | tile partials | out (G x Q)]
+    const size_t extra = (size_t)(G * ncol + n_tiles * 2 * ncol + G * (Q > 0 ? Q : 0));
+    LRVB_TRY(glmm_poisson_infl_setup(c, mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out, extra, b));
+    double* gsum = b.extra; double* part = gsum + G * ncol; double* od = part + n_tiles * 2 * ncol;
+    HIP_TRY(hipMemsetAsync(gsum, 0, (size_t)(G * ncol) * sizeof(double), c->stream));       // empty groups keep the zeros
+    const double* off = c->goff_n ? c->goff.p : nullptr;
+    LRVB_TRY(launch_glmm_poisson_infl_gsum(c, (int)K, c->gz.p, off, b.m, b.v, b.e, b.r, gsum, part));
     LRVB_TRY(launch_gemm(c, false, true, G, Q, 2 * c->P, 1.0, gsum + 2 * K, ncol, b.Ag, 2 * c->P, 0.0, od, Q));
     LRVB_TRY(launch_glmm_slopes_infl_local(c, (int)K, Q, gsum, b.Al, od));
     LRVB_TRY(obs_reduce(c, od, G * Q));                       // a sum over observations; a group may straddle ranks

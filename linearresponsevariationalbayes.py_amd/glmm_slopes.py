@@ -28,6 +28,8 @@ elimination left on the device (`block_arrow_solve_by_phases`, DESIGN.md section
 
 The host algebra of the block arrow is `block_arrow.py` (re-exported here); everything of the objective that is not a device
 entry is `_LogisticMixedModel`, which `LogisticGLMMObjective` (glmm.py) instantiates at K = 1.
+What the K-effect models share whatever their likelihood -- the layout, the Schur entry, the device-resident solve -- is `_SlopesArrow`,
+which `PoissonGLMMObjective` (glmm_poisson.py) inherits as well.
 """
 import numpy as np
 from scipy import special
@@ -193,9 +195,11 @@ class _LogisticMixedModel(DeclaredHypers):
     speak the K-generic layouts of include/lrvb_hip.h (group sums G x ncol, closed-form entries G x 2 K x 3, e and r as G x K);
     `_solve_on_device` where it has a device-resident block-arrow solve."""
     _lrvb_device_functor = True
+    _loss = 'logistic'                               # the loss the device context is created with
 
     def __init__(self, par, x, y, z, groups, n_groups, beta_prior_info, mu_prior, tau_prior, gh_deg, names, weights, device):
-        """z: the N x K group design, or None for one effect per group with the unit design (nothing is sent to the device)."""
+        """z: the N x K group design, or None for one effect per group with the unit design (nothing is sent to the device).
+        gh_deg=None: a likelihood whose psi is closed-form builds no Gauss-Hermite nodes."""
         self.par = par
         x = _hip.as_f64(x)
         self.n_obs, self.P = x.shape
@@ -207,11 +211,11 @@ class _LogisticMixedModel(DeclaredHypers):
         self.G = int(n_groups)
         self._names = tuple(names)
         self._index(par, names)
-        self.gh_x, self.gh_w = np.polynomial.hermite.hermgauss(int(gh_deg))
+        self.gh_x, self.gh_w = (None, None) if gh_deg is None else np.polynomial.hermite.hermgauss(int(gh_deg))
         self._declare_hyper('beta_prior_info', HyperVectorParam('beta_prior_info', 1, lb=0.0, val=np.array([float(beta_prior_info)])))
         self._declare_hyper('mu_prior', HyperVectorParam('mu_prior', 2, val=np.array(list(map(float, mu_prior)))))
         self._declare_hyper('tau_prior', HyperVectorParam('tau_prior', 2, lb=0.0, val=np.array(list(map(float, tau_prior)))))
-        self.ctx = DeviceContext(par.layout_blocks(), loss='logistic', n_obs=self.n_obs, n_cols=self.P, device=device)
+        self.ctx = DeviceContext(par.layout_blocks(), loss=self._loss, n_obs=self.n_obs, n_cols=self.P, device=device)
         self.ctx.set_data(_hip.SLOT_X, x)
         self._y = _hip.as_f64(y).ravel().copy()
         self.ctx.set_data(_hip.SLOT_Y, self._y)
@@ -456,7 +460,7 @@ class _LogisticMixedModel(DeclaredHypers):
         Schur complement with the factor on the global context: call `global_hessian(x, want_host=False)` and
         `_ensure_gctx().chol_factor_last()` at the same point first (free coordinates); a factor built at another point, or
         under other weights or hyper-parameters, is refused with a ValueError.
-        on_device=True (the slopes model only; free coordinates, this process's own rows): the local blocks and the border stay
+        on_device=True (the models with K effects per group, `_SlopesArrow`; free coordinates, this process's own rows): the local blocks and the border stay
         on the device (`block_arrow_solve_by_phases` around lrvb_glmm_slopes_solve_forward / _back); the
         factors are built here when they are not those of this point and reused otherwise."""
         if on_device:
@@ -585,10 +589,8 @@ class _LogisticMixedModel(DeclaredHypers):
         v, r = 1.0 / ib, 1.0 / ig
         rho = x @ eta[:P] + np.sum(z * e[gid], axis=1)
         s = (x * x) @ v + np.sum(z * z * r[gid], axis=1)
-        sd = np.sqrt(s)
-        _, d1, _ = self.ctx.gh_logistic(rho, sd, self.gh_x, self.gh_w, order=2)
-        p_rho = d1[:, 0] - self._y
-        p_s = 0.5 * d1[:, 1] / sd                            # s_n > 0 wherever a row has a non-zero x or z
+        p_rho, p_s = self._row_psi_derivs(rho, s)
+        p_rho = p_rho - self._y
         C = np.zeros((N, ng + 2 * GK))
         C[:, :P] = p_rho[:, None] * x
         C[:, P:2 * P] = p_s[:, None] * (x * x) * (-v * v)[None, :]
@@ -600,6 +602,12 @@ class _LogisticMixedModel(DeclaredHypers):
             C = C * self._jac(eta)[0][None, :]
         return np.ascontiguousarray(C.T)
 
+    def _row_psi_derivs(self, rho, s):
+        """(psi_rho, psi_s) of every row, on the host path of the dense weight cross Hessian."""
+        sd = np.sqrt(s)
+        _, d1, _ = self.ctx.gh_logistic(rho, sd, self.gh_x, self.gh_w, order=2)
+        return d1[:, 0], 0.5 * d1[:, 1] / sd                  # s_n > 0 wherever a row has a non-zero x or z
+
     def global_sensitivity(self, hyper_par, free_val):
         """d theta_global / d hyper^T = -H_S^-1 C_g (n_global x Ph) for a prior hyper-parameter: its cross Hessian has no local
         rows, so the local parameters enter through the Schur complement only."""
@@ -610,13 +618,10 @@ class _LogisticMixedModel(DeclaredHypers):
         return -gc.chol_solve(Cg)
 
 
-class LogisticGLMMSlopesObjective(_LogisticMixedModel):
-    def __init__(self, par, x, y, z, groups, n_groups, beta_prior_info=1.0, mu_prior=(0.0, 1.0), tau_prior=(1.0, 1.0), gh_deg=20,
-                 names=('beta', 'mu', 'tau', 'u'), weights=None, device=0):
-        """names: the parameters of q(beta), q(mu), q(tau_k) -- named names[2] + str(k), k = 0..K-1 -- and q(u)."""
-        if z is None:
-            raise ValueError('z must be N x K with 1 <= K <= 4')
-        super().__init__(par, x, y, z, groups, n_groups, beta_prior_info, mu_prior, tau_prior, gh_deg, names, weights, device)
+class _SlopesArrow:
+    """What the models with K effects per group share on top of `_LogisticMixedModel`, whatever their likelihood: the parameter
+    layout of DESIGN.md section 18, the Schur entry on the resident group sums and the block-arrow solve resident on the device
+    (`LogisticGLMMSlopesObjective`, `PoissonGLMMObjective`)."""
 
     def _layout(self, par, names):
         P, K, G = self.P, self.K, self.G
@@ -633,18 +638,8 @@ class LogisticGLMMSlopesObjective(_LogisticMixedModel):
             raise ValueError(msg)
         return want, msg, 'the parameter holds more than the blocks of the model'
 
-    # ---- the device entries -------------------------------------------------------------------------------------------------
-    def _terms(self, *point, **want):
-        return self.ctx.glmm_slopes_terms(*point, **want)
-
     def _schur(self, local_blocks, border_scale, closed_rows):
         return self.ctx.glmm_slopes_schur(local_blocks, border_scale, closed_rows)
-
-    def _obs_influence(self, *point_and_operand, **window):
-        return self.ctx.glmm_slopes_obs_influence(*point_and_operand, **window)
-
-    def _group_influence(self, *point_and_operand):
-        return self.ctx.glmm_slopes_group_influence(*point_and_operand)
 
     # ---- the block-arrow solve resident on the device ------------------------------------------------------------------------
     def _device_factors(self, x, is_free):
@@ -675,3 +670,22 @@ class LogisticGLMMSlopesObjective(_LogisticMixedModel):
         return block_arrow_solve_by_phases(R, self.n_global, coupled_rows(self.P, self.K), s, self.ctx.glmm_slopes_solve_forward,
                                            self._ensure_gctx().chol_solve,
                                            lambda xc: self.ctx.glmm_slopes_solve_back(xc, self.G, self.K))
+
+
+class LogisticGLMMSlopesObjective(_SlopesArrow, _LogisticMixedModel):
+    def __init__(self, par, x, y, z, groups, n_groups, beta_prior_info=1.0, mu_prior=(0.0, 1.0), tau_prior=(1.0, 1.0), gh_deg=20,
+                 names=('beta', 'mu', 'tau', 'u'), weights=None, device=0):
+        """names: the parameters of q(beta), q(mu), q(tau_k) -- named names[2] + str(k), k = 0..K-1 -- and q(u)."""
+        if z is None:
+            raise ValueError('z must be N x K with 1 <= K <= 4')
+        super().__init__(par, x, y, z, groups, n_groups, beta_prior_info, mu_prior, tau_prior, gh_deg, names, weights, device)
+
+    # ---- the device entries -------------------------------------------------------------------------------------------------
+    def _terms(self, *point, **want):
+        return self.ctx.glmm_slopes_terms(*point, **want)
+
+    def _obs_influence(self, *point_and_operand, **window):
+        return self.ctx.glmm_slopes_obs_influence(*point_and_operand, **window)
+
+    def _group_influence(self, *point_and_operand):
+        return self.ctx.glmm_slopes_group_influence(*point_and_operand)

@@ -482,6 +482,53 @@ class DeviceContext(object):
                                                               _hip.ptr(Al), Q, _hip.ptr(out)))
         return out
 
+    # ---- Poisson mixed model (lrvb_glmm_poisson_*): the layouts of the slopes entries, no quadrature ---------------------------
+    def set_offset(self, offset):
+        """The per-row offset (log exposure) of the Poisson mixed model, or None to clear it (lrvb_set_offset)."""
+        if offset is None:
+            self._check(self._lib.lrvb_set_offset(self._h, None, 0))
+            return
+        o = _hip.as_f64(offset).ravel()
+        self._check(self._lib.lrvb_set_offset(self._h, _hip.ptr(o), o.size))
+
+    def glmm_poisson_terms(self, mean, var, e, r, want_grad=True, want_hess=True, want_border=True):
+        """Data term of the Poisson mixed model with K effects per group in the coordinates (mean, var, e, r), e and r being G x K
+        (lrvb_glmm_poisson_terms): what `glmm_slopes_terms` returns, in its layouts.  The group sums stay resident for
+        `glmm_slopes_schur`.  A point at which exp(rho + s / 2) overflows is a ValueError."""
+        m, v = _hip.as_f64(mean).ravel(), _hip.as_f64(var).ravel()
+        e, r = _hip.as_f64(e), _hip.as_f64(r)
+        P = self.n_cols
+        if e.ndim != 2 or r.shape != e.shape or m.size != P or v.size != P:
+            raise ValueError('expected mean and var of length {}, e and r of one shape G x K'.format(P))
+        G, K = e.shape
+        nsc = 2 * K + K * (2 * K + 1)
+        val = np.empty(1)
+        gg = np.empty(2 * P) if want_grad else None
+        Hb = np.empty((3, P, P)) if want_hess else None
+        border = bool(want_hess and want_border)
+        gs = np.empty((G, nsc + (4 * K * P if border else 0))) if (want_grad or want_hess) else None
+        self._check(self._lib.lrvb_glmm_poisson_terms(self._h, _hip.ptr(m), _hip.ptr(v), P, _hip.ptr(e), _hip.ptr(r), G, K, _hip.ptr(val),
+                                                     _hip.ptr(gg), _hip.ptr(Hb), _hip.ptr(gs), 1 if border else 0))
+        return float(val[0]), gg, Hb, gs
+
+    def glmm_poisson_obs_influence(self, mean, var, e, r, A, n0=0, n1=None):
+        """(n1 - n0) x Q rows of the Poisson mixed model, as `glmm_slopes_obs_influence` (lrvb_glmm_poisson_obs_influence)."""
+        (m, v, e, r, _, _, Ag, Al), Q = self._glmm_influence_args(mean, var, e, r, (), (), A)
+        n0 = int(n0)
+        n1 = self.n_obs if n1 is None else int(n1)
+        out = np.empty((max(n1 - n0, 0), Q))
+        self._check(self._lib.lrvb_glmm_poisson_obs_influence(self._h, _hip.ptr(m), _hip.ptr(v), self.n_cols, _hip.ptr(e), _hip.ptr(r),
+                                                             e.shape[0], e.shape[1], _hip.ptr(Ag), _hip.ptr(Al), Q, n0, n1, _hip.ptr(out)))
+        return out
+
+    def glmm_poisson_group_influence(self, mean, var, e, r, A):
+        """G x Q group influence of the Poisson mixed model, as `glmm_slopes_group_influence` (lrvb_glmm_poisson_group_influence)."""
+        (m, v, e, r, _, _, Ag, Al), Q = self._glmm_influence_args(mean, var, e, r, (), (), A)
+        out = np.empty((e.shape[0], Q))
+        self._check(self._lib.lrvb_glmm_poisson_group_influence(self._h, _hip.ptr(m), _hip.ptr(v), self.n_cols, _hip.ptr(e), _hip.ptr(r),
+                                                               e.shape[0], e.shape[1], _hip.ptr(Ag), _hip.ptr(Al), Q, _hip.ptr(out)))
+        return out
+
     # ---- multinomial (softmax) regression: beta is (K - 1) x n_cols, D = (K - 1) n_cols (lrvb_softmax_*) --------------------
     def softmax_set_labels(self, labels, n_classes):
         y = np.ascontiguousarray(np.asarray(labels).ravel(), dtype=np.int32)

@@ -1,7 +1,22 @@
-// k_glmm_slopes.hip -- logistic mixed model with K <= 4 independent random effects per group:
-//   y_n ~ Bernoulli(sigma(x_n . beta + z_n . u_g(n))),   q(beta_j) = N(m_j, v_j),   q(u_gk) = N(e_gk, r_gk).
-// Per observation rho_n = x_n . m + z_n . e_g, s_n = (x_n o x_n) . v + (z_n o z_n) . r_g and the five quadrature coefficients
-// a1, a2, c11, c12, c22 of k_glmm.hip (same nodes, same Stein-rule derivatives).  With K = 1 and z = 1 it is that model.
+// k_glmm_slopes.hip -- mixed models with K <= 4 independent random effects per group, q(beta_j) = N(m_j, v_j), q(u_gk) = N(e_gk, r_gk):
+//   logistic:  y_n ~ Bernoulli(sigma(x_n . beta + z_n . u_g(n)))
+//   Poisson  (DESIGN.md section 26):  y_n ~ Poisson(exp(o_n + x_n . beta + z_n . u_g(n)))
+// Per observation rho_n = x_n . m + z_n . e_g, s_n = (x_n o x_n) . v + (z_n o z_n) . r_g and five coefficients a1, a2, c11, c12, c22.
+// Every kernel that walks the rows is written ONCE, as a template over a likelihood policy: LogisticLik
+// (the quadrature of k_glmm.hip: same nodes, same Stein-rule derivatives; with K = 1 and z = 1 it is that model) and PoissonLik
+// (psi = E exp(t) = exp(o + rho + s / 2) exactly: ONE exp per row, no nodes).  A policy supplies
+//   Args / Lds      what only its kernels are handed (the nodes, a struct | the offset, a __restrict__ pointer) and its LDS (node
+//                   tables | the tile's offsets) -- nothing of the other's;
+//   init, stage_row what it puts there, once per workgroup and once per staged row;
+//   row_shift, infl (rho, s) -> (e1, e2) = (psi_rho, 2 psi_s) on all four lanes of a row, row_shift being what the row adds to rho
+//                   (the staged offset), read ahead of the dot products: the two influence kernels;
+//   moments, coefs  (rho, s) -> the row's value and its NCF coefficient rows: the rows kernel;
+//   cf_row, HAS_FACTOR / cf_factor, NB / o_d / d_stride, DK
+//                   rows kernel: where the five coefficients live.  The logistic model keeps five rows.  With h = w psi the
+//                   Poisson ones are a1 = h - w y, a2 = h / 2, c11 = h, c12 = h / 2, c22 = h / 4: TWO rows (a1, h) and the constant
+//                   factors 1, 1/2, 1, 1/2, 1/4.  A power of two is applied ONCE to a finished sum (at the flush of a segment; to
+//                   a whole block in the host's terms body), bit for bit the sum of the scaled terms.  So its products table has
+//                   NB = 2 blocks per component (h z_k, h z_k^2), stored densely, against the logistic 4 at stride 16.
 //
 // glmm_slopes_rows_kernel is ONE pass over the rows in group-sorted order, built like glmm_rows_kernel: a workgroup (4 waves) walks
 // tiles of GS_T = 64 sorted rows.
@@ -9,11 +24,12 @@
 //      P .. P + K - 1 of the same LDS row, stride GS_XS);
 //   2. four lanes share a row for the four dot products (lane q4 takes the x columns q4, q4 + 4, .. and the z column q4) and for
 //      the quadrature nodes; xor shuffles add the quarters;
-//   3. lane 0 of the four writes the five coefficients to the ORIGINAL row position (global block and gradient by the library's
+//   3. lane 0 of the four writes the coefficients to the ORIGINAL row position (global block and gradient by the library's
 //      weighted products, unchanged) and to LDS;
-//   4. the 4 K products of a row that P border columns each share,
-//        d[0 K + k] = c11 z_k,  d[1 K + k] = c12 z_k^2,  d[2 K + k] = c12 z_k,  d[3 K + k] = c22 z_k^2,
-//      are formed ONCE per row into LDS (GS_DS doubles per row);
+//   4. the products of a row that P border columns each share (logistic: 4 K,
+//        d[0 K + k] = c11 z_k,  d[1 K + k] = c12 z_k^2,  d[2 K + k] = c12 z_k,  d[3 K + k] = c22 z_k^2;
+//      Poisson: the first 2 K of them with h for both coefficients, blocks 2 and 3 reading blocks 0 and 1)
+//      are formed ONCE per row into LDS;
 //   5. segmented sums from the tile still in LDS over the ncol = nsc + 4 K P columns of a group,
 //        [ sum a1 z (K) | sum a2 z o z (K) | upper triangle, row-major, of the 2 K x 2 K block  sum c q q^T  (K (2 K + 1)) |
 //          border: column nsc + (b K + k) P + j = sum d[b K + k] x_j (b = 0, 1) or d[b K + k] x_j^2 (b = 2, 3) ],
@@ -23,96 +39,64 @@
 //      of group: a group inside one tile goes to its row of the result, the piece of a group cut by a tile boundary to one of
 //      the tile's two partial rows, which glmm_fixup_kernel (k_glmm.hip) adds in tile order.
 // No atomics anywhere: the result is a fixed-order sum, bitwise reproducible.  Empty groups keep the zeros the caller wrote.
+// The Poisson policy does not clamp: where o + rho + s / 2 overflows the exponent, psi = inf reaches the sums and the entry refuses
+// the non-finite value (LRVB_ERR_INVALID).
 #include "lrvb_internal.h"
 #include "k_kernels.h"
 #include <math.h>
+#include <type_traits>
 
 constexpr int GS_T = 64;                 // sorted rows per tile (= GL_T of k_glmm.hip: glmm_fixup_kernel and glmm_num_tiles are shared)
 constexpr int GS_XS = 68;                // LDS row stride in doubles: 64 columns of x + 4 of z; 68 = 4 mod 32, so the 8 rows x 4 lanes
                                          // of a 32-lane half read 32 different 8-byte bank pairs in the dot products
-constexpr int GS_DS = 16;                // the 4 K shared products of a row
 constexpr int GS_OWN = 4;                // border columns per thread: 4 K P <= 1024 = 4 x 256
 
-__global__ __launch_bounds__(256)
-void glmm_slopes_rows_kernel(i64 N, int P, int Kz, i64 G, const double* __restrict__ X, const double* __restrict__ Z,
-                             const double* __restrict__ y, const double* __restrict__ w, const i64* __restrict__ perm,
-                             const i64* __restrict__ offs, const double* __restrict__ m, const double* __restrict__ vb,
-                             const double* __restrict__ eg, const double* __restrict__ rg, const double* __restrict__ gx,
-                             const double* __restrict__ gw, int nq, double* __restrict__ coef, i64 NP, double* __restrict__ gsum,
-                             double* __restrict__ part, double* __restrict__ vpart)
-{
-    __shared__ double xs[GS_T * GS_XS], dk[GS_T * GS_DS], cf[5 * GS_T], ms[64], vs[64], sx[128], sw[128], red[4];
-    __shared__ i64 s_row[GS_T];
-    __shared__ int s_gid[GS_T], s_whole[GS_T];
-    const int tid = threadIdx.x;
-    const int K2 = 2 * Kz, K4 = 4 * Kz;
-    const int nsc = K2 + Kz * (K2 + 1), nbord = K4 * P, ncol = nsc + nbord;
-    const double r2 = 1.4142135623730951, ispi = 0.5641895835477563;     // sqrt(2), 1 / sqrt(pi)
-    if (tid < nq) { sx[tid] = r2 * gx[tid]; sw[tid] = ispi * gw[tid]; }
-    if (tid < P) { ms[tid] = m[tid]; vs[tid] = vb[tid]; }
-    const i64 n_tiles = (N + GS_T - 1) / GS_T;
-    const int row = tid >> 2, q4 = tid & 3;
-    // the border columns of this thread: column t = tid + 256 i is block bk = t / P (d[bk]) and x column j = t - bk P
-    int o_x[GS_OWN], o_d[GS_OWN];
-    bool o_has[GS_OWN], o_sq[GS_OWN];
-#pragma unroll
-    for (int i = 0; i < GS_OWN; ++i) {
-        const int t = tid + 256 * i;
-        o_has[i] = t < nbord;
-        const int bk = o_has[i] ? t / P : 0;
-        o_d[i] = bk; o_x[i] = o_has[i] ? t - bk * P : 0; o_sq[i] = bk >= K2;
+// ---- the two likelihood policies -------------------------------------------------------------------------------------------------
+// `kind` names one of the five coefficients: 0 = a1, 1 = a2, 2 = c11, 3 = c12, 4 = c22.
+struct LogisticLik {
+    struct Args { const double* gx; const double* gw; int nq; };         // Gauss-Hermite nodes and weights (device), 1 <= nq <= 128
+    struct Lds { double sx[128], sw[128]; };                             // sqrt(2) x_k, w_k / sqrt(pi)
+    struct Moments { double v, e1, e2, e3, e4; };
+    static constexpr const char* LIMITS = "logistic mixed model with slopes: P <= 64, 1 <= K <= 4, at most 128 nodes";
+    static bool args_ok(const Args& a) { return a.nq >= 1 && a.nq <= 128; }
+    static constexpr int NCF = 5, NB = 4, DK = 16;
+    static constexpr bool HAS_FACTOR = false;
+    static __device__ __forceinline__ int cf_row(int kind) { return kind; }
+    static __device__ __forceinline__ double cf_factor(int) { return 1.0; }                      // HAS_FACTOR is false: no flush multiplies by it
+    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return b * Kz + k; }
+    static __device__ __forceinline__ int d_stride(int) { return DK; }
+
+    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid)
+    {
+        const double r2 = 1.4142135623730951, ispi = 0.5641895835477563;     // sqrt(2), 1 / sqrt(pi)
+        if (tid < a.nq) { L.sx[tid] = r2 * a.gx[tid]; L.sw[tid] = ispi * a.gw[tid]; }
     }
-    // the scalar column of this thread (tid < nsc): cf[s_c] q[s_i] q[s_j] with q = [z | z o z | 1]
-    const bool has_sc = tid < nsc;
-    int s_c = 0, s_i = K2, s_j = K2;
-    if (tid < Kz) { s_c = 0; s_i = tid; }
-    else if (tid < K2) { s_c = 1; s_i = tid; }
-    else if (has_sc) {
-        int u = tid - K2, i = 0;
-        while (u >= K2 - i) { u -= K2 - i; ++i; }
-        s_i = i; s_j = i + u;
-        s_c = s_j < Kz ? 2 : (s_i >= Kz ? 4 : 3);
-    }
-    const int zi = P + (s_i < Kz ? s_i : s_i - Kz), zj = P + (s_j < Kz ? s_j : s_j - Kz);    // unused where the factor is 1
-    const bool i_one = s_i >= K2, i_sq = s_i >= Kz, j_one = s_j >= K2, j_sq = s_j >= Kz;
-    for (i64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const i64 t0 = tile * GS_T;
-        const int rows = (int)(N - t0 < GS_T ? N - t0 : GS_T);
-        __syncthreads();                                                 // the previous tile is consumed (and the nodes are in place)
-        if (tid < GS_T) {
-            int g = 0, whole = 0;
-            i64 pr = 0;
-            if (tid < rows) {
-                const i64 i = t0 + tid;
-                pr = perm[i];
-                i64 lo = 0, hi = G;                                      // the last g with offs[g] <= i (its offs[g + 1] > i)
-                while (hi - lo > 1) { const i64 mid = (lo + hi) >> 1; if (offs[mid] <= i) lo = mid; else hi = mid; }
-                g = (int)lo;
-                whole = (offs[lo] >= t0 && offs[lo + 1] <= t0 + GS_T) ? 1 : 0;
-            }
-            s_row[tid] = pr; s_gid[tid] = g; s_whole[tid] = whole;
-        }
-        __syncthreads();
-        for (int e = tid; e < rows * P; e += 256) { const int rr = e / P, cc = e - rr * P; xs[rr * GS_XS + cc] = X[s_row[rr] * P + cc]; }
-        for (int e = tid; e < rows * Kz; e += 256) { const int rr = e / Kz, cc = e - rr * Kz; xs[rr * GS_XS + P + cc] = Z[s_row[rr] * Kz + cc]; }
-        __syncthreads();
-        double rho = 0.0, s = 0.0;
-        if (row < rows) {
-            const double* xr = xs + row * GS_XS;
-            for (int j = q4; j < P; j += 4) { const double x = xr[j]; rho += x * ms[j]; s += x * x * vs[j]; }
-            if (q4 < Kz) {
-                const i64 gk = (i64)s_gid[row] * Kz + q4;
-                const double z = xr[P + q4];
-                rho += z * eg[gk]; s += z * z * rg[gk];
-            }
-        }
-        rho += __shfl_xor(rho, 1); s += __shfl_xor(s, 1);
-        rho += __shfl_xor(rho, 2); s += __shfl_xor(s, 2);
-        double v = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0, e4 = 0.0;
-        if (row < rows) {
+    static __device__ __forceinline__ void stage_row(Lds&, const Args&, int, bool, i64) {}
+    static __device__ __forceinline__ double row_shift(const Lds&, int) { return 0.0; }
+    // the sibling of gi_psi_derivs (k_glmm.hip): e1 = psi_rho and e2 = E g2 = 2 psi_s
+    static __device__ __forceinline__ void infl(const Lds& L, const Args& a, double, bool live, int q4, double rho, double s, double& e1,
+                                                double& e2)
+    {
+        e1 = 0.0; e2 = 0.0;
+        if (live) {
             const double sd = sqrt(fmax(s, 0.0));
-            for (int k = q4; k < nq; k += 4) {
-                const double t = rho + sd * sx[k], wk = sw[k];
+            for (int k = q4; k < a.nq; k += 4) {
+                const double t = rho + sd * L.sx[k], wk = L.sw[k];
+                const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
+                const double sg = t >= 0.0 ? ie : e * ie;
+                e1 += wk * sg; e2 += wk * e * ie * ie;
+            }
+        }
+        e1 += __shfl_xor(e1, 1); e2 += __shfl_xor(e2, 1);
+        e1 += __shfl_xor(e1, 2); e2 += __shfl_xor(e2, 2);
+    }
+    static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
+    {
+        double v = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0, e4 = 0.0;
+        if (live) {
+            const double sd = sqrt(fmax(s, 0.0));
+            for (int k = q4; k < a.nq; k += 4) {
+                const double t = rho + sd * L.sx[k], wk = L.sw[k];
                 const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
                 const double sp = (t > 0.0 ? t : 0.0) + log1p(e);
                 const double sg = t >= 0.0 ? ie : e * ie;
@@ -127,28 +111,180 @@ void glmm_slopes_rows_kernel(i64 N, int P, int Kz, i64 G, const double* __restri
             v += __shfl_xor(v, off); e1 += __shfl_xor(e1, off); e2 += __shfl_xor(e2, off);
             e3 += __shfl_xor(e3, off); e4 += __shfl_xor(e4, off);
         }
+        return {v, e1, e2, e3, e4};
+    }
+    static __device__ __forceinline__ double coefs(const Lds&, int, const Moments& mo, double wi, double yi, double rho, double,
+                                                   double* k)
+    {
+        k[0] = wi * (mo.e1 - yi); k[1] = wi * 0.5 * mo.e2; k[2] = wi * mo.e2; k[3] = wi * 0.5 * mo.e3; k[4] = wi * 0.25 * mo.e4;
+        return wi * (mo.v - yi * rho);
+    }
+};
+
+struct PoissonLik {
+    typedef const double* __restrict__ Args;                             // the per-row offset (device, original row order) or nullptr
+    struct Lds { double s_off[GS_T]; };                                  // the offsets of the tile's rows
+    struct Moments {};
+    static constexpr const char* LIMITS = "Poisson mixed model: P <= 64, 1 <= K <= 4";
+    static bool args_ok(const Args&) { return true; }
+    static constexpr int NCF = 2, NB = 2, DK = 8;                        // coefficient rows [a1 | h]
+    static constexpr bool HAS_FACTOR = true;
+    static __device__ __forceinline__ int cf_row(int kind) { return kind == 0 ? 0 : 1; }
+    static __device__ __forceinline__ double cf_factor(int kind) { return kind == 4 ? 0.25 : ((kind & 1) ? 0.5 : 1.0); }
+    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return (b & 1) * Kz + k; }
+    static __device__ __forceinline__ int d_stride(int Kz) { return 2 * Kz; }
+
+    static __device__ __forceinline__ void init(Lds&, const Args&, int) {}
+    static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
+    {
+        L.s_off[t] = (a && live) ? a[src] : 0.0;
+    }
+    static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_off[row]; }
+    static __device__ __forceinline__ void infl(const Lds&, const Args&, double o, bool live, int, double rho, double s, double& e1,
+                                                double& e2)
+    {
+        e1 = e2 = live ? exp((rho + o) + 0.5 * s) : 0.0;
+    }
+    static __device__ __forceinline__ Moments moments(const Lds&, const Args&, bool, int, double, double) { return {}; }
+    static __device__ __forceinline__ double coefs(const Lds& L, int row, const Moments&, double wi, double yi, double rho, double s,
+                                                   double* k)
+    {
+        rho += L.s_off[row];
+        const double psi = exp(rho + 0.5 * s);
+        const double h = wi * psi;
+        k[0] = h - wi * yi; k[1] = h;
+        return wi * (psi - yi * rho);
+    }
+};
+
+// ---- what the kernels over group-sorted rows share ----------------------------------------------------------------------------------
+// The head of a tile of sorted rows: thread t < GS_T finds row t0 + t's original position, its group (the last g with
+// offs[g] <= i) and whether that group lies whole inside the tile; then the tile's rows of X and Z are gathered into xs (row
+// stride XS, z behind the P columns of x).  Ends on a barrier.
+template <class Lik, int XS>
+__device__ __forceinline__ void gs_stage_sorted_tile(int tid, i64 t0, int rows, int P, int Kz, i64 G, const double* __restrict__ X,
+                                                     const double* __restrict__ Z, const i64* __restrict__ perm,
+                                                     const i64* __restrict__ offs, const typename Lik::Args& la, typename Lik::Lds& lik,
+                                                     double* xs, i64* s_row, int* s_gid, int* s_whole)
+{
+    if (tid < GS_T) {
+        int g = 0, whole = 0;
+        i64 pr = 0;
+        if (tid < rows) {
+            const i64 i = t0 + tid;
+            pr = perm[i];
+            i64 lo = 0, hi = G;                                          // the last g with offs[g] <= i (its offs[g + 1] > i)
+            while (hi - lo > 1) { const i64 mid = (lo + hi) >> 1; if (offs[mid] <= i) lo = mid; else hi = mid; }
+            g = (int)lo;
+            whole = (offs[lo] >= t0 && offs[lo + 1] <= t0 + GS_T) ? 1 : 0;
+        }
+        s_row[tid] = pr; s_gid[tid] = g; s_whole[tid] = whole;
+        Lik::stage_row(lik, la, tid, tid < rows, pr);
+    }
+    __syncthreads();
+    for (int e = tid; e < rows * P; e += 256) { const int rr = e / P, cc = e - rr * P; xs[rr * XS + cc] = X[s_row[rr] * P + cc]; }
+    for (int e = tid; e < rows * Kz; e += 256) { const int rr = e / Kz, cc = e - rr * Kz; xs[rr * XS + P + cc] = Z[s_row[rr] * Kz + cc]; }
+    __syncthreads();
+}
+
+// Where the walk of a tile flushes the segment that ends at a change of group: the group's own row of the result where the group
+// lies whole inside the tile, else one of the tile's two partial rows -- row 0 for the piece that began at the tile's first row
+// (the tail of a group cut by the boundary before it), row 1 for the piece that runs to its end.
+__device__ __forceinline__ double* gs_flush_dst(bool whole, int g, i64 tile, int run_start, int ncol, double* gsum, double* part)
+{
+    return whole ? gsum + (i64)g * ncol : part + (tile * 2 + (run_start == 0 ? 0 : 1)) * ncol;
+}
+
+template <class Lik>
+__global__ __launch_bounds__(256)
+void glmm_slopes_rows_kernel(i64 N, int P, int Kz, i64 G, const double* __restrict__ X, const double* __restrict__ Z,
+                             const double* __restrict__ y, const double* __restrict__ w, const i64* __restrict__ perm,
+                             const i64* __restrict__ offs, const double* __restrict__ m, const double* __restrict__ vb,
+                             const double* __restrict__ eg, const double* __restrict__ rg, typename Lik::Args la,
+                             double* __restrict__ coef, i64 NP, double* __restrict__ gsum, double* __restrict__ part,
+                             double* __restrict__ vpart)
+{
+    __shared__ double xs[GS_T * GS_XS], dk[GS_T * Lik::DK], cf[Lik::NCF * GS_T], ms[64], vs[64], red[4];
+    __shared__ typename Lik::Lds lik;
+    __shared__ i64 s_row[GS_T];
+    __shared__ int s_gid[GS_T], s_whole[GS_T];
+    const int tid = threadIdx.x;
+    const int K2 = 2 * Kz, ND = Lik::NB * Kz, DS = Lik::d_stride(Kz);
+    const int nsc = K2 + Kz * (K2 + 1), nbord = 4 * Kz * P, ncol = nsc + nbord;
+    Lik::init(lik, la, tid);
+    if (tid < P) { ms[tid] = m[tid]; vs[tid] = vb[tid]; }
+    const i64 n_tiles = (N + GS_T - 1) / GS_T;
+    const int row = tid >> 2, q4 = tid & 3;
+    // the border columns of this thread: column t = tid + 256 i is block bk = t / P (b = bk / K, k = bk - b K) and x column
+    // j = t - bk P; it reads the product o_d(b, k), squares x for b >= 2 and (Poisson) carries the factor of its coefficient
+    int o_x[GS_OWN], o_d[GS_OWN];
+    bool o_has[GS_OWN], o_sq[GS_OWN];
+    double o_f[GS_OWN];
+#pragma unroll
+    for (int i = 0; i < GS_OWN; ++i) {
+        const int t = tid + 256 * i;
+        o_has[i] = t < nbord;
+        const int bk = o_has[i] ? t / P : 0, b = bk / Kz, k = bk - b * Kz;
+        o_d[i] = Lik::o_d(b, k, Kz); o_x[i] = o_has[i] ? t - bk * P : 0; o_sq[i] = bk >= K2;
+        o_f[i] = Lik::cf_factor(b == 0 ? 2 : (b == 3 ? 4 : 3));
+    }
+    // the scalar column of this thread (tid < nsc): coefficient s_k times q[s_i] q[s_j] with q = [z | z o z | 1]
+    const bool has_sc = tid < nsc;
+    int s_k = 0, s_i = K2, s_j = K2;
+    if (tid < Kz) { s_k = 0; s_i = tid; }
+    else if (tid < K2) { s_k = 1; s_i = tid; }
+    else if (has_sc) {
+        int u = tid - K2, i = 0;
+        while (u >= K2 - i) { u -= K2 - i; ++i; }
+        s_i = i; s_j = i + u;
+        s_k = s_j < Kz ? 2 : (s_i >= Kz ? 4 : 3);
+    }
+    const int s_c = Lik::cf_row(s_k);
+    const double s_f = Lik::cf_factor(s_k);
+    const int zi = P + (s_i < Kz ? s_i : s_i - Kz), zj = P + (s_j < Kz ? s_j : s_j - Kz);    // unused where the factor is 1
+    const bool i_one = s_i >= K2, i_sq = s_i >= Kz, j_one = s_j >= K2, j_sq = s_j >= Kz;
+    for (i64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const i64 t0 = tile * GS_T;
+        const int rows = (int)(N - t0 < GS_T ? N - t0 : GS_T);
+        __syncthreads();                                                 // the previous tile is consumed (and the nodes, m, v are in place)
+        gs_stage_sorted_tile<Lik, GS_XS>(tid, t0, rows, P, Kz, G, X, Z, perm, offs, la, lik, xs, s_row, s_gid, s_whole);
+        double rho = 0.0, s = 0.0;
+        if (row < rows) {
+            const double* xr = xs + row * GS_XS;
+            for (int j = q4; j < P; j += 4) { const double x = xr[j]; rho += x * ms[j]; s += x * x * vs[j]; }
+            if (q4 < Kz) {
+                const i64 gk = (i64)s_gid[row] * Kz + q4;
+                const double z = xr[P + q4];
+                rho += z * eg[gk]; s += z * z * rg[gk];
+            }
+        }
+        rho += __shfl_xor(rho, 1); s += __shfl_xor(s, 1);
+        rho += __shfl_xor(rho, 2); s += __shfl_xor(s, 2);
+        const typename Lik::Moments mo = Lik::moments(lik, la, row < rows, q4, rho, s);
         double contrib = 0.0;
         if (q4 == 0) {
-            double k1 = 0.0, k2 = 0.0, k11 = 0.0, k12 = 0.0, k22 = 0.0;
+            double k[Lik::NCF];
+#pragma unroll
+            for (int i = 0; i < Lik::NCF; ++i) k[i] = 0.0;
             if (row < rows) {
                 const i64 pr = s_row[row];
-                const double wi = w[pr], yi = y[pr];
-                contrib = wi * (v - yi * rho);
-                k1 = wi * (e1 - yi); k2 = wi * 0.5 * e2; k11 = wi * e2; k12 = wi * 0.5 * e3; k22 = wi * 0.25 * e4;
-                coef[pr] = k1; coef[NP + pr] = k2; coef[2 * NP + pr] = k11; coef[3 * NP + pr] = k12; coef[4 * NP + pr] = k22;
+                contrib = Lik::coefs(lik, row, mo, w[pr], y[pr], rho, s, k);
+#pragma unroll
+                for (int i = 0; i < Lik::NCF; ++i) coef[i * NP + pr] = k[i];
             }
-            cf[row] = k1; cf[GS_T + row] = k2; cf[2 * GS_T + row] = k11; cf[3 * GS_T + row] = k12; cf[4 * GS_T + row] = k22;
+#pragma unroll
+            for (int i = 0; i < Lik::NCF; ++i) cf[i * GS_T + row] = k[i];
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) contrib += __shfl_xor(contrib, off);
         if ((tid & 63) == 0) red[tid >> 6] = contrib;
         __syncthreads();
         if (tid == 0) vpart[tile] = (red[0] + red[1]) + (red[2] + red[3]);
-        // the 4 K products of a row that its border columns share
-        for (int e = tid; e < rows * K4; e += 256) {
-            const int rr = e / K4, bk = e - rr * K4, b = bk / Kz, k = bk - b * Kz;
+        // the NB K products of a row that its border columns share
+        for (int e = tid; e < rows * ND; e += 256) {
+            const int rr = e / ND, bk = e - rr * ND, b = bk / Kz, k = bk - b * Kz;
             const double z = xs[rr * GS_XS + P + k];
-            dk[rr * GS_DS + bk] = cf[(b == 0 ? 2 : (b == 3 ? 4 : 3)) * GS_T + rr] * ((b & 1) ? z * z : z);
+            dk[rr * DS + bk] = cf[Lik::cf_row(b == 0 ? 2 : (b == 3 ? 4 : 3)) * GS_T + rr] * ((b & 1) ? z * z : z);
         }
         __syncthreads();
         // segmented sums over the tile's rows, in row order
@@ -157,7 +293,7 @@ void glmm_slopes_rows_kernel(i64 N, int P, int Kz, i64 G, const double* __restri
             int run_start = 0;
             for (int rr = 0; rr < rows; ++rr) {
                 const double* xr = xs + rr * GS_XS;
-                const double* dr = dk + rr * GS_DS;
+                const double* dr = dk + rr * DS;
 #pragma unroll
                 for (int i = 0; i < GS_OWN; ++i)
                     if (o_has[i]) { double x = xr[o_x[i]]; if (o_sq[i]) x *= x; acc[i] += dr[o_d[i]] * x; }
@@ -169,11 +305,17 @@ void glmm_slopes_rows_kernel(i64 N, int P, int Kz, i64 G, const double* __restri
                 }
                 const int g = s_gid[rr];
                 if (rr == rows - 1 || s_gid[rr + 1] != g) {
-                    double* dst = s_whole[rr] ? gsum + (i64)g * ncol : part + (tile * 2 + (run_start == 0 ? 0 : 1)) * ncol;
+                    double* dst = gs_flush_dst(s_whole[rr], g, tile, run_start, ncol, gsum, part);
 #pragma unroll
                     for (int i = 0; i < GS_OWN; ++i)
-                        if (o_has[i]) { dst[nsc + tid + 256 * i] = acc[i]; acc[i] = 0.0; }
-                    if (has_sc) dst[tid] = accs;
+                        if (o_has[i]) {
+                            if constexpr (Lik::HAS_FACTOR) acc[i] = o_f[i] * acc[i];
+                            dst[nsc + tid + 256 * i] = acc[i]; acc[i] = 0.0;
+                        }
+                    if (has_sc) {
+                        if constexpr (Lik::HAS_FACTOR) accs = s_f * accs;
+                        dst[tid] = accs;
+                    }
                     accs = 0.0; run_start = rr + 1;
                 }
             }
@@ -181,21 +323,27 @@ void glmm_slopes_rows_kernel(i64 N, int P, int Kz, i64 G, const double* __restri
     }
 }
 
-int launch_glmm_slopes_rows(lrvb_ctx* c, int Kz, const double* Z, const double* m, const double* vb, const double* eg, const double* rg,
-                            const double* gx, const double* gw, int nq, double* coef, i64 NP, double* gsum, double* part, double* vpart) {
+template <class Lik>
+static int gs_launch_rows(lrvb_ctx* c, int Kz, const double* Z, typename Lik::Args la, const double* m, const double* vb, const double* eg,
+                          const double* rg, double* coef, i64 NP, double* gsum, double* part, double* vpart) {
     const i64 N = c->N, G = c->n_groups;
-    if (c->P > 64 || Kz < 1 || Kz > 4 || nq < 1 || nq > 128)
-        LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "logistic mixed model with slopes: P <= 64, 1 <= K <= 4, at most 128 nodes");
+    if (c->P > 64 || Kz < 1 || Kz > 4 || !Lik::args_ok(la)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "%s", Lik::LIMITS);
     const int ncol = glmm_slopes_ncol((int)c->P, Kz);
     const i64* gdev = reinterpret_cast<const i64*>(c->groups.p);
     const i64 n_tiles = glmm_num_tiles(N);
     const unsigned grid = (unsigned)(n_tiles < 2048 ? (n_tiles < 1 ? 1 : n_tiles) : 2048);
-    hipLaunchKernelGGL(glmm_slopes_rows_kernel, dim3(grid), dim3(256), 0, c->stream, N, (int)c->P, Kz, G, (const double*)c->X.p, Z,
-                       (const double*)c->y.p, (const double*)c->w.p, gdev, gdev + N, m, vb, eg, rg, gx, gw, nq, coef, NP, gsum, part, vpart);
+    hipLaunchKernelGGL(glmm_slopes_rows_kernel<Lik>, dim3(grid), dim3(256), 0, c->stream, N, (int)c->P, Kz, G, (const double*)c->X.p, Z,
+                       (const double*)c->y.p, (const double*)c->w.p, gdev, gdev + N, m, vb, eg, rg, la, coef, NP, gsum, part, vpart);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(glmm_fixup_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, G, ncol, gdev + N, (const double*)part, gsum);
     HIP_TRY(hipGetLastError());
     return LRVB_OK;
+}
+
+int launch_glmm_slopes_rows(lrvb_ctx* c, const GlmmLik& lik, int Kz, const double* Z, const double* m, const double* vb, const double* eg,
+                            const double* rg, double* coef, i64 NP, double* gsum, double* part, double* vpart) {
+    return lik.poisson ? gs_launch_rows<PoissonLik>(c, Kz, Z, lik.off, m, vb, eg, rg, coef, NP, gsum, part, vpart)
+                       : gs_launch_rows<LogisticLik>(c, Kz, Z, {lik.gx, lik.gw, lik.n_nodes}, m, vb, eg, rg, coef, NP, gsum, part, vpart);
 }
 int glmm_slopes_ncol(int P, int Kz) { return 2 * Kz + Kz * (2 * Kz + 1) + 4 * Kz * P; }
 
@@ -373,14 +521,14 @@ int launch_glmm_slopes_solve(lrvb_ctx* c, int Kz, bool back, i64 Q, const double
     return LRVB_OK;
 }
 
-// ---- streamed weight influence (lrvb_glmm_slopes_obs_influence) -------------------------------------------
+// ---- streamed weight influence (lrvb_glmm_slopes_obs_influence / lrvb_glmm_poisson_obs_influence) ---------
 // out[n - n0][q] = a1' (x_n . A_m[q] + sum_k z_nk A_e[q, g(n), k]) + a2' ((x_n o x_n) . A_v[q] + sum_k z_nk^2 A_r[q, g(n), k]),
 // a1' = psi_rho - y_n, a2' = psi_s PER UNIT WEIGHT (w_n does not enter).  Built like glmm_infl_rows_kernel (k_glmm.hip): ONE pass
 // over the rows n0..n1 in their original order, X and Z read once for any Q; a workgroup (4 waves) walks tiles of GS_T = 64 rows:
 //   1. the tile (contiguous in X) is staged in LDS, row stride GSI_XS, the row's K values of z behind its x columns (columns
 //      P .. P + K - 1, as glmm_slopes_rows_kernel stages them);
-//   2. four lanes share a row for the two dot products (lane q4 also takes the z column q4) and the quadrature; only E g1 and
-//      E g2 are formed, and a1', a2' go to LDS;
+//   2. four lanes share a row for the two dot products (lane q4 also takes the z column q4) and the likelihood's Lik::infl (the
+//      quadrature: only E g1 and E g2 are formed; or one exp), and a1', a2' go to LDS;
 //   3. wave w owns the rows 16 w .. 16 w + 15.  Per block of 16 outputs the contractions X A_m^T and (X o X) A_v^T run as
 //      16 x 16 x 4 fp64 MFMA tiles, two accumulator chains each, x o x squared in a register.  The B operand is zero past Q and
 //      past P, so the staged z columns (and whatever lies behind them) that the last k-step reads meet zeros;
@@ -406,12 +554,14 @@ constexpr int GSI_XS = 70;
 
 typedef double gsi_d4 __attribute__((ext_vector_type(4)));
 
-// The per-row part both influence kernels share, the sibling of gi_psi_derivs (k_glmm.hip) with the z terms and the column map
-// of GSI_XS: every one of the four lanes of the staged row xr returns e1 = psi_rho and e2 = E g2 = 2 psi_s.  Called by all lanes.
-__device__ __forceinline__ void gsi_psi_derivs(const double* xr, bool live, int g, int q4, int P, int Kz, int nq, const double* ms,
+// The per-row part both influence kernels share, with the z terms and the column map of GSI_XS: every one of the four lanes of the
+// staged row xr returns e1 = psi_rho and e2 = 2 psi_s of the likelihood.  Called by all lanes.
+template <class Lik>
+__device__ __forceinline__ void gsi_psi_derivs(const double* xr, int row, bool live, int g, int q4, int P, int Kz, const double* ms,
                                                const double* vs, const double* __restrict__ eg, const double* __restrict__ rg,
-                                               const double* sx, const double* sw, double& e1, double& e2)
+                                               const typename Lik::Lds& lik, const typename Lik::Args& la, double& e1, double& e2)
 {
+    const double o = Lik::row_shift(lik, row);                          // read ahead of the dot products, which hide its latency
     double rho = 0.0, s = 0.0;
     if (live) {
         for (int h = (q4 & 1) + 16 * (q4 >> 1); h < P; h += 32)
@@ -424,33 +574,23 @@ __device__ __forceinline__ void gsi_psi_derivs(const double* xr, bool live, int 
     }
     rho += __shfl_xor(rho, 1); s += __shfl_xor(s, 1);
     rho += __shfl_xor(rho, 2); s += __shfl_xor(s, 2);
-    e1 = 0.0; e2 = 0.0;
-    if (live) {
-        const double sd = sqrt(fmax(s, 0.0));
-        for (int k = q4; k < nq; k += 4) {
-            const double t = rho + sd * sx[k], wk = sw[k];
-            const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
-            const double sg = t >= 0.0 ? ie : e * ie;
-            e1 += wk * sg; e2 += wk * e * ie * ie;
-        }
-    }
-    e1 += __shfl_xor(e1, 1); e2 += __shfl_xor(e2, 1);
-    e1 += __shfl_xor(e1, 2); e2 += __shfl_xor(e2, 2);
+    Lik::infl(lik, la, o, live, q4, rho, s, e1, e2);
 }
 
-__global__ __launch_bounds__(256)
-void glmm_slopes_infl_rows_kernel(i64 n0, i64 R /* rows of the window */, int P, int Kz, const double* __restrict__ X,
-                                  const double* __restrict__ Z, const double* __restrict__ y, const int* __restrict__ gid,
-                                  const double* __restrict__ m, const double* __restrict__ vb, const double* __restrict__ eg,
-                                  const double* __restrict__ rg, const double* __restrict__ gx, const double* __restrict__ gw, int nq,
-                                  const double* __restrict__ Ag /* Q x 2 P */, const double* __restrict__ Al /* G x 2 K x Q */, int Q,
-                                  double* __restrict__ out /* R x Q */)
+template <class Lik>
+__device__ __forceinline__
+void gsi_infl_rows(i64 n0, i64 R /* rows of the window */, int P, int Kz, const double* __restrict__ X,
+                   const double* __restrict__ Z, const double* __restrict__ y, const int* __restrict__ gid,
+                   const double* __restrict__ m, const double* __restrict__ vb, const double* __restrict__ eg,
+                   const double* __restrict__ rg, typename Lik::Args la,
+                   const double* __restrict__ Ag /* Q x 2 P */, const double* __restrict__ Al /* G x 2 K x Q */, int Q,
+                   double* __restrict__ out /* R x Q */)
 {
-    __shared__ double xs[GS_T * GSI_XS], a1s[GS_T], a2s[GS_T], ms[64], vs[64], sx[128], sw[128];
+    __shared__ double xs[GS_T * GSI_XS], a1s[GS_T], a2s[GS_T], ms[64], vs[64];
+    __shared__ typename Lik::Lds lik;
     __shared__ int s_gid[GS_T];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, l4 = lane >> 4;
-    const double r2 = 1.4142135623730951, ispi = 0.5641895835477563;     // sqrt(2), 1 / sqrt(pi)
-    if (tid < nq) { sx[tid] = r2 * gx[tid]; sw[tid] = ispi * gw[tid]; }
+    Lik::init(lik, la, tid);
     if (tid < 64) { ms[tid] = tid < P ? m[tid] : 0.0; vs[tid] = tid < P ? vb[tid] : 0.0; }
     for (int e = tid; e < GS_T * GSI_XS; e += 256) xs[e] = 0.0;          // what no tile writes stays zero (finite) for the whole kernel
     const int KS = (P + 3) >> 2;                                         // k-steps of the contractions
@@ -473,8 +613,11 @@ void glmm_slopes_infl_rows_kernel(i64 n0, i64 R /* rows of the window */, int P,
     for (i64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const i64 t0 = tile * GS_T;
         const int rows = (int)(R - t0 < GS_T ? R - t0 : GS_T);
-        __syncthreads();                                                 // the previous tile is consumed (and the nodes are in place)
-        if (tid < GS_T) s_gid[tid] = tid < rows ? gid[n0 + t0 + tid] : 0;
+        __syncthreads();                                                 // the previous tile is consumed (and the nodes, m, v are in place)
+        if (tid < GS_T) {
+            s_gid[tid] = tid < rows ? gid[n0 + t0 + tid] : 0;
+            Lik::stage_row(lik, la, tid, tid < rows, n0 + t0 + tid);
+        }
         {
             const double* src = X + (n0 + t0) * (i64)P;
             for (int e = tid; e < rows * P; e += 256) { const int rr = e / P, cc = e - rr * P; xs[rr * GSI_XS + cc] = src[e]; }
@@ -483,7 +626,7 @@ void glmm_slopes_infl_rows_kernel(i64 n0, i64 R /* rows of the window */, int P,
         }
         __syncthreads();
         double e1, e2;
-        gsi_psi_derivs(xs + row * GSI_XS, row < rows, s_gid[row], q4, P, Kz, nq, ms, vs, eg, rg, sx, sw, e1, e2);
+        gsi_psi_derivs<Lik>(xs + row * GSI_XS, row, row < rows, s_gid[row], q4, P, Kz, ms, vs, eg, rg, lik, la, e1, e2);
         if (q4 == 0) {
             double k1 = 0.0, k2 = 0.0;
             if (row < rows) { k1 = e1 - y[n0 + t0 + row]; k2 = 0.5 * e2; }
@@ -529,42 +672,77 @@ void glmm_slopes_infl_rows_kernel(i64 n0, i64 R /* rows of the window */, int P,
     }
 }
 
-int launch_glmm_slopes_infl_rows(lrvb_ctx* c, int Kz, const double* Z, i64 n0, i64 n1, const int* gid, const double* m, const double* vb,
-                                 const double* eg, const double* rg, const double* gx, const double* gw, int nq, const double* Ag,
-                                 const double* Al, i64 Q, double* out) {
-    if (c->P > 64 || Kz < 1 || Kz > 4 || nq < 1 || nq > 128)
-        LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "logistic mixed model with slopes: P <= 64, 1 <= K <= 4, at most 128 nodes");
+// The two entries of the walk above.  Each has its likelihood's arguments where that likelihood's kernel has always had them (the
+// offset behind Z, the nodes behind rg): with ONE templated signature the Poisson instantiation loaded its kernel arguments and
+// spilled its SGPRs differently and ran 0.7 to 1 % slower than before the merge.
+__global__ __launch_bounds__(256)
+void glmm_slopes_infl_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* __restrict__ X, const double* __restrict__ Z,
+                                  const double* __restrict__ y, const int* __restrict__ gid, const double* __restrict__ m,
+                                  const double* __restrict__ vb, const double* __restrict__ eg, const double* __restrict__ rg,
+                                  const double* __restrict__ gx, const double* __restrict__ gw, int nq, const double* __restrict__ Ag,
+                                  const double* __restrict__ Al, int Q, double* __restrict__ out)
+{
+    gsi_infl_rows<LogisticLik>(n0, R, P, Kz, X, Z, y, gid, m, vb, eg, rg, {gx, gw, nq}, Ag, Al, Q, out);
+}
+
+__global__ __launch_bounds__(256)
+void glmm_poisson_infl_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* __restrict__ X, const double* __restrict__ Z,
+                                   const double* __restrict__ off, const double* __restrict__ y, const int* __restrict__ gid,
+                                   const double* __restrict__ m, const double* __restrict__ vb, const double* __restrict__ eg,
+                                   const double* __restrict__ rg, const double* __restrict__ Ag, const double* __restrict__ Al, int Q,
+                                   double* __restrict__ out)
+{
+    gsi_infl_rows<PoissonLik>(n0, R, P, Kz, X, Z, y, gid, m, vb, eg, rg, off, Ag, Al, Q, out);
+}
+
+template <class Lik>
+static int gs_launch_infl_rows(lrvb_ctx* c, int Kz, const double* Z, typename Lik::Args la, i64 n0, i64 n1, const int* gid, const double* m,
+                               const double* vb, const double* eg, const double* rg, const double* Ag, const double* Al, i64 Q,
+                               double* out) {
+    if (c->P > 64 || Kz < 1 || Kz > 4 || !Lik::args_ok(la)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "%s", Lik::LIMITS);
     const i64 R = n1 - n0;
     if (R <= 0) return LRVB_OK;
     const i64 n_tiles = (R + GS_T - 1) / GS_T;
     const unsigned grid = (unsigned)(n_tiles < 2048 ? n_tiles : 2048);
-    hipLaunchKernelGGL(glmm_slopes_infl_rows_kernel, dim3(grid), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
-                       (const double*)c->y.p, gid, m, vb, eg, rg, gx, gw, nq, Ag, Al, (int)Q, out);
+    if constexpr (std::is_same<Lik, PoissonLik>::value)
+        hipLaunchKernelGGL(glmm_poisson_infl_rows_kernel, dim3(grid), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
+                           (const double*)la, (const double*)c->y.p, gid, m, vb, eg, rg, Ag, Al, (int)Q, out);
+    else
+        hipLaunchKernelGGL(glmm_slopes_infl_rows_kernel, dim3(grid), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
+                           (const double*)c->y.p, gid, m, vb, eg, rg, la.gx, la.gw, la.nq, Ag, Al, (int)Q, out);
     HIP_TRY(hipGetLastError());
     return LRVB_OK;
 }
 
-// ---- group influence (lrvb_glmm_slopes_group_influence) ---------------------------------------------------------------------------
+int launch_glmm_slopes_infl_rows(lrvb_ctx* c, const GlmmLik& lik, int Kz, const double* Z, i64 n0, i64 n1, const int* gid, const double* m,
+                                 const double* vb, const double* eg, const double* rg, const double* Ag, const double* Al, i64 Q,
+                                 double* out) {
+    return lik.poisson ? gs_launch_infl_rows<PoissonLik>(c, Kz, Z, lik.off, n0, n1, gid, m, vb, eg, rg, Ag, Al, Q, out)
+                       : gs_launch_infl_rows<LogisticLik>(c, Kz, Z, {lik.gx, lik.gw, lik.n_nodes}, n0, n1, gid, m, vb, eg, rg, Ag, Al, Q, out);
+}
+
+// ---- group influence (lrvb_glmm_slopes_group_influence / lrvb_glmm_poisson_group_influence) --------------------------------------
 // Per group the WEIGHTED sums  [sum a1 z (K) | sum a2 z o z (K) | sum a1 x (P) | sum a2 x o x (P)],  a1 = w (psi_rho - y),
-// a2 = w psi_s  (2 K + 2 P columns): glmm_slopes_rows_kernel cut down to them -- group-sorted rows, two quadrature sums, the same
-// in-order walk of the tile (thread t owns column t), the pieces of a cut group in the tile's two partial rows, added by
-// glmm_fixup_kernel in tile order.  The staging and the column map of the dot products are those of the row kernel above.  The
-// contraction with the operand is N-independent: a (G x 2 P) (2 P x Q) product on the library's GEMM and
-// glmm_slopes_infl_local_kernel for the 2 K local columns.  Fixed order everywhere, no atomics.
+// a2 = w psi_s  (2 K + 2 P columns): glmm_slopes_rows_kernel cut down to them -- group-sorted rows, two coefficients from
+// Lik::infl, the same in-order walk of the tile (thread t owns column t), the pieces of a cut group in the tile's two partial
+// rows, added by glmm_fixup_kernel in tile order.  The staging is that of the rows kernel, stride and column map of the dot
+// products those of the row kernel above.  The contraction with the operand is N-independent: a (G x 2 P) (2 P x Q) product on the
+// library's GEMM and glmm_slopes_infl_local_kernel for the 2 K local columns.  Fixed order everywhere, no atomics.
+template <class Lik>
 __global__ __launch_bounds__(256)
 void glmm_slopes_infl_gsum_kernel(i64 N, int P, int Kz, i64 G, const double* __restrict__ X, const double* __restrict__ Z,
                                   const double* __restrict__ y, const double* __restrict__ w, const i64* __restrict__ perm,
                                   const i64* __restrict__ offs, const double* __restrict__ m, const double* __restrict__ vb,
-                                  const double* __restrict__ eg, const double* __restrict__ rg, const double* __restrict__ gx,
-                                  const double* __restrict__ gw, int nq, double* __restrict__ gsum, double* __restrict__ part)
+                                  const double* __restrict__ eg, const double* __restrict__ rg, typename Lik::Args la,
+                                  double* __restrict__ gsum, double* __restrict__ part)
 {
-    __shared__ double xs[GS_T * GSI_XS], cf[2 * GS_T], ms[64], vs[64], sx[128], sw[128];
+    __shared__ double xs[GS_T * GSI_XS], cf[2 * GS_T], ms[64], vs[64];
+    __shared__ typename Lik::Lds lik;
     __shared__ i64 s_row[GS_T];
     __shared__ int s_gid[GS_T], s_whole[GS_T];
     const int tid = threadIdx.x;
     const int K2 = 2 * Kz, ncol = K2 + 2 * P;
-    const double r2 = 1.4142135623730951, ispi = 0.5641895835477563;
-    if (tid < nq) { sx[tid] = r2 * gx[tid]; sw[tid] = ispi * gw[tid]; }
+    Lik::init(lik, la, tid);
     if (tid < P) { ms[tid] = m[tid]; vs[tid] = vb[tid]; }
     const i64 n_tiles = (N + GS_T - 1) / GS_T;
     const int row = tid >> 2, q4 = tid & 3;
@@ -576,25 +754,9 @@ void glmm_slopes_infl_gsum_kernel(i64 N, int P, int Kz, i64 G, const double* __r
         const i64 t0 = tile * GS_T;
         const int rows = (int)(N - t0 < GS_T ? N - t0 : GS_T);
         __syncthreads();
-        if (tid < GS_T) {
-            int g = 0, whole = 0;
-            i64 pr = 0;
-            if (tid < rows) {
-                const i64 i = t0 + tid;
-                pr = perm[i];
-                i64 lo = 0, hi = G;                                      // the last g with offs[g] <= i (its offs[g + 1] > i)
-                while (hi - lo > 1) { const i64 mid = (lo + hi) >> 1; if (offs[mid] <= i) lo = mid; else hi = mid; }
-                g = (int)lo;
-                whole = (offs[lo] >= t0 && offs[lo + 1] <= t0 + GS_T) ? 1 : 0;
-            }
-            s_row[tid] = pr; s_gid[tid] = g; s_whole[tid] = whole;
-        }
-        __syncthreads();
-        for (int e = tid; e < rows * P; e += 256) { const int rr = e / P, cc = e - rr * P; xs[rr * GSI_XS + cc] = X[s_row[rr] * P + cc]; }
-        for (int e = tid; e < rows * Kz; e += 256) { const int rr = e / Kz, cc = e - rr * Kz; xs[rr * GSI_XS + P + cc] = Z[s_row[rr] * Kz + cc]; }
-        __syncthreads();
+        gs_stage_sorted_tile<Lik, GSI_XS>(tid, t0, rows, P, Kz, G, X, Z, perm, offs, la, lik, xs, s_row, s_gid, s_whole);
         double e1, e2;
-        gsi_psi_derivs(xs + row * GSI_XS, row < rows, s_gid[row], q4, P, Kz, nq, ms, vs, eg, rg, sx, sw, e1, e2);
+        gsi_psi_derivs<Lik>(xs + row * GSI_XS, row, row < rows, s_gid[row], q4, P, Kz, ms, vs, eg, rg, lik, la, e1, e2);
         if (q4 == 0) {
             double k1 = 0.0, k2 = 0.0;
             if (row < rows) { const i64 pr = s_row[row]; const double wi = w[pr]; k1 = wi * (e1 - y[pr]); k2 = wi * 0.5 * e2; }
@@ -610,8 +772,7 @@ void glmm_slopes_infl_gsum_kernel(i64 N, int P, int Kz, i64 G, const double* __r
                 acc += cf[(sq ? GS_T : 0) + rr] * x;
                 const int g = s_gid[rr];
                 if (rr == rows - 1 || s_gid[rr + 1] != g) {
-                    double* dst = s_whole[rr] ? gsum + (i64)g * ncol : part + (tile * 2 + (run_start == 0 ? 0 : 1)) * ncol;
-                    dst[tid] = acc;
+                    gs_flush_dst(s_whole[rr], g, tile, run_start, ncol, gsum, part)[tid] = acc;
                     acc = 0.0; run_start = rr + 1;
                 }
             }
@@ -635,27 +796,52 @@ void glmm_slopes_infl_local_kernel(i64 G, int Q, int K2, int ncol, const double*
     out[i] += acc;
 }
 
-int launch_glmm_slopes_infl_gsum(lrvb_ctx* c, int Kz, const double* Z, const double* m, const double* vb, const double* eg,
-                                 const double* rg, const double* gx, const double* gw, int nq, double* gsum, double* part) {
+
+template <class Lik>
+static int gs_launch_infl_gsum(lrvb_ctx* c, int Kz, const double* Z, typename Lik::Args la, const double* m, const double* vb,
+                               const double* eg, const double* rg, double* gsum, double* part) {
     const i64 N = c->N, G = c->n_groups;
-    if (c->P > 64 || Kz < 1 || Kz > 4 || nq < 1 || nq > 128)
-        LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "logistic mixed model with slopes: P <= 64, 1 <= K <= 4, at most 128 nodes");
+    if (c->P > 64 || Kz < 1 || Kz > 4 || !Lik::args_ok(la)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "%s", Lik::LIMITS);
     const int ncol = 2 * Kz + 2 * (int)c->P;
     const i64* gdev = reinterpret_cast<const i64*>(c->groups.p);
     const i64 n_tiles = glmm_num_tiles(N);
     const unsigned grid = (unsigned)(n_tiles < 2048 ? (n_tiles < 1 ? 1 : n_tiles) : 2048);
-    hipLaunchKernelGGL(glmm_slopes_infl_gsum_kernel, dim3(grid), dim3(256), 0, c->stream, N, (int)c->P, Kz, G, (const double*)c->X.p, Z,
-                       (const double*)c->y.p, (const double*)c->w.p, gdev, gdev + N, m, vb, eg, rg, gx, gw, nq, gsum, part);
+    hipLaunchKernelGGL(glmm_slopes_infl_gsum_kernel<Lik>, dim3(grid), dim3(256), 0, c->stream, N, (int)c->P, Kz, G, (const double*)c->X.p, Z,
+                       (const double*)c->y.p, (const double*)c->w.p, gdev, gdev + N, m, vb, eg, rg, la, gsum, part);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(glmm_fixup_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, G, ncol, gdev + N, (const double*)part, gsum);
     HIP_TRY(hipGetLastError());
     return LRVB_OK;
 }
 
+int launch_glmm_slopes_infl_gsum(lrvb_ctx* c, const GlmmLik& lik, int Kz, const double* Z, const double* m, const double* vb,
+                                 const double* eg, const double* rg, double* gsum, double* part) {
+    return lik.poisson ? gs_launch_infl_gsum<PoissonLik>(c, Kz, Z, lik.off, m, vb, eg, rg, gsum, part)
+                       : gs_launch_infl_gsum<LogisticLik>(c, Kz, Z, {lik.gx, lik.gw, lik.n_nodes}, m, vb, eg, rg, gsum, part);
+}
+
 int launch_glmm_slopes_infl_local(lrvb_ctx* c, int Kz, i64 Q, const double* S, const double* Al, double* out) {
     const i64 G = c->n_groups, n = G * Q;
     hipLaunchKernelGGL(glmm_slopes_infl_local_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, G, (int)Q, 2 * Kz,
                        2 * Kz + 2 * (int)c->P, S, Al, out);
+    HIP_TRY(hipGetLastError());
+    return LRVB_OK;
+}
+
+
+// The three global blocks of the Poisson model were all formed with the one coefficient vector h: [X^T h X | X^T h X2 | X2^T h X2].
+// c12 = h / 2 and c22 = h / 4: the second and third block take their factor here (exact).
+__global__ void glmm_poisson_scale_blocks_kernel(i64 PP, double* __restrict__ Hb)
+{
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= PP) return;
+    Hb[PP + i] *= 0.5;
+    Hb[2 * PP + i] *= 0.25;
+}
+
+int launch_glmm_poisson_scale_blocks(lrvb_ctx* c, double* Hb) {
+    const i64 PP = c->P * c->P;
+    hipLaunchKernelGGL(glmm_poisson_scale_blocks_kernel, dim3((unsigned)((PP + 255) / 256)), dim3(256), 0, c->stream, PP, Hb);
     HIP_TRY(hipGetLastError());
     return LRVB_OK;
 }

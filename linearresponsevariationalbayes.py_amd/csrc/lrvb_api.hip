@@ -2674,16 +2674,19 @@ extern "C" int lrvb_set_group_design(lrvb_ctx* c, const double* z, int64_t n, in
     return LRVB_OK;
 }
 
-// c->glmms: [H blocks (3 P^2) | group sums (G x ncol) | gradient (2 P) | value], adjacent as in lrvb_glmm_terms.  c->work1:
-// [nodes 256 | m, v (2 up(P)) | e, r (2 up(G K)) | five coefficient vectors (5 NP, original order, zero past N) | tile partials]
-extern "C" int lrvb_glmm_slopes_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
-                                      const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
-                                      double* value_out, double* grad_global_out, double* H_blocks_out, double* group_sums_out,
-                                      int32_t want_border) {
-    LRVB_TRY(ctx_bind(c));
-    if (!mean || !var || !e_loc || !r_loc || !gh_x || !gh_w || !value_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
-    if (n_nodes < 1 || n_nodes > 128) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 128 quadrature nodes");
-    if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the logistic mixed model needs P <= 64 (got %lld)", (long long)c->P);
+// ---- the host layer the logistic and the Poisson K-effect model share --------------------------------------
+// An entry hands over its likelihood as a GlmmLik: the logistic ones with the caller's (host) nodes, the Poisson ones with
+// nothing -- the bodies below replace the node pointers by the uploaded copies, or fill in the resident offset.
+static GlmmLik glmms_logistic(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{false, gh_x, gh_w, (int)n_nodes, nullptr}; }
+static GlmmLik glmms_poisson() { return GlmmLik{true, nullptr, nullptr, 0, nullptr}; }
+
+// The argument and state checks of all six entries, in one order (`other_null`: a required pointer of the entry's own is null).
+static int glmms_check(lrvb_ctx* c, const GlmmLik& lik, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                       const double* r_loc, int64_t G_in, int64_t K, bool other_null) {
+    if (!mean || !var || !e_loc || !r_loc || (!lik.poisson && (!lik.gx || !lik.gw)) || other_null) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    if (!lik.poisson && (lik.n_nodes < 1 || lik.n_nodes > 128)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 128 quadrature nodes");
+    if (c->P > 64)
+        LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the %s mixed model needs P <= 64 (got %lld)", lik.poisson ? "Poisson" : "logistic", (long long)c->P);
     if (K < 1 || K > 4) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 4 random effects per group (got %lld)", (long long)K);
     if (c->loss == LRVB_LOSS_NONE || c->data_only || !(c->have_X && c->have_y))
         LRVB_FAIL(LRVB_ERR_STATE, "the context needs a design matrix and responses: lrvb_set_data for LRVB_SLOT_X and LRVB_SLOT_Y");
@@ -2691,11 +2694,32 @@ extern "C" int lrvb_glmm_slopes_terms(lrvb_ctx* c, const double* mean, const dou
     if (c->gz_K <= 0) LRVB_FAIL(LRVB_ERR_STATE, "no group design: call lrvb_set_group_design first");
     if (c->gz_n != c->N || c->gz_K != K)
         LRVB_FAIL(LRVB_ERR_STATE, "the group design is %lld x %d, the model needs %lld x %lld", (long long)c->gz_n, c->gz_K, (long long)c->N, (long long)K);
+    if (lik.poisson && c->goff_n != 0 && c->goff_n != c->N)
+        LRVB_FAIL(LRVB_ERR_STATE, "the offset has %lld entries, the model has %lld observations", (long long)c->goff_n, (long long)c->N);
+    LRVB_TRY(check_len(P_in, c->P, "mean / var"));
+    LRVB_TRY(check_len(G_in, c->n_groups, "groups of e / r"));
+    for (i64 j = 0; j < c->P; ++j) if (!(var[j] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "var[%lld] is not positive", (long long)j);
+    for (i64 g = 0; g < c->n_groups * K; ++g) if (!(r_loc[g] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "r[%lld] is not positive", (long long)g);
+    return LRVB_OK;
+}
+
+// The likelihood as the kernels read it: the nodes uploaded behind `g` (256 doubles: x | w), or the resident offset.
+static int glmms_to_device(lrvb_ctx* c, GlmmLik& lik, double* g) {
+    if (lik.poisson) { lik.off = c->goff_n ? c->goff.p : nullptr; return LRVB_OK; }
+    LRVB_TRY(h2d(c, g, lik.gx, (size_t)lik.n_nodes));
+    LRVB_TRY(h2d(c, g + 128, lik.gw, (size_t)lik.n_nodes));
+    lik.gx = g; lik.gw = g + 128;
+    return LRVB_OK;
+}
+
+// c->glmms: [H blocks (3 P^2) | group sums (G x ncol) | gradient (2 P) | value], adjacent as in lrvb_glmm_terms.  c->work1:
+// [nodes 256 (logistic only) | m, v (2 up(P)) | e, r (2 up(G K)) | the coefficient vectors (original order, zero past N): five,
+// a1 a2 c11 c12 c22 (5 NP), or the Poisson model's two, a1 and h (2 NP) | tile partials]
+static int glmms_terms(lrvb_ctx* c, GlmmLik lik, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                       const double* r_loc, int64_t G_in, int64_t K, double* value_out, double* grad_global_out, double* H_blocks_out,
+                       double* group_sums_out, int32_t want_border) {
+    LRVB_TRY(glmms_check(c, lik, mean, var, P_in, e_loc, r_loc, G_in, K, !value_out));
     const i64 N = c->N, P = c->P, G = c->n_groups, ncol = glmm_slopes_ncol((int)P, (int)K), nsc = ncol - 4 * K * P;
-    LRVB_TRY(check_len(P_in, P, "mean / var"));
-    LRVB_TRY(check_len(G_in, G, "groups of e / r"));
-    for (i64 j = 0; j < P; ++j) if (!(var[j] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "var[%lld] is not positive", (long long)j);
-    for (i64 g = 0; g < G * K; ++g) if (!(r_loc[g] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "r[%lld] is not positive", (long long)g);
     c->glmms_drop();
     const bool want_g = grad_global_out != nullptr, want_H = H_blocks_out != nullptr;
     DevBuf& X2 = c->mx_Xk;
@@ -2705,36 +2729,42 @@ extern "C" int lrvb_glmm_slopes_terms(lrvb_ctx* c, const double* mean, const dou
         c->x2_ready = true;
     }
     auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
-    const i64 NP = up(N + 64), n_tiles = glmm_num_tiles(N), GK = G * K;
-    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(256 + 2 * up(P) + 2 * up(GK) + 5 * NP + n_tiles * 2 * ncol + n_tiles)));
+    const i64 NP = up(N + 64), n_tiles = glmm_num_tiles(N), GK = G * K, ncf = lik.poisson ? 2 : 5, nodes = lik.poisson ? 0 : 256;
+    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(nodes + 2 * up(P) + 2 * up(GK) + ncf * NP + n_tiles * 2 * ncol + n_tiles)));
     LRVB_TRY(buf_reserve(c, c->glmms, (size_t)(3 * P * P + G * ncol + 2 * P + 1)));
-    double* g = c->work1.p; double* dm = g + 256; double* dv = dm + up(P); double* de = dv + up(P); double* dr = de + up(GK);
-    double* coef = dr + up(GK); double* part = coef + 5 * NP; double* vpart = part + n_tiles * 2 * ncol;
+    double* g = c->work1.p; double* dm = g + nodes; double* dv = dm + up(P); double* de = dv + up(P); double* dr = de + up(GK);
+    double* coef = dr + up(GK); double* part = coef + ncf * NP; double* vpart = part + n_tiles * 2 * ncol;
     double* Hb = c->glmms.p; double* gsum = Hb + 3 * P * P; double* gred = gsum + G * ncol; double* vred = gred + 2 * P;
-    LRVB_TRY(h2d(c, g, gh_x, (size_t)n_nodes));
-    LRVB_TRY(h2d(c, g + 128, gh_w, (size_t)n_nodes));
+    LRVB_TRY(glmms_to_device(c, lik, g));
     LRVB_TRY(h2d(c, dm, mean, (size_t)P));
     LRVB_TRY(h2d(c, dv, var, (size_t)P));
     LRVB_TRY(h2d(c, de, e_loc, (size_t)GK));
     LRVB_TRY(h2d(c, dr, r_loc, (size_t)GK));
-    HIP_TRY(hipMemsetAsync(coef, 0, (size_t)(5 * NP) * sizeof(double), c->stream));
+    HIP_TRY(hipMemsetAsync(coef, 0, (size_t)(ncf * NP) * sizeof(double), c->stream));
     HIP_TRY(hipMemsetAsync(gsum, 0, (size_t)(G * ncol + 2 * P + 1) * sizeof(double), c->stream));
-    LRVB_TRY(launch_glmm_slopes_rows(c, (int)K, c->gz.p, dm, dv, de, dr, g, g + 128, (int)n_nodes, coef, NP, gsum, part, vpart));
+    LRVB_TRY(launch_glmm_slopes_rows(c, lik, (int)K, c->gz.p, dm, dv, de, dr, coef, NP, gsum, part, vpart));
     hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, c->stream, (const double*)vpart, n_tiles, vred);
     HIP_TRY(hipGetLastError());
+    // Poisson: a2 = h / 2 (the factor rides on the product), c11 = h, c12 = h / 2, c22 = h / 4 (one vector, the blocks scaled after)
+    const double* a2 = coef + NP;
+    const double* c11 = lik.poisson ? a2 : coef + 2 * NP; const double* c12 = lik.poisson ? a2 : coef + 3 * NP;
+    const double* c22 = lik.poisson ? a2 : coef + 4 * NP;
     if (want_g) {
         LRVB_TRY(launch_gemv(c, true, N, P, 1.0, c->X.p, P, coef, 0.0, gred));
-        LRVB_TRY(launch_gemv(c, true, N, P, 1.0, X2.p, P, coef + NP, 0.0, gred + P));
+        LRVB_TRY(launch_gemv(c, true, N, P, lik.poisson ? 0.5 : 1.0, X2.p, P, a2, 0.0, gred + P));
     }
     if (want_H) {
-        LRVB_TRY(weighted_tn(c, c->X.p, c->X.p, P, N, coef + 2 * NP, Hb, c->mx_A));
-        LRVB_TRY(weighted_tn(c, c->X.p, X2.p, P, N, coef + 3 * NP, Hb + P * P, c->mx_A));
-        LRVB_TRY(weighted_tn(c, X2.p, X2.p, P, N, coef + 4 * NP, Hb + 2 * P * P, c->mx_A));
+        LRVB_TRY(weighted_tn(c, c->X.p, c->X.p, P, N, c11, Hb, c->mx_A));
+        LRVB_TRY(weighted_tn(c, c->X.p, X2.p, P, N, c12, Hb + P * P, c->mx_A));
+        LRVB_TRY(weighted_tn(c, X2.p, X2.p, P, N, c22, Hb + 2 * P * P, c->mx_A));
+        if (lik.poisson) LRVB_TRY(launch_glmm_poisson_scale_blocks(c, Hb));
     }
     double* first = want_H ? Hb : gsum;
     LRVB_TRY(obs_reduce(c, first, (i64)(vred + 1 - first)));
-    c->glmms_valid = true; c->glmms_K = (int)K;
     LRVB_TRY(d2h(c, value_out, vred, 1));
+    if (lik.poisson && !std::isfinite(*value_out))
+        LRVB_FAIL(LRVB_ERR_INVALID, "the Poisson data term is not finite at this point: exp(rho + s / 2) overflows for some row (the kernel does not clamp)");
+    c->glmms_valid = true; c->glmms_K = (int)K;
     if (want_g) LRVB_TRY(d2h(c, grad_global_out, gred, (size_t)(2 * P)));
     if (want_H) LRVB_TRY(d2h(c, H_blocks_out, Hb, (size_t)(3 * P * P)));
     if (group_sums_out) {
@@ -2746,6 +2776,15 @@ extern "C" int lrvb_glmm_slopes_terms(lrvb_ctx* c, const double* mean, const dou
         }
     }
     return LRVB_OK;
+}
+
+extern "C" int lrvb_glmm_slopes_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                      const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
+                                      double* value_out, double* grad_global_out, double* H_blocks_out, double* group_sums_out,
+                                      int32_t want_border) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_terms(c, glmms_logistic(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, value_out, grad_global_out,
+                       H_blocks_out, group_sums_out, want_border);
 }
 
 extern "C" int lrvb_glmm_slopes_schur(lrvb_ctx* c, const double* local_blocks, const double* border_scale, const double* closed_rows,
@@ -2895,35 +2934,20 @@ extern "C" int lrvb_glmm_group_influence(lrvb_ctx* c, const double* mean, const 
     return d2h(c, out, od, (size_t)(G * Q));
 }
 
-// ---- weight influence of the logistic mixed model with slopes (k_glmm_slopes.hip) -------------------------------------------------
-// The checks of lrvb_glmm_slopes_terms, in its order, then the operand.  c->work1 holds
-//   [nodes 256 | m, v (2 up(P)) | e, r (2 up(G K)) | A_global (Q x 2 P) | A_local (G x 2 K x Q) | call-specific scratch]
-static int glmm_slopes_infl_setup(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
-                                  const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
-                                  const double* A_global, const double* A_local, int64_t Q, const void* out, size_t extra,
-                                  GlmmInflBufs& b) {
-    if (!mean || !var || !e_loc || !r_loc || !gh_x || !gh_w || !A_global || !A_local || !out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
-    if (n_nodes < 1 || n_nodes > 128) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 128 quadrature nodes");
-    if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the logistic mixed model needs P <= 64 (got %lld)", (long long)c->P);
-    if (K < 1 || K > 4) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 4 random effects per group (got %lld)", (long long)K);
-    if (c->loss == LRVB_LOSS_NONE || c->data_only || !(c->have_X && c->have_y))
-        LRVB_FAIL(LRVB_ERR_STATE, "the context needs a design matrix and responses: lrvb_set_data for LRVB_SLOT_X and LRVB_SLOT_Y");
-    if (c->n_groups <= 0) LRVB_FAIL(LRVB_ERR_STATE, "no groups: call lrvb_set_groups first");
-    if (c->gz_K <= 0) LRVB_FAIL(LRVB_ERR_STATE, "no group design: call lrvb_set_group_design first");
-    if (c->gz_n != c->N || c->gz_K != K)
-        LRVB_FAIL(LRVB_ERR_STATE, "the group design is %lld x %d, the model needs %lld x %lld", (long long)c->gz_n, c->gz_K, (long long)c->N, (long long)K);
-    const i64 P = c->P, G = c->n_groups, GK = G * K;
-    LRVB_TRY(check_len(P_in, P, "mean / var"));
-    LRVB_TRY(check_len(G_in, G, "groups of e / r"));
-    for (i64 j = 0; j < P; ++j) if (!(var[j] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "var[%lld] is not positive", (long long)j);
-    for (i64 g = 0; g < GK; ++g) if (!(r_loc[g] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "r[%lld] is not positive", (long long)g);
+// ---- weight influence of the two K-effect mixed models (k_glmm_slopes.hip) ---------------------------------------------------------
+// The checks of glmms_terms, in its order, then the operand.  c->work1 holds
+//   [nodes 256 (logistic only) | m, v (2 up(P)) | e, r (2 up(G K)) | A_global (Q x 2 P) | A_local (G x 2 K x Q) | call-specific scratch]
+static int glmms_infl_setup(lrvb_ctx* c, GlmmLik& lik, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                            const double* r_loc, int64_t G_in, int64_t K, const double* A_global, const double* A_local, int64_t Q,
+                            const void* out, size_t extra, GlmmInflBufs& b) {
+    LRVB_TRY(glmms_check(c, lik, mean, var, P_in, e_loc, r_loc, G_in, K, !A_global || !A_local || !out));
     if (Q < 1) LRVB_FAIL(LRVB_ERR_INVALID, "Q must be positive");
+    const i64 P = c->P, GK = c->n_groups * K, nodes = lik.poisson ? 0 : 256;
     auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
-    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(256 + 2 * up(P) + 2 * up(GK) + up(Q * 2 * P) + up(GK * 2 * Q)) + extra));
-    b.g = c->work1.p; b.m = b.g + 256; b.v = b.m + up(P); b.e = b.v + up(P); b.r = b.e + up(GK);
+    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(nodes + 2 * up(P) + 2 * up(GK) + up(Q * 2 * P) + up(GK * 2 * Q)) + extra));
+    b.g = c->work1.p; b.m = b.g + nodes; b.v = b.m + up(P); b.e = b.v + up(P); b.r = b.e + up(GK);
     b.Ag = b.r + up(GK); b.Al = b.Ag + up(Q * 2 * P); b.extra = b.Al + up(GK * 2 * Q);
-    LRVB_TRY(h2d(c, b.g, gh_x, (size_t)n_nodes));
-    LRVB_TRY(h2d(c, b.g + 128, gh_w, (size_t)n_nodes));
+    LRVB_TRY(glmms_to_device(c, lik, b.g));
     LRVB_TRY(h2d(c, b.m, mean, (size_t)P));
     LRVB_TRY(h2d(c, b.v, var, (size_t)P));
     LRVB_TRY(h2d(c, b.e, e_loc, (size_t)GK));
@@ -2933,44 +2957,55 @@ static int glmm_slopes_infl_setup(lrvb_ctx* c, const double* mean, const double*
     return LRVB_OK;
 }
 
-extern "C" int lrvb_glmm_slopes_obs_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
-                                              const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
-                                              int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, int64_t n0,
-                                              int64_t n1, double* out) {
-    LRVB_TRY(ctx_bind(c));
+static int glmms_obs_influence(lrvb_ctx* c, GlmmLik lik, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                               const double* r_loc, int64_t G_in, int64_t K, const double* A_global, const double* A_local, int64_t Q,
+                               int64_t n0, int64_t n1, double* out) {
     GlmmInflBufs b;
-    LRVB_TRY(glmm_slopes_infl_setup(c, mean, var, P_in, e_loc, r_loc, G_in, K, gh_x, gh_w, n_nodes, A_global, A_local, Q, out, 0, b));
+    LRVB_TRY(glmms_infl_setup(c, lik, mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out, 0, b));
     if (n0 < 0 || n1 > c->N || n0 > n1) LRVB_FAIL(LRVB_ERR_INVALID, "row range [%lld, %lld) outside [0, %lld)", (long long)n0, (long long)n1, (long long)c->N);
     const i64 rows = n1 - n0;
     if (rows == 0) return LRVB_OK;
     LRVB_TRY(buf_reserve(c, c->cgT, (size_t)(rows * Q)));
     const i64 NW = (c->N + grouped_rows_per_wave(c->N) - 1) / grouped_rows_per_wave(c->N);
     const int* gid = reinterpret_cast<const int*>(reinterpret_cast<const i64*>(c->groups.p) + c->N + c->n_groups + 1 + NW);
-    LRVB_TRY(launch_glmm_slopes_infl_rows(c, (int)K, c->gz.p, n0, n1, gid, b.m, b.v, b.e, b.r, b.g, b.g + 128, (int)n_nodes, b.Ag, b.Al, Q,
-                                          c->cgT.p));
+    LRVB_TRY(launch_glmm_slopes_infl_rows(c, lik, (int)K, c->gz.p, n0, n1, gid, b.m, b.v, b.e, b.r, b.Ag, b.Al, Q, c->cgT.p));
     return d2h(c, out, c->cgT.p, (size_t)(rows * Q));       // per-observation rows: rank-local, no hook call
 }
 
-extern "C" int lrvb_glmm_slopes_group_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
-                                                const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
-                                                int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, double* out) {
-    LRVB_TRY(ctx_bind(c));
+static int glmms_group_influence(lrvb_ctx* c, GlmmLik lik, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                 const double* r_loc, int64_t G_in, int64_t K, const double* A_global, const double* A_local, int64_t Q,
+                                 double* out) {
     GlmmInflBufs b;
     const i64 Kc = K < 1 ? 1 : (K > 4 ? 4 : K);               // the setup refuses K outside 1..4 before the scratch is used
     const i64 ncol = 2 * Kc + 2 * c->P, n_tiles = glmm_num_tiles(c->N), G = c->n_groups > 0 ? c->n_groups : 0;
     // scratch: [group sums (G x (2 K + 2 P)) | tile partials | out (G x Q)]
     const size_t extra = (size_t)(G * ncol + n_tiles * 2 * ncol + G * (Q > 0 ? Q : 0));
-    LRVB_TRY(glmm_slopes_infl_setup(c, mean, var, P_in, e_loc, r_loc, G_in, K, gh_x, gh_w, n_nodes, A_global, A_local, Q, out, extra, b));
+    LRVB_TRY(glmms_infl_setup(c, lik, mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out, extra, b));
     double* gsum = b.extra; double* part = gsum + G * ncol; double* od = part + n_tiles * 2 * ncol;
     HIP_TRY(hipMemsetAsync(gsum, 0, (size_t)(G * ncol) * sizeof(double), c->stream));       // empty groups keep the zeros
-    LRVB_TRY(launch_glmm_slopes_infl_gsum(c, (int)K, c->gz.p, b.m, b.v, b.e, b.r, b.g, b.g + 128, (int)n_nodes, gsum, part));
+    LRVB_TRY(launch_glmm_slopes_infl_gsum(c, lik, (int)K, c->gz.p, b.m, b.v, b.e, b.r, gsum, part));
     LRVB_TRY(launch_gemm(c, false, true, G, Q, 2 * c->P, 1.0, gsum + 2 * K, ncol, b.Ag, 2 * c->P, 0.0, od, Q));
     LRVB_TRY(launch_glmm_slopes_infl_local(c, (int)K, Q, gsum, b.Al, od));
     LRVB_TRY(obs_reduce(c, od, G * Q));                       // a sum over observations; a group may straddle ranks
     return d2h(c, out, od, (size_t)(G * Q));
 }
 
-// ---- Poisson mixed model with K <= 4 random effects per group (k_glmm_poisson.hip) -------------------------
+extern "C" int lrvb_glmm_slopes_obs_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                              const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                              int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, int64_t n0,
+                                              int64_t n1, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_obs_influence(c, glmms_logistic(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, n0, n1, out);
+}
+
+extern "C" int lrvb_glmm_slopes_group_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                                const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                                int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_group_influence(c, glmms_logistic(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out);
+}
+
+// ---- Poisson mixed model with K <= 4 random effects per group (k_glmm_slopes.hip, DESIGN.md sections 26 and 27) ------------------
 extern "C" int lrvb_set_offset(lrvb_ctx* c, const double* offset, int64_t n) {
     LRVB_TRY(ctx_bind(c));
     c->glmms_drop();                                                     // sums formed under another offset are not those of the model
@@ -2984,145 +3019,27 @@ extern "C" int lrvb_set_offset(lrvb_ctx* c, const double* offset, int64_t n) {
     return LRVB_OK;
 }
 
-// The state checks the three Poisson entries share, in the order of lrvb_glmm_slopes_terms, then the offset.
-static int glmm_poisson_check(lrvb_ctx* c, const double* var, int64_t P_in, const double* r_loc, int64_t G_in, int64_t K) {
-    if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the Poisson mixed model needs P <= 64 (got %lld)", (long long)c->P);
-    if (K < 1 || K > 4) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 4 random effects per group (got %lld)", (long long)K);
-    if (c->loss == LRVB_LOSS_NONE || c->data_only || !(c->have_X && c->have_y))
-        LRVB_FAIL(LRVB_ERR_STATE, "the context needs a design matrix and responses: lrvb_set_data for LRVB_SLOT_X and LRVB_SLOT_Y");
-    if (c->n_groups <= 0) LRVB_FAIL(LRVB_ERR_STATE, "no groups: call lrvb_set_groups first");
-    if (c->gz_K <= 0) LRVB_FAIL(LRVB_ERR_STATE, "no group design: call lrvb_set_group_design first");
-    if (c->gz_n != c->N || c->gz_K != K)
-        LRVB_FAIL(LRVB_ERR_STATE, "the group design is %lld x %d, the model needs %lld x %lld", (long long)c->gz_n, c->gz_K, (long long)c->N, (long long)K);
-    if (c->goff_n != 0 && c->goff_n != c->N)
-        LRVB_FAIL(LRVB_ERR_STATE, "the offset has %lld entries, the model has %lld observations", (long long)c->goff_n, (long long)c->N);
-    LRVB_TRY(check_len(P_in, c->P, "mean / var"));
-    LRVB_TRY(check_len(G_in, c->n_groups, "groups of e / r"));
-    for (i64 j = 0; j < c->P; ++j) if (!(var[j] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "var[%lld] is not positive", (long long)j);
-    for (i64 g = 0; g < c->n_groups * K; ++g) if (!(r_loc[g] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "r[%lld] is not positive", (long long)g);
-    return LRVB_OK;
-}
-
-// c->glmms: [H blocks (3 P^2) | group sums (G x ncol) | gradient (2 P) | value], as lrvb_glmm_slopes_terms leaves them.  c->work1:
-// [m, v (2 up(P)) | e, r (2 up(G K)) | two coefficient vectors a1, h (2 NP, original order, zero past N) | tile partials]
+// The three Poisson entries: the shared bodies above with the Poisson likelihood (no nodes; the offset of lrvb_set_offset).
 extern "C" int lrvb_glmm_poisson_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
                                        const double* r_loc, int64_t G_in, int64_t K, double* value_out, double* grad_global_out,
                                        double* H_blocks_out, double* group_sums_out, int32_t want_border) {
     LRVB_TRY(ctx_bind(c));
-    if (!mean || !var || !e_loc || !r_loc || !value_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
-    LRVB_TRY(glmm_poisson_check(c, var, P_in, r_loc, G_in, K));
-    const i64 N = c->N, P = c->P, G = c->n_groups, ncol = glmm_slopes_ncol((int)P, (int)K), nsc = ncol - 4 * K * P;
-    c->glmms_drop();
-    const bool want_g = grad_global_out != nullptr, want_H = H_blocks_out != nullptr;
-    DevBuf& X2 = c->mx_Xk;
-    if ((want_g || want_H) && (!c->x2_ready || X2.n < (size_t)(N * P))) {
-        LRVB_TRY(buf_reserve(c, X2, (size_t)(N * P)));
-        EW(square_kernel, N * P, (const double*)c->X.p, X2.p);
-        c->x2_ready = true;
-    }
-    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
-    const i64 NP = up(N + 64), n_tiles = glmm_num_tiles(N), GK = G * K;
-    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(2 * up(P) + 2 * up(GK) + 2 * NP + n_tiles * 2 * ncol + n_tiles)));
-    LRVB_TRY(buf_reserve(c, c->glmms, (size_t)(3 * P * P + G * ncol + 2 * P + 1)));
-    double* dm = c->work1.p; double* dv = dm + up(P); double* de = dv + up(P); double* dr = de + up(GK);
-    double* coef = dr + up(GK); double* part = coef + 2 * NP; double* vpart = part + n_tiles * 2 * ncol;
-    double* Hb = c->glmms.p; double* gsum = Hb + 3 * P * P; double* gred = gsum + G * ncol; double* vred = gred + 2 * P;
-    LRVB_TRY(h2d(c, dm, mean, (size_t)P));
-    LRVB_TRY(h2d(c, dv, var, (size_t)P));
-    LRVB_TRY(h2d(c, de, e_loc, (size_t)GK));
-    LRVB_TRY(h2d(c, dr, r_loc, (size_t)GK));
-    HIP_TRY(hipMemsetAsync(coef, 0, (size_t)(2 * NP) * sizeof(double), c->stream));
-    HIP_TRY(hipMemsetAsync(gsum, 0, (size_t)(G * ncol + 2 * P + 1) * sizeof(double), c->stream));
-    const double* off = c->goff_n ? c->goff.p : nullptr;
-    LRVB_TRY(launch_glmm_poisson_rows(c, (int)K, c->gz.p, off, dm, dv, de, dr, coef, NP, gsum, part, vpart));
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, c->stream, (const double*)vpart, n_tiles, vred);
-    HIP_TRY(hipGetLastError());
-    if (want_g) {                                                        // a1 = coef[0], a2 = h / 2 = coef[NP] / 2
-        LRVB_TRY(launch_gemv(c, true, N, P, 1.0, c->X.p, P, coef, 0.0, gred));
-        LRVB_TRY(launch_gemv(c, true, N, P, 0.5, X2.p, P, coef + NP, 0.0, gred + P));
-    }
-    if (want_H) {                                                        // c11 = h, c12 = h / 2, c22 = h / 4: one vector, scaled blocks
-        LRVB_TRY(weighted_tn(c, c->X.p, c->X.p, P, N, coef + NP, Hb, c->mx_A));
-        LRVB_TRY(weighted_tn(c, c->X.p, X2.p, P, N, coef + NP, Hb + P * P, c->mx_A));
-        LRVB_TRY(weighted_tn(c, X2.p, X2.p, P, N, coef + NP, Hb + 2 * P * P, c->mx_A));
-        LRVB_TRY(launch_glmm_poisson_scale_blocks(c, Hb));
-    }
-    double* first = want_H ? Hb : gsum;
-    LRVB_TRY(obs_reduce(c, first, (i64)(vred + 1 - first)));
-    LRVB_TRY(d2h(c, value_out, vred, 1));
-    if (!std::isfinite(*value_out))
-        LRVB_FAIL(LRVB_ERR_INVALID, "the Poisson data term is not finite at this point: exp(rho + s / 2) overflows for some row (the kernel does not clamp)");
-    c->glmms_valid = true; c->glmms_K = (int)K;
-    if (want_g) LRVB_TRY(d2h(c, grad_global_out, gred, (size_t)(2 * P)));
-    if (want_H) LRVB_TRY(d2h(c, H_blocks_out, Hb, (size_t)(3 * P * P)));
-    if (group_sums_out) {
-        if (want_border) LRVB_TRY(d2h(c, group_sums_out, gsum, (size_t)(G * ncol)));
-        else {                                                           // the scalar columns of every group; the border stays
-            HIP_TRY(hipMemcpy2DAsync(group_sums_out, (size_t)nsc * sizeof(double), gsum, (size_t)ncol * sizeof(double),
-                                     (size_t)nsc * sizeof(double), (size_t)G, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-        }
-    }
-    return LRVB_OK;
-}
-
-// ---- weight influence of the Poisson mixed model -------------------------------------------------------------------------------------
-// c->work1 holds [m, v (2 up(P)) | e, r (2 up(G K)) | A_global (Q x 2 P) | A_local (G x 2 K x Q) | call-specific scratch]
-static int glmm_poisson_infl_setup(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
-                                   const double* r_loc, int64_t G_in, int64_t K, const double* A_global, const double* A_local,
-                                   int64_t Q, const void* out, size_t extra, GlmmInflBufs& b) {
-    if (!mean || !var || !e_loc || !r_loc || !A_global || !A_local || !out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
-    LRVB_TRY(glmm_poisson_check(c, var, P_in, r_loc, G_in, K));
-    if (Q < 1) LRVB_FAIL(LRVB_ERR_INVALID, "Q must be positive");
-    const i64 P = c->P, GK = c->n_groups * K;
-    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
-    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(2 * up(P) + 2 * up(GK) + up(Q * 2 * P) + up(GK * 2 * Q)) + extra));
-    b.g = nullptr; b.m = c->work1.p; b.v = b.m + up(P); b.e = b.v + up(P); b.r = b.e + up(GK);
-    b.Ag = b.r + up(GK); b.Al = b.Ag + up(Q * 2 * P); b.extra = b.Al + up(GK * 2 * Q);
-    LRVB_TRY(h2d(c, b.m, mean, (size_t)P));
-    LRVB_TRY(h2d(c, b.v, var, (size_t)P));
-    LRVB_TRY(h2d(c, b.e, e_loc, (size_t)GK));
-    LRVB_TRY(h2d(c, b.r, r_loc, (size_t)GK));
-    LRVB_TRY(h2d(c, b.Ag, A_global, (size_t)(Q * 2 * P)));
-    LRVB_TRY(h2d(c, b.Al, A_local, (size_t)(GK * 2 * Q)));
-    return LRVB_OK;
+    return glmms_terms(c, glmms_poisson(), mean, var, P_in, e_loc, r_loc, G_in, K, value_out, grad_global_out, H_blocks_out,
+                       group_sums_out, want_border);
 }
 
 extern "C" int lrvb_glmm_poisson_obs_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
                                                const double* r_loc, int64_t G_in, int64_t K, const double* A_global,
                                                const double* A_local, int64_t Q, int64_t n0, int64_t n1, double* out) {
     LRVB_TRY(ctx_bind(c));
-    GlmmInflBufs b;
-    LRVB_TRY(glmm_poisson_infl_setup(c, mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out, 0, b));
-    if (n0 < 0 || n1 > c->N || n0 > n1) LRVB_FAIL(LRVB_ERR_INVALID, "row range [%lld, %lld) outside [0, %lld)", (long long)n0, (long long)n1, (long long)c->N);
-    const i64 rows = n1 - n0;
-    if (rows == 0) return LRVB_OK;
-    LRVB_TRY(buf_reserve(c, c->cgT, (size_t)(rows * Q)));
-    const i64 NW = (c->N + grouped_rows_per_wave(c->N) - 1) / grouped_rows_per_wave(c->N);
-    const int* gid = reinterpret_cast<const int*>(reinterpret_cast<const i64*>(c->groups.p) + c->N + c->n_groups + 1 + NW);
-    const double* off = c->goff_n ? c->goff.p : nullptr;
-    LRVB_TRY(launch_glmm_poisson_infl_rows(c, (int)K, c->gz.p, off, n0, n1, gid, b.m, b.v, b.e, b.r, b.Ag, b.Al, Q, c->cgT.p));
-    return d2h(c, out, c->cgT.p, (size_t)(rows * Q));       // per-observation rows: rank-local, no hook call
+    return glmms_obs_influence(c, glmms_poisson(), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, n0, n1, out);
 }
 
 extern "C" int lrvb_glmm_poisson_group_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
                                                  const double* r_loc, int64_t G_in, int64_t K, const double* A_global,
                                                  const double* A_local, int64_t Q, double* out) {
     LRVB_TRY(ctx_bind(c));
-    GlmmInflBufs b;
-    const i64 Kc = K < 1 ? 1 : (K > 4 ? 4 : K);               // the setup refuses K outside 1..4 before the scratch is used
-    const i64 ncol = 2 * Kc + 2 * c->P, n_tiles = glmm_num_tiles(c->N), G = c->n_groups > 0 ? c->n_groups : 0;
-    // scratch: [group sums (G x (2 K + 2 P)) | tile partials | out (G x Q)]
-    const size_t extra = (size_t)(G * ncol + n_tiles * 2 * ncol + G * (Q > 0 ? Q : 0));
-    LRVB_TRY(glmm_poisson_infl_setup(c, mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out, extra, b));
-    double* gsum = b.extra; double* part = gsum + G * ncol; double* od = part + n_tiles * 2 * ncol;
-    HIP_TRY(hipMemsetAsync(gsum, 0, (size_t)(G * ncol) * sizeof(double), c->stream));       // empty groups keep the zeros
-    const double* off = c->goff_n ? c->goff.p : nullptr;
-    LRVB_TRY(launch_glmm_poisson_infl_gsum(c, (int)K, c->gz.p, off, b.m, b.v, b.e, b.r, gsum, part));
-    LRVB_TRY(launch_gemm(c, false, true, G, Q, 2 * c->P, 1.0, gsum + 2 * K, ncol, b.Ag, 2 * c->P, 0.0, od, Q));
-    LRVB_TRY(launch_glmm_slopes_infl_local(c, (int)K, Q, gsum, b.Al, od));
-    LRVB_TRY(obs_reduce(c, od, G * Q));                       // a sum over observations; a group may straddle ranks
-    return d2h(c, out, od, (size_t)(G * Q));
+    return glmms_group_influence(c, glmms_poisson(), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out);
 }
 
 // ---- logistic regression with a full-covariance Gaussian posterior q(beta) = N(m, Sigma) ----------------------------------

@@ -136,7 +136,7 @@ struct lrvb_ctx {
     // U (2 K G x ld(R))] of glmms_fac_K effects, and T = L^-1 R_local (2 K G x glmms_T_Q; 0 = no forward pass yet)
     DevBuf glmms_fac, glmms_T; bool glmms_fac_valid = false; int glmms_fac_K = 0; i64 glmms_T_Q = 0;
     void glmms_drop() { glmms_valid = false; glmms_fac_valid = false; glmms_T_Q = 0; }
-    // lrvb_glmm_poisson_* (k_glmm_poisson.hip): the per-row offset (log exposure) of lrvb_set_offset, goff_n doubles (0 = none:
+    // lrvb_glmm_poisson_* (k_glmm_slopes.hip): the per-row offset (log exposure) of lrvb_set_offset, goff_n doubles (0 = none:
     // the offset is zero).  The Poisson entries leave their sums in `glmms` as lrvb_glmm_slopes_terms does; no other entry reads it
     DevBuf goff; i64 goff_n = 0;
     DevBuf opt;                    // trust-region Newton-CG: 12 D-vectors (+ the D x D preconditioner)
@@ -247,41 +247,30 @@ int  launch_glmm_infl_gsum(lrvb_ctx* c, const double* m, const double* vb, const
                            double* part /* 2 (2 + 2 P) doubles per tile of glmm_num_tiles */);
 int  launch_glmm_infl_local(lrvb_ctx* c, i64 Q, const double* S, const double* Al, double* out /* G x Q, += */);
 
-// k_glmm_slopes.hip (P = n_cols <= 64, 1 <= K <= 4; groups and the group design set)
+// k_glmm_slopes.hip (the logistic and the Poisson mixed model; P = n_cols <= 64, 1 <= K <= 4; groups and the group design set).
+// The three kernels over the rows are templates over a likelihood policy; GlmmLik picks the instantiation
+// and carries what only it reads: the Gauss-Hermite nodes (logistic), or the per-row offset or nullptr (Poisson).
+struct GlmmLik { bool poisson; const double* gx; const double* gw; int n_nodes; const double* off; };
 int  glmm_slopes_ncol(int P, int K);      // columns of one group's sums: 2 K + K (2 K + 1) + 4 K P
-int  launch_glmm_slopes_rows(lrvb_ctx* c, int K, const double* Z /* N x K */, const double* m, const double* vb,
-                             const double* eg /* G x K */, const double* rg /* G x K */, const double* gx, const double* gw, int n_nodes,
-                             double* coef /* 5 x NP, original row order */, i64 NP, double* gsum /* G x ncol, zeroed by the caller */,
+int  launch_glmm_slopes_rows(lrvb_ctx* c, const GlmmLik& lik, int K, const double* Z /* N x K */, const double* m, const double* vb,
+                             const double* eg /* G x K */, const double* rg /* G x K */,
+                             double* coef /* original row order: 5 x NP (logistic), 2 x NP: a1 | h = w psi (Poisson) */, i64 NP,
+                             double* gsum /* G x ncol, zeroed by the caller */,
                              double* part /* 2 ncol doubles per tile of glmm_num_tiles */, double* vpart);
+int  launch_glmm_poisson_scale_blocks(lrvb_ctx* c, double* Hb /* 3 x P x P, all formed with h: blocks 1, 2 times 1/2, 1/4 */);
 int  launch_glmm_slopes_schur_rows(lrvb_ctx* c, int K, const double* gsum, const double* loc /* G x K (2 K + 1) */,
                                    const double* scale /* G x 2 K */, const double* closed /* G x 2 K x 3 */,
                                    double* U /* 2 K G x ldu */, int ldu, int* bad);
 int  launch_glmm_slopes_solve(lrvb_ctx* c, int K, bool back, i64 Q, const double* loc /* the blocks as uploaded */,
                               double* T /* G x 2 K x Q: forward in place; read by back */, double* W /* back only, in place */);
-int  launch_glmm_slopes_infl_rows(lrvb_ctx* c, int K, const double* Z, i64 n0, i64 n1, const int* gid /* original row order */,
-                                  const double* m, const double* vb, const double* eg, const double* rg, const double* gx,
-                                  const double* gw, int n_nodes, const double* Ag /* Q x 2 P */, const double* Al /* G x 2 K x Q */,
-                                  i64 Q, double* out /* (n1 - n0) x Q */);
-int  launch_glmm_slopes_infl_gsum(lrvb_ctx* c, int K, const double* Z, const double* m, const double* vb, const double* eg,
-                                  const double* rg, const double* gx, const double* gw, int n_nodes,
-                                  double* gsum /* G x (2 K + 2 P), zeroed by the caller */,
+int  launch_glmm_slopes_infl_rows(lrvb_ctx* c, const GlmmLik& lik, int K, const double* Z, i64 n0, i64 n1,
+                                  const int* gid /* original row order */, const double* m, const double* vb, const double* eg,
+                                  const double* rg, const double* Ag /* Q x 2 P */, const double* Al /* G x 2 K x Q */, i64 Q,
+                                  double* out /* (n1 - n0) x Q */);
+int  launch_glmm_slopes_infl_gsum(lrvb_ctx* c, const GlmmLik& lik, int K, const double* Z, const double* m, const double* vb,
+                                  const double* eg, const double* rg, double* gsum /* G x (2 K + 2 P), zeroed by the caller */,
                                   double* part /* 2 (2 K + 2 P) doubles per tile of glmm_num_tiles */);
 int  launch_glmm_slopes_infl_local(lrvb_ctx* c, int K, i64 Q, const double* S, const double* Al, double* out /* G x Q, += */);
-
-// k_glmm_poisson.hip (Poisson mixed model, the layouts of k_glmm_slopes.hip; off: the per-row offset or nullptr)
-int  launch_glmm_poisson_rows(lrvb_ctx* c, int K, const double* Z /* N x K */, const double* off, const double* m, const double* vb,
-                              const double* eg /* G x K */, const double* rg /* G x K */,
-                              double* coef /* 2 x NP: a1 | h = w psi, original row order */, i64 NP,
-                              double* gsum /* G x ncol, zeroed by the caller */,
-                              double* part /* 2 ncol doubles per tile of glmm_num_tiles */, double* vpart);
-int  launch_glmm_poisson_scale_blocks(lrvb_ctx* c, double* Hb /* 3 x P x P, all formed with h: blocks 1, 2 times 1/2, 1/4 */);
-int  launch_glmm_poisson_infl_rows(lrvb_ctx* c, int K, const double* Z, const double* off, i64 n0, i64 n1,
-                                   const int* gid /* original row order */, const double* m, const double* vb, const double* eg,
-                                   const double* rg, const double* Ag /* Q x 2 P */, const double* Al /* G x 2 K x Q */, i64 Q,
-                                   double* out /* (n1 - n0) x Q */);
-int  launch_glmm_poisson_infl_gsum(lrvb_ctx* c, int K, const double* Z, const double* off, const double* m, const double* vb,
-                                   const double* eg, const double* rg, double* gsum /* G x (2 K + 2 P), zeroed by the caller */,
-                                   double* part /* 2 (2 K + 2 P) doubles per tile of glmm_num_tiles */);
 
 // k_lmm.hip
 struct LmmIdx { int p, ms, ls, iem, iim, iay, iby, iam, ibm; i64 ld; };    // vector-coordinate positions of the global parameters

@@ -10,7 +10,7 @@ of `LogisticGLMMSlopesObjective` (glmm_slopes.py).  Only t
     psi_n = E exp(t) = exp(rho_n + s_n / 2),  t ~ N(rho_n, s_n)             -- exact, no quadrature.
 
 The constant sum_n w_n log y_n! of the Poisson log-likelihood does not depend on the parameters and is DROPPED from the value.
-The O(N) work is `lrvb_glmm_poisson_terms` (csrc/k_glmm_poisson.hip); everything after the per-row coefficients -- the group
+The O(N) work is `lrvb_glmm_poisson_terms` (csrc/k_glmm_slopes.hip); everything after the per-row coefficients -- the group
 sums, `glmm_slopes_closed_forms`, `block_arrow.py`, the Schur entry and the device-resident solve -- is the shared layer, unchanged.
 """
 import numpy as np

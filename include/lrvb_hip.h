@@ -514,9 +514,10 @@ int lrvb_glmm_slopes_group_influence(lrvb_ctx* ctx, const double* mean, const do
 /* ---- Poisson mixed model with K <= 4 independent random effects per group ---------------------------
  *   y_n ~ Poisson(exp(o_n + x_n . beta + z_n . u_g(n))),  q(beta_j) = N(mean_j, var_j),  q(u_gk) = N(e_gk, r_gk).
  * The per-row offset o (log exposure; n doubles) lives in one device buffer of its own.  offset == NULL clears it (the offset is
- * then zero); it is replaced by the next call.  Only the three lrvb_glmm_poisson_* entries read it: no other entry looks at
- * it.  The call drops the resident group sums and factor (they were formed under another offset).  A length other than n_obs
- * is found when a Poisson entry runs: LRVB_ERR_STATE there.  n < 1 with a non-null offset: LRVB_ERR_SIZE.                   */
+ * then zero); it is replaced by the next call.  The three lrvb_glmm_poisson_* and the three lrvb_glmm_binomial_* entries read
+ * it; no other entry looks at it (the logistic lrvb_glmm_slopes_* entries in particular do not).  The call drops the resident
+ * group sums and factor (they were formed under another offset).  A length other than n_obs is found when a Poisson or binomial
+ * entry runs: LRVB_ERR_STATE there.  n < 1 with a non-null offset: LRVB_ERR_SIZE.                                             */
 int lrvb_set_offset(lrvb_ctx* ctx, const double* offset, int64_t n);
 /* Data term of that model at (mean, var (P each), e, r (G x K each, group-major)), the group design of lrvb_set_group_design:
  *   rho_n = o_n + x_n . mean + z_n . e_g(n),  s_n = (x_n o x_n) . var + (z_n o z_n) . r_g(n),  psi_n = exp(rho_n + s_n / 2)
@@ -548,6 +549,42 @@ int lrvb_glmm_poisson_obs_influence(lrvb_ctx* ctx, const double* mean, const dou
 int lrvb_glmm_poisson_group_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e,
                                       const double* r, int64_t G, int64_t K, const double* A_global, const double* A_local,
                                       int64_t Q, double* out);
+
+/* ---- binomial mixed model with K <= 4 independent random effects per group, per-row trials and offset ----
+ *   y_n ~ Binomial(m_n, sigma(o_n + x_n . beta + z_n . u_g(n))),  q(beta_j) = N(mean_j, var_j),  q(u_gk) = N(e_gk, r_gk).
+ * The per-row trial counts m (n doubles; real values are accepted) live in one device buffer of their own, the sibling of the
+ * offset's: trials == NULL clears it (one trial per row); it is replaced by the next call; only the three lrvb_glmm_binomial_*
+ * entries read it; the call drops the resident group sums and factor.  A length other than n_obs is found when a binomial entry
+ * runs: LRVB_ERR_STATE there.  n < 1 with non-null trials: LRVB_ERR_SIZE.                                                     */
+int lrvb_set_trials(lrvb_ctx* ctx, const double* trials, int64_t n);
+/* Data term of that model at (mean, var (P each), e, r (G x K each, group-major)), with the Gauss-Hermite rule of
+ * lrvb_glmm_slopes_terms, the offset of lrvb_set_offset (none: 0) and the trials of lrvb_set_trials (none: 1):
+ *   rho_n = o_n + x_n . mean + z_n . e_g(n),  s_n as there,  psi = E softplus(t), t ~ N(rho_n, s_n)
+ *   value = sum_n w_n [m_n psi(rho_n, s_n) - y_n rho_n]                                  (log C(m_n, y_n) is dropped)
+ * and the five per-row coefficients of lrvb_glmm_slopes_terms with every derivative of psi times m_n.  With no trials and no
+ * offset (or ones and zeros) every output equals that of lrvb_glmm_slopes_terms bit for bit.  With m_n = y_n + phi and the offset
+ * o_n - log phi the value is the parameter-dependent part of the negative-binomial (NB2) term with dispersion phi.  Arguments,
+ * outputs, the column layout of group_sums_out, want_border, the fixed summation order and the reduce-hook contract (ONE buffer
+ * [H blocks, when asked for | group sums | gradient | value], one hook call) are those of lrvb_glmm_slopes_terms; the group sums
+ * stay resident for lrvb_glmm_slopes_schur, lrvb_glmm_slopes_solve_forward and lrvb_glmm_slopes_solve_back.  Errors as
+ * lrvb_glmm_slopes_terms, and an offset or trials buffer whose length is not n_obs: LRVB_ERR_STATE.  y, the trials and the offset
+ * are not validated here (the Python layer asks for finite values, trials >= 0 and 0 <= y <= trials).                        */
+int lrvb_glmm_binomial_terms(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                             int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes, double* value_out,
+                             double* grad_global_out, double* H_blocks_out, double* group_sums_out, int32_t want_border);
+/* Streamed weight influence of the binomial mixed model: lrvb_glmm_slopes_obs_influence with, per unit weight,
+ *   a1' = m_n psi_rho(rho_n, s_n) - y_n,   a2' = m_n psi_s(rho_n, s_n),   rho_n including the offset.
+ * Operand layouts, the row window, the output, "a window equals the same rows of the full result bitwise" and "no reduce-hook
+ * call" as there; errors as lrvb_glmm_binomial_terms, and n0 > n1 or n1 > n_obs: LRVB_ERR_INVALID.                            */
+int lrvb_glmm_binomial_obs_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                                     int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
+                                     const double* A_global, const double* A_local, int64_t Q, int64_t n0, int64_t n1, double* out);
+/* Group influence of that model: out[g][q] = sum over the rows n of group g of w_n * (the row of lrvb_glmm_binomial_obs_influence)
+ * (G x Q, host), as lrvb_glmm_slopes_group_influence: a fixed-order sum of 2 K + 2 P columns per group, an exact zero row for
+ * an empty group, ONE reduce-hook call on the G x Q result.  Errors as lrvb_glmm_binomial_obs_influence.                      */
+int lrvb_glmm_binomial_group_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e,
+                                       const double* r, int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
+                                       const double* A_global, const double* A_local, int64_t Q, double* out);
 
 /* ---- multinomial (softmax) regression ---------------------------------------------------------
  * K classes (2 <= K <= 17), labels y_n in {0 .. K-1}, class 0 the reference; coefficients beta ((K-1) x P, row-major, row a

@@ -50,6 +50,7 @@ from .softmax import SoftmaxRegressionObjective
 from .glmm import LogisticGLMMObjective
 from .glmm_slopes import LogisticGLMMSlopesObjective
 from .glmm_poisson import PoissonGLMMObjective
+from .glmm_binomial import BinomialGLMMObjective, NegBinomialGLMMObjective
 from .torch_closure import TorchObjective
 from . import regression as regression_utils
 from . import packing as ProjectionParams

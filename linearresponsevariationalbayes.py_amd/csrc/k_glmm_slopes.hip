@@ -1,10 +1,12 @@
 // k_glmm_slopes.hip -- mixed models with K <= 4 independent random effects per group, q(beta_j) = N(m_j, v_j), q(u_gk) = N(e_gk, r_gk):
 //   logistic:  y_n ~ Bernoulli(sigma(x_n . beta + z_n . u_g(n)))
 //   Poisson  (DESIGN.md section 26):  y_n ~ Poisson(exp(o_n + x_n . beta + z_n . u_g(n)))
+//   binomial:  y_n ~ Binomial(m_n, sigma(o_n + x_n . beta + z_n . u_g(n))), and through it NB2
 // Per observation rho_n = x_n . m + z_n . e_g, s_n = (x_n o x_n) . v + (z_n o z_n) . r_g and five coefficients a1, a2, c11, c12, c22.
 // Every kernel that walks the rows is written ONCE, as a template over a likelihood policy: LogisticLik
 // (the quadrature of k_glmm.hip: same nodes, same Stein-rule derivatives; with K = 1 and z = 1 it is that model) and PoissonLik
-// (psi = E exp(t) = exp(o + rho + s / 2) exactly: ONE exp per row, no nodes).  A policy supplies
+// (psi = E exp(t) = exp(o + rho + s / 2) exactly: ONE exp per row, no nodes); BinomialLik is the first that needs both kinds of
+// state, the nodes and staged per-row data.  A policy supplies
 //   Args / Lds      what only its kernels are handed (the nodes, a struct | the offset, a __restrict__ pointer) and its LDS (node
 //                   tables | the tile's offsets) -- nothing of the other's;
 //   init, stage_row what it puts there, once per workgroup and once per staged row;
@@ -154,6 +156,63 @@ struct PoissonLik {
         const double h = wi * psi;
         k[0] = h - wi * yi; k[1] = h;
         return wi * (psi - yi * rho);
+    }
+};
+
+// Binomial with a per-row trial count m_n and a per-row offset o_n: the logistic quadrature at rho + o, its
+// finished moments times m_n.  The data term is sum w [m E softplus(t) - y rho], t ~ N(rho, s), rho including the offset; with
+// m = y + phi and the offset o - log phi it is the negative binomial (NB2) term for a known dispersion phi.  Nodes AND staged
+// per-row data: the node tables and init are LogisticLik's, the staging is PoissonLik's with a second array.  The coefficient
+// layout is the logistic one.  m = 1 and o = 0 (either pointer null, or the values themselves) give the logistic instantiation
+// bit for bit: x * 1.0 and x + 0.0 are exact, and the products with m are kept out of every fused multiply-add, so that the
+// sums behind them are contracted as LogisticLik's are.
+struct BinomialLik {
+    struct Args { LogisticLik::Args q; const double* __restrict__ off; const double* __restrict__ trials; };   // either may be nullptr
+    struct Lds { LogisticLik::Lds q; double s_off[GS_T], s_m[GS_T]; };   // the node tables; the offsets and trials of the tile's rows
+    typedef LogisticLik::Moments Moments;
+    static constexpr const char* LIMITS = "binomial mixed model: P <= 64, 1 <= K <= 4, at most 128 nodes";
+    static bool args_ok(const Args& a) { return LogisticLik::args_ok(a.q); }
+    static constexpr int NCF = 5, NB = 4, DK = 16;
+    static constexpr bool HAS_FACTOR = false;
+    static __device__ __forceinline__ int cf_row(int kind) { return kind; }
+    static __device__ __forceinline__ double cf_factor(int) { return 1.0; }
+    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return b * Kz + k; }
+    static __device__ __forceinline__ int d_stride(int) { return DK; }
+
+    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { LogisticLik::init(L.q, a.q, tid); }
+    static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
+    {
+        L.s_off[t] = (a.off && live) ? a.off[src] : 0.0;
+        L.s_m[t] = (a.trials && live) ? a.trials[src] : 1.0;
+    }
+    static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_off[row]; }
+    // Neither infl nor moments is handed its row: in all three kernels the four lanes of staged row r are the threads 4 r .. 4 r + 3.
+    static __device__ __forceinline__ int lane_row() { return (int)(threadIdx.x >> 2); }
+    static __device__ __forceinline__ void infl(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& e1,
+                                                double& e2)
+    {
+        const double mt = L.s_m[lane_row()];
+        LogisticLik::infl(L.q, a.q, 0.0, live, q4, rho + o, s, e1, e2);
+        {
+#pragma clang fp contract(off)
+            e1 = e1 * mt; e2 = e2 * mt;
+        }
+    }
+    static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
+    {
+        const int row = lane_row();
+        const double mt = L.s_m[row];
+        Moments mo = LogisticLik::moments(L.q, a.q, live, q4, rho + L.s_off[row], s);
+        {
+#pragma clang fp contract(off)
+            mo.v = mo.v * mt; mo.e1 = mo.e1 * mt; mo.e2 = mo.e2 * mt; mo.e3 = mo.e3 * mt; mo.e4 = mo.e4 * mt;
+        }
+        return mo;
+    }
+    static __device__ __forceinline__ double coefs(const Lds& L, int row, const Moments& mo, double wi, double yi, double rho, double s,
+                                                   double* k)
+    {
+        return LogisticLik::coefs(L.q, row, mo, wi, yi, rho + L.s_off[row], s, k);
     }
 };
 
@@ -342,8 +401,11 @@ static int gs_launch_rows(lrvb_ctx* c, int Kz, const double* Z, typename Lik::Ar
 
 int launch_glmm_slopes_rows(lrvb_ctx* c, const GlmmLik& lik, int Kz, const double* Z, const double* m, const double* vb, const double* eg,
                             const double* rg, double* coef, i64 NP, double* gsum, double* part, double* vpart) {
-    return lik.poisson ? gs_launch_rows<PoissonLik>(c, Kz, Z, lik.off, m, vb, eg, rg, coef, NP, gsum, part, vpart)
-                       : gs_launch_rows<LogisticLik>(c, Kz, Z, {lik.gx, lik.gw, lik.n_nodes}, m, vb, eg, rg, coef, NP, gsum, part, vpart);
+    if (lik.kind == GLMM_POISSON) return gs_launch_rows<PoissonLik>(c, Kz, Z, lik.off, m, vb, eg, rg, coef, NP, gsum, part, vpart);
+    if (lik.kind == GLMM_BINOMIAL)
+        return gs_launch_rows<BinomialLik>(c, Kz, Z, {{lik.gx, lik.gw, lik.n_nodes}, lik.off, lik.trials}, m, vb, eg, rg, coef, NP, gsum, part,
+                                           vpart);
+    return gs_launch_rows<LogisticLik>(c, Kz, Z, {lik.gx, lik.gw, lik.n_nodes}, m, vb, eg, rg, coef, NP, gsum, part, vpart);
 }
 int glmm_slopes_ncol(int P, int Kz) { return 2 * Kz + Kz * (2 * Kz + 1) + 4 * Kz * P; }
 
@@ -672,7 +734,7 @@ void gsi_infl_rows(i64 n0, i64 R /* rows of the window */, int P, int Kz, const 
     }
 }
 
-// The two entries of the walk above.  Each has its likelihood's arguments where that likelihood's kernel has always had them (the
+// The three entries of the walk above.  Each has its likelihood's arguments where that likelihood's kernel has always had them (the
 // offset behind Z, the nodes behind rg): with ONE templated signature the Poisson instantiation loaded its kernel arguments and
 // spilled its SGPRs differently and ran 0.7 to 1 % slower than before the merge.
 __global__ __launch_bounds__(256)
@@ -695,6 +757,17 @@ void glmm_poisson_infl_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* _
     gsi_infl_rows<PoissonLik>(n0, R, P, Kz, X, Z, y, gid, m, vb, eg, rg, off, Ag, Al, Q, out);
 }
 
+__global__ __launch_bounds__(256)
+void glmm_binomial_infl_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* __restrict__ X, const double* __restrict__ Z,
+                                    const double* __restrict__ off, const double* __restrict__ trials, const double* __restrict__ y,
+                                    const int* __restrict__ gid, const double* __restrict__ m, const double* __restrict__ vb,
+                                    const double* __restrict__ eg, const double* __restrict__ rg, const double* __restrict__ gx,
+                                    const double* __restrict__ gw, int nq, const double* __restrict__ Ag, const double* __restrict__ Al,
+                                    int Q, double* __restrict__ out)
+{
+    gsi_infl_rows<BinomialLik>(n0, R, P, Kz, X, Z, y, gid, m, vb, eg, rg, {{gx, gw, nq}, off, trials}, Ag, Al, Q, out);
+}
+
 template <class Lik>
 static int gs_launch_infl_rows(lrvb_ctx* c, int Kz, const double* Z, typename Lik::Args la, i64 n0, i64 n1, const int* gid, const double* m,
                                const double* vb, const double* eg, const double* rg, const double* Ag, const double* Al, i64 Q,
@@ -707,6 +780,10 @@ static int gs_launch_infl_rows(lrvb_ctx* c, int Kz, const double* Z, typename Li
     if constexpr (std::is_same<Lik, PoissonLik>::value)
         hipLaunchKernelGGL(glmm_poisson_infl_rows_kernel, dim3(grid), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
                            (const double*)la, (const double*)c->y.p, gid, m, vb, eg, rg, Ag, Al, (int)Q, out);
+    else if constexpr (std::is_same<Lik, BinomialLik>::value)
+        hipLaunchKernelGGL(glmm_binomial_infl_rows_kernel, dim3(grid), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
+                           (const double*)la.off, (const double*)la.trials, (const double*)c->y.p, gid, m, vb, eg, rg, la.q.gx, la.q.gw,
+                           la.q.nq, Ag, Al, (int)Q, out);
     else
         hipLaunchKernelGGL(glmm_slopes_infl_rows_kernel, dim3(grid), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
                            (const double*)c->y.p, gid, m, vb, eg, rg, la.gx, la.gw, la.nq, Ag, Al, (int)Q, out);
@@ -717,8 +794,11 @@ static int gs_launch_infl_rows(lrvb_ctx* c, int Kz, const double* Z, typename Li
 int launch_glmm_slopes_infl_rows(lrvb_ctx* c, const GlmmLik& lik, int Kz, const double* Z, i64 n0, i64 n1, const int* gid, const double* m,
                                  const double* vb, const double* eg, const double* rg, const double* Ag, const double* Al, i64 Q,
                                  double* out) {
-    return lik.poisson ? gs_launch_infl_rows<PoissonLik>(c, Kz, Z, lik.off, n0, n1, gid, m, vb, eg, rg, Ag, Al, Q, out)
-                       : gs_launch_infl_rows<LogisticLik>(c, Kz, Z, {lik.gx, lik.gw, lik.n_nodes}, n0, n1, gid, m, vb, eg, rg, Ag, Al, Q, out);
+    if (lik.kind == GLMM_POISSON) return gs_launch_infl_rows<PoissonLik>(c, Kz, Z, lik.off, n0, n1, gid, m, vb, eg, rg, Ag, Al, Q, out);
+    if (lik.kind == GLMM_BINOMIAL)
+        return gs_launch_infl_rows<BinomialLik>(c, Kz, Z, {{lik.gx, lik.gw, lik.n_nodes}, lik.off, lik.trials}, n0, n1, gid, m, vb, eg, rg, Ag,
+                                                Al, Q, out);
+    return gs_launch_infl_rows<LogisticLik>(c, Kz, Z, {lik.gx, lik.gw, lik.n_nodes}, n0, n1, gid, m, vb, eg, rg, Ag, Al, Q, out);
 }
 
 // ---- group influence (lrvb_glmm_slopes_group_influence / lrvb_glmm_poisson_group_influence) --------------------------------------
@@ -816,8 +896,10 @@ static int gs_launch_infl_gsum(lrvb_ctx* c, int Kz, const double* Z, typename Li
 
 int launch_glmm_slopes_infl_gsum(lrvb_ctx* c, const GlmmLik& lik, int Kz, const double* Z, const double* m, const double* vb,
                                  const double* eg, const double* rg, double* gsum, double* part) {
-    return lik.poisson ? gs_launch_infl_gsum<PoissonLik>(c, Kz, Z, lik.off, m, vb, eg, rg, gsum, part)
-                       : gs_launch_infl_gsum<LogisticLik>(c, Kz, Z, {lik.gx, lik.gw, lik.n_nodes}, m, vb, eg, rg, gsum, part);
+    if (lik.kind == GLMM_POISSON) return gs_launch_infl_gsum<PoissonLik>(c, Kz, Z, lik.off, m, vb, eg, rg, gsum, part);
+    if (lik.kind == GLMM_BINOMIAL)
+        return gs_launch_infl_gsum<BinomialLik>(c, Kz, Z, {{lik.gx, lik.gw, lik.n_nodes}, lik.off, lik.trials}, m, vb, eg, rg, gsum, part);
+    return gs_launch_infl_gsum<LogisticLik>(c, Kz, Z, {lik.gx, lik.gw, lik.n_nodes}, m, vb, eg, rg, gsum, part);
 }
 
 int launch_glmm_slopes_infl_local(lrvb_ctx* c, int Kz, i64 Q, const double* S, const double* Al, double* out) {

@@ -231,7 +231,7 @@ extern "C" int lrvb_ctx_destroy(lrvb_ctx* c) {
     DevBuf* all[] = { &c->X, &c->y, &c->w, &c->quadA, &c->quadM, &c->quadB, &c->theta, &c->eta, &c->j1, &c->j2,
                       &c->vtmp, &c->vtmp2, &c->vtmp3, &c->g_eta, &c->g_free, &c->lp, &c->cw, &c->zbuf,
                       &c->part_vec, &c->part_val, &c->stats, &c->tile_part, &c->Heta, &c->Hfree, &c->Jdense,
-                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn, &c->glmm, &c->gz, &c->goff, &c->glmms, &c->glmms_fac, &c->glmms_T,
+                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn, &c->glmm, &c->gz, &c->goff, &c->gtr, &c->glmms, &c->glmms_fac, &c->glmms_T,
                       &c->sm.labels, &c->sm.p, &c->sm.wpad, &c->sm.work, &c->sm.col, &c->sm.tiles, &c->sm.rows };
     for (DevBuf* b : all) buf_free(*b);
     if (c->host_pinned) (void)hipHostFree(c->host_pinned);
@@ -2676,17 +2676,21 @@ extern "C" int lrvb_set_group_design(lrvb_ctx* c, const double* z, int64_t n, in
 
 // ---- the host layer the logistic and the Poisson K-effect model share --------------------------------------
 // An entry hands over its likelihood as a GlmmLik: the logistic ones with the caller's (host) nodes, the Poisson ones with
-// nothing -- the bodies below replace the node pointers by the uploaded copies, or fill in the resident offset.
-static GlmmLik glmms_logistic(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{false, gh_x, gh_w, (int)n_nodes, nullptr}; }
-static GlmmLik glmms_poisson() { return GlmmLik{true, nullptr, nullptr, 0, nullptr}; }
+// nothing, the binomial ones with the nodes again -- the bodies below replace the node pointers by the uploaded copies and fill in
+// the resident offset and trials.
+static GlmmLik glmms_logistic(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_LOGISTIC, gh_x, gh_w, (int)n_nodes, nullptr, nullptr}; }
+static GlmmLik glmms_poisson() { return GlmmLik{GLMM_POISSON, nullptr, nullptr, 0, nullptr, nullptr}; }
+static GlmmLik glmms_binomial(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_BINOMIAL, gh_x, gh_w, (int)n_nodes, nullptr, nullptr}; }
+static const char* glmms_name(const GlmmLik& lik) { return lik.kind == GLMM_POISSON ? "Poisson" : (lik.kind == GLMM_BINOMIAL ? "binomial" : "logistic"); }
 
 // The argument and state checks of all six entries, in one order (`other_null`: a required pointer of the entry's own is null).
 static int glmms_check(lrvb_ctx* c, const GlmmLik& lik, const double* mean, const double* var, int64_t P_in, const double* e_loc,
                        const double* r_loc, int64_t G_in, int64_t K, bool other_null) {
-    if (!mean || !var || !e_loc || !r_loc || (!lik.poisson && (!lik.gx || !lik.gw)) || other_null) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
-    if (!lik.poisson && (lik.n_nodes < 1 || lik.n_nodes > 128)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 128 quadrature nodes");
+    const bool poisson = lik.kind == GLMM_POISSON;
+    if (!mean || !var || !e_loc || !r_loc || (!poisson && (!lik.gx || !lik.gw)) || other_null) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    if (!poisson && (lik.n_nodes < 1 || lik.n_nodes > 128)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 128 quadrature nodes");
     if (c->P > 64)
-        LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the %s mixed model needs P <= 64 (got %lld)", lik.poisson ? "Poisson" : "logistic", (long long)c->P);
+        LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the %s mixed model needs P <= 64 (got %lld)", glmms_name(lik), (long long)c->P);
     if (K < 1 || K > 4) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 4 random effects per group (got %lld)", (long long)K);
     if (c->loss == LRVB_LOSS_NONE || c->data_only || !(c->have_X && c->have_y))
         LRVB_FAIL(LRVB_ERR_STATE, "the context needs a design matrix and responses: lrvb_set_data for LRVB_SLOT_X and LRVB_SLOT_Y");
@@ -2694,8 +2698,10 @@ static int glmms_check(lrvb_ctx* c, const GlmmLik& lik, const double* mean, cons
     if (c->gz_K <= 0) LRVB_FAIL(LRVB_ERR_STATE, "no group design: call lrvb_set_group_design first");
     if (c->gz_n != c->N || c->gz_K != K)
         LRVB_FAIL(LRVB_ERR_STATE, "the group design is %lld x %d, the model needs %lld x %lld", (long long)c->gz_n, c->gz_K, (long long)c->N, (long long)K);
-    if (lik.poisson && c->goff_n != 0 && c->goff_n != c->N)
+    if (lik.kind != GLMM_LOGISTIC && c->goff_n != 0 && c->goff_n != c->N)
         LRVB_FAIL(LRVB_ERR_STATE, "the offset has %lld entries, the model has %lld observations", (long long)c->goff_n, (long long)c->N);
+    if (lik.kind == GLMM_BINOMIAL && c->gtr_n != 0 && c->gtr_n != c->N)
+        LRVB_FAIL(LRVB_ERR_STATE, "the trials have %lld entries, the model has %lld observations", (long long)c->gtr_n, (long long)c->N);
     LRVB_TRY(check_len(P_in, c->P, "mean / var"));
     LRVB_TRY(check_len(G_in, c->n_groups, "groups of e / r"));
     for (i64 j = 0; j < c->P; ++j) if (!(var[j] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "var[%lld] is not positive", (long long)j);
@@ -2703,9 +2709,11 @@ static int glmms_check(lrvb_ctx* c, const GlmmLik& lik, const double* mean, cons
     return LRVB_OK;
 }
 
-// The likelihood as the kernels read it: the nodes uploaded behind `g` (256 doubles: x | w), or the resident offset.
+// The likelihood as the kernels read it: the nodes uploaded behind `g` (256 doubles: x | w), the resident offset and trials.
 static int glmms_to_device(lrvb_ctx* c, GlmmLik& lik, double* g) {
-    if (lik.poisson) { lik.off = c->goff_n ? c->goff.p : nullptr; return LRVB_OK; }
+    if (lik.kind != GLMM_LOGISTIC) lik.off = c->goff_n ? c->goff.p : nullptr;
+    if (lik.kind == GLMM_BINOMIAL) lik.trials = c->gtr_n ? c->gtr.p : nullptr;
+    if (lik.kind == GLMM_POISSON) return LRVB_OK;
     LRVB_TRY(h2d(c, g, lik.gx, (size_t)lik.n_nodes));
     LRVB_TRY(h2d(c, g + 128, lik.gw, (size_t)lik.n_nodes));
     lik.gx = g; lik.gw = g + 128;
@@ -2713,12 +2721,13 @@ static int glmms_to_device(lrvb_ctx* c, GlmmLik& lik, double* g) {
 }
 
 // c->glmms: [H blocks (3 P^2) | group sums (G x ncol) | gradient (2 P) | value], adjacent as in lrvb_glmm_terms.  c->work1:
-// [nodes 256 (logistic only) | m, v (2 up(P)) | e, r (2 up(G K)) | the coefficient vectors (original order, zero past N): five,
+// [nodes 256 (not Poisson) | m, v (2 up(P)) | e, r (2 up(G K)) | the coefficient vectors (original order, zero past N): five,
 // a1 a2 c11 c12 c22 (5 NP), or the Poisson model's two, a1 and h (2 NP) | tile partials]
 static int glmms_terms(lrvb_ctx* c, GlmmLik lik, const double* mean, const double* var, int64_t P_in, const double* e_loc,
                        const double* r_loc, int64_t G_in, int64_t K, double* value_out, double* grad_global_out, double* H_blocks_out,
                        double* group_sums_out, int32_t want_border) {
     LRVB_TRY(glmms_check(c, lik, mean, var, P_in, e_loc, r_loc, G_in, K, !value_out));
+    const bool poisson = lik.kind == GLMM_POISSON;
     const i64 N = c->N, P = c->P, G = c->n_groups, ncol = glmm_slopes_ncol((int)P, (int)K), nsc = ncol - 4 * K * P;
     c->glmms_drop();
     const bool want_g = grad_global_out != nullptr, want_H = H_blocks_out != nullptr;
@@ -2729,7 +2738,7 @@ static int glmms_terms(lrvb_ctx* c, GlmmLik lik, const double* mean, const doubl
         c->x2_ready = true;
     }
     auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
-    const i64 NP = up(N + 64), n_tiles = glmm_num_tiles(N), GK = G * K, ncf = lik.poisson ? 2 : 5, nodes = lik.poisson ? 0 : 256;
+    const i64 NP = up(N + 64), n_tiles = glmm_num_tiles(N), GK = G * K, ncf = poisson ? 2 : 5, nodes = poisson ? 0 : 256;
     LRVB_TRY(buf_reserve(c, c->work1, (size_t)(nodes + 2 * up(P) + 2 * up(GK) + ncf * NP + n_tiles * 2 * ncol + n_tiles)));
     LRVB_TRY(buf_reserve(c, c->glmms, (size_t)(3 * P * P + G * ncol + 2 * P + 1)));
     double* g = c->work1.p; double* dm = g + nodes; double* dv = dm + up(P); double* de = dv + up(P); double* dr = de + up(GK);
@@ -2747,22 +2756,22 @@ static int glmms_terms(lrvb_ctx* c, GlmmLik lik, const double* mean, const doubl
     HIP_TRY(hipGetLastError());
     // Poisson: a2 = h / 2 (the factor rides on the product), c11 = h, c12 = h / 2, c22 = h / 4 (one vector, the blocks scaled after)
     const double* a2 = coef + NP;
-    const double* c11 = lik.poisson ? a2 : coef + 2 * NP; const double* c12 = lik.poisson ? a2 : coef + 3 * NP;
-    const double* c22 = lik.poisson ? a2 : coef + 4 * NP;
+    const double* c11 = poisson ? a2 : coef + 2 * NP; const double* c12 = poisson ? a2 : coef + 3 * NP;
+    const double* c22 = poisson ? a2 : coef + 4 * NP;
     if (want_g) {
         LRVB_TRY(launch_gemv(c, true, N, P, 1.0, c->X.p, P, coef, 0.0, gred));
-        LRVB_TRY(launch_gemv(c, true, N, P, lik.poisson ? 0.5 : 1.0, X2.p, P, a2, 0.0, gred + P));
+        LRVB_TRY(launch_gemv(c, true, N, P, poisson ? 0.5 : 1.0, X2.p, P, a2, 0.0, gred + P));
     }
     if (want_H) {
         LRVB_TRY(weighted_tn(c, c->X.p, c->X.p, P, N, c11, Hb, c->mx_A));
         LRVB_TRY(weighted_tn(c, c->X.p, X2.p, P, N, c12, Hb + P * P, c->mx_A));
         LRVB_TRY(weighted_tn(c, X2.p, X2.p, P, N, c22, Hb + 2 * P * P, c->mx_A));
-        if (lik.poisson) LRVB_TRY(launch_glmm_poisson_scale_blocks(c, Hb));
+        if (poisson) LRVB_TRY(launch_glmm_poisson_scale_blocks(c, Hb));
     }
     double* first = want_H ? Hb : gsum;
     LRVB_TRY(obs_reduce(c, first, (i64)(vred + 1 - first)));
     LRVB_TRY(d2h(c, value_out, vred, 1));
-    if (lik.poisson && !std::isfinite(*value_out))
+    if (poisson && !std::isfinite(*value_out))
         LRVB_FAIL(LRVB_ERR_INVALID, "the Poisson data term is not finite at this point: exp(rho + s / 2) overflows for some row (the kernel does not clamp)");
     c->glmms_valid = true; c->glmms_K = (int)K;
     if (want_g) LRVB_TRY(d2h(c, grad_global_out, gred, (size_t)(2 * P)));
@@ -2936,13 +2945,13 @@ extern "C" int lrvb_glmm_group_influence(lrvb_ctx* c, const double* mean, const 
 
 // ---- weight influence of the two K-effect mixed models (k_glmm_slopes.hip) ---------------------------------------------------------
 // The checks of glmms_terms, in its order, then the operand.  c->work1 holds
-//   [nodes 256 (logistic only) | m, v (2 up(P)) | e, r (2 up(G K)) | A_global (Q x 2 P) | A_local (G x 2 K x Q) | call-specific scratch]
+//   [nodes 256 (not Poisson) | m, v (2 up(P)) | e, r (2 up(G K)) | A_global (Q x 2 P) | A_local (G x 2 K x Q) | call-specific scratch]
 static int glmms_infl_setup(lrvb_ctx* c, GlmmLik& lik, const double* mean, const double* var, int64_t P_in, const double* e_loc,
                             const double* r_loc, int64_t G_in, int64_t K, const double* A_global, const double* A_local, int64_t Q,
                             const void* out, size_t extra, GlmmInflBufs& b) {
     LRVB_TRY(glmms_check(c, lik, mean, var, P_in, e_loc, r_loc, G_in, K, !A_global || !A_local || !out));
     if (Q < 1) LRVB_FAIL(LRVB_ERR_INVALID, "Q must be positive");
-    const i64 P = c->P, GK = c->n_groups * K, nodes = lik.poisson ? 0 : 256;
+    const i64 P = c->P, GK = c->n_groups * K, nodes = lik.kind == GLMM_POISSON ? 0 : 256;
     auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
     LRVB_TRY(buf_reserve(c, c->work1, (size_t)(nodes + 2 * up(P) + 2 * up(GK) + up(Q * 2 * P) + up(GK * 2 * Q)) + extra));
     b.g = c->work1.p; b.m = b.g + nodes; b.v = b.m + up(P); b.e = b.v + up(P); b.r = b.e + up(GK);
@@ -3040,6 +3049,46 @@ extern "C" int lrvb_glmm_poisson_group_influence(lrvb_ctx* c, const double* mean
                                                  const double* A_local, int64_t Q, double* out) {
     LRVB_TRY(ctx_bind(c));
     return glmms_group_influence(c, glmms_poisson(), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out);
+}
+
+// ---- binomial mixed model with per-row trials and offset, and through it the negative binomial one -------
+extern "C" int lrvb_set_trials(lrvb_ctx* c, const double* trials, int64_t n) {
+    LRVB_TRY(ctx_bind(c));
+    c->glmms_drop();                                                     // sums formed under other trial counts are not those of the model
+    c->gtr_n = 0;
+    if (!trials) return LRVB_OK;
+    if (n < 1) LRVB_FAIL(LRVB_ERR_SIZE, "the trials need at least one entry");
+    LRVB_TRY(buf_reserve(c, c->gtr, (size_t)n));
+    HIP_TRY(hipMemcpyAsync(c->gtr.p, trials, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->gtr_n = n;
+    return LRVB_OK;
+}
+
+// The three binomial entries: the shared bodies above with the binomial likelihood (the caller's nodes; the offset of
+// lrvb_set_offset and the trials of lrvb_set_trials).
+extern "C" int lrvb_glmm_binomial_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                        const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                        int32_t n_nodes, double* value_out, double* grad_global_out, double* H_blocks_out,
+                                        double* group_sums_out, int32_t want_border) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_terms(c, glmms_binomial(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, value_out, grad_global_out,
+                       H_blocks_out, group_sums_out, want_border);
+}
+
+extern "C" int lrvb_glmm_binomial_obs_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                                const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                                int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, int64_t n0,
+                                                int64_t n1, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_obs_influence(c, glmms_binomial(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, n0, n1, out);
+}
+
+extern "C" int lrvb_glmm_binomial_group_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                                  const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                                  int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_group_influence(c, glmms_binomial(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out);
 }
 
 // ---- logistic regression with a full-covariance Gaussian posterior q(beta) = N(m, Sigma) ----------------------------------

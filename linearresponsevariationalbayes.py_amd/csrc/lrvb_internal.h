@@ -139,6 +139,8 @@ struct lrvb_ctx {
     // lrvb_glmm_poisson_* (k_glmm_slopes.hip): the per-row offset (log exposure) of lrvb_set_offset, goff_n doubles (0 = none:
     // the offset is zero).  The Poisson entries leave their sums in `glmms` as lrvb_glmm_slopes_terms does; no other entry reads it
     DevBuf goff; i64 goff_n = 0;
+    // lrvb_glmm_binomial_* read that offset too, and the per-row trial counts of lrvb_set_trials, gtr_n doubles (0 = none: one trial)
+    DevBuf gtr; i64 gtr_n = 0;
     DevBuf opt;                    // trust-region Newton-CG: 12 D-vectors (+ the D x D preconditioner)
     DevBuf cgm[9];                 // blocked CG: B, X, R, P, Q, Z (Q x D), U, W (Q x V), R^T (P x Q)
     DevBuf cgT;                    // N x Q products X U^T of the blocked HVP
@@ -249,12 +251,14 @@ int  launch_glmm_infl_local(lrvb_ctx* c, i64 Q, const double* S, const double* A
 
 // k_glmm_slopes.hip (the logistic and the Poisson mixed model; P = n_cols <= 64, 1 <= K <= 4; groups and the group design set).
 // The three kernels over the rows are templates over a likelihood policy; GlmmLik picks the instantiation
-// and carries what only it reads: the Gauss-Hermite nodes (logistic), or the per-row offset or nullptr (Poisson).
-struct GlmmLik { bool poisson; const double* gx; const double* gw; int n_nodes; const double* off; };
+// and carries what only it reads: the Gauss-Hermite nodes (logistic, binomial), the per-row offset or nullptr (Poisson, binomial),
+// the per-row trials or nullptr (binomial).
+enum GlmmKind { GLMM_LOGISTIC = 0, GLMM_POISSON = 1, GLMM_BINOMIAL = 2 };
+struct GlmmLik { GlmmKind kind; const double* gx; const double* gw; int n_nodes; const double* off; const double* trials; };
 int  glmm_slopes_ncol(int P, int K);      // columns of one group's sums: 2 K + K (2 K + 1) + 4 K P
 int  launch_glmm_slopes_rows(lrvb_ctx* c, const GlmmLik& lik, int K, const double* Z /* N x K */, const double* m, const double* vb,
                              const double* eg /* G x K */, const double* rg /* G x K */,
-                             double* coef /* original row order: 5 x NP (logistic), 2 x NP: a1 | h = w psi (Poisson) */, i64 NP,
+                             double* coef /* original row order: 5 x NP (logistic, binomial), 2 x NP: a1 | h = w psi (Poisson) */, i64 NP,
                              double* gsum /* G x ncol, zeroed by the caller */,
                              double* part /* 2 ncol doubles per tile of glmm_num_tiles */, double* vpart);
 int  launch_glmm_poisson_scale_blocks(lrvb_ctx* c, double* Hb /* 3 x P x P, all formed with h: blocks 1, 2 times 1/2, 1/4 */);

@@ -1,0 +1,111 @@
+"""Binomial and negative-binomial mixed models with K <= 4 independent random effects per group:
+
+    y_n ~ Binomial(m_n, sigma(o_n + x_n . beta + z_n . u_{g(n)})),   z_n in R^K,   u_gk ~ N(mu_k, 1 / tau_k) independently over k
+
+with a trial count m_n and an offset o_n per row -- the `cbind(successes, failures)` form of aggregated binary data; m = 1, o = 0
+is `LogisticGLMMSlopesObjective`.  Priors, variational families, parameter layout, vector and free coordinates, n_global = 2 P + 4 K
+and the coupled rows are that class's (glmm_slopes.py).  Only the data term differs:
+
+    sum_n w_n [ m_n psi(rho_n, s_n) - y_n rho_n ],   rho_n = o_n + x_n . m + z_n . e_g,   s_n = (x_n o x_n) . v + (z_n o z_n) . r_g,
+    psi = E softplus(t),  t ~ N(rho_n, s_n)          -- the Gauss-Hermite rule and Stein-rule derivatives of the logistic model.
+
+The constant sum_n w_n log C(m_n, y_n) of the binomial log-likelihood does not depend on the parameters and is DROPPED from the
+value.
+
+Negative binomial (NB2: mean e^eta, variance e^eta + e^2eta / phi, KNOWN dispersion phi): the parameter-dependent part of -log p is
+(y + phi) softplus(eta - log phi) - y (eta - log phi), i.e. the binomial term with "trials" y + phi (real, not integer) and the
+offset o - log phi.  `NegBinomialGLMMObjective` is that construction and nothing else; phi is fixed data, not a hyper-parameter,
+and is not estimated.
+
+The O(N) work is `lrvb_glmm_binomial_terms` (csrc/k_glmm_slopes.hip, the policy BinomialLik of the shared tile walk); everything
+after the per-row coefficients is the shared layer, unchanged.
+"""
+import numpy as np
+from scipy.special import expit, gammaln
+
+from . import _hip
+from .glmm_slopes import _LogisticMixedModel, _SlopesArrow
+
+
+def _row_vector(a, n, what):
+    a = _hip.as_f64(a).ravel().copy()
+    if a.size != n or not np.all(np.isfinite(a)):
+        raise ValueError('{} must hold {} finite values'.format(what, n))
+    return a
+
+
+class BinomialGLMMObjective(_SlopesArrow, _LogisticMixedModel):
+    _loss = 'logistic'
+
+    def __init__(self, par, x, y, z, groups, n_groups, trials=None, offset=None, beta_prior_info=1.0, mu_prior=(0.0, 1.0),
+                 tau_prior=(1.0, 1.0), gh_deg=20, names=('beta', 'mu', 'tau', 'u'), weights=None, device=0):
+        """y: successes, 0 <= y_n <= trials_n (log C(m, y) is dropped from the value).  trials: the N trial counts m_n >= 0 (real
+        values are accepted: the negative-binomial subclass sends y + phi), or None for one trial per row.  offset: the N offsets
+        o_n, or None for zero.  z: the N x K group design, or None for one effect per group with the unit design (a column of
+        ones is sent).  names: as `LogisticGLMMSlopesObjective`.  All checks run before the device context is created."""
+        y = _hip.as_f64(y).ravel()
+        n = np.shape(x)[0]
+        if y.size != n or not np.all(np.isfinite(y)):
+            raise ValueError('y must hold {} finite values'.format(n))
+        if trials is not None:
+            trials = _row_vector(trials, n, 'trials')
+            if np.any(trials < 0.0):
+                raise ValueError('trials must be >= 0')
+        if np.any(y < 0.0) or np.any(y > (1.0 if trials is None else trials)):
+            raise ValueError('y must satisfy 0 <= y <= trials')
+        if offset is not None:
+            offset = _row_vector(offset, n, 'offset')
+        if z is None:
+            z = np.ones((n, 1))
+        super().__init__(par, x, y, z, groups, n_groups, beta_prior_info, mu_prior, tau_prior, gh_deg, names, weights, device)
+        self._trials, self._offset = trials, offset
+        self.ctx.set_trials(trials)
+        self.ctx.set_offset(offset)
+
+    # ---- the device entries -------------------------------------------------------------------------------------------------
+    def _terms(self, *point, **want):
+        return self.ctx.glmm_binomial_terms(*point, **want)
+
+    def _obs_influence(self, *point_and_operand, **window):
+        return self.ctx.glmm_binomial_obs_influence(*point_and_operand, **window)
+
+    def _group_influence(self, *point_and_operand):
+        return self.ctx.glmm_binomial_group_influence(*point_and_operand)
+
+    def _row_psi_derivs(self, rho, s):
+        """The logistic derivatives at rho + o, times m, by the rule the kernels use (Stein's identity on the nodes:
+        psi_rho = E sigma(t), psi_s = E sigma'(t) / 2), so that the dense weight cross Hessian is the derivative of the same
+        function as the streamed rows.  N x nodes on the host: the dense protocol is the small-N one."""
+        if self._offset is not None:
+            rho = rho + self._offset
+        t = rho[:, None] + np.sqrt(np.maximum(s, 0.0))[:, None] * (np.sqrt(2.0) * self.gh_x)[None, :]
+        sg = expit(t)
+        wk = self.gh_w / np.sqrt(np.pi)
+        p_rho, p_s = (sg * wk).sum(1), 0.5 * (sg * (1.0 - sg) * wk).sum(1)
+        return (p_rho, p_s) if self._trials is None else (self._trials * p_rho, self._trials * p_s)
+
+
+class NegBinomialGLMMObjective(BinomialGLMMObjective):
+    def __init__(self, par, x, y, z, groups, n_groups, dispersion, offset=None, beta_prior_info=1.0, mu_prior=(0.0, 1.0),
+                 tau_prior=(1.0, 1.0), gh_deg=20, names=('beta', 'mu', 'tau', 'u'), weights=None, device=0):
+        """y: counts (finite, >= 0).  dispersion: phi > 0, a scalar or N values -- Var y = mu + mu^2 / phi, so phi -> infinity is
+        the Poisson model; fixed data, not estimated.  offset: the N log exposures, or None.  The model is the binomial one with
+        trials y + phi and offset o - log phi; `value` is -ELBO up to the constant `log_norm_const()`."""
+        y = _hip.as_f64(y).ravel()
+        n = np.shape(x)[0]
+        if y.size != n or not np.all(np.isfinite(y)) or np.any(y < 0.0):
+            raise ValueError('y must hold {} finite counts >= 0'.format(n))
+        phi = _hip.as_f64(dispersion).ravel()
+        if phi.size not in (1, n) or not np.all(np.isfinite(phi)) or np.any(phi <= 0.0):
+            raise ValueError('dispersion must be a finite positive scalar or {} finite positive values'.format(n))
+        phi = np.full(n, phi[0]) if phi.size == 1 else phi.copy()
+        o = np.zeros(n) if offset is None else _row_vector(offset, n, 'offset')
+        super().__init__(par, x, y, z, groups, n_groups, y + phi, o - np.log(phi), beta_prior_info, mu_prior, tau_prior, gh_deg, names,
+                         weights, device)
+        self._phi = phi
+
+    def log_norm_const(self):
+        """C(y, phi) = sum_n w_n [log Gamma(y_n + phi_n) - log Gamma(phi_n) - log Gamma(y_n + 1)] at the current weights:
+        -ELBO(phi) = value - C + KL terms that do not depend on phi, so two dispersions are compared by value - log_norm_const()."""
+        w = np.asarray(self.weights_par.get_vector(), dtype=np.float64).ravel()
+        return float(np.sum(w * (gammaln(self._y + self._phi) - gammaln(self._phi) - gammaln(self._y + 1.0))))

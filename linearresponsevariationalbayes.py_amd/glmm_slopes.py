@@ -621,7 +621,7 @@ class _LogisticMixedModel(DeclaredHypers):
 class _SlopesArrow:
     """What the models with K effects per group share on top of `_LogisticMixedModel`, whatever their likelihood: the parameter
     layout of DESIGN.md section 18, the Schur entry on the resident group sums and the block-arrow solve resident on the device
-    (`LogisticGLMMSlopesObjective`, `PoissonGLMMObjective`)."""
+    (`LogisticGLMMSlopesObjective`, `PoissonGLMMObjective`, `BinomialGLMMObjective` and its negative-binomial subclass)."""
 
     def _layout(self, par, names):
         P, K, G = self.P, self.K, self.G

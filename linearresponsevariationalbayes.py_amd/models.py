@@ -484,7 +484,7 @@ class DeviceContext(object):
 
     # ---- Poisson mixed model (lrvb_glmm_poisson_*): the layouts of the slopes entries, no quadrature ---------------------------
     def set_offset(self, offset):
-        """The per-row offset (log exposure) of the Poisson mixed model, or None to clear it (lrvb_set_offset)."""
+        """The per-row offset of the Poisson (log exposure) and the binomial mixed model, or None to clear it (lrvb_set_offset)."""
         if offset is None:
             self._check(self._lib.lrvb_set_offset(self._h, None, 0))
             return
@@ -527,6 +527,57 @@ class DeviceContext(object):
         out = np.empty((e.shape[0], Q))
         self._check(self._lib.lrvb_glmm_poisson_group_influence(self._h, _hip.ptr(m), _hip.ptr(v), self.n_cols, _hip.ptr(e), _hip.ptr(r),
                                                                e.shape[0], e.shape[1], _hip.ptr(Ag), _hip.ptr(Al), Q, _hip.ptr(out)))
+        return out
+
+    # ---- binomial mixed model (lrvb_glmm_binomial_*): the layouts of the slopes entries, per-row trials and offset -------------
+    def set_trials(self, trials):
+        """The per-row trial counts of the binomial mixed model, or None to clear them: one trial per row (lrvb_set_trials)."""
+        if trials is None:
+            self._check(self._lib.lrvb_set_trials(self._h, None, 0))
+            return
+        t = _hip.as_f64(trials).ravel()
+        self._check(self._lib.lrvb_set_trials(self._h, _hip.ptr(t), t.size))
+
+    def glmm_binomial_terms(self, mean, var, e, r, gh_x, gh_w, want_grad=True, want_hess=True, want_border=True):
+        """Data term of the binomial mixed model with K effects per group, the trials of `set_trials` and the offset of
+        `set_offset` (lrvb_glmm_binomial_terms): what `glmm_slopes_terms` returns, in its layouts.  The group sums stay
+        resident for `glmm_slopes_schur`."""
+        m, v = _hip.as_f64(mean).ravel(), _hip.as_f64(var).ravel()
+        e, r = _hip.as_f64(e), _hip.as_f64(r)
+        gx, gw = _hip.as_f64(gh_x).ravel(), _hip.as_f64(gh_w).ravel()
+        P = self.n_cols
+        if e.ndim != 2 or r.shape != e.shape or m.size != P or v.size != P or gx.size != gw.size:
+            raise ValueError('expected mean and var of length {}, e and r of one shape G x K and as many weights as nodes'.format(P))
+        G, K = e.shape
+        nsc = 2 * K + K * (2 * K + 1)
+        val = np.empty(1)
+        gg = np.empty(2 * P) if want_grad else None
+        Hb = np.empty((3, P, P)) if want_hess else None
+        border = bool(want_hess and want_border)
+        gs = np.empty((G, nsc + (4 * K * P if border else 0))) if (want_grad or want_hess) else None
+        self._check(self._lib.lrvb_glmm_binomial_terms(self._h, _hip.ptr(m), _hip.ptr(v), P, _hip.ptr(e), _hip.ptr(r), G, K, _hip.ptr(gx),
+                                                      _hip.ptr(gw), gx.size, _hip.ptr(val), _hip.ptr(gg), _hip.ptr(Hb), _hip.ptr(gs),
+                                                      1 if border else 0))
+        return float(val[0]), gg, Hb, gs
+
+    def glmm_binomial_obs_influence(self, mean, var, e, r, gh_x, gh_w, A, n0=0, n1=None):
+        """(n1 - n0) x Q rows of the binomial mixed model, as `glmm_slopes_obs_influence` (lrvb_glmm_binomial_obs_influence)."""
+        (m, v, e, r, gx, gw, Ag, Al), Q = self._glmm_influence_args(mean, var, e, r, gh_x, gh_w, A)
+        n0 = int(n0)
+        n1 = self.n_obs if n1 is None else int(n1)
+        out = np.empty((max(n1 - n0, 0), Q))
+        self._check(self._lib.lrvb_glmm_binomial_obs_influence(self._h, _hip.ptr(m), _hip.ptr(v), self.n_cols, _hip.ptr(e), _hip.ptr(r),
+                                                              e.shape[0], e.shape[1], _hip.ptr(gx), _hip.ptr(gw), gx.size, _hip.ptr(Ag),
+                                                              _hip.ptr(Al), Q, n0, n1, _hip.ptr(out)))
+        return out
+
+    def glmm_binomial_group_influence(self, mean, var, e, r, gh_x, gh_w, A):
+        """G x Q group influence of the binomial mixed model, as `glmm_slopes_group_influence` (lrvb_glmm_binomial_group_influence)."""
+        (m, v, e, r, gx, gw, Ag, Al), Q = self._glmm_influence_args(mean, var, e, r, gh_x, gh_w, A)
+        out = np.empty((e.shape[0], Q))
+        self._check(self._lib.lrvb_glmm_binomial_group_influence(self._h, _hip.ptr(m), _hip.ptr(v), self.n_cols, _hip.ptr(e), _hip.ptr(r),
+                                                                e.shape[0], e.shape[1], _hip.ptr(gx), _hip.ptr(gw), gx.size, _hip.ptr(Ag),
+                                                                _hip.ptr(Al), Q, _hip.ptr(out)))
         return out
 
     # ---- multinomial (softmax) regression: beta is (K - 1) x n_cols, D = (K - 1) n_cols (lrvb_softmax_*) --------------------

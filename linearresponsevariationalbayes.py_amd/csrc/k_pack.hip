@@ -23,9 +23,11 @@ __device__ __forceinline__ void box_eval(double f, double lb, double ub, double&
     else if (!has_lb && has_ub) { const double x = exp(-f); e = ub - x; d1 = x; d2 = -x; }
     else {
         // stable logistic; the reference's exp(f)/(1+exp(f)) overflows for f > 709
+        // 1 - s is taken directly for f >= 0, where s -> 1 and the subtraction cancels (eta' lost every digit by f = 37)
         const double ef = exp(-fabs(f));
         const double s = f >= 0.0 ? 1.0 / (1.0 + ef) : ef / (1.0 + ef);
-        const double r = ub - lb, sp = s * (1.0 - s);
+        const double cs = f >= 0.0 ? ef / (1.0 + ef) : 1.0 - s;
+        const double r = ub - lb, sp = s * cs;
         e = r * s + lb; d1 = r * sp; d2 = r * sp * (1.0 - 2.0 * s);
     }
 }

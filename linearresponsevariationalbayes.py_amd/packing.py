@@ -56,7 +56,7 @@ def _box_d1_d2(f, lb, ub):
         return e, -e
     ef = np.exp(-np.abs(f))
     s = np.where(f >= 0, 1.0 / (1.0 + ef), ef / (1.0 + ef))
-    sp = (ub - lb) * s * (1.0 - s)
+    sp = (ub - lb) * s * np.where(f >= 0, ef / (1.0 + ef), 1.0 - s)      # the complement directly where s -> 1
     return sp, sp * (1.0 - 2.0 * s)
 
 

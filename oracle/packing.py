@@ -33,7 +33,7 @@ def box_constrain(f, lb, ub):
     ef = np.exp(-np.abs(f))
     s = np.where(f >= 0, 1.0 / (1.0 + ef), ef / (1.0 + ef))
     r = ub - lb
-    sp = s * (1.0 - s)
+    sp = s * np.where(f >= 0, ef / (1.0 + ef), 1.0 - s)      # the complement directly where s -> 1 (1 - s cancels there)
     return r * s + lb, r * sp, r * sp * (1.0 - 2.0 * s)
 
 

@@ -362,6 +362,10 @@ int lrvb_logitnormal_mvn_chain(lrvb_ctx* ctx, int64_t P, const double* cov, cons
  *   [H blocks (3 P^2, only when asked for) | group sums (G x (5 + 4 P)) | gradient (2 P) | value (1)]
  * and goes through the hook exactly once (groups may straddle ranks: their sums add).  The group sums stay resident in the
  * context for lrvb_glmm_schur until the next lrvb_glmm_terms or lrvb_set_groups.
+ * ONE resident buffer serves this entry and the K-effect terms entries below (lrvb_glmm_slopes_terms, lrvb_glmm_poisson_terms,
+ * lrvb_glmm_binomial_terms): on one context a call of this entry drops the resident K-effect sums and the factor of
+ * lrvb_glmm_slopes_schur, and a K-effect terms call drops the sums of this entry.  Either family's elimination refuses the
+ * other's sums (LRVB_ERR_STATE): use one context per model.
  * P > 64 or more than 128 nodes: LRVB_ERR_UNSUPPORTED; groups, X or y not set: LRVB_ERR_STATE; var_j <= 0 or r_g <= 0:
  * LRVB_ERR_INVALID.                                                                                                     */
 int lrvb_glmm_terms(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r, int64_t G,
@@ -402,7 +406,7 @@ int lrvb_set_group_design(lrvb_ctx* ctx, const double* z, int64_t n, int64_t K);
  * Reduce hook: every sum over observations of the call lies in ONE device buffer
  *   [H blocks (3 P^2, only when asked for) | group sums (G x ncol) | gradient (2 P) | value (1)]
  * and goes through the hook exactly once.  The group sums stay resident for lrvb_glmm_slopes_schur until the next
- * lrvb_glmm_slopes_terms, lrvb_set_group_design or lrvb_set_groups.
+ * lrvb_glmm_slopes_terms, lrvb_set_group_design or lrvb_set_groups -- or the next lrvb_glmm_terms, which shares the buffer (see there).
  * P > 64, K < 1, K > 4 or more than 128 nodes: LRVB_ERR_UNSUPPORTED; groups, the group design, X or y not set, or a group
  * design that is not n_obs x K: LRVB_ERR_STATE; var_j <= 0 or r_gk <= 0: LRVB_ERR_INVALID; G is not the number of groups:
  * LRVB_ERR_SIZE.                                                                                                          */

@@ -3,7 +3,7 @@
 // psi(rho, s) = E log(1 + e^z), z ~ N(rho, s), by Gauss-Hermite with the derivative convention of lmvn_coef_kernel
 // (k_logitmvn.hip: Stein's identity on the same nodes, no division by sd).
 //
-// glmm_rows_kernel is ONE pass over the rows in group-sorted order.  A workgroup (4 waves) walks tiles of GL_T = 64 sorted rows:
+// glmm_rows_kernel is ONE pass over the rows in group-sorted order.  A workgroup (4 waves) walks tiles of GLMM_T = 64 sorted rows:
 //   1. the tile's rows are gathered through the permutation into LDS (a row is contiguous in X, so the gather is row-granular;
 //      any P, no alignment requirement -- there is no separate odd-P route);
 //   2. four lanes share a row: each forms a quarter of the two dot products (m and v live in LDS), two xor shuffles add them,
@@ -18,12 +18,40 @@
 //      the run that starts at the tile's first row, slot 1: the run that leaves through its last row) and glmm_fixup_kernel adds
 //      the pieces of such a group in tile order.  No atomics anywhere: the result is a fixed-order sum, bitwise reproducible.
 // Empty groups keep the zeros the caller wrote.
-#include "lrvb_internal.h"
-#include "k_kernels.h"
-#include <math.h>
+//
+// This is the K-effect model of k_glmm_slopes.hip at K = 1 with z = 1, and everything that does not depend on the geometry of the
+// walk is that file's (k_glmm_walk.h): the quadrature is LogisticLik (init, moments, coefs, infl), the head
+// of a tile is gs_stage_sorted_tile without a design, the destination of a flush is gs_flush_dst.  What stays here is what makes
+// this walk faster than the K = 1 instantiation: dot products that add a single e_g, r_g, the strides 65 and 66, one border column
+// per thread (gl_walk_tile) and the MFMA loop of glmm_infl_rows_kernel.
+#include "k_glmm_walk.h"
 
-constexpr int GL_T = 64;                 // sorted rows per tile
 constexpr int GL_XS = 65;                // LDS row stride of the tile (odd: the four lanes of a row and 16 rows hit different banks)
+
+// The segmented sums of one tile, in row order: thread tid owns output column NSC + tid (has_col: the staged column jc, squared
+// where sq, times coefficient row ci) and, for tid < NSC, scalar column tid (the sum of coefficient row tid); a flush at every
+// change of group, to gs_flush_dst.
+template <int NSC>
+__device__ __forceinline__ void gl_walk_tile(int tid, i64 tile, int rows, int ncol, bool has_col, int jc, int ci, bool sq, const double* xs,
+                                             const double* cf, const int* s_gid, const int* s_whole, double* __restrict__ gsum,
+                                             double* __restrict__ part)
+{
+    if (has_col || tid < NSC) {
+        double acc = 0.0, accs = 0.0;
+        int run_start = 0;
+        for (int rr = 0; rr < rows; ++rr) {
+            if (has_col) { double x = xs[rr * GL_XS + jc]; if (sq) x *= x; acc += cf[ci * GLMM_T + rr] * x; }
+            if (tid < NSC) accs += cf[tid * GLMM_T + rr];
+            const int g = s_gid[rr];
+            if (rr == rows - 1 || s_gid[rr + 1] != g) {
+                double* dst = gs_flush_dst(s_whole[rr], g, tile, run_start, ncol, gsum, part);
+                if (has_col) dst[NSC + tid] = acc;
+                if (tid < NSC) dst[tid] = accs;
+                acc = 0.0; accs = 0.0; run_start = rr + 1;
+            }
+        }
+    }
+}
 
 __global__ __launch_bounds__(256)
 void glmm_rows_kernel(i64 N, int P, i64 G, const double* __restrict__ X, const double* __restrict__ y, const double* __restrict__ w,
@@ -32,15 +60,16 @@ void glmm_rows_kernel(i64 N, int P, i64 G, const double* __restrict__ X, const d
                       const double* __restrict__ gx, const double* __restrict__ gw, int K, double* __restrict__ coef, i64 NP,
                       double* __restrict__ gsum, double* __restrict__ part, double* __restrict__ vpart)
 {
-    __shared__ double xs[GL_T * GL_XS], cf[5 * GL_T], ms[64], vs[64], sx[128], sw[128], red[4];
-    __shared__ i64 s_row[GL_T];
-    __shared__ int s_gid[GL_T], s_whole[GL_T];
+    __shared__ double xs[GLMM_T * GL_XS], cf[5 * GLMM_T], ms[64], vs[64], red[4];
+    __shared__ LogisticLik::Lds lik;
+    __shared__ i64 s_row[GLMM_T];
+    __shared__ int s_gid[GLMM_T], s_whole[GLMM_T];
     const int tid = threadIdx.x;
     const int ncol = 5 + 4 * P;
-    const double r2 = 1.4142135623730951, ispi = 0.5641895835477563;     // sqrt(2), 1 / sqrt(pi)
-    if (tid < K) { sx[tid] = r2 * gx[tid]; sw[tid] = ispi * gw[tid]; }
+    const LogisticLik::Args la{gx, gw, K};
+    LogisticLik::init(lik, la, tid);
     if (tid < P) { ms[tid] = m[tid]; vs[tid] = vb[tid]; }
-    const i64 n_tiles = (N + GL_T - 1) / GL_T;
+    const i64 n_tiles = (N + GLMM_T - 1) / GLMM_T;
     const int row = tid >> 2, q4 = tid & 3;
     // the output column of this thread in the segmented sums: 5 + tid (tid < 4 P); threads 0..4 also carry scalar column tid
     const int blk = tid / P, jc = tid - blk * P;
@@ -48,25 +77,10 @@ void glmm_rows_kernel(i64 N, int P, i64 G, const double* __restrict__ X, const d
     const int ci = blk == 0 ? 2 : (blk == 3 ? 4 : 3);                    // c11 | c12 | c12 | c22
     const bool sq = blk >= 2;
     for (i64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const i64 t0 = tile * GL_T;
-        const int rows = (int)(N - t0 < GL_T ? N - t0 : GL_T);
+        const i64 t0 = tile * GLMM_T;
+        const int rows = (int)(N - t0 < GLMM_T ? N - t0 : GLMM_T);
         __syncthreads();                                                 // the previous tile is consumed (and the nodes are in place)
-        if (tid < GL_T) {
-            int g = 0, whole = 0;
-            i64 pr = 0;
-            if (tid < rows) {
-                const i64 i = t0 + tid;
-                pr = perm[i];
-                i64 lo = 0, hi = G;                                      // the last g with offs[g] <= i (its offs[g + 1] > i)
-                while (hi - lo > 1) { const i64 mid = (lo + hi) >> 1; if (offs[mid] <= i) lo = mid; else hi = mid; }
-                g = (int)lo;
-                whole = (offs[lo] >= t0 && offs[lo + 1] <= t0 + GL_T) ? 1 : 0;
-            }
-            s_row[tid] = pr; s_gid[tid] = g; s_whole[tid] = whole;
-        }
-        __syncthreads();
-        for (int e = tid; e < rows * P; e += 256) { const int rr = e / P, cc = e - rr * P; xs[rr * GL_XS + cc] = X[s_row[rr] * P + cc]; }
-        __syncthreads();
+        gs_stage_sorted_tile<LogisticLik, GL_XS, false>(tid, t0, rows, P, 0, G, X, nullptr, perm, offs, la, lik, xs, s_row, s_gid, s_whole);
         double rho = 0.0, s = 0.0;
         if (row < rows) {
             const double* xr = xs + row * GL_XS;
@@ -74,38 +88,19 @@ void glmm_rows_kernel(i64 N, int P, i64 G, const double* __restrict__ X, const d
         }
         rho += __shfl_xor(rho, 1); s += __shfl_xor(s, 1);
         rho += __shfl_xor(rho, 2); s += __shfl_xor(s, 2);
-        double v = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0, e4 = 0.0;
-        if (row < rows) {
-            const int g = s_gid[row];
-            rho += eg[g]; s += rg[g];
-            const double sd = sqrt(fmax(s, 0.0));
-            for (int k = q4; k < K; k += 4) {
-                const double t = rho + sd * sx[k], wk = sw[k];
-                const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
-                const double sp = (t > 0.0 ? t : 0.0) + log1p(e);
-                const double sg = t >= 0.0 ? ie : e * ie;
-                const double g2 = e * ie * ie;
-                const double om = (1.0 - e) * ie;                        // |1 - 2 sigma|
-                const double g3 = t >= 0.0 ? -g2 * om : g2 * om;
-                v += wk * sp; e1 += wk * sg; e2 += wk * g2; e3 += wk * g3; e4 += wk * g2 * (1.0 - 6.0 * g2);
-            }
-        }
-#pragma unroll
-        for (int off = 1; off <= 2; off <<= 1) {
-            v += __shfl_xor(v, off); e1 += __shfl_xor(e1, off); e2 += __shfl_xor(e2, off);
-            e3 += __shfl_xor(e3, off); e4 += __shfl_xor(e4, off);
-        }
+        if (row < rows) { const int g = s_gid[row]; rho += eg[g]; s += rg[g]; }
+        const LogisticLik::Moments mo = LogisticLik::moments(lik, la, row < rows, q4, rho, s);
         double contrib = 0.0;
         if (q4 == 0) {
-            double k1 = 0.0, k2 = 0.0, k11 = 0.0, k12 = 0.0, k22 = 0.0;
+            double k[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
             if (row < rows) {
                 const i64 pr = s_row[row];
-                const double wi = w[pr], yi = y[pr];
-                contrib = wi * (v - yi * rho);
-                k1 = wi * (e1 - yi); k2 = wi * 0.5 * e2; k11 = wi * e2; k12 = wi * 0.5 * e3; k22 = wi * 0.25 * e4;
-                coef[pr] = k1; coef[NP + pr] = k2; coef[2 * NP + pr] = k11; coef[3 * NP + pr] = k12; coef[4 * NP + pr] = k22;
+                contrib = LogisticLik::coefs(lik, row, mo, w[pr], y[pr], rho, s, k);
+#pragma unroll
+                for (int i = 0; i < 5; ++i) coef[i * NP + pr] = k[i];
             }
-            cf[row] = k1; cf[GL_T + row] = k2; cf[2 * GL_T + row] = k11; cf[3 * GL_T + row] = k12; cf[4 * GL_T + row] = k22;
+#pragma unroll
+            for (int i = 0; i < 5; ++i) cf[i * GLMM_T + row] = k[i];
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) contrib += __shfl_xor(contrib, off);
@@ -113,21 +108,7 @@ void glmm_rows_kernel(i64 N, int P, i64 G, const double* __restrict__ X, const d
         __syncthreads();
         if (tid == 0) vpart[tile] = (red[0] + red[1]) + (red[2] + red[3]);
         // segmented sums over the tile's rows, in row order
-        if (has_col || tid < 5) {
-            double acc = 0.0, accs = 0.0;
-            int run_start = 0;
-            for (int rr = 0; rr < rows; ++rr) {
-                if (has_col) { double x = xs[rr * GL_XS + jc]; if (sq) x *= x; acc += cf[ci * GL_T + rr] * x; }
-                if (tid < 5) accs += cf[tid * GL_T + rr];
-                const int g = s_gid[rr];
-                if (rr == rows - 1 || s_gid[rr + 1] != g) {
-                    double* dst = s_whole[rr] ? gsum + (i64)g * ncol : part + (tile * 2 + (run_start == 0 ? 0 : 1)) * ncol;
-                    if (has_col) dst[5 + tid] = acc;
-                    if (tid < 5) dst[tid] = accs;
-                    acc = 0.0; accs = 0.0; run_start = rr + 1;
-                }
-            }
-        }
+        gl_walk_tile<5>(tid, tile, rows, ncol, has_col, jc, ci, sq, xs, cf, s_gid, s_whole, gsum, part);
     }
 }
 
@@ -139,9 +120,9 @@ void glmm_fixup_kernel(i64 G, int ncol, const i64* __restrict__ offs, const doub
     if (g >= G) return;
     const i64 gs = offs[g], ge = offs[g + 1];
     if (ge <= gs) return;
-    const i64 tf = gs / GL_T, tl = (ge - 1) / GL_T;
+    const i64 tf = gs / GLMM_T, tl = (ge - 1) / GLMM_T;
     if (tf == tl) return;                                                // written by the rows kernel
-    const int first_slot = (gs % GL_T) != 0 ? 1 : 0;
+    const int first_slot = (gs % GLMM_T) != 0 ? 1 : 0;
     for (int c = threadIdx.x; c < ncol; c += 256) {
         double acc = part[(tf * 2 + first_slot) * ncol + c];
 #pragma unroll 4
@@ -156,7 +137,7 @@ int launch_glmm_rows(lrvb_ctx* c, const double* m, const double* vb, const doubl
     if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "logistic mixed model: P <= 64");
     const int ncol = 5 + 4 * (int)c->P;
     const i64* gdev = reinterpret_cast<const i64*>(c->groups.p);
-    const i64 n_tiles = (N + GL_T - 1) / GL_T;
+    const i64 n_tiles = glmm_num_tiles(N);
     const unsigned grid = (unsigned)(n_tiles < 2048 ? (n_tiles < 1 ? 1 : n_tiles) : 2048);
     hipLaunchKernelGGL(glmm_rows_kernel, dim3(grid), dim3(256), 0, c->stream, N, (int)c->P, G, (const double*)c->X.p,
                        (const double*)c->y.p, (const double*)c->w.p, gdev, gdev + N, m, vb, eg, rg, gx, gw, K, coef, NP, gsum, part, vpart);
@@ -165,54 +146,12 @@ int launch_glmm_rows(lrvb_ctx* c, const double* m, const double* vb, const doubl
     HIP_TRY(hipGetLastError());
     return LRVB_OK;
 }
-i64 glmm_num_tiles(i64 N) { return (N + GL_T - 1) / GL_T; }
-
-// ---- elimination of the 2 G local parameters -------------------------------------------------------------------------------
-// Per group g: A_g = [a11 a12; a12 a22] (the complete local block in free coordinates, from the host) = L L^T, and the two
-// border rows over the R = 2 P + 3 coupled global coordinates [m (P) | v (P) | e_mu, a, b]
-//   c_e = f_e [sum c11 x | sum c12 x o x | closed_e (3)],   c_r = f_r [sum c12 x | sum c22 x o x | closed_r (3)]
-// from the RESIDENT group sums.  The kernel writes U_g = L^-1 [c_e; c_r] (2 x R), so that sum_g C_g A_g^-1 C_g^T = U^T U is one
-// Gram over 2 G rows.  A block that is not positive definite raises the flag.
-__global__ __launch_bounds__(128)
-void glmm_schur_rows_kernel(i64 G, int P, const double* __restrict__ gsum, const double* __restrict__ loc /* G x 3 */,
-                            const double* __restrict__ scale /* G x 2 */, const double* __restrict__ closed /* G x 6 */,
-                            double* __restrict__ U, int ldu, int* __restrict__ bad)
-{
-    const i64 g = blockIdx.x;
-    if (g >= G) return;
-    const int ncol = 5 + 4 * P, R = 2 * P + 3;
-    const double a11 = loc[g * 3], a12 = loc[g * 3 + 1], a22 = loc[g * 3 + 2];
-    const bool ok1 = a11 > 0.0;
-    const double l11 = sqrt(ok1 ? a11 : 1.0), l21 = a12 / l11, d = a22 - l21 * l21;
-    const bool ok = ok1 && d > 0.0;
-    if (!ok && threadIdx.x == 0) *bad = 1;
-    const double l22 = sqrt(ok ? d : 1.0);
-    const double fe = scale[g * 2], fr = scale[g * 2 + 1];
-    const double* gs = gsum + g * ncol;
-    for (int c = threadIdx.x; c < R; c += 128) {
-        double ce, cr;
-        if (c < P) { ce = gs[5 + c]; cr = gs[5 + P + c]; }
-        else if (c < 2 * P) { ce = gs[5 + 2 * P + (c - P)]; cr = gs[5 + 3 * P + (c - P)]; }
-        else { ce = closed[g * 6 + (c - 2 * P)]; cr = closed[g * 6 + 3 + (c - 2 * P)]; }
-        const double u1 = fe * ce / l11;
-        const double u2 = (fr * cr - l21 * u1) / l22;
-        U[(2 * g) * ldu + c] = u1;
-        U[(2 * g + 1) * ldu + c] = u2;
-    }
-}
-
-int launch_glmm_schur_rows(lrvb_ctx* c, const double* gsum, const double* loc, const double* scale, const double* closed,
-                           double* U, int ldu, int* bad) {
-    const i64 G = c->n_groups;
-    hipLaunchKernelGGL(glmm_schur_rows_kernel, dim3((unsigned)G), dim3(128), 0, c->stream, G, (int)c->P, gsum, loc, scale, closed, U, ldu, bad);
-    HIP_TRY(hipGetLastError());
-    return LRVB_OK;
-}
+i64 glmm_num_tiles(i64 N) { return (N + GLMM_T - 1) / GLMM_T; }
 
 // ---- streamed weight influence (lrvb_glmm_obs_influence) ----------------------------------------------------------------------
 // out[n - n0][q] = a1' (x_n . A_m[q] + A_e[q, g(n)]) + a2' ((x_n o x_n) . A_v[q] + A_r[q, g(n)]),  a1' = psi_rho - y_n, a2' = psi_s
 // PER UNIT WEIGHT (w_n does not enter: a row of weight zero gets the influence of adding it).  ONE pass over the rows n0..n1 in
-// their original order, X read once for any Q.  A workgroup (4 waves) walks tiles of GL_T = 64 rows:
+// their original order, X read once for any Q.  A workgroup (4 waves) walks tiles of GLMM_T = 64 rows:
 //   1. the tile (contiguous in X) is staged in LDS, row stride GI_XS; the columns P .. 4 ceil(P / 4) hold zeros;
 //   2. four lanes share a row for the two dot products and the quadrature, as in glmm_rows_kernel, but only the two sums E g1
 //      and E g2 are formed (no value, no second derivatives), and a1', a2' go to LDS;
@@ -227,30 +166,19 @@ constexpr int GI_XS = 66;                // LDS row stride: lanes (i, k) of an M
 
 typedef double gi_d4 __attribute__((ext_vector_type(4)));
 
-// The per-row part both influence kernels share (glmm_rows_kernel keeps its own five-sum loop): four lanes share the staged row
-// xr -- each a quarter of the two dot products, then a quarter of the nodes -- and every one of them returns e1 = psi_rho and
-// e2 = E g2 = 2 psi_s of group g's row.  Called by all lanes (xor shuffles); a lane whose row is not live returns zeros.
-__device__ __forceinline__ void gi_psi_derivs(const double* xr, bool live, int g, int q4, int P, int K, const double* ms,
-                                              const double* vs, const double* __restrict__ eg, const double* __restrict__ rg,
-                                              const double* sx, const double* sw, double& e1, double& e2)
+// The per-row part both influence kernels share: four lanes share the staged row xr -- each a quarter of the two dot products, then
+// (LogisticLik::infl) a quarter of the nodes -- and every one of them returns e1 = psi_rho and e2 = E g2 = 2 psi_s of group g's row.
+// Called by all lanes (xor shuffles); a lane whose row is not live returns zeros.
+__device__ __forceinline__ void gi_psi_derivs(const double* xr, bool live, int g, int q4, int P, const double* ms, const double* vs,
+                                              const double* __restrict__ eg, const double* __restrict__ rg, const LogisticLik::Lds& lik,
+                                              const LogisticLik::Args& la, double& e1, double& e2)
 {
     double rho = 0.0, s = 0.0;
     if (live) for (int j = q4; j < P; j += 4) { const double x = xr[j]; rho += x * ms[j]; s += x * x * vs[j]; }
     rho += __shfl_xor(rho, 1); s += __shfl_xor(s, 1);
     rho += __shfl_xor(rho, 2); s += __shfl_xor(s, 2);
-    e1 = 0.0; e2 = 0.0;
-    if (live) {
-        rho += eg[g]; s += rg[g];
-        const double sd = sqrt(fmax(s, 0.0));
-        for (int k = q4; k < K; k += 4) {
-            const double t = rho + sd * sx[k], wk = sw[k];
-            const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
-            const double sg = t >= 0.0 ? ie : e * ie;
-            e1 += wk * sg; e2 += wk * e * ie * ie;
-        }
-    }
-    e1 += __shfl_xor(e1, 1); e2 += __shfl_xor(e2, 1);
-    e1 += __shfl_xor(e1, 2); e2 += __shfl_xor(e2, 2);
+    if (live) { rho += eg[g]; s += rg[g]; }
+    LogisticLik::infl(lik, la, 0.0, live, q4, rho, s, e1, e2);
 }
 
 __global__ __launch_bounds__(256)
@@ -260,13 +188,14 @@ void glmm_infl_rows_kernel(i64 n0, i64 R /* rows of the window */, int P, const 
                            const double* __restrict__ gw, int K, const double* __restrict__ Ag /* Q x 2 P */,
                            const double* __restrict__ Al /* G x 2 Q */, int Q, double* __restrict__ out /* R x Q */)
 {
-    __shared__ double xs[GL_T * GI_XS], a1s[GL_T], a2s[GL_T], ms[64], vs[64], sx[128], sw[128];
-    __shared__ int s_gid[GL_T];
+    __shared__ double xs[GLMM_T * GI_XS], a1s[GLMM_T], a2s[GLMM_T], ms[64], vs[64];
+    __shared__ LogisticLik::Lds lik;
+    __shared__ int s_gid[GLMM_T];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, l4 = lane >> 4;
-    const double r2 = 1.4142135623730951, ispi = 0.5641895835477563;     // sqrt(2), 1 / sqrt(pi)
-    if (tid < K) { sx[tid] = r2 * gx[tid]; sw[tid] = ispi * gw[tid]; }
+    const LogisticLik::Args la{gx, gw, K};
+    LogisticLik::init(lik, la, tid);
     if (tid < 64) { ms[tid] = tid < P ? m[tid] : 0.0; vs[tid] = tid < P ? vb[tid] : 0.0; }
-    for (int e = tid; e < GL_T * GI_XS; e += 256) xs[e] = 0.0;           // the padding columns stay zero for the whole kernel
+    for (int e = tid; e < GLMM_T * GI_XS; e += 256) xs[e] = 0.0;           // the padding columns stay zero for the whole kernel
     const int KS = (P + 3) >> 2;                                         // k-steps of the contractions
     const int nqb = (Q + 15) >> 4;
     double bm[16], bv[16];
@@ -281,20 +210,20 @@ void glmm_infl_rows_kernel(i64 n0, i64 R /* rows of the window */, int P, const 
         }
     };
     if (nqb == 1) load_b(0);
-    const i64 n_tiles = (R + GL_T - 1) / GL_T;
+    const i64 n_tiles = (R + GLMM_T - 1) / GLMM_T;
     const int row = tid >> 2, q4 = tid & 3;
     for (i64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const i64 t0 = tile * GL_T;
-        const int rows = (int)(R - t0 < GL_T ? R - t0 : GL_T);
+        const i64 t0 = tile * GLMM_T;
+        const int rows = (int)(R - t0 < GLMM_T ? R - t0 : GLMM_T);
         __syncthreads();                                                 // the previous tile is consumed (and the nodes are in place)
-        if (tid < GL_T) s_gid[tid] = tid < rows ? gid[n0 + t0 + tid] : 0;
+        if (tid < GLMM_T) s_gid[tid] = tid < rows ? gid[n0 + t0 + tid] : 0;
         {
             const double* src = X + (n0 + t0) * (i64)P;
             for (int e = tid; e < rows * P; e += 256) { const int rr = e / P, cc = e - rr * P; xs[rr * GI_XS + cc] = src[e]; }
         }
         __syncthreads();
         double e1, e2;
-        gi_psi_derivs(xs + row * GI_XS, row < rows, s_gid[row], q4, P, K, ms, vs, eg, rg, sx, sw, e1, e2);
+        gi_psi_derivs(xs + row * GI_XS, row < rows, s_gid[row], q4, P, ms, vs, eg, rg, lik, la, e1, e2);
         if (q4 == 0) {
             double k1 = 0.0, k2 = 0.0;
             if (row < rows) { k1 = e1 - y[n0 + t0 + row]; k2 = 0.5 * e2; }
@@ -340,7 +269,7 @@ int launch_glmm_infl_rows(lrvb_ctx* c, i64 n0, i64 n1, const int* gid, const dou
     if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "logistic mixed model: P <= 64");
     const i64 R = n1 - n0;
     if (R <= 0) return LRVB_OK;
-    const i64 n_tiles = (R + GL_T - 1) / GL_T;
+    const i64 n_tiles = (R + GLMM_T - 1) / GLMM_T;
     const unsigned grid = (unsigned)(n_tiles < 2048 ? n_tiles : 2048);
     hipLaunchKernelGGL(glmm_infl_rows_kernel, dim3(grid), dim3(256), 0, c->stream, n0, R, (int)c->P, (const double*)c->X.p,
                        (const double*)c->y.p, gid, m, vb, eg, rg, gx, gw, K, Ag, Al, (int)Q, out);
@@ -361,62 +290,34 @@ void glmm_infl_gsum_kernel(i64 N, int P, i64 G, const double* __restrict__ X, co
                            const double* __restrict__ gx, const double* __restrict__ gw, int K, double* __restrict__ gsum,
                            double* __restrict__ part)
 {
-    __shared__ double xs[GL_T * GL_XS], cf[2 * GL_T], ms[64], vs[64], sx[128], sw[128];
-    __shared__ i64 s_row[GL_T];
-    __shared__ int s_gid[GL_T], s_whole[GL_T];
+    __shared__ double xs[GLMM_T * GL_XS], cf[2 * GLMM_T], ms[64], vs[64];
+    __shared__ LogisticLik::Lds lik;
+    __shared__ i64 s_row[GLMM_T];
+    __shared__ int s_gid[GLMM_T], s_whole[GLMM_T];
     const int tid = threadIdx.x;
     const int ncol = 2 + 2 * P;
-    const double r2 = 1.4142135623730951, ispi = 0.5641895835477563;
-    if (tid < K) { sx[tid] = r2 * gx[tid]; sw[tid] = ispi * gw[tid]; }
+    const LogisticLik::Args la{gx, gw, K};
+    LogisticLik::init(lik, la, tid);
     if (tid < P) { ms[tid] = m[tid]; vs[tid] = vb[tid]; }
-    const i64 n_tiles = (N + GL_T - 1) / GL_T;
+    const i64 n_tiles = (N + GLMM_T - 1) / GLMM_T;
     const int row = tid >> 2, q4 = tid & 3;
     const bool has_col = tid < 2 * P;                                    // output column 2 + tid; threads 0, 1 also a scalar column
     const bool sq = tid >= P;
     const int jc = sq ? tid - P : tid;
     for (i64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const i64 t0 = tile * GL_T;
-        const int rows = (int)(N - t0 < GL_T ? N - t0 : GL_T);
+        const i64 t0 = tile * GLMM_T;
+        const int rows = (int)(N - t0 < GLMM_T ? N - t0 : GLMM_T);
         __syncthreads();
-        if (tid < GL_T) {
-            int g = 0, whole = 0;
-            i64 pr = 0;
-            if (tid < rows) {
-                const i64 i = t0 + tid;
-                pr = perm[i];
-                i64 lo = 0, hi = G;                                      // the last g with offs[g] <= i (its offs[g + 1] > i)
-                while (hi - lo > 1) { const i64 mid = (lo + hi) >> 1; if (offs[mid] <= i) lo = mid; else hi = mid; }
-                g = (int)lo;
-                whole = (offs[lo] >= t0 && offs[lo + 1] <= t0 + GL_T) ? 1 : 0;
-            }
-            s_row[tid] = pr; s_gid[tid] = g; s_whole[tid] = whole;
-        }
-        __syncthreads();
-        for (int e = tid; e < rows * P; e += 256) { const int rr = e / P, cc = e - rr * P; xs[rr * GL_XS + cc] = X[s_row[rr] * P + cc]; }
-        __syncthreads();
+        gs_stage_sorted_tile<LogisticLik, GL_XS, false>(tid, t0, rows, P, 0, G, X, nullptr, perm, offs, la, lik, xs, s_row, s_gid, s_whole);
         double e1, e2;
-        gi_psi_derivs(xs + row * GL_XS, row < rows, s_gid[row], q4, P, K, ms, vs, eg, rg, sx, sw, e1, e2);
+        gi_psi_derivs(xs + row * GL_XS, row < rows, s_gid[row], q4, P, ms, vs, eg, rg, lik, la, e1, e2);
         if (q4 == 0) {
             double k1 = 0.0, k2 = 0.0;
             if (row < rows) { const i64 pr = s_row[row]; const double wi = w[pr]; k1 = wi * (e1 - y[pr]); k2 = wi * 0.5 * e2; }
-            cf[row] = k1; cf[GL_T + row] = k2;
+            cf[row] = k1; cf[GLMM_T + row] = k2;
         }
         __syncthreads();
-        if (has_col || tid < 2) {
-            double acc = 0.0, accs = 0.0;
-            int run_start = 0;
-            for (int rr = 0; rr < rows; ++rr) {
-                if (has_col) { double x = xs[rr * GL_XS + jc]; if (sq) x *= x; acc += cf[(sq ? GL_T : 0) + rr] * x; }
-                if (tid < 2) accs += cf[tid * GL_T + rr];
-                const int g = s_gid[rr];
-                if (rr == rows - 1 || s_gid[rr + 1] != g) {
-                    double* dst = s_whole[rr] ? gsum + (i64)g * ncol : part + (tile * 2 + (run_start == 0 ? 0 : 1)) * ncol;
-                    if (has_col) dst[2 + tid] = acc;
-                    if (tid < 2) dst[tid] = accs;
-                    acc = 0.0; accs = 0.0; run_start = rr + 1;
-                }
-            }
-        }
+        gl_walk_tile<2>(tid, tile, rows, ncol, has_col, jc, sq ? 1 : 0, sq, xs, cf, s_gid, s_whole, gsum, part);
     }
 }
 
@@ -437,7 +338,7 @@ int launch_glmm_infl_gsum(lrvb_ctx* c, const double* m, const double* vb, const 
     if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "logistic mixed model: P <= 64");
     const int ncol = 2 + 2 * (int)c->P;
     const i64* gdev = reinterpret_cast<const i64*>(c->groups.p);
-    const i64 n_tiles = (N + GL_T - 1) / GL_T;
+    const i64 n_tiles = glmm_num_tiles(N);
     const unsigned grid = (unsigned)(n_tiles < 2048 ? (n_tiles < 1 ? 1 : n_tiles) : 2048);
     hipLaunchKernelGGL(glmm_infl_gsum_kernel, dim3(grid), dim3(256), 0, c->stream, N, (int)c->P, G, (const double*)c->X.p,
                        (const double*)c->y.p, (const double*)c->w.p, gdev, gdev + N, m, vb, eg, rg, gx, gw, K, gsum, part);

@@ -3,8 +3,8 @@
 //   Poisson  (DESIGN.md section 26):  y_n ~ Poisson(exp(o_n + x_n . beta + z_n . u_g(n)))
 //   binomial:  y_n ~ Binomial(m_n, sigma(o_n + x_n . beta + z_n . u_g(n))), and through it NB2
 // Per observation rho_n = x_n . m + z_n . e_g, s_n = (x_n o x_n) . v + (z_n o z_n) . r_g and five coefficients a1, a2, c11, c12, c22.
-// Every kernel that walks the rows is written ONCE, as a template over a likelihood policy: LogisticLik
-// (the quadrature of k_glmm.hip: same nodes, same Stein-rule derivatives; with K = 1 and z = 1 it is that model) and PoissonLik
+// Every kernel that walks the rows is written ONCE, as a template over a likelihood policy (k_glmm_walk.h, DESIGN.md sections 27 and
+// 31): LogisticLik (the quadrature k_glmm.hip runs too; with K = 1 and z = 1 this is that model) and PoissonLik
 // (psi = E exp(t) = exp(o + rho + s / 2) exactly: ONE exp per row, no nodes); BinomialLik is the first that needs both kinds of
 // state, the nodes and staged per-row data.  A policy supplies
 //   Args / Lds      what only its kernels are handed (the nodes, a struct | the offset, a __restrict__ pointer) and its LDS (node
@@ -21,7 +21,7 @@
 //                   NB = 2 blocks per component (h z_k, h z_k^2), stored densely, against the logistic 4 at stride 16.
 //
 // glmm_slopes_rows_kernel is ONE pass over the rows in group-sorted order, built like glmm_rows_kernel: a workgroup (4 waves) walks
-// tiles of GS_T = 64 sorted rows.
+// tiles of GLMM_T = 64 sorted rows.
 //   1. the tile's rows of X are gathered through the permutation into LDS, and the row's K values of z behind them (columns
 //      P .. P + K - 1 of the same LDS row, stride GS_XS);
 //   2. four lanes share a row for the four dot products (lane q4 takes the x columns q4, q4 + 4, .. and the z column q4) and for
@@ -43,216 +43,12 @@
 // No atomics anywhere: the result is a fixed-order sum, bitwise reproducible.  Empty groups keep the zeros the caller wrote.
 // The Poisson policy does not clamp: where o + rho + s / 2 overflows the exponent, psi = inf reaches the sums and the entry refuses
 // the non-finite value (LRVB_ERR_INVALID).
-#include "lrvb_internal.h"
-#include "k_kernels.h"
-#include <math.h>
+#include "k_glmm_walk.h"
 #include <type_traits>
 
-constexpr int GS_T = 64;                 // sorted rows per tile (= GL_T of k_glmm.hip: glmm_fixup_kernel and glmm_num_tiles are shared)
 constexpr int GS_XS = 68;                // LDS row stride in doubles: 64 columns of x + 4 of z; 68 = 4 mod 32, so the 8 rows x 4 lanes
                                          // of a 32-lane half read 32 different 8-byte bank pairs in the dot products
 constexpr int GS_OWN = 4;                // border columns per thread: 4 K P <= 1024 = 4 x 256
-
-// ---- the two likelihood policies -------------------------------------------------------------------------------------------------
-// `kind` names one of the five coefficients: 0 = a1, 1 = a2, 2 = c11, 3 = c12, 4 = c22.
-struct LogisticLik {
-    struct Args { const double* gx; const double* gw; int nq; };         // Gauss-Hermite nodes and weights (device), 1 <= nq <= 128
-    struct Lds { double sx[128], sw[128]; };                             // sqrt(2) x_k, w_k / sqrt(pi)
-    struct Moments { double v, e1, e2, e3, e4; };
-    static constexpr const char* LIMITS = "logistic mixed model with slopes: P <= 64, 1 <= K <= 4, at most 128 nodes";
-    static bool args_ok(const Args& a) { return a.nq >= 1 && a.nq <= 128; }
-    static constexpr int NCF = 5, NB = 4, DK = 16;
-    static constexpr bool HAS_FACTOR = false;
-    static __device__ __forceinline__ int cf_row(int kind) { return kind; }
-    static __device__ __forceinline__ double cf_factor(int) { return 1.0; }                      // HAS_FACTOR is false: no flush multiplies by it
-    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return b * Kz + k; }
-    static __device__ __forceinline__ int d_stride(int) { return DK; }
-
-    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid)
-    {
-        const double r2 = 1.4142135623730951, ispi = 0.5641895835477563;     // sqrt(2), 1 / sqrt(pi)
-        if (tid < a.nq) { L.sx[tid] = r2 * a.gx[tid]; L.sw[tid] = ispi * a.gw[tid]; }
-    }
-    static __device__ __forceinline__ void stage_row(Lds&, const Args&, int, bool, i64) {}
-    static __device__ __forceinline__ double row_shift(const Lds&, int) { return 0.0; }
-    // the sibling of gi_psi_derivs (k_glmm.hip): e1 = psi_rho and e2 = E g2 = 2 psi_s
-    static __device__ __forceinline__ void infl(const Lds& L, const Args& a, double, bool live, int q4, double rho, double s, double& e1,
-                                                double& e2)
-    {
-        e1 = 0.0; e2 = 0.0;
-        if (live) {
-            const double sd = sqrt(fmax(s, 0.0));
-            for (int k = q4; k < a.nq; k += 4) {
-                const double t = rho + sd * L.sx[k], wk = L.sw[k];
-                const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
-                const double sg = t >= 0.0 ? ie : e * ie;
-                e1 += wk * sg; e2 += wk * e * ie * ie;
-            }
-        }
-        e1 += __shfl_xor(e1, 1); e2 += __shfl_xor(e2, 1);
-        e1 += __shfl_xor(e1, 2); e2 += __shfl_xor(e2, 2);
-    }
-    static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
-    {
-        double v = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0, e4 = 0.0;
-        if (live) {
-            const double sd = sqrt(fmax(s, 0.0));
-            for (int k = q4; k < a.nq; k += 4) {
-                const double t = rho + sd * L.sx[k], wk = L.sw[k];
-                const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
-                const double sp = (t > 0.0 ? t : 0.0) + log1p(e);
-                const double sg = t >= 0.0 ? ie : e * ie;
-                const double g2 = e * ie * ie;
-                const double om = (1.0 - e) * ie;                        // |1 - 2 sigma|
-                const double g3 = t >= 0.0 ? -g2 * om : g2 * om;
-                v += wk * sp; e1 += wk * sg; e2 += wk * g2; e3 += wk * g3; e4 += wk * g2 * (1.0 - 6.0 * g2);
-            }
-        }
-#pragma unroll
-        for (int off = 1; off <= 2; off <<= 1) {
-            v += __shfl_xor(v, off); e1 += __shfl_xor(e1, off); e2 += __shfl_xor(e2, off);
-            e3 += __shfl_xor(e3, off); e4 += __shfl_xor(e4, off);
-        }
-        return {v, e1, e2, e3, e4};
-    }
-    static __device__ __forceinline__ double coefs(const Lds&, int, const Moments& mo, double wi, double yi, double rho, double,
-                                                   double* k)
-    {
-        k[0] = wi * (mo.e1 - yi); k[1] = wi * 0.5 * mo.e2; k[2] = wi * mo.e2; k[3] = wi * 0.5 * mo.e3; k[4] = wi * 0.25 * mo.e4;
-        return wi * (mo.v - yi * rho);
-    }
-};
-
-struct PoissonLik {
-    typedef const double* __restrict__ Args;                             // the per-row offset (device, original row order) or nullptr
-    struct Lds { double s_off[GS_T]; };                                  // the offsets of the tile's rows
-    struct Moments {};
-    static constexpr const char* LIMITS = "Poisson mixed model: P <= 64, 1 <= K <= 4";
-    static bool args_ok(const Args&) { return true; }
-    static constexpr int NCF = 2, NB = 2, DK = 8;                        // coefficient rows [a1 | h]
-    static constexpr bool HAS_FACTOR = true;
-    static __device__ __forceinline__ int cf_row(int kind) { return kind == 0 ? 0 : 1; }
-    static __device__ __forceinline__ double cf_factor(int kind) { return kind == 4 ? 0.25 : ((kind & 1) ? 0.5 : 1.0); }
-    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return (b & 1) * Kz + k; }
-    static __device__ __forceinline__ int d_stride(int Kz) { return 2 * Kz; }
-
-    static __device__ __forceinline__ void init(Lds&, const Args&, int) {}
-    static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
-    {
-        L.s_off[t] = (a && live) ? a[src] : 0.0;
-    }
-    static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_off[row]; }
-    static __device__ __forceinline__ void infl(const Lds&, const Args&, double o, bool live, int, double rho, double s, double& e1,
-                                                double& e2)
-    {
-        e1 = e2 = live ? exp((rho + o) + 0.5 * s) : 0.0;
-    }
-    static __device__ __forceinline__ Moments moments(const Lds&, const Args&, bool, int, double, double) { return {}; }
-    static __device__ __forceinline__ double coefs(const Lds& L, int row, const Moments&, double wi, double yi, double rho, double s,
-                                                   double* k)
-    {
-        rho += L.s_off[row];
-        const double psi = exp(rho + 0.5 * s);
-        const double h = wi * psi;
-        k[0] = h - wi * yi; k[1] = h;
-        return wi * (psi - yi * rho);
-    }
-};
-
-// Binomial with a per-row trial count m_n and a per-row offset o_n: the logistic quadrature at rho + o, its
-// finished moments times m_n.  The data term is sum w [m E softplus(t) - y rho], t ~ N(rho, s), rho including the offset; with
-// m = y + phi and the offset o - log phi it is the negative binomial (NB2) term for a known dispersion phi.  Nodes AND staged
-// per-row data: the node tables and init are LogisticLik's, the staging is PoissonLik's with a second array.  The coefficient
-// layout is the logistic one.  m = 1 and o = 0 (either pointer null, or the values themselves) give the logistic instantiation
-// bit for bit: x * 1.0 and x + 0.0 are exact, and the products with m are kept out of every fused multiply-add, so that the
-// sums behind them are contracted as LogisticLik's are.
-struct BinomialLik {
-    struct Args { LogisticLik::Args q; const double* __restrict__ off; const double* __restrict__ trials; };   // either may be nullptr
-    struct Lds { LogisticLik::Lds q; double s_off[GS_T], s_m[GS_T]; };   // the node tables; the offsets and trials of the tile's rows
-    typedef LogisticLik::Moments Moments;
-    static constexpr const char* LIMITS = "binomial mixed model: P <= 64, 1 <= K <= 4, at most 128 nodes";
-    static bool args_ok(const Args& a) { return LogisticLik::args_ok(a.q); }
-    static constexpr int NCF = 5, NB = 4, DK = 16;
-    static constexpr bool HAS_FACTOR = false;
-    static __device__ __forceinline__ int cf_row(int kind) { return kind; }
-    static __device__ __forceinline__ double cf_factor(int) { return 1.0; }
-    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return b * Kz + k; }
-    static __device__ __forceinline__ int d_stride(int) { return DK; }
-
-    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { LogisticLik::init(L.q, a.q, tid); }
-    static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
-    {
-        L.s_off[t] = (a.off && live) ? a.off[src] : 0.0;
-        L.s_m[t] = (a.trials && live) ? a.trials[src] : 1.0;
-    }
-    static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_off[row]; }
-    // Neither infl nor moments is handed its row: in all three kernels the four lanes of staged row r are the threads 4 r .. 4 r + 3.
-    static __device__ __forceinline__ int lane_row() { return (int)(threadIdx.x >> 2); }
-    static __device__ __forceinline__ void infl(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& e1,
-                                                double& e2)
-    {
-        const double mt = L.s_m[lane_row()];
-        LogisticLik::infl(L.q, a.q, 0.0, live, q4, rho + o, s, e1, e2);
-        {
-#pragma clang fp contract(off)
-            e1 = e1 * mt; e2 = e2 * mt;
-        }
-    }
-    static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
-    {
-        const int row = lane_row();
-        const double mt = L.s_m[row];
-        Moments mo = LogisticLik::moments(L.q, a.q, live, q4, rho + L.s_off[row], s);
-        {
-#pragma clang fp contract(off)
-            mo.v = mo.v * mt; mo.e1 = mo.e1 * mt; mo.e2 = mo.e2 * mt; mo.e3 = mo.e3 * mt; mo.e4 = mo.e4 * mt;
-        }
-        return mo;
-    }
-    static __device__ __forceinline__ double coefs(const Lds& L, int row, const Moments& mo, double wi, double yi, double rho, double s,
-                                                   double* k)
-    {
-        return LogisticLik::coefs(L.q, row, mo, wi, yi, rho + L.s_off[row], s, k);
-    }
-};
-
-// ---- what the kernels over group-sorted rows share ----------------------------------------------------------------------------------
-// The head of a tile of sorted rows: thread t < GS_T finds row t0 + t's original position, its group (the last g with
-// offs[g] <= i) and whether that group lies whole inside the tile; then the tile's rows of X and Z are gathered into xs (row
-// stride XS, z behind the P columns of x).  Ends on a barrier.
-template <class Lik, int XS>
-__device__ __forceinline__ void gs_stage_sorted_tile(int tid, i64 t0, int rows, int P, int Kz, i64 G, const double* __restrict__ X,
-                                                     const double* __restrict__ Z, const i64* __restrict__ perm,
-                                                     const i64* __restrict__ offs, const typename Lik::Args& la, typename Lik::Lds& lik,
-                                                     double* xs, i64* s_row, int* s_gid, int* s_whole)
-{
-    if (tid < GS_T) {
-        int g = 0, whole = 0;
-        i64 pr = 0;
-        if (tid < rows) {
-            const i64 i = t0 + tid;
-            pr = perm[i];
-            i64 lo = 0, hi = G;                                          // the last g with offs[g] <= i (its offs[g + 1] > i)
-            while (hi - lo > 1) { const i64 mid = (lo + hi) >> 1; if (offs[mid] <= i) lo = mid; else hi = mid; }
-            g = (int)lo;
-            whole = (offs[lo] >= t0 && offs[lo + 1] <= t0 + GS_T) ? 1 : 0;
-        }
-        s_row[tid] = pr; s_gid[tid] = g; s_whole[tid] = whole;
-        Lik::stage_row(lik, la, tid, tid < rows, pr);
-    }
-    __syncthreads();
-    for (int e = tid; e < rows * P; e += 256) { const int rr = e / P, cc = e - rr * P; xs[rr * XS + cc] = X[s_row[rr] * P + cc]; }
-    for (int e = tid; e < rows * Kz; e += 256) { const int rr = e / Kz, cc = e - rr * Kz; xs[rr * XS + P + cc] = Z[s_row[rr] * Kz + cc]; }
-    __syncthreads();
-}
-
-// Where the walk of a tile flushes the segment that ends at a change of group: the group's own row of the result where the group
-// lies whole inside the tile, else one of the tile's two partial rows -- row 0 for the piece that began at the tile's first row
-// (the tail of a group cut by the boundary before it), row 1 for the piece that runs to its end.
-__device__ __forceinline__ double* gs_flush_dst(bool whole, int g, i64 tile, int run_start, int ncol, double* gsum, double* part)
-{
-    return whole ? gsum + (i64)g * ncol : part + (tile * 2 + (run_start == 0 ? 0 : 1)) * ncol;
-}
 
 template <class Lik>
 __global__ __launch_bounds__(256)
@@ -263,16 +59,16 @@ void glmm_slopes_rows_kernel(i64 N, int P, int Kz, i64 G, const double* __restri
                              double* __restrict__ coef, i64 NP, double* __restrict__ gsum, double* __restrict__ part,
                              double* __restrict__ vpart)
 {
-    __shared__ double xs[GS_T * GS_XS], dk[GS_T * Lik::DK], cf[Lik::NCF * GS_T], ms[64], vs[64], red[4];
+    __shared__ double xs[GLMM_T * GS_XS], dk[GLMM_T * Lik::DK], cf[Lik::NCF * GLMM_T], ms[64], vs[64], red[4];
     __shared__ typename Lik::Lds lik;
-    __shared__ i64 s_row[GS_T];
-    __shared__ int s_gid[GS_T], s_whole[GS_T];
+    __shared__ i64 s_row[GLMM_T];
+    __shared__ int s_gid[GLMM_T], s_whole[GLMM_T];
     const int tid = threadIdx.x;
     const int K2 = 2 * Kz, ND = Lik::NB * Kz, DS = Lik::d_stride(Kz);
     const int nsc = K2 + Kz * (K2 + 1), nbord = 4 * Kz * P, ncol = nsc + nbord;
     Lik::init(lik, la, tid);
     if (tid < P) { ms[tid] = m[tid]; vs[tid] = vb[tid]; }
-    const i64 n_tiles = (N + GS_T - 1) / GS_T;
+    const i64 n_tiles = (N + GLMM_T - 1) / GLMM_T;
     const int row = tid >> 2, q4 = tid & 3;
     // the border columns of this thread: column t = tid + 256 i is block bk = t / P (b = bk / K, k = bk - b K) and x column
     // j = t - bk P; it reads the product o_d(b, k), squares x for b >= 2 and (Poisson) carries the factor of its coefficient
@@ -303,8 +99,8 @@ void glmm_slopes_rows_kernel(i64 N, int P, int Kz, i64 G, const double* __restri
     const int zi = P + (s_i < Kz ? s_i : s_i - Kz), zj = P + (s_j < Kz ? s_j : s_j - Kz);    // unused where the factor is 1
     const bool i_one = s_i >= K2, i_sq = s_i >= Kz, j_one = s_j >= K2, j_sq = s_j >= Kz;
     for (i64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const i64 t0 = tile * GS_T;
-        const int rows = (int)(N - t0 < GS_T ? N - t0 : GS_T);
+        const i64 t0 = tile * GLMM_T;
+        const int rows = (int)(N - t0 < GLMM_T ? N - t0 : GLMM_T);
         __syncthreads();                                                 // the previous tile is consumed (and the nodes, m, v are in place)
         gs_stage_sorted_tile<Lik, GS_XS>(tid, t0, rows, P, Kz, G, X, Z, perm, offs, la, lik, xs, s_row, s_gid, s_whole);
         double rho = 0.0, s = 0.0;
@@ -332,7 +128,7 @@ void glmm_slopes_rows_kernel(i64 N, int P, int Kz, i64 G, const double* __restri
                 for (int i = 0; i < Lik::NCF; ++i) coef[i * NP + pr] = k[i];
             }
 #pragma unroll
-            for (int i = 0; i < Lik::NCF; ++i) cf[i * GS_T + row] = k[i];
+            for (int i = 0; i < Lik::NCF; ++i) cf[i * GLMM_T + row] = k[i];
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) contrib += __shfl_xor(contrib, off);
@@ -343,7 +139,7 @@ void glmm_slopes_rows_kernel(i64 N, int P, int Kz, i64 G, const double* __restri
         for (int e = tid; e < rows * ND; e += 256) {
             const int rr = e / ND, bk = e - rr * ND, b = bk / Kz, k = bk - b * Kz;
             const double z = xs[rr * GS_XS + P + k];
-            dk[rr * DS + bk] = cf[Lik::cf_row(b == 0 ? 2 : (b == 3 ? 4 : 3)) * GS_T + rr] * ((b & 1) ? z * z : z);
+            dk[rr * DS + bk] = cf[Lik::cf_row(b == 0 ? 2 : (b == 3 ? 4 : 3)) * GLMM_T + rr] * ((b & 1) ? z * z : z);
         }
         __syncthreads();
         // segmented sums over the tile's rows, in row order
@@ -360,7 +156,7 @@ void glmm_slopes_rows_kernel(i64 N, int P, int Kz, i64 G, const double* __restri
                     double fi = 1.0, fj = 1.0;
                     if (!i_one) { fi = xr[zi]; if (i_sq) fi *= fi; }
                     if (!j_one) { fj = xr[zj]; if (j_sq) fj *= fj; }
-                    accs += cf[s_c * GS_T + rr] * (fi * fj);
+                    accs += cf[s_c * GLMM_T + rr] * (fi * fj);
                 }
                 const int g = s_gid[rr];
                 if (rr == rows - 1 || s_gid[rr + 1] != g) {
@@ -399,8 +195,15 @@ static int gs_launch_rows(lrvb_ctx* c, int Kz, const double* Z, typename Lik::Ar
     return LRVB_OK;
 }
 
+// Z = nullptr is the unit design: the logistic model with one effect per group on its own kernels (k_glmm.hip)
+static int gs_unit_design(const GlmmLik& lik, int Kz) {
+    if (lik.kind != GLMM_LOGISTIC || Kz != 1) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the unit group design is the logistic mixed model with one effect per group");
+    return LRVB_OK;
+}
+
 int launch_glmm_slopes_rows(lrvb_ctx* c, const GlmmLik& lik, int Kz, const double* Z, const double* m, const double* vb, const double* eg,
                             const double* rg, double* coef, i64 NP, double* gsum, double* part, double* vpart) {
+    if (!Z) { LRVB_TRY(gs_unit_design(lik, Kz)); return launch_glmm_rows(c, m, vb, eg, rg, lik.gx, lik.gw, lik.n_nodes, coef, NP, gsum, part, vpart); }
     if (lik.kind == GLMM_POISSON) return gs_launch_rows<PoissonLik>(c, Kz, Z, lik.off, m, vb, eg, rg, coef, NP, gsum, part, vpart);
     if (lik.kind == GLMM_BINOMIAL)
         return gs_launch_rows<BinomialLik>(c, Kz, Z, {{lik.gx, lik.gw, lik.n_nodes}, lik.off, lik.trials}, m, vb, eg, rg, coef, NP, gsum, part,
@@ -586,7 +389,7 @@ int launch_glmm_slopes_solve(lrvb_ctx* c, int Kz, bool back, i64 Q, const double
 // ---- streamed weight influence (lrvb_glmm_slopes_obs_influence / lrvb_glmm_poisson_obs_influence) ---------
 // out[n - n0][q] = a1' (x_n . A_m[q] + sum_k z_nk A_e[q, g(n), k]) + a2' ((x_n o x_n) . A_v[q] + sum_k z_nk^2 A_r[q, g(n), k]),
 // a1' = psi_rho - y_n, a2' = psi_s PER UNIT WEIGHT (w_n does not enter).  Built like glmm_infl_rows_kernel (k_glmm.hip): ONE pass
-// over the rows n0..n1 in their original order, X and Z read once for any Q; a workgroup (4 waves) walks tiles of GS_T = 64 rows:
+// over the rows n0..n1 in their original order, X and Z read once for any Q; a workgroup (4 waves) walks tiles of GLMM_T = 64 rows:
 //   1. the tile (contiguous in X) is staged in LDS, row stride GSI_XS, the row's K values of z behind its x columns (columns
 //      P .. P + K - 1, as glmm_slopes_rows_kernel stages them);
 //   2. four lanes share a row for the two dot products (lane q4 also takes the z column q4) and the likelihood's Lik::infl (the
@@ -648,13 +451,13 @@ void gsi_infl_rows(i64 n0, i64 R /* rows of the window */, int P, int Kz, const 
                    const double* __restrict__ Ag /* Q x 2 P */, const double* __restrict__ Al /* G x 2 K x Q */, int Q,
                    double* __restrict__ out /* R x Q */)
 {
-    __shared__ double xs[GS_T * GSI_XS], a1s[GS_T], a2s[GS_T], ms[64], vs[64];
+    __shared__ double xs[GLMM_T * GSI_XS], a1s[GLMM_T], a2s[GLMM_T], ms[64], vs[64];
     __shared__ typename Lik::Lds lik;
-    __shared__ int s_gid[GS_T];
+    __shared__ int s_gid[GLMM_T];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, l4 = lane >> 4;
     Lik::init(lik, la, tid);
     if (tid < 64) { ms[tid] = tid < P ? m[tid] : 0.0; vs[tid] = tid < P ? vb[tid] : 0.0; }
-    for (int e = tid; e < GS_T * GSI_XS; e += 256) xs[e] = 0.0;          // what no tile writes stays zero (finite) for the whole kernel
+    for (int e = tid; e < GLMM_T * GSI_XS; e += 256) xs[e] = 0.0;          // what no tile writes stays zero (finite) for the whole kernel
     const int KS = (P + 3) >> 2;                                         // k-steps of the contractions
     const int nqb = (Q + 15) >> 4;
     const int K2 = 2 * Kz;
@@ -670,13 +473,13 @@ void gsi_infl_rows(i64 n0, i64 R /* rows of the window */, int P, int Kz, const 
         }
     };
     if (nqb == 1) load_b(0);
-    const i64 n_tiles = (R + GS_T - 1) / GS_T;
+    const i64 n_tiles = (R + GLMM_T - 1) / GLMM_T;
     const int row = tid >> 2, q4 = tid & 3;
     for (i64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const i64 t0 = tile * GS_T;
-        const int rows = (int)(R - t0 < GS_T ? R - t0 : GS_T);
+        const i64 t0 = tile * GLMM_T;
+        const int rows = (int)(R - t0 < GLMM_T ? R - t0 : GLMM_T);
         __syncthreads();                                                 // the previous tile is consumed (and the nodes, m, v are in place)
-        if (tid < GS_T) {
+        if (tid < GLMM_T) {
             s_gid[tid] = tid < rows ? gid[n0 + t0 + tid] : 0;
             Lik::stage_row(lik, la, tid, tid < rows, n0 + t0 + tid);
         }
@@ -775,7 +578,7 @@ static int gs_launch_infl_rows(lrvb_ctx* c, int Kz, const double* Z, typename Li
     if (c->P > 64 || Kz < 1 || Kz > 4 || !Lik::args_ok(la)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "%s", Lik::LIMITS);
     const i64 R = n1 - n0;
     if (R <= 0) return LRVB_OK;
-    const i64 n_tiles = (R + GS_T - 1) / GS_T;
+    const i64 n_tiles = (R + GLMM_T - 1) / GLMM_T;
     const unsigned grid = (unsigned)(n_tiles < 2048 ? n_tiles : 2048);
     if constexpr (std::is_same<Lik, PoissonLik>::value)
         hipLaunchKernelGGL(glmm_poisson_infl_rows_kernel, dim3(grid), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
@@ -794,6 +597,7 @@ static int gs_launch_infl_rows(lrvb_ctx* c, int Kz, const double* Z, typename Li
 int launch_glmm_slopes_infl_rows(lrvb_ctx* c, const GlmmLik& lik, int Kz, const double* Z, i64 n0, i64 n1, const int* gid, const double* m,
                                  const double* vb, const double* eg, const double* rg, const double* Ag, const double* Al, i64 Q,
                                  double* out) {
+    if (!Z) { LRVB_TRY(gs_unit_design(lik, Kz)); return launch_glmm_infl_rows(c, n0, n1, gid, m, vb, eg, rg, lik.gx, lik.gw, lik.n_nodes, Ag, Al, Q, out); }
     if (lik.kind == GLMM_POISSON) return gs_launch_infl_rows<PoissonLik>(c, Kz, Z, lik.off, n0, n1, gid, m, vb, eg, rg, Ag, Al, Q, out);
     if (lik.kind == GLMM_BINOMIAL)
         return gs_launch_infl_rows<BinomialLik>(c, Kz, Z, {{lik.gx, lik.gw, lik.n_nodes}, lik.off, lik.trials}, n0, n1, gid, m, vb, eg, rg, Ag,
@@ -816,23 +620,23 @@ void glmm_slopes_infl_gsum_kernel(i64 N, int P, int Kz, i64 G, const double* __r
                                   const double* __restrict__ eg, const double* __restrict__ rg, typename Lik::Args la,
                                   double* __restrict__ gsum, double* __restrict__ part)
 {
-    __shared__ double xs[GS_T * GSI_XS], cf[2 * GS_T], ms[64], vs[64];
+    __shared__ double xs[GLMM_T * GSI_XS], cf[2 * GLMM_T], ms[64], vs[64];
     __shared__ typename Lik::Lds lik;
-    __shared__ i64 s_row[GS_T];
-    __shared__ int s_gid[GS_T], s_whole[GS_T];
+    __shared__ i64 s_row[GLMM_T];
+    __shared__ int s_gid[GLMM_T], s_whole[GLMM_T];
     const int tid = threadIdx.x;
     const int K2 = 2 * Kz, ncol = K2 + 2 * P;
     Lik::init(lik, la, tid);
     if (tid < P) { ms[tid] = m[tid]; vs[tid] = vb[tid]; }
-    const i64 n_tiles = (N + GS_T - 1) / GS_T;
+    const i64 n_tiles = (N + GLMM_T - 1) / GLMM_T;
     const int row = tid >> 2, q4 = tid & 3;
     // output column tid (< ncol): a1 z_k | a2 z_k^2 | a1 x_j | a2 x_j^2 -- the staged column jc, squared or not
     const bool has_col = tid < ncol;
     const bool sq = has_col && (tid < K2 ? tid >= Kz : tid >= K2 + P);
     const int jc = !has_col ? 0 : (tid < Kz ? P + tid : (tid < K2 ? P + tid - Kz : (tid < K2 + P ? tid - K2 : tid - K2 - P)));
     for (i64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const i64 t0 = tile * GS_T;
-        const int rows = (int)(N - t0 < GS_T ? N - t0 : GS_T);
+        const i64 t0 = tile * GLMM_T;
+        const int rows = (int)(N - t0 < GLMM_T ? N - t0 : GLMM_T);
         __syncthreads();
         gs_stage_sorted_tile<Lik, GSI_XS>(tid, t0, rows, P, Kz, G, X, Z, perm, offs, la, lik, xs, s_row, s_gid, s_whole);
         double e1, e2;
@@ -840,7 +644,7 @@ void glmm_slopes_infl_gsum_kernel(i64 N, int P, int Kz, i64 G, const double* __r
         if (q4 == 0) {
             double k1 = 0.0, k2 = 0.0;
             if (row < rows) { const i64 pr = s_row[row]; const double wi = w[pr]; k1 = wi * (e1 - y[pr]); k2 = wi * 0.5 * e2; }
-            cf[row] = k1; cf[GS_T + row] = k2;
+            cf[row] = k1; cf[GLMM_T + row] = k2;
         }
         __syncthreads();
         if (has_col) {
@@ -849,7 +653,7 @@ void glmm_slopes_infl_gsum_kernel(i64 N, int P, int Kz, i64 G, const double* __r
             for (int rr = 0; rr < rows; ++rr) {
                 double x = xs[rr * GSI_XS + jc];
                 if (sq) x *= x;
-                acc += cf[(sq ? GS_T : 0) + rr] * x;
+                acc += cf[(sq ? GLMM_T : 0) + rr] * x;
                 const int g = s_gid[rr];
                 if (rr == rows - 1 || s_gid[rr + 1] != g) {
                     gs_flush_dst(s_whole[rr], g, tile, run_start, ncol, gsum, part)[tid] = acc;
@@ -896,6 +700,7 @@ static int gs_launch_infl_gsum(lrvb_ctx* c, int Kz, const double* Z, typename Li
 
 int launch_glmm_slopes_infl_gsum(lrvb_ctx* c, const GlmmLik& lik, int Kz, const double* Z, const double* m, const double* vb,
                                  const double* eg, const double* rg, double* gsum, double* part) {
+    if (!Z) { LRVB_TRY(gs_unit_design(lik, Kz)); return launch_glmm_infl_gsum(c, m, vb, eg, rg, lik.gx, lik.gw, lik.n_nodes, gsum, part); }
     if (lik.kind == GLMM_POISSON) return gs_launch_infl_gsum<PoissonLik>(c, Kz, Z, lik.off, m, vb, eg, rg, gsum, part);
     if (lik.kind == GLMM_BINOMIAL)
         return gs_launch_infl_gsum<BinomialLik>(c, Kz, Z, {{lik.gx, lik.gw, lik.n_nodes}, lik.off, lik.trials}, m, vb, eg, rg, gsum, part);

@@ -1,0 +1,214 @@
+// k_glmm_walk.h -- what every mixed-model kernel that walks the rows shares (DESIGN.md sections 27 and 31): the tile size, the
+// likelihood policies, the head of a tile of group-sorted rows and the destination of a flushed segment.  Included by k_glmm.hip
+// (the random intercept: its own three kernels over the rows, on LogisticLik) and by k_glmm_slopes.hip (K <= 4 effects per group: the
+// three walks templated over the policy).  glmm_fixup_kernel and glmm_num_tiles keep their ONE definition in k_glmm.hip (a
+// __global__ function in a header would be compiled into both code objects); k_kernels.h and lrvb_internal.h declare them.
+#pragma once
+#include "lrvb_internal.h"
+#include "k_kernels.h"
+#include <math.h>
+
+constexpr int GLMM_T = 64;               // sorted rows per tile, for every walk, glmm_fixup_kernel and glmm_num_tiles
+
+// ---- the likelihood policies -------------------------------------------------------------------------------------------------------
+// `kind` names one of the five coefficients: 0 = a1, 1 = a2, 2 = c11, 3 = c12, 4 = c22.
+struct LogisticLik {
+    struct Args { const double* gx; const double* gw; int nq; };         // Gauss-Hermite nodes and weights (device), 1 <= nq <= 128
+    struct Lds { double sx[128], sw[128]; };                             // sqrt(2) x_k, w_k / sqrt(pi)
+    struct Moments { double v, e1, e2, e3, e4; };
+    static constexpr const char* LIMITS = "logistic mixed model with slopes: P <= 64, 1 <= K <= 4, at most 128 nodes";
+    static bool args_ok(const Args& a) { return a.nq >= 1 && a.nq <= 128; }
+    static constexpr int NCF = 5, NB = 4, DK = 16;
+    static constexpr bool HAS_FACTOR = false;
+    static __device__ __forceinline__ int cf_row(int kind) { return kind; }
+    static __device__ __forceinline__ double cf_factor(int) { return 1.0; }                      // HAS_FACTOR is false: no flush multiplies by it
+    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return b * Kz + k; }
+    static __device__ __forceinline__ int d_stride(int) { return DK; }
+
+    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid)
+    {
+        const double r2 = 1.4142135623730951, ispi = 0.5641895835477563;     // sqrt(2), 1 / sqrt(pi)
+        if (tid < a.nq) { L.sx[tid] = r2 * a.gx[tid]; L.sw[tid] = ispi * a.gw[tid]; }
+    }
+    static __device__ __forceinline__ void stage_row(Lds&, const Args&, int, bool, i64) {}
+    static __device__ __forceinline__ double row_shift(const Lds&, int) { return 0.0; }
+    // e1 = psi_rho and e2 = E g2 = 2 psi_s (gi_psi_derivs of k_glmm.hip and gsi_psi_derivs of k_glmm_slopes.hip end in it)
+    static __device__ __forceinline__ void infl(const Lds& L, const Args& a, double, bool live, int q4, double rho, double s, double& e1,
+                                                double& e2)
+    {
+        e1 = 0.0; e2 = 0.0;
+        if (live) {
+            const double sd = sqrt(fmax(s, 0.0));
+            for (int k = q4; k < a.nq; k += 4) {
+                const double t = rho + sd * L.sx[k], wk = L.sw[k];
+                const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
+                const double sg = t >= 0.0 ? ie : e * ie;
+                e1 += wk * sg; e2 += wk * e * ie * ie;
+            }
+        }
+        e1 += __shfl_xor(e1, 1); e2 += __shfl_xor(e2, 1);
+        e1 += __shfl_xor(e1, 2); e2 += __shfl_xor(e2, 2);
+    }
+    static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
+    {
+        double v = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0, e4 = 0.0;
+        if (live) {
+            const double sd = sqrt(fmax(s, 0.0));
+            for (int k = q4; k < a.nq; k += 4) {
+                const double t = rho + sd * L.sx[k], wk = L.sw[k];
+                const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
+                const double sp = (t > 0.0 ? t : 0.0) + log1p(e);
+                const double sg = t >= 0.0 ? ie : e * ie;
+                const double g2 = e * ie * ie;
+                const double om = (1.0 - e) * ie;                        // |1 - 2 sigma|
+                const double g3 = t >= 0.0 ? -g2 * om : g2 * om;
+                v += wk * sp; e1 += wk * sg; e2 += wk * g2; e3 += wk * g3; e4 += wk * g2 * (1.0 - 6.0 * g2);
+            }
+        }
+#pragma unroll
+        for (int off = 1; off <= 2; off <<= 1) {
+            v += __shfl_xor(v, off); e1 += __shfl_xor(e1, off); e2 += __shfl_xor(e2, off);
+            e3 += __shfl_xor(e3, off); e4 += __shfl_xor(e4, off);
+        }
+        return {v, e1, e2, e3, e4};
+    }
+    static __device__ __forceinline__ double coefs(const Lds&, int, const Moments& mo, double wi, double yi, double rho, double,
+                                                   double* k)
+    {
+        k[0] = wi * (mo.e1 - yi); k[1] = wi * 0.5 * mo.e2; k[2] = wi * mo.e2; k[3] = wi * 0.5 * mo.e3; k[4] = wi * 0.25 * mo.e4;
+        return wi * (mo.v - yi * rho);
+    }
+};
+
+struct PoissonLik {
+    typedef const double* __restrict__ Args;                             // the per-row offset (device, original row order) or nullptr
+    struct Lds { double s_off[GLMM_T]; };                                  // the offsets of the tile's rows
+    struct Moments {};
+    static constexpr const char* LIMITS = "Poisson mixed model: P <= 64, 1 <= K <= 4";
+    static bool args_ok(const Args&) { return true; }
+    static constexpr int NCF = 2, NB = 2, DK = 8;                        // coefficient rows [a1 | h]
+    static constexpr bool HAS_FACTOR = true;
+    static __device__ __forceinline__ int cf_row(int kind) { return kind == 0 ? 0 : 1; }
+    static __device__ __forceinline__ double cf_factor(int kind) { return kind == 4 ? 0.25 : ((kind & 1) ? 0.5 : 1.0); }
+    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return (b & 1) * Kz + k; }
+    static __device__ __forceinline__ int d_stride(int Kz) { return 2 * Kz; }
+
+    static __device__ __forceinline__ void init(Lds&, const Args&, int) {}
+    static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
+    {
+        L.s_off[t] = (a && live) ? a[src] : 0.0;
+    }
+    static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_off[row]; }
+    static __device__ __forceinline__ void infl(const Lds&, const Args&, double o, bool live, int, double rho, double s, double& e1,
+                                                double& e2)
+    {
+        e1 = e2 = live ? exp((rho + o) + 0.5 * s) : 0.0;
+    }
+    static __device__ __forceinline__ Moments moments(const Lds&, const Args&, bool, int, double, double) { return {}; }
+    static __device__ __forceinline__ double coefs(const Lds& L, int row, const Moments&, double wi, double yi, double rho, double s,
+                                                   double* k)
+    {
+        rho += L.s_off[row];
+        const double psi = exp(rho + 0.5 * s);
+        const double h = wi * psi;
+        k[0] = h - wi * yi; k[1] = h;
+        return wi * (psi - yi * rho);
+    }
+};
+
+// Binomial with a per-row trial count m_n and a per-row offset o_n: the logistic quadrature at rho + o, its
+// finished moments times m_n.  The data term is sum w [m E softplus(t) - y rho], t ~ N(rho, s), rho including the offset; with
+// m = y + phi and the offset o - log phi it is the negative binomial (NB2) term for a known dispersion phi.  Nodes AND staged
+// per-row data: the node tables and init are LogisticLik's, the staging is PoissonLik's with a second array.  The coefficient
+// layout is the logistic one.  m = 1 and o = 0 (either pointer null, or the values themselves) give the logistic instantiation
+// bit for bit: x * 1.0 and x + 0.0 are exact, and the products with m are kept out of every fused multiply-add, so that the
+// sums behind them are contracted as LogisticLik's are.
+struct BinomialLik {
+    struct Args { LogisticLik::Args q; const double* __restrict__ off; const double* __restrict__ trials; };   // either may be nullptr
+    struct Lds { LogisticLik::Lds q; double s_off[GLMM_T], s_m[GLMM_T]; };   // the node tables; the offsets and trials of the tile's rows
+    typedef LogisticLik::Moments Moments;
+    static constexpr const char* LIMITS = "binomial mixed model: P <= 64, 1 <= K <= 4, at most 128 nodes";
+    static bool args_ok(const Args& a) { return LogisticLik::args_ok(a.q); }
+    static constexpr int NCF = 5, NB = 4, DK = 16;
+    static constexpr bool HAS_FACTOR = false;
+    static __device__ __forceinline__ int cf_row(int kind) { return kind; }
+    static __device__ __forceinline__ double cf_factor(int) { return 1.0; }
+    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return b * Kz + k; }
+    static __device__ __forceinline__ int d_stride(int) { return DK; }
+
+    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { LogisticLik::init(L.q, a.q, tid); }
+    static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
+    {
+        L.s_off[t] = (a.off && live) ? a.off[src] : 0.0;
+        L.s_m[t] = (a.trials && live) ? a.trials[src] : 1.0;
+    }
+    static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_off[row]; }
+    // Neither infl nor moments is handed its row: in all three kernels the four lanes of staged row r are the threads 4 r .. 4 r + 3.
+    static __device__ __forceinline__ int lane_row() { return (int)(threadIdx.x >> 2); }
+    static __device__ __forceinline__ void infl(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& e1,
+                                                double& e2)
+    {
+        const double mt = L.s_m[lane_row()];
+        LogisticLik::infl(L.q, a.q, 0.0, live, q4, rho + o, s, e1, e2);
+        {
+#pragma clang fp contract(off)
+            e1 = e1 * mt; e2 = e2 * mt;
+        }
+    }
+    static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
+    {
+        const int row = lane_row();
+        const double mt = L.s_m[row];
+        Moments mo = LogisticLik::moments(L.q, a.q, live, q4, rho + L.s_off[row], s);
+        {
+#pragma clang fp contract(off)
+            mo.v = mo.v * mt; mo.e1 = mo.e1 * mt; mo.e2 = mo.e2 * mt; mo.e3 = mo.e3 * mt; mo.e4 = mo.e4 * mt;
+        }
+        return mo;
+    }
+    static __device__ __forceinline__ double coefs(const Lds& L, int row, const Moments& mo, double wi, double yi, double rho, double s,
+                                                   double* k)
+    {
+        return LogisticLik::coefs(L.q, row, mo, wi, yi, rho + L.s_off[row], s, k);
+    }
+};
+
+// ---- what the kernels over group-sorted rows share ----------------------------------------------------------------------------------
+// The head of a tile of sorted rows: thread t < GLMM_T finds row t0 + t's original position, its group (the last g with
+// offs[g] <= i) and whether that group lies whole inside the tile; then the tile's rows of X and Z are gathered into xs (row
+// stride XS, z behind the P columns of x).  HAS_Z = false is the unit design of the random intercept: no Z is read, and no division
+// by Kz is emitted.  Ends on a barrier.
+template <class Lik, int XS, bool HAS_Z = true>
+__device__ __forceinline__ void gs_stage_sorted_tile(int tid, i64 t0, int rows, int P, int Kz, i64 G, const double* __restrict__ X,
+                                                     const double* __restrict__ Z, const i64* __restrict__ perm,
+                                                     const i64* __restrict__ offs, const typename Lik::Args& la, typename Lik::Lds& lik,
+                                                     double* xs, i64* s_row, int* s_gid, int* s_whole)
+{
+    if (tid < GLMM_T) {
+        int g = 0, whole = 0;
+        i64 pr = 0;
+        if (tid < rows) {
+            const i64 i = t0 + tid;
+            pr = perm[i];
+            i64 lo = 0, hi = G;                                          // the last g with offs[g] <= i (its offs[g + 1] > i)
+            while (hi - lo > 1) { const i64 mid = (lo + hi) >> 1; if (offs[mid] <= i) lo = mid; else hi = mid; }
+            g = (int)lo;
+            whole = (offs[lo] >= t0 && offs[lo + 1] <= t0 + GLMM_T) ? 1 : 0;
+        }
+        s_row[tid] = pr; s_gid[tid] = g; s_whole[tid] = whole;
+        Lik::stage_row(lik, la, tid, tid < rows, pr);
+    }
+    __syncthreads();
+    for (int e = tid; e < rows * P; e += 256) { const int rr = e / P, cc = e - rr * P; xs[rr * XS + cc] = X[s_row[rr] * P + cc]; }
+    if constexpr (HAS_Z)
+        for (int e = tid; e < rows * Kz; e += 256) { const int rr = e / Kz, cc = e - rr * Kz; xs[rr * XS + P + cc] = Z[s_row[rr] * Kz + cc]; }
+    __syncthreads();
+}
+
+// Where the walk of a tile flushes the segment that ends at a change of group: the group's own row of the result where the group
+// lies whole inside the tile, else one of the tile's two partial rows -- row 0 for the piece that began at the tile's first row
+// (the tail of a group cut by the boundary before it), row 1 for the piece that runs to its end.
+__device__ __forceinline__ double* gs_flush_dst(bool whole, int g, i64 tile, int run_start, int ncol, double* gsum, double* part)
+{
+    return whole ? gsum + (i64)g * ncol : part + (tile * 2 + (run_start == 0 ? 0 : 1)) * ncol;
+}

@@ -231,7 +231,7 @@ extern "C" int lrvb_ctx_destroy(lrvb_ctx* c) {
     DevBuf* all[] = { &c->X, &c->y, &c->w, &c->quadA, &c->quadM, &c->quadB, &c->theta, &c->eta, &c->j1, &c->j2,
                       &c->vtmp, &c->vtmp2, &c->vtmp3, &c->g_eta, &c->g_free, &c->lp, &c->cw, &c->zbuf,
                       &c->part_vec, &c->part_val, &c->stats, &c->tile_part, &c->Heta, &c->Hfree, &c->Jdense,
-                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn, &c->glmm, &c->gz, &c->goff, &c->gtr, &c->glmms, &c->glmms_fac, &c->glmms_T,
+                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn, &c->gz, &c->goff, &c->gtr, &c->glmms, &c->glmms_fac, &c->glmms_T,
                       &c->sm.labels, &c->sm.p, &c->sm.wpad, &c->sm.work, &c->sm.col, &c->sm.tiles, &c->sm.rows };
     for (DevBuf* b : all) buf_free(*b);
     if (c->host_pinned) (void)hipHostFree(c->host_pinned);
@@ -412,6 +412,7 @@ static int check_point_len(const lrvb_ctx* c, i64 got, bool is_free) {
 
 // ---- small elementwise kernels used only by the orchestration -------------------------
 static inline unsigned nb256(i64 n) { return (unsigned)((n + 255) / 256); }
+static inline i64 up(i64 n) { return ((n + 7) / 8) * 8; }      // doubles to a 64-byte boundary: every segment of a carved buffer starts on one
 #define EW(kernel, n, ...) do { if ((n) > 0) { hipLaunchKernelGGL(kernel, dim3(nb256(n)), dim3(256), 0, c->stream, n, __VA_ARGS__); HIP_TRY(hipGetLastError()); } } while (0)
 
 // ---- evaluation state -----------------------------------------------------------------
@@ -1626,7 +1627,6 @@ extern "C" int lrvb_set_groups(lrvb_ctx* c, const int32_t* gid, int64_t n, int64
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->n_groups = n_groups;
     c->gstats_valid = false;
-    c->glmm_valid = false;
     c->glmms_drop();
     if (c->gz_n != n) { c->gz_n = 0; c->gz_K = 0; }      // a group design of another row count is dropped
     c->zs_valid = false; c->ws_valid = false;
@@ -2559,106 +2559,6 @@ extern "C" int lrvb_logitnormal_terms(lrvb_ctx* c, const double* mean, const dou
     return LRVB_OK;
 }
 
-// ---- logistic mixed model with a random intercept (k_glmm.hip) ----------------------------------------------------------------
-// c->glmm: [H blocks (3 P^2) | group sums (G x (5 + 4 P)) | gradient (2 P) | value] -- every sum over observations of the call,
-// adjacent, so that the part that was formed goes through the reduce hook in one piece.  c->work1 holds the scratch:
-// [nodes 256 | m, v (2 up(P)) | e, r (2 up(G)) | five coefficient vectors (5 NP, original order, zero past N) | tile partials]
-extern "C" int lrvb_glmm_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc, const double* r_loc,
-                               int64_t G_in, const double* gh_x, const double* gh_w, int32_t n_nodes, double* value_out,
-                               double* grad_global_out, double* grad_local_out, double* H_blocks_out, double* border_out, double* local_out) {
-    LRVB_TRY(ctx_bind(c));
-    if (!mean || !var || !e_loc || !r_loc || !gh_x || !gh_w || !value_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
-    if (n_nodes < 1 || n_nodes > 128) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 128 quadrature nodes");
-    if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the logistic mixed model needs P <= 64 (got %lld)", (long long)c->P);
-    if (c->loss == LRVB_LOSS_NONE || c->data_only || !(c->have_X && c->have_y))
-        LRVB_FAIL(LRVB_ERR_STATE, "the context needs a design matrix and responses: lrvb_set_data for LRVB_SLOT_X and LRVB_SLOT_Y");
-    if (c->n_groups <= 0) LRVB_FAIL(LRVB_ERR_STATE, "no groups: call lrvb_set_groups first");
-    const i64 N = c->N, P = c->P, G = c->n_groups, ncol = 5 + 4 * P;
-    LRVB_TRY(check_len(P_in, P, "mean / var"));
-    LRVB_TRY(check_len(G_in, G, "e / r"));
-    for (i64 j = 0; j < P; ++j) if (!(var[j] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "var[%lld] is not positive", (long long)j);
-    for (i64 g = 0; g < G; ++g) if (!(r_loc[g] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "r[%lld] is not positive", (long long)g);
-    c->glmm_valid = false;
-    const bool want_g = grad_global_out != nullptr, want_H = H_blocks_out != nullptr;
-    DevBuf& X2 = c->mx_Xk;
-    if ((want_g || want_H) && (!c->x2_ready || X2.n < (size_t)(N * P))) {
-        LRVB_TRY(buf_reserve(c, X2, (size_t)(N * P)));
-        EW(square_kernel, N * P, (const double*)c->X.p, X2.p);
-        c->x2_ready = true;
-    }
-    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
-    const i64 NP = up(N + 64), n_tiles = glmm_num_tiles(N);
-    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(256 + 2 * up(P) + 2 * up(G) + 5 * NP + n_tiles * 2 * ncol + n_tiles)));
-    LRVB_TRY(buf_reserve(c, c->glmm, (size_t)(3 * P * P + G * ncol + 2 * P + 1)));
-    double* g = c->work1.p; double* dm = g + 256; double* dv = dm + up(P); double* de = dv + up(P); double* dr = de + up(G);
-    double* coef = dr + up(G); double* part = coef + 5 * NP; double* vpart = part + n_tiles * 2 * ncol;
-    double* Hb = c->glmm.p; double* gsum = Hb + 3 * P * P; double* gred = gsum + G * ncol; double* vred = gred + 2 * P;
-    LRVB_TRY(h2d(c, g, gh_x, (size_t)n_nodes));
-    LRVB_TRY(h2d(c, g + 128, gh_w, (size_t)n_nodes));
-    LRVB_TRY(h2d(c, dm, mean, (size_t)P));
-    LRVB_TRY(h2d(c, dv, var, (size_t)P));
-    LRVB_TRY(h2d(c, de, e_loc, (size_t)G));
-    LRVB_TRY(h2d(c, dr, r_loc, (size_t)G));
-    HIP_TRY(hipMemsetAsync(coef, 0, (size_t)(5 * NP) * sizeof(double), c->stream));
-    HIP_TRY(hipMemsetAsync(gsum, 0, (size_t)(G * ncol + 2 * P + 1) * sizeof(double), c->stream));
-    LRVB_TRY(launch_glmm_rows(c, dm, dv, de, dr, g, g + 128, (int)n_nodes, coef, NP, gsum, part, vpart));
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, c->stream, (const double*)vpart, n_tiles, vred);
-    HIP_TRY(hipGetLastError());
-    if (want_g) {
-        LRVB_TRY(launch_gemv(c, true, N, P, 1.0, c->X.p, P, coef, 0.0, gred));
-        LRVB_TRY(launch_gemv(c, true, N, P, 1.0, X2.p, P, coef + NP, 0.0, gred + P));
-    }
-    if (want_H) {
-        LRVB_TRY(weighted_tn(c, c->X.p, c->X.p, P, N, coef + 2 * NP, Hb, c->mx_A));
-        LRVB_TRY(weighted_tn(c, c->X.p, X2.p, P, N, coef + 3 * NP, Hb + P * P, c->mx_A));
-        LRVB_TRY(weighted_tn(c, X2.p, X2.p, P, N, coef + 4 * NP, Hb + 2 * P * P, c->mx_A));
-    }
-    double* first = want_H ? Hb : gsum;
-    LRVB_TRY(obs_reduce(c, first, (i64)(vred + 1 - first)));
-    c->glmm_valid = true;
-    LRVB_TRY(d2h(c, value_out, vred, 1));
-    if (want_g) LRVB_TRY(d2h(c, grad_global_out, gred, (size_t)(2 * P)));
-    if (want_H) LRVB_TRY(d2h(c, H_blocks_out, Hb, (size_t)(3 * P * P)));
-    if (grad_local_out || border_out || local_out) {
-        std::vector<double> host((size_t)(G * ncol));
-        LRVB_TRY(d2h(c, host.data(), gsum, host.size()));
-        for (i64 gi = 0; gi < G; ++gi) {
-            const double* row = host.data() + gi * ncol;
-            if (grad_local_out) { grad_local_out[2 * gi] = row[0]; grad_local_out[2 * gi + 1] = row[1]; }
-            if (local_out) { local_out[3 * gi] = row[2]; local_out[3 * gi + 1] = row[3]; local_out[3 * gi + 2] = row[4]; }
-            if (border_out) memcpy(border_out + gi * 4 * P, row + 5, (size_t)(4 * P) * sizeof(double));
-        }
-    }
-    return LRVB_OK;
-}
-
-extern "C" int lrvb_glmm_schur(lrvb_ctx* c, const double* local_2x2, const double* border_scale, const double* closed_rows, int64_t G_in,
-                               double* M_out) {
-    LRVB_TRY(ctx_bind(c));
-    if (!local_2x2 || !border_scale || !closed_rows || !M_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
-    if (c->n_groups <= 0 || !c->glmm_valid) LRVB_FAIL(LRVB_ERR_STATE, "no group sums resident: call lrvb_glmm_terms first");
-    const i64 P = c->P, G = c->n_groups, ncol = 5 + 4 * P, R = 2 * P + 3;
-    LRVB_TRY(check_len(G_in, G, "local blocks"));
-    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
-    const int ldu = (int)up(R);
-    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(8 + up(3 * G) + up(2 * G) + up(6 * G) + 2 * G * ldu + R * R)));
-    double* flag = c->work1.p; double* loc = flag + 8; double* sc = loc + up(3 * G); double* cl = sc + up(2 * G);
-    double* U = cl + up(6 * G); double* Md = U + 2 * G * ldu;
-    LRVB_TRY(h2d(c, loc, local_2x2, (size_t)(3 * G)));
-    LRVB_TRY(h2d(c, sc, border_scale, (size_t)(2 * G)));
-    LRVB_TRY(h2d(c, cl, closed_rows, (size_t)(6 * G)));
-    HIP_TRY(hipMemsetAsync(flag, 0, sizeof(double), c->stream));
-    const double* gsum = c->glmm.p + 3 * P * P;
-    LRVB_TRY(launch_glmm_schur_rows(c, gsum, loc, sc, cl, U, ldu, reinterpret_cast<int*>(flag)));
-    LRVB_TRY(launch_gemm(c, true, false, R, R, 2 * G, 1.0, U, ldu, U, ldu, 0.0, Md, R));
-    double fh = 0.0;
-    LRVB_TRY(d2h(c, &fh, flag, 1));
-    int bad = 0;
-    memcpy(&bad, &fh, sizeof(int));
-    if (bad) LRVB_FAIL(LRVB_ERR_NOT_POSDEF, "a 2 x 2 local block of the logistic mixed model is not positive definite");
-    return d2h(c, M_out, Md, (size_t)(R * R));
-}
-
 // ---- logistic mixed model with K <= 4 random effects per group (k_glmm_slopes.hip) ---------------------------------------------
 extern "C" int lrvb_set_group_design(lrvb_ctx* c, const double* z, int64_t n, int64_t K) {
     LRVB_TRY(ctx_bind(c));
@@ -2674,16 +2574,18 @@ extern "C" int lrvb_set_group_design(lrvb_ctx* c, const double* z, int64_t n, in
     return LRVB_OK;
 }
 
-// ---- the host layer the logistic and the Poisson K-effect model share --------------------------------------
-// An entry hands over its likelihood as a GlmmLik: the logistic ones with the caller's (host) nodes, the Poisson ones with
-// nothing, the binomial ones with the nodes again -- the bodies below replace the node pointers by the uploaded copies and fill in
-// the resident offset and trials.
-static GlmmLik glmms_logistic(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_LOGISTIC, gh_x, gh_w, (int)n_nodes, nullptr, nullptr}; }
-static GlmmLik glmms_poisson() { return GlmmLik{GLMM_POISSON, nullptr, nullptr, 0, nullptr, nullptr}; }
-static GlmmLik glmms_binomial(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_BINOMIAL, gh_x, gh_w, (int)n_nodes, nullptr, nullptr}; }
+// ---- the host layer every mixed model shares (DESIGN.md sections 27 and 31) -------------------------------------------------------
+// An entry hands over its likelihood as a GlmmLik: the random intercept the logistic one with K = 1 and the unit design, the
+// logistic ones with the caller's (host) nodes, the Poisson ones with nothing, the binomial ones with the nodes again -- the bodies
+// below replace the node pointers by the uploaded copies and fill in the resident offset and trials.
+static GlmmLik glmms_intercept(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_LOGISTIC, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, true}; }
+static GlmmLik glmms_logistic(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_LOGISTIC, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false}; }
+static GlmmLik glmms_poisson() { return GlmmLik{GLMM_POISSON, nullptr, nullptr, 0, nullptr, nullptr, false}; }
+static GlmmLik glmms_binomial(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_BINOMIAL, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false}; }
 static const char* glmms_name(const GlmmLik& lik) { return lik.kind == GLMM_POISSON ? "Poisson" : (lik.kind == GLMM_BINOMIAL ? "binomial" : "logistic"); }
 
-// The argument and state checks of all six entries, in one order (`other_null`: a required pointer of the entry's own is null).
+// The argument and state checks of all twelve entries over the rows, in one order (`other_null`: a required pointer of the entry's own is null).
+// The unit design has no group design to check, and its length message names "e / r" as the intercept entries always have.
 static int glmms_check(lrvb_ctx* c, const GlmmLik& lik, const double* mean, const double* var, int64_t P_in, const double* e_loc,
                        const double* r_loc, int64_t G_in, int64_t K, bool other_null) {
     const bool poisson = lik.kind == GLMM_POISSON;
@@ -2695,15 +2597,15 @@ static int glmms_check(lrvb_ctx* c, const GlmmLik& lik, const double* mean, cons
     if (c->loss == LRVB_LOSS_NONE || c->data_only || !(c->have_X && c->have_y))
         LRVB_FAIL(LRVB_ERR_STATE, "the context needs a design matrix and responses: lrvb_set_data for LRVB_SLOT_X and LRVB_SLOT_Y");
     if (c->n_groups <= 0) LRVB_FAIL(LRVB_ERR_STATE, "no groups: call lrvb_set_groups first");
-    if (c->gz_K <= 0) LRVB_FAIL(LRVB_ERR_STATE, "no group design: call lrvb_set_group_design first");
-    if (c->gz_n != c->N || c->gz_K != K)
+    if (!lik.unit && c->gz_K <= 0) LRVB_FAIL(LRVB_ERR_STATE, "no group design: call lrvb_set_group_design first");
+    if (!lik.unit && (c->gz_n != c->N || c->gz_K != K))
         LRVB_FAIL(LRVB_ERR_STATE, "the group design is %lld x %d, the model needs %lld x %lld", (long long)c->gz_n, c->gz_K, (long long)c->N, (long long)K);
     if (lik.kind != GLMM_LOGISTIC && c->goff_n != 0 && c->goff_n != c->N)
         LRVB_FAIL(LRVB_ERR_STATE, "the offset has %lld entries, the model has %lld observations", (long long)c->goff_n, (long long)c->N);
     if (lik.kind == GLMM_BINOMIAL && c->gtr_n != 0 && c->gtr_n != c->N)
         LRVB_FAIL(LRVB_ERR_STATE, "the trials have %lld entries, the model has %lld observations", (long long)c->gtr_n, (long long)c->N);
     LRVB_TRY(check_len(P_in, c->P, "mean / var"));
-    LRVB_TRY(check_len(G_in, c->n_groups, "groups of e / r"));
+    LRVB_TRY(check_len(G_in, c->n_groups, lik.unit ? "e / r" : "groups of e / r"));
     for (i64 j = 0; j < c->P; ++j) if (!(var[j] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "var[%lld] is not positive", (long long)j);
     for (i64 g = 0; g < c->n_groups * K; ++g) if (!(r_loc[g] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "r[%lld] is not positive", (long long)g);
     return LRVB_OK;
@@ -2720,7 +2622,8 @@ static int glmms_to_device(lrvb_ctx* c, GlmmLik& lik, double* g) {
     return LRVB_OK;
 }
 
-// c->glmms: [H blocks (3 P^2) | group sums (G x ncol) | gradient (2 P) | value], adjacent as in lrvb_glmm_terms.  c->work1:
+// c->glmms: [H blocks (3 P^2) | group sums (G x ncol) | gradient (2 P) | value] -- every sum over observations of the call, adjacent,
+// so that the part that was formed goes through the reduce hook in one piece.  c->work1:
 // [nodes 256 (not Poisson) | m, v (2 up(P)) | e, r (2 up(G K)) | the coefficient vectors (original order, zero past N): five,
 // a1 a2 c11 c12 c22 (5 NP), or the Poisson model's two, a1 and h (2 NP) | tile partials]
 static int glmms_terms(lrvb_ctx* c, GlmmLik lik, const double* mean, const double* var, int64_t P_in, const double* e_loc,
@@ -2737,7 +2640,6 @@ static int glmms_terms(lrvb_ctx* c, GlmmLik lik, const double* mean, const doubl
         EW(square_kernel, N * P, (const double*)c->X.p, X2.p);
         c->x2_ready = true;
     }
-    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
     const i64 NP = up(N + 64), n_tiles = glmm_num_tiles(N), GK = G * K, ncf = poisson ? 2 : 5, nodes = poisson ? 0 : 256;
     LRVB_TRY(buf_reserve(c, c->work1, (size_t)(nodes + 2 * up(P) + 2 * up(GK) + ncf * NP + n_tiles * 2 * ncol + n_tiles)));
     LRVB_TRY(buf_reserve(c, c->glmms, (size_t)(3 * P * P + G * ncol + 2 * P + 1)));
@@ -2751,7 +2653,7 @@ static int glmms_terms(lrvb_ctx* c, GlmmLik lik, const double* mean, const doubl
     LRVB_TRY(h2d(c, dr, r_loc, (size_t)GK));
     HIP_TRY(hipMemsetAsync(coef, 0, (size_t)(ncf * NP) * sizeof(double), c->stream));
     HIP_TRY(hipMemsetAsync(gsum, 0, (size_t)(G * ncol + 2 * P + 1) * sizeof(double), c->stream));
-    LRVB_TRY(launch_glmm_slopes_rows(c, lik, (int)K, c->gz.p, dm, dv, de, dr, coef, NP, gsum, part, vpart));
+    LRVB_TRY(launch_glmm_slopes_rows(c, lik, (int)K, lik.unit ? nullptr : c->gz.p, dm, dv, de, dr, coef, NP, gsum, part, vpart));
     hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, c->stream, (const double*)vpart, n_tiles, vred);
     HIP_TRY(hipGetLastError());
     // Poisson: a2 = h / 2 (the factor rides on the product), c11 = h, c12 = h / 2, c22 = h / 4 (one vector, the blocks scaled after)
@@ -2770,10 +2672,11 @@ static int glmms_terms(lrvb_ctx* c, GlmmLik lik, const double* mean, const doubl
     }
     double* first = want_H ? Hb : gsum;
     LRVB_TRY(obs_reduce(c, first, (i64)(vred + 1 - first)));
+    if (lik.unit) { c->glmms_valid = true; c->glmms_K = 0; }             // the intercept entry marks its sums HERE, ahead of the copies, as it always has
     LRVB_TRY(d2h(c, value_out, vred, 1));
     if (poisson && !std::isfinite(*value_out))
         LRVB_FAIL(LRVB_ERR_INVALID, "the Poisson data term is not finite at this point: exp(rho + s / 2) overflows for some row (the kernel does not clamp)");
-    c->glmms_valid = true; c->glmms_K = (int)K;
+    c->glmms_valid = true; c->glmms_K = lik.unit ? 0 : (int)K;           // 0: the sums of lrvb_glmm_terms, for lrvb_glmm_schur only
     if (want_g) LRVB_TRY(d2h(c, grad_global_out, gred, (size_t)(2 * P)));
     if (want_H) LRVB_TRY(d2h(c, H_blocks_out, Hb, (size_t)(3 * P * P)));
     if (group_sums_out) {
@@ -2796,6 +2699,59 @@ extern "C" int lrvb_glmm_slopes_terms(lrvb_ctx* c, const double* mean, const dou
                        H_blocks_out, group_sums_out, want_border);
 }
 
+// ---- logistic mixed model with a random intercept (k_glmm.hip) ----------------------------------------------------------------
+// The K-effect model at K = 1 with the unit group design: the four entries are the shared bodies above and below (glmms_terms,
+// glmms_infl_setup, glmms_obs_influence, glmms_group_influence) with glmms_intercept(), whose launchers are handed Z = nullptr and
+// launch the kernels of k_glmm.hip.  The sums live in c->glmms, marked glmms_K = 0; [g_loc 2 | loc 3 | border 4 P] is the column
+// layout of glmm_slopes_ncol(P, 1).
+extern "C" int lrvb_glmm_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc, const double* r_loc,
+                               int64_t G_in, const double* gh_x, const double* gh_w, int32_t n_nodes, double* value_out,
+                               double* grad_global_out, double* grad_local_out, double* H_blocks_out, double* border_out, double* local_out) {
+    LRVB_TRY(ctx_bind(c));
+    LRVB_TRY(glmms_terms(c, glmms_intercept(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, 1, value_out, grad_global_out,
+                         H_blocks_out, nullptr, 0));
+    if (grad_local_out || border_out || local_out) {                     // the resident group sums, unstacked
+        const i64 P = c->P, G = c->n_groups, ncol = 5 + 4 * P;
+        std::vector<double> host((size_t)(G * ncol));
+        LRVB_TRY(d2h(c, host.data(), c->glmms.p + 3 * P * P, host.size()));
+        for (i64 gi = 0; gi < G; ++gi) {
+            const double* row = host.data() + gi * ncol;
+            if (grad_local_out) { grad_local_out[2 * gi] = row[0]; grad_local_out[2 * gi + 1] = row[1]; }
+            if (local_out) { local_out[3 * gi] = row[2]; local_out[3 * gi + 1] = row[3]; local_out[3 * gi + 2] = row[4]; }
+            if (border_out) memcpy(border_out + gi * 4 * P, row + 5, (size_t)(4 * P) * sizeof(double));
+        }
+    }
+    return LRVB_OK;
+}
+
+extern "C" int lrvb_glmm_schur(lrvb_ctx* c, const double* local_2x2, const double* border_scale, const double* closed_rows, int64_t G_in,
+                               double* M_out) {
+    LRVB_TRY(ctx_bind(c));
+    if (!local_2x2 || !border_scale || !closed_rows || !M_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    if (c->n_groups <= 0 || !c->glmms_valid || c->glmms_K != 0) LRVB_FAIL(LRVB_ERR_STATE, "no group sums resident: call lrvb_glmm_terms first");
+    const i64 P = c->P, G = c->n_groups, R = 2 * P + 3;
+    LRVB_TRY(check_len(G_in, G, "local blocks"));
+    const int ldu = (int)up(R);
+    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(8 + up(3 * G) + up(2 * G) + up(6 * G) + 2 * G * ldu + R * R)));
+    double* flag = c->work1.p; double* loc = flag + 8; double* sc = loc + up(3 * G); double* cl = sc + up(2 * G);
+    double* U = cl + up(6 * G); double* Md = U + 2 * G * ldu;
+    LRVB_TRY(h2d(c, loc, local_2x2, (size_t)(3 * G)));
+    LRVB_TRY(h2d(c, sc, border_scale, (size_t)(2 * G)));
+    LRVB_TRY(h2d(c, cl, closed_rows, (size_t)(6 * G)));
+    HIP_TRY(hipMemsetAsync(flag, 0, sizeof(double), c->stream));
+    const double* gsum = c->glmms.p + 3 * P * P;
+    // glmm_slopes_schur_rows_kernel<1>: [a11, a12, a22] is the upper triangle of its 2 x 2 block, G x 6 its G x 2 x 3 closed rows;
+    // it gives the bits of the 2 x 2 kernel this entry had
+    LRVB_TRY(launch_glmm_slopes_schur_rows(c, 1, gsum, loc, sc, cl, U, ldu, reinterpret_cast<int*>(flag)));
+    LRVB_TRY(launch_gemm(c, true, false, R, R, 2 * G, 1.0, U, ldu, U, ldu, 0.0, Md, R));
+    double fh = 0.0;
+    LRVB_TRY(d2h(c, &fh, flag, 1));
+    int bad = 0;
+    memcpy(&bad, &fh, sizeof(int));
+    if (bad) LRVB_FAIL(LRVB_ERR_NOT_POSDEF, "a 2 x 2 local block of the logistic mixed model is not positive definite");
+    return d2h(c, M_out, Md, (size_t)(R * R));
+}
+
 extern "C" int lrvb_glmm_slopes_schur(lrvb_ctx* c, const double* local_blocks, const double* border_scale, const double* closed_rows,
                                       int64_t G_in, int64_t K, double* M_out) {
     LRVB_TRY(ctx_bind(c));
@@ -2805,7 +2761,6 @@ extern "C" int lrvb_glmm_slopes_schur(lrvb_ctx* c, const double* local_blocks, c
         LRVB_FAIL(LRVB_ERR_STATE, "no group sums of %lld effects resident: call lrvb_glmm_slopes_terms first", (long long)K);
     const i64 P = c->P, G = c->n_groups, R = 2 * P + 3 * K, K2 = 2 * K, NT = K * (K2 + 1);
     LRVB_TRY(check_len(G_in, G, "local blocks"));
-    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
     const int ldu = (int)up(R);
     c->glmms_fac_valid = false; c->glmms_T_Q = 0;
     // the uploaded blocks and U outlive the call in a buffer of their own (lrvb_glmm_slopes_solve_forward / _back)
@@ -2845,7 +2800,6 @@ extern "C" int lrvb_glmm_slopes_solve_forward(lrvb_ctx* c, const double* R_local
     LRVB_TRY(ctx_bind(c));
     LRVB_TRY(glmm_slopes_solve_check(c, R_local, red_out, G_in, K, Q));
     const i64 P = c->P, G = c->n_groups, R = 2 * P + 3 * K, K2 = 2 * K, NT = K * (K2 + 1);
-    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
     const i64 ldu = up(R);
     c->glmms_T_Q = 0;
     LRVB_TRY(buf_reserve(c, c->glmms_T, (size_t)(K2 * G * Q)));
@@ -2865,7 +2819,6 @@ extern "C" int lrvb_glmm_slopes_solve_back(lrvb_ctx* c, const double* x_coupled,
     if (c->glmms_T_Q == 0) LRVB_FAIL(LRVB_ERR_STATE, "no forward pass resident: call lrvb_glmm_slopes_solve_forward first");
     LRVB_TRY(check_len(Q, c->glmms_T_Q, "columns (those of the forward pass)"));
     const i64 P = c->P, G = c->n_groups, R = 2 * P + 3 * K, K2 = 2 * K, NT = K * (K2 + 1);
-    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
     const i64 ldu = up(R);
     LRVB_TRY(buf_reserve(c, c->work1, (size_t)(up(R * Q) + K2 * G * Q)));
     double* loc = c->glmms_fac.p; double* U = loc + up(NT * G); double* xs = c->work1.p; double* W = xs + up(R * Q);
@@ -2875,84 +2828,16 @@ extern "C" int lrvb_glmm_slopes_solve_back(lrvb_ctx* c, const double* x_coupled,
     return d2h(c, X_local_out, W, (size_t)(K2 * G * Q));
 }
 
-// ---- weight influence of the logistic mixed model (k_glmm.hip) -------------------------------------------------------------------
-// The checks of lrvb_glmm_terms, in its order, then the operand.  c->work1 holds
-//   [nodes 256 | m, v (2 up(P)) | e, r (2 up(G)) | A_global (Q x 2 P) | A_local (G x 2 Q) | call-specific scratch]
-struct GlmmInflBufs { double *g, *m, *v, *e, *r, *Ag, *Al, *extra; };
-static int glmm_infl_setup(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc, const double* r_loc,
-                           int64_t G_in, const double* gh_x, const double* gh_w, int32_t n_nodes, const double* A_global,
-                           const double* A_local, int64_t Q, const void* out, size_t extra, GlmmInflBufs& b) {
-    if (!mean || !var || !e_loc || !r_loc || !gh_x || !gh_w || !A_global || !A_local || !out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
-    if (n_nodes < 1 || n_nodes > 128) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 128 quadrature nodes");
-    if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the logistic mixed model needs P <= 64 (got %lld)", (long long)c->P);
-    if (c->loss == LRVB_LOSS_NONE || c->data_only || !(c->have_X && c->have_y))
-        LRVB_FAIL(LRVB_ERR_STATE, "the context needs a design matrix and responses: lrvb_set_data for LRVB_SLOT_X and LRVB_SLOT_Y");
-    if (c->n_groups <= 0) LRVB_FAIL(LRVB_ERR_STATE, "no groups: call lrvb_set_groups first");
-    const i64 P = c->P, G = c->n_groups;
-    LRVB_TRY(check_len(P_in, P, "mean / var"));
-    LRVB_TRY(check_len(G_in, G, "e / r"));
-    for (i64 j = 0; j < P; ++j) if (!(var[j] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "var[%lld] is not positive", (long long)j);
-    for (i64 g = 0; g < G; ++g) if (!(r_loc[g] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "r[%lld] is not positive", (long long)g);
-    if (Q < 1) LRVB_FAIL(LRVB_ERR_INVALID, "Q must be positive");
-    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
-    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(256 + 2 * up(P) + 2 * up(G) + up(Q * 2 * P) + up(G * 2 * Q)) + extra));
-    b.g = c->work1.p; b.m = b.g + 256; b.v = b.m + up(P); b.e = b.v + up(P); b.r = b.e + up(G);
-    b.Ag = b.r + up(G); b.Al = b.Ag + up(Q * 2 * P); b.extra = b.Al + up(G * 2 * Q);
-    LRVB_TRY(h2d(c, b.g, gh_x, (size_t)n_nodes));
-    LRVB_TRY(h2d(c, b.g + 128, gh_w, (size_t)n_nodes));
-    LRVB_TRY(h2d(c, b.m, mean, (size_t)P));
-    LRVB_TRY(h2d(c, b.v, var, (size_t)P));
-    LRVB_TRY(h2d(c, b.e, e_loc, (size_t)G));
-    LRVB_TRY(h2d(c, b.r, r_loc, (size_t)G));
-    LRVB_TRY(h2d(c, b.Ag, A_global, (size_t)(Q * 2 * P)));
-    LRVB_TRY(h2d(c, b.Al, A_local, (size_t)(G * 2 * Q)));
-    return LRVB_OK;
-}
-
-extern "C" int lrvb_glmm_obs_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
-                                       const double* r_loc, int64_t G_in, const double* gh_x, const double* gh_w, int32_t n_nodes,
-                                       const double* A_global, const double* A_local, int64_t Q, int64_t n0, int64_t n1, double* out) {
-    LRVB_TRY(ctx_bind(c));
-    GlmmInflBufs b;
-    LRVB_TRY(glmm_infl_setup(c, mean, var, P_in, e_loc, r_loc, G_in, gh_x, gh_w, n_nodes, A_global, A_local, Q, out, 0, b));
-    if (n0 < 0 || n1 > c->N || n0 > n1) LRVB_FAIL(LRVB_ERR_INVALID, "row range [%lld, %lld) outside [0, %lld)", (long long)n0, (long long)n1, (long long)c->N);
-    const i64 rows = n1 - n0;
-    if (rows == 0) return LRVB_OK;
-    LRVB_TRY(buf_reserve(c, c->cgT, (size_t)(rows * Q)));
-    const i64 NW = (c->N + grouped_rows_per_wave(c->N) - 1) / grouped_rows_per_wave(c->N);
-    const int* gid = reinterpret_cast<const int*>(reinterpret_cast<const i64*>(c->groups.p) + c->N + c->n_groups + 1 + NW);
-    LRVB_TRY(launch_glmm_infl_rows(c, n0, n1, gid, b.m, b.v, b.e, b.r, b.g, b.g + 128, (int)n_nodes, b.Ag, b.Al, Q, c->cgT.p));
-    return d2h(c, out, c->cgT.p, (size_t)(rows * Q));       // per-observation rows: rank-local, no hook call
-}
-
-extern "C" int lrvb_glmm_group_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
-                                         const double* r_loc, int64_t G_in, const double* gh_x, const double* gh_w, int32_t n_nodes,
-                                         const double* A_global, const double* A_local, int64_t Q, double* out) {
-    LRVB_TRY(ctx_bind(c));
-    GlmmInflBufs b;
-    const i64 ncol = 2 + 2 * c->P, n_tiles = glmm_num_tiles(c->N), G = c->n_groups > 0 ? c->n_groups : 0;
-    // scratch: [group sums (G x (2 + 2 P)) | tile partials | out (G x Q)]
-    const size_t extra = (size_t)(G * ncol + n_tiles * 2 * ncol + G * (Q > 0 ? Q : 0));
-    LRVB_TRY(glmm_infl_setup(c, mean, var, P_in, e_loc, r_loc, G_in, gh_x, gh_w, n_nodes, A_global, A_local, Q, out, extra, b));
-    double* gsum = b.extra; double* part = gsum + G * ncol; double* od = part + n_tiles * 2 * ncol;
-    HIP_TRY(hipMemsetAsync(gsum, 0, (size_t)(G * ncol) * sizeof(double), c->stream));       // empty groups keep the zeros
-    LRVB_TRY(launch_glmm_infl_gsum(c, b.m, b.v, b.e, b.r, b.g, b.g + 128, (int)n_nodes, gsum, part));
-    LRVB_TRY(launch_gemm(c, false, true, G, Q, 2 * c->P, 1.0, gsum + 2, ncol, b.Ag, 2 * c->P, 0.0, od, Q));
-    LRVB_TRY(launch_glmm_infl_local(c, Q, gsum, b.Al, od));
-    LRVB_TRY(obs_reduce(c, od, G * Q));                       // a sum over observations; a group may straddle ranks
-    return d2h(c, out, od, (size_t)(G * Q));
-}
-
-// ---- weight influence of the two K-effect mixed models (k_glmm_slopes.hip) ---------------------------------------------------------
+// ---- weight influence of every mixed model (k_glmm.hip, k_glmm_slopes.hip) --------------------------------------------------------
 // The checks of glmms_terms, in its order, then the operand.  c->work1 holds
 //   [nodes 256 (not Poisson) | m, v (2 up(P)) | e, r (2 up(G K)) | A_global (Q x 2 P) | A_local (G x 2 K x Q) | call-specific scratch]
+struct GlmmInflBufs { double *g, *m, *v, *e, *r, *Ag, *Al, *extra; };
 static int glmms_infl_setup(lrvb_ctx* c, GlmmLik& lik, const double* mean, const double* var, int64_t P_in, const double* e_loc,
                             const double* r_loc, int64_t G_in, int64_t K, const double* A_global, const double* A_local, int64_t Q,
                             const void* out, size_t extra, GlmmInflBufs& b) {
     LRVB_TRY(glmms_check(c, lik, mean, var, P_in, e_loc, r_loc, G_in, K, !A_global || !A_local || !out));
     if (Q < 1) LRVB_FAIL(LRVB_ERR_INVALID, "Q must be positive");
     const i64 P = c->P, GK = c->n_groups * K, nodes = lik.kind == GLMM_POISSON ? 0 : 256;
-    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };
     LRVB_TRY(buf_reserve(c, c->work1, (size_t)(nodes + 2 * up(P) + 2 * up(GK) + up(Q * 2 * P) + up(GK * 2 * Q)) + extra));
     b.g = c->work1.p; b.m = b.g + nodes; b.v = b.m + up(P); b.e = b.v + up(P); b.r = b.e + up(GK);
     b.Ag = b.r + up(GK); b.Al = b.Ag + up(Q * 2 * P); b.extra = b.Al + up(GK * 2 * Q);
@@ -2977,7 +2862,7 @@ static int glmms_obs_influence(lrvb_ctx* c, GlmmLik lik, const double* mean, con
     LRVB_TRY(buf_reserve(c, c->cgT, (size_t)(rows * Q)));
     const i64 NW = (c->N + grouped_rows_per_wave(c->N) - 1) / grouped_rows_per_wave(c->N);
     const int* gid = reinterpret_cast<const int*>(reinterpret_cast<const i64*>(c->groups.p) + c->N + c->n_groups + 1 + NW);
-    LRVB_TRY(launch_glmm_slopes_infl_rows(c, lik, (int)K, c->gz.p, n0, n1, gid, b.m, b.v, b.e, b.r, b.Ag, b.Al, Q, c->cgT.p));
+    LRVB_TRY(launch_glmm_slopes_infl_rows(c, lik, (int)K, lik.unit ? nullptr : c->gz.p, n0, n1, gid, b.m, b.v, b.e, b.r, b.Ag, b.Al, Q, c->cgT.p));
     return d2h(c, out, c->cgT.p, (size_t)(rows * Q));       // per-observation rows: rank-local, no hook call
 }
 
@@ -2992,11 +2877,26 @@ static int glmms_group_influence(lrvb_ctx* c, GlmmLik lik, const double* mean, c
     LRVB_TRY(glmms_infl_setup(c, lik, mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out, extra, b));
     double* gsum = b.extra; double* part = gsum + G * ncol; double* od = part + n_tiles * 2 * ncol;
     HIP_TRY(hipMemsetAsync(gsum, 0, (size_t)(G * ncol) * sizeof(double), c->stream));       // empty groups keep the zeros
-    LRVB_TRY(launch_glmm_slopes_infl_gsum(c, lik, (int)K, c->gz.p, b.m, b.v, b.e, b.r, gsum, part));
+    LRVB_TRY(launch_glmm_slopes_infl_gsum(c, lik, (int)K, lik.unit ? nullptr : c->gz.p, b.m, b.v, b.e, b.r, gsum, part));
     LRVB_TRY(launch_gemm(c, false, true, G, Q, 2 * c->P, 1.0, gsum + 2 * K, ncol, b.Ag, 2 * c->P, 0.0, od, Q));
-    LRVB_TRY(launch_glmm_slopes_infl_local(c, (int)K, Q, gsum, b.Al, od));
+    if (lik.unit) LRVB_TRY(launch_glmm_infl_local(c, Q, gsum, b.Al, od));                   // the intercept keeps its two-column kernel
+    else LRVB_TRY(launch_glmm_slopes_infl_local(c, (int)K, Q, gsum, b.Al, od));
     LRVB_TRY(obs_reduce(c, od, G * Q));                       // a sum over observations; a group may straddle ranks
     return d2h(c, out, od, (size_t)(G * Q));
+}
+
+extern "C" int lrvb_glmm_obs_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                       const double* r_loc, int64_t G_in, const double* gh_x, const double* gh_w, int32_t n_nodes,
+                                       const double* A_global, const double* A_local, int64_t Q, int64_t n0, int64_t n1, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_obs_influence(c, glmms_intercept(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, 1, A_global, A_local, Q, n0, n1, out);
+}
+
+extern "C" int lrvb_glmm_group_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                         const double* r_loc, int64_t G_in, const double* gh_x, const double* gh_w, int32_t n_nodes,
+                                         const double* A_global, const double* A_local, int64_t Q, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_group_influence(c, glmms_intercept(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, 1, A_global, A_local, Q, out);
 }
 
 extern "C" int lrvb_glmm_slopes_obs_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
@@ -3109,7 +3009,6 @@ static int lmvn_check(lrvb_ctx* c, int64_t P_in, int32_t n_nodes) {
 
 static int lmvn_reserve(lrvb_ctx* c, LmvnBufs& B) {
     const i64 N = c->N, P = c->P, NP = ((N + 64 + 7) / 8) * 8;
-    auto up = [](i64 n) { return ((n + 7) / 8) * 8; };            // every segment starts on a 64-byte boundary
     B.nblk = (N + 255) / 256;
     LRVB_TRY(buf_reserve(c, c->lmvn, (size_t)(256 + 3 * up(P) + 3 * up(P * P) + 2 * up(N) + 8 * NP + B.nblk)));
     double* p = c->lmvn.p;

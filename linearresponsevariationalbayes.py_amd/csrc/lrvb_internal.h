@@ -126,10 +126,11 @@ struct lrvb_ctx {
         bool p_valid = false; std::vector<double> p_beta;
     } sm;
     DevBuf lmvn;                   // lrvb_logitnormal_mvn_*: parameters, row pass, per-observation coefficients
-    DevBuf glmm; bool glmm_valid = false;   // lrvb_glmm_terms: [H blocks (3 P^2) | group sums (G x (5 + 4 P)) | gradient (2 P) | value], summed over ranks; the group sums stay resident for lrvb_glmm_schur
-    // lrvb_glmm_slopes_terms (K <= 4 effects per group): the group design z (gz_n x gz_K, row-major; lrvb_set_group_design) and
-    // [H blocks (3 P^2) | group sums (G x glmm_slopes_ncol) | gradient (2 P) | value] of the last call with glmms_K effects,
-    // summed over ranks; the group sums stay resident for lrvb_glmm_slopes_schur
+    // the mixed models (K <= 4 effects per group): the group design z (gz_n x gz_K, row-major; lrvb_set_group_design) and
+    // [H blocks (3 P^2) | group sums (G x glmm_slopes_ncol) | gradient (2 P) | value] of the last terms call, summed over ranks.
+    // The group sums stay resident: with glmms_K effects for lrvb_glmm_slopes_schur, or with glmms_K = 0 -- the sums of
+    // lrvb_glmm_terms (the random intercept: the layout at K = 1) -- for lrvb_glmm_schur.  ONE buffer: a terms call of either
+    // family drops the other's sums and factor
     DevBuf gz; i64 gz_n = 0; int gz_K = 0;
     DevBuf glmms; bool glmms_valid = false; int glmms_K = 0;
     // what lrvb_glmm_slopes_schur leaves for lrvb_glmm_slopes_solve_forward / _back: [uploaded local blocks (up(K (2 K + 1) G)) |
@@ -234,13 +235,12 @@ int  launch_softmax_influence_contract(lrvb_ctx* c, i64 n0, i64 rows, int G, int
 int  launch_lmvn_rowpass(lrvb_ctx* c, const double* A, const double* b, double* r, double* t);   // r_n = x_n^T A x_n, t_n = x_n . b
 int  launch_lmvn_cross(lrvb_ctx* c, const double* cvec, double* H, i64 ld);    // H[a, P + v] = H[P + v, a] = delta_v (X^T diag(c) U)[a, v]
 
-// k_glmm.hip (P = n_cols <= 64; groups set)
+// k_glmm.hip (the random intercept; P = n_cols <= 64; groups set).  The three launchers over the rows are reached through those of
+// k_glmm_slopes.hip with Z = nullptr.
 i64  glmm_num_tiles(i64 N);               // tiles of the rows pass: `part` holds 2 (5 + 4 P) doubles per tile, `vpart` one
 int  launch_glmm_rows(lrvb_ctx* c, const double* m, const double* vb, const double* eg, const double* rg, const double* gx,
                       const double* gw, int K, double* coef /* 5 x NP, original row order */, i64 NP,
                       double* gsum /* G x (5 + 4 P), zeroed by the caller */, double* part, double* vpart);
-int  launch_glmm_schur_rows(lrvb_ctx* c, const double* gsum, const double* loc, const double* scale, const double* closed,
-                            double* U /* 2 G x ldu */, int ldu, int* bad);
 int  launch_glmm_infl_rows(lrvb_ctx* c, i64 n0, i64 n1, const int* gid /* original row order */, const double* m, const double* vb,
                            const double* eg, const double* rg, const double* gx, const double* gw, int K, const double* Ag /* Q x 2 P */,
                            const double* Al /* G x 2 Q */, i64 Q, double* out /* (n1 - n0) x Q */);
@@ -252,11 +252,12 @@ int  launch_glmm_infl_local(lrvb_ctx* c, i64 Q, const double* S, const double* A
 // k_glmm_slopes.hip (the logistic and the Poisson mixed model; P = n_cols <= 64, 1 <= K <= 4; groups and the group design set).
 // The three kernels over the rows are templates over a likelihood policy; GlmmLik picks the instantiation
 // and carries what only it reads: the Gauss-Hermite nodes (logistic, binomial), the per-row offset or nullptr (Poisson, binomial),
-// the per-row trials or nullptr (binomial).
+// the per-row trials or nullptr (binomial).  `unit`: the unit group design of the random intercept (logistic,
+// K = 1, z = 1, nothing on the device): the host bodies hand the launchers Z = nullptr, and those launch the kernels of k_glmm.hip.
 enum GlmmKind { GLMM_LOGISTIC = 0, GLMM_POISSON = 1, GLMM_BINOMIAL = 2 };
-struct GlmmLik { GlmmKind kind; const double* gx; const double* gw; int n_nodes; const double* off; const double* trials; };
+struct GlmmLik { GlmmKind kind; const double* gx; const double* gw; int n_nodes; const double* off; const double* trials; bool unit; };
 int  glmm_slopes_ncol(int P, int K);      // columns of one group's sums: 2 K + K (2 K + 1) + 4 K P
-int  launch_glmm_slopes_rows(lrvb_ctx* c, const GlmmLik& lik, int K, const double* Z /* N x K */, const double* m, const double* vb,
+int  launch_glmm_slopes_rows(lrvb_ctx* c, const GlmmLik& lik, int K, const double* Z /* N x K; nullptr: the unit design */, const double* m, const double* vb,
                              const double* eg /* G x K */, const double* rg /* G x K */,
                              double* coef /* original row order: 5 x NP (logistic, binomial), 2 x NP: a1 | h = w psi (Poisson) */, i64 NP,
                              double* gsum /* G x ncol, zeroed by the caller */,

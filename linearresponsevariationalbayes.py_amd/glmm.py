@@ -95,7 +95,7 @@ def arrow_solve(Hgg, rows, Hx, loc, R, schur_solve=None):
 
 
 class LogisticGLMMObjective(_LogisticMixedModel):
-    """The mixed model with one effect per group and the unit group design, on its own device entries (csrc/k_glmm.hip)."""
+    """The mixed model with one effect per group and the unit group design, on its own kernels over the rows (csrc/k_glmm.hip)."""
 
     def __init__(self, par, x, y, groups, n_groups, beta_prior_info=1.0, mu_prior=(0.0, 1.0), tau_prior=(1.0, 1.0), gh_deg=20,
                  names=('beta', 'mu', 'tau', 'u'), weights=None, device=0):

@@ -17,7 +17,7 @@ Negative binomial (NB2: mean e^eta, variance e^eta + e^2eta / phi, KNOWN dispers
 offset o - log phi.  `NegBinomialGLMMObjective` is that construction and nothing else; phi is fixed data, not a hyper-parameter,
 and is not estimated.
 
-The O(N) work is `lrvb_glmm_binomial_terms` (csrc/k_glmm_slopes.hip, the policy BinomialLik of the shared tile walk); everything
+The O(N) work is `lrvb_glmm_binomial_terms` (csrc/k_glmm_slopes.hip, the policy BinomialLik of csrc/k_glmm_walk.h); everything
 after the per-row coefficients is the shared layer, unchanged.
 """
 import numpy as np

@@ -322,25 +322,65 @@ class DeviceContext(object):
                                                     _hip.ptr(val), _hip.ptr(g), _hip.ptr(Hb)))
         return float(val[0]), g, (None if Hb is None else (Hb[0], Hb[1], Hb[2]))
 
+    # ---- the mixed models: four families (intercept, slopes, Poisson, binomial) x (terms, row influence, group influence) ----------
+    # The twelve public methods below differ in the C entry they call (`fn`), in whether it takes Gauss-Hermite nodes (`nodes`) and in
+    # whether it takes K (`has_K`: e and r are G x K and the group sums come back stacked; without it, the intercept's entries, they are
+    # G-vectors and lrvb_glmm_terms fills three separate arrays).
+    def _glmm_terms(self, fn, nodes, has_K, mean, var, e, r, gh_x, gh_w, want_grad, want_hess, want_border):
+        m, v = _hip.as_f64(mean).ravel(), _hip.as_f64(var).ravel()
+        e, r = _hip.as_f64(e), _hip.as_f64(r)
+        if not has_K:
+            e, r = e.ravel(), r.ravel()
+        gx, gw = _hip.as_f64(gh_x).ravel(), _hip.as_f64(gh_w).ravel()
+        P = self.n_cols
+        if (has_K and e.ndim != 2) or r.shape != e.shape or m.size != P or v.size != P or gx.size != gw.size:
+            raise ValueError('expected mean and var of length {}, e and r of one {}{}'.format(
+                P, 'shape G x K' if has_K else 'length', ' and as many weights as nodes' if nodes else ''))
+        G, K = e.shape if has_K else (e.size, 1)
+        val = np.empty(1)
+        gg = np.empty(2 * P) if want_grad else None
+        Hb = np.empty((3, P, P)) if want_hess else None
+        border = bool(want_hess and want_border)
+        args = [self._h, _hip.ptr(m), _hip.ptr(v), P, _hip.ptr(e), _hip.ptr(r), G] + ([K] if has_K else [])
+        args += [_hip.ptr(gx), _hip.ptr(gw), gx.size] if nodes else []
+        if has_K:
+            nsc = 2 * K + K * (2 * K + 1)
+            gs = np.empty((G, nsc + (4 * K * P if border else 0))) if (want_grad or want_hess) else None
+            self._check(fn(*args, _hip.ptr(val), _hip.ptr(gg), _hip.ptr(Hb), _hip.ptr(gs), 1 if border else 0))
+            return float(val[0]), gg, Hb, gs
+        gl = np.empty((G, 2)) if want_grad else None
+        B = np.empty((G, 4 * P)) if border else None
+        L = np.empty((G, 3)) if want_hess else None
+        self._check(fn(*args, _hip.ptr(val), _hip.ptr(gg), _hip.ptr(gl), _hip.ptr(Hb), _hip.ptr(B), _hip.ptr(L)))
+        return float(val[0]), gg, gl, Hb, B, L
+
+    def _glmm_obs_influence(self, fn, nodes, has_K, mean, var, e, r, gh_x, gh_w, A, n0, n1):
+        if not has_K:
+            e, r = _hip.as_f64(e).reshape(-1, 1), _hip.as_f64(r).reshape(-1, 1)    # G x 1: one effect per group
+        (m, v, e, r, gx, gw, Ag, Al), Q = self._glmm_influence_args(mean, var, e, r, gh_x, gh_w, A)
+        n0 = int(n0)
+        n1 = self.n_obs if n1 is None else int(n1)
+        out = np.empty((max(n1 - n0, 0), Q))
+        args = [self._h, _hip.ptr(m), _hip.ptr(v), self.n_cols, _hip.ptr(e), _hip.ptr(r), e.shape[0]] + ([e.shape[1]] if has_K else [])
+        args += [_hip.ptr(gx), _hip.ptr(gw), gx.size] if nodes else []
+        self._check(fn(*args, _hip.ptr(Ag), _hip.ptr(Al), Q, n0, n1, _hip.ptr(out)))
+        return out
+
+    def _glmm_group_influence(self, fn, nodes, has_K, mean, var, e, r, gh_x, gh_w, A):
+        if not has_K:
+            e, r = _hip.as_f64(e).reshape(-1, 1), _hip.as_f64(r).reshape(-1, 1)    # G x 1: one effect per group
+        (m, v, e, r, gx, gw, Ag, Al), Q = self._glmm_influence_args(mean, var, e, r, gh_x, gh_w, A)
+        out = np.empty((e.shape[0], Q))
+        args = [self._h, _hip.ptr(m), _hip.ptr(v), self.n_cols, _hip.ptr(e), _hip.ptr(r), e.shape[0]] + ([e.shape[1]] if has_K else [])
+        args += [_hip.ptr(gx), _hip.ptr(gw), gx.size] if nodes else []
+        self._check(fn(*args, _hip.ptr(Ag), _hip.ptr(Al), Q, _hip.ptr(out)))
+        return out
+
     def glmm_terms(self, mean, var, e, r, gh_x, gh_w, want_grad=True, want_hess=True, want_border=True):
         """Data term of the logistic mixed model in the coordinates (mean, var, e, r) (lrvb_glmm_terms): value, global gradient
         (2 P), local gradient (G x 2), the Hessian blocks (3 x P x P), the border (G x 4 P) and the local sums (G x 3).  The group
         sums stay resident for `glmm_schur`; want_border=False leaves the border there and returns None for it."""
-        m, v = _hip.as_f64(mean).ravel(), _hip.as_f64(var).ravel()
-        e, r = _hip.as_f64(e).ravel(), _hip.as_f64(r).ravel()
-        gx, gw = _hip.as_f64(gh_x).ravel(), _hip.as_f64(gh_w).ravel()
-        P, G = self.n_cols, e.size
-        if m.size != P or v.size != P or r.size != G or gx.size != gw.size:
-            raise ValueError('expected mean and var of length {}, e and r of one length and as many weights as nodes'.format(P))
-        val = np.empty(1)
-        gg = np.empty(2 * P) if want_grad else None
-        gl = np.empty((G, 2)) if want_grad else None
-        Hb = np.empty((3, P, P)) if want_hess else None
-        B = np.empty((G, 4 * P)) if (want_hess and want_border) else None
-        L = np.empty((G, 3)) if want_hess else None
-        self._check(self._lib.lrvb_glmm_terms(self._h, _hip.ptr(m), _hip.ptr(v), P, _hip.ptr(e), _hip.ptr(r), G, _hip.ptr(gx), _hip.ptr(gw),
-                                             gx.size, _hip.ptr(val), _hip.ptr(gg), _hip.ptr(gl), _hip.ptr(Hb), _hip.ptr(B), _hip.ptr(L)))
-        return float(val[0]), gg, gl, Hb, B, L
+        return self._glmm_terms(self._lib.lrvb_glmm_terms, True, False, mean, var, e, r, gh_x, gh_w, want_grad, want_hess, want_border)
 
     def glmm_schur(self, local_2x2, border_scale, closed_rows):
         """M ((2 P + 3)^2) = sum_g C_g^T A_g^-1 C_g from the resident group sums of the last `glmm_terms` (lrvb_glmm_schur)."""
@@ -365,23 +405,7 @@ class DeviceContext(object):
         (lrvb_glmm_slopes_terms): value, global gradient (2 P), the Hessian blocks (3 x P x P) and the group sums in the column
         layout of include/lrvb_hip.h -- G x ncol, or G x nsc (no border) with want_border=False, or None where neither the
         gradient nor the Hessian is asked for.  The group sums stay resident for `glmm_slopes_schur`."""
-        m, v = _hip.as_f64(mean).ravel(), _hip.as_f64(var).ravel()
-        e, r = _hip.as_f64(e), _hip.as_f64(r)
-        gx, gw = _hip.as_f64(gh_x).ravel(), _hip.as_f64(gh_w).ravel()
-        P = self.n_cols
-        if e.ndim != 2 or r.shape != e.shape or m.size != P or v.size != P or gx.size != gw.size:
-            raise ValueError('expected mean and var of length {}, e and r of one shape G x K and as many weights as nodes'.format(P))
-        G, K = e.shape
-        nsc = 2 * K + K * (2 * K + 1)
-        val = np.empty(1)
-        gg = np.empty(2 * P) if want_grad else None
-        Hb = np.empty((3, P, P)) if want_hess else None
-        border = bool(want_hess and want_border)
-        gs = np.empty((G, nsc + (4 * K * P if border else 0))) if (want_grad or want_hess) else None
-        self._check(self._lib.lrvb_glmm_slopes_terms(self._h, _hip.ptr(m), _hip.ptr(v), P, _hip.ptr(e), _hip.ptr(r), G, K, _hip.ptr(gx),
-                                                    _hip.ptr(gw), gx.size, _hip.ptr(val), _hip.ptr(gg), _hip.ptr(Hb), _hip.ptr(gs),
-                                                    1 if border else 0))
-        return float(val[0]), gg, Hb, gs
+        return self._glmm_terms(self._lib.lrvb_glmm_slopes_terms, True, True, mean, var, e, r, gh_x, gh_w, want_grad, want_hess, want_border)
 
     def glmm_slopes_schur(self, local_blocks, border_scale, closed_rows):
         """M ((2 P + 3 K)^2) = sum_g C_g^T A_g^-1 C_g from the resident group sums of the last `glmm_slopes_terms`
@@ -438,49 +462,25 @@ class DeviceContext(object):
     def glmm_obs_influence(self, mean, var, e, r, gh_x, gh_w, A, n0=0, n1=None):
         """(n1 - n0) x Q rows, row n = A times column n of the weight cross Hessian of the logistic mixed model in the coordinates
         (mean, var, e, r), per unit weight (lrvb_glmm_obs_influence).  A: Q x (2 P + 2 G), columns [A_m | A_v | A_e | A_r]."""
-        e, r = _hip.as_f64(e).reshape(-1, 1), _hip.as_f64(r).reshape(-1, 1)        # G x 1: one effect per group
-        (m, v, e, r, gx, gw, Ag, Al), Q = self._glmm_influence_args(mean, var, e, r, gh_x, gh_w, A)
-        n0 = int(n0)
-        n1 = self.n_obs if n1 is None else int(n1)
-        out = np.empty((max(n1 - n0, 0), Q))
-        self._check(self._lib.lrvb_glmm_obs_influence(self._h, _hip.ptr(m), _hip.ptr(v), self.n_cols, _hip.ptr(e), _hip.ptr(r), e.size,
-                                                     _hip.ptr(gx), _hip.ptr(gw), gx.size, _hip.ptr(Ag), _hip.ptr(Al), Q, n0, n1, _hip.ptr(out)))
-        return out
+        return self._glmm_obs_influence(self._lib.lrvb_glmm_obs_influence, True, False, mean, var, e, r, gh_x, gh_w, A, n0, n1)
 
     def glmm_group_influence(self, mean, var, e, r, gh_x, gh_w, A):
         """G x Q: row g = sum over the rows of group g of w_n times the row of `glmm_obs_influence` (lrvb_glmm_group_influence):
         the derivative with respect to a common multiplier on the weights of the group's rows.  The group's own prior term on
         u_g is not part of it."""
-        e, r = _hip.as_f64(e).reshape(-1, 1), _hip.as_f64(r).reshape(-1, 1)        # G x 1: one effect per group
-        (m, v, e, r, gx, gw, Ag, Al), Q = self._glmm_influence_args(mean, var, e, r, gh_x, gh_w, A)
-        out = np.empty((e.size, Q))
-        self._check(self._lib.lrvb_glmm_group_influence(self._h, _hip.ptr(m), _hip.ptr(v), self.n_cols, _hip.ptr(e), _hip.ptr(r), e.size,
-                                                       _hip.ptr(gx), _hip.ptr(gw), gx.size, _hip.ptr(Ag), _hip.ptr(Al), Q, _hip.ptr(out)))
-        return out
+        return self._glmm_group_influence(self._lib.lrvb_glmm_group_influence, True, False, mean, var, e, r, gh_x, gh_w, A)
 
     def glmm_slopes_obs_influence(self, mean, var, e, r, gh_x, gh_w, A, n0=0, n1=None):
         """(n1 - n0) x Q rows, row n = A times column n of the weight cross Hessian of the logistic mixed model with K effects per
         group in the coordinates (mean, var, e, r), per unit weight (lrvb_glmm_slopes_obs_influence).  A: Q x (2 P + 2 G K),
         columns [A_m | A_v | A_e | A_r], the local parts group-major as e and r."""
-        (m, v, e, r, gx, gw, Ag, Al), Q = self._glmm_influence_args(mean, var, e, r, gh_x, gh_w, A)
-        n0 = int(n0)
-        n1 = self.n_obs if n1 is None else int(n1)
-        out = np.empty((max(n1 - n0, 0), Q))
-        self._check(self._lib.lrvb_glmm_slopes_obs_influence(self._h, _hip.ptr(m), _hip.ptr(v), self.n_cols, _hip.ptr(e), _hip.ptr(r),
-                                                            e.shape[0], e.shape[1], _hip.ptr(gx), _hip.ptr(gw), gx.size, _hip.ptr(Ag),
-                                                            _hip.ptr(Al), Q, n0, n1, _hip.ptr(out)))
-        return out
+        return self._glmm_obs_influence(self._lib.lrvb_glmm_slopes_obs_influence, True, True, mean, var, e, r, gh_x, gh_w, A, n0, n1)
 
     def glmm_slopes_group_influence(self, mean, var, e, r, gh_x, gh_w, A):
         """G x Q: row g = sum over the rows of group g of w_n times the row of `glmm_slopes_obs_influence`
         (lrvb_glmm_slopes_group_influence): the derivative with respect to a common multiplier on the weights of the group's rows.
         The group's own prior terms on u_g are not part of it."""
-        (m, v, e, r, gx, gw, Ag, Al), Q = self._glmm_influence_args(mean, var, e, r, gh_x, gh_w, A)
-        out = np.empty((e.shape[0], Q))
-        self._check(self._lib.lrvb_glmm_slopes_group_influence(self._h, _hip.ptr(m), _hip.ptr(v), self.n_cols, _hip.ptr(e), _hip.ptr(r),
-                                                              e.shape[0], e.shape[1], _hip.ptr(gx), _hip.ptr(gw), gx.size, _hip.ptr(Ag),
-                                                              _hip.ptr(Al), Q, _hip.ptr(out)))
-        return out
+        return self._glmm_group_influence(self._lib.lrvb_glmm_slopes_group_influence, True, True, mean, var, e, r, gh_x, gh_w, A)
 
     # ---- Poisson mixed model (lrvb_glmm_poisson_*): the layouts of the slopes entries, no quadrature ---------------------------
     def set_offset(self, offset):
@@ -495,39 +495,15 @@ class DeviceContext(object):
         """Data term of the Poisson mixed model with K effects per group in the coordinates (mean, var, e, r), e and r being G x K
         (lrvb_glmm_poisson_terms): what `glmm_slopes_terms` returns, in its layouts.  The group sums stay resident for
         `glmm_slopes_schur`.  A point at which exp(rho + s / 2) overflows is a ValueError."""
-        m, v = _hip.as_f64(mean).ravel(), _hip.as_f64(var).ravel()
-        e, r = _hip.as_f64(e), _hip.as_f64(r)
-        P = self.n_cols
-        if e.ndim != 2 or r.shape != e.shape or m.size != P or v.size != P:
-            raise ValueError('expected mean and var of length {}, e and r of one shape G x K'.format(P))
-        G, K = e.shape
-        nsc = 2 * K + K * (2 * K + 1)
-        val = np.empty(1)
-        gg = np.empty(2 * P) if want_grad else None
-        Hb = np.empty((3, P, P)) if want_hess else None
-        border = bool(want_hess and want_border)
-        gs = np.empty((G, nsc + (4 * K * P if border else 0))) if (want_grad or want_hess) else None
-        self._check(self._lib.lrvb_glmm_poisson_terms(self._h, _hip.ptr(m), _hip.ptr(v), P, _hip.ptr(e), _hip.ptr(r), G, K, _hip.ptr(val),
-                                                     _hip.ptr(gg), _hip.ptr(Hb), _hip.ptr(gs), 1 if border else 0))
-        return float(val[0]), gg, Hb, gs
+        return self._glmm_terms(self._lib.lrvb_glmm_poisson_terms, False, True, mean, var, e, r, (), (), want_grad, want_hess, want_border)
 
     def glmm_poisson_obs_influence(self, mean, var, e, r, A, n0=0, n1=None):
         """(n1 - n0) x Q rows of the Poisson mixed model, as `glmm_slopes_obs_influence` (lrvb_glmm_poisson_obs_influence)."""
-        (m, v, e, r, _, _, Ag, Al), Q = self._glmm_influence_args(mean, var, e, r, (), (), A)
-        n0 = int(n0)
-        n1 = self.n_obs if n1 is None else int(n1)
-        out = np.empty((max(n1 - n0, 0), Q))
-        self._check(self._lib.lrvb_glmm_poisson_obs_influence(self._h, _hip.ptr(m), _hip.ptr(v), self.n_cols, _hip.ptr(e), _hip.ptr(r),
-                                                             e.shape[0], e.shape[1], _hip.ptr(Ag), _hip.ptr(Al), Q, n0, n1, _hip.ptr(out)))
-        return out
+        return self._glmm_obs_influence(self._lib.lrvb_glmm_poisson_obs_influence, False, True, mean, var, e, r, (), (), A, n0, n1)
 
     def glmm_poisson_group_influence(self, mean, var, e, r, A):
         """G x Q group influence of the Poisson mixed model, as `glmm_slopes_group_influence` (lrvb_glmm_poisson_group_influence)."""
-        (m, v, e, r, _, _, Ag, Al), Q = self._glmm_influence_args(mean, var, e, r, (), (), A)
-        out = np.empty((e.shape[0], Q))
-        self._check(self._lib.lrvb_glmm_poisson_group_influence(self._h, _hip.ptr(m), _hip.ptr(v), self.n_cols, _hip.ptr(e), _hip.ptr(r),
-                                                               e.shape[0], e.shape[1], _hip.ptr(Ag), _hip.ptr(Al), Q, _hip.ptr(out)))
-        return out
+        return self._glmm_group_influence(self._lib.lrvb_glmm_poisson_group_influence, False, True, mean, var, e, r, (), (), A)
 
     # ---- binomial mixed model (lrvb_glmm_binomial_*): the layouts of the slopes entries, per-row trials and offset -------------
     def set_trials(self, trials):
@@ -542,43 +518,15 @@ class DeviceContext(object):
         """Data term of the binomial mixed model with K effects per group, the trials of `set_trials` and the offset of
         `set_offset` (lrvb_glmm_binomial_terms): what `glmm_slopes_terms` returns, in its layouts.  The group sums stay
         resident for `glmm_slopes_schur`."""
-        m, v = _hip.as_f64(mean).ravel(), _hip.as_f64(var).ravel()
-        e, r = _hip.as_f64(e), _hip.as_f64(r)
-        gx, gw = _hip.as_f64(gh_x).ravel(), _hip.as_f64(gh_w).ravel()
-        P = self.n_cols
-        if e.ndim != 2 or r.shape != e.shape or m.size != P or v.size != P or gx.size != gw.size:
-            raise ValueError('expected mean and var of length {}, e and r of one shape G x K and as many weights as nodes'.format(P))
-        G, K = e.shape
-        nsc = 2 * K + K * (2 * K + 1)
-        val = np.empty(1)
-        gg = np.empty(2 * P) if want_grad else None
-        Hb = np.empty((3, P, P)) if want_hess else None
-        border = bool(want_hess and want_border)
-        gs = np.empty((G, nsc + (4 * K * P if border else 0))) if (want_grad or want_hess) else None
-        self._check(self._lib.lrvb_glmm_binomial_terms(self._h, _hip.ptr(m), _hip.ptr(v), P, _hip.ptr(e), _hip.ptr(r), G, K, _hip.ptr(gx),
-                                                      _hip.ptr(gw), gx.size, _hip.ptr(val), _hip.ptr(gg), _hip.ptr(Hb), _hip.ptr(gs),
-                                                      1 if border else 0))
-        return float(val[0]), gg, Hb, gs
+        return self._glmm_terms(self._lib.lrvb_glmm_binomial_terms, True, True, mean, var, e, r, gh_x, gh_w, want_grad, want_hess, want_border)
 
     def glmm_binomial_obs_influence(self, mean, var, e, r, gh_x, gh_w, A, n0=0, n1=None):
         """(n1 - n0) x Q rows of the binomial mixed model, as `glmm_slopes_obs_influence` (lrvb_glmm_binomial_obs_influence)."""
-        (m, v, e, r, gx, gw, Ag, Al), Q = self._glmm_influence_args(mean, var, e, r, gh_x, gh_w, A)
-        n0 = int(n0)
-        n1 = self.n_obs if n1 is None else int(n1)
-        out = np.empty((max(n1 - n0, 0), Q))
-        self._check(self._lib.lrvb_glmm_binomial_obs_influence(self._h, _hip.ptr(m), _hip.ptr(v), self.n_cols, _hip.ptr(e), _hip.ptr(r),
-                                                              e.shape[0], e.shape[1], _hip.ptr(gx), _hip.ptr(gw), gx.size, _hip.ptr(Ag),
-                                                              _hip.ptr(Al), Q, n0, n1, _hip.ptr(out)))
-        return out
+        return self._glmm_obs_influence(self._lib.lrvb_glmm_binomial_obs_influence, True, True, mean, var, e, r, gh_x, gh_w, A, n0, n1)
 
     def glmm_binomial_group_influence(self, mean, var, e, r, gh_x, gh_w, A):
         """G x Q group influence of the binomial mixed model, as `glmm_slopes_group_influence` (lrvb_glmm_binomial_group_influence)."""
-        (m, v, e, r, gx, gw, Ag, Al), Q = self._glmm_influence_args(mean, var, e, r, gh_x, gh_w, A)
-        out = np.empty((e.shape[0], Q))
-        self._check(self._lib.lrvb_glmm_binomial_group_influence(self._h, _hip.ptr(m), _hip.ptr(v), self.n_cols, _hip.ptr(e), _hip.ptr(r),
-                                                                e.shape[0], e.shape[1], _hip.ptr(gx), _hip.ptr(gw), gx.size, _hip.ptr(Ag),
-                                                                _hip.ptr(Al), Q, _hip.ptr(out)))
-        return out
+        return self._glmm_group_influence(self._lib.lrvb_glmm_binomial_group_influence, True, True, mean, var, e, r, gh_x, gh_w, A)
 
     # ---- multinomial (softmax) regression: beta is (K - 1) x n_cols, D = (K - 1) n_cols (lrvb_softmax_*) --------------------
     def softmax_set_labels(self, labels, n_classes):

@@ -8,10 +8,12 @@ solve), prints the LRVB standard errors of beta and mu (through the Schur comple
 mean-field ones, ranks the groups by their influence on beta[0] (streamed on the device), drops the top group, refits and prints
 the predicted change next to the actual one.
 
-    python examples/poisson_glmm.py [--small] [--device-solve]
+    python examples/poisson_glmm.py [--small] [--device-solve] [--predict]
 
 --device-solve takes the Newton polish and the operand of the group influence through the device-resident block-arrow solve
-(`on_device=True`): the border of the Hessian never reaches the host.
+(`on_device=True`): the border of the Hessian never reaches the host.  --predict prints, after the standard errors, the standard
+errors of a few groups' effects and the fitted rates of a few rows and of one unseen design row at the population level, each
+with its LRVB and its mean-field standard error (`ranef_se`, `predict`: the rows are streamed on the device).
 """
 import os
 import sys
@@ -82,6 +84,23 @@ def main():
     print('%-10s %12s %12s' % ('', 'mean-field se', 'LRVB se'))
     for k in list(range(min(P, 4))) + [P + k for k in range(K)]:
         print('%-10s %12.5f %12.5f' % (names[k], se_mf[k], se_lr[k]))
+
+    if '--predict' in sys.argv:
+        se_u, se_u_mf = fun.ranef_se(th, on_device=True)
+        print('%-10s %12s %12s' % ('', 'mean-field se', 'LRVB se'))
+        for g in range(3):
+            for k in range(K):
+                print('%-10s %12.5f %12.5f' % ('u[%d, %d]' % (g, k), se_u_mf[g, k], se_u[g, k]))
+        t0 = time.perf_counter()
+        fitted = fun.predict(th, on_device=True)                          # all N rows; the group blocks are already resident
+        t_fit = time.perf_counter() - t0
+        x_new = rng.standard_normal((1, P)) / np.sqrt(P)
+        unseen = fun.predict(th, newdata=dict(x=x_new, z=np.array([[1.0, 0.5]]), groups=[-1], offset=np.zeros(1)), on_device=True)
+        print('fitted rate of %d rows in %.3f s; the linear predictor and its standard errors:' % (N, t_fit))
+        print('%-12s %10s %10s %12s %10s %10s' % ('row', 'rho', 'rate', 'mean-field se', 'LRVB se', 'group'))
+        for label, out, i, g in [('%d' % i, fitted, i, int(gid[i])) for i in range(4)] + [('unseen', unseen, 0, -1)]:
+            print('%-12s %10.4f %10.4f %12.5f %10.5f %10s' % (label, out['rho'][i], out['mean_lrvb'][i], np.sqrt(out['var_mf'][i]),
+                                                           np.sqrt(out['var_lrvb'][i]), 'population' if g < 0 else str(g)))
 
     # leave one cluster out: groups ranked by their streamed influence on beta[0], the top one dropped and refitted
     Mb = np.zeros((1, ng))

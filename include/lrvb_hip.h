@@ -590,6 +590,55 @@ int lrvb_glmm_binomial_group_influence(lrvb_ctx* ctx, const double* mean, const 
                                        const double* r, int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
                                        const double* A_global, const double* A_local, int64_t Q, double* out);
 
+/* ---- group blocks of H^-1, fitted values and predictions with their linear-response variance ------------
+ * For every mixed model with K <= 4 effects per group.  After a successful lrvb_glmm_slopes_schur (the factor L_g, U_g resident)
+ * and a factored free Schur complement S on the caller's side, with
+ *   W (R x R, row-major) = (S^-1)[coupled rows, coupled rows], R = 2 P + 3 K in the order of M_out of lrvb_glmm_slopes_schur, and
+ *   s (R) the scaling of the coupled rows of lrvb_glmm_slopes_solve_forward / _back (the border is Hx[r, l] = s_r C_g[l, r]),
+ * Y_g = L_g^-T (U_g diag(s)) (2 K x R) gives the blocks of H^-1 of group g:
+ *   Cov(coupled rows, l_g) = -W Y_g^T,   Cov(l_g, l_g) = A_g^-1 + Y_g W Y_g^T.
+ * One workgroup per group writes the K leading rows (the means e_g. of the effects) into a RESIDENT buffer of G + 1 rows of
+ * K K + K P doubles, [Sigma_uu (K x K, row-major) | Sigma_ubeta (K x P, k-major: the P values against the means of beta
+ * contiguous)]; row G is the pseudo-group of a population-level prediction (u = mu): W[mu rows, mu rows] | W[mu rows, :P].
+ * out (host, (G + 1) x (K K + K P); may be NULL) receives a copy.  Fixed order, no atomics: two calls give equal bits.  The
+ * upload is R^2 + R doubles.  The buffer is dropped wherever the factor is (lrvb_glmm_slopes_terms and its siblings,
+ * lrvb_set_group_design, lrvb_set_groups, lrvb_set_offset, lrvb_set_trials, the next lrvb_glmm_slopes_schur).
+ * No reduce-hook call.  Errors as lrvb_glmm_slopes_solve_forward: a null W or s: LRVB_ERR_INVALID; K < 1 or K > 4:
+ * LRVB_ERR_UNSUPPORTED; no resident factor of K effects: LRVB_ERR_STATE; G not the number of groups, P not n_cols: LRVB_ERR_SIZE. */
+int lrvb_glmm_slopes_group_cov(lrvb_ctx* ctx, const double* W, const double* s, int64_t P, int64_t G, int64_t K, double* out);
+/* Fitted values and predictions: the streaming sibling of lrvb_glmm_slopes_obs_influence.  Point arguments as there, except that
+ * e and r are G' x K with G' = G or G + 1 (row G: the pseudo-group, e_mu and 1 / i_mu); cov_beta (P x P, row-major, host) is
+ * Sigma_bb = W[:P, :P].  Per row with design (x, z), group g and offset o,
+ *   rho = o + x . mean + z . e_g,   var_mf = (x o x) . var + (z o z) . r_g,
+ *   var_lrvb = x^T Sigma_bb x + 2 sum_k z_k (x . Sigma_ubeta[g][k]) + z^T Sigma_uu[g] z      (blocks of the resident buffer),
+ *   mean_mf, mean_lrvb = the response-scale mean of the likelihood at (rho, var_mf) and at (rho, var_lrvb): E sigma(t),
+ *   t ~ N(rho, .), by the Gauss-Hermite rule (logistic); exp(rho + . / 2) (Poisson); m E sigma(t) (binomial, m the trials).
+ * out (host, 5 x n row-major: rho | var_mf | var_lrvb | mean_mf | mean_lrvb).  The rows are
+ *   x_new == NULL: the window [n0, n1) of the context's rows, groups, group design (and offset, trials), n = n1 - n0;
+ *   x_new != NULL: n = n_new new rows x_new (n x P), z_new (n x K), gid_new (n int32 in [0, G')), offset_new and trials_new (n
+ *   each; NULL: zero, one), uploaded to scratch; n0 and n1 are ignored.  A gid_new outside [0, G') is refused here, before
+ *   anything is launched: LRVB_ERR_INVALID.
+ * ONE pass over the rows in their order: a tile of 64 rows is staged on chip, x^T Sigma_bb x runs on the fp64 matrix cores, the
+ * K P + K K values of the row's own group are gathered and added behind it.  A window equals the same rows of the full result
+ * bitwise, and new rows that are copies of the context's rows give the context's bits.  Rank-local: NO reduce-hook call.
+ * The resident blocks belong to the weights, offset and point at the time of lrvb_glmm_slopes_schur.  lrvb_set_weights does NOT
+ * drop the resident mixed-model state (it never has): after a direct call of it these entries still return LRVB_OK, with blocks of the
+ * OLD weights.  A caller who changes the weights runs the terms, lrvb_glmm_slopes_schur and lrvb_glmm_slopes_group_cov again (the
+ * Python classes do, through the key of the point).
+ * Errors as the _obs_influence sibling, and: no resident group covariance of K effects: LRVB_ERR_STATE; G' not G or G + 1:
+ * LRVB_ERR_SIZE; a null cov_beta, out, z_new or gid_new, n_new < 0, a bad window: LRVB_ERR_INVALID.                              */
+int lrvb_glmm_slopes_predict(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                             int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes, const double* cov_beta,
+                             int64_t n0, int64_t n1, const double* x_new, const double* z_new, const int32_t* gid_new, int64_t n_new,
+                             double* out);
+int lrvb_glmm_poisson_predict(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                              int64_t G, int64_t K, const double* cov_beta, int64_t n0, int64_t n1, const double* x_new,
+                              const double* z_new, const int32_t* gid_new, const double* offset_new, int64_t n_new, double* out);
+int lrvb_glmm_binomial_predict(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                               int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes, const double* cov_beta,
+                               int64_t n0, int64_t n1, const double* x_new, const double* z_new, const int32_t* gid_new,
+                               const double* offset_new, const double* trials_new, int64_t n_new, double* out);
+
 /* ---- multinomial (softmax) regression ---------------------------------------------------------
  * K classes (2 <= K <= 17), labels y_n in {0 .. K-1}, class 0 the reference; coefficients beta ((K-1) x P, row-major, row a
  * belongs to class a + 1, P = n_cols <= 1024), z_na = x_n . beta_a, z_n0 = 0, p_n = softmax(z_n).  The data term

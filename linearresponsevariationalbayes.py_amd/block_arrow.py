@@ -220,3 +220,93 @@ def block_arrow_solve_by_phases(R, n_global, rows, s, forward, schur_solve, back
     xl = np.asarray(back(np.ascontiguousarray(s[:, None] * xg[rows]))).reshape(G, 2 * K, -1)
     out = np.vstack([xg, _from_groups(xl, G, K)])
     return out.ravel() if vec else out
+
+
+# ---- group blocks of H^-1 and the variance of a row's linear predictor ---------------------------------------
+def unpack_group_cov(buf, P, K):
+    """The G' x (K K + K P) group-covariance buffer of the device, rows [Sigma_uu (K x K, row-major) | Sigma_ubeta (K x P, k-major)],
+    as (cov_u G' x K x K, cov_beta_u G' x P x K)."""
+    buf = np.asarray(buf, dtype=np.float64).reshape(-1, K * K + K * P)
+    return buf[:, :K * K].reshape(-1, K, K).copy(), np.ascontiguousarray(buf[:, K * K:].reshape(-1, K, P).transpose(0, 2, 1))
+
+
+def block_arrow_group_cov_by_phases(n_global, rows, P, K, s, schur_solve, group_blocks):
+    """The blocks of H^-1 that predictions need, where the local factor is held by somebody else (the device, or a numpy
+    restatement of it) as L_g and U_g = L_g^-1 C_g with Hx[r, l] = s_r C_g[l, r] (`block_arrow_solve_by_phases`):
+
+        schur_solve(rhs: n_global x R) -> S^-1 rhs;   W = (S^-1)[rows, rows] from the unit columns of `rows`
+        group_blocks(W: R x R, s) -> (G + 1) x (K K + K P): row g = [(A_g^-1 + Y_g W Y_g^T)[:K, :K] | -(Y_g W)[:K, :P]],
+                                     Y_g = L_g^-T (U_g diag(s)); row G = the pseudo-group [W[mu, mu] | W[mu, :P]]
+
+    Returns (cov_beta P x P, the buffer)."""
+    rows, s = np.asarray(rows), np.asarray(s, dtype=np.float64)
+    R = len(rows)
+    if R != 2 * P + 3 * K or s.shape != (R,):
+        raise ValueError('expected the {} coupled rows and their scaling'.format(2 * P + 3 * K))
+    E = np.zeros((int(n_global), R))
+    E[rows, np.arange(R)] = 1.0
+    W = np.ascontiguousarray(np.asarray(schur_solve(E), dtype=np.float64).reshape(int(n_global), R)[rows])
+    buf = np.asarray(group_blocks(W, s), dtype=np.float64)
+    return W[:P, :P].copy(), buf
+
+
+def _host_group_blocks(chol, U3, P, K):
+    """group_blocks of `block_arrow_group_cov_by_phases` in numpy from (L, 1 / diag L) of `_local_chol` and U3 (R x 2 K x G: slab i is
+    row i of L_g^-1 C_g for every group)."""
+    L, dinv = chol
+    R, G = U3.shape[0], U3.shape[2]
+    mu = 2 * P + 3 * np.arange(K)
+
+    def group_blocks(W, s):
+        Y = [U3[:, i] * s[:, None] for i in range(2 * K)]
+        _backward(L, dinv, Y, lambda c: c)
+        Ye = np.stack(Y[:K])                                               # K x R x G: the rows of e_g.
+        Eg = np.einsum('krg,rc->kcg', Ye, W)
+        Ai = np.zeros((2 * K, 2 * K, G))                                   # A_g^-1, column by column
+        for k in range(K):
+            T = [np.full((1, G), 1.0 if i == k else 0.0) for i in range(2 * K)]
+            _forward(L, dinv, T, T, lambda c: c)
+            _backward(L, dinv, T, lambda c: c)
+            for l in range(K):
+                Ai[l, k] = T[l][0]
+        uu = Ai[:K, :K].transpose(2, 0, 1) + np.einsum('kcg,lcg->gkl', Eg, Ye)
+        ub = -Eg[:, :P].transpose(2, 0, 1)                                 # G x K x P
+        buf = np.empty((G + 1, K * K + K * P))
+        buf[:G, :K * K], buf[:G, K * K:] = uu.reshape(G, -1), ub.reshape(G, -1)
+        buf[G, :K * K], buf[G, K * K:] = W[np.ix_(mu, mu)].ravel(), W[mu, :P].ravel()
+        return buf
+    return group_blocks
+
+
+def block_arrow_group_cov(Hgg, rows, Hx, loc, P, K, population=False):
+    """(cov_beta P x P, cov_u G x K x K, cov_beta_u G x P x K): the blocks of H^-1 between the means of beta and the means e_g. of
+    every group's effects, from the pieces of the block arrow -- O(G K R^2 + n_global^3), no dense matrix.  With
+    Y_g = A_g^-1 C_g^T (2 K x R) and W = (S^-1)[rows, rows]:  Cov(rows, l_g) = -W Y_g^T,  Cov(l_g, l_g) = A_g^-1 + Y_g W Y_g^T.
+    population=True appends the pseudo-group G of a population-level prediction (u = mu): cov_u[G] = W[mu, mu],
+    cov_beta_u[G] = W[:P, mu]."""
+    ng, G = Hgg.shape[0], loc.shape[0]
+    R = len(rows)
+    chol = _local_chol(loc)
+    U = _half_border(chol, Hx, G, K)
+    S = Hgg.copy()
+    S[np.ix_(rows, rows)] -= U @ U.T
+    Ls = np.linalg.cholesky(0.5 * (S + S.T))
+    cov_beta, buf = block_arrow_group_cov_by_phases(ng, rows, P, K, np.ones(R), lambda rhs: sp_linalg.cho_solve((Ls, True), rhs),
+                                                    _host_group_blocks(chol, U.reshape(R, 2 * K, G), P, K))
+    cov_u, cov_bu = unpack_group_cov(buf, P, K)
+    return (cov_beta, cov_u, cov_bu) if population else (cov_beta, cov_u[:G], cov_bu[:G])
+
+
+def predict_rows(x, z, gid, offset, m, v, e, r, cov_beta, cov_u, cov_beta_u):
+    """(rho, var_mf, var_lrvb) of rows with design (x N x P, z N x K), group index gid (into e, r, cov_u, cov_beta_u: the
+    pseudo-group of a population-level row included) and offset (N, or None):
+        rho = o + x . m + z . e_g,   var_mf = (x o x) . v + (z o z) . r_g,
+        var_lrvb = x^T S_bb x + 2 x^T S_bu,g z + z^T S_uu,g z."""
+    x, z, gid = np.asarray(x, dtype=np.float64), np.asarray(z, dtype=np.float64), np.asarray(gid)
+    rho = x @ m + np.sum(z * e[gid], axis=1)
+    if offset is not None:
+        rho = rho + np.asarray(offset, dtype=np.float64)
+    var_mf = (x * x) @ v + np.sum(z * z * r[gid], axis=1)
+    var_lr = (np.einsum('np,pq,nq->n', x, cov_beta, x) + 2.0 * np.einsum('np,npk,nk->n', x, cov_beta_u[gid], z)
+              + np.einsum('nk,nkl,nl->n', z, cov_u[gid], z))
+    return rho, var_mf, var_lr

@@ -605,6 +605,309 @@ int launch_glmm_slopes_infl_rows(lrvb_ctx* c, const GlmmLik& lik, int Kz, const 
     return gs_launch_infl_rows<LogisticLik>(c, Kz, Z, {lik.gx, lik.gw, lik.n_nodes}, n0, n1, gid, m, vb, eg, rg, Ag, Al, Q, out);
 }
 
+// ---- group blocks of H^-1 and fitted values with their linear-response variance ---------------------------
+// From the factor lrvb_glmm_slopes_schur left resident (the blocks as uploaded, U_g = L_g^-1 C_g), W = (S^-1)[rows, rows] (R x R)
+// and the scaling s of the coupled rows, one workgroup per group writes the two blocks of H^-1 that a prediction in that group
+// needs, row g of a G + 1 row buffer of K K + K P doubles, [Sigma_uu (K x K, row-major) | Sigma_ubeta (K x P, k-major)]:
+//   1. thread 0: L_g by gs_local_chol (the L of the solve kernels, bit for bit);
+//   2. thread c < R: column c of Y_g = L_g^-T (U_g diag(s)) by back substitution; its K leading rows (the rows of e_g.) go to LDS.
+//      Threads 192 .. 192 + K - 1: column k of A_g^-1 = L^-T L^-1, its K leading entries to LDS;
+//   3. thread c < R: column c of E_g = Y_g[:K] W, a sum over the R rows of W in their order (consecutive threads read consecutive
+//      doubles of a row of W, R R <= 157 KB and so expected in L2; Y is an LDS broadcast);  Sigma_ubeta[k][j] = -E_g[k][j], j < P;
+//   4. thread t < K K: Sigma_uu[k][l] = A_g^-1[k][l] + sum_c E_g[k][c] Y_g[l][c], in the order of c.
+// Workgroup G writes the pseudo-group of a population-level prediction (u = mu): Sigma_uu = W[mu rows, mu rows], Sigma_ubeta =
+// W[mu rows, :P].  E_g is formed here and not by the library's GEMM: Y_g would have to be written out (K G x ld(R) doubles, the
+// size of half of U) and read back for 2 K R^2 flops per group, and the kernel would still be needed around it (a choice on
+// these counts; the GEMM variant was not built or timed).  No atomics, one
+// writer per output, fixed order: two calls give equal bits.
+constexpr int GSP_RMAX = 2 * 64 + 3 * 4;   // coupled rows at P = 64, K = 4
+
+template <int KZ>
+__global__ __launch_bounds__(256)
+void glmm_slopes_group_cov_kernel(i64 G, int P, const double* __restrict__ loc /* G x K (2 K + 1) */, const double* __restrict__ U,
+                                  int ldu, const double* __restrict__ W /* R x R */, const double* __restrict__ s /* R */,
+                                  double* __restrict__ out /* (G + 1) x (K K + K P) */)
+{
+    constexpr int K2 = 2 * KZ, NT = KZ * (K2 + 1), KK = KZ * KZ;
+    __shared__ double Ls[K2 * K2], Ys[KZ * GSP_RMAX], Es[KZ * GSP_RMAX], Ai[KK];
+    const i64 g = blockIdx.x;
+    if (g > G) return;
+    const int R = 2 * P + 3 * KZ, ncg = KK + KZ * P;
+    const int tid = threadIdx.x;
+    double* og = out + g * ncg;
+    if (g == G) {
+        for (int t = tid; t < ncg; t += 256) {
+            if (t < KK) { const int k = t / KZ, l = t - k * KZ; og[t] = W[(i64)(2 * P + 3 * k) * R + 2 * P + 3 * l]; }
+            else { const int u = t - KK, k = u / P, j = u - k * P; og[t] = W[(i64)(2 * P + 3 * k) * R + j]; }
+        }
+        return;
+    }
+    if (tid == 0) gs_local_chol<K2>(loc + g * NT, Ls);
+    __syncthreads();
+    for (int c = tid; c < R; c += 256) {
+        double y[K2];
+        const double sc = s[c];
+#pragma unroll
+        for (int i = 0; i < K2; ++i) y[i] = U[(g * K2 + i) * ldu + c] * sc;
+#pragma unroll
+        for (int i = K2 - 1; i >= 0; --i) {
+            double v = y[i];
+#pragma unroll
+            for (int j = i + 1; j < K2; ++j) v -= Ls[j * K2 + i] * y[j];
+            y[i] = v / Ls[i * K2 + i];
+        }
+#pragma unroll
+        for (int k = 0; k < KZ; ++k) Ys[k * GSP_RMAX + c] = y[k];
+    }
+    if (tid >= 192 && tid < 192 + KZ) {
+        const int k = tid - 192;
+        double x[K2];
+#pragma unroll
+        for (int i = 0; i < K2; ++i) {
+            double v = i == k ? 1.0 : 0.0;
+#pragma unroll
+            for (int j = 0; j < i; ++j) v -= Ls[i * K2 + j] * x[j];
+            x[i] = v / Ls[i * K2 + i];
+        }
+#pragma unroll
+        for (int i = K2 - 1; i >= 0; --i) {
+            double v = x[i];
+#pragma unroll
+            for (int j = i + 1; j < K2; ++j) v -= Ls[j * K2 + i] * x[j];
+            x[i] = v / Ls[i * K2 + i];
+        }
+#pragma unroll
+        for (int l = 0; l < KZ; ++l) Ai[l * KZ + k] = x[l];
+    }
+    __syncthreads();
+    for (int c = tid; c < R; c += 256) {
+        double acc[KZ];
+#pragma unroll
+        for (int k = 0; k < KZ; ++k) acc[k] = 0.0;
+        for (int cp = 0; cp < R; ++cp) {
+            const double w = W[(i64)cp * R + c];
+#pragma unroll
+            for (int k = 0; k < KZ; ++k) acc[k] += Ys[k * GSP_RMAX + cp] * w;
+        }
+#pragma unroll
+        for (int k = 0; k < KZ; ++k) {
+            Es[k * GSP_RMAX + c] = acc[k];
+            if (c < P) og[KK + k * P + c] = -acc[k];
+        }
+    }
+    __syncthreads();
+    if (tid < KK) {
+        const int k = tid / KZ, l = tid - k * KZ;
+        double acc = 0.0;
+        for (int c = 0; c < R; ++c) acc += Es[k * GSP_RMAX + c] * Ys[l * GSP_RMAX + c];
+        og[tid] = Ai[tid] + acc;
+    }
+}
+
+int launch_glmm_slopes_group_cov(lrvb_ctx* c, int Kz, const double* loc, const double* U, int ldu, const double* W, const double* s,
+                                 double* out) {
+    const i64 G = c->n_groups;
+    const dim3 grid((unsigned)(G + 1)), block(256);
+    const int P = (int)c->P;
+    if (P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "mixed model with slopes: P <= 64");
+    switch (Kz) {
+    case 1: hipLaunchKernelGGL(glmm_slopes_group_cov_kernel<1>, grid, block, 0, c->stream, G, P, loc, U, ldu, W, s, out); break;
+    case 2: hipLaunchKernelGGL(glmm_slopes_group_cov_kernel<2>, grid, block, 0, c->stream, G, P, loc, U, ldu, W, s, out); break;
+    case 3: hipLaunchKernelGGL(glmm_slopes_group_cov_kernel<3>, grid, block, 0, c->stream, G, P, loc, U, ldu, W, s, out); break;
+    case 4: hipLaunchKernelGGL(glmm_slopes_group_cov_kernel<4>, grid, block, 0, c->stream, G, P, loc, U, ldu, W, s, out); break;
+    default: LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "mixed model with slopes: 1 <= K <= 4");
+    }
+    HIP_TRY(hipGetLastError());
+    return LRVB_OK;
+}
+
+// gsp_predict_rows: the streaming sibling of gsi_infl_rows -- the same tile of 64 rows in their original order, the same staging
+// of x | z at stride GSI_XS, the same Lik::init / stage_row / row_shift -- for five columns of n doubles,
+//   rho = o + x . m + z . e_g,   var_mf = (x o x) . v + (z o z) . r_g,
+//   var_lrvb = x^T S_bb x + 2 sum_k z_k (x . S_ubeta[g][k]) + z^T S_uu[g] z,
+//   mean_mf, mean_lrvb = the policy's e1 (E sigma(t), exp(rho + ./2), m E sigma(t)) at (rho, var_mf) and at (rho, var_lrvb).
+//   1. four lanes per row form rho and var_mf with the column map of gsi_psi_derivs and keep them in registers;
+//   2. wave w owns the rows 16 w .. 16 w + 15: per block of 16 columns of S_bb (P x P, the B operand, zero past P) the product
+//      X S_bb runs as 16 x 16 x 4 fp64 MFMA tiles, two accumulator chains; in the D layout (register r <-> row (l >> 4) + 4 r,
+//      column l & 15) every entry is multiplied by the staged x of its row and column and added to the lane's partial sum of
+//      that row;
+//   3. behind it the lane adds its share of the cross term: the K P values of S_ubeta of the row's OWN group are gathered, 16
+//      consecutive doubles per step for the 16 lanes of a row, against the staged x, times z_k.  The rows of a tile belong to
+//      different groups, so this cannot be an MFMA operand;
+//   4. xor shuffles over the 16 lanes of a row add the partial sums in a fixed order; z^T S_uu z (K K gathered values) is added
+//      and the row's variance goes to LDS;
+//   5. the four lanes of a row run Lik::infl twice, and lane 0 writes the five values.
+// With P <= 16 the B fragments are loaded once per workgroup.  A row's result depends on nothing but the row: a window equals
+// the same rows of the full result bitwise.  No atomics.
+template <class Lik>
+__device__ __forceinline__
+void gsp_predict_rows(i64 n0, i64 R /* rows of the window */, int P, int Kz, const double* __restrict__ X,
+                      const double* __restrict__ Z, const int* __restrict__ gid, const double* __restrict__ m,
+                      const double* __restrict__ vb, const double* __restrict__ eg, const double* __restrict__ rg,
+                      typename Lik::Args la, const double* __restrict__ Sbb /* P x P */,
+                      const double* __restrict__ gcov /* G' x (K K + K P) */, double* __restrict__ out /* 5 x ldo */, i64 ldo)
+{
+    __shared__ double xs[GLMM_T * GSI_XS], vq[GLMM_T], ms[64], vs[64];
+    __shared__ typename Lik::Lds lik;
+    __shared__ int s_gid[GLMM_T];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, l4 = lane >> 4;
+    Lik::init(lik, la, tid);
+    if (tid < 64) { ms[tid] = tid < P ? m[tid] : 0.0; vs[tid] = tid < P ? vb[tid] : 0.0; }
+    for (int e = tid; e < GLMM_T * GSI_XS; e += 256) xs[e] = 0.0;          // what no tile writes stays zero (finite) for the whole kernel
+    const int KS = (P + 3) >> 2;                                         // k-steps of the contraction
+    const int ncb = (P + 15) >> 4;
+    const int KK = Kz * Kz, ncg = KK + Kz * P;
+    double bm[16];
+    auto load_b = [&](int cb) {
+        const int q = 16 * cb + l15;
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk) {
+            const int k = 4 * kk + l4;
+            bm[kk] = (q < P && k < P) ? Sbb[k * P + q] : 0.0;
+        }
+    };
+    if (ncb == 1) load_b(0);
+    const i64 n_tiles = (R + GLMM_T - 1) / GLMM_T;
+    const int row = tid >> 2, q4 = tid & 3;
+    for (i64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const i64 t0 = tile * GLMM_T;
+        const int rows = (int)(R - t0 < GLMM_T ? R - t0 : GLMM_T);
+        __syncthreads();                                                 // the previous tile is consumed (and the nodes, m, v are in place)
+        if (tid < GLMM_T) {
+            s_gid[tid] = tid < rows ? gid[n0 + t0 + tid] : 0;
+            Lik::stage_row(lik, la, tid, tid < rows, n0 + t0 + tid);
+        }
+        {
+            const double* src = X + (n0 + t0) * (i64)P;
+            for (int e = tid; e < rows * P; e += 256) { const int rr = e / P, cc = e - rr * P; xs[rr * GSI_XS + cc] = src[e]; }
+            const double* zsrc = Z + (n0 + t0) * (i64)Kz;
+            for (int e = tid; e < rows * Kz; e += 256) { const int rr = e / Kz, cc = e - rr * Kz; xs[rr * GSI_XS + P + cc] = zsrc[e]; }
+        }
+        __syncthreads();
+        // rho and the mean-field variance: the dot products of gsi_psi_derivs
+        const bool live = row < rows;
+        const double o = Lik::row_shift(lik, row);
+        double rho = 0.0, s = 0.0;
+        if (live) {
+            const double* xr = xs + row * GSI_XS;
+            for (int h = (q4 & 1) + 16 * (q4 >> 1); h < P; h += 32)
+                for (int j = h; j < h + 16 && j < P; j += 2) { const double x = xr[j]; rho += x * ms[j]; s += x * x * vs[j]; }
+            if (q4 < Kz) {
+                const i64 gk = (i64)s_gid[row] * Kz + q4;
+                const double z = xr[P + q4];
+                rho += z * eg[gk]; s += z * z * rg[gk];
+            }
+        }
+        rho += __shfl_xor(rho, 1); s += __shfl_xor(s, 1);
+        rho += __shfl_xor(rho, 2); s += __shfl_xor(s, 2);
+        // the quadratic form of this wave's 16 rows
+        const double* xa = xs + (16 * wave + l15) * GSI_XS + l4;
+        double t[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int cb = 0; cb < ncb; ++cb) {
+            if (ncb > 1) load_b(cb);
+            gsi_d4 a0 = {0.0, 0.0, 0.0, 0.0}, a1 = a0;
+#pragma unroll
+            for (int kk = 0; kk < 16; kk += 2) {
+                if (kk < KS) a0 = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[4 * kk], bm[kk], a0, 0, 0, 0);
+                if (kk + 1 < KS) a1 = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[4 * kk + 4], bm[kk + 1], a1, 0, 0, 0);
+            }
+            const int q = 16 * cb + l15;
+            if (q < P) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) t[r] += (a0[r] + a1[r]) * xs[(16 * wave + l4 + 4 * r) * GSI_XS + q];
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int rr = 16 * wave + l4 + 4 * r;
+            const double* xr = xs + rr * GSI_XS;
+            const double* gc = gcov + (i64)s_gid[rr] * ncg;
+            if (rr < rows) {
+                double cr = 0.0;
+                for (int k = 0; k < Kz; ++k) {
+                    const double* sub = gc + KK + k * P;
+                    double a = 0.0;
+                    for (int j = l15; j < P; j += 16) a += xr[j] * sub[j];
+                    cr += xr[P + k] * a;
+                }
+                t[r] += 2.0 * cr;
+            }
+            double tv = t[r];
+            tv += __shfl_xor(tv, 1); tv += __shfl_xor(tv, 2); tv += __shfl_xor(tv, 4); tv += __shfl_xor(tv, 8);
+            if (l15 == 0) {
+                double uu = 0.0;
+                if (rr < rows)
+                    for (int k = 0; k < Kz; ++k)
+                        for (int l = 0; l < Kz; ++l) uu += xr[P + k] * xr[P + l] * gc[k * Kz + l];
+                vq[rr] = rr < rows ? tv + uu : 0.0;
+            }
+        }
+        __syncthreads();
+        const double v_lr = vq[row];
+        double m_mf, m_lr, e2;
+        Lik::infl(lik, la, o, live, q4, rho, s, m_mf, e2);
+        Lik::infl(lik, la, o, live, q4, rho, v_lr, m_lr, e2);
+        if (live && q4 == 0) {
+            double* dst = out + t0 + row;
+            dst[0] = rho + o; dst[ldo] = s; dst[2 * ldo] = v_lr; dst[3 * ldo] = m_mf; dst[4 * ldo] = m_lr;
+        }
+    }
+}
+
+// The three entries of the walk above, with flat arguments in the order of their influence siblings.
+__global__ __launch_bounds__(256)
+void glmm_slopes_predict_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* __restrict__ X, const double* __restrict__ Z,
+                                     const int* __restrict__ gid, const double* __restrict__ m, const double* __restrict__ vb,
+                                     const double* __restrict__ eg, const double* __restrict__ rg, const double* __restrict__ gx,
+                                     const double* __restrict__ gw, int nq, const double* __restrict__ Sbb,
+                                     const double* __restrict__ gcov, double* __restrict__ out, i64 ldo)
+{
+    gsp_predict_rows<LogisticLik>(n0, R, P, Kz, X, Z, gid, m, vb, eg, rg, {gx, gw, nq}, Sbb, gcov, out, ldo);
+}
+
+__global__ __launch_bounds__(256)
+void glmm_poisson_predict_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* __restrict__ X, const double* __restrict__ Z,
+                                      const double* __restrict__ off, const int* __restrict__ gid, const double* __restrict__ m,
+                                      const double* __restrict__ vb, const double* __restrict__ eg, const double* __restrict__ rg,
+                                      const double* __restrict__ Sbb, const double* __restrict__ gcov, double* __restrict__ out, i64 ldo)
+{
+    gsp_predict_rows<PoissonLik>(n0, R, P, Kz, X, Z, gid, m, vb, eg, rg, off, Sbb, gcov, out, ldo);
+}
+
+__global__ __launch_bounds__(256)
+void glmm_binomial_predict_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* __restrict__ X, const double* __restrict__ Z,
+                                       const double* __restrict__ off, const double* __restrict__ trials, const int* __restrict__ gid,
+                                       const double* __restrict__ m, const double* __restrict__ vb, const double* __restrict__ eg,
+                                       const double* __restrict__ rg, const double* __restrict__ gx, const double* __restrict__ gw,
+                                       int nq, const double* __restrict__ Sbb, const double* __restrict__ gcov,
+                                       double* __restrict__ out, i64 ldo)
+{
+    gsp_predict_rows<BinomialLik>(n0, R, P, Kz, X, Z, gid, m, vb, eg, rg, {{gx, gw, nq}, off, trials}, Sbb, gcov, out, ldo);
+}
+
+int launch_glmm_slopes_predict_rows(lrvb_ctx* c, const GlmmLik& lik, int Kz, const double* X, const double* Z, i64 n0, i64 n1,
+                                    const int* gid, const double* m, const double* vb, const double* eg, const double* rg,
+                                    const double* Sbb, const double* gcov, double* out, i64 ldo) {
+    if (c->P > 64 || Kz < 1 || Kz > 4 || !X || !Z) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "mixed-model prediction: P <= 64, 1 <= K <= 4, a group design");
+    if (lik.kind != GLMM_POISSON && (lik.n_nodes < 1 || lik.n_nodes > 128)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 128 quadrature nodes");
+    const i64 R = n1 - n0;
+    if (R <= 0) return LRVB_OK;
+    const i64 n_tiles = (R + GLMM_T - 1) / GLMM_T;
+    const dim3 grid((unsigned)(n_tiles < 2048 ? n_tiles : 2048)), block(256);
+    const int P = (int)c->P;
+    if (lik.kind == GLMM_POISSON)
+        hipLaunchKernelGGL(glmm_poisson_predict_rows_kernel, grid, block, 0, c->stream, n0, R, P, Kz, X, Z, lik.off, gid, m, vb, eg, rg, Sbb,
+                           gcov, out, ldo);
+    else if (lik.kind == GLMM_BINOMIAL)
+        hipLaunchKernelGGL(glmm_binomial_predict_rows_kernel, grid, block, 0, c->stream, n0, R, P, Kz, X, Z, lik.off, lik.trials, gid, m, vb,
+                           eg, rg, lik.gx, lik.gw, lik.n_nodes, Sbb, gcov, out, ldo);
+    else
+        hipLaunchKernelGGL(glmm_slopes_predict_rows_kernel, grid, block, 0, c->stream, n0, R, P, Kz, X, Z, gid, m, vb, eg, rg, lik.gx, lik.gw,
+                           lik.n_nodes, Sbb, gcov, out, ldo);
+    HIP_TRY(hipGetLastError());
+    return LRVB_OK;
+}
+
 // ---- group influence (lrvb_glmm_slopes_group_influence / lrvb_glmm_poisson_group_influence) --------------------------------------
 // Per group the WEIGHTED sums  [sum a1 z (K) | sum a2 z o z (K) | sum a1 x (P) | sum a2 x o x (P)],  a1 = w (psi_rho - y),
 // a2 = w psi_s  (2 K + 2 P columns): glmm_slopes_rows_kernel cut down to them -- group-sorted rows, two coefficients from

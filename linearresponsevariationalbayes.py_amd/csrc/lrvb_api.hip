@@ -231,7 +231,7 @@ extern "C" int lrvb_ctx_destroy(lrvb_ctx* c) {
     DevBuf* all[] = { &c->X, &c->y, &c->w, &c->quadA, &c->quadM, &c->quadB, &c->theta, &c->eta, &c->j1, &c->j2,
                       &c->vtmp, &c->vtmp2, &c->vtmp3, &c->g_eta, &c->g_free, &c->lp, &c->cw, &c->zbuf,
                       &c->part_vec, &c->part_val, &c->stats, &c->tile_part, &c->Heta, &c->Hfree, &c->Jdense,
-                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn, &c->gz, &c->goff, &c->gtr, &c->glmms, &c->glmms_fac, &c->glmms_T,
+                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn, &c->gz, &c->goff, &c->gtr, &c->glmms, &c->glmms_fac, &c->glmms_T, &c->glmms_gcov,
                       &c->sm.labels, &c->sm.p, &c->sm.wpad, &c->sm.work, &c->sm.col, &c->sm.tiles, &c->sm.rows };
     for (DevBuf* b : all) buf_free(*b);
     if (c->host_pinned) (void)hipHostFree(c->host_pinned);
@@ -2762,7 +2762,7 @@ extern "C" int lrvb_glmm_slopes_schur(lrvb_ctx* c, const double* local_blocks, c
     const i64 P = c->P, G = c->n_groups, R = 2 * P + 3 * K, K2 = 2 * K, NT = K * (K2 + 1);
     LRVB_TRY(check_len(G_in, G, "local blocks"));
     const int ldu = (int)up(R);
-    c->glmms_fac_valid = false; c->glmms_T_Q = 0;
+    c->glmms_fac_valid = false; c->glmms_T_Q = 0; c->glmms_gcov_rows = 0;
     // the uploaded blocks and U outlive the call in a buffer of their own (lrvb_glmm_slopes_solve_forward / _back)
     LRVB_TRY(buf_reserve(c, c->work1, (size_t)(8 + up(K2 * G) + up(3 * K2 * G) + R * R)));
     LRVB_TRY(buf_reserve(c, c->glmms_fac, (size_t)(up(NT * G) + K2 * G * ldu)));
@@ -2989,6 +2989,117 @@ extern "C" int lrvb_glmm_binomial_group_influence(lrvb_ctx* c, const double* mea
                                                   int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, double* out) {
     LRVB_TRY(ctx_bind(c));
     return glmms_group_influence(c, glmms_binomial(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out);
+}
+
+// ---- group blocks of H^-1 and predictions with their linear-response variance (k_glmm_slopes.hip) ----------
+extern "C" int lrvb_glmm_slopes_group_cov(lrvb_ctx* c, const double* W, const double* s, int64_t P_in, int64_t G_in, int64_t K,
+                                          double* out) {
+    LRVB_TRY(ctx_bind(c));
+    LRVB_TRY(glmm_slopes_solve_check(c, W, s, G_in, K, 1));
+    LRVB_TRY(check_len(P_in, c->P, "columns of the design"));
+    if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the mixed models need P <= 64 (got %lld)", (long long)c->P);
+    const i64 P = c->P, G = c->n_groups, R = 2 * P + 3 * K, K2 = 2 * K, NT = K * (K2 + 1), ncg = K * K + K * P;
+    const int ldu = (int)up(R);
+    c->glmms_gcov_rows = 0;
+    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(up(R * R) + up(R))));
+    LRVB_TRY(buf_reserve(c, c->glmms_gcov, (size_t)((G + 1) * ncg)));
+    double* Wd = c->work1.p; double* sd = Wd + up(R * R);
+    LRVB_TRY(h2d(c, Wd, W, (size_t)(R * R)));
+    LRVB_TRY(h2d(c, sd, s, (size_t)R));
+    const double* loc = c->glmms_fac.p; const double* U = loc + up(NT * G);
+    LRVB_TRY(launch_glmm_slopes_group_cov(c, (int)K, loc, U, ldu, Wd, sd, c->glmms_gcov.p));
+    if (out) LRVB_TRY(d2h(c, out, c->glmms_gcov.p, (size_t)((G + 1) * ncg)));
+    c->glmms_gcov_rows = G + 1;
+    return LRVB_OK;
+}
+
+// The predict entries: the checks of glmms_terms in its order (e and r may carry the pseudo-group: Gp = G or G + 1 rows), the
+// resident group covariance, then the rows.  c->work1: [nodes 256 (not Poisson) | m, v (2 up(P)) | e, r (2 up(Gp K)) | Sigma_bb (P P)];
+// c->cgT: [out (5 n) | new rows: x (n P) | z (n K) | offset (n) | trials (n) | groups (n int32)].
+static int glmms_predict(lrvb_ctx* c, GlmmLik lik, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                         const double* r_loc, int64_t Gp, int64_t K, const double* cov_beta, int64_t n0, int64_t n1, const double* x_new,
+                         const double* z_new, const int32_t* gid_new, const double* off_new, const double* tr_new, int64_t n_new,
+                         double* out) {
+    const i64 G = c->n_groups;
+    LRVB_TRY(glmms_check(c, lik, mean, var, P_in, e_loc, r_loc, Gp == G + 1 ? G : Gp, K, !cov_beta || !out));
+    for (i64 k = G * K; k < Gp * K; ++k) if (!(r_loc[k] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "r[%lld] is not positive", (long long)k);
+    if (!c->glmms_valid || !c->glmms_fac_valid || c->glmms_fac_K != K || c->glmms_gcov_rows == 0)
+        LRVB_FAIL(LRVB_ERR_STATE, "no group covariance of %lld effects resident: call lrvb_glmm_slopes_group_cov first", (long long)K);
+    if (Gp > c->glmms_gcov_rows) LRVB_FAIL(LRVB_ERR_SIZE, "e / r have %lld groups, the group covariance %lld", (long long)Gp, (long long)c->glmms_gcov_rows);
+    const bool fresh = x_new != nullptr;
+    i64 n;
+    std::vector<int32_t> gid_h;
+    if (fresh) {
+        if (!z_new || !gid_new || n_new < 0) LRVB_FAIL(LRVB_ERR_INVALID, "new rows need x, z, their groups and a count >= 0");
+        n = n_new;
+        gid_h.assign((size_t)(2 * ((n + 1) / 2)), 0);
+        for (i64 i = 0; i < n; ++i) {                      // on the host, before anything is launched: an index outside is an out-of-bounds read
+            if (gid_new[i] < 0 || gid_new[i] >= Gp)
+                LRVB_FAIL(LRVB_ERR_INVALID, "group %d of new row %lld outside [0, %lld)", (int)gid_new[i], (long long)i, (long long)Gp);
+            gid_h[(size_t)i] = gid_new[i];
+        }
+    } else {
+        if (n0 < 0 || n1 > c->N || n0 > n1) LRVB_FAIL(LRVB_ERR_INVALID, "row range [%lld, %lld) outside [0, %lld)", (long long)n0, (long long)n1, (long long)c->N);
+        n = n1 - n0;
+    }
+    if (n == 0) return LRVB_OK;
+    const i64 P = c->P, GK = Gp * K, nodes = lik.kind == GLMM_POISSON ? 0 : 256;
+    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(nodes + 2 * up(P) + 2 * up(GK) + P * P)));
+    LRVB_TRY(buf_reserve(c, c->cgT, (size_t)(up(5 * n) + (fresh ? up(n * P) + up(n * K) + 2 * up(n) + up((n + 1) / 2) : 0))));
+    double* g = c->work1.p; double* dm = g + nodes; double* dv = dm + up(P); double* de = dv + up(P); double* dr = de + up(GK);
+    double* Sbb = dr + up(GK);
+    double* od = c->cgT.p; double* xn = od + up(5 * n); double* zn = xn + up(n * P); double* on = zn + up(n * K); double* tn = on + up(n);
+    double* gn = tn + up(n);
+    LRVB_TRY(glmms_to_device(c, lik, g));
+    LRVB_TRY(h2d(c, dm, mean, (size_t)P));
+    LRVB_TRY(h2d(c, dv, var, (size_t)P));
+    LRVB_TRY(h2d(c, de, e_loc, (size_t)GK));
+    LRVB_TRY(h2d(c, dr, r_loc, (size_t)GK));
+    LRVB_TRY(h2d(c, Sbb, cov_beta, (size_t)(P * P)));
+    const double* X = c->X.p; const double* Z = c->gz.p;
+    const int* gid;
+    if (fresh) {
+        LRVB_TRY(h2d(c, xn, x_new, (size_t)(n * P)));
+        LRVB_TRY(h2d(c, zn, z_new, (size_t)(n * K)));
+        LRVB_TRY(h2d(c, gn, reinterpret_cast<const double*>(gid_h.data()), gid_h.size() / 2));
+        lik.off = nullptr; lik.trials = nullptr;
+        if (lik.kind != GLMM_LOGISTIC && off_new) { LRVB_TRY(h2d(c, on, off_new, (size_t)n)); lik.off = on; }
+        if (lik.kind == GLMM_BINOMIAL && tr_new) { LRVB_TRY(h2d(c, tn, tr_new, (size_t)n)); lik.trials = tn; }
+        X = xn; Z = zn; gid = reinterpret_cast<const int*>(gn); n0 = 0; n1 = n;
+    } else {
+        const i64 NW = (c->N + grouped_rows_per_wave(c->N) - 1) / grouped_rows_per_wave(c->N);
+        gid = reinterpret_cast<const int*>(reinterpret_cast<const i64*>(c->groups.p) + c->N + c->n_groups + 1 + NW);
+    }
+    LRVB_TRY(launch_glmm_slopes_predict_rows(c, lik, (int)K, X, Z, n0, n1, gid, dm, dv, de, dr, Sbb, c->glmms_gcov.p, od, n));
+    return d2h(c, out, od, (size_t)(5 * n));                  // per-observation rows: rank-local, no hook call
+}
+
+extern "C" int lrvb_glmm_slopes_predict(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                        const double* r_loc, int64_t Gp, int64_t K, const double* gh_x, const double* gh_w,
+                                        int32_t n_nodes, const double* cov_beta, int64_t n0, int64_t n1, const double* x_new,
+                                        const double* z_new, const int32_t* gid_new, int64_t n_new, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_predict(c, glmms_logistic(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, Gp, K, cov_beta, n0, n1, x_new, z_new,
+                         gid_new, nullptr, nullptr, n_new, out);
+}
+
+extern "C" int lrvb_glmm_poisson_predict(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                         const double* r_loc, int64_t Gp, int64_t K, const double* cov_beta, int64_t n0, int64_t n1,
+                                         const double* x_new, const double* z_new, const int32_t* gid_new, const double* offset_new,
+                                         int64_t n_new, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_predict(c, glmms_poisson(), mean, var, P_in, e_loc, r_loc, Gp, K, cov_beta, n0, n1, x_new, z_new, gid_new, offset_new,
+                         nullptr, n_new, out);
+}
+
+extern "C" int lrvb_glmm_binomial_predict(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                          const double* r_loc, int64_t Gp, int64_t K, const double* gh_x, const double* gh_w,
+                                          int32_t n_nodes, const double* cov_beta, int64_t n0, int64_t n1, const double* x_new,
+                                          const double* z_new, const int32_t* gid_new, const double* offset_new,
+                                          const double* trials_new, int64_t n_new, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_predict(c, glmms_binomial(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, Gp, K, cov_beta, n0, n1, x_new, z_new,
+                         gid_new, offset_new, trials_new, n_new, out);
 }
 
 // ---- logistic regression with a full-covariance Gaussian posterior q(beta) = N(m, Sigma) ----------------------------------

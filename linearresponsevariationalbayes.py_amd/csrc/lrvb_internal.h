@@ -136,7 +136,10 @@ struct lrvb_ctx {
     // what lrvb_glmm_slopes_schur leaves for lrvb_glmm_slopes_solve_forward / _back: [uploaded local blocks (up(K (2 K + 1) G)) |
     // U (2 K G x ld(R))] of glmms_fac_K effects, and T = L^-1 R_local (2 K G x glmms_T_Q; 0 = no forward pass yet)
     DevBuf glmms_fac, glmms_T; bool glmms_fac_valid = false; int glmms_fac_K = 0; i64 glmms_T_Q = 0;
-    void glmms_drop() { glmms_valid = false; glmms_fac_valid = false; glmms_T_Q = 0; }
+    // what lrvb_glmm_slopes_group_cov leaves for the lrvb_glmm_*_predict entries: glmms_gcov_rows (G + 1; 0 = none) rows of
+    // [Sigma_uu (K K) | Sigma_ubeta (K P)], the last one the pseudo-group of a population-level prediction.  It lives and dies with the factor
+    DevBuf glmms_gcov; i64 glmms_gcov_rows = 0;
+    void glmms_drop() { glmms_valid = false; glmms_fac_valid = false; glmms_T_Q = 0; glmms_gcov_rows = 0; }
     // lrvb_glmm_poisson_* (k_glmm_slopes.hip): the per-row offset (log exposure) of lrvb_set_offset, goff_n doubles (0 = none:
     // the offset is zero).  The Poisson entries leave their sums in `glmms` as lrvb_glmm_slopes_terms does; no other entry reads it
     DevBuf goff; i64 goff_n = 0;
@@ -276,6 +279,12 @@ int  launch_glmm_slopes_infl_gsum(lrvb_ctx* c, const GlmmLik& lik, int K, const 
                                   const double* eg, const double* rg, double* gsum /* G x (2 K + 2 P), zeroed by the caller */,
                                   double* part /* 2 (2 K + 2 P) doubles per tile of glmm_num_tiles */);
 int  launch_glmm_slopes_infl_local(lrvb_ctx* c, int K, i64 Q, const double* S, const double* Al, double* out /* G x Q, += */);
+int  launch_glmm_slopes_group_cov(lrvb_ctx* c, int K, const double* loc /* the blocks as uploaded */, const double* U, int ldu,
+                                  const double* W /* R x R */, const double* s /* R */, double* out /* (G + 1) x (K K + K P) */);
+int  launch_glmm_slopes_predict_rows(lrvb_ctx* c, const GlmmLik& lik, int K, const double* X /* the context's rows or new ones */,
+                                     const double* Z, i64 n0, i64 n1, const int* gid, const double* m, const double* vb,
+                                     const double* eg /* G' x K */, const double* rg, const double* Sbb /* P x P */,
+                                     const double* gcov /* G' x (K K + K P) */, double* out /* 5 x ldo */, i64 ldo);
 
 // k_lmm.hip
 struct LmmIdx { int p, ms, ls, iem, iim, iay, iby, iam, ibm; i64 ld; };    // vector-coordinate positions of the global parameters

@@ -72,6 +72,11 @@ class BinomialGLMMObjective(_SlopesArrow, _LogisticMixedModel):
     def _group_influence(self, *point_and_operand):
         return self.ctx.glmm_binomial_group_influence(*point_and_operand)
 
+    def _predict_entry(self, point, cov_beta, window, rows):
+        if window is not None:
+            return self.ctx.glmm_binomial_predict(*point, cov_beta, n0=window[0], n1=window[1])
+        return self.ctx.glmm_binomial_predict(*point, cov_beta, new=rows)
+
     def _row_psi_derivs(self, rho, s):
         """The logistic derivatives at rho + o, times m, by the rule the kernels use (Stein's identity on the nodes:
         psi_rho = E sigma(t), psi_s = E sigma'(t) / 2), so that the dense weight cross Hessian is the derivative of the same
@@ -103,6 +108,23 @@ class NegBinomialGLMMObjective(BinomialGLMMObjective):
         super().__init__(par, x, y, z, groups, n_groups, y + phi, o - np.log(phi), beta_prior_info, mu_prior, tau_prior, gh_deg, names,
                          weights, device)
         self._phi = phi
+        self._raw_offset = o
+
+    # ---- predictions: the NB mean exp(o + rho + s / 2) is the Poisson policy's, at the RAW offset (the binomial e1 is not the NB mean) ----
+    def _predict_offset(self):
+        return self._raw_offset
+
+    def _predict_rows_of(self, newdata, n0, n1):
+        x, z, gid, off, _ = super()._predict_rows_of(newdata, n0, n1)
+        return x, z, gid, off, None
+
+    def _predict_entry(self, point, cov_beta, window, rows):
+        """The rows go to the Poisson entry as new rows: the offset resident on the context is o - log phi."""
+        m, v, e, r = point[:4]
+        return self.ctx.glmm_poisson_predict(m, v, e, r, cov_beta, new=rows[:4])
+
+    def _response_mean(self, rho, s, trials):
+        return np.exp(rho + 0.5 * s)
 
     def log_norm_const(self):
         """C(y, phi) = sum_n w_n [log Gamma(y_n + phi_n) - log Gamma(phi_n) - log Gamma(y_n + 1)] at the current weights:

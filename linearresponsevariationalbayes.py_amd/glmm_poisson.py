@@ -52,6 +52,15 @@ class PoissonGLMMObjective(_SlopesArrow, _LogisticMixedModel):
     def _group_influence(self, m, v, e, r, gh_x, gh_w, A):
         return self.ctx.glmm_poisson_group_influence(m, v, e, r, A)
 
+    def _predict_entry(self, point, cov_beta, window, rows):
+        m, v, e, r = point[:4]
+        if window is not None:
+            return self.ctx.glmm_poisson_predict(m, v, e, r, cov_beta, n0=window[0], n1=window[1])
+        return self.ctx.glmm_poisson_predict(m, v, e, r, cov_beta, new=rows[:4])
+
+    def _response_mean(self, rho, s, trials):
+        return np.exp(rho + 0.5 * s)
+
     def _row_psi_derivs(self, rho, s):
         psi = np.exp(rho + (0.0 if self._offset is None else self._offset) + 0.5 * s)
         return psi, 0.5 * psi

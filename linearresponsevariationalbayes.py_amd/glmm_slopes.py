@@ -37,6 +37,7 @@ from scipy import special
 from . import _hip
 from .block_arrow import (block_arrow_to_free, block_arrow_matvec, block_arrow_dense, block_arrow_sparse,    # noqa: F401 (re-exported)
                           block_arrow_schur_term, block_arrow_local_solve, block_arrow_solve, block_arrow_solve_by_phases,
+                          block_arrow_group_cov, block_arrow_group_cov_by_phases, unpack_group_cov, predict_rows,
                           _to_groups, _from_groups, _local_index, _local_chol)
 from .models import DeviceContext, DeclaredHypers, refuse_double_reduction
 from .packing import HyperVectorParam, ResidentVector
@@ -231,6 +232,7 @@ class _LogisticMixedModel(DeclaredHypers):
         self._external = None
         self._point_key = None
         self._dev_factor_key = None                  # what the factors of solve(on_device=True) were built at
+        self._gcov = None                            # (that key, cov_beta) while the group covariance of `group_cov` is resident
         self._push_state()                           # the initial weights on the device: direct calls on `ctx` see them from the start
 
     tau_beta = property(lambda self: float(self._hyper_vec('beta_prior_info')[0]))
@@ -658,6 +660,7 @@ class _SlopesArrow:
             self.global_hessian(fv, want_host=False)
             self._ensure_gctx().chol_factor_last()
             self._dev_factor_key = key
+            self._gcov = None                        # the group covariance went with the old factor
         eta = self._eta(fv, True)
         dv = np.concatenate([np.ones(self.P), -1.0 / eta[self.P:2 * self.P] ** 2, np.ones(3 * self.K)])
         return self._jac(eta)[0][coupled_rows(self.P, self.K)] * dv
@@ -670,6 +673,118 @@ class _SlopesArrow:
         return block_arrow_solve_by_phases(R, self.n_global, coupled_rows(self.P, self.K), s, self.ctx.glmm_slopes_solve_forward,
                                            self._ensure_gctx().chol_solve,
                                            lambda xc: self.ctx.glmm_slopes_solve_back(xc, self.G, self.K))
+
+
+    # ---- group blocks of H^-1, fitted values and predictions --------------------------------------------
+    def _group_cov(self, x, is_free, on_device):
+        """(cov_beta, cov_u (G + 1) x K x K, cov_beta_u (G + 1) x P x K), the pseudo-group of a population-level row last.  With
+        on_device the buffer stays resident on `ctx` for the predict entry and only cov_beta is kept here."""
+        if not is_free:
+            raise ValueError('the linear-response covariance of the means is taken in free coordinates')
+        P, K, G = self.P, self.K, self.G
+        if not on_device:
+            _, Hgg, rows, Hx, loc = self._arrow(x, True)
+            return block_arrow_group_cov(Hgg, rows, Hx, loc, P, K, population=True)
+        s = self._device_factors(x, True)
+        key = self._dev_factor_key
+        if self._gcov is not None and self._gcov[0] == key:
+            return self._gcov[1], None, None
+        self._gcov = None
+        cov_beta, buf = block_arrow_group_cov_by_phases(self.n_global, coupled_rows(P, K), P, K, s, self._ensure_gctx().chol_solve,
+                                                        lambda W, sc: self.ctx.glmm_slopes_group_cov(W, sc, G, K))
+        self._gcov = (key, cov_beta)
+        return (cov_beta,) + unpack_group_cov(buf, P, K)
+
+    @_hip.host_blas
+    def group_cov(self, x, is_free=True, on_device=False):
+        """(cov_beta P x P, cov_u G x K x K, cov_beta_u G x P x K): the linear-response covariance of the means of beta, of every
+        group's effects, and between the two -- the blocks of H^-1 in free coordinates, in which E beta = m and E u_gk = e_gk
+        are coordinates themselves (lme4's `condVar` is cov_u).  Host route: `block_arrow_group_cov`.  on_device=True: one more
+        pass over the factor `solve(on_device=True)` leaves resident (lrvb_glmm_slopes_group_cov); a factor already at this
+        point is reused, but the blocks themselves are formed again on every call (the `chol_solve` of R columns, the upload, the
+        kernel and the copy of G + 1 rows: the host copy is not kept; `predict` does keep the resident buffer of a cached point);
+        vector coordinates and installed statistics are refused, as there."""
+        if on_device and self._gcov is not None:
+            self._gcov = None                        # the caller asks for the blocks themselves: form them again
+        cb, cu, cbu = self._group_cov(x, is_free, on_device)
+        return cb, cu[:self.G], cbu[:self.G]
+
+    def ranef_se(self, x, is_free=True, on_device=False):
+        """(linear-response, mean-field) standard errors of the group effects, G x K each: sqrt diag Sigma_uu next to 1 / sqrt i."""
+        cu = self.group_cov(x, is_free, on_device)[1]
+        eta = self._eta(x, is_free)
+        ig = _split_eta(eta, self.P, self.K, self.G)[7]
+        return np.sqrt(np.diagonal(cu, axis1=1, axis2=2)), 1.0 / np.sqrt(ig)
+
+    def _predict_rows_of(self, newdata, n0, n1):
+        """(x, z, groups with -1 -> G, offset, trials) of the rows to predict; newdata=None: the window of the model's own rows."""
+        G, N = self.G, self.n_obs
+        if newdata is None:
+            n0 = int(n0)
+            n1 = N if n1 is None else int(n1)
+            if n0 < 0 or n1 > N or n0 > n1:
+                raise ValueError('row range [{}, {}) outside [0, {})'.format(n0, n1, N))
+            sl = slice(n0, n1)
+            off, tr = self._predict_offset(), getattr(self, '_trials', None)
+            return self._x[sl], self._z[sl], self._groups[sl], None if off is None else off[sl], None if tr is None else tr[sl]
+        unknown = set(newdata) - {'x', 'z', 'groups', 'offset', 'trials'}
+        if unknown:
+            raise ValueError('newdata has the keys x, z, groups, offset, trials (got {})'.format(sorted(unknown)))
+        x = _hip.as_f64(newdata['x'])
+        n = x.shape[0]
+        z = np.ones((n, 1)) if newdata.get('z') is None else _hip.as_f64(newdata['z'])
+        gid = np.asarray(newdata['groups']).ravel()
+        if x.ndim != 2 or x.shape[1] != self.P or z.shape != (n, self.K) or gid.size != n:
+            raise ValueError('newdata: x must be n x {}, z n x {} and groups of length n'.format(self.P, self.K))
+        if np.any(gid != np.round(gid)) or np.any(gid < -1) or np.any(gid >= G):
+            raise ValueError('newdata: groups must lie in [0, {}) or be -1 (population level)'.format(G))
+        gid = np.where(gid < 0, G, gid).astype(np.int32)
+        extra = []
+        for name in ('offset', 'trials'):
+            a = newdata.get(name)
+            if a is not None:
+                a = _hip.as_f64(a).ravel()
+                if a.size != n or not np.all(np.isfinite(a)):
+                    raise ValueError('newdata: {} must hold {} finite values'.format(name, n))
+            extra.append(a)
+        return x, z, gid, extra[0], extra[1]
+
+    def _predict_offset(self):
+        return getattr(self, '_offset', None)
+
+    @_hip.host_blas
+    def predict(self, x, newdata=None, n0=0, n1=None, is_free=True, on_device=False):
+        """Fitted values (newdata=None: rows n0..n1 of the model's data) or predictions for new rows
+        `newdata = dict(x=, z=, groups=, offset=, trials=)`, as a dict of five arrays of one value per row:
+
+            rho        o + x . m + z . e_g             the linear predictor at the variational means
+            var_mf     (x o x) . v + (z o z) . r_g     its mean-field variance
+            var_lrvb   c^T H^-1 c, c = (x at m, z at e_g): its linear-response variance (the N x D matrix of the c is never formed)
+            mean_mf, mean_lrvb   the response-scale mean E g(t), t ~ N(rho, var), under either variance
+
+        groups may hold -1: the row is predicted at the population level, as if its effect u equalled mu (e_mu, 1 / i_mu and
+        the blocks of mu in H^-1 stand in for the group's); any other value outside [0, G) is a ValueError.  This is not the
+        predictive distribution of a new group, which would add 1 / tau.  on_device=True: the group blocks stay on the device
+        (`group_cov`) and the rows are streamed there (lrvb_glmm_slopes_predict and its siblings); free coordinates only."""
+        rows = self._predict_rows_of(newdata, n0, n1)
+        cb, cu, cbu = self._group_cov(x, is_free, on_device)
+        eta = self._eta(x, True)
+        P, K, G = self.P, self.K, self.G
+        m, ib, e_mu, i_mu, _, _, e, ig = _split_eta(eta, P, K, G)
+        v, e2, r2 = 1.0 / ib, np.vstack([e, e_mu[None, :]]), np.vstack([1.0 / ig, 1.0 / i_mu[None, :]])
+        if on_device:
+            out = self._predict_entry((m, v, e2, r2, self.gh_x, self.gh_w), cb, None if newdata is not None else (int(n0), n1), rows)
+        else:
+            rho, s_mf, v_lr = predict_rows(rows[0], rows[1], rows[2], rows[3], m, v, e2, r2, cb, cu, cbu)
+            out = rho, s_mf, v_lr, self._response_mean(rho, s_mf, rows[4]), self._response_mean(rho, v_lr, rows[4])
+        return dict(zip(('rho', 'var_mf', 'var_lrvb', 'mean_mf', 'mean_lrvb'), out))
+
+    def _response_mean(self, rho, s, trials):
+        """E sigma(t), t ~ N(rho, s), by the Gauss-Hermite rule of the kernels; times the trials where the model has them."""
+        from scipy.special import expit
+        t = rho[:, None] + np.sqrt(np.maximum(s, 0.0))[:, None] * (np.sqrt(2.0) * self.gh_x)[None, :]
+        p = (expit(t) * (self.gh_w / np.sqrt(np.pi))[None, :]).sum(1)
+        return p if trials is None else trials * p
 
 
 class LogisticGLMMSlopesObjective(_SlopesArrow, _LogisticMixedModel):
@@ -689,3 +804,8 @@ class LogisticGLMMSlopesObjective(_SlopesArrow, _LogisticMixedModel):
 
     def _group_influence(self, *point_and_operand):
         return self.ctx.glmm_slopes_group_influence(*point_and_operand)
+
+    def _predict_entry(self, point, cov_beta, window, rows):
+        if window is not None:
+            return self.ctx.glmm_slopes_predict(*point, cov_beta, n0=window[0], n1=window[1])
+        return self.ctx.glmm_slopes_predict(*point, cov_beta, new=rows[:3])

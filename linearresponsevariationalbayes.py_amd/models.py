@@ -441,6 +441,67 @@ class DeviceContext(object):
         self._check(self._lib.lrvb_glmm_slopes_solve_back(self._h, _hip.ptr(xc), G, K, xc.shape[1], _hip.ptr(X)))
         return X
 
+    def glmm_slopes_group_cov(self, W, s, G, K, want_host=True):
+        """The group blocks of H^-1 from the factor the last `glmm_slopes_schur` left resident (lrvb_glmm_slopes_group_cov):
+        W = (S^-1)[coupled rows, coupled rows] (R x R), s the scaling of the coupled rows.  Returns the (G + 1) x (K K + K P)
+        buffer [Sigma_uu | Sigma_ubeta], row G the pseudo-group of a population-level prediction (None with want_host=False);
+        it stays resident for the predict entries."""
+        W, s = _hip.as_f64(W), _hip.as_f64(s).ravel()
+        R = 2 * self.n_cols + 3 * K
+        if W.shape != (R, R) or s.size != R:
+            raise ValueError('expected W {0} x {0} and s of length {0}'.format(R))
+        out = np.empty((G + 1, K * K + K * self.n_cols)) if want_host else None
+        self._check(self._lib.lrvb_glmm_slopes_group_cov(self._h, _hip.ptr(W), _hip.ptr(s), self.n_cols, G, K, _hip.ptr(out)))
+        return out
+
+    def _glmm_predict(self, fn, nodes, n_extra, mean, var, e, r, gh_x, gh_w, cov_beta, n0, n1, new):
+        """The five columns (5 x n: rho, var_mf, var_lrvb, mean_mf, mean_lrvb) of a predict entry.  new: None for the window
+        [n0, n1) of the context's rows, or (x, z, groups, offset, trials) of new rows, of which the entry takes the first
+        3 + n_extra (offset and trials may be None)."""
+        m, v = _hip.as_f64(mean).ravel(), _hip.as_f64(var).ravel()
+        e, r = _hip.as_f64(e), _hip.as_f64(r)
+        gx, gw = _hip.as_f64(gh_x).ravel(), _hip.as_f64(gh_w).ravel()
+        P = self.n_cols
+        Sbb = _hip.as_f64(cov_beta)
+        if e.ndim != 2 or r.shape != e.shape or m.size != P or v.size != P or gx.size != gw.size or Sbb.shape != (P, P):
+            raise ValueError('expected mean and var of length {0}, e and r of one shape G x K and cov_beta {0} x {0}'.format(P))
+        Gp, K = e.shape
+        args = [self._h, _hip.ptr(m), _hip.ptr(v), P, _hip.ptr(e), _hip.ptr(r), Gp, K]
+        args += [_hip.ptr(gx), _hip.ptr(gw), gx.size] if nodes else []
+        if new is None:
+            n0 = int(n0)
+            n1 = self.n_obs if n1 is None else int(n1)
+            n = max(n1 - n0, 0)
+            rows, keep = [None, None, None] + [None] * n_extra + [0], ()
+        else:
+            x, z = _hip.as_f64(new[0]), _hip.as_f64(new[1])
+            gid = np.ascontiguousarray(np.asarray(new[2]).ravel(), dtype=np.int32)
+            n = gid.size
+            if x.shape != (n, P) or z.shape != (n, K):
+                raise ValueError('new rows: x must be n x {}, z n x {} and groups of length n'.format(P, K))
+            extra = [None if a is None else _hip.as_f64(a).ravel() for a in new[3:3 + n_extra]]
+            if any(a is not None and a.size != n for a in extra):
+                raise ValueError('new rows: offset and trials hold one value per row')
+            n0, n1 = 0, 0
+            keep = (x, z, gid, extra)
+            rows = [_hip.ptr(x), _hip.ptr(z), gid.ctypes.data] + [_hip.ptr(a) for a in extra] + [n]
+        out = np.empty((5, n))
+        self._check(fn(*args, _hip.ptr(Sbb), n0, n1, *rows, _hip.ptr(out)))
+        del keep
+        return out
+
+    def glmm_slopes_predict(self, mean, var, e, r, gh_x, gh_w, cov_beta, n0=0, n1=None, new=None):
+        """Fitted values of the logistic mixed model with K effects per group (lrvb_glmm_slopes_predict); see `_glmm_predict`."""
+        return self._glmm_predict(self._lib.lrvb_glmm_slopes_predict, True, 0, mean, var, e, r, gh_x, gh_w, cov_beta, n0, n1, new)
+
+    def glmm_poisson_predict(self, mean, var, e, r, cov_beta, n0=0, n1=None, new=None):
+        """Fitted rates of the Poisson mixed model (lrvb_glmm_poisson_predict); new rows carry an offset."""
+        return self._glmm_predict(self._lib.lrvb_glmm_poisson_predict, False, 1, mean, var, e, r, (), (), cov_beta, n0, n1, new)
+
+    def glmm_binomial_predict(self, mean, var, e, r, gh_x, gh_w, cov_beta, n0=0, n1=None, new=None):
+        """Fitted counts of the binomial mixed model (lrvb_glmm_binomial_predict); new rows carry an offset and trials."""
+        return self._glmm_predict(self._lib.lrvb_glmm_binomial_predict, True, 2, mean, var, e, r, gh_x, gh_w, cov_beta, n0, n1, new)
+
     def _glmm_influence_args(self, mean, var, e, r, gh_x, gh_w, A):
         """The point (e, r: G x K) and the operand A (Q x (2 P + 2 G K), columns [A_m | A_v | A_e (G K, group-major) | A_r (G K)])
         in the layout of the C entries: A_global (Q x 2 P) and A_local (G x 2 K x Q), by `glmm_slopes.split_influence_operand`.

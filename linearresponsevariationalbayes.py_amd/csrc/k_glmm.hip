@@ -137,9 +137,7 @@ int launch_glmm_rows(lrvb_ctx* c, const double* m, const double* vb, const doubl
     if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "logistic mixed model: P <= 64");
     const int ncol = 5 + 4 * (int)c->P;
     const i64* gdev = reinterpret_cast<const i64*>(c->groups.p);
-    const i64 n_tiles = glmm_num_tiles(N);
-    const unsigned grid = (unsigned)(n_tiles < 2048 ? (n_tiles < 1 ? 1 : n_tiles) : 2048);
-    hipLaunchKernelGGL(glmm_rows_kernel, dim3(grid), dim3(256), 0, c->stream, N, (int)c->P, G, (const double*)c->X.p,
+    hipLaunchKernelGGL(glmm_rows_kernel, dim3(glmm_grid(N)), dim3(256), 0, c->stream, N, (int)c->P, G, (const double*)c->X.p,
                        (const double*)c->y.p, (const double*)c->w.p, gdev, gdev + N, m, vb, eg, rg, gx, gw, K, coef, NP, gsum, part, vpart);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(glmm_fixup_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, G, ncol, gdev + N, (const double*)part, gsum);
@@ -269,9 +267,7 @@ int launch_glmm_infl_rows(lrvb_ctx* c, i64 n0, i64 n1, const int* gid, const dou
     if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "logistic mixed model: P <= 64");
     const i64 R = n1 - n0;
     if (R <= 0) return LRVB_OK;
-    const i64 n_tiles = (R + GLMM_T - 1) / GLMM_T;
-    const unsigned grid = (unsigned)(n_tiles < 2048 ? n_tiles : 2048);
-    hipLaunchKernelGGL(glmm_infl_rows_kernel, dim3(grid), dim3(256), 0, c->stream, n0, R, (int)c->P, (const double*)c->X.p,
+    hipLaunchKernelGGL(glmm_infl_rows_kernel, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, (const double*)c->X.p,
                        (const double*)c->y.p, gid, m, vb, eg, rg, gx, gw, K, Ag, Al, (int)Q, out);
     HIP_TRY(hipGetLastError());
     return LRVB_OK;
@@ -338,9 +334,7 @@ int launch_glmm_infl_gsum(lrvb_ctx* c, const double* m, const double* vb, const 
     if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "logistic mixed model: P <= 64");
     const int ncol = 2 + 2 * (int)c->P;
     const i64* gdev = reinterpret_cast<const i64*>(c->groups.p);
-    const i64 n_tiles = glmm_num_tiles(N);
-    const unsigned grid = (unsigned)(n_tiles < 2048 ? (n_tiles < 1 ? 1 : n_tiles) : 2048);
-    hipLaunchKernelGGL(glmm_infl_gsum_kernel, dim3(grid), dim3(256), 0, c->stream, N, (int)c->P, G, (const double*)c->X.p,
+    hipLaunchKernelGGL(glmm_infl_gsum_kernel, dim3(glmm_grid(N)), dim3(256), 0, c->stream, N, (int)c->P, G, (const double*)c->X.p,
                        (const double*)c->y.p, (const double*)c->w.p, gdev, gdev + N, m, vb, eg, rg, gx, gw, K, gsum, part);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(glmm_fixup_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, G, ncol, gdev + N, (const double*)part, gsum);

@@ -41,6 +41,7 @@
 //      of group: a group inside one tile goes to its row of the result, the piece of a group cut by a tile boundary to one of
 //      the tile's two partial rows, which glmm_fixup_kernel (k_glmm.hip) adds in tile order.
 // No atomics anywhere: the result is a fixed-order sum, bitwise reproducible.  Empty groups keep the zeros the caller wrote.
+// The launchers dispatch over K with gs_with_K and over the likelihood with gs_with_lik.
 // The Poisson policy does not clamp: where o + rho + s / 2 overflows the exponent, psi = inf reaches the sums and the entry refuses
 // the non-finite value (LRVB_ERR_INVALID).
 #include "k_glmm_walk.h"
@@ -178,6 +179,29 @@ void glmm_slopes_rows_kernel(i64 N, int P, int Kz, i64 G, const double* __restri
     }
 }
 
+// The runtime Kz in 1..4 as a compile-time constant: f(std::integral_constant<int, Kz>); any other value is refused with `text`.
+template <class F>
+static int gs_with_K(int Kz, const char* text, F&& f) {
+    switch (Kz) {
+    case 1: f(std::integral_constant<int, 1>()); break;
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 3: f(std::integral_constant<int, 3>()); break;
+    case 4: f(std::integral_constant<int, 4>()); break;
+    default: LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "%s", text);
+    }
+    HIP_TRY(hipGetLastError());
+    return LRVB_OK;
+}
+
+// The likelihood of a GlmmLik as its policy: f(Lik(), la) with la the Lik::Args the kernels of that policy are handed.
+template <class F>
+static int gs_with_lik(const GlmmLik& lik, F&& f) {
+    const LogisticLik::Args q{lik.gx, lik.gw, lik.n_nodes};
+    if (lik.kind == GLMM_POISSON) return f(PoissonLik(), PoissonLik::Args(lik.off));
+    if (lik.kind == GLMM_BINOMIAL) return f(BinomialLik(), BinomialLik::Args{q, lik.off, lik.trials});
+    return f(LogisticLik(), q);
+}
+
 template <class Lik>
 static int gs_launch_rows(lrvb_ctx* c, int Kz, const double* Z, typename Lik::Args la, const double* m, const double* vb, const double* eg,
                           const double* rg, double* coef, i64 NP, double* gsum, double* part, double* vpart) {
@@ -185,9 +209,7 @@ static int gs_launch_rows(lrvb_ctx* c, int Kz, const double* Z, typename Lik::Ar
     if (c->P > 64 || Kz < 1 || Kz > 4 || !Lik::args_ok(la)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "%s", Lik::LIMITS);
     const int ncol = glmm_slopes_ncol((int)c->P, Kz);
     const i64* gdev = reinterpret_cast<const i64*>(c->groups.p);
-    const i64 n_tiles = glmm_num_tiles(N);
-    const unsigned grid = (unsigned)(n_tiles < 2048 ? (n_tiles < 1 ? 1 : n_tiles) : 2048);
-    hipLaunchKernelGGL(glmm_slopes_rows_kernel<Lik>, dim3(grid), dim3(256), 0, c->stream, N, (int)c->P, Kz, G, (const double*)c->X.p, Z,
+    hipLaunchKernelGGL(glmm_slopes_rows_kernel<Lik>, dim3(glmm_grid(N)), dim3(256), 0, c->stream, N, (int)c->P, Kz, G, (const double*)c->X.p, Z,
                        (const double*)c->y.p, (const double*)c->w.p, gdev, gdev + N, m, vb, eg, rg, la, coef, NP, gsum, part, vpart);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(glmm_fixup_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, G, ncol, gdev + N, (const double*)part, gsum);
@@ -204,11 +226,7 @@ static int gs_unit_design(const GlmmLik& lik, int Kz) {
 int launch_glmm_slopes_rows(lrvb_ctx* c, const GlmmLik& lik, int Kz, const double* Z, const double* m, const double* vb, const double* eg,
                             const double* rg, double* coef, i64 NP, double* gsum, double* part, double* vpart) {
     if (!Z) { LRVB_TRY(gs_unit_design(lik, Kz)); return launch_glmm_rows(c, m, vb, eg, rg, lik.gx, lik.gw, lik.n_nodes, coef, NP, gsum, part, vpart); }
-    if (lik.kind == GLMM_POISSON) return gs_launch_rows<PoissonLik>(c, Kz, Z, lik.off, m, vb, eg, rg, coef, NP, gsum, part, vpart);
-    if (lik.kind == GLMM_BINOMIAL)
-        return gs_launch_rows<BinomialLik>(c, Kz, Z, {{lik.gx, lik.gw, lik.n_nodes}, lik.off, lik.trials}, m, vb, eg, rg, coef, NP, gsum, part,
-                                           vpart);
-    return gs_launch_rows<LogisticLik>(c, Kz, Z, {lik.gx, lik.gw, lik.n_nodes}, m, vb, eg, rg, coef, NP, gsum, part, vpart);
+    return gs_with_lik(lik, [&](auto L, auto la) { return gs_launch_rows<decltype(L)>(c, Kz, Z, la, m, vb, eg, rg, coef, NP, gsum, part, vpart); });
 }
 int glmm_slopes_ncol(int P, int Kz) { return 2 * Kz + Kz * (2 * Kz + 1) + 4 * Kz * P; }
 
@@ -297,15 +315,9 @@ int launch_glmm_slopes_schur_rows(lrvb_ctx* c, int Kz, const double* gsum, const
     const i64 G = c->n_groups;
     const dim3 grid((unsigned)G), block(256);
     const int P = (int)c->P;
-    switch (Kz) {
-    case 1: hipLaunchKernelGGL(glmm_slopes_schur_rows_kernel<1>, grid, block, 0, c->stream, G, P, gsum, loc, scale, closed, U, ldu, bad); break;
-    case 2: hipLaunchKernelGGL(glmm_slopes_schur_rows_kernel<2>, grid, block, 0, c->stream, G, P, gsum, loc, scale, closed, U, ldu, bad); break;
-    case 3: hipLaunchKernelGGL(glmm_slopes_schur_rows_kernel<3>, grid, block, 0, c->stream, G, P, gsum, loc, scale, closed, U, ldu, bad); break;
-    case 4: hipLaunchKernelGGL(glmm_slopes_schur_rows_kernel<4>, grid, block, 0, c->stream, G, P, gsum, loc, scale, closed, U, ldu, bad); break;
-    default: LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "logistic mixed model with slopes: 1 <= K <= 4");
-    }
-    HIP_TRY(hipGetLastError());
-    return LRVB_OK;
+    return gs_with_K(Kz, "logistic mixed model with slopes: 1 <= K <= 4", [&](auto k) {
+        hipLaunchKernelGGL(glmm_slopes_schur_rows_kernel<decltype(k)::value>, grid, block, 0, c->stream, G, P, gsum, loc, scale, closed, U, ldu, bad);
+    });
 }
 
 // ---- the two substitution passes of the device-resident block-arrow solve ---------------------------------
@@ -371,19 +383,11 @@ void glmm_slopes_solve_back_kernel(i64 G, i64 Q, const double* __restrict__ loc,
 int launch_glmm_slopes_solve(lrvb_ctx* c, int Kz, bool back, i64 Q, const double* loc, double* T, double* W) {
     const i64 G = c->n_groups;
     const dim3 grid((unsigned)G), block(Q <= 64 ? 64 : (Q <= 128 ? 128 : 256));
-#define GS_SOLVE(KK) do {                                                                                                        \
-        if (back) hipLaunchKernelGGL(glmm_slopes_solve_back_kernel<KK>, grid, block, 0, c->stream, G, Q, loc, (const double*)T, W); \
-        else hipLaunchKernelGGL(glmm_slopes_solve_forward_kernel<KK>, grid, block, 0, c->stream, G, Q, loc, T); } while (0)
-    switch (Kz) {
-    case 1: GS_SOLVE(1); break;
-    case 2: GS_SOLVE(2); break;
-    case 3: GS_SOLVE(3); break;
-    case 4: GS_SOLVE(4); break;
-    default: LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "logistic mixed model with slopes: 1 <= K <= 4");
-    }
-#undef GS_SOLVE
-    HIP_TRY(hipGetLastError());
-    return LRVB_OK;
+    return gs_with_K(Kz, "logistic mixed model with slopes: 1 <= K <= 4", [&](auto k) {
+        constexpr int KK = decltype(k)::value;
+        if (back) hipLaunchKernelGGL(glmm_slopes_solve_back_kernel<KK>, grid, block, 0, c->stream, G, Q, loc, (const double*)T, W);
+        else hipLaunchKernelGGL(glmm_slopes_solve_forward_kernel<KK>, grid, block, 0, c->stream, G, Q, loc, T);
+    });
 }
 
 // ---- streamed weight influence (lrvb_glmm_slopes_obs_influence / lrvb_glmm_poisson_obs_influence) ---------
@@ -578,17 +582,15 @@ static int gs_launch_infl_rows(lrvb_ctx* c, int Kz, const double* Z, typename Li
     if (c->P > 64 || Kz < 1 || Kz > 4 || !Lik::args_ok(la)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "%s", Lik::LIMITS);
     const i64 R = n1 - n0;
     if (R <= 0) return LRVB_OK;
-    const i64 n_tiles = (R + GLMM_T - 1) / GLMM_T;
-    const unsigned grid = (unsigned)(n_tiles < 2048 ? n_tiles : 2048);
     if constexpr (std::is_same<Lik, PoissonLik>::value)
-        hipLaunchKernelGGL(glmm_poisson_infl_rows_kernel, dim3(grid), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
+        hipLaunchKernelGGL(glmm_poisson_infl_rows_kernel, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
                            (const double*)la, (const double*)c->y.p, gid, m, vb, eg, rg, Ag, Al, (int)Q, out);
     else if constexpr (std::is_same<Lik, BinomialLik>::value)
-        hipLaunchKernelGGL(glmm_binomial_infl_rows_kernel, dim3(grid), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
+        hipLaunchKernelGGL(glmm_binomial_infl_rows_kernel, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
                            (const double*)la.off, (const double*)la.trials, (const double*)c->y.p, gid, m, vb, eg, rg, la.q.gx, la.q.gw,
                            la.q.nq, Ag, Al, (int)Q, out);
     else
-        hipLaunchKernelGGL(glmm_slopes_infl_rows_kernel, dim3(grid), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
+        hipLaunchKernelGGL(glmm_slopes_infl_rows_kernel, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
                            (const double*)c->y.p, gid, m, vb, eg, rg, la.gx, la.gw, la.nq, Ag, Al, (int)Q, out);
     HIP_TRY(hipGetLastError());
     return LRVB_OK;
@@ -598,11 +600,7 @@ int launch_glmm_slopes_infl_rows(lrvb_ctx* c, const GlmmLik& lik, int Kz, const 
                                  const double* vb, const double* eg, const double* rg, const double* Ag, const double* Al, i64 Q,
                                  double* out) {
     if (!Z) { LRVB_TRY(gs_unit_design(lik, Kz)); return launch_glmm_infl_rows(c, n0, n1, gid, m, vb, eg, rg, lik.gx, lik.gw, lik.n_nodes, Ag, Al, Q, out); }
-    if (lik.kind == GLMM_POISSON) return gs_launch_infl_rows<PoissonLik>(c, Kz, Z, lik.off, n0, n1, gid, m, vb, eg, rg, Ag, Al, Q, out);
-    if (lik.kind == GLMM_BINOMIAL)
-        return gs_launch_infl_rows<BinomialLik>(c, Kz, Z, {{lik.gx, lik.gw, lik.n_nodes}, lik.off, lik.trials}, n0, n1, gid, m, vb, eg, rg, Ag,
-                                                Al, Q, out);
-    return gs_launch_infl_rows<LogisticLik>(c, Kz, Z, {lik.gx, lik.gw, lik.n_nodes}, n0, n1, gid, m, vb, eg, rg, Ag, Al, Q, out);
+    return gs_with_lik(lik, [&](auto L, auto la) { return gs_launch_infl_rows<decltype(L)>(c, Kz, Z, la, n0, n1, gid, m, vb, eg, rg, Ag, Al, Q, out); });
 }
 
 // ---- group blocks of H^-1 and fitted values with their linear-response variance ---------------------------
@@ -710,15 +708,9 @@ int launch_glmm_slopes_group_cov(lrvb_ctx* c, int Kz, const double* loc, const d
     const dim3 grid((unsigned)(G + 1)), block(256);
     const int P = (int)c->P;
     if (P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "mixed model with slopes: P <= 64");
-    switch (Kz) {
-    case 1: hipLaunchKernelGGL(glmm_slopes_group_cov_kernel<1>, grid, block, 0, c->stream, G, P, loc, U, ldu, W, s, out); break;
-    case 2: hipLaunchKernelGGL(glmm_slopes_group_cov_kernel<2>, grid, block, 0, c->stream, G, P, loc, U, ldu, W, s, out); break;
-    case 3: hipLaunchKernelGGL(glmm_slopes_group_cov_kernel<3>, grid, block, 0, c->stream, G, P, loc, U, ldu, W, s, out); break;
-    case 4: hipLaunchKernelGGL(glmm_slopes_group_cov_kernel<4>, grid, block, 0, c->stream, G, P, loc, U, ldu, W, s, out); break;
-    default: LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "mixed model with slopes: 1 <= K <= 4");
-    }
-    HIP_TRY(hipGetLastError());
-    return LRVB_OK;
+    return gs_with_K(Kz, "mixed model with slopes: 1 <= K <= 4", [&](auto k) {
+        hipLaunchKernelGGL(glmm_slopes_group_cov_kernel<decltype(k)::value>, grid, block, 0, c->stream, G, P, loc, U, ldu, W, s, out);
+    });
 }
 
 // gsp_predict_rows: the streaming sibling of gsi_infl_rows -- the same tile of 64 rows in their original order, the same staging
@@ -892,8 +884,7 @@ int launch_glmm_slopes_predict_rows(lrvb_ctx* c, const GlmmLik& lik, int Kz, con
     if (lik.kind != GLMM_POISSON && (lik.n_nodes < 1 || lik.n_nodes > 128)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 128 quadrature nodes");
     const i64 R = n1 - n0;
     if (R <= 0) return LRVB_OK;
-    const i64 n_tiles = (R + GLMM_T - 1) / GLMM_T;
-    const dim3 grid((unsigned)(n_tiles < 2048 ? n_tiles : 2048)), block(256);
+    const dim3 grid(glmm_grid(R)), block(256);
     const int P = (int)c->P;
     if (lik.kind == GLMM_POISSON)
         hipLaunchKernelGGL(glmm_poisson_predict_rows_kernel, grid, block, 0, c->stream, n0, R, P, Kz, X, Z, lik.off, gid, m, vb, eg, rg, Sbb,
@@ -991,9 +982,7 @@ static int gs_launch_infl_gsum(lrvb_ctx* c, int Kz, const double* Z, typename Li
     if (c->P > 64 || Kz < 1 || Kz > 4 || !Lik::args_ok(la)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "%s", Lik::LIMITS);
     const int ncol = 2 * Kz + 2 * (int)c->P;
     const i64* gdev = reinterpret_cast<const i64*>(c->groups.p);
-    const i64 n_tiles = glmm_num_tiles(N);
-    const unsigned grid = (unsigned)(n_tiles < 2048 ? (n_tiles < 1 ? 1 : n_tiles) : 2048);
-    hipLaunchKernelGGL(glmm_slopes_infl_gsum_kernel<Lik>, dim3(grid), dim3(256), 0, c->stream, N, (int)c->P, Kz, G, (const double*)c->X.p, Z,
+    hipLaunchKernelGGL(glmm_slopes_infl_gsum_kernel<Lik>, dim3(glmm_grid(N)), dim3(256), 0, c->stream, N, (int)c->P, Kz, G, (const double*)c->X.p, Z,
                        (const double*)c->y.p, (const double*)c->w.p, gdev, gdev + N, m, vb, eg, rg, la, gsum, part);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(glmm_fixup_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, G, ncol, gdev + N, (const double*)part, gsum);
@@ -1004,10 +993,7 @@ static int gs_launch_infl_gsum(lrvb_ctx* c, int Kz, const double* Z, typename Li
 int launch_glmm_slopes_infl_gsum(lrvb_ctx* c, const GlmmLik& lik, int Kz, const double* Z, const double* m, const double* vb,
                                  const double* eg, const double* rg, double* gsum, double* part) {
     if (!Z) { LRVB_TRY(gs_unit_design(lik, Kz)); return launch_glmm_infl_gsum(c, m, vb, eg, rg, lik.gx, lik.gw, lik.n_nodes, gsum, part); }
-    if (lik.kind == GLMM_POISSON) return gs_launch_infl_gsum<PoissonLik>(c, Kz, Z, lik.off, m, vb, eg, rg, gsum, part);
-    if (lik.kind == GLMM_BINOMIAL)
-        return gs_launch_infl_gsum<BinomialLik>(c, Kz, Z, {{lik.gx, lik.gw, lik.n_nodes}, lik.off, lik.trials}, m, vb, eg, rg, gsum, part);
-    return gs_launch_infl_gsum<LogisticLik>(c, Kz, Z, {lik.gx, lik.gw, lik.n_nodes}, m, vb, eg, rg, gsum, part);
+    return gs_with_lik(lik, [&](auto L, auto la) { return gs_launch_infl_gsum<decltype(L)>(c, Kz, Z, la, m, vb, eg, rg, gsum, part); });
 }
 
 int launch_glmm_slopes_infl_local(lrvb_ctx* c, int Kz, i64 Q, const double* S, const double* Al, double* out) {

@@ -1,7 +1,8 @@
-// k_glmm_walk.h -- what every mixed-model kernel that walks the rows shares (DESIGN.md sections 27 and 31): the tile size, the
-// likelihood policies, the head of a tile of group-sorted rows and the destination of a flushed segment.  Included by k_glmm.hip
-// (the random intercept: its own three kernels over the rows, on LogisticLik) and by k_glmm_slopes.hip (K <= 4 effects per group: the
-// three walks templated over the policy).  glmm_fixup_kernel and glmm_num_tiles keep their ONE definition in k_glmm.hip (a
+// k_glmm_walk.h -- what every mixed-model kernel that walks the rows shares (DESIGN.md sections 27, 31 and 33): the tile size, the
+// likelihood policies, the head of a tile of group-sorted rows (gs_stage_sorted_tile), the destination of a flushed segment
+// (gs_flush_dst) and the grid of every walk (glmm_grid).  Included by k_glmm.hip (the random intercept: its own three kernels over
+// the rows, on LogisticLik) and by k_glmm_slopes.hip (K <= 4 effects per group: the three walks templated over the policy).
+// glmm_fixup_kernel and glmm_num_tiles keep their ONE definition in k_glmm.hip (a
 // __global__ function in a header would be compiled into both code objects); k_kernels.h and lrvb_internal.h declare them.
 #pragma once
 #include "lrvb_internal.h"
@@ -212,3 +213,6 @@ __device__ __forceinline__ double* gs_flush_dst(bool whole, int g, i64 tile, int
 {
     return whole ? gsum + (i64)g * ncol : part + (tile * 2 + (run_start == 0 ? 0 : 1)) * ncol;
 }
+
+// One grid for every walk over `rows` rows: a workgroup per tile, at most 2048 of them (a workgroup then walks several tiles).
+inline unsigned glmm_grid(i64 rows) { const i64 n_tiles = glmm_num_tiles(rows); return (unsigned)(n_tiles < 1 ? 1 : (n_tiles < 2048 ? n_tiles : 2048)); }

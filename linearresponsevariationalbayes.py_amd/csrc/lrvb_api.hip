@@ -1598,6 +1598,17 @@ extern "C" int lrvb_obs_quadform(lrvb_ctx* c, const double* M, const double* cve
 
 // ---- grouped sufficient statistics (hierarchical models: BASELINE.json config 4) -----------------
 
+// c->groups, as lrvb_set_groups below writes it (i64 and double are both 8 bytes):
+// [perm (N) | offsets (G + 1) | first group of each wave (NW) | the ids themselves, int32, in the original row order]
+static i64 groups_words_before_ids(i64 n, i64 n_groups) {
+    const i64 R = grouped_rows_per_wave(n);
+    return n + n_groups + 1 + (n + R - 1) / R;
+}
+// The ids of the rows in their original order, for the kernels that stream a window of rows (row influence, predict)
+static const int* groups_ids(const lrvb_ctx* c) {
+    return reinterpret_cast<const int*>(reinterpret_cast<const i64*>(c->groups.p) + groups_words_before_ids(c->N, c->n_groups));
+}
+
 extern "C" int lrvb_set_groups(lrvb_ctx* c, const int32_t* gid, int64_t n, int64_t n_groups) {
     LRVB_TRY(ctx_bind(c));
     if (!gid || n != c->N || n_groups <= 0) LRVB_FAIL(LRVB_ERR_SIZE, "group ids must have %lld entries and n_groups > 0", (long long)c->N);
@@ -1616,11 +1627,10 @@ extern "C" int lrvb_set_groups(lrvb_ctx* c, const int32_t* gid, int64_t n, int64
     std::vector<i64> wg0((size_t)NW);
     for (i64 wv = 0; wv < NW; ++wv)
         wg0[(size_t)wv] = (i64)(std::upper_bound(offs.begin(), offs.end(), wv * R) - offs.begin()) - 1;
-    // [perm | offsets | first group of each wave | the ids themselves, int32, in the original row order (lrvb_glmm_obs_influence)]
-    const size_t words = (size_t)n + (size_t)n_groups + 1 + (size_t)NW + ((size_t)n + 1) / 2;
-    LRVB_TRY(buf_reserve(c, c->groups, words));          // i64 and double are both 8 bytes
+    const i64 before_ids = groups_words_before_ids(n, n_groups);      // the layout above; groups_ids() reads it back
+    LRVB_TRY(buf_reserve(c, c->groups, (size_t)before_ids + ((size_t)n + 1) / 2));
     i64* dev = reinterpret_cast<i64*>(c->groups.p);
-    HIP_TRY(hipMemcpyAsync(dev + n + n_groups + 1 + NW, gid, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dev + before_ids, gid, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(dev, perm.data(), (size_t)n * sizeof(i64), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(dev + n, offs.data(), ((size_t)n_groups + 1) * sizeof(i64), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(dev + n + n_groups + 1, wg0.data(), (size_t)NW * sizeof(i64), hipMemcpyHostToDevice, c->stream));
@@ -2560,17 +2570,28 @@ extern "C" int lrvb_logitnormal_terms(lrvb_ctx* c, const double* mean, const dou
 }
 
 // ---- logistic mixed model with K <= 4 random effects per group (k_glmm_slopes.hip) ---------------------------------------------
+// The per-row data a mixed model keeps resident (group design, offset, trials): sums formed under other values are dropped, and
+// `rows` stays zero until the n x width values have arrived.  A null pointer clears the data; `empty` is the refusal of n < 1.
+static int glmms_set_rows(lrvb_ctx* c, DevBuf& buf, i64& rows, const double* values, int64_t n, int64_t width, const char* empty) {
+    c->glmms_drop();
+    rows = 0;
+    if (!values) return LRVB_OK;
+    if (n < 1) LRVB_FAIL(LRVB_ERR_SIZE, "%s", empty);
+    LRVB_TRY(buf_reserve(c, buf, (size_t)(n * width)));
+    HIP_TRY(hipMemcpyAsync(buf.p, values, (size_t)(n * width) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    rows = n;
+    return LRVB_OK;
+}
+
 extern "C" int lrvb_set_group_design(lrvb_ctx* c, const double* z, int64_t n, int64_t K) {
     LRVB_TRY(ctx_bind(c));
     if (!z) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
     if (K < 1 || K > 4) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 4 random effects per group (got %lld)", (long long)K);
-    if (n < 1) LRVB_FAIL(LRVB_ERR_SIZE, "the group design needs at least one row");
-    c->glmms_drop();
-    c->gz_n = 0; c->gz_K = 0;
-    LRVB_TRY(buf_reserve(c, c->gz, (size_t)(n * K)));
-    HIP_TRY(hipMemcpyAsync(c->gz.p, z, (size_t)(n * K) * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->gz_n = n; c->gz_K = (int)K;
+    if (n < 1) LRVB_FAIL(LRVB_ERR_SIZE, "the group design needs at least one row");      // refused with the resident state untouched
+    c->gz_K = 0;
+    LRVB_TRY(glmms_set_rows(c, c->gz, c->gz_n, z, n, K, ""));
+    c->gz_K = (int)K;
     return LRVB_OK;
 }
 
@@ -2611,6 +2632,14 @@ static int glmms_check(lrvb_ctx* c, const GlmmLik& lik, const double* mean, cons
     return LRVB_OK;
 }
 
+// The not-positive-definite flag of an elimination: an int a kernel raised in the first word of the double at `flag`
+static int read_flag(lrvb_ctx* c, const double* flag, int* bad) {
+    double fh = 0.0;
+    LRVB_TRY(d2h(c, &fh, flag, 1));
+    memcpy(bad, &fh, sizeof(int));
+    return LRVB_OK;
+}
+
 // The likelihood as the kernels read it: the nodes uploaded behind `g` (256 doubles: x | w), the resident offset and trials.
 static int glmms_to_device(lrvb_ctx* c, GlmmLik& lik, double* g) {
     if (lik.kind != GLMM_LOGISTIC) lik.off = c->goff_n ? c->goff.p : nullptr;
@@ -2620,6 +2649,22 @@ static int glmms_to_device(lrvb_ctx* c, GlmmLik& lik, double* g) {
     LRVB_TRY(h2d(c, g + 128, lik.gw, (size_t)lik.n_nodes));
     lik.gx = g; lik.gw = g + 128;
     return LRVB_OK;
+}
+
+// The point on the device, at the head of c->work1: [nodes 256 (not Poisson) | m, v (2 up(P)) | e, r (2 up(GK))], `doubles` in
+// all; what a body keeps behind it (`tail` doubles) starts at g + doubles.  Reserves work1, uploads the likelihood and the point.
+struct GlmmPoint { double *g, *m, *v, *e, *r; i64 doubles; };
+static int glmms_point_upload(lrvb_ctx* c, GlmmLik& lik, const double* mean, const double* var, const double* e_loc, const double* r_loc,
+                              i64 P, i64 GK, size_t tail, GlmmPoint* pt) {
+    const i64 nodes = lik.kind == GLMM_POISSON ? 0 : 256;
+    pt->doubles = nodes + 2 * up(P) + 2 * up(GK);
+    LRVB_TRY(buf_reserve(c, c->work1, (size_t)pt->doubles + tail));
+    pt->g = c->work1.p; pt->m = pt->g + nodes; pt->v = pt->m + up(P); pt->e = pt->v + up(P); pt->r = pt->e + up(GK);
+    LRVB_TRY(glmms_to_device(c, lik, pt->g));
+    LRVB_TRY(h2d(c, pt->m, mean, (size_t)P));
+    LRVB_TRY(h2d(c, pt->v, var, (size_t)P));
+    LRVB_TRY(h2d(c, pt->e, e_loc, (size_t)GK));
+    return h2d(c, pt->r, r_loc, (size_t)GK);
 }
 
 // c->glmms: [H blocks (3 P^2) | group sums (G x ncol) | gradient (2 P) | value] -- every sum over observations of the call, adjacent,
@@ -2640,20 +2685,15 @@ static int glmms_terms(lrvb_ctx* c, GlmmLik lik, const double* mean, const doubl
         EW(square_kernel, N * P, (const double*)c->X.p, X2.p);
         c->x2_ready = true;
     }
-    const i64 NP = up(N + 64), n_tiles = glmm_num_tiles(N), GK = G * K, ncf = poisson ? 2 : 5, nodes = poisson ? 0 : 256;
-    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(nodes + 2 * up(P) + 2 * up(GK) + ncf * NP + n_tiles * 2 * ncol + n_tiles)));
+    const i64 NP = up(N + 64), n_tiles = glmm_num_tiles(N), GK = G * K, ncf = poisson ? 2 : 5;
+    GlmmPoint pt;
+    LRVB_TRY(glmms_point_upload(c, lik, mean, var, e_loc, r_loc, P, GK, (size_t)(ncf * NP + n_tiles * 2 * ncol + n_tiles), &pt));
     LRVB_TRY(buf_reserve(c, c->glmms, (size_t)(3 * P * P + G * ncol + 2 * P + 1)));
-    double* g = c->work1.p; double* dm = g + nodes; double* dv = dm + up(P); double* de = dv + up(P); double* dr = de + up(GK);
-    double* coef = dr + up(GK); double* part = coef + ncf * NP; double* vpart = part + n_tiles * 2 * ncol;
+    double* coef = pt.g + pt.doubles; double* part = coef + ncf * NP; double* vpart = part + n_tiles * 2 * ncol;
     double* Hb = c->glmms.p; double* gsum = Hb + 3 * P * P; double* gred = gsum + G * ncol; double* vred = gred + 2 * P;
-    LRVB_TRY(glmms_to_device(c, lik, g));
-    LRVB_TRY(h2d(c, dm, mean, (size_t)P));
-    LRVB_TRY(h2d(c, dv, var, (size_t)P));
-    LRVB_TRY(h2d(c, de, e_loc, (size_t)GK));
-    LRVB_TRY(h2d(c, dr, r_loc, (size_t)GK));
     HIP_TRY(hipMemsetAsync(coef, 0, (size_t)(ncf * NP) * sizeof(double), c->stream));
     HIP_TRY(hipMemsetAsync(gsum, 0, (size_t)(G * ncol + 2 * P + 1) * sizeof(double), c->stream));
-    LRVB_TRY(launch_glmm_slopes_rows(c, lik, (int)K, lik.unit ? nullptr : c->gz.p, dm, dv, de, dr, coef, NP, gsum, part, vpart));
+    LRVB_TRY(launch_glmm_slopes_rows(c, lik, (int)K, lik.unit ? nullptr : c->gz.p, pt.m, pt.v, pt.e, pt.r, coef, NP, gsum, part, vpart));
     hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, c->stream, (const double*)vpart, n_tiles, vred);
     HIP_TRY(hipGetLastError());
     // Poisson: a2 = h / 2 (the factor rides on the product), c11 = h, c12 = h / 2, c22 = h / 4 (one vector, the blocks scaled after)
@@ -2724,32 +2764,43 @@ extern "C" int lrvb_glmm_terms(lrvb_ctx* c, const double* mean, const double* va
     return LRVB_OK;
 }
 
+// The elimination behind both Schur entries: M = sum_g C_g^T A_g^-1 C_g = U^T U from the resident group sums.  The intercept's entry
+// (K = 1: [a11, a12, a22] is the upper triangle of its 2 x 2 block, G x 6 its G x 2 x 3 closed rows) keeps all
+// of it in c->work1, [flag 8 | blocks up(NT G) | chain factors up(2 K G) | closed rows up(6 K G) | U (2 K G x ldu) | M (R R)]; with
+// `keep` the blocks as uploaded and U = L^-1 C go to c->glmms_fac, [blocks | U], where they outlive the call (the solve passes, the
+// group covariance), and work1 holds the rest in the same order.
+static int glmms_schur(lrvb_ctx* c, i64 K, bool keep, const double* blocks, const double* border_scale, const double* closed_rows,
+                       double* M_out, const char* not_posdef) {
+    const i64 P = c->P, G = c->n_groups, R = 2 * P + 3 * K, K2 = 2 * K, NT = K * (K2 + 1);
+    const int ldu = (int)up(R);
+    const i64 fac = up(NT * G) + K2 * G * ldu;
+    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(8 + up(K2 * G) + up(3 * K2 * G) + R * R + (keep ? 0 : fac))));
+    if (keep) LRVB_TRY(buf_reserve(c, c->glmms_fac, (size_t)fac));
+    double* flag = c->work1.p;
+    double* loc = keep ? c->glmms_fac.p : flag + 8;
+    double* sc = keep ? flag + 8 : loc + up(NT * G); double* cl = sc + up(K2 * G);
+    double* U = keep ? loc + up(NT * G) : cl + up(3 * K2 * G);
+    double* Md = keep ? cl + up(3 * K2 * G) : U + K2 * G * ldu;
+    LRVB_TRY(h2d(c, loc, blocks, (size_t)(NT * G)));
+    LRVB_TRY(h2d(c, sc, border_scale, (size_t)(K2 * G)));
+    LRVB_TRY(h2d(c, cl, closed_rows, (size_t)(3 * K2 * G)));
+    HIP_TRY(hipMemsetAsync(flag, 0, sizeof(double), c->stream));
+    LRVB_TRY(launch_glmm_slopes_schur_rows(c, (int)K, c->glmms.p + 3 * P * P, loc, sc, cl, U, ldu, reinterpret_cast<int*>(flag)));
+    LRVB_TRY(launch_gemm(c, true, false, R, R, K2 * G, 1.0, U, ldu, U, ldu, 0.0, Md, R));
+    int bad = 0;
+    LRVB_TRY(read_flag(c, flag, &bad));
+    if (bad) LRVB_FAIL(LRVB_ERR_NOT_POSDEF, "%s", not_posdef);
+    return d2h(c, M_out, Md, (size_t)(R * R));
+}
+
 extern "C" int lrvb_glmm_schur(lrvb_ctx* c, const double* local_2x2, const double* border_scale, const double* closed_rows, int64_t G_in,
                                double* M_out) {
     LRVB_TRY(ctx_bind(c));
     if (!local_2x2 || !border_scale || !closed_rows || !M_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
     if (c->n_groups <= 0 || !c->glmms_valid || c->glmms_K != 0) LRVB_FAIL(LRVB_ERR_STATE, "no group sums resident: call lrvb_glmm_terms first");
-    const i64 P = c->P, G = c->n_groups, R = 2 * P + 3;
-    LRVB_TRY(check_len(G_in, G, "local blocks"));
-    const int ldu = (int)up(R);
-    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(8 + up(3 * G) + up(2 * G) + up(6 * G) + 2 * G * ldu + R * R)));
-    double* flag = c->work1.p; double* loc = flag + 8; double* sc = loc + up(3 * G); double* cl = sc + up(2 * G);
-    double* U = cl + up(6 * G); double* Md = U + 2 * G * ldu;
-    LRVB_TRY(h2d(c, loc, local_2x2, (size_t)(3 * G)));
-    LRVB_TRY(h2d(c, sc, border_scale, (size_t)(2 * G)));
-    LRVB_TRY(h2d(c, cl, closed_rows, (size_t)(6 * G)));
-    HIP_TRY(hipMemsetAsync(flag, 0, sizeof(double), c->stream));
-    const double* gsum = c->glmms.p + 3 * P * P;
-    // glmm_slopes_schur_rows_kernel<1>: [a11, a12, a22] is the upper triangle of its 2 x 2 block, G x 6 its G x 2 x 3 closed rows;
-    // it gives the bits of the 2 x 2 kernel this entry had
-    LRVB_TRY(launch_glmm_slopes_schur_rows(c, 1, gsum, loc, sc, cl, U, ldu, reinterpret_cast<int*>(flag)));
-    LRVB_TRY(launch_gemm(c, true, false, R, R, 2 * G, 1.0, U, ldu, U, ldu, 0.0, Md, R));
-    double fh = 0.0;
-    LRVB_TRY(d2h(c, &fh, flag, 1));
-    int bad = 0;
-    memcpy(&bad, &fh, sizeof(int));
-    if (bad) LRVB_FAIL(LRVB_ERR_NOT_POSDEF, "a 2 x 2 local block of the logistic mixed model is not positive definite");
-    return d2h(c, M_out, Md, (size_t)(R * R));
+    LRVB_TRY(check_len(G_in, c->n_groups, "local blocks"));
+    return glmms_schur(c, 1, false, local_2x2, border_scale, closed_rows, M_out,
+                       "a 2 x 2 local block of the logistic mixed model is not positive definite");
 }
 
 extern "C" int lrvb_glmm_slopes_schur(lrvb_ctx* c, const double* local_blocks, const double* border_scale, const double* closed_rows,
@@ -2759,28 +2810,10 @@ extern "C" int lrvb_glmm_slopes_schur(lrvb_ctx* c, const double* local_blocks, c
     if (K < 1 || K > 4) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 4 random effects per group (got %lld)", (long long)K);
     if (c->n_groups <= 0 || !c->glmms_valid || c->glmms_K != K)
         LRVB_FAIL(LRVB_ERR_STATE, "no group sums of %lld effects resident: call lrvb_glmm_slopes_terms first", (long long)K);
-    const i64 P = c->P, G = c->n_groups, R = 2 * P + 3 * K, K2 = 2 * K, NT = K * (K2 + 1);
-    LRVB_TRY(check_len(G_in, G, "local blocks"));
-    const int ldu = (int)up(R);
+    LRVB_TRY(check_len(G_in, c->n_groups, "local blocks"));
     c->glmms_fac_valid = false; c->glmms_T_Q = 0; c->glmms_gcov_rows = 0;
-    // the uploaded blocks and U outlive the call in a buffer of their own (lrvb_glmm_slopes_solve_forward / _back)
-    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(8 + up(K2 * G) + up(3 * K2 * G) + R * R)));
-    LRVB_TRY(buf_reserve(c, c->glmms_fac, (size_t)(up(NT * G) + K2 * G * ldu)));
-    double* flag = c->work1.p; double* sc = flag + 8; double* cl = sc + up(K2 * G); double* Md = cl + up(3 * K2 * G);
-    double* loc = c->glmms_fac.p; double* U = loc + up(NT * G);
-    LRVB_TRY(h2d(c, loc, local_blocks, (size_t)(NT * G)));
-    LRVB_TRY(h2d(c, sc, border_scale, (size_t)(K2 * G)));
-    LRVB_TRY(h2d(c, cl, closed_rows, (size_t)(3 * K2 * G)));
-    HIP_TRY(hipMemsetAsync(flag, 0, sizeof(double), c->stream));
-    const double* gsum = c->glmms.p + 3 * P * P;
-    LRVB_TRY(launch_glmm_slopes_schur_rows(c, (int)K, gsum, loc, sc, cl, U, ldu, reinterpret_cast<int*>(flag)));
-    LRVB_TRY(launch_gemm(c, true, false, R, R, K2 * G, 1.0, U, ldu, U, ldu, 0.0, Md, R));
-    double fh = 0.0;
-    LRVB_TRY(d2h(c, &fh, flag, 1));
-    int bad = 0;
-    memcpy(&bad, &fh, sizeof(int));
-    if (bad) LRVB_FAIL(LRVB_ERR_NOT_POSDEF, "a local block of the logistic mixed model with slopes is not positive definite");
-    LRVB_TRY(d2h(c, M_out, Md, (size_t)(R * R)));
+    LRVB_TRY(glmms_schur(c, K, true, local_blocks, border_scale, closed_rows, M_out,
+                         "a local block of the logistic mixed model with slopes is not positive definite"));
     c->glmms_fac_valid = true; c->glmms_fac_K = (int)K;
     return LRVB_OK;
 }
@@ -2831,24 +2864,17 @@ extern "C" int lrvb_glmm_slopes_solve_back(lrvb_ctx* c, const double* x_coupled,
 // ---- weight influence of every mixed model (k_glmm.hip, k_glmm_slopes.hip) --------------------------------------------------------
 // The checks of glmms_terms, in its order, then the operand.  c->work1 holds
 //   [nodes 256 (not Poisson) | m, v (2 up(P)) | e, r (2 up(G K)) | A_global (Q x 2 P) | A_local (G x 2 K x Q) | call-specific scratch]
-struct GlmmInflBufs { double *g, *m, *v, *e, *r, *Ag, *Al, *extra; };
+struct GlmmInflBufs { GlmmPoint pt; double *Ag, *Al, *extra; };
 static int glmms_infl_setup(lrvb_ctx* c, GlmmLik& lik, const double* mean, const double* var, int64_t P_in, const double* e_loc,
                             const double* r_loc, int64_t G_in, int64_t K, const double* A_global, const double* A_local, int64_t Q,
                             const void* out, size_t extra, GlmmInflBufs& b) {
     LRVB_TRY(glmms_check(c, lik, mean, var, P_in, e_loc, r_loc, G_in, K, !A_global || !A_local || !out));
     if (Q < 1) LRVB_FAIL(LRVB_ERR_INVALID, "Q must be positive");
-    const i64 P = c->P, GK = c->n_groups * K, nodes = lik.kind == GLMM_POISSON ? 0 : 256;
-    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(nodes + 2 * up(P) + 2 * up(GK) + up(Q * 2 * P) + up(GK * 2 * Q)) + extra));
-    b.g = c->work1.p; b.m = b.g + nodes; b.v = b.m + up(P); b.e = b.v + up(P); b.r = b.e + up(GK);
-    b.Ag = b.r + up(GK); b.Al = b.Ag + up(Q * 2 * P); b.extra = b.Al + up(GK * 2 * Q);
-    LRVB_TRY(glmms_to_device(c, lik, b.g));
-    LRVB_TRY(h2d(c, b.m, mean, (size_t)P));
-    LRVB_TRY(h2d(c, b.v, var, (size_t)P));
-    LRVB_TRY(h2d(c, b.e, e_loc, (size_t)GK));
-    LRVB_TRY(h2d(c, b.r, r_loc, (size_t)GK));
+    const i64 P = c->P, GK = c->n_groups * K;
+    LRVB_TRY(glmms_point_upload(c, lik, mean, var, e_loc, r_loc, P, GK, (size_t)(up(Q * 2 * P) + up(GK * 2 * Q)) + extra, &b.pt));
+    b.Ag = b.pt.g + b.pt.doubles; b.Al = b.Ag + up(Q * 2 * P); b.extra = b.Al + up(GK * 2 * Q);
     LRVB_TRY(h2d(c, b.Ag, A_global, (size_t)(Q * 2 * P)));
-    LRVB_TRY(h2d(c, b.Al, A_local, (size_t)(GK * 2 * Q)));
-    return LRVB_OK;
+    return h2d(c, b.Al, A_local, (size_t)(GK * 2 * Q));
 }
 
 static int glmms_obs_influence(lrvb_ctx* c, GlmmLik lik, const double* mean, const double* var, int64_t P_in, const double* e_loc,
@@ -2860,9 +2886,7 @@ static int glmms_obs_influence(lrvb_ctx* c, GlmmLik lik, const double* mean, con
     const i64 rows = n1 - n0;
     if (rows == 0) return LRVB_OK;
     LRVB_TRY(buf_reserve(c, c->cgT, (size_t)(rows * Q)));
-    const i64 NW = (c->N + grouped_rows_per_wave(c->N) - 1) / grouped_rows_per_wave(c->N);
-    const int* gid = reinterpret_cast<const int*>(reinterpret_cast<const i64*>(c->groups.p) + c->N + c->n_groups + 1 + NW);
-    LRVB_TRY(launch_glmm_slopes_infl_rows(c, lik, (int)K, lik.unit ? nullptr : c->gz.p, n0, n1, gid, b.m, b.v, b.e, b.r, b.Ag, b.Al, Q, c->cgT.p));
+    LRVB_TRY(launch_glmm_slopes_infl_rows(c, lik, (int)K, lik.unit ? nullptr : c->gz.p, n0, n1, groups_ids(c), b.pt.m, b.pt.v, b.pt.e, b.pt.r, b.Ag, b.Al, Q, c->cgT.p));
     return d2h(c, out, c->cgT.p, (size_t)(rows * Q));       // per-observation rows: rank-local, no hook call
 }
 
@@ -2877,7 +2901,7 @@ static int glmms_group_influence(lrvb_ctx* c, GlmmLik lik, const double* mean, c
     LRVB_TRY(glmms_infl_setup(c, lik, mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out, extra, b));
     double* gsum = b.extra; double* part = gsum + G * ncol; double* od = part + n_tiles * 2 * ncol;
     HIP_TRY(hipMemsetAsync(gsum, 0, (size_t)(G * ncol) * sizeof(double), c->stream));       // empty groups keep the zeros
-    LRVB_TRY(launch_glmm_slopes_infl_gsum(c, lik, (int)K, lik.unit ? nullptr : c->gz.p, b.m, b.v, b.e, b.r, gsum, part));
+    LRVB_TRY(launch_glmm_slopes_infl_gsum(c, lik, (int)K, lik.unit ? nullptr : c->gz.p, b.pt.m, b.pt.v, b.pt.e, b.pt.r, gsum, part));
     LRVB_TRY(launch_gemm(c, false, true, G, Q, 2 * c->P, 1.0, gsum + 2 * K, ncol, b.Ag, 2 * c->P, 0.0, od, Q));
     if (lik.unit) LRVB_TRY(launch_glmm_infl_local(c, Q, gsum, b.Al, od));                   // the intercept keeps its two-column kernel
     else LRVB_TRY(launch_glmm_slopes_infl_local(c, (int)K, Q, gsum, b.Al, od));
@@ -2917,15 +2941,7 @@ extern "C" int lrvb_glmm_slopes_group_influence(lrvb_ctx* c, const double* mean,
 // ---- Poisson mixed model with K <= 4 random effects per group (k_glmm_slopes.hip, DESIGN.md sections 26 and 27) ------------------
 extern "C" int lrvb_set_offset(lrvb_ctx* c, const double* offset, int64_t n) {
     LRVB_TRY(ctx_bind(c));
-    c->glmms_drop();                                                     // sums formed under another offset are not those of the model
-    c->goff_n = 0;
-    if (!offset) return LRVB_OK;
-    if (n < 1) LRVB_FAIL(LRVB_ERR_SIZE, "the offset needs at least one entry");
-    LRVB_TRY(buf_reserve(c, c->goff, (size_t)n));
-    HIP_TRY(hipMemcpyAsync(c->goff.p, offset, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->goff_n = n;
-    return LRVB_OK;
+    return glmms_set_rows(c, c->goff, c->goff_n, offset, n, 1, "the offset needs at least one entry");
 }
 
 // The three Poisson entries: the shared bodies above with the Poisson likelihood (no nodes; the offset of lrvb_set_offset).
@@ -2954,15 +2970,7 @@ extern "C" int lrvb_glmm_poisson_group_influence(lrvb_ctx* c, const double* mean
 // ---- binomial mixed model with per-row trials and offset, and through it the negative binomial one -------
 extern "C" int lrvb_set_trials(lrvb_ctx* c, const double* trials, int64_t n) {
     LRVB_TRY(ctx_bind(c));
-    c->glmms_drop();                                                     // sums formed under other trial counts are not those of the model
-    c->gtr_n = 0;
-    if (!trials) return LRVB_OK;
-    if (n < 1) LRVB_FAIL(LRVB_ERR_SIZE, "the trials need at least one entry");
-    LRVB_TRY(buf_reserve(c, c->gtr, (size_t)n));
-    HIP_TRY(hipMemcpyAsync(c->gtr.p, trials, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->gtr_n = n;
-    return LRVB_OK;
+    return glmms_set_rows(c, c->gtr, c->gtr_n, trials, n, 1, "the trials need at least one entry");
 }
 
 // The three binomial entries: the shared bodies above with the binomial likelihood (the caller's nodes; the offset of
@@ -3043,18 +3051,13 @@ static int glmms_predict(lrvb_ctx* c, GlmmLik lik, const double* mean, const dou
         n = n1 - n0;
     }
     if (n == 0) return LRVB_OK;
-    const i64 P = c->P, GK = Gp * K, nodes = lik.kind == GLMM_POISSON ? 0 : 256;
-    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(nodes + 2 * up(P) + 2 * up(GK) + P * P)));
+    const i64 P = c->P, GK = Gp * K;
+    GlmmPoint pt;
+    LRVB_TRY(glmms_point_upload(c, lik, mean, var, e_loc, r_loc, P, GK, (size_t)(P * P), &pt));
     LRVB_TRY(buf_reserve(c, c->cgT, (size_t)(up(5 * n) + (fresh ? up(n * P) + up(n * K) + 2 * up(n) + up((n + 1) / 2) : 0))));
-    double* g = c->work1.p; double* dm = g + nodes; double* dv = dm + up(P); double* de = dv + up(P); double* dr = de + up(GK);
-    double* Sbb = dr + up(GK);
+    double* Sbb = pt.g + pt.doubles;
     double* od = c->cgT.p; double* xn = od + up(5 * n); double* zn = xn + up(n * P); double* on = zn + up(n * K); double* tn = on + up(n);
     double* gn = tn + up(n);
-    LRVB_TRY(glmms_to_device(c, lik, g));
-    LRVB_TRY(h2d(c, dm, mean, (size_t)P));
-    LRVB_TRY(h2d(c, dv, var, (size_t)P));
-    LRVB_TRY(h2d(c, de, e_loc, (size_t)GK));
-    LRVB_TRY(h2d(c, dr, r_loc, (size_t)GK));
     LRVB_TRY(h2d(c, Sbb, cov_beta, (size_t)(P * P)));
     const double* X = c->X.p; const double* Z = c->gz.p;
     const int* gid;
@@ -3066,11 +3069,8 @@ static int glmms_predict(lrvb_ctx* c, GlmmLik lik, const double* mean, const dou
         if (lik.kind != GLMM_LOGISTIC && off_new) { LRVB_TRY(h2d(c, on, off_new, (size_t)n)); lik.off = on; }
         if (lik.kind == GLMM_BINOMIAL && tr_new) { LRVB_TRY(h2d(c, tn, tr_new, (size_t)n)); lik.trials = tn; }
         X = xn; Z = zn; gid = reinterpret_cast<const int*>(gn); n0 = 0; n1 = n;
-    } else {
-        const i64 NW = (c->N + grouped_rows_per_wave(c->N) - 1) / grouped_rows_per_wave(c->N);
-        gid = reinterpret_cast<const int*>(reinterpret_cast<const i64*>(c->groups.p) + c->N + c->n_groups + 1 + NW);
-    }
-    LRVB_TRY(launch_glmm_slopes_predict_rows(c, lik, (int)K, X, Z, n0, n1, gid, dm, dv, de, dr, Sbb, c->glmms_gcov.p, od, n));
+    } else gid = groups_ids(c);
+    LRVB_TRY(launch_glmm_slopes_predict_rows(c, lik, (int)K, X, Z, n0, n1, gid, pt.m, pt.v, pt.e, pt.r, Sbb, c->glmms_gcov.p, od, n));
     return d2h(c, out, od, (size_t)(5 * n));                  // per-observation rows: rank-local, no hook call
 }
 

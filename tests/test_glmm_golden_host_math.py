@@ -4,7 +4,9 @@ and gradients of both models agree with the torch references (tests/glmm_slopes_
 to the tolerances of `_check_against_reference` in the GPU tests: value 1e-11, gradient 1e-10 relative.  So a fixture recorded from
 a broken build does not pass for the truth that tests/test_gpu_glmm_walk_golden.py compares against bit for bit.  The intercept
 fixture is checked the same way against tests/glmm_reference.py, at the same tolerances; what it holds raw
-of the Hessian pieces at the 1e-9 of tests/test_gpu_glmm.py."""
+of the Hessian pieces at the 1e-9 of tests/test_gpu_glmm.py.  tests/golden/glmm_solve_predict_parent.npz: the
+inputs digests, how many cases hold each output raw, and the raw solves and predict columns against a dense solve and a dense
+inverse of the torch reference Hessians of the four families."""
 import os
 import re
 import sys
@@ -186,3 +188,237 @@ def test_intercept_recorded_outputs_agree_with_the_reference(ifixture, case):
             assert e2 < 1e-9
         else:
             assert tuple(ifixture[head + name + ':shape']) == want.shape
+
+
+# ---- tests/golden/glmm_solve_predict_parent.npz: the device-resident solve, the group covariance and predict --
+import make_glmm_solve_predict_golden as sp                              # noqa: E402
+import glmm_binomial_reference as bref                                   # noqa: E402
+
+S_IDS = [c['name'] for c in sp.CASES]
+S_OUTPUTS = (['schur', 'group_cov', 'predict_window', 'predict_new']
+             + ['%s_q%d' % (e, q) for e in ('solve_forward', 'solve_back') for q in sp.SOLVE_QS])
+S_BINOMIAL = ['value', 'grad', 'H_blocks', 'group_sums'] + ['%s_q%d' % (e, q) for e in ('obs_influence', 'group_influence') for q in sp.INFL_QS]
+U53 = 2.0 ** -53
+LD = np.longdouble
+
+
+@pytest.fixture(scope='module')
+def sfixture():
+    with np.load(sp.FIXTURE) as f:
+        return {k: f[k] for k in f.files}
+
+
+def _raw_count(fx, name):
+    return sum(('%s/%s/%s' % (c['name'], fam, name)) in fx for c in sp.CASES for fam in sp.FAMILIES) // len(sp.FAMILIES)
+
+
+def test_solve_predict_fixture_names_its_parent_and_is_complete(sfixture):
+    assert os.path.getsize(sp.FIXTURE) < 1024 * 1024
+    assert re.fullmatch(r'[0-9a-f]{40}', str(sfixture['parent_commit']))
+    assert 'HIP version' in str(sfixture['hipcc_version'])
+    assert sp.CASES is mg.CASES and sp.RAW_MAX == mg.RAW_MAX == 2048 and sp.SOLVE_QS == (1, 70, 129)
+    for case in sp.CASES:
+        N, P, K, G = case['shape']
+        R = 2 * P + 3 * K
+        n0, n1 = mg.window(N)
+        for fam in sp.FAMILIES:
+            head = '%s/%s/' % (case['name'], fam)
+            for name in S_OUTPUTS + (S_BINOMIAL if fam == 'binomial' else []):
+                key = head + name
+                raw = key in sfixture
+                assert raw != (key + ':sha256' in sfixture and key + ':shape' in sfixture), key
+                if raw:
+                    assert sfixture[key].size <= mg.RAW_MAX and np.all(np.isfinite(sfixture[key]))
+                else:
+                    assert np.prod(sfixture[key + ':shape']) > mg.RAW_MAX
+            assert sfixture[head + 'predict_window'].shape == (5, n1 - n0) and sfixture[head + 'predict_new'].shape == (5, sp.N_NEW)
+            assert sfixture[head + 'solve_forward_q1'].shape == (R, 1) and sfixture[head + 'solve_back_q1'].shape == (G, 2 * K, 1)
+    # So that the checks below are not hollow, every kind is held raw in at least three of the six cases, for every Q it has -- but
+    # for ONE: the forward pass at Q = 129 is (2 P + 3 K) x 129 doubles, 645 and 1161 in the two smallest cases and 2064 = RAW_MAX + 16
+    # in the third (P = 5, K = 2), so it is raw in two.  The counts, by the shapes:
+    assert [_raw_count(sfixture, 'solve_back_q%d' % q) for q in sp.SOLVE_QS] == [6, 4, 3]          # G 2 K Q
+    assert [_raw_count(sfixture, 'solve_forward_q%d' % q) for q in sp.SOLVE_QS] == [6, 3, 2]       # (2 P + 3 K) Q
+    assert _raw_count(sfixture, 'group_cov') == 5                                                   # (G + 1) (K K + K P)
+    assert _raw_count(sfixture, 'predict_window') == _raw_count(sfixture, 'predict_new') == 6       # 5 n, n <= 300
+    refusals = [k for k in sfixture if k.startswith('refusal/') and k.endswith(':status')]
+    assert len(refusals) == sp.N_REFUSALS and all(int(sfixture[k]) < 0 and str(sfixture[k[:-len('status')] + 'text']) for k in refusals)
+    text = lambda k: str(sfixture['refusal/' + k + ':text'])
+    assert text('solve_forward_k1_after_intercept_schur') == 'no factor of 1 effects resident: call lrvb_glmm_slopes_schur first'
+    assert text('solve_back/no_forward') == 'no forward pass resident: call lrvb_glmm_slopes_solve_forward first'
+    assert text('schur/not_positive_definite') == 'a local block of the logistic mixed model with slopes is not positive definite'
+    assert text('predict/no_group_cov') == 'no group covariance of 2 effects resident: call lrvb_glmm_slopes_group_cov first'
+
+
+@pytest.mark.parametrize('case', sp.CASES, ids=S_IDS)
+def test_solve_predict_cases_rebuild_from_their_seeds(sfixture, case):
+    a, b = sp.build_case(case), sp.build_case(case)
+    assert sp.inputs_digest(a) == sp.inputs_digest(b) == str(sfixture[case['name'] + ':inputs'])
+    N, P, K, G = case['shape']
+    assert np.any(a['new']['groups'] == -1) and np.all(a['new']['groups'] < G) and np.any(a['trials'] != 1.0) and np.any(a['o_binomial'] != 0.0)
+
+
+_href = {}
+
+
+def _reference_hessian(case, b, fam):
+    """The dense Hessian of the torch reference in free coordinates at the point of the case, computed once."""
+    key = (case['name'], fam)
+    if key not in _href:
+        N, P, K, G = case['shape']
+        x, z, w, gid = b['x'], b['z'], b['w'], b['gid']
+        if fam == 'logistic':
+            t = sref.tensors(x, b['y_logistic'], z, w, gid, mg.HYP)
+            f, args = sref.kl_free, t[:5] + (G, t[5], b['deg'])
+        elif fam == 'poisson':
+            f, args = pref.kl_free, pref.targs(x, b['y_poisson'], z, w, b['o_poisson'], gid, G, mg.HYP)
+        elif fam == 'binomial':
+            f, args = bref.kl_free, bref.targs(x, b['y_binomial'], z, w, b['o_binomial'], b['trials'], gid, G, mg.HYP)
+        else:
+            f, args = bref.nb_kl_free, bref.targs(x, b['y_negbinomial'], z, w, b['o_binomial'], b['phi'], gid, G, mg.HYP)
+        deg, bref.GH_DEG = bref.GH_DEG, b['deg']                          # the binomial reference reads its node count from the module
+        try:
+            H = gref.value_grad_hess(f, b['free'], args)[2]
+        finally:
+            bref.GH_DEG = deg
+        np.linalg.cholesky(H)                                            # the point of the case: positive definite in every family
+        _href[key] = (H, float(np.linalg.cond(H)))
+    return _href[key]
+
+
+def _fro(a):
+    return np.sqrt(np.sum(np.square(np.asarray(a, dtype=LD))))
+
+
+def _backward_error(H, X, R):
+    """tests/test_gpu_glmm_slopes_device_solve.py::_backward_error: ||R - H X||_F / (||H||_F ||X||_F + ||R||_F) in longdouble."""
+    Hl, Xl, Rl = (np.asarray(a, dtype=LD).reshape(a.shape[0], -1) for a in (H, X, R))
+    return float(_fro(Rl - Hl @ Xl) / (_fro(Hl) * _fro(Xl) + _fro(Rl)))
+
+
+@pytest.mark.parametrize('case', sp.CASES, ids=S_IDS)
+def test_recorded_solves_agree_with_block_arrow_solve(sfixture, case):
+    """The raw solve outputs against the host route, `block_arrow_solve` on the blocks of the reference Hessian, by the rules of
+    tests/test_gpu_glmm_slopes_device_solve.py: eta_dev <= 8 eta_host + D 2^-53 and ||X_dev - X_host||_F <= 2 kappa_2(H)
+    (eta_dev + eta_host) ||X_host||_F.  The fixture holds the local rows of X only, so its own backward error cannot be formed; the
+    forward bound is taken with the largest eta_dev the first rule admits, 2 kappa (9 eta_host + D 2^-53), eta_host measured in
+    longdouble.  The forward pass (H_xl H_ll^-1 R_l) / s is held to the same rule on the local system (kappa_2(H_ll), the measured
+    backward error of the host's H_ll^-1 R_l, D_l = 2 G K), plus D_l 2^-53 for the product, relative to ||H_xl / s||_F ||H_ll^-1 R_l||_F."""
+    from lrvb_amd.block_arrow import _from_groups, _local_index, block_arrow_solve
+    from lrvb_amd.glmm_slopes import coupled_rows
+    N, P, K, G = case['shape']
+    b = sp.build_case(case)
+    ng, rows = 2 * P + 4 * K, coupled_rows(P, K)
+    eta = sp.eta_of(b, P, K, G)
+    # Hx[r, l] = s_r C_g[l, r]: the device holds the border in the coordinates (mean, var, e_mu, a, b)
+    s = np.concatenate([np.ones(P), -1.0 / eta[P:2 * P], np.stack([np.ones(K), eta[ng - 2 * K:ng:2], eta[ng - 2 * K + 1:ng:2]], axis=1).ravel()])
+    li = ng + _local_index(G, K)
+    seen = 0
+    for fam in sp.FAMILIES:
+        H, kappa = _reference_hessian(case, b, fam)
+        D, Dl = H.shape[0], H.shape[0] - ng
+        Hgg, Hx, Hll = H[:ng, :ng], H[rows][:, ng:], H[ng:, ng:]
+        loc = H[li[:, :, None], li[:, None, :]]
+        kl = float(np.linalg.cond(Hll))
+        for Q in sp.SOLVE_QS:
+            head = '%s/%s/' % (case['name'], fam)
+            Rhs = b['rhs'][Q]
+            if head + 'solve_back_q%d' % Q in sfixture:
+                Xh = block_arrow_solve(Hgg, rows, Hx, loc, Rhs)
+                e_host = _backward_error(H, Xh, Rhs)
+                got = _from_groups(sfixture[head + 'solve_back_q%d' % Q], G, K)
+                err, bound = float(_fro(got - Xh[ng:]) / _fro(Xh)), 2.0 * kappa * (9.0 * e_host + D * U53)
+                print(case['name'], fam, Q, 'back: err %.3e, eta_host %.3e, kappa %.3e, bound %.3e' % (err, e_host, kappa, bound))
+                assert err <= bound
+                seen += 1
+            if head + 'solve_forward_q%d' % Q in sfixture:
+                tl = block_arrow_solve(Hgg, rows, Hx, loc, np.vstack([np.zeros((ng, Q)), Rhs[ng:]]), schur_solve=lambda r: np.zeros_like(r))[ng:]
+                e_l = _backward_error(Hll, tl, Rhs[ng:])
+                Hs = Hx / s[:, None]
+                err = float(_fro(sfixture[head + 'solve_forward_q%d' % Q] - Hs @ tl) / (_fro(Hs) * _fro(tl)))
+                bound = 2.0 * kl * (9.0 * e_l + Dl * U53) + Dl * U53
+                print(case['name'], fam, Q, 'forward: err %.3e, eta_host %.3e, kappa_l %.3e, bound %.3e' % (err, e_l, kl, bound))
+                assert err <= bound
+                seen += 1
+    assert seen >= 4 * 2                                                 # Q = 1 is raw in every case
+
+
+def _gh_mean(kind, rho, s, trials, gh_x, gh_w, mp=False):
+    """tests/test_gpu_glmm_predict.py::_gh_mean: the response-scale mean by the rule of the kernels."""
+    import mpmath
+    if not mp:
+        if kind in ('poisson', 'negbinomial'):
+            return np.exp(rho + 0.5 * s)
+        t = rho[:, None] + np.sqrt(np.maximum(s, 0.0))[:, None] * (np.sqrt(2.0) * gh_x)[None, :]
+        p = ((1.0 / (1.0 + np.exp(-t))) * (gh_w / np.sqrt(np.pi))[None, :]).sum(1)
+        return p if trials is None else trials * p
+    mpmath.mp.dps = 40
+    out = []
+    for i in range(rho.size):
+        rh, sv = mpmath.mpf(float(rho[i])), mpmath.mpf(float(s[i]))
+        if kind in ('poisson', 'negbinomial'):
+            out.append(mpmath.exp(rh + sv / 2))
+            continue
+        sd = mpmath.sqrt(max(sv, 0))
+        p = sum(mpmath.mpf(float(wk)) / (1 + mpmath.exp(-(rh + sd * mpmath.sqrt(2) * mpmath.mpf(float(xk))))) for xk, wk in zip(gh_x, gh_w))
+        p = p / mpmath.sqrt(mpmath.pi)
+        out.append(p if trials is None else p * mpmath.mpf(float(trials[i])))
+    return out
+
+
+@pytest.mark.parametrize('case', sp.CASES, ids=S_IDS)
+def test_recorded_predictions_agree_with_the_dense_inverse(sfixture, case):
+    """The raw predict columns against `block_arrow.predict_rows` with the blocks of a dense inverse, by the rules of
+    tests/test_gpu_glmm_predict.py: rho and var_mf within (P + K + 2) 2^-53 of the sum of the absolute values of their terms,
+    var_lrvb by the two-route rule err <= 8 err_host + kappa_2(H) D 2^-53 (err_host: the float64 inverse; both against the inverse
+    refined by one Newton step in longdouble), the two means against the float64 restatement of the quadrature on the recorded
+    rho and variances within 8 x that restatement's own error against mpmath (floor 16 x 2^-53), on the first eight rows."""
+    import mpmath
+    from lrvb_amd.block_arrow import predict_rows
+    N, P, K, G = case['shape']
+    b = sp.build_case(case)
+    ng, GK = 2 * P + 4 * K, G * K
+    eta = sp.eta_of(b, P, K, G)
+    m, v = eta[:P], 1.0 / eta[P:2 * P]
+    e2 = np.vstack([eta[ng:ng + GK].reshape(G, K), eta[2 * P:2 * P + K][None, :]])
+    r2 = np.vstack([1.0 / eta[ng + GK:].reshape(G, K), 1.0 / eta[2 * P + K:2 * P + 2 * K][None, :]])
+    gh_x, gh_w = np.polynomial.hermite.hermgauss(b['deg'])
+    n0, n1 = mg.window(N)
+    ie = np.vstack([ng + np.arange(GK).reshape(G, K), 2 * P + np.arange(K)[None, :]])       # the e rows of every group, then e_mu
+    for fam in sp.FAMILIES:
+        H, kappa = _reference_hessian(case, b, fam)
+        Hinv = np.linalg.inv(H)
+        Hl, X0 = H.astype(LD), Hinv.astype(LD)
+        Hinv_ld = X0 + X0 @ (np.eye(H.shape[0], dtype=LD) - Hl @ X0)    # one Newton step: error kappa^2 u^2, far below either route's
+        blocks = lambda A: (A[:P, :P], np.stack([A[np.ix_(ie[g], ie[g])] for g in range(G + 1)]), np.stack([A[:P][:, ie[g]] for g in range(G + 1)]))
+        (cb, cu, cbu), ref_blocks = blocks(Hinv), blocks(Hinv_ld)
+        floor = kappa * H.shape[0] * U53
+        off = {'logistic': None, 'poisson': b['o_poisson'], 'binomial': b['o_binomial'], 'negbinomial': b['o_binomial']}[fam]   # the negative binomial predicts at its RAW offset
+        tr = b['trials'] if fam == 'binomial' else None                  # ... and through the Poisson mean: no trials
+        new = sp.new_rows(fam, b)
+        sl = slice(n0, n1)
+        gnew = np.where(new['groups'] < 0, G, new['groups'])
+        for what, rows, trials in (('predict_window', (b['x'][sl], b['z'][sl], b['gid'][sl], None if off is None else off[sl]),
+                                    None if tr is None else tr[sl]),
+                                   ('predict_new', (new['x'], new['z'], gnew, new.get('offset')), new.get('trials'))):
+            got = sfixture['%s/%s/%s' % (case['name'], fam, what)]
+            x, z, gid, o = rows
+            rho, s_mf, v_lr = predict_rows(x, z, gid, o, m, v, e2, r2, cb, cu, cbu)
+            t_rho = np.concatenate([(np.zeros(x.shape[0]) if o is None else o)[:, None], x * m[None, :], z * e2[gid]], axis=1).astype(LD)
+            t_s = np.concatenate([(x * x).astype(LD) * v[None, :].astype(LD), (z * z).astype(LD) * r2[gid].astype(LD)], axis=1)
+            assert np.all(np.abs(got[0].astype(LD) - t_rho.sum(1)) <= (P + K + 2) * U53 * np.abs(t_rho).sum(1))
+            assert np.all(np.abs(got[1].astype(LD) - t_s.sum(1)) <= (P + K + 2) * U53 * np.abs(t_s).sum(1))
+            want = predict_rows(x, z, gid, o, m, v, e2, r2, *ref_blocks)[2]
+            e_fix, e_host = np.abs(got[2].astype(LD) - want) / want, np.abs(v_lr.astype(LD) - want) / want
+            print(case['name'], fam, what, 'var_lrvb: err %.3e, err_host %.3e, floor %.3e' % (float(e_fix.max()), float(e_host.max()), floor))
+            assert np.all(want > 0) and np.all(e_fix <= 8.0 * e_host + floor)
+            sub = np.arange(min(8, x.shape[0]))
+            trs = None if trials is None else trials[sub]
+            for col, var in ((3, 1), (4, 2)):
+                mine = _gh_mean(fam, got[0][sub], got[var][sub], trs, gh_x, gh_w)
+                exact = _gh_mean(fam, got[0][sub], got[var][sub], trs, gh_x, gh_w, mp=True)
+                for a, d, ex in zip(mine, got[col][sub], exact):
+                    if ex == 0:
+                        assert a == 0.0 and d == 0.0                     # a binomial row without trials
+                        continue
+                    own = float(abs(mpmath.mpf(float(a)) - ex) / abs(ex))
+                    assert abs(d - a) <= max(8.0 * own, 16.0 * U53) * abs(a)

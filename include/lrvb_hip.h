@@ -447,6 +447,27 @@ int lrvb_glmm_slopes_schur(lrvb_ctx* ctx, const double* local_blocks, const doub
  * K > 4: LRVB_ERR_UNSUPPORTED; Q < 1 or a null pointer: LRVB_ERR_INVALID.                                                    */
 int lrvb_glmm_slopes_solve_forward(lrvb_ctx* ctx, const double* R_local, int64_t G, int64_t K, int64_t Q, double* red_out);
 int lrvb_glmm_slopes_solve_back(lrvb_ctx* ctx, const double* x_coupled, int64_t G, int64_t K, int64_t Q, double* X_local_out);
+/* The elimination and the solve for a DENSE closed border: a K-effect model whose local coordinates couple to NC closed global
+ * coordinates of any meaning (correlated random effects with a Wishart precision: [e_mu (K) | n | vech V], NC = K + 1 + K (K + 1) / 2).
+ * After any K-effect terms entry (lrvb_glmm_slopes_terms, lrvb_glmm_poisson_terms, lrvb_glmm_binomial_terms):
+ *   local_blocks (G x K (2 K + 1)) and border_scale (G x 2 K) as lrvb_glmm_slopes_schur;
+ *   the closed border entries of group g are AFFINE in its K-vector d_g (d_loc, G x K, row-major):
+ *     closed_g[i][c] = A0[i][c] + sum_l A1[i][l][c] d_gl,   i over the 2 K local coordinates [e_g. | r_g.], c over the NC columns,
+ *   A0 (2 K x NC) and A1 (2 K x K x NC) row-major, shared by all groups, in the coordinates of the caller's choice on the closed
+ *   side (the chain factor border_scale[g][i] multiplies row i as it does the group sums).
+ * M_out (R x R, R = 2 P + NC <= 144, row-major) = sum_g C_g^T A_g^-1 C_g over [mean (P) | var (P) | the NC closed columns in the
+ * caller's order].  The factor stays resident as after lrvb_glmm_slopes_schur, with NC recorded: lrvb_glmm_arrow_solve_forward / _back
+ * are lrvb_glmm_slopes_solve_forward / _back on R = 2 P + NC coupled rows.  A factor answers only the entries of its own coupled
+ * layout: an arrow entry asked for another NC than the factor's, or a legacy entry (lrvb_glmm_slopes_solve_forward / _back,
+ * lrvb_glmm_slopes_group_cov) on a factor whose NC is not 3 K, is LRVB_ERR_STATE, and so is the reverse.  Whatever drops the
+ * factor of lrvb_glmm_slopes_schur drops this one.  Fixed order, no atomics: two calls give equal bits.
+ * K < 1, K > 4, NC < K or NC > 16: LRVB_ERR_UNSUPPORTED; a null pointer or Q < 1: LRVB_ERR_INVALID; G not the number of groups:
+ * LRVB_ERR_SIZE; no resident group sums of K effects: LRVB_ERR_STATE; a block that is not positive definite:
+ * LRVB_ERR_NOT_POSDEF (no factor is left).  No reduce-hook call.                                                            */
+int lrvb_glmm_arrow_schur(lrvb_ctx* ctx, const double* local_blocks, const double* border_scale, const double* d_loc, const double* A0,
+                          const double* A1, int64_t G, int64_t K, int64_t NC, double* M_out);
+int lrvb_glmm_arrow_solve_forward(lrvb_ctx* ctx, const double* R_local, int64_t G, int64_t K, int64_t NC, int64_t Q, double* red_out);
+int lrvb_glmm_arrow_solve_back(lrvb_ctx* ctx, const double* x_coupled, int64_t G, int64_t K, int64_t NC, int64_t Q, double* X_local_out);
 
 /* Streamed weight influence of the logistic mixed model.  Point arguments as lrvb_glmm_terms.  Per observation, PER UNIT WEIGHT,
  *   a1' = psi_rho(rho_n, s_n) - y_n,   a2' = psi_s(rho_n, s_n)
@@ -606,6 +627,10 @@ int lrvb_glmm_binomial_group_influence(lrvb_ctx* ctx, const double* mean, const 
  * No reduce-hook call.  Errors as lrvb_glmm_slopes_solve_forward: a null W or s: LRVB_ERR_INVALID; K < 1 or K > 4:
  * LRVB_ERR_UNSUPPORTED; no resident factor of K effects: LRVB_ERR_STATE; G not the number of groups, P not n_cols: LRVB_ERR_SIZE. */
 int lrvb_glmm_slopes_group_cov(lrvb_ctx* ctx, const double* W, const double* s, int64_t P, int64_t G, int64_t K, double* out);
+/* The same on a factor of lrvb_glmm_arrow_schur: W is R x R and s has R entries, R = 2 P + NC in the order of its M_out.
+ * Convention: THE FIRST K CLOSED COLUMNS ARE e_mu_0 .. e_mu_{K-1} (the pseudo-group reads the rows 2 P + k).  The buffer it leaves
+ * resident is that of lrvb_glmm_slopes_group_cov, and the predict entries read it unchanged.  Errors as lrvb_glmm_arrow_solve_forward. */
+int lrvb_glmm_arrow_group_cov(lrvb_ctx* ctx, const double* W, const double* s, int64_t P, int64_t G, int64_t K, int64_t NC, double* out);
 /* Fitted values and predictions: the streaming sibling of lrvb_glmm_slopes_obs_influence.  Point arguments as there, except that
  * e and r are G' x K with G' = G or G + 1 (row G: the pseudo-group, e_mu and 1 / i_mu); cov_beta (P x P, row-major, host) is
  * Sigma_bb = W[:P, :P].  Per row with design (x, z), group g and offset o,

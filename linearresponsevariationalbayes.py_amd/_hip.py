@@ -92,6 +92,10 @@ _SIGNATURES = {
     'lrvb_glmm_slopes_solve_forward': [_VP, _VP, c_i64, c_i64, c_i64, _VP],
     'lrvb_glmm_slopes_solve_back': [_VP, _VP, c_i64, c_i64, c_i64, _VP],
     'lrvb_glmm_slopes_group_cov': [_VP, _VP, _VP, c_i64, c_i64, c_i64, _VP],
+    'lrvb_glmm_arrow_schur': [_VP, _VP, _VP, _VP, _VP, _VP, c_i64, c_i64, c_i64, _VP],
+    'lrvb_glmm_arrow_solve_forward': [_VP, _VP, c_i64, c_i64, c_i64, c_i64, _VP],
+    'lrvb_glmm_arrow_solve_back': [_VP, _VP, c_i64, c_i64, c_i64, c_i64, _VP],
+    'lrvb_glmm_arrow_group_cov': [_VP, _VP, _VP, c_i64, c_i64, c_i64, c_i64, _VP],
     'lrvb_glmm_slopes_predict': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, ctypes.c_int32, _VP, c_i64, c_i64, _VP, _VP, _VP, c_i64, _VP],
     'lrvb_glmm_poisson_predict': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, c_i64, c_i64, _VP, _VP, _VP, _VP, c_i64, _VP],
     'lrvb_glmm_binomial_predict': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, ctypes.c_int32, _VP, c_i64, c_i64, _VP, _VP, _VP, _VP, _VP, c_i64, _VP],

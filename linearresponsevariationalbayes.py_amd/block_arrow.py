@@ -93,14 +93,31 @@ def _half_border(chol, Hx, G, K):
     return U.reshape(R, 2 * K * G)
 
 
-def block_arrow_to_free(cf, j1, j2, n_global, G, K):
+def block_arrow_to_free(cf, j1, j2, n_global, G, K, dense=None):
     """The pieces of `glmm_slopes_closed_forms` in FREE coordinates for an element-wise packing (j1 = d eta / d theta, j2 = its
-    second derivative, both D-vectors): (grad, Hgg, rows, Hx, loc)."""
+    second derivative, both D-vectors): (grad, Hgg, rows, Hx, loc).
+    dense = (lo, J, H2): the global coordinates lo .. lo + n - 1 are packed by a map with the dense n x n Jacobian J
+    (d eta / d theta) and second derivative H2 (n x n x n, [eta, theta, theta]) instead -- the log-Cholesky map of a positive
+    definite matrix; j1 must be 1 and j2 0 there.  The global Jacobian is then block-diagonal with this one dense block, and
+    its second-order term enters the global block only."""
     g, ng = cf['grad'], n_global
     jg = j1[:ng]
     Hgg = cf['Hgg'] * jg[:, None] * jg[None, :] + np.diag(g[:ng] * j2[:ng])
     rows = cf['rows']
     Hx = None if cf['Hx'] is None else cf['Hx'] * jg[rows][:, None] * j1[ng:][None, :]
+    if dense is not None:
+        lo, J, H2 = dense
+        sl = slice(lo, lo + J.shape[0])
+        Hgg[:, sl] = Hgg[:, sl] @ J
+        Hgg[sl, :] = J.T @ Hgg[sl, :]
+        Hgg[sl, sl] += np.einsum('i,ipq->pq', g[sl], H2)
+        g = g.copy()
+        g[sl] = J.T @ g[sl]
+        if Hx is not None:
+            at = np.flatnonzero((rows >= lo) & (rows < lo + J.shape[0]))       # the block's coordinates among the coupled rows
+            if at.size != J.shape[0]:
+                raise ValueError('the dense block must lie within the coupled rows')
+            Hx[at] = J.T @ Hx[at]
     jl = _to_groups(j1[ng:], G, K)[:, :, 0]
     dl = _to_groups(g[ng:] * j2[ng:], G, K)[:, :, 0]
     loc = cf['loc'] * jl[:, :, None] * jl[:, None, :]
@@ -208,7 +225,7 @@ def block_arrow_solve_by_phases(R, n_global, rows, s, forward, schur_solve, back
     R = np.asarray(R, dtype=np.float64)
     vec = R.ndim == 1
     rows, s = np.asarray(rows), np.asarray(s, dtype=np.float64)
-    ng, K = int(n_global), int(n_global) - len(rows)               # n_global = 2 P + 4 K, len(rows) = 2 P + 3 K
+    ng, K = int(n_global), int(n_global) - len(rows)               # the K rows i_mu are the global rows that do not couple
     R2 = R.reshape(R.shape[0], -1)
     if K < 1 or (R2.shape[0] - ng) % (2 * K) or R2.shape[0] <= ng:
         raise ValueError('R must have n_global + 2 G K rows')
@@ -230,7 +247,7 @@ def unpack_group_cov(buf, P, K):
     return buf[:, :K * K].reshape(-1, K, K).copy(), np.ascontiguousarray(buf[:, K * K:].reshape(-1, K, P).transpose(0, 2, 1))
 
 
-def block_arrow_group_cov_by_phases(n_global, rows, P, K, s, schur_solve, group_blocks):
+def block_arrow_group_cov_by_phases(n_global, rows, P, K, s, schur_solve, group_blocks, n_closed=None):
     """The blocks of H^-1 that predictions need, where the local factor is held by somebody else (the device, or a numpy
     restatement of it) as L_g and U_g = L_g^-1 C_g with Hx[r, l] = s_r C_g[l, r] (`block_arrow_solve_by_phases`):
 
@@ -238,11 +255,14 @@ def block_arrow_group_cov_by_phases(n_global, rows, P, K, s, schur_solve, group_
         group_blocks(W: R x R, s) -> (G + 1) x (K K + K P): row g = [(A_g^-1 + Y_g W Y_g^T)[:K, :K] | -(Y_g W)[:K, :P]],
                                      Y_g = L_g^-T (U_g diag(s)); row G = the pseudo-group [W[mu, mu] | W[mu, :P]]
 
+    n_closed: the closed columns behind [m | i_beta] among the coupled rows (None: the 3 K of the independent-effects models).
+
     Returns (cov_beta P x P, the buffer)."""
     rows, s = np.asarray(rows), np.asarray(s, dtype=np.float64)
     R = len(rows)
-    if R != 2 * P + 3 * K or s.shape != (R,):
-        raise ValueError('expected the {} coupled rows and their scaling'.format(2 * P + 3 * K))
+    want = 2 * P + (3 * K if n_closed is None else int(n_closed))
+    if R != want or s.shape != (R,):
+        raise ValueError('expected the {} coupled rows and their scaling'.format(want))
     E = np.zeros((int(n_global), R))
     E[rows, np.arange(R)] = 1.0
     W = np.ascontiguousarray(np.asarray(schur_solve(E), dtype=np.float64).reshape(int(n_global), R)[rows])
@@ -250,12 +270,12 @@ def block_arrow_group_cov_by_phases(n_global, rows, P, K, s, schur_solve, group_
     return W[:P, :P].copy(), buf
 
 
-def _host_group_blocks(chol, U3, P, K):
+def _host_group_blocks(chol, U3, P, K, mu=None):
     """group_blocks of `block_arrow_group_cov_by_phases` in numpy from (L, 1 / diag L) of `_local_chol` and U3 (R x 2 K x G: slab i is
-    row i of L_g^-1 C_g for every group)."""
+    row i of L_g^-1 C_g for every group).  mu: where the means of mu_k sit among the coupled rows (None: 2 P + 3 k)."""
     L, dinv = chol
     R, G = U3.shape[0], U3.shape[2]
-    mu = 2 * P + 3 * np.arange(K)
+    mu = 2 * P + 3 * np.arange(K) if mu is None else np.asarray(mu)
 
     def group_blocks(W, s):
         Y = [U3[:, i] * s[:, None] for i in range(2 * K)]
@@ -278,12 +298,12 @@ def _host_group_blocks(chol, U3, P, K):
     return group_blocks
 
 
-def block_arrow_group_cov(Hgg, rows, Hx, loc, P, K, population=False):
+def block_arrow_group_cov(Hgg, rows, Hx, loc, P, K, population=False, mu=None):
     """(cov_beta P x P, cov_u G x K x K, cov_beta_u G x P x K): the blocks of H^-1 between the means of beta and the means e_g. of
     every group's effects, from the pieces of the block arrow -- O(G K R^2 + n_global^3), no dense matrix.  With
     Y_g = A_g^-1 C_g^T (2 K x R) and W = (S^-1)[rows, rows]:  Cov(rows, l_g) = -W Y_g^T,  Cov(l_g, l_g) = A_g^-1 + Y_g W Y_g^T.
     population=True appends the pseudo-group G of a population-level prediction (u = mu): cov_u[G] = W[mu, mu],
-    cov_beta_u[G] = W[:P, mu]."""
+    cov_beta_u[G] = W[:P, mu].  mu: where the means of mu_k sit among the coupled rows (None: 2 P + 3 k of R = 2 P + 3 K)."""
     ng, G = Hgg.shape[0], loc.shape[0]
     R = len(rows)
     chol = _local_chol(loc)
@@ -292,7 +312,8 @@ def block_arrow_group_cov(Hgg, rows, Hx, loc, P, K, population=False):
     S[np.ix_(rows, rows)] -= U @ U.T
     Ls = np.linalg.cholesky(0.5 * (S + S.T))
     cov_beta, buf = block_arrow_group_cov_by_phases(ng, rows, P, K, np.ones(R), lambda rhs: sp_linalg.cho_solve((Ls, True), rhs),
-                                                    _host_group_blocks(chol, U.reshape(R, 2 * K, G), P, K))
+                                                    _host_group_blocks(chol, U.reshape(R, 2 * K, G), P, K, mu),
+                                                    n_closed=None if mu is None else R - 2 * P)
     cov_u, cov_bu = unpack_group_cov(buf, P, K)
     return (cov_beta, cov_u, cov_bu) if population else (cov_beta, cov_u[:G], cov_bu[:G])
 

@@ -320,6 +320,75 @@ int launch_glmm_slopes_schur_rows(lrvb_ctx* c, int Kz, const double* gsum, const
     });
 }
 
+// ---- elimination with a dense closed border (lrvb_glmm_arrow_schur) -----------------------------------------
+// The kernel above with the closed border generalised: R = 2 P + NC coupled coordinates [m (P) | v (P) | NC closed columns in the
+// caller's order], and the closed entries of group g affine in its K-vector d_g,
+//   closed_g[i][c] = A0[i][c] + sum_l A1[i][l][c] d_gl      (A0: 2 K x NC, A1: 2 K x K x NC, row-major, shared by all groups),
+// so that G K doubles of d cross the bus and not G 2 K NC of closed rows.  The two tables and d_g are staged in LDS (at most
+// 8 x 16 + 8 x 4 x 16 + 4 doubles) by the waves 1..3 while thread 0 of wave 0 factors the block (gs_local_chol: the same L, bit
+// for bit); thread c then forms column c of the 2 K border rows -- the group sums for c < 2 P, the affine form in the order
+// l = 0 .. K - 1 for the closed columns, both times the chain factor -- and takes it through the forward substitution.  The
+// closed columns read LDS only: the tables as a broadcast per (i, l) row, consecutive threads consecutive doubles.
+constexpr int GSA_NCMAX = 16;               // closed columns: K + 1 + K (K + 1) / 2 = 15 at K = 4
+
+template <int KZ>
+__global__ __launch_bounds__(256)
+void glmm_arrow_schur_rows_kernel(i64 G, int P, int NC, const double* __restrict__ gsum, const double* __restrict__ loc /* G x K (2 K + 1) */,
+                                  const double* __restrict__ scale /* G x 2 K */, const double* __restrict__ dloc /* G x K */,
+                                  const double* __restrict__ A0 /* 2 K x NC */, const double* __restrict__ A1 /* 2 K x K x NC */,
+                                  double* __restrict__ U, int ldu, int* __restrict__ bad)
+{
+    constexpr int K2 = 2 * KZ, NT = KZ * (K2 + 1), nsc = K2 + NT;
+    __shared__ double Ls[K2 * K2], fs[K2], ds[KZ], A0s[K2 * GSA_NCMAX], A1s[K2 * KZ * GSA_NCMAX];
+    const i64 g = blockIdx.x;
+    if (g >= G) return;
+    const int ncol = nsc + 4 * KZ * P, R = 2 * P + NC;
+    const int tid = threadIdx.x;
+    if (tid == 0 && !gs_local_chol<K2>(loc + g * NT, Ls)) *bad = 1;
+    if (tid >= 64) {
+        const int t = tid - 64;
+        if (t < K2) fs[t] = scale[g * K2 + t];
+        if (t < KZ) ds[t] = dloc[g * KZ + t];
+        for (int q = t; q < K2 * NC; q += 192) A0s[q] = A0[q];
+        for (int q = t; q < K2 * KZ * NC; q += 192) A1s[q] = A1[q];
+    }
+    __syncthreads();
+    const double* gs = gsum + g * ncol + nsc;
+    for (int c = tid; c < R; c += 256) {
+        double u[K2];
+#pragma unroll
+        for (int i = 0; i < K2; ++i) {
+            const int k = i < KZ ? i : i - KZ;
+            double ce;
+            if (c < P) ce = gs[((i < KZ ? 0 : KZ) + k) * P + c];
+            else if (c < 2 * P) ce = gs[((i < KZ ? K2 : 3 * KZ) + k) * P + (c - P)];
+            else {
+                const int q = c - 2 * P;
+                ce = A0s[i * NC + q];
+#pragma unroll
+                for (int l = 0; l < KZ; ++l) ce += A1s[(i * KZ + l) * NC + q] * ds[l];
+            }
+            double t = fs[i] * ce;
+#pragma unroll
+            for (int j = 0; j < i; ++j) t -= Ls[i * K2 + j] * u[j];
+            u[i] = t / Ls[i * K2 + i];
+            U[(g * K2 + i) * ldu + c] = u[i];
+        }
+    }
+}
+
+int launch_glmm_arrow_schur_rows(lrvb_ctx* c, int Kz, int NC, const double* gsum, const double* loc, const double* scale, const double* dloc,
+                                 const double* A0, const double* A1, double* U, int ldu, int* bad) {
+    const i64 G = c->n_groups;
+    const dim3 grid((unsigned)G), block(256);
+    const int P = (int)c->P;
+    if (NC < Kz || NC > GSA_NCMAX) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "mixed model with a dense closed border: K <= NC <= 16");
+    return gs_with_K(Kz, "mixed model with a dense closed border: 1 <= K <= 4", [&](auto k) {
+        hipLaunchKernelGGL(glmm_arrow_schur_rows_kernel<decltype(k)::value>, grid, block, 0, c->stream, G, P, NC, gsum, loc, scale, dloc, A0, A1,
+                           U, ldu, bad);
+    });
+}
+
 // ---- the two substitution passes of the device-resident block-arrow solve ---------------------------------
 // One workgroup per group.  Thread 0 re-derives L_g from the resident copy of the uploaded block (gs_local_chol: the L that
 // U_g = L_g^-1 C_g was formed with) into LDS; thread t then owns the columns q = t, t + blockDim.x, .. of the group's 2 K x Q
@@ -702,14 +771,105 @@ void glmm_slopes_group_cov_kernel(i64 G, int P, const double* __restrict__ loc /
     }
 }
 
-int launch_glmm_slopes_group_cov(lrvb_ctx* c, int Kz, const double* loc, const double* U, int ldu, const double* W, const double* s,
+// The same for a factor of lrvb_glmm_arrow_schur: R = 2 P + NC coupled rows, the LDS rows sized for
+// R <= 2 x 64 + 16, and the means of mu in the FIRST K closed columns (rows 2 P + k of W) for the pseudo-group.  A kernel of its
+// own, so that the one above keeps its text and its machine code.
+constexpr int GSA_RMAX = 2 * 64 + GSA_NCMAX;
+
+template <int KZ>
+__global__ __launch_bounds__(256)
+void glmm_arrow_group_cov_kernel(i64 G, int P, int NC, const double* __restrict__ loc /* G x K (2 K + 1) */, const double* __restrict__ U,
+                                 int ldu, const double* __restrict__ W /* R x R */, const double* __restrict__ s /* R */,
+                                 double* __restrict__ out /* (G + 1) x (K K + K P) */)
+{
+    constexpr int K2 = 2 * KZ, NT = KZ * (K2 + 1), KK = KZ * KZ;
+    __shared__ double Ls[K2 * K2], Ys[KZ * GSA_RMAX], Es[KZ * GSA_RMAX], Ai[KK];
+    const i64 g = blockIdx.x;
+    if (g > G) return;
+    const int R = 2 * P + NC, ncg = KK + KZ * P;
+    const int tid = threadIdx.x;
+    double* og = out + g * ncg;
+    if (g == G) {
+        for (int t = tid; t < ncg; t += 256) {
+            if (t < KK) { const int k = t / KZ, l = t - k * KZ; og[t] = W[(i64)(2 * P + k) * R + 2 * P + l]; }
+            else { const int u = t - KK, k = u / P, j = u - k * P; og[t] = W[(i64)(2 * P + k) * R + j]; }
+        }
+        return;
+    }
+    if (tid == 0) gs_local_chol<K2>(loc + g * NT, Ls);
+    __syncthreads();
+    for (int c = tid; c < R; c += 256) {
+        double y[K2];
+        const double sc = s[c];
+#pragma unroll
+        for (int i = 0; i < K2; ++i) y[i] = U[(g * K2 + i) * ldu + c] * sc;
+#pragma unroll
+        for (int i = K2 - 1; i >= 0; --i) {
+            double v = y[i];
+#pragma unroll
+            for (int j = i + 1; j < K2; ++j) v -= Ls[j * K2 + i] * y[j];
+            y[i] = v / Ls[i * K2 + i];
+        }
+#pragma unroll
+        for (int k = 0; k < KZ; ++k) Ys[k * GSA_RMAX + c] = y[k];
+    }
+    if (tid >= 192 && tid < 192 + KZ) {
+        const int k = tid - 192;
+        double x[K2];
+#pragma unroll
+        for (int i = 0; i < K2; ++i) {
+            double v = i == k ? 1.0 : 0.0;
+#pragma unroll
+            for (int j = 0; j < i; ++j) v -= Ls[i * K2 + j] * x[j];
+            x[i] = v / Ls[i * K2 + i];
+        }
+#pragma unroll
+        for (int i = K2 - 1; i >= 0; --i) {
+            double v = x[i];
+#pragma unroll
+            for (int j = i + 1; j < K2; ++j) v -= Ls[j * K2 + i] * x[j];
+            x[i] = v / Ls[i * K2 + i];
+        }
+#pragma unroll
+        for (int l = 0; l < KZ; ++l) Ai[l * KZ + k] = x[l];
+    }
+    __syncthreads();
+    for (int c = tid; c < R; c += 256) {
+        double acc[KZ];
+#pragma unroll
+        for (int k = 0; k < KZ; ++k) acc[k] = 0.0;
+        for (int cp = 0; cp < R; ++cp) {
+            const double w = W[(i64)cp * R + c];
+#pragma unroll
+            for (int k = 0; k < KZ; ++k) acc[k] += Ys[k * GSA_RMAX + cp] * w;
+        }
+#pragma unroll
+        for (int k = 0; k < KZ; ++k) {
+            Es[k * GSA_RMAX + c] = acc[k];
+            if (c < P) og[KK + k * P + c] = -acc[k];
+        }
+    }
+    __syncthreads();
+    if (tid < KK) {
+        const int k = tid / KZ, l = tid - k * KZ;
+        double acc = 0.0;
+        for (int c = 0; c < R; ++c) acc += Es[k * GSA_RMAX + c] * Ys[l * GSA_RMAX + c];
+        og[tid] = Ai[tid] + acc;
+    }
+}
+
+// NC = 0: the legacy layout of lrvb_glmm_slopes_group_cov (3 K closed columns, the mean of mu_k at 2 P + 3 k).
+int launch_glmm_slopes_group_cov(lrvb_ctx* c, int Kz, int NC, const double* loc, const double* U, int ldu, const double* W, const double* s,
                                  double* out) {
     const i64 G = c->n_groups;
     const dim3 grid((unsigned)(G + 1)), block(256);
     const int P = (int)c->P;
     if (P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "mixed model with slopes: P <= 64");
+    if (NC != 0 && (NC < Kz || NC > GSA_NCMAX)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "mixed model with a dense closed border: K <= NC <= 16");
     return gs_with_K(Kz, "mixed model with slopes: 1 <= K <= 4", [&](auto k) {
-        hipLaunchKernelGGL(glmm_slopes_group_cov_kernel<decltype(k)::value>, grid, block, 0, c->stream, G, P, loc, U, ldu, W, s, out);
+        constexpr int KK = decltype(k)::value;
+        if (NC == 0) hipLaunchKernelGGL(glmm_slopes_group_cov_kernel<KK>, grid, block, 0, c->stream, G, P, loc, U, ldu, W, s, out);
+        else hipLaunchKernelGGL(glmm_arrow_group_cov_kernel<KK>, grid, block, 0, c->stream, G, P, NC, loc, U, ldu, W, s, out);
     });
 }
 

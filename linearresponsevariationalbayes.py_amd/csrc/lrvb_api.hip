@@ -2764,28 +2764,41 @@ extern "C" int lrvb_glmm_terms(lrvb_ctx* c, const double* mean, const double* va
     return LRVB_OK;
 }
 
-// The elimination behind both Schur entries: M = sum_g C_g^T A_g^-1 C_g = U^T U from the resident group sums.  The intercept's entry
-// (K = 1: [a11, a12, a22] is the upper triangle of its 2 x 2 block, G x 6 its G x 2 x 3 closed rows) keeps all
-// of it in c->work1, [flag 8 | blocks up(NT G) | chain factors up(2 K G) | closed rows up(6 K G) | U (2 K G x ldu) | M (R R)]; with
-// `keep` the blocks as uploaded and U = L^-1 C go to c->glmms_fac, [blocks | U], where they outlive the call (the solve passes, the
-// group covariance), and work1 holds the rest in the same order.
-static int glmms_schur(lrvb_ctx* c, i64 K, bool keep, const double* blocks, const double* border_scale, const double* closed_rows,
+// The elimination behind the Schur entries: M = sum_g C_g^T A_g^-1 C_g = U^T U from the resident group sums, over R = 2 P + NC
+// coupled coordinates.  The intercept's entry (K = 1: [a11, a12, a22] is the upper triangle of its 2 x 2 block, G x 6 its
+// G x 2 x 3 closed rows) keeps all of it in c->work1,
+// [flag 8 | blocks up(NT G) | chain factors up(2 K G) | closed part | U (2 K G x ldu) | M (R R)]; with `keep` the blocks as uploaded
+// and U = L^-1 C go to c->glmms_fac, [blocks | U], where they outlive the call (the solve passes, the group covariance), and work1
+// holds the rest in the same order.  The closed part is the G x 2 K x 3 closed rows of the legacy layout (NC = 3 K), or, with
+// tables (lrvb_glmm_arrow_schur), [d up(G K) | A0 up(2 K NC) | A1 up(2 K K NC)].
+struct GlmmClosed { const double *rows, *d, *A0, *A1; };
+static int glmms_schur(lrvb_ctx* c, i64 K, i64 NC, bool keep, const double* blocks, const double* border_scale, const GlmmClosed& cl_in,
                        double* M_out, const char* not_posdef) {
-    const i64 P = c->P, G = c->n_groups, R = 2 * P + 3 * K, K2 = 2 * K, NT = K * (K2 + 1);
+    const i64 P = c->P, G = c->n_groups, R = 2 * P + NC, K2 = 2 * K, NT = K * (K2 + 1);
     const int ldu = (int)up(R);
     const i64 fac = up(NT * G) + K2 * G * ldu;
-    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(8 + up(K2 * G) + up(3 * K2 * G) + R * R + (keep ? 0 : fac))));
+    const i64 ncl = cl_in.rows ? up(3 * K2 * G) : up(G * K) + up(K2 * NC) + up(K2 * K * NC);
+    LRVB_TRY(buf_reserve(c, c->work1, (size_t)(8 + up(K2 * G) + ncl + R * R + (keep ? 0 : fac))));
     if (keep) LRVB_TRY(buf_reserve(c, c->glmms_fac, (size_t)fac));
     double* flag = c->work1.p;
     double* loc = keep ? c->glmms_fac.p : flag + 8;
     double* sc = keep ? flag + 8 : loc + up(NT * G); double* cl = sc + up(K2 * G);
-    double* U = keep ? loc + up(NT * G) : cl + up(3 * K2 * G);
-    double* Md = keep ? cl + up(3 * K2 * G) : U + K2 * G * ldu;
+    double* U = keep ? loc + up(NT * G) : cl + ncl;
+    double* Md = keep ? cl + ncl : U + K2 * G * ldu;
     LRVB_TRY(h2d(c, loc, blocks, (size_t)(NT * G)));
     LRVB_TRY(h2d(c, sc, border_scale, (size_t)(K2 * G)));
-    LRVB_TRY(h2d(c, cl, closed_rows, (size_t)(3 * K2 * G)));
     HIP_TRY(hipMemsetAsync(flag, 0, sizeof(double), c->stream));
-    LRVB_TRY(launch_glmm_slopes_schur_rows(c, (int)K, c->glmms.p + 3 * P * P, loc, sc, cl, U, ldu, reinterpret_cast<int*>(flag)));
+    const double* gsum = c->glmms.p + 3 * P * P;
+    if (cl_in.rows) {
+        LRVB_TRY(h2d(c, cl, cl_in.rows, (size_t)(3 * K2 * G)));
+        LRVB_TRY(launch_glmm_slopes_schur_rows(c, (int)K, gsum, loc, sc, cl, U, ldu, reinterpret_cast<int*>(flag)));
+    } else {
+        double* A0 = cl + up(G * K); double* A1 = A0 + up(K2 * NC);
+        LRVB_TRY(h2d(c, cl, cl_in.d, (size_t)(G * K)));
+        LRVB_TRY(h2d(c, A0, cl_in.A0, (size_t)(K2 * NC)));
+        LRVB_TRY(h2d(c, A1, cl_in.A1, (size_t)(K2 * K * NC)));
+        LRVB_TRY(launch_glmm_arrow_schur_rows(c, (int)K, (int)NC, gsum, loc, sc, cl, A0, A1, U, ldu, reinterpret_cast<int*>(flag)));
+    }
     LRVB_TRY(launch_gemm(c, true, false, R, R, K2 * G, 1.0, U, ldu, U, ldu, 0.0, Md, R));
     int bad = 0;
     LRVB_TRY(read_flag(c, flag, &bad));
@@ -2799,40 +2812,59 @@ extern "C" int lrvb_glmm_schur(lrvb_ctx* c, const double* local_2x2, const doubl
     if (!local_2x2 || !border_scale || !closed_rows || !M_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
     if (c->n_groups <= 0 || !c->glmms_valid || c->glmms_K != 0) LRVB_FAIL(LRVB_ERR_STATE, "no group sums resident: call lrvb_glmm_terms first");
     LRVB_TRY(check_len(G_in, c->n_groups, "local blocks"));
-    return glmms_schur(c, 1, false, local_2x2, border_scale, closed_rows, M_out,
+    return glmms_schur(c, 1, 3, false, local_2x2, border_scale, GlmmClosed{closed_rows, nullptr, nullptr, nullptr}, M_out,
                        "a 2 x 2 local block of the logistic mixed model is not positive definite");
+}
+
+// The K-effect Schur entries: the checks, the elimination, and the factor left resident with its coupled layout recorded.
+static int glmms_schur_keep(lrvb_ctx* c, const double* local_blocks, const double* border_scale, const GlmmClosed& cl, int64_t G_in, int64_t K,
+                            int64_t NC, double* M_out, const char* not_posdef) {
+    if (K < 1 || K > 4) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 4 random effects per group (got %lld)", (long long)K);
+    if (NC < K || NC > 16) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "K to 16 closed columns (got %lld)", (long long)NC);
+    if (c->n_groups <= 0 || !c->glmms_valid || c->glmms_K != K)
+        LRVB_FAIL(LRVB_ERR_STATE, "no group sums of %lld effects resident: call lrvb_glmm_slopes_terms first", (long long)K);
+    LRVB_TRY(check_len(G_in, c->n_groups, "local blocks"));
+    c->glmms_fac_valid = false; c->glmms_T_Q = 0; c->glmms_gcov_rows = 0;
+    LRVB_TRY(glmms_schur(c, K, NC, true, local_blocks, border_scale, cl, M_out, not_posdef));
+    c->glmms_fac_valid = true; c->glmms_fac_K = (int)K; c->glmms_fac_NC = (int)NC;
+    return LRVB_OK;
 }
 
 extern "C" int lrvb_glmm_slopes_schur(lrvb_ctx* c, const double* local_blocks, const double* border_scale, const double* closed_rows,
                                       int64_t G_in, int64_t K, double* M_out) {
     LRVB_TRY(ctx_bind(c));
     if (!local_blocks || !border_scale || !closed_rows || !M_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
-    if (K < 1 || K > 4) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 4 random effects per group (got %lld)", (long long)K);
-    if (c->n_groups <= 0 || !c->glmms_valid || c->glmms_K != K)
-        LRVB_FAIL(LRVB_ERR_STATE, "no group sums of %lld effects resident: call lrvb_glmm_slopes_terms first", (long long)K);
-    LRVB_TRY(check_len(G_in, c->n_groups, "local blocks"));
-    c->glmms_fac_valid = false; c->glmms_T_Q = 0; c->glmms_gcov_rows = 0;
-    LRVB_TRY(glmms_schur(c, K, true, local_blocks, border_scale, closed_rows, M_out,
-                         "a local block of the logistic mixed model with slopes is not positive definite"));
-    c->glmms_fac_valid = true; c->glmms_fac_K = (int)K;
-    return LRVB_OK;
+    return glmms_schur_keep(c, local_blocks, border_scale, GlmmClosed{closed_rows, nullptr, nullptr, nullptr}, G_in, K, K < 1 ? K : 3 * K, M_out,
+                            "a local block of the logistic mixed model with slopes is not positive definite");
+}
+
+extern "C" int lrvb_glmm_arrow_schur(lrvb_ctx* c, const double* local_blocks, const double* border_scale, const double* d_loc, const double* A0,
+                                     const double* A1, int64_t G_in, int64_t K, int64_t NC, double* M_out) {
+    LRVB_TRY(ctx_bind(c));
+    if (!local_blocks || !border_scale || !d_loc || !A0 || !A1 || !M_out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    return glmms_schur_keep(c, local_blocks, border_scale, GlmmClosed{nullptr, d_loc, A0, A1}, G_in, K, NC, M_out,
+                            "a local block of the mixed model with correlated effects is not positive definite");
 }
 
 // The two device passes of the block-arrow solve around the host's Schur solve.  c->glmms_fac holds the
-// blocks as uploaded and U = L^-1 C of the last lrvb_glmm_slopes_schur; c->glmms_T keeps T = L^-1 R_local between the passes.
-static int glmm_slopes_solve_check(lrvb_ctx* c, const void* in, const void* out, int64_t G_in, int64_t K, int64_t Q) {
+// blocks as uploaded and U = L^-1 C of the last Schur entry that keeps its factor, over R = 2 P + NC coupled rows; c->glmms_T keeps
+// T = L^-1 R_local between the passes.  The legacy entries ask for NC = 3 K, the arrow entries for the caller's NC.
+static int glmm_slopes_solve_check(lrvb_ctx* c, const void* in, const void* out, int64_t G_in, int64_t K, int64_t NC, int64_t Q, bool arrow) {
     if (!in || !out) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
     if (K < 1 || K > 4) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 4 random effects per group (got %lld)", (long long)K);
+    if (NC < K || NC > 16) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "K to 16 closed columns (got %lld)", (long long)NC);
     if (Q < 1) LRVB_FAIL(LRVB_ERR_INVALID, "Q must be positive");
-    if (c->n_groups <= 0 || !c->glmms_valid || !c->glmms_fac_valid || c->glmms_fac_K != K)
+    if (c->n_groups <= 0 || !c->glmms_valid || !c->glmms_fac_valid || c->glmms_fac_K != K || c->glmms_fac_NC != NC) {
+        if (arrow) LRVB_FAIL(LRVB_ERR_STATE, "no factor of %lld effects and %lld closed columns resident: call lrvb_glmm_arrow_schur first",
+                             (long long)K, (long long)NC);
         LRVB_FAIL(LRVB_ERR_STATE, "no factor of %lld effects resident: call lrvb_glmm_slopes_schur first", (long long)K);
+    }
     return check_len(G_in, c->n_groups, "groups of the right-hand side");
 }
 
-extern "C" int lrvb_glmm_slopes_solve_forward(lrvb_ctx* c, const double* R_local, int64_t G_in, int64_t K, int64_t Q, double* red_out) {
-    LRVB_TRY(ctx_bind(c));
-    LRVB_TRY(glmm_slopes_solve_check(c, R_local, red_out, G_in, K, Q));
-    const i64 P = c->P, G = c->n_groups, R = 2 * P + 3 * K, K2 = 2 * K, NT = K * (K2 + 1);
+static int glmms_solve_forward(lrvb_ctx* c, const double* R_local, int64_t G_in, int64_t K, int64_t NC, int64_t Q, double* red_out, bool arrow) {
+    LRVB_TRY(glmm_slopes_solve_check(c, R_local, red_out, G_in, K, NC, Q, arrow));
+    const i64 P = c->P, G = c->n_groups, R = 2 * P + NC, K2 = 2 * K, NT = K * (K2 + 1);
     const i64 ldu = up(R);
     c->glmms_T_Q = 0;
     LRVB_TRY(buf_reserve(c, c->glmms_T, (size_t)(K2 * G * Q)));
@@ -2846,12 +2878,11 @@ extern "C" int lrvb_glmm_slopes_solve_forward(lrvb_ctx* c, const double* R_local
     return LRVB_OK;
 }
 
-extern "C" int lrvb_glmm_slopes_solve_back(lrvb_ctx* c, const double* x_coupled, int64_t G_in, int64_t K, int64_t Q, double* X_local_out) {
-    LRVB_TRY(ctx_bind(c));
-    LRVB_TRY(glmm_slopes_solve_check(c, x_coupled, X_local_out, G_in, K, Q));
+static int glmms_solve_back(lrvb_ctx* c, const double* x_coupled, int64_t G_in, int64_t K, int64_t NC, int64_t Q, double* X_local_out, bool arrow) {
+    LRVB_TRY(glmm_slopes_solve_check(c, x_coupled, X_local_out, G_in, K, NC, Q, arrow));
     if (c->glmms_T_Q == 0) LRVB_FAIL(LRVB_ERR_STATE, "no forward pass resident: call lrvb_glmm_slopes_solve_forward first");
     LRVB_TRY(check_len(Q, c->glmms_T_Q, "columns (those of the forward pass)"));
-    const i64 P = c->P, G = c->n_groups, R = 2 * P + 3 * K, K2 = 2 * K, NT = K * (K2 + 1);
+    const i64 P = c->P, G = c->n_groups, R = 2 * P + NC, K2 = 2 * K, NT = K * (K2 + 1);
     const i64 ldu = up(R);
     LRVB_TRY(buf_reserve(c, c->work1, (size_t)(up(R * Q) + K2 * G * Q)));
     double* loc = c->glmms_fac.p; double* U = loc + up(NT * G); double* xs = c->work1.p; double* W = xs + up(R * Q);
@@ -2859,6 +2890,27 @@ extern "C" int lrvb_glmm_slopes_solve_back(lrvb_ctx* c, const double* x_coupled,
     LRVB_TRY(launch_gemm(c, false, false, K2 * G, Q, R, 1.0, U, ldu, xs, Q, 0.0, W, Q));      // W_g = U_g x
     LRVB_TRY(launch_glmm_slopes_solve(c, (int)K, true, Q, loc, c->glmms_T.p, W));
     return d2h(c, X_local_out, W, (size_t)(K2 * G * Q));
+}
+
+extern "C" int lrvb_glmm_slopes_solve_forward(lrvb_ctx* c, const double* R_local, int64_t G_in, int64_t K, int64_t Q, double* red_out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_solve_forward(c, R_local, G_in, K, K < 1 ? K : 3 * K, Q, red_out, false);
+}
+
+extern "C" int lrvb_glmm_slopes_solve_back(lrvb_ctx* c, const double* x_coupled, int64_t G_in, int64_t K, int64_t Q, double* X_local_out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_solve_back(c, x_coupled, G_in, K, K < 1 ? K : 3 * K, Q, X_local_out, false);
+}
+
+extern "C" int lrvb_glmm_arrow_solve_forward(lrvb_ctx* c, const double* R_local, int64_t G_in, int64_t K, int64_t NC, int64_t Q, double* red_out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_solve_forward(c, R_local, G_in, K, NC, Q, red_out, true);
+}
+
+extern "C" int lrvb_glmm_arrow_solve_back(lrvb_ctx* c, const double* x_coupled, int64_t G_in, int64_t K, int64_t NC, int64_t Q,
+                                          double* X_local_out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_solve_back(c, x_coupled, G_in, K, NC, Q, X_local_out, true);
 }
 
 // ---- weight influence of every mixed model (k_glmm.hip, k_glmm_slopes.hip) --------------------------------------------------------
@@ -3000,13 +3052,12 @@ extern "C" int lrvb_glmm_binomial_group_influence(lrvb_ctx* c, const double* mea
 }
 
 // ---- group blocks of H^-1 and predictions with their linear-response variance (k_glmm_slopes.hip) ----------
-extern "C" int lrvb_glmm_slopes_group_cov(lrvb_ctx* c, const double* W, const double* s, int64_t P_in, int64_t G_in, int64_t K,
-                                          double* out) {
-    LRVB_TRY(ctx_bind(c));
-    LRVB_TRY(glmm_slopes_solve_check(c, W, s, G_in, K, 1));
+static int glmms_group_cov(lrvb_ctx* c, const double* W, const double* s, int64_t P_in, int64_t G_in, int64_t K, int64_t NC, bool arrow,
+                           double* out) {
+    LRVB_TRY(glmm_slopes_solve_check(c, W, s, G_in, K, NC, 1, arrow));
     LRVB_TRY(check_len(P_in, c->P, "columns of the design"));
     if (c->P > 64) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the mixed models need P <= 64 (got %lld)", (long long)c->P);
-    const i64 P = c->P, G = c->n_groups, R = 2 * P + 3 * K, K2 = 2 * K, NT = K * (K2 + 1), ncg = K * K + K * P;
+    const i64 P = c->P, G = c->n_groups, R = 2 * P + NC, K2 = 2 * K, NT = K * (K2 + 1), ncg = K * K + K * P;
     const int ldu = (int)up(R);
     c->glmms_gcov_rows = 0;
     LRVB_TRY(buf_reserve(c, c->work1, (size_t)(up(R * R) + up(R))));
@@ -3015,10 +3066,22 @@ extern "C" int lrvb_glmm_slopes_group_cov(lrvb_ctx* c, const double* W, const do
     LRVB_TRY(h2d(c, Wd, W, (size_t)(R * R)));
     LRVB_TRY(h2d(c, sd, s, (size_t)R));
     const double* loc = c->glmms_fac.p; const double* U = loc + up(NT * G);
-    LRVB_TRY(launch_glmm_slopes_group_cov(c, (int)K, loc, U, ldu, Wd, sd, c->glmms_gcov.p));
+    LRVB_TRY(launch_glmm_slopes_group_cov(c, (int)K, arrow ? (int)NC : 0, loc, U, ldu, Wd, sd, c->glmms_gcov.p));
     if (out) LRVB_TRY(d2h(c, out, c->glmms_gcov.p, (size_t)((G + 1) * ncg)));
     c->glmms_gcov_rows = G + 1;
     return LRVB_OK;
+}
+
+extern "C" int lrvb_glmm_slopes_group_cov(lrvb_ctx* c, const double* W, const double* s, int64_t P_in, int64_t G_in, int64_t K,
+                                          double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_group_cov(c, W, s, P_in, G_in, K, K < 1 ? K : 3 * K, false, out);
+}
+
+extern "C" int lrvb_glmm_arrow_group_cov(lrvb_ctx* c, const double* W, const double* s, int64_t P_in, int64_t G_in, int64_t K, int64_t NC,
+                                         double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_group_cov(c, W, s, P_in, G_in, K, NC, true, out);
 }
 
 // The predict entries: the checks of glmms_terms in its order (e and r may carry the pseudo-group: Gp = G or G + 1 rows), the

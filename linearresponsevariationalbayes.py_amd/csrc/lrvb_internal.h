@@ -134,8 +134,10 @@ struct lrvb_ctx {
     DevBuf gz; i64 gz_n = 0; int gz_K = 0;
     DevBuf glmms; bool glmms_valid = false; int glmms_K = 0;
     // what lrvb_glmm_slopes_schur leaves for lrvb_glmm_slopes_solve_forward / _back: [uploaded local blocks (up(K (2 K + 1) G)) |
-    // U (2 K G x ld(R))] of glmms_fac_K effects, and T = L^-1 R_local (2 K G x glmms_T_Q; 0 = no forward pass yet)
-    DevBuf glmms_fac, glmms_T; bool glmms_fac_valid = false; int glmms_fac_K = 0; i64 glmms_T_Q = 0;
+    // U (2 K G x ld(R))] of glmms_fac_K effects, and T = L^-1 R_local (2 K G x glmms_T_Q; 0 = no forward pass yet).
+    // glmms_fac_NC: the closed columns of the factor's coupled layout, R = 2 P + NC (3 K from lrvb_glmm_slopes_schur, the
+    // caller's NC from lrvb_glmm_arrow_schur): the solve and group-covariance entries of either family ask for theirs
+    DevBuf glmms_fac, glmms_T; bool glmms_fac_valid = false; int glmms_fac_K = 0, glmms_fac_NC = 0; i64 glmms_T_Q = 0;
     // what lrvb_glmm_slopes_group_cov leaves for the lrvb_glmm_*_predict entries: glmms_gcov_rows (G + 1; 0 = none) rows of
     // [Sigma_uu (K K) | Sigma_ubeta (K P)], the last one the pseudo-group of a population-level prediction.  It lives and dies with the factor
     DevBuf glmms_gcov; i64 glmms_gcov_rows = 0;
@@ -269,6 +271,9 @@ int  launch_glmm_poisson_scale_blocks(lrvb_ctx* c, double* Hb /* 3 x P x P, all 
 int  launch_glmm_slopes_schur_rows(lrvb_ctx* c, int K, const double* gsum, const double* loc /* G x K (2 K + 1) */,
                                    const double* scale /* G x 2 K */, const double* closed /* G x 2 K x 3 */,
                                    double* U /* 2 K G x ldu */, int ldu, int* bad);
+int  launch_glmm_arrow_schur_rows(lrvb_ctx* c, int K, int NC, const double* gsum, const double* loc /* G x K (2 K + 1) */,
+                                  const double* scale /* G x 2 K */, const double* dloc /* G x K */, const double* A0 /* 2 K x NC */,
+                                  const double* A1 /* 2 K x K x NC */, double* U /* 2 K G x ldu, ldu >= 2 P + NC */, int ldu, int* bad);
 int  launch_glmm_slopes_solve(lrvb_ctx* c, int K, bool back, i64 Q, const double* loc /* the blocks as uploaded */,
                               double* T /* G x 2 K x Q: forward in place; read by back */, double* W /* back only, in place */);
 int  launch_glmm_slopes_infl_rows(lrvb_ctx* c, const GlmmLik& lik, int K, const double* Z, i64 n0, i64 n1,
@@ -279,7 +284,8 @@ int  launch_glmm_slopes_infl_gsum(lrvb_ctx* c, const GlmmLik& lik, int K, const 
                                   const double* eg, const double* rg, double* gsum /* G x (2 K + 2 P), zeroed by the caller */,
                                   double* part /* 2 (2 K + 2 P) doubles per tile of glmm_num_tiles */);
 int  launch_glmm_slopes_infl_local(lrvb_ctx* c, int K, i64 Q, const double* S, const double* Al, double* out /* G x Q, += */);
-int  launch_glmm_slopes_group_cov(lrvb_ctx* c, int K, const double* loc /* the blocks as uploaded */, const double* U, int ldu,
+int  launch_glmm_slopes_group_cov(lrvb_ctx* c, int K, int NC /* 0: the legacy layout, 3 K closed columns */,
+                                  const double* loc /* the blocks as uploaded */, const double* U, int ldu,
                                   const double* W /* R x R */, const double* s /* R */, double* out /* (G + 1) x (K K + K P) */);
 int  launch_glmm_slopes_predict_rows(lrvb_ctx* c, const GlmmLik& lik, int K, const double* X /* the context's rows or new ones */,
                                      const double* Z, i64 n0, i64 n1, const int* gid, const double* m, const double* vb,

@@ -29,7 +29,9 @@ elimination left on the device (`block_arrow_solve_by_phases`, DESIGN.md section
 The host algebra of the block arrow is `block_arrow.py` (re-exported here); everything of the objective that is not a device
 entry is `_LogisticMixedModel`, which `LogisticGLMMObjective` (glmm.py) instantiates at K = 1.
 What the K-effect models share whatever their likelihood -- the layout, the Schur entry, the device-resident solve -- is `_SlopesArrow`,
-which `PoissonGLMMObjective` (glmm_poisson.py) inherits as well.
+which `PoissonGLMMObjective` (glmm_poisson.py) inherits as well.  The coupled layout itself sits behind
+four hooks of `_SlopesArrow` (`_coupled_rows`, `_coupled_scaling`, `_solve_entries`, `_group_cov_phases`), which `_CorrelatedArrow`
+(glmm_corr.py, DESIGN.md section 34: correlated effects, a dense closed border) replaces.
 """
 import numpy as np
 from scipy import special
@@ -215,7 +217,7 @@ class _LogisticMixedModel(DeclaredHypers):
         self.gh_x, self.gh_w = (None, None) if gh_deg is None else np.polynomial.hermite.hermgauss(int(gh_deg))
         self._declare_hyper('beta_prior_info', HyperVectorParam('beta_prior_info', 1, lb=0.0, val=np.array([float(beta_prior_info)])))
         self._declare_hyper('mu_prior', HyperVectorParam('mu_prior', 2, val=np.array(list(map(float, mu_prior)))))
-        self._declare_hyper('tau_prior', HyperVectorParam('tau_prior', 2, lb=0.0, val=np.array(list(map(float, tau_prior)))))
+        self._declare_effect_prior(tau_prior)
         self.ctx = DeviceContext(par.layout_blocks(), loss=self._loss, n_obs=self.n_obs, n_cols=self.P, device=device)
         self.ctx.set_data(_hip.SLOT_X, x)
         self._y = _hip.as_f64(y).ravel().copy()
@@ -241,11 +243,22 @@ class _LogisticMixedModel(DeclaredHypers):
     a0 = property(lambda self: float(self._hyper_vec('tau_prior')[0]))
     b0 = property(lambda self: float(self._hyper_vec('tau_prior')[1]))
 
+    def _declare_effect_prior(self, tau_prior):
+        """The hyper-parameter of the prior on the effects' precision: Gamma(a0, b0) on every tau_k."""
+        self._declare_hyper('tau_prior', HyperVectorParam('tau_prior', 2, lb=0.0, val=np.array(list(map(float, tau_prior)))))
+
+    def _n_global(self):
+        return 2 * self.P + 4 * self.K
+
+    def _split(self, eta):
+        """eta as (m, i_beta, e_mu, i_mu, the two pieces of q(precision), e G x K, i G x K)."""
+        return _split_eta(eta, self.P, self.K, self.G)
+
     def _index(self, par, names):
         """The layout must be the canonical one, in vector and in free coordinates, every coordinate packed element-wise
         (identity, or lb + exp).  `_layout` gives it: the (parameter, field, first, last coordinate) of every block, the message
         for a layout that differs, and the message for a parameter that holds more than these blocks."""
-        self.n_global = ng = 2 * self.P + 4 * self.K
+        self.n_global = ng = self._n_global()
         D = ng + 2 * self.G * self.K
         vi, fi = par.vector_indices_dict, par.free_indices_dict
         want, msg, msg_more = self._layout(par, names)
@@ -256,6 +269,9 @@ class _LogisticMixedModel(DeclaredHypers):
                     raise ValueError(msg)
         if par.vector_size() != D or par.free_size() != D:
             raise ValueError(msg_more)
+        self._index_packing(par)
+
+    def _index_packing(self, par):
         lb = []
         for blk in par.layout_blocks():
             if blk['kind'] != _hip.BLOCK_BOX or np.isfinite(blk['ub']) or blk['free_size'] != blk['vec_size']:
@@ -279,6 +295,20 @@ class _LogisticMixedModel(DeclaredHypers):
         j1 = np.where(self._bounded, eta - np.where(self._bounded, self._lb, 0.0), 1.0)
         return j1, np.where(self._bounded, j1, 0.0)
 
+    def _global_jac_T(self, C, eta):
+        """J_g^T C for the n_global leading rows C of a gradient or a cross Hessian (J_g = d eta_global / d theta_global)."""
+        jg = self._jac(eta)[0][:self.n_global]
+        return C * (jg if np.ndim(C) == 1 else jg[:, None])
+
+    def _grad_to_free(self, g, eta):
+        ng = self.n_global
+        return np.concatenate([self._global_jac_T(g[:ng], eta), g[ng:] * self._jac(eta)[0][ng:]])
+
+    def _arrow_to_free(self, cf, eta):
+        """(grad, Hgg, rows, Hx, loc) of the closed forms `cf` in free coordinates."""
+        j1, j2 = self._jac(eta)
+        return block_arrow_to_free(cf, j1, j2, self.n_global, self.G, self.K)
+
     def _push_state(self):
         w = self._w_res.changed(self.weights_par)
         if w is not None:
@@ -294,7 +324,7 @@ class _LogisticMixedModel(DeclaredHypers):
 
     def _point(self, eta):
         """The arguments of the terms entry at eta, the weights pushed: (m, v, e, r: G x K, nodes, weights)."""
-        _, ib, _, _, _, _, e, ig = _split_eta(eta, self.P, self.K, self.G)
+        _, ib, _, _, _, _, e, ig = self._split(eta)
         self._push_state()
         self._dev_factor_key = None                  # the terms entry drops the factor on the device
         return eta[:self.P], 1.0 / ib, e, 1.0 / ig, self.gh_x, self.gh_w
@@ -354,8 +384,7 @@ class _LogisticMixedModel(DeclaredHypers):
             eta = self._eta(x, is_free)
             cf = self._closed(eta)
             if is_free:
-                j1, j2 = self._jac(eta)
-                self._pieces = block_arrow_to_free(cf, j1, j2, self.n_global, self.G, self.K)
+                self._pieces = self._arrow_to_free(cf, eta)
             else:
                 self._pieces = (cf['grad'], cf['Hgg'], cf['rows'], cf['Hx'], cf['loc'])
             self._point_key = key
@@ -375,7 +404,7 @@ class _LogisticMixedModel(DeclaredHypers):
     def grad(self, x, is_free=True):
         eta = self._eta(x, is_free)
         g = self._closed(eta, True, False)['grad']
-        return g * self._jac(eta)[0] if is_free else g
+        return self._grad_to_free(g, eta) if is_free else g
 
     jacobian = grad
 
@@ -424,7 +453,7 @@ class _LogisticMixedModel(DeclaredHypers):
         g, Hgg, rows = cf['grad'], cf['Hgg'].copy(), cf['rows']
         loc_f = block_arrow_to_free(cf, j1, j2, ng, G, K)[4]
         if self._external is None:
-            _, ib, e_mu, _, a, b, e, ig = _split_eta(eta, P, K, G)
+            _, ib, e_mu, _, a, b, e, ig = self._split(eta)
             r = 1.0 / ig
             d = e - e_mu[None, :]
             ta, tb = 1.0 / b, -a / b ** 2
@@ -504,7 +533,7 @@ class _LogisticMixedModel(DeclaredHypers):
             S = np.asarray(chol.solve(np.ascontiguousarray(M.T))).reshape(ng + 2 * GK, -1)
         eta = self._eta(x, is_free)
         j1 = self._jac(eta)[0] if is_free else np.ones(eta.size)
-        _, ib, _, _, _, _, e, ig = _split_eta(eta, P, K, G)
+        _, ib, _, _, _, _, e, ig = self._split(eta)
         v, r = 1.0 / ib, 1.0 / ig
         chain = np.concatenate([j1[:P], -v * v * j1[P:2 * P], j1[ng:ng + GK], -(r * r).ravel() * j1[ng + GK:]])
         keep = np.concatenate([np.arange(2 * P), np.arange(ng, ng + 2 * GK)])
@@ -570,7 +599,7 @@ class _LogisticMixedModel(DeclaredHypers):
             raise NotImplementedError('the weight cross Hessian has local rows: use cross_hessian')
         eta = self._eta(val, is_free)
         C = self._prior_hyper(kind, eta[:self.n_global], 'cross')
-        return C * self._jac(eta)[0][:self.n_global, None] if is_free else C
+        return self._global_jac_T(C, eta) if is_free else C
 
     @_hip.host_blas
     def cross_hessian(self, hyper_par, val1, val1_is_free):
@@ -587,7 +616,7 @@ class _LogisticMixedModel(DeclaredHypers):
         GK = G * K
         x, gid = self._x, self._groups
         z = np.ones((N, 1)) if self._z is None else self._z
-        _, ib, _, _, _, _, e, ig = _split_eta(eta, P, K, G)
+        _, ib, _, _, _, _, e, ig = self._split(eta)
         v, r = 1.0 / ib, 1.0 / ig
         rho = x @ eta[:P] + np.sum(z * e[gid], axis=1)
         s = (x * x) @ v + np.sum(z * z * r[gid], axis=1)
@@ -643,6 +672,29 @@ class _SlopesArrow:
     def _schur(self, local_blocks, border_scale, closed_rows):
         return self.ctx.glmm_slopes_schur(local_blocks, border_scale, closed_rows)
 
+    # ---- the coupled layout of the device factor: what `_CorrelatedArrow` (glmm_corr.py) replaces -------------------------------
+    def _coupled_rows(self):
+        return coupled_rows(self.P, self.K)
+
+    def _coupled_scaling(self, eta):
+        """s: the border in free coordinates is Hx[r, l] = s_r C_g[l, r] for the device's C_g."""
+        dv = np.concatenate([np.ones(self.P), -1.0 / eta[self.P:2 * self.P] ** 2, np.ones(3 * self.K)])
+        return self._jac(eta)[0][self._coupled_rows()] * dv
+
+    def _solve_entries(self):
+        """(forward, back) of `block_arrow_solve_by_phases` on the resident factor."""
+        return self.ctx.glmm_slopes_solve_forward, lambda xc: self.ctx.glmm_slopes_solve_back(xc, self.G, self.K)
+
+    def _group_cov_phases(self, s):
+        """`block_arrow_group_cov_by_phases` on the resident factor: (cov_beta, the (G + 1)-row buffer)."""
+        P, K, G = self.P, self.K, self.G
+        return block_arrow_group_cov_by_phases(self.n_global, self._coupled_rows(), P, K, s, self._ensure_gctx().chol_solve,
+                                               lambda W, sc: self.ctx.glmm_slopes_group_cov(W, sc, G, K))
+
+    def _host_group_cov(self, x):
+        _, Hgg, rows, Hx, loc = self._arrow(x, True)
+        return block_arrow_group_cov(Hgg, rows, Hx, loc, self.P, self.K, population=True)
+
     # ---- the block-arrow solve resident on the device ------------------------------------------------------------------------
     def _device_factors(self, x, is_free):
         """on_device=True: the Schur factor on the global context and the local factor (L_g, U_g) on `ctx` at the free point x,
@@ -661,18 +713,15 @@ class _SlopesArrow:
             self._ensure_gctx().chol_factor_last()
             self._dev_factor_key = key
             self._gcov = None                        # the group covariance went with the old factor
-        eta = self._eta(fv, True)
-        dv = np.concatenate([np.ones(self.P), -1.0 / eta[self.P:2 * self.P] ** 2, np.ones(3 * self.K)])
-        return self._jac(eta)[0][coupled_rows(self.P, self.K)] * dv
+        return self._coupled_scaling(self._eta(fv, True))
 
     def _solve_on_device(self, x, R, is_free):
         s = self._device_factors(x, is_free)
         D = self.n_global + 2 * self.G * self.K
         if np.shape(R)[0] != D:
             raise ValueError('R must have {} rows'.format(D))
-        return block_arrow_solve_by_phases(R, self.n_global, coupled_rows(self.P, self.K), s, self.ctx.glmm_slopes_solve_forward,
-                                           self._ensure_gctx().chol_solve,
-                                           lambda xc: self.ctx.glmm_slopes_solve_back(xc, self.G, self.K))
+        forward, back = self._solve_entries()
+        return block_arrow_solve_by_phases(R, self.n_global, self._coupled_rows(), s, forward, self._ensure_gctx().chol_solve, back)
 
 
     # ---- group blocks of H^-1, fitted values and predictions --------------------------------------------
@@ -683,15 +732,13 @@ class _SlopesArrow:
             raise ValueError('the linear-response covariance of the means is taken in free coordinates')
         P, K, G = self.P, self.K, self.G
         if not on_device:
-            _, Hgg, rows, Hx, loc = self._arrow(x, True)
-            return block_arrow_group_cov(Hgg, rows, Hx, loc, P, K, population=True)
+            return self._host_group_cov(x)
         s = self._device_factors(x, True)
         key = self._dev_factor_key
         if self._gcov is not None and self._gcov[0] == key:
             return self._gcov[1], None, None
         self._gcov = None
-        cov_beta, buf = block_arrow_group_cov_by_phases(self.n_global, coupled_rows(P, K), P, K, s, self._ensure_gctx().chol_solve,
-                                                        lambda W, sc: self.ctx.glmm_slopes_group_cov(W, sc, G, K))
+        cov_beta, buf = self._group_cov_phases(s)
         self._gcov = (key, cov_beta)
         return (cov_beta,) + unpack_group_cov(buf, P, K)
 
@@ -713,7 +760,7 @@ class _SlopesArrow:
         """(linear-response, mean-field) standard errors of the group effects, G x K each: sqrt diag Sigma_uu next to 1 / sqrt i."""
         cu = self.group_cov(x, is_free, on_device)[1]
         eta = self._eta(x, is_free)
-        ig = _split_eta(eta, self.P, self.K, self.G)[7]
+        ig = self._split(eta)[7]
         return np.sqrt(np.diagonal(cu, axis1=1, axis2=2)), 1.0 / np.sqrt(ig)
 
     def _predict_rows_of(self, newdata, n0, n1):
@@ -770,7 +817,7 @@ class _SlopesArrow:
         cb, cu, cbu = self._group_cov(x, is_free, on_device)
         eta = self._eta(x, True)
         P, K, G = self.P, self.K, self.G
-        m, ib, e_mu, i_mu, _, _, e, ig = _split_eta(eta, P, K, G)
+        m, ib, e_mu, i_mu, _, _, e, ig = self._split(eta)
         v, e2, r2 = 1.0 / ib, np.vstack([e, e_mu[None, :]]), np.vstack([1.0 / ig, 1.0 / i_mu[None, :]])
         if on_device:
             out = self._predict_entry((m, v, e2, r2, self.gh_x, self.gh_w), cb, None if newdata is not None else (int(n0), n1), rows)

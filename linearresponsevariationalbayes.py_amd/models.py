@@ -454,6 +454,52 @@ class DeviceContext(object):
         self._check(self._lib.lrvb_glmm_slopes_group_cov(self._h, _hip.ptr(W), _hip.ptr(s), self.n_cols, G, K, _hip.ptr(out)))
         return out
 
+    # ---- the same four steps for a dense closed border of NC columns (lrvb_glmm_arrow_*) ----------------
+    def glmm_arrow_schur(self, local_blocks, border_scale, d_loc, A0, A1):
+        """M ((2 P + NC)^2) = sum_g C_g^T A_g^-1 C_g from the resident group sums of the last K-effect terms entry
+        (lrvb_glmm_arrow_schur): blocks and chain factors as `glmm_slopes_schur`, the closed border of group g as
+        A0 (2 K x NC) + sum_l A1[:, l] (2 K x K x NC) d_loc[g, l]."""
+        A, sc, d = _hip.as_f64(local_blocks), _hip.as_f64(border_scale), _hip.as_f64(d_loc)
+        A0, A1 = _hip.as_f64(A0), _hip.as_f64(A1)
+        G, K = sc.shape[0], sc.shape[1] // 2
+        NC = A0.shape[-1]
+        if sc.shape != (G, 2 * K) or A.shape != (G, K * (2 * K + 1)) or d.shape != (G, K) or A0.shape != (2 * K, NC) or A1.shape != (2 * K, K, NC):
+            raise ValueError('expected G x K (2 K + 1) local blocks, G x 2 K chain factors, G x K offsets and the tables 2 K x NC, 2 K x K x NC')
+        R = 2 * self.n_cols + NC
+        M = np.empty((R, R))
+        self._check(self._lib.lrvb_glmm_arrow_schur(self._h, _hip.ptr(A), _hip.ptr(sc), _hip.ptr(d), _hip.ptr(A0), _hip.ptr(A1), G, K, NC, _hip.ptr(M)))
+        return M
+
+    def glmm_arrow_solve_forward(self, R_local, NC):
+        """`glmm_slopes_solve_forward` on the factor of `glmm_arrow_schur`: red is (2 P + NC) x Q (lrvb_glmm_arrow_solve_forward)."""
+        Rl = _hip.as_f64(R_local)
+        if Rl.ndim != 3 or Rl.shape[1] % 2:
+            raise ValueError('expected a G x 2 K x Q right-hand side')
+        G, K, Q = Rl.shape[0], Rl.shape[1] // 2, Rl.shape[2]
+        red = np.empty((2 * self.n_cols + NC, Q))
+        self._check(self._lib.lrvb_glmm_arrow_solve_forward(self._h, _hip.ptr(Rl), G, K, NC, Q, _hip.ptr(red)))
+        return red
+
+    def glmm_arrow_solve_back(self, x_coupled, G, K, NC):
+        """`glmm_slopes_solve_back` on the factor of `glmm_arrow_schur` (lrvb_glmm_arrow_solve_back); x_coupled is (2 P + NC) x Q."""
+        xc = _hip.as_f64(x_coupled)
+        if xc.ndim != 2 or xc.shape[0] != 2 * self.n_cols + NC:
+            raise ValueError('expected the {} coupled rows x Q'.format(2 * self.n_cols + NC))
+        X = np.empty((G, 2 * K, xc.shape[1]))
+        self._check(self._lib.lrvb_glmm_arrow_solve_back(self._h, _hip.ptr(xc), G, K, NC, xc.shape[1], _hip.ptr(X)))
+        return X
+
+    def glmm_arrow_group_cov(self, W, s, G, K, NC, want_host=True):
+        """`glmm_slopes_group_cov` on the factor of `glmm_arrow_schur` (lrvb_glmm_arrow_group_cov): W is R x R, s of length
+        R = 2 P + NC, the first K closed columns being the means of mu."""
+        W, s = _hip.as_f64(W), _hip.as_f64(s).ravel()
+        R = 2 * self.n_cols + NC
+        if W.shape != (R, R) or s.size != R:
+            raise ValueError('expected W {0} x {0} and s of length {0}'.format(R))
+        out = np.empty((G + 1, K * K + K * self.n_cols)) if want_host else None
+        self._check(self._lib.lrvb_glmm_arrow_group_cov(self._h, _hip.ptr(W), _hip.ptr(s), self.n_cols, G, K, NC, _hip.ptr(out)))
+        return out
+
     def _glmm_predict(self, fn, nodes, n_extra, mean, var, e, r, gh_x, gh_w, cov_beta, n0, n1, new):
         """The five columns (5 x n: rho, var_mf, var_lrvb, mean_mf, mean_lrvb) of a predict entry.  new: None for the window
         [n0, n1) of the context's rows, or (x, z, groups, offset, trials) of new rows, of which the entry takes the first

@@ -8,9 +8,11 @@ random intercept and a random slope per group -- with linear-response covariance
         Simulates over-dispersed counts and fits `PoissonGLMMObjective` and `NegBinomialGLMMObjective` (phi known) side by
         side: the Poisson fit is over-confident, and both sets of LRVB standard errors are printed.
 
-    python examples/binomial_glmm.py [--small] [--device-solve]
+    python examples/binomial_glmm.py [--small] [--device-solve] [--link probit|cloglog]
 
 --device-solve takes the Newton polish through the device-resident block-arrow solve (`on_device=True`).
+--link fits model 1 alone under that link, p = Phi(.) or p = 1 - exp(-exp(.)), on data simulated under it,
+and prints the LRVB standard errors against the mean-field ones, the random-effect standard errors and a few fitted means.
 """
 import os
 import sys
@@ -60,6 +62,37 @@ def standard_errors(par, fun, th, P, K):
     return se_mf, se_lr
 
 
+def link_model(link, rng, x, z, gid, G, lin, beta, mu, names, shown, device_solve):
+    """Model 1 under the probit or the cloglog link, on data simulated under that link."""
+    from scipy.special import ndtr
+    if link not in ('probit', 'cloglog'):
+        raise SystemExit("--link takes 'probit' or 'cloglog'")
+    N, P = x.shape
+    K = z.shape[1]
+    trials = rng.integers(1, 21, size=N).astype(np.float64)
+    p = ndtr(lin) if link == 'probit' else -np.expm1(-np.exp(lin))
+    y = rng.binomial(trials.astype(np.int64), p).astype(np.float64)
+    par = params(P, K, G)
+    fun = vb.BinomialGLMMObjective(par, x, y, z, gid, G, trials=trials, link=link)
+    objective = vb.Objective(par, fun)
+    t0 = time.perf_counter()
+    th = fit(objective, fun, np.zeros(par.free_size()), device_solve)
+    print('binomial fit, %s link: %d rows for %d trials, %.2f s, max |free gradient| %.2e'
+          % (link, N, int(trials.sum()), time.perf_counter() - t0, np.max(np.abs(fun.grad(th, True)))))
+    par.set_free(th)
+    print('beta[:4] fitted %s, simulated %s' % (np.array2string(par['beta']['mean'].get()[:4], precision=3), np.array2string(beta[:4], precision=3)))
+    print('mu fitted %s, simulated %s' % (np.array2string(par['mu']['mean'].get(), precision=3), np.array2string(mu, precision=3)))
+    se_mf, se_lr = standard_errors(par, fun, th, P, K)
+    print('%-10s %14s %12s' % ('', 'mean-field se', 'LRVB se'))
+    for k in shown:
+        print('%-10s %14.5f %12.5f' % (names[k], se_mf[k], se_lr[k]))
+    u_lr, u_mf = fun.ranef_se(th, on_device=device_solve)
+    print('se(u_g0): mean-field median %.4f, LRVB median %.4f' % (np.median(u_mf[:, 0]), np.median(u_lr[:, 0])))
+    fitted = fun.predict(th, n0=0, n1=5, on_device=device_solve)
+    print('rows 0..4: successes %s of %s, fitted mean (LRVB variance) %s' % (y[:5].astype(int), trials[:5].astype(int),
+                                                                           np.array2string(fitted['mean_lrvb'], precision=2)))
+
+
 def main():
     small = '--small' in sys.argv
     device_solve = '--device-solve' in sys.argv
@@ -75,6 +108,9 @@ def main():
     lin = x @ beta + (z * u[gid]).sum(1)
     names = ['beta[%d]' % j for j in range(P)] + ['mu[%d]' % k for k in range(K)]
     shown = list(range(min(P, 4))) + [P + k for k in range(K)]
+    if '--link' in sys.argv:
+        link_model(sys.argv[sys.argv.index('--link') + 1], rng, x, z, gid, G, lin, beta, mu, names, shown, device_solve)
+        return
 
     # ---- 1. aggregated binomial data ----------------------------------------------------------------------------------------
     trials = rng.integers(1, 21, size=N).astype(np.float64)

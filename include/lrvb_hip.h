@@ -582,6 +582,26 @@ int lrvb_glmm_poisson_group_influence(lrvb_ctx* ctx, const double* mean, const d
  * entries read it; the call drops the resident group sums and factor.  A length other than n_obs is found when a binomial entry
  * runs: LRVB_ERR_STATE there.  n < 1 with non-null trials: LRVB_ERR_SIZE.                                                     */
 int lrvb_set_trials(lrvb_ctx* ctx, const double* trials, int64_t n);
+/* The link of the binomial mixed model, a sibling of lrvb_set_trials:
+ *   LRVB_LINK_LOGIT (the default)  p = sigma(t)           every lrvb_glmm_binomial_* entry exactly as documented below
+ *   LRVB_LINK_PROBIT               p = Phi(t)
+ *   LRVB_LINK_CLOGLOG              p = 1 - exp(-e^t)
+ * Any other value: LRVB_ERR_UNSUPPORTED, the state untouched.  Only the four lrvb_glmm_binomial_* entries (terms, obs_influence,
+ * group_influence, predict) read it; the logistic lrvb_glmm_slopes_*, the Poisson and the lrvb_glmm_arrow_* entries do not.  The call
+ * drops the resident group sums, the factor and the group covariance, as lrvb_set_trials does (a following
+ * lrvb_glmm_slopes_schur: LRVB_ERR_STATE).  Under the probit and the cloglog link, with h1 = -log p, h0 = -log(1 - p),
+ * H_n = y_n h1 + (m_n - y_n) h0 and t ~ N(rho_n, s_n), rho_n including the offset:
+ *   value = sum_n w_n E H_n(t)                                                            (log C(m_n, y_n) is dropped)
+ *   a1 = w E H', a2 = w E H'' / 2, c11 = w E H'', c12 = w E H''' / 2, c22 = w E H'''' / 4   (Stein's identity on the nodes)
+ * in the five-row layout, the scratch sizes and the summation order of the logit entries; E h1^(k) by the Gauss-Hermite rule of
+ * the caller's nodes, probit E h0^(k) by the same rule at -t, cloglog E h0^(k) = exp(rho + s / 2) exactly and NOT clamped: a point
+ * where it overflows is refused with LRVB_ERR_INVALID, as by lrvb_glmm_poisson_terms.  The influence entries use, per unit weight,
+ * a1' = E H' (there is no "- y_n") and a2' = E H'' / 2.  The predict entry returns the response-scale means m Phi(rho / sqrt(1 + var))
+ * (probit, closed form) and m E [1 - exp(-e^t)] (cloglog, on the nodes).  y is read from LRVB_SLOT_Y in the original row order.  */
+#define LRVB_LINK_LOGIT 0
+#define LRVB_LINK_PROBIT 1
+#define LRVB_LINK_CLOGLOG 2
+int lrvb_set_link(lrvb_ctx* ctx, int32_t link);
 /* Data term of that model at (mean, var (P each), e, r (G x K each, group-major)), with the Gauss-Hermite rule of
  * lrvb_glmm_slopes_terms, the offset of lrvb_set_offset (none: 0) and the trials of lrvb_set_trials (none: 1):
  *   rho_n = o_n + x_n . mean + z_n . e_g(n),  s_n as there,  psi = E softplus(t), t ~ N(rho_n, s_n)

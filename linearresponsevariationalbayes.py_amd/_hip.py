@@ -108,6 +108,7 @@ _SIGNATURES = {
     'lrvb_glmm_poisson_obs_influence': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, c_i64, c_i64, c_i64, _VP],
     'lrvb_glmm_poisson_group_influence': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, c_i64, _VP],
     'lrvb_set_trials': [_VP, _VP, c_i64],
+    'lrvb_set_link': [_VP, ctypes.c_int32],
     'lrvb_glmm_binomial_terms': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, _VP, _VP, ctypes.c_int32],
     'lrvb_glmm_binomial_obs_influence': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, c_i64, c_i64, c_i64, _VP],
     'lrvb_glmm_binomial_group_influence': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, c_i64, _VP],

@@ -2,6 +2,7 @@
 //   logistic:  y_n ~ Bernoulli(sigma(x_n . beta + z_n . u_g(n)))
 //   Poisson  (DESIGN.md section 26):  y_n ~ Poisson(exp(o_n + x_n . beta + z_n . u_g(n)))
 //   binomial:  y_n ~ Binomial(m_n, sigma(o_n + x_n . beta + z_n . u_g(n))), and through it NB2
+//   binomial with a probit or cloglog link:  p = Phi(.) or 1 - exp(-exp(.)) in the place of sigma(.)
 // Per observation rho_n = x_n . m + z_n . e_g, s_n = (x_n o x_n) . v + (z_n o z_n) . r_g and five coefficients a1, a2, c11, c12, c22.
 // Every kernel that walks the rows is written ONCE, as a template over a likelihood policy (k_glmm_walk.h, DESIGN.md sections 27 and
 // 31): LogisticLik (the quadrature k_glmm.hip runs too; with K = 1 and z = 1 this is that model) and PoissonLik
@@ -12,6 +13,9 @@
 //   init, stage_row what it puts there, once per workgroup and once per staged row;
 //   row_shift, infl (rho, s) -> (e1, e2) = (psi_rho, 2 psi_s) on all four lanes of a row, row_shift being what the row adds to rho
 //                   (the staged offset), read ahead of the dot products: the two influence kernels;
+//   MINUS_Y, mean   whether those two kernels subtract y from e1 (every canonical likelihood: a1' = psi_rho - y) or take e1 as the
+//                   whole a1' (BinomialLinkLik, which stages y itself), and the response-scale mean of the predict walk
+//                   (infl's e1 for the canonical ones; a function of its own for the two links);
 //   moments, coefs  (rho, s) -> the row's value and its NCF coefficient rows: the rows kernel;
 //   cf_row, HAS_FACTOR / cf_factor, NB / o_d / d_stride, DK
 //                   rows kernel: where the five coefficients live.  The logistic model keeps five rows.  With h = w psi the
@@ -198,9 +202,17 @@ template <class F>
 static int gs_with_lik(const GlmmLik& lik, F&& f) {
     const LogisticLik::Args q{lik.gx, lik.gw, lik.n_nodes};
     if (lik.kind == GLMM_POISSON) return f(PoissonLik(), PoissonLik::Args(lik.off));
+    if (lik.kind == GLMM_BINOMIAL && lik.link == GLMM_LINK_PROBIT)
+        return f(BinomialLinkLik<GLMM_LINK_PROBIT>(), BinomialLinkLik<GLMM_LINK_PROBIT>::Args{q, lik.off, lik.trials, lik.y});
+    if (lik.kind == GLMM_BINOMIAL && lik.link == GLMM_LINK_CLOGLOG)
+        return f(BinomialLinkLik<GLMM_LINK_CLOGLOG>(), BinomialLinkLik<GLMM_LINK_CLOGLOG>::Args{q, lik.off, lik.trials, lik.y});
     if (lik.kind == GLMM_BINOMIAL) return f(BinomialLik(), BinomialLik::Args{q, lik.off, lik.trials});
     return f(LogisticLik(), q);
 }
+
+// The link of a policy: 0 (logit, or no link at all) for every policy but BinomialLinkLik
+template <class Lik> struct gs_link_of { static constexpr int value = GLMM_LINK_LOGIT; };
+template <int LINK> struct gs_link_of<BinomialLinkLik<LINK>> { static constexpr int value = LINK; };
 
 template <class Lik>
 static int gs_launch_rows(lrvb_ctx* c, int Kz, const double* Z, typename Lik::Args la, const double* m, const double* vb, const double* eg,
@@ -461,7 +473,7 @@ int launch_glmm_slopes_solve(lrvb_ctx* c, int Kz, bool back, i64 Q, const double
 
 // ---- streamed weight influence (lrvb_glmm_slopes_obs_influence / lrvb_glmm_poisson_obs_influence) ---------
 // out[n - n0][q] = a1' (x_n . A_m[q] + sum_k z_nk A_e[q, g(n), k]) + a2' ((x_n o x_n) . A_v[q] + sum_k z_nk^2 A_r[q, g(n), k]),
-// a1' = psi_rho - y_n, a2' = psi_s PER UNIT WEIGHT (w_n does not enter).  Built like glmm_infl_rows_kernel (k_glmm.hip): ONE pass
+// a1' = psi_rho - y_n (Lik::MINUS_Y; the two links hand over a1' = E H' whole), a2' = psi_s PER UNIT WEIGHT (w_n does not enter).  Built like glmm_infl_rows_kernel (k_glmm.hip): ONE pass
 // over the rows n0..n1 in their original order, X and Z read once for any Q; a workgroup (4 waves) walks tiles of GLMM_T = 64 rows:
 //   1. the tile (contiguous in X) is staged in LDS, row stride GSI_XS, the row's K values of z behind its x columns (columns
 //      P .. P + K - 1, as glmm_slopes_rows_kernel stages them);
@@ -567,7 +579,11 @@ void gsi_infl_rows(i64 n0, i64 R /* rows of the window */, int P, int Kz, const 
         gsi_psi_derivs<Lik>(xs + row * GSI_XS, row, row < rows, s_gid[row], q4, P, Kz, ms, vs, eg, rg, lik, la, e1, e2);
         if (q4 == 0) {
             double k1 = 0.0, k2 = 0.0;
-            if (row < rows) { k1 = e1 - y[n0 + t0 + row]; k2 = 0.5 * e2; }
+            if (row < rows) {
+                if constexpr (Lik::MINUS_Y) k1 = e1 - y[n0 + t0 + row];
+                else k1 = e1;                                            // a1' whole: the policy staged y itself
+                k2 = 0.5 * e2;
+            }
             a1s[row] = k1; a2s[row] = k2;
         }
         __syncthreads();
@@ -644,6 +660,19 @@ void glmm_binomial_infl_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* 
     gsi_infl_rows<BinomialLik>(n0, R, P, Kz, X, Z, y, gid, m, vb, eg, rg, {{gx, gw, nq}, off, trials}, Ag, Al, Q, out);
 }
 
+// The probit and the cloglog link: the arguments of the binomial entry; y is also what the policy stages.
+template <int LINK>
+__global__ __launch_bounds__(256)
+void glmm_link_infl_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* __restrict__ X, const double* __restrict__ Z,
+                                const double* __restrict__ off, const double* __restrict__ trials, const double* __restrict__ y,
+                                const int* __restrict__ gid, const double* __restrict__ m, const double* __restrict__ vb,
+                                const double* __restrict__ eg, const double* __restrict__ rg, const double* __restrict__ gx,
+                                const double* __restrict__ gw, int nq, const double* __restrict__ Ag, const double* __restrict__ Al,
+                                int Q, double* __restrict__ out)
+{
+    gsi_infl_rows<BinomialLinkLik<LINK>>(n0, R, P, Kz, X, Z, y, gid, m, vb, eg, rg, {{gx, gw, nq}, off, trials, y}, Ag, Al, Q, out);
+}
+
 template <class Lik>
 static int gs_launch_infl_rows(lrvb_ctx* c, int Kz, const double* Z, typename Lik::Args la, i64 n0, i64 n1, const int* gid, const double* m,
                                const double* vb, const double* eg, const double* rg, const double* Ag, const double* Al, i64 Q,
@@ -658,6 +687,10 @@ static int gs_launch_infl_rows(lrvb_ctx* c, int Kz, const double* Z, typename Li
         hipLaunchKernelGGL(glmm_binomial_infl_rows_kernel, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
                            (const double*)la.off, (const double*)la.trials, (const double*)c->y.p, gid, m, vb, eg, rg, la.q.gx, la.q.gw,
                            la.q.nq, Ag, Al, (int)Q, out);
+    else if constexpr (gs_link_of<Lik>::value != GLMM_LINK_LOGIT)
+        hipLaunchKernelGGL(glmm_link_infl_rows_kernel<gs_link_of<Lik>::value>, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz,
+                           (const double*)c->X.p, Z, (const double*)la.off, (const double*)la.trials, (const double*)la.y, gid, m, vb, eg, rg,
+                           la.q.gx, la.q.gw, la.q.nq, Ag, Al, (int)Q, out);
     else
         hipLaunchKernelGGL(glmm_slopes_infl_rows_kernel, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
                            (const double*)c->y.p, gid, m, vb, eg, rg, la.gx, la.gw, la.nq, Ag, Al, (int)Q, out);
@@ -877,7 +910,8 @@ int launch_glmm_slopes_group_cov(lrvb_ctx* c, int Kz, int NC, const double* loc,
 // of x | z at stride GSI_XS, the same Lik::init / stage_row / row_shift -- for five columns of n doubles,
 //   rho = o + x . m + z . e_g,   var_mf = (x o x) . v + (z o z) . r_g,
 //   var_lrvb = x^T S_bb x + 2 sum_k z_k (x . S_ubeta[g][k]) + z^T S_uu[g] z,
-//   mean_mf, mean_lrvb = the policy's e1 (E sigma(t), exp(rho + ./2), m E sigma(t)) at (rho, var_mf) and at (rho, var_lrvb).
+//   mean_mf, mean_lrvb = the policy's `mean` (E sigma(t), exp(rho + ./2), m E sigma(t): its e1; m Phi(rho / sqrt(1 + .)) and
+//   m E [1 - exp(-e^t)] for the two links) at (rho, var_mf) and at (rho, var_lrvb).
 //   1. four lanes per row form rho and var_mf with the column map of gsi_psi_derivs and keep them in registers;
 //   2. wave w owns the rows 16 w .. 16 w + 15: per block of 16 columns of S_bb (P x P, the B operand, zero past P) the product
 //      X S_bb runs as 16 x 16 x 4 fp64 MFMA tiles, two accumulator chains; in the D layout (register r <-> row (l >> 4) + 4 r,
@@ -888,7 +922,7 @@ int launch_glmm_slopes_group_cov(lrvb_ctx* c, int Kz, int NC, const double* loc,
 //      different groups, so this cannot be an MFMA operand;
 //   4. xor shuffles over the 16 lanes of a row add the partial sums in a fixed order; z^T S_uu z (K K gathered values) is added
 //      and the row's variance goes to LDS;
-//   5. the four lanes of a row run Lik::infl twice, and lane 0 writes the five values.
+//   5. the four lanes of a row run Lik::mean twice, and lane 0 writes the five values.
 // With P <= 16 the B fragments are loaded once per workgroup.  A row's result depends on nothing but the row: a window equals
 // the same rows of the full result bitwise.  No atomics.
 template <class Lik>
@@ -996,9 +1030,9 @@ void gsp_predict_rows(i64 n0, i64 R /* rows of the window */, int P, int Kz, con
         }
         __syncthreads();
         const double v_lr = vq[row];
-        double m_mf, m_lr, e2;
-        Lik::infl(lik, la, o, live, q4, rho, s, m_mf, e2);
-        Lik::infl(lik, la, o, live, q4, rho, v_lr, m_lr, e2);
+        double m_mf, m_lr;
+        Lik::mean(lik, la, o, live, q4, rho, s, m_mf);
+        Lik::mean(lik, la, o, live, q4, rho, v_lr, m_lr);
         if (live && q4 == 0) {
             double* dst = out + t0 + row;
             dst[0] = rho + o; dst[ldo] = s; dst[2 * ldo] = v_lr; dst[3 * ldo] = m_mf; dst[4 * ldo] = m_lr;
@@ -1037,6 +1071,19 @@ void glmm_binomial_predict_rows_kernel(i64 n0, i64 R, int P, int Kz, const doubl
     gsp_predict_rows<BinomialLik>(n0, R, P, Kz, X, Z, gid, m, vb, eg, rg, {{gx, gw, nq}, off, trials}, Sbb, gcov, out, ldo);
 }
 
+// The probit and the cloglog link: the arguments of the binomial entry.  No y: the response mean needs none, and new rows have none.
+template <int LINK>
+__global__ __launch_bounds__(256)
+void glmm_link_predict_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* __restrict__ X, const double* __restrict__ Z,
+                                   const double* __restrict__ off, const double* __restrict__ trials, const int* __restrict__ gid,
+                                   const double* __restrict__ m, const double* __restrict__ vb, const double* __restrict__ eg,
+                                   const double* __restrict__ rg, const double* __restrict__ gx, const double* __restrict__ gw,
+                                   int nq, const double* __restrict__ Sbb, const double* __restrict__ gcov,
+                                   double* __restrict__ out, i64 ldo)
+{
+    gsp_predict_rows<BinomialLinkLik<LINK>>(n0, R, P, Kz, X, Z, gid, m, vb, eg, rg, {{gx, gw, nq}, off, trials, nullptr}, Sbb, gcov, out, ldo);
+}
+
 int launch_glmm_slopes_predict_rows(lrvb_ctx* c, const GlmmLik& lik, int Kz, const double* X, const double* Z, i64 n0, i64 n1,
                                     const int* gid, const double* m, const double* vb, const double* eg, const double* rg,
                                     const double* Sbb, const double* gcov, double* out, i64 ldo) {
@@ -1049,6 +1096,12 @@ int launch_glmm_slopes_predict_rows(lrvb_ctx* c, const GlmmLik& lik, int Kz, con
     if (lik.kind == GLMM_POISSON)
         hipLaunchKernelGGL(glmm_poisson_predict_rows_kernel, grid, block, 0, c->stream, n0, R, P, Kz, X, Z, lik.off, gid, m, vb, eg, rg, Sbb,
                            gcov, out, ldo);
+    else if (lik.kind == GLMM_BINOMIAL && lik.link == GLMM_LINK_PROBIT)
+        hipLaunchKernelGGL(glmm_link_predict_rows_kernel<GLMM_LINK_PROBIT>, grid, block, 0, c->stream, n0, R, P, Kz, X, Z, lik.off, lik.trials, gid,
+                           m, vb, eg, rg, lik.gx, lik.gw, lik.n_nodes, Sbb, gcov, out, ldo);
+    else if (lik.kind == GLMM_BINOMIAL && lik.link == GLMM_LINK_CLOGLOG)
+        hipLaunchKernelGGL(glmm_link_predict_rows_kernel<GLMM_LINK_CLOGLOG>, grid, block, 0, c->stream, n0, R, P, Kz, X, Z, lik.off, lik.trials, gid,
+                           m, vb, eg, rg, lik.gx, lik.gw, lik.n_nodes, Sbb, gcov, out, ldo);
     else if (lik.kind == GLMM_BINOMIAL)
         hipLaunchKernelGGL(glmm_binomial_predict_rows_kernel, grid, block, 0, c->stream, n0, R, P, Kz, X, Z, lik.off, lik.trials, gid, m, vb,
                            eg, rg, lik.gx, lik.gw, lik.n_nodes, Sbb, gcov, out, ldo);
@@ -1097,7 +1150,13 @@ void glmm_slopes_infl_gsum_kernel(i64 N, int P, int Kz, i64 G, const double* __r
         gsi_psi_derivs<Lik>(xs + row * GSI_XS, row, row < rows, s_gid[row], q4, P, Kz, ms, vs, eg, rg, lik, la, e1, e2);
         if (q4 == 0) {
             double k1 = 0.0, k2 = 0.0;
-            if (row < rows) { const i64 pr = s_row[row]; const double wi = w[pr]; k1 = wi * (e1 - y[pr]); k2 = wi * 0.5 * e2; }
+            if (row < rows) {
+                const i64 pr = s_row[row];
+                const double wi = w[pr];
+                if constexpr (Lik::MINUS_Y) k1 = wi * (e1 - y[pr]);
+                else k1 = wi * e1;
+                k2 = wi * 0.5 * e2;
+            }
             cf[row] = k1; cf[GLMM_T + row] = k2;
         }
         __syncthreads();

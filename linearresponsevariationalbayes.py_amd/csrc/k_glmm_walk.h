@@ -50,6 +50,14 @@ struct LogisticLik {
         e1 += __shfl_xor(e1, 1); e2 += __shfl_xor(e2, 1);
         e1 += __shfl_xor(e1, 2); e2 += __shfl_xor(e2, 2);
     }
+    // What the walk asks of a canonical likelihood: the influence kernels subtract y from e1, and the
+    // response-scale mean of the predict walk is infl's e1.
+    static constexpr bool MINUS_Y = true;
+    static __device__ __forceinline__ void mean(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& mu)
+    {
+        double e2;
+        infl(L, a, o, live, q4, rho, s, mu, e2);
+    }
     static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
     {
         double v = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0, e4 = 0.0;
@@ -105,6 +113,13 @@ struct PoissonLik {
     {
         e1 = e2 = live ? exp((rho + o) + 0.5 * s) : 0.0;
     }
+    // canonical: see LogisticLik
+    static constexpr bool MINUS_Y = true;
+    static __device__ __forceinline__ void mean(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& mu)
+    {
+        double e2;
+        infl(L, a, o, live, q4, rho, s, mu, e2);
+    }
     static __device__ __forceinline__ Moments moments(const Lds&, const Args&, bool, int, double, double) { return {}; }
     static __device__ __forceinline__ double coefs(const Lds& L, int row, const Moments&, double wi, double yi, double rho, double s,
                                                    double* k)
@@ -156,6 +171,13 @@ struct BinomialLik {
             e1 = e1 * mt; e2 = e2 * mt;
         }
     }
+    // canonical: see LogisticLik
+    static constexpr bool MINUS_Y = true;
+    static __device__ __forceinline__ void mean(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& mu)
+    {
+        double e2;
+        infl(L, a, o, live, q4, rho, s, mu, e2);
+    }
     static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
     {
         const int row = lane_row();
@@ -171,6 +193,168 @@ struct BinomialLik {
                                                    double* k)
     {
         return LogisticLik::coefs(L.q, row, mo, wi, yi, rho + L.s_off[row], s, k);
+    }
+};
+
+// Binomial with a probit or a complementary log-log link: p = Phi(t) or p = 1 - exp(-e^t).  The first
+// likelihoods here that are not canonical: with h1 = -log p, h0 = -log(1 - p) the row's term is E [y h1(t) + (m - y) h0(t)],
+// t ~ N(rho, s), rho including the offset -- no "- y rho", success and failure with curvatures of their own, and a response mean
+// that is not psi_rho.  So MINUS_Y is false (infl returns a1' = y E h1' + (m - y) E h0' whole) and `mean` is a function of its
+// own.  Nodes, offsets and trials are staged as BinomialLik stages them, y from the same ORIGINAL row index behind them (a null
+// y -- the predict walk, which needs none -- stages zeros).  Coefficients by Stein's identity on the nodes, in the logistic
+// five-row layout:  value = E H, a1 = E H', a2 = E H'' / 2, c11 = E H'', c12 = E H''' / 2, c22 = E H'''' / 4  (times w).
+//   probit   h1' = -lambda, lambda = phi / Phi = sqrt(2 / pi) / erfcx(-t / sqrt 2) (never phi / Phi: 0 / 0 below t = -38), and with
+//            d = t + lambda, w = lambda d:  h1'' = w,  h1''' = w' = lambda (1 - w) - w d,  h1'''' = -w' (d + lambda) - 2 w (1 - w).
+//            erfcx overflows to +inf for large t: lambda = 0 and every derivative is 0, no branch on data.  h0(t) = h1(-t): the
+//            same rule at -t, odd derivatives negated.  -log Phi: t^2 / 2 - log(erfcx(-t / sqrt 2) / 2) for t < 0,
+//            -log1p(-erfc(t / sqrt 2) / 2) for t >= 0.
+//   cloglog  u = e^t, r = u / expm1(u):  h1' = -r,  r' = r q with q = 1 - u - r,  q' = -u - r', and so on by the product rule.
+//            Past u = 700 (r < 1e-301) r is set to 0 and u to 700 in the polynomials, a select: u = +inf gives exact zeros, not
+//            inf / inf.  h1 = -log(-expm1(-u)).  h0 = u EXACTLY integrable: E h0 and all its derivatives are exp(rho + s / 2), one
+//            exp per row as in PoissonLik and not clamped -- where it overflows the non-finite value reaches the sums and the
+//            entry refuses it.  Below t = -745 (u = 0) r is 0 / 0 and the row is refused in the same way.
+// The products with y and m - y are formed per lane ahead of the xor shuffles; the four lanes of a row share the nodes as
+// LogisticLik::moments does.  Fixed order, no atomics.
+constexpr int GLMM_LINK_LOGIT = 0, GLMM_LINK_PROBIT = 1, GLMM_LINK_CLOGLOG = 2;     // LRVB_LINK_* of the C ABI
+
+template <int LINK>
+struct BinomialLinkLik {
+    static_assert(LINK == GLMM_LINK_PROBIT || LINK == GLMM_LINK_CLOGLOG, "the logit link is BinomialLik");
+    struct Args { LogisticLik::Args q; const double* __restrict__ off; const double* __restrict__ trials; const double* __restrict__ y; };
+    struct Lds { LogisticLik::Lds q; double s_off[GLMM_T], s_m[GLMM_T], s_y[GLMM_T]; };
+    typedef LogisticLik::Moments Moments;
+    static constexpr const char* LIMITS = "binomial mixed model: P <= 64, 1 <= K <= 4, at most 128 nodes";
+    static bool args_ok(const Args& a) { return LogisticLik::args_ok(a.q); }
+    static constexpr int NCF = 5, NB = 4, DK = 16;
+    static constexpr bool HAS_FACTOR = false;
+    static constexpr bool MINUS_Y = false;
+    static __device__ __forceinline__ int cf_row(int kind) { return kind; }
+    static __device__ __forceinline__ double cf_factor(int) { return 1.0; }
+    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return b * Kz + k; }
+    static __device__ __forceinline__ int d_stride(int) { return DK; }
+
+    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { LogisticLik::init(L.q, a.q, tid); }
+    static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
+    {
+        L.s_off[t] = (a.off && live) ? a.off[src] : 0.0;
+        L.s_m[t] = (a.trials && live) ? a.trials[src] : 1.0;
+        L.s_y[t] = (a.y && live) ? a.y[src] : 0.0;
+    }
+    static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_off[row]; }
+    static __device__ __forceinline__ int lane_row() { return (int)(threadIdx.x >> 2); }
+
+    // h1' and h1'' at t (N = 2), or h1 .. h1'''' (N = 5), into h[5 - N ..]: h[0] is the value wherever it is asked for
+    template <int N>
+    static __device__ __forceinline__ void h1(double t, double* h)
+    {
+        if constexpr (LINK == GLMM_LINK_PROBIT) {
+            const double ex = erfcx(-0.7071067811865476 * t);
+            const double lam = 0.7978845608028654 / ex;                  // sqrt(2 / pi) / erfcx(-t / sqrt 2)
+            const double d = t + lam, w = lam * d;
+            h[1] = -lam; h[2] = w;
+            if constexpr (N == 5) {
+                const double w1 = lam * (1.0 - w) - w * d;
+                h[3] = w1; h[4] = -w1 * (d + lam) - 2.0 * w * (1.0 - w);
+                if (t < 0.0) h[0] = 0.5 * t * t - log(0.5 * ex);
+                else h[0] = -log1p(-0.5 * erfc(0.7071067811865476 * t));
+            }
+        } else {
+            const double u = exp(t), uc = fmin(u, 700.0);
+            const double r = u > 700.0 ? 0.0 : uc / expm1(uc);
+            const double q = 1.0 - uc - r, r1 = r * q;
+            h[1] = -r; h[2] = -r1;
+            if constexpr (N == 5) {
+                const double q1 = -uc - r1, r2 = r1 * q + r * q1, q2 = -uc - r2;
+                h[3] = -r2; h[4] = -(r2 * q + 2.0 * r1 * q1 + r * q2);
+                h[0] = -log(-expm1(-u));
+            }
+        }
+    }
+    // a1' = y E h1' + (m - y) E h0' and E H'' = 2 a2' per unit weight, on all four lanes of a row
+    static __device__ __forceinline__ void infl(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& e1,
+                                                double& e2)
+    {
+        const int row = lane_row();
+        const double yt = L.s_y[row], ft = L.s_m[row] - yt;
+        rho += o;
+        e1 = 0.0; e2 = 0.0;
+        if (live) {
+            const double sd = sqrt(fmax(s, 0.0));
+            for (int k = q4; k < a.q.nq; k += 4) {
+                const double t = rho + sd * L.q.sx[k], wk = L.q.sw[k];
+                double h[5];
+                h1<2>(t, h);
+                double g1 = yt * h[1], g2 = yt * h[2];
+                if constexpr (LINK == GLMM_LINK_PROBIT) {
+                    h1<2>(-t, h);
+                    g1 -= ft * h[1]; g2 += ft * h[2];
+                }
+                e1 += wk * g1; e2 += wk * g2;
+            }
+        }
+        e1 += __shfl_xor(e1, 1); e2 += __shfl_xor(e2, 1);
+        e1 += __shfl_xor(e1, 2); e2 += __shfl_xor(e2, 2);
+        if constexpr (LINK == GLMM_LINK_CLOGLOG) {
+            const double eh = live ? ft * exp(rho + 0.5 * s) : 0.0;
+            e1 += eh; e2 += eh;
+        }
+    }
+    // the response-scale mean m p: probit in closed form, E Phi(t) = Phi(rho / sqrt(1 + s)); cloglog on the nodes
+    static __device__ __forceinline__ void mean(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& mu)
+    {
+        const double mt = L.s_m[lane_row()];
+        rho += o;
+        if constexpr (LINK == GLMM_LINK_PROBIT) {
+            mu = live ? mt * (0.5 * erfc(-rho / sqrt(2.0 * (1.0 + fmax(s, 0.0))))) : 0.0;
+        } else {
+            double p = 0.0;
+            if (live) {
+                const double sd = sqrt(fmax(s, 0.0));
+                for (int k = q4; k < a.q.nq; k += 4) p += L.q.sw[k] * -expm1(-exp(rho + sd * L.q.sx[k]));
+            }
+            p += __shfl_xor(p, 1);
+            p += __shfl_xor(p, 2);
+            mu = mt * p;
+        }
+    }
+    static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
+    {
+        const int row = lane_row();
+        const double yt = L.s_y[row], ft = L.s_m[row] - yt;
+        rho += L.s_off[row];
+        double e[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        if (live) {
+            const double sd = sqrt(fmax(s, 0.0));
+            for (int k = q4; k < a.q.nq; k += 4) {
+                const double t = rho + sd * L.q.sx[k], wk = L.q.sw[k];
+                double h[5], g[5];
+                h1<5>(t, h);
+#pragma unroll
+                for (int i = 0; i < 5; ++i) g[i] = yt * h[i];
+                if constexpr (LINK == GLMM_LINK_PROBIT) {
+                    h1<5>(-t, h);
+#pragma unroll
+                    for (int i = 0; i < 5; ++i) g[i] += ft * ((i & 1) ? -h[i] : h[i]);
+                }
+#pragma unroll
+                for (int i = 0; i < 5; ++i) e[i] += wk * g[i];
+            }
+        }
+#pragma unroll
+        for (int off = 1; off <= 2; off <<= 1)
+#pragma unroll
+            for (int i = 0; i < 5; ++i) e[i] += __shfl_xor(e[i], off);
+        if constexpr (LINK == GLMM_LINK_CLOGLOG) {
+            const double eh = live ? ft * exp(rho + 0.5 * s) : 0.0;
+#pragma unroll
+            for (int i = 0; i < 5; ++i) e[i] += eh;
+        }
+        return {e[0], e[1], e[2], e[3], e[4]};
+    }
+    static __device__ __forceinline__ double coefs(const Lds&, int, const Moments& mo, double wi, double, double, double, double* k)
+    {
+        k[0] = wi * mo.e1; k[1] = wi * 0.5 * mo.e2; k[2] = wi * mo.e2; k[3] = wi * 0.5 * mo.e3; k[4] = wi * 0.25 * mo.e4;
+        return wi * mo.v;
     }
 };
 

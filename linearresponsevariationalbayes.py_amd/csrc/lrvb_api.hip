@@ -2602,7 +2602,7 @@ extern "C" int lrvb_set_group_design(lrvb_ctx* c, const double* z, int64_t n, in
 static GlmmLik glmms_intercept(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_LOGISTIC, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, true}; }
 static GlmmLik glmms_logistic(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_LOGISTIC, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false}; }
 static GlmmLik glmms_poisson() { return GlmmLik{GLMM_POISSON, nullptr, nullptr, 0, nullptr, nullptr, false}; }
-static GlmmLik glmms_binomial(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_BINOMIAL, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false}; }
+static GlmmLik glmms_binomial(const lrvb_ctx* c, const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_BINOMIAL, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, c->glmms_link, nullptr}; }
 static const char* glmms_name(const GlmmLik& lik) { return lik.kind == GLMM_POISSON ? "Poisson" : (lik.kind == GLMM_BINOMIAL ? "binomial" : "logistic"); }
 
 // The argument and state checks of all twelve entries over the rows, in one order (`other_null`: a required pointer of the entry's own is null).
@@ -2644,6 +2644,7 @@ static int read_flag(lrvb_ctx* c, const double* flag, int* bad) {
 static int glmms_to_device(lrvb_ctx* c, GlmmLik& lik, double* g) {
     if (lik.kind != GLMM_LOGISTIC) lik.off = c->goff_n ? c->goff.p : nullptr;
     if (lik.kind == GLMM_BINOMIAL) lik.trials = c->gtr_n ? c->gtr.p : nullptr;
+    if (lik.link != LRVB_LINK_LOGIT) lik.y = c->y.p;                      // the probit and cloglog policies stage y themselves
     if (lik.kind == GLMM_POISSON) return LRVB_OK;
     LRVB_TRY(h2d(c, g, lik.gx, (size_t)lik.n_nodes));
     LRVB_TRY(h2d(c, g + 128, lik.gw, (size_t)lik.n_nodes));
@@ -2716,6 +2717,8 @@ static int glmms_terms(lrvb_ctx* c, GlmmLik lik, const double* mean, const doubl
     LRVB_TRY(d2h(c, value_out, vred, 1));
     if (poisson && !std::isfinite(*value_out))
         LRVB_FAIL(LRVB_ERR_INVALID, "the Poisson data term is not finite at this point: exp(rho + s / 2) overflows for some row (the kernel does not clamp)");
+    if (lik.link == LRVB_LINK_CLOGLOG && !std::isfinite(*value_out))
+        LRVB_FAIL(LRVB_ERR_INVALID, "the cloglog data term is not finite at this point: exp(rho + s / 2) overflows, or exp(t) underflows to 0, for some row (the kernel does not clamp)");
     c->glmms_valid = true; c->glmms_K = lik.unit ? 0 : (int)K;           // 0: the sums of lrvb_glmm_terms, for lrvb_glmm_schur only
     if (want_g) LRVB_TRY(d2h(c, grad_global_out, gred, (size_t)(2 * P)));
     if (want_H) LRVB_TRY(d2h(c, H_blocks_out, Hb, (size_t)(3 * P * P)));
@@ -3025,6 +3028,16 @@ extern "C" int lrvb_set_trials(lrvb_ctx* c, const double* trials, int64_t n) {
     return glmms_set_rows(c, c->gtr, c->gtr_n, trials, n, 1, "the trials need at least one entry");
 }
 
+// The link of the binomial entries: a sibling of lrvb_set_trials.  What was formed under another link is dropped.
+extern "C" int lrvb_set_link(lrvb_ctx* c, int32_t link) {
+    LRVB_TRY(ctx_bind(c));
+    if (link != LRVB_LINK_LOGIT && link != LRVB_LINK_PROBIT && link != LRVB_LINK_CLOGLOG)
+        LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the links are logit (0), probit (1) and cloglog (2) (got %d)", (int)link);
+    c->glmms_drop();
+    c->glmms_link = (int)link;
+    return LRVB_OK;
+}
+
 // The three binomial entries: the shared bodies above with the binomial likelihood (the caller's nodes; the offset of
 // lrvb_set_offset and the trials of lrvb_set_trials).
 extern "C" int lrvb_glmm_binomial_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
@@ -3032,7 +3045,7 @@ extern "C" int lrvb_glmm_binomial_terms(lrvb_ctx* c, const double* mean, const d
                                         int32_t n_nodes, double* value_out, double* grad_global_out, double* H_blocks_out,
                                         double* group_sums_out, int32_t want_border) {
     LRVB_TRY(ctx_bind(c));
-    return glmms_terms(c, glmms_binomial(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, value_out, grad_global_out,
+    return glmms_terms(c, glmms_binomial(c, gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, value_out, grad_global_out,
                        H_blocks_out, group_sums_out, want_border);
 }
 
@@ -3041,14 +3054,14 @@ extern "C" int lrvb_glmm_binomial_obs_influence(lrvb_ctx* c, const double* mean,
                                                 int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, int64_t n0,
                                                 int64_t n1, double* out) {
     LRVB_TRY(ctx_bind(c));
-    return glmms_obs_influence(c, glmms_binomial(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, n0, n1, out);
+    return glmms_obs_influence(c, glmms_binomial(c, gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, n0, n1, out);
 }
 
 extern "C" int lrvb_glmm_binomial_group_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
                                                   const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
                                                   int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, double* out) {
     LRVB_TRY(ctx_bind(c));
-    return glmms_group_influence(c, glmms_binomial(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out);
+    return glmms_group_influence(c, glmms_binomial(c, gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out);
 }
 
 // ---- group blocks of H^-1 and predictions with their linear-response variance (k_glmm_slopes.hip) ----------
@@ -3161,7 +3174,7 @@ extern "C" int lrvb_glmm_binomial_predict(lrvb_ctx* c, const double* mean, const
                                           const double* z_new, const int32_t* gid_new, const double* offset_new,
                                           const double* trials_new, int64_t n_new, double* out) {
     LRVB_TRY(ctx_bind(c));
-    return glmms_predict(c, glmms_binomial(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, Gp, K, cov_beta, n0, n1, x_new, z_new,
+    return glmms_predict(c, glmms_binomial(c, gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, Gp, K, cov_beta, n0, n1, x_new, z_new,
                          gid_new, offset_new, trials_new, n_new, out);
 }
 

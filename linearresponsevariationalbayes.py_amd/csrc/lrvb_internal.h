@@ -147,6 +147,8 @@ struct lrvb_ctx {
     DevBuf goff; i64 goff_n = 0;
     // lrvb_glmm_binomial_* read that offset too, and the per-row trial counts of lrvb_set_trials, gtr_n doubles (0 = none: one trial)
     DevBuf gtr; i64 gtr_n = 0;
+    // and the link of lrvb_set_link (LRVB_LINK_LOGIT = 0 by default); no other entry reads it
+    int glmms_link = 0;
     DevBuf opt;                    // trust-region Newton-CG: 12 D-vectors (+ the D x D preconditioner)
     DevBuf cgm[9];                 // blocked CG: B, X, R, P, Q, Z (Q x D), U, W (Q x V), R^T (P x Q)
     DevBuf cgT;                    // N x Q products X U^T of the blocked HVP
@@ -260,7 +262,10 @@ int  launch_glmm_infl_local(lrvb_ctx* c, i64 Q, const double* S, const double* A
 // the per-row trials or nullptr (binomial).  `unit`: the unit group design of the random intercept (logistic,
 // K = 1, z = 1, nothing on the device): the host bodies hand the launchers Z = nullptr, and those launch the kernels of k_glmm.hip.
 enum GlmmKind { GLMM_LOGISTIC = 0, GLMM_POISSON = 1, GLMM_BINOMIAL = 2 };
-struct GlmmLik { GlmmKind kind; const double* gx; const double* gw; int n_nodes; const double* off; const double* trials; bool unit; };
+// `link` (binomial only, LRVB_LINK_*; 0 = logit: BinomialLik) picks the probit or cloglog policy of DESIGN.md section 35, and `y`
+// is the response those two stage themselves (the host bodies fill it in with the offset and the trials).
+struct GlmmLik { GlmmKind kind; const double* gx; const double* gw; int n_nodes; const double* off; const double* trials; bool unit;
+                 int link; const double* y; };
 int  glmm_slopes_ncol(int P, int K);      // columns of one group's sums: 2 K + K (2 K + 1) + 4 K P
 int  launch_glmm_slopes_rows(lrvb_ctx* c, const GlmmLik& lik, int K, const double* Z /* N x K; nullptr: the unit design */, const double* m, const double* vb,
                              const double* eg /* G x K */, const double* rg /* G x K */,

@@ -17,11 +17,18 @@ Negative binomial (NB2: mean e^eta, variance e^eta + e^2eta / phi, KNOWN dispers
 offset o - log phi.  `NegBinomialGLMMObjective` is that construction and nothing else; phi is fixed data, not a hyper-parameter,
 and is not estimated.
 
+Links: `link='probit'` (p = Phi(t)) and `link='cloglog'` (p = 1 - exp(-e^t)) replace the data term by
+
+    sum_n w_n E [ y_n h1(t) + (m_n - y_n) h0(t) ],   h1 = -log p,  h0 = -log(1 - p),  t ~ N(rho_n, s_n)
+
+on the same nodes (cloglog: E h0 = exp(rho + s / 2) in closed form).  `link_h`, `link_row_derivs` and `link_response_mean` below are
+the host forms of what the kernels compute per node and per row; they need no device.
+
 The O(N) work is `lrvb_glmm_binomial_terms` (csrc/k_glmm_slopes.hip, the policy BinomialLik of csrc/k_glmm_walk.h); everything
 after the per-row coefficients is the shared layer, unchanged.
 """
 import numpy as np
-from scipy.special import expit, gammaln
+from scipy.special import erfc, erfcx, expit, gammaln, ndtr
 
 from . import _hip
 from .glmm_slopes import _LogisticMixedModel, _SlopesArrow
@@ -34,15 +41,102 @@ def _row_vector(a, n, what):
     return a
 
 
+LINKS = {'logit': 0, 'probit': 1, 'cloglog': 2}                         # LRVB_LINK_* of the C ABI
+
+
+def _h1_probit(t, order):
+    """-log Phi(t) and its derivatives through the inverse Mills ratio lambda = sqrt(2 / pi) / erfcx(-t / sqrt 2)."""
+    with np.errstate(over='ignore', divide='ignore', invalid='ignore'):
+        ex = erfcx(-t / np.sqrt(2.0))
+        lam = np.sqrt(2.0 / np.pi) / ex
+        d = t + lam
+        w = lam * d
+        w1 = lam * (1.0 - w) - w * d
+        h = [np.where(t < 0.0, 0.5 * t * t - np.log(0.5 * ex), -np.log1p(-0.5 * erfc(np.maximum(t, 0.0) / np.sqrt(2.0)))),
+             -lam, w, w1, -w1 * (d + lam) - 2.0 * w * (1.0 - w)]
+    return h[:order + 1]
+
+
+def _h1_cloglog(t, order):
+    """-log(1 - exp(-u)), u = e^t, and its derivatives in t through r = u / expm1(u): r' = r (1 - u - r)."""
+    with np.errstate(over='ignore', divide='ignore', invalid='ignore'):
+        u = np.exp(t)
+        uc = np.minimum(u, 700.0)
+        r = np.where(u > 700.0, 0.0, uc / np.expm1(uc))
+        q = 1.0 - uc - r
+        r1 = r * q
+        q1 = -uc - r1
+        r2 = r1 * q + r * q1
+        q2 = -uc - r2
+        h = [-np.log(-np.expm1(-u)), -r, -r1, -r2, -(r2 * q + 2.0 * r1 * q1 + r * q2)]
+    return h[:order + 1]
+
+
+def link_h(link, t, order=4):
+    """([h1, h1', .., h1^(order)], [h0, .., h0^(order)]) at t, order <= 4: the per-trial terms h1 = -log p, h0 = -log(1 - p) of
+    the probit or cloglog link by the formulas of the kernels (k_glmm_walk.h, BinomialLinkLik)."""
+    t = np.asarray(t, dtype=np.float64)
+    if link == 'probit':
+        h0 = _h1_probit(-t, order)
+        return _h1_probit(t, order), [(-a if k & 1 else a) for k, a in enumerate(h0)]
+    if link == 'cloglog':
+        return _h1_cloglog(t, order), [np.exp(t)] * (order + 1)
+    raise ValueError("link_h: link must be 'probit' or 'cloglog'")
+
+
+def _nodes(rho, s, gh_x, gh_w):
+    rho, s = np.asarray(rho, dtype=np.float64), np.asarray(s, dtype=np.float64)
+    t = rho[..., None] + np.sqrt(np.maximum(s, 0.0))[..., None] * (np.sqrt(2.0) * np.asarray(gh_x, dtype=np.float64))
+    return t, np.asarray(gh_w, dtype=np.float64) / np.sqrt(np.pi)
+
+
+def link_expected_h(link, rho, s, y, trials, gh_x, gh_w):
+    """E H^(k), k = 0..4, H = y h1 + (trials - y) h0, t ~ N(rho, s) (rho including the offset) by the kernels' rule: h1 on the
+    nodes, probit h0 on the nodes at -t, cloglog h0 = exp(rho + s / 2) in closed form.  A 5 x ... array."""
+    t, wk = _nodes(rho, s, gh_x, gh_w)
+    h1, h0 = link_h(link, t, 4)
+    y, f = np.asarray(y, dtype=np.float64), np.asarray(trials, dtype=np.float64) - np.asarray(y, dtype=np.float64)
+    e1 = np.stack([(a * wk).sum(-1) for a in h1])
+    if link == 'cloglog':
+        with np.errstate(over='ignore'):
+            e0 = np.stack([np.exp(np.asarray(rho, dtype=np.float64) + 0.5 * np.asarray(s, dtype=np.float64))] * 5)
+    else:
+        e0 = np.stack([(a * wk).sum(-1) for a in h0])
+    with np.errstate(invalid='ignore'):
+        return y * e1 + f * e0
+
+
+def link_row_derivs(link, rho, s, y, trials, gh_x, gh_w):
+    """(a1', a2') per unit weight of the streamed influence rows: a1' = E H' (there is no "- y"), a2' = E H'' / 2."""
+    e = link_expected_h(link, rho, s, y, trials, gh_x, gh_w)
+    return e[1], 0.5 * e[2]
+
+
+def link_response_mean(link, rho, s, trials, gh_x, gh_w):
+    """trials E p(t), t ~ N(rho, s): probit in closed form, Phi(rho / sqrt(1 + s)); cloglog on the nodes, E [-expm1(-e^t)]."""
+    if link == 'probit':
+        p = ndtr(np.asarray(rho, dtype=np.float64) / np.sqrt(1.0 + np.maximum(np.asarray(s, dtype=np.float64), 0.0)))
+    elif link == 'cloglog':
+        t, wk = _nodes(rho, s, gh_x, gh_w)
+        with np.errstate(over='ignore'):
+            p = (-np.expm1(-np.exp(t)) * wk).sum(-1)
+    else:
+        raise ValueError("link_response_mean: link must be 'probit' or 'cloglog'")
+    return p if trials is None else np.asarray(trials, dtype=np.float64) * p
+
+
 class BinomialGLMMObjective(_SlopesArrow, _LogisticMixedModel):
     _loss = 'logistic'
 
     def __init__(self, par, x, y, z, groups, n_groups, trials=None, offset=None, beta_prior_info=1.0, mu_prior=(0.0, 1.0),
-                 tau_prior=(1.0, 1.0), gh_deg=20, names=('beta', 'mu', 'tau', 'u'), weights=None, device=0):
+                 tau_prior=(1.0, 1.0), gh_deg=20, names=('beta', 'mu', 'tau', 'u'), weights=None, device=0, link='logit'):
         """y: successes, 0 <= y_n <= trials_n (log C(m, y) is dropped from the value).  trials: the N trial counts m_n >= 0 (real
         values are accepted: the negative-binomial subclass sends y + phi), or None for one trial per row.  offset: the N offsets
         o_n, or None for zero.  z: the N x K group design, or None for one effect per group with the unit design (a column of
-        ones is sent).  names: as `LogisticGLMMSlopesObjective`.  All checks run before the device context is created."""
+        ones is sent).  names: as `LogisticGLMMSlopesObjective`.  link: 'logit' (the default), 'probit' or 'cloglog'.  All checks run
+        before the device context is created."""
+        if link not in LINKS:
+            raise ValueError("link must be 'logit', 'probit' or 'cloglog' (got {!r})".format(link))
         y = _hip.as_f64(y).ravel()
         n = np.shape(x)[0]
         if y.size != n or not np.all(np.isfinite(y)):
@@ -58,7 +152,8 @@ class BinomialGLMMObjective(_SlopesArrow, _LogisticMixedModel):
         if z is None:
             z = np.ones((n, 1))
         super().__init__(par, x, y, z, groups, n_groups, beta_prior_info, mu_prior, tau_prior, gh_deg, names, weights, device)
-        self._trials, self._offset = trials, offset
+        self._trials, self._offset, self.link = trials, offset, link
+        self.ctx.set_link(LINKS[link])
         self.ctx.set_trials(trials)
         self.ctx.set_offset(offset)
 
@@ -83,11 +178,22 @@ class BinomialGLMMObjective(_SlopesArrow, _LogisticMixedModel):
         function as the streamed rows.  N x nodes on the host: the dense protocol is the small-N one."""
         if self._offset is not None:
             rho = rho + self._offset
+        if self.link != 'logit':
+            # `cross_hessian` of the base class subtracts y from the first value; a1' of these links has no such term, so y is
+            # ADDED here (met by what is returned, not by an override: (a1' + y) - y differs from a1' by an ulp of |y| at most)
+            a1, a2 = link_row_derivs(self.link, rho, s, self._y, 1.0 if self._trials is None else self._trials, self.gh_x, self.gh_w)
+            return a1 + self._y, a2
         t = rho[:, None] + np.sqrt(np.maximum(s, 0.0))[:, None] * (np.sqrt(2.0) * self.gh_x)[None, :]
         sg = expit(t)
         wk = self.gh_w / np.sqrt(np.pi)
         p_rho, p_s = (sg * wk).sum(1), 0.5 * (sg * (1.0 - sg) * wk).sum(1)
         return (p_rho, p_s) if self._trials is None else (self._trials * p_rho, self._trials * p_s)
+
+
+    def _response_mean(self, rho, s, trials):
+        if self.link == 'logit':
+            return super()._response_mean(rho, s, trials)
+        return link_response_mean(self.link, rho, s, trials, self.gh_x, self.gh_w)
 
 
 class NegBinomialGLMMObjective(BinomialGLMMObjective):

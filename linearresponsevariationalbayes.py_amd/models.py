@@ -621,6 +621,11 @@ class DeviceContext(object):
         t = _hip.as_f64(trials).ravel()
         self._check(self._lib.lrvb_set_trials(self._h, _hip.ptr(t), t.size))
 
+    def set_link(self, link):
+        """The link of the binomial mixed model: 0 logit (the default), 1 probit, 2 cloglog (lrvb_set_link).  Only the
+        `glmm_binomial_*` entries read it; the call drops the resident group sums and factor."""
+        self._check(self._lib.lrvb_set_link(self._h, int(link)))
+
     def glmm_binomial_terms(self, mean, var, e, r, gh_x, gh_w, want_grad=True, want_hess=True, want_border=True):
         """Data term of the binomial mixed model with K effects per group, the trials of `set_trials` and the offset of
         `set_offset` (lrvb_glmm_binomial_terms): what `glmm_slopes_terms` returns, in its layouts.  The group sums stay

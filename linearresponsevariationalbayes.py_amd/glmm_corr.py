@@ -301,7 +301,7 @@ class _CorrelatedArrow(_SlopesArrow):
         eta = self._eta(fv, True)
         cf = self._closed(eta, want_border=False)    # the group sums of the point stay resident; the border is not copied back
         g, Hgg, rows, Hx, loc_f = self._arrow_to_free(cf, eta)
-        if self._external is None:
+        if self._external_stats is None:
             s = self._coupled_scaling(eta)
             M = self._device_schur(eta, loc_f) * s[:, None] * s[None, :]
         else:

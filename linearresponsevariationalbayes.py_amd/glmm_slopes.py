@@ -41,8 +41,8 @@ from .block_arrow import (block_arrow_to_free, block_arrow_matvec, block_arrow_d
                           block_arrow_schur_term, block_arrow_local_solve, block_arrow_solve, block_arrow_solve_by_phases,
                           block_arrow_group_cov, block_arrow_group_cov_by_phases, unpack_group_cov, predict_rows,
                           _to_groups, _from_groups, _local_index, _local_chol)
-from .models import DeviceContext, DeclaredHypers, refuse_double_reduction
-from .packing import HyperVectorParam, ResidentVector
+from .models import DeviceContext, DeviceModel
+from .packing import HyperVectorParam
 from .quadform import gamma_prior_hyper_grad, gamma_prior_hyper_cross
 from .hierarchical import _gamma_block, _gamma_entropy
 
@@ -192,12 +192,12 @@ def split_influence_operand(A, P, K, G):
     return np.ascontiguousarray(A[:, :2 * P]), np.ascontiguousarray(Al).reshape(G, 2 * K, Q)
 
 
-class _LogisticMixedModel(DeclaredHypers):
+class _LogisticMixedModel(DeviceModel):
     """What the logistic mixed models share -- everything but the parameter layout and the device entries, for K effects per
     group.  A model gives `_layout` and the four device hooks `_terms`, `_schur`, `_obs_influence` and `_group_influence`, which
     speak the K-generic layouts of include/lrvb_hip.h (group sums G x ncol, closed-form entries G x 2 K x 3, e and r as G x K);
     `_solve_on_device` where it has a device-resident block-arrow solve."""
-    _lrvb_device_functor = True
+    _stats_at_point = True
     _loss = 'logistic'                               # the loss the device context is created with
 
     def __init__(self, par, x, y, z, groups, n_groups, beta_prior_info, mu_prior, tau_prior, gh_deg, names, weights, device):
@@ -226,13 +226,8 @@ class _LogisticMixedModel(DeclaredHypers):
         self.ctx.set_groups(self._groups, self.G)
         if z is not None:
             self.ctx.set_group_design(z)
-        w0 = np.ones(self.n_obs) if weights is None else _hip.as_f64(weights).ravel().copy()
-        self._declare_hyper('weights', HyperVectorParam('weights', self.n_obs, val=w0))
-        self.tilt_par = None
-        self._w_res = ResidentVector()
+        self._declare_weights(self.n_obs, weights)
         self._x, self._z = x, z
-        self._external = None
-        self._point_key = None
         self._dev_factor_key = None                  # what the factors of solve(on_device=True) were built at
         self._gcov = None                            # (that key, cov_beta) while the group covariance of `group_cov` is resident
         self._push_state()                           # the initial weights on the device: direct calls on `ctx` see them from the start
@@ -309,12 +304,6 @@ class _LogisticMixedModel(DeclaredHypers):
         j1, j2 = self._jac(eta)
         return block_arrow_to_free(cf, j1, j2, self.n_global, self.G, self.K)
 
-    def _push_state(self):
-        w = self._w_res.changed(self.weights_par)
-        if w is not None:
-            self.ctx.set_weights(w)
-            self._point_key = None
-
     # ---- data pieces (GPU) ------------------------------------------------------------------------------------------
     def _pieces_of(self, val, gg, Hb, gs):
         if gs is None:
@@ -348,23 +337,13 @@ class _LogisticMixedModel(DeclaredHypers):
 
     def set_reduced_stats(self, flat, eta=None):
         """Install statistics summed over all shards for the point eta (None = use this process's own rows again)."""
-        refuse_double_reduction(getattr(self, 'ctx', None), flat)
-        self._point_key = None
-        if flat is None:
-            self._external = None
-            return
-        flat = np.asarray(flat, dtype=np.float64).ravel()
-        if flat.size != self.stats_size() or eta is None:
-            raise ValueError('expected {} statistics and the point they were formed at'.format(self.stats_size()))
-        self._external = (np.asarray(eta, dtype=np.float64).copy(), flat.copy())
+        self._install_reduced_stats(flat, self.stats_size(), eta)
 
     def _data(self, eta, want_grad, want_hess, want_border=True):
-        if self._external is None:
+        f = self._installed_stats(eta)
+        if f is None:
             return self._device_terms(eta, want_grad, want_hess, want_border)
-        if not np.array_equal(self._external[0], eta):
-            raise ValueError('the installed statistics were formed at another point')
         P, G = self.P, self.G
-        f = self._external[1]
         o = 1 + 2 * P
         return self._pieces_of(float(f[0]), f[1:o], f[o:o + 3 * P * P].reshape(3, P, P), f[o + 3 * P * P:].reshape(G, -1))
 
@@ -376,26 +355,16 @@ class _LogisticMixedModel(DeclaredHypers):
                                         want_hess=want_hess)
 
     def _arrow(self, x, is_free):
-        """(grad, Hgg, rows, Hx, loc) at x in its own coordinates, cached per point, weights and hyper-parameters."""
-        self._push_state()
-        key = (bool(is_free), np.asarray(x, dtype=np.float64).tobytes(), self._w_res.key, self._hyper_state_key(),
-               None if self._external is None else id(self._external))
-        if self._point_key != key:
-            eta = self._eta(x, is_free)
+        """(grad, Hgg, rows, Hx, loc) at x in its own coordinates, cached per point and `_data_key`."""
+        eta = self._eta(x, is_free)                  # on a hit too: `par` holds the point afterwards
+
+        def make():
             cf = self._closed(eta)
-            if is_free:
-                self._pieces = self._arrow_to_free(cf, eta)
-            else:
-                self._pieces = (cf['grad'], cf['Hgg'], cf['rows'], cf['Hx'], cf['loc'])
-            self._point_key = key
-        else:
-            self._eta(x, is_free)
+            return self._arrow_to_free(cf, eta) if is_free else (cf['grad'], cf['Hgg'], cf['rows'], cf['Hx'], cf['loc'])
+        self._pieces = self._at_point('arrow', x, is_free, make)
         return self._pieces
 
     # ---- functor protocol -------------------------------------------------------------------------------------------
-    def __call__(self):
-        return self.value(np.asarray(self.par.get_free(), dtype=np.float64), True)
-
     @_hip.host_blas
     def value(self, x, is_free=True):
         return self._closed(self._eta(x, is_free), False, False)['value']
@@ -452,7 +421,7 @@ class _LogisticMixedModel(DeclaredHypers):
         cf = self._closed(eta, want_border=False)    # the group sums of the point stay resident; the border is not copied back
         g, Hgg, rows = cf['grad'], cf['Hgg'].copy(), cf['rows']
         loc_f = block_arrow_to_free(cf, j1, j2, ng, G, K)[4]
-        if self._external is None:
+        if self._external_stats is None:
             _, ib, e_mu, _, a, b, e, ig = self._split(eta)
             r = 1.0 / ig
             d = e - e_mu[None, :]
@@ -477,9 +446,8 @@ class _LogisticMixedModel(DeclaredHypers):
         return out
 
     def _resident_key(self, fv):
-        """What the Schur complement resident on the global context was built at: point, weights, hyper-parameters."""
-        return (np.asarray(fv, dtype=np.float64).tobytes(), self._w_res.key, self._hyper_state_key(),
-                None if self._external is None else id(self._external))
+        """What the Schur complement resident on the global context was built at: the point and `_data_key`."""
+        return (np.asarray(fv, dtype=np.float64).tobytes(), self._data_key())
 
     # ---- the whole arrow: solve, covariance of any moment, weight influence --------------------------------------------------
     def _solve_on_device(self, x, R, is_free):
@@ -703,7 +671,7 @@ class _SlopesArrow:
         coordinates is Hx[r, l] = s_r C_g[l, r] for the device's C_g."""
         if not is_free:
             raise ValueError('on_device=True solves in free coordinates')
-        if self._external is not None:
+        if self._external_stats is not None:
             raise ValueError('on_device=True uses the group sums resident on this device, not installed statistics')
         fv = _hip.as_f64(x).ravel()
         self._push_state()

@@ -20,8 +20,8 @@ from scipy import special
 from scipy import sparse as sp_sparse
 
 from . import _hip
-from .models import DeviceContext, DeclaredHypers, sym_to_vech, vech_to_sym, refuse_double_reduction
-from .packing import VectorParam, HyperVectorParam, ResidentVector
+from .models import DeviceContext, DeviceModel, sym_to_vech, vech_to_sym
+from .packing import VectorParam, HyperVectorParam
 from .quadform import (duplication_matrix, mvn_prior_hyper_grad, mvn_prior_hyper_cross, gamma_prior_hyper_grad,
                        gamma_prior_hyper_cross)
 
@@ -40,8 +40,7 @@ def _gamma_entropy(a, b):
     return a - np.log(b) + special.gammaln(a) + (1.0 - a) * special.digamma(a)
 
 
-class LMMObjective(DeclaredHypers):
-    _lrvb_device_functor = True
+class LMMObjective(DeviceModel):
 
     def __init__(self, par, x, y, groups, n_groups, beta_prior_mean=None, beta_prior_info=None,
                  mu_prior_mean=0.0, mu_prior_info=1.0, tau_y_prior=(1.0, 1.0), tau_mu_prior=(1.0, 1.0),
@@ -58,12 +57,7 @@ class LMMObjective(DeclaredHypers):
         self.ctx = DeviceContext(par.layout_blocks(), loss='data_only', n_obs=self.n_obs, n_cols=p + 1, device=device)
         self.ctx.set_data(_hip.SLOT_X, np.hstack([x, y]))
         self.ctx.set_groups(groups, G)
-        w0 = np.ones(self.n_obs) if weights is None else _hip.as_f64(weights).ravel().copy()
-        self._declare_hyper('weights', HyperVectorParam('weights', self.n_obs, val=w0))
-        self.tilt_par = None
-        self._w_res = ResidentVector()
-        self._stats_cache = None
-        self._external_stats = None
+        self._declare_weights(self.n_obs, weights)
 
     # ---- the priors are hyper-parameters (LRVB/ModelSensitivity.py:555-612: prior sensitivity) -------------------------
     def _declare_priors(self, beta_prior_mean, beta_prior_info, mu_prior_mean, mu_prior_info, tau_y_prior, tau_mu_prior):
@@ -190,50 +184,32 @@ class LMMObjective(DeclaredHypers):
                              and self._iby == self._iay + 1 and self._ibm == self._iam + 1 and p <= 57)
 
     # ---- sufficient statistics (GPU) ---------------------------------------------------------
-    def _push_state(self):
-        w = self._w_res.changed(self.weights_par)              # O(1) for the objective's own HyperVectorParam
-        if w is not None:
-            self.ctx.set_weights(w)
-            self._stats_cache = None
-            self._S_dev = None
-
     def invalidate_stats(self):
         """Forget the cached statistics (the weights on the device were changed behind this object's back, or a
         benchmark wants the pass over the observations inside every step)."""
-        self._stats_cache = None
-        self._S_dev = None
+        self._forget('stats', 'S_dev')
 
     def device_stats(self):
         """S (q x q, host copy) with the group sums left ON THE DEVICE, both summed over the ranks inside the library
-        when the context carries a reduce hook (`ShardedObjective`, `native_comm_init`)."""
+        when the context carries a reduce hook (`ShardedObjective`, `native_comm_init`): the cached copy keys on
+        `_data_key`, so a hook installed or removed since (local vs global sums) drops it."""
         self._push_state()
-        self._check_hook_epoch()
-        if getattr(self, '_S_dev', None) is None:
-            self._S_dev = self.ctx.grouped_stats(want_S=True, want_gs=False)[0]
-        return self._S_dev
-
-    def _check_hook_epoch(self):
-        """A reduce hook installed or removed since the statistics were cached makes them stale (local vs global sums)."""
-        if getattr(self, '_epoch', None) != self.ctx.hook_epoch:
-            self._stats_cache = None
-            self._S_dev = None
-            self._epoch = self.ctx.hook_epoch
+        return self._memo('S_dev', self._data_key(), lambda: self.ctx.grouped_stats(want_S=True, want_gs=False)[0])
 
     def local_stats(self):
         """The statistics as one flat host vector [S (q*q) | group sums (G*(q+1))]: this process's own rows -- the
         buffer a host-side all-reduce (`allreduce_stats`, the gloo tests) sums over shards -- or, when the context carries
         a reduce hook, already the sum over all ranks (one reduction of the device buffer inside `lrvb_grouped_stats`)."""
         self._push_state()
-        self._check_hook_epoch()
-        if self._stats_cache is None:
+
+        def make():
             S, gs = self.ctx.grouped_stats(want_S=True, want_gs=True)
-            self._stats_cache = np.concatenate([S.ravel(), gs.ravel()])
-        return self._stats_cache
+            return np.concatenate([S.ravel(), gs.ravel()])
+        return self._memo('stats', self._data_key(), make)
 
     def set_reduced_stats(self, flat):
         """Install statistics summed over all shards (None = use this process's own)."""
-        refuse_double_reduction(getattr(self, "ctx", None), flat)
-        self._external_stats = None if flat is None else np.asarray(flat, dtype=np.float64).copy()
+        self._install_reduced_stats(flat)
 
     def _stats(self):
         flat = self._external_stats if self._external_stats is not None else self.local_stats()
@@ -372,13 +348,6 @@ class LMMObjective(DeclaredHypers):
         return g, H
 
     # ---- functor protocol (dense; intended for small G) ---------------------------------------------
-    def _eta(self, x, is_free):
-        x = _hip.as_f64(x).ravel()
-        return self.ctx.constrain(x) if is_free else x
-
-    def __call__(self):
-        return self.value(np.asarray(self.par.get_free(), dtype=np.float64), True)
-
     @_hip.host_blas
     def value(self, x, is_free):
         return self.value_vec(self._eta(x, is_free))
@@ -396,9 +365,6 @@ class LMMObjective(DeclaredHypers):
             raise MemoryError('dense Hessian of {} parameters: use global_hessian() (Schur complement)'.format(self.par.vector_size()))
         g, H = self._dense_vec(self._eta(x, is_free))
         return self.ctx.free_hessian_from_vector(x, g, H) if is_free else H
-
-    def hvp(self, x, v, is_free):
-        return self.hessian(x, is_free) @ _hip.as_f64(v).ravel()
 
     # ---- arrow structure: sparse export (SparseObjectives.get_sparse_sub_hessian, :587-594) ------------
     @_hip.host_blas
@@ -508,11 +474,10 @@ class LMMObjective(DeclaredHypers):
             raise ValueError('Free value is the wrong length')
         gc = self._ensure_gctx()
         self._push_state()
-        self._check_hook_epoch()
         idx = [self._ms.start, self._ls.start, self._iem, self._iim, self._iay, self._iby, self._iam, self._ibm]
         want_sums = bool(getattr(self, 'want_diagnostics', False))
         H, sums = self.ctx.lmm_global_hessian(gc, fv, self._host_pack(fv), idx, self._info_lb, want_sums=want_sums, want_host=want_host)
-        self._S_dev = None                                       # (the statistics were formed inside the call, not cached here)
+        self._forget('S_dev')                                    # (the statistics were formed inside the call, not cached here)
         self.last_local_grad_norm = float(np.sqrt(sums[70])) if want_sums else None
         return H
 

@@ -16,12 +16,11 @@ free-coordinate conversion (device) follow.  Same functor protocol as the other 
 import numpy as np
 
 from . import _hip
-from .models import DeviceContext
-from .packing import VectorParam, HyperVectorParam, ResidentVector
+from .models import DeviceContext, DeviceModel
 
 
-class LogitNormalRegressionObjective(object):
-    _lrvb_device_functor = True
+class LogitNormalRegressionObjective(DeviceModel):
+    _stats_at_point = True
 
     def __init__(self, par, x, y, beta_name='beta', prior_info=1.0, gh_deg=20, weights=None, device=0):
         self.par = par
@@ -40,21 +39,8 @@ class LogitNormalRegressionObjective(object):
         self.ctx.set_data(_hip.SLOT_X, x)
         self._y = _hip.as_f64(y).ravel().copy()
         self.ctx.set_data(_hip.SLOT_Y, self._y)
-        w0 = np.ones(self.n_obs) if weights is None else _hip.as_f64(weights).ravel().copy()
-        self.weights_par = HyperVectorParam('weights', self.n_obs, val=w0)
-        self.tilt_par = None
-        self._w_res = ResidentVector()
+        self._declare_weights(self.n_obs, weights)
         self._x = x
-
-    def _push_state(self):
-        w = self._w_res.changed(self.weights_par)              # O(1) for the objective's own HyperVectorParam
-        if w is not None:
-            self.ctx.set_weights(w)
-            self._h_key = None
-
-    def _eta(self, x, is_free):
-        x = _hip.as_f64(x).ravel()
-        return self.ctx.constrain(x) if is_free else x
 
     # ---- observations sharded over GPUs: the data term is a sum over rows --------------------------------------
     def local_stats(self, eta):
@@ -68,23 +54,12 @@ class LogitNormalRegressionObjective(object):
 
     def set_reduced_stats(self, flat, eta=None):
         """Install statistics summed over all shards for the point eta (None = use this process's own rows again)."""
-        if flat is None:
-            self._external = None
-            return
-        flat = np.asarray(flat, dtype=np.float64).ravel()
-        P = self.P
-        if flat.size != 1 + 2 * P + 3 * P * P or eta is None:
-            raise ValueError('expected {} statistics and the point they were formed at'.format(1 + 2 * P + 3 * P * P))
-        self._external = (np.asarray(eta, dtype=np.float64).copy(), flat.copy())
-        self._h_key = None
+        self._install_reduced_stats(flat, 1 + 2 * self.P + 3 * self.P * self.P, eta)
 
     def _data_terms(self, eta, want_grad, want_hess):
         P = self.P
-        ext = getattr(self, '_external', None)
-        if ext is not None:
-            if not np.array_equal(ext[0], eta):
-                raise ValueError('the installed statistics were formed at another point')
-            f = ext[1]
+        f = self._installed_stats(eta)
+        if f is not None:
             Hb = f[1 + 2 * P:].reshape(3, P, P)
             return float(f[0]), f[1:1 + 2 * P], (Hb[0], Hb[1], Hb[2])
         self._push_state()
@@ -113,9 +88,6 @@ class LogitNormalRegressionObjective(object):
         return val, g, H
 
     # ---- functor protocol ------------------------------------------------------------------------------------
-    def __call__(self):
-        return self.value(np.asarray(self.par.get_free(), dtype=np.float64), True)
-
     def value(self, x, is_free=True):
         return float(self._terms(self._eta(x, is_free), False, False)[0])
 
@@ -129,27 +101,7 @@ class LogitNormalRegressionObjective(object):
         _, g, H = self._terms(self._eta(x, is_free))
         return self.ctx.free_hessian_from_vector(x, g, H) if is_free else H
 
-    def _hessian_cached(self, x, is_free):
-        self._push_state()
-        key = (bool(is_free), np.asarray(x, dtype=np.float64).tobytes(), self._w_res.key)
-        if getattr(self, '_h_key', None) != key:
-            self._h_val = self.hessian(x, is_free)
-            self._h_key = key
-        return self._h_val
-
-    def hvp(self, x, v, is_free=True):
-        return self._hessian_cached(x, is_free) @ _hip.as_f64(v).ravel()
-
-    def cg_solve(self, free_val, b, x0=None, Minv=None, tol=1e-8, maxiter=0):
-        H = self._hessian_cached(free_val, True)
-        return self.ctx.cg_solve_matrix(H, b, x0=x0, Minv=Minv, tol=tol, maxiter=maxiter)
-
     # ---- weight sensitivity ------------------------------------------------------------------------------------
-    def hyper_kind(self, hyper_par):
-        if hyper_par is self.weights_par:
-            return 'weights'
-        raise NotImplementedError('the second parameter must be this objective\'s `weights_par`')
-
     def cross_hessian(self, hyper_par, val1, val1_is_free):
         """d2 f / d par1 d w^T (n1 x N): row n of the per-observation gradient matrix is
         [psi_mu x_n | psi_var x_n^2] chained to (mean, info) and, if asked, to free coordinates."""

@@ -16,8 +16,7 @@ quadrature error, exactly where psi is resolved, and a zero design row (s = 0) i
 import numpy as np
 
 from . import _hip
-from .models import DeviceContext
-from .packing import HyperVectorParam, ResidentVector
+from .models import DeviceContext, DeviceModel
 
 MAX_P = 64
 
@@ -91,8 +90,8 @@ def _unvech_lower(v, P):
     return A
 
 
-class LogitNormalMVNRegressionObjective(object):
-    _lrvb_device_functor = True
+class LogitNormalMVNRegressionObjective(DeviceModel):
+    _stats_at_point = True
 
     def __init__(self, par, x, y, beta_name='beta', prior_info=1.0, gh_deg=20, weights=None, device=0):
         self.par = par
@@ -128,24 +127,10 @@ class LogitNormalMVNRegressionObjective(object):
         self.ctx.set_data(_hip.SLOT_X, x)
         self._y = yv
         self.ctx.set_data(_hip.SLOT_Y, self._y)
-        w0 = np.ones(self.n_obs) if weights is None else _hip.as_f64(weights).ravel().copy()
-        self.weights_par = HyperVectorParam('weights', self.n_obs, val=w0)
-        self.tilt_par = None
-        self._w_res = ResidentVector()
+        self._declare_weights(self.n_obs, weights)
         self._x = x
-        self._external = None
         self.n_dense_builds = 0            # data-term Hessians formed (the matrix-free product never adds to it)
         self._lib = _hip.load()
-
-    def _push_state(self):
-        w = self._w_res.changed(self.weights_par)
-        if w is not None:
-            self.ctx.set_weights(w)
-            self._h_key = None
-
-    def _eta(self, x, is_free):
-        x = _hip.as_f64(x).ravel()
-        return self.ctx.constrain(x) if is_free else x
 
     def _point(self, eta):
         P = self.P
@@ -197,22 +182,13 @@ class LogitNormalMVNRegressionObjective(object):
 
     def set_reduced_stats(self, flat, eta=None):
         """Install statistics summed over all shards for the point eta (None = use this process's own rows again)."""
-        if flat is None:
-            self._external = None
-            return
-        flat = np.asarray(flat, dtype=np.float64).ravel()
         D = self.P + self.Pv
-        if flat.size != 1 + D + D * D or eta is None:
-            raise ValueError('expected {} statistics and the point they were formed at'.format(1 + D + D * D))
-        self._external = (np.asarray(eta, dtype=np.float64).copy(), flat.copy())
-        self._h_key = None
+        self._install_reduced_stats(flat, 1 + D + D * D, eta)
 
     def _data_terms(self, eta, m, S, want_grad, want_hess):
         D = self.P + self.Pv
-        if self._external is not None:
-            if not np.array_equal(self._external[0], eta):
-                raise ValueError('the installed statistics were formed at another point')
-            f = self._external[1]
+        f = self._installed_stats(eta)
+        if f is not None:
             return float(f[0]), f[1:1 + D], f[1 + D:].reshape(D, D)
         return self.mvn_terms(m, S, want_grad=want_grad, want_hess=want_hess)
 
@@ -232,9 +208,6 @@ class LogitNormalMVNRegressionObjective(object):
         return val, g, H
 
     # ---- functor protocol ------------------------------------------------------------------------------------
-    def __call__(self):
-        return self.value(np.asarray(self.par.get_free(), dtype=np.float64), True)
-
     def value(self, x, is_free=True):
         return float(self._terms(self._eta(x, is_free), False, False)[0])
 
@@ -253,21 +226,13 @@ class LogitNormalMVNRegressionObjective(object):
         _, g, H = self._terms(self._eta(x, is_free))
         return self.ctx.free_hessian_from_vector(x, g, H) if is_free else H
 
-    def _hessian_cached(self, x, is_free):
-        self._push_state()
-        key = (bool(is_free), np.asarray(x, dtype=np.float64).tobytes(), self._w_res.key)
-        if getattr(self, '_h_key', None) != key:
-            self._h_val = self.hessian(x, is_free)
-            self._h_key = key
-        return self._h_val
-
     def hvp(self, x, v, is_free=True):
         """Hessian times v without forming a D x D matrix: the data term by `lrvb_logitnormal_mvn_hvp`, the chain to
         vech Lambda and (for free coordinates) through the log-Cholesky map as P x P matrix products."""
         P, tau = self.P, self.prior_info
         v = _hip.as_f64(v).ravel()
         eta = self._eta(x, is_free)
-        if self._external is not None:
+        if self._external_stats is not None:
             H = self.hessian(x, is_free)
             return H @ v
         m, Sigma, _ = self._point(eta)
@@ -284,16 +249,7 @@ class LogitNormalMVNRegressionObjective(object):
             return hv
         return np.concatenate([hv[:P], psd_free_vjp_hvp(xf[P:], v[P:], hv[P:], g[P:], P)])
 
-    def cg_solve(self, free_val, b, x0=None, Minv=None, tol=1e-8, maxiter=0):
-        H = self._hessian_cached(free_val, True)
-        return self.ctx.cg_solve_matrix(H, b, x0=x0, Minv=Minv, tol=tol, maxiter=maxiter)
-
     # ---- weight sensitivity ------------------------------------------------------------------------------------
-    def hyper_kind(self, hyper_par):
-        if hyper_par is self.weights_par:
-            return 'weights'
-        raise NotImplementedError('the second parameter must be this objective\'s `weights_par`')
-
     def cross_hessian(self, hyper_par, val1, val1_is_free):
         """d2 f / d par1 d w^T (D x N).  Row n of the per-observation gradient matrix in (m, vech Lambda) is
         [(psi_mu - y_n) x_n | -psi_s delta o vech(z_n z_n^T)], z_n = Sigma x_n, chained to free coordinates if asked."""

@@ -23,8 +23,8 @@ import numpy as np
 from scipy import special, sparse
 
 from . import _hip
-from .models import DeviceContext, DeclaredHypers, refuse_double_reduction
-from .packing import VectorParam, HyperVectorParam, ResidentVector
+from .models import DeviceContext, DeviceModel
+from .packing import VectorParam, HyperVectorParam
 from .specfun import polygamma12
 
 
@@ -46,8 +46,7 @@ def _dirichlet_terms(alpha, d):
     return val, grad, hess
 
 
-class MixtureObjective(DeclaredHypers):
-    _lrvb_device_functor = True
+class MixtureObjective(DeviceModel):
 
     def __init__(self, par, x, pi_prior=1.0, phi_prior=1.0, names=('pi', 'phi', 'z'), weights=None, device=0):
         self.par = par
@@ -84,11 +83,7 @@ class MixtureObjective(DeclaredHypers):
         assert size == ng
         self.ctx = DeviceContext(blocks, loss='data_only', n_obs=N, n_cols=V, device=device)
         self.ctx.set_data(_hip.SLOT_X, x)
-        w0 = np.ones(N) if weights is None else _hip.as_f64(weights).ravel().copy()
-        self._declare_hyper('weights', HyperVectorParam('weights', N, val=w0))
-        self.tilt_par = None
-        self._w_res = ResidentVector()
-        self._external_stats = None
+        self._declare_weights(N, weights)
         # Opt-in for repeated evaluations at ONE local point (benchmarks, several moment sets at an optimum): the
         # N (K - 1) simplex logits are uploaded by the first call and reused from HBM afterwards.  The caller promises
         # not to change them while this is set; `drop_resident_logits()` forces the next upload.
@@ -180,11 +175,6 @@ class MixtureObjective(DeclaredHypers):
         self._fz_on_device = bool(keep)
         return fz
 
-    def _push_state(self):
-        w = self._w_res.changed(self.weights_par)              # O(1) for the objective's own HyperVectorParam
-        if w is not None:
-            self.ctx.set_weights(w)
-
     # ---- pieces ------------------------------------------------------------------------------------
     def _split(self, free_val):
         free_val = _hip.as_f64(free_val).ravel()
@@ -272,13 +262,9 @@ class MixtureObjective(DeclaredHypers):
 
     def set_reduced_stats(self, flat):
         """Install statistics summed over all shards (None = use this process's own)."""
-        refuse_double_reduction(getattr(self, "ctx", None), flat)
-        self._external_stats = None if flat is None else np.asarray(flat, dtype=np.float64).copy()
+        self._install_reduced_stats(flat)
 
     # ---- functor protocol ------------------------------------------------------------------------------
-    def __call__(self):
-        return self.value(np.asarray(self.par.get_free(), dtype=np.float64), True)
-
     @_hip.host_blas
     def value(self, x, is_free=True):
         if not is_free:

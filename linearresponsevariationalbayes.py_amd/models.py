@@ -1240,6 +1240,87 @@ class DeclaredHypers(object):
         return tuple(key)
 
 
+class DeviceModel(DeclaredHypers):
+    """Host state every model class keeps around its device context `self.ctx` (read only when a method is called): the
+    resident observation weights, one-entry memos of data-dependent results, statistics installed by the caller, `__call__`.
+    A class gives `value` and `hessian`; `_eta`, `hvp` and `cg_solve` are the dense defaults."""
+    _lrvb_device_functor = True
+    _stats_at_point = False            # the installed statistics belong to one point, which `set_reduced_stats` must be given
+    _external_stats = _external_eta = None
+    _stats_token = 0                   # bumped by every install or clear of statistics
+
+    def _declare_weights(self, n_obs, weights):
+        w0 = np.ones(n_obs) if weights is None else _hip.as_f64(weights).ravel().copy()
+        if w0.size != n_obs:
+            raise ValueError('weights must have {} entries'.format(n_obs))
+        self._declare_hyper('weights', HyperVectorParam('weights', n_obs, val=w0))
+        self.tilt_par = None
+        self._w_res = ResidentVector()
+
+    def _push_state(self):
+        w = self._w_res.changed(self.weights_par)              # O(1) for the objective's own HyperVectorParam
+        if w is not None:
+            self.ctx.set_weights(w)
+
+    def _data_key(self):
+        """Identity of everything but the point that a data-dependent host cache depends on: weights, hyper-parameters,
+        whether the context reduces over ranks (local or global sums), the installed statistics."""
+        return (self._w_res.key, self._hyper_state_key(), self.ctx.hook_epoch, self._stats_token)
+
+    def _memo(self, slot, key, make):
+        """make(), computed once per key: one entry per named slot."""
+        memos = self.__dict__.setdefault('_memos', {})
+        hit = memos.get(slot)
+        if hit is None or hit[0] != key:
+            hit = memos[slot] = (key, make())
+        return hit[1]
+
+    def _forget(self, *slots):
+        memos = self.__dict__.get('_memos')
+        if memos:                                              # (nothing cached: the per-step path of a benchmark that forgets every step)
+            for slot in slots:
+                memos.pop(slot, None)
+
+    def _at_point(self, slot, x, is_free, make):
+        self._push_state()
+        return self._memo(slot, (bool(is_free), _hip.as_f64(x).ravel().tobytes(), self._data_key()), make)
+
+    # ---- statistics summed over shards by the caller ---------------------------------------------------------------
+    def _install_reduced_stats(self, flat, size=None, eta=None):
+        refuse_double_reduction(getattr(self, 'ctx', None), flat)
+        at_point = self._stats_at_point and flat is not None
+        if flat is not None:
+            flat = np.asarray(flat, dtype=np.float64).ravel()
+            if (size is not None and flat.size != size) or (at_point and eta is None):
+                raise ValueError('expected {} statistics'.format(size) + (' and the point they were formed at' if at_point else ''))
+            flat = flat.copy()
+        self._external_stats, self._external_eta = flat, (np.array(eta, dtype=np.float64) if at_point else None)
+        self._stats_token += 1
+
+    def _installed_stats(self, eta=None):
+        """The installed statistics (None: this process's own rows are used), which must be those of the point eta."""
+        if self._external_eta is not None and not np.array_equal(self._external_eta, eta):
+            raise ValueError('the installed statistics were formed at another point')
+        return self._external_stats
+
+    # ---- functor protocol ------------------------------------------------------------------------------------------
+    def _eta(self, x, is_free):
+        x = _hip.as_f64(x).ravel()
+        return self.ctx.constrain(x) if is_free else x
+
+    def __call__(self):
+        return self.value(np.asarray(self.par.get_free(), dtype=np.float64), True)
+
+    def _hessian_cached(self, x, is_free):
+        return self._at_point('hessian', x, is_free, lambda: self.hessian(x, is_free))
+
+    def hvp(self, x, v, is_free=True):
+        return self._hessian_cached(x, is_free) @ _hip.as_f64(v).ravel()
+
+    def cg_solve(self, free_val, b, x0=None, Minv=None, tol=1e-8, maxiter=0):
+        return self.ctx.cg_solve_matrix(self._hessian_cached(free_val, True), b, x0=x0, Minv=Minv, tol=tol, maxiter=maxiter)
+
+
 class DeviceObjective(DeclaredHypers):
     """A declared objective bound to a parameter object `par` (any object with the packing
     protocol and `layout_blocks()`).

@@ -18,8 +18,8 @@ beta an ArrayParam with lb = 0, Lambda a PosDefMatrixParam) -- BASELINE.json con
 import numpy as np
 
 from . import _hip
-from .models import DeviceContext, DeclaredHypers, sym_to_vech, vech_to_sym, refuse_double_reduction
-from .packing import VectorParam, HyperVectorParam, ResidentVector
+from .models import DeviceContext, DeviceModel, sym_to_vech, vech_to_sym
+from .packing import HyperVectorParam
 
 
 def duplication_matrix(k):
@@ -85,14 +85,13 @@ def gamma_prior_hyper_cross(V, ia, ib, a, b, special):
     return C
 
 
-class QuadraticDataObjective(DeclaredHypers):
+class QuadraticDataObjective(DeviceModel):
     """Base functor.  Subclasses provide the N-independent closed forms:
 
       _terms(eta, S, W)   -> (value, grad (V,), hess (V, V)) in vector coordinates
       _obs_terms(eta)     -> (M (V, q, q) symmetric, c (V,)):  d l_n / d eta_k = 1/2 z_n^T M_k z_n + c_k
       _prior_hyper(kind, eta, want) -> d f / d eps (Ph,) or d2 f / d eta d eps^T (V, Ph) for the priors they declare
     """
-    _lrvb_device_functor = True
 
     def __init__(self, par, z, weights=None, device=0):
         self.par = par
@@ -102,32 +101,18 @@ class QuadraticDataObjective(DeclaredHypers):
         if self.ctx.D != par.free_size() or self.ctx.V != par.vector_size():
             raise ValueError('layout_blocks() of the parameter disagrees with its free/vector sizes')
         self.ctx.set_data(_hip.SLOT_X, z)
-        w0 = np.ones(self.n_obs) if weights is None else _hip.as_f64(weights).ravel().copy()
-        self._declare_hyper('weights', HyperVectorParam('weights', self.n_obs, val=w0))
-        self.tilt_par = None
-        self._w_res = ResidentVector()
-        self._S = None
-        self._W = None
+        self._declare_weights(self.n_obs, weights)
 
     # ---- device state ----------------------------------------------------------------------
-    def _push_state(self):
-        w = self._w_res.changed(self.weights_par)              # O(1) for the objective's own HyperVectorParam
-        if w is not None:
-            self.ctx.set_weights(w)
-            self._S = None
-
     def _stats(self):
-        ext = getattr(self, '_external_stats', None)
+        ext = self._external_stats
         if ext is not None:
             return ext[:-1].reshape(self.q, self.q), float(ext[-1])
         self._push_state()
-        if self._S is None or getattr(self, '_S_epoch', None) != self.ctx.hook_epoch:
-            # GPU: sum_n w_n z_n z_n^T and sum_n w_n in one buffer -- with a reduce hook on the context (observations sharded
-            # over ranks) both arrive summed over all ranks, one reduction.  (A hook installed or removed since the last
-            # evaluation makes the cached statistics stale: they key on the context's hook epoch.)
-            self._S, self._W = self.ctx.weighted_gram(with_sum=True)
-            self._S_epoch = self.ctx.hook_epoch
-        return self._S, self._W
+        # GPU: sum_n w_n z_n z_n^T and sum_n w_n in one buffer -- with a reduce hook on the context (observations sharded
+        # over ranks) both arrive summed over all ranks, one reduction.  (A hook installed or removed since the last
+        # evaluation makes the cached statistics stale: `_data_key` holds the context's hook epoch.)
+        return self._memo('stats', self._data_key(), lambda: self.ctx.weighted_gram(with_sum=True))
 
     # ---- observations sharded over GPUs: the statistics are sums over rows ---------------------------
     def local_stats(self):
@@ -136,30 +121,16 @@ class QuadraticDataObjective(DeclaredHypers):
         exchange (`distributed.allreduce_stats` + `set_reduced_stats`) performs.  With a hook on the context
         (`ShardedObjective`, `native_comm_init`) they are ALREADY the sums over all ranks, reduced on the device inside
         the statistics call; `gram` likewise returns the global G^T G then."""
-        self._external_stats = None
+        if self._external_stats is not None:
+            self._install_reduced_stats(None)
         S, W = self._stats()
         return np.concatenate([np.asarray(S, dtype=np.float64).ravel(), [W]])
 
     def set_reduced_stats(self, flat):
         """Install statistics summed over all shards (None = use this process's own)."""
-        refuse_double_reduction(getattr(self, "ctx", None), flat)
-        if flat is None:
-            self._external_stats = None
-            return
-        flat = np.asarray(flat, dtype=np.float64).ravel()
-        if flat.size != self.q * self.q + 1:
-            raise ValueError('expected {} statistics'.format(self.q * self.q + 1))
-        self._external_stats = flat.copy()
-        self._h_key = None
-
-    def _eta(self, x, is_free):
-        x = _hip.as_f64(x).ravel()
-        return self.ctx.constrain(x) if is_free else x
+        self._install_reduced_stats(flat, self.q * self.q + 1)
 
     # ---- functor protocol ------------------------------------------------------------------
-    def __call__(self):
-        return self.value(np.asarray(self.par.get_free(), dtype=np.float64), True)
-
     def _terms_vg(self, eta, S, W):
         """(value, gradient) only; subclasses whose Hessian blocks are expensive override this."""
         return self._terms(eta, S, W)[:2]
@@ -187,17 +158,6 @@ class QuadraticDataObjective(DeclaredHypers):
             return H
         return self.ctx.free_hessian_from_vector(x, g, H)      # J^T H J + sum_k g_k d2 eta_k, on device
 
-    def _hessian_cached(self, x, is_free):
-        self._push_state()
-        key = (bool(is_free), np.asarray(x, dtype=np.float64).tobytes(), self._w_res.key, self._hyper_state_key(), self.ctx.hook_epoch)
-        if getattr(self, '_h_key', None) != key:
-            self._h_val = self.hessian(x, is_free)
-            self._h_key = key
-        return self._h_val
-
-    def hvp(self, x, v, is_free):
-        return self._hessian_cached(x, is_free) @ _hip.as_f64(v).ravel()
-
     @_hip.host_blas
     def gram(self, free_val):
         """G^T G of the per-observation gradient matrix in free coordinates (Kronecker rows generated
@@ -209,9 +169,10 @@ class QuadraticDataObjective(DeclaredHypers):
         """H(free_val)^-1 b by conjugate gradients on the device; the Hessian is assembled once and
         stays resident for further right-hand sides at the same point."""
         H = self._hessian_cached(free_val, True)
-        resident = getattr(self, '_cg_key', None) == self._h_key
+        key = self._memos['hessian'][0]
+        resident = getattr(self, '_cg_key', None) == key
         out = self.ctx.cg_solve_matrix(None if resident else H, b, x0=x0, Minv=Minv, tol=tol, maxiter=maxiter)
-        self._cg_key = self._h_key
+        self._cg_key = key
         return out
 
     def _prior_hyper(self, kind, eta, want):
@@ -390,7 +351,7 @@ class MVNRegressionObjective(QuadraticDataObjective):
         """The (k(k+1)/2)^2 block of q(beta)'s information matrix is three Kronecker products of k x k matrices: the device
         writes it from the factors (lrvb_hvec_add_symkron) and converts the assembled matrix to free coordinates; the host
         sends the rest of the vector-coordinate Hessian (its other blocks are O(V k) numbers)."""
-        if is_free and getattr(self, '_external_stats', None) is None and not getattr(self, 'stepwise', False) and hasattr(self.ctx, 'mvnreg_hessian') \
+        if is_free and self._external_stats is None and not getattr(self, 'stepwise', False) and hasattr(self.ctx, 'mvnreg_hessian') \
                 and self._ia == self._ls.stop and self._ib == self._ia + 1 and self._ms.stop == self._ls.start:
             return self.device_hessian(x)[0]
         S, W = self._stats()

@@ -15,15 +15,14 @@ import numpy as np
 import scipy.sparse.linalg
 
 from . import _hip
-from .models import DeviceContext
-from .packing import ArrayParam, HyperVectorParam, ResidentVector, _box_d1_d2
+from .models import DeviceContext, DeviceModel
+from .packing import ArrayParam, _box_d1_d2
 
 MAX_CLASSES = 17
 MAX_COLS = 1024
 
 
-class SoftmaxRegressionObjective(object):
-    _lrvb_device_functor = True
+class SoftmaxRegressionObjective(DeviceModel):
 
     def __init__(self, par, x, y, n_classes, beta_name='beta', prior_info=1.0, prior_mean=None, weights=None, device=0):
         K = int(n_classes)
@@ -66,26 +65,10 @@ class SoftmaxRegressionObjective(object):
         self.ctx.set_data(_hip.SLOT_X, x)
         self._y = y.astype(np.int32)
         self.ctx.softmax_set_labels(self._y, K)
-        w0 = np.ones(N) if weights is None else _hip.as_f64(weights).ravel().copy()
-        if w0.size != N:
-            raise ValueError('weights must have {} entries'.format(N))
-        self.weights_par = HyperVectorParam('weights', N, val=w0)
-        self.tilt_par = None
-        self._w_res = ResidentVector()
+        self._declare_weights(N, weights)
         self._x = x
-        self._pt = None
         self._lb, self._ub = beta._lb, beta._ub
         self._identity_map = bool(np.all(np.isneginf(self._lb)) and np.all(np.isposinf(self._ub)))     # free = vector coordinates
-
-    def _push_state(self):
-        w = self._w_res.changed(self.weights_par)
-        if w is not None:
-            self.ctx.set_weights(w)
-            self._pt = None
-
-    def _eta(self, x, is_free):
-        x = _hip.as_f64(x).ravel()
-        return self.ctx.constrain(x) if is_free else x
 
     # ---- vector coordinates --------------------------------------------------------------------------------------
     def _terms(self, eta, want_grad=True, want_hess=True):
@@ -101,18 +84,14 @@ class SoftmaxRegressionObjective(object):
 
     # per point: the diagonal Jacobian of the box map and the diagonal second-order term of the free conversion
     def _point(self, x, is_free):
-        x = _hip.as_f64(x).ravel()
-        key = (bool(is_free), x.tobytes(), self._w_res.key)
-        if self._pt is None or self._pt[0] != key:
+        def make():
             eta = self._eta(x, is_free)
             g = self._terms(eta, True, False)[1]
-            if is_free:
-                d1, d2 = self._box_diag(x)
-                jd, td = d1, g * d2
-            else:
-                jd, td = np.ones(self.D), np.zeros(self.D)
-            self._pt = (key, eta, g, jd, td)
-        return self._pt
+            if not is_free:
+                return eta, np.ones(self.D), np.zeros(self.D)
+            d1, d2 = self._box_diag(x)
+            return eta, d1, g * d2
+        return self._at_point('point', x, is_free, make)
 
     def _box_diag(self, x):
         """First and second derivatives of the (element-wise) box map vector = constrain(free): the diagonal of the free-to-vector
@@ -122,9 +101,6 @@ class SoftmaxRegressionObjective(object):
         return _box_d1_d2(_hip.as_f64(x).ravel(), self._lb, self._ub)
 
     # ---- functor protocol ------------------------------------------------------------------------------------------
-    def __call__(self):
-        return self.value(np.asarray(self.par.get_free(), dtype=np.float64), True)
-
     def value(self, x, is_free=True):
         return float(self._terms(self._eta(x, is_free), False, False)[0])
 
@@ -140,8 +116,7 @@ class SoftmaxRegressionObjective(object):
 
     def hvp(self, x, v, is_free=True):
         """Matrix-free: one fused pass over X per product (`lrvb_softmax_hvp`)."""
-        self._push_state()
-        _, eta, _, jd, td = self._point(x, is_free)
+        eta, jd, td = self._point(x, is_free)
         u = jd * _hip.as_f64(v).ravel()
         hu = self.ctx.softmax_hvp(eta, self.K, u) + self.prior_info * u
         return jd * hu + td * _hip.as_f64(v).ravel()
@@ -161,11 +136,6 @@ class SoftmaxRegressionObjective(object):
         return sol, int(info), count[0]
 
     # ---- weight sensitivity --------------------------------------------------------------------------------------
-    def hyper_kind(self, hyper_par):
-        if hyper_par is self.weights_par:
-            return 'weights'
-        raise NotImplementedError('the second parameter must be this objective\'s `weights_par`')
-
     def _logits(self, eta):
         z = np.zeros((self.n_obs, self.K))
         z[:, 1:] = self._x @ eta.reshape(self.K - 1, self.P).T

@@ -64,7 +64,7 @@ par4 = lmm_par(p4, G4)
 fun4 = vb.LMMObjective(par4, x4, y4, gid4, G4)
 th4 = par4.get_free()
 def stats4():
-    fun4._w_res.key = None; fun4._stats_cache = None
+    fun4._w_res.key = None; fun4.invalidate_stats()
     return fun4.local_stats()
 ms, _ = timeit(stats4); print('C4  shard N=1.25e6 p=43 G=1e4: sufficient statistics (host weights in) %.2f ms' % ms)
 ms, HS4 = timeit(lambda: fun4.global_hessian(th4), reps=2); print('C4  Schur complement onto the %d global parameters %.1f ms' % (HS4.shape[0], ms))

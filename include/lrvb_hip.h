@@ -539,7 +539,7 @@ int lrvb_glmm_slopes_group_influence(lrvb_ctx* ctx, const double* mean, const do
 /* ---- Poisson mixed model with K <= 4 independent random effects per group ---------------------------
  *   y_n ~ Poisson(exp(o_n + x_n . beta + z_n . u_g(n))),  q(beta_j) = N(mean_j, var_j),  q(u_gk) = N(e_gk, r_gk).
  * The per-row offset o (log exposure; n doubles) lives in one device buffer of its own.  offset == NULL clears it (the offset is
- * then zero); it is replaced by the next call.  The three lrvb_glmm_poisson_* and the three lrvb_glmm_binomial_* entries read
+ * then zero); it is replaced by the next call.  The lrvb_glmm_poisson_*, lrvb_glmm_binomial_* and lrvb_glmm_ztpoisson_* entries read
  * it; no other entry looks at it (the logistic lrvb_glmm_slopes_* entries in particular do not).  The call drops the resident
  * group sums and factor (they were formed under another offset).  A length other than n_obs is found when a Poisson or binomial
  * entry runs: LRVB_ERR_STATE there.  n < 1 with a non-null offset: LRVB_ERR_SIZE.                                             */
@@ -631,6 +631,42 @@ int lrvb_glmm_binomial_group_influence(lrvb_ctx* ctx, const double* mean, const 
                                        const double* r, int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
                                        const double* A_global, const double* A_local, int64_t Q, double* out);
 
+/* ---- zero-truncated Poisson mixed model with K <= 4 independent random effects per group ---------------
+ *   y_n in {1, 2, ..},  P(y_n | t_n) = e^{y_n t_n - u_n} / (y_n! (1 - e^{-u_n})),  u_n = e^{t_n},  t_n = o_n + x_n . beta + z_n . u_g(n):
+ * the count part of a hurdle model (the zero part is the binomial model on 1[y > 0] under any link).  Canonical in t with the
+ * log-partition A(t) = log(e^u - 1) = u + log(-expm1(-u)); A' = u + r is the response mean u / (1 - e^{-u}), r = u / expm1(u).
+ * Data term at (mean, var (P each), e, r (G x K each, group-major)), with the Gauss-Hermite rule of lrvb_glmm_slopes_terms and the
+ * offset of lrvb_set_offset (none: 0):
+ *   rho_n = o_n + x_n . mean + z_n . e_g(n),  s_n as there,  t ~ N(rho_n, s_n)
+ *   value = sum_n w_n [E A(t) - y_n rho_n]                                                       (log y_n! is dropped)
+ *   a1 = w (E A' - y), a2 = w E A'' / 2, c11 = w E A'', c12 = w E A''' / 2, c22 = w E A'''' / 4    (Stein's identity on the nodes)
+ * in the five-row layout, the scratch sizes and the summation order of the logistic entries.  The e^t part of every E A^(k) is
+ * exp(rho + s / 2) exactly and NOT clamped; log(-expm1(-u)) and the derivatives of r go on the caller's nodes.  A point where
+ * exp(rho + s / 2) overflows, or where e^t underflows to 0 on a node, gives a value that is not finite after the reduction: the
+ * call returns LRVB_ERR_INVALID, the other outputs are then unspecified and no sums stay resident.  Arguments, outputs, the column
+ * layout of group_sums_out, want_border, the fixed summation order (two calls at one point are bitwise equal) and the reduce-hook
+ * contract are those of lrvb_glmm_slopes_terms; the group sums stay resident for lrvb_glmm_slopes_schur,
+ * lrvb_glmm_slopes_solve_forward, lrvb_glmm_slopes_solve_back and lrvb_glmm_slopes_group_cov.  The entries read neither
+ * lrvb_set_trials nor lrvb_set_link.  Errors as lrvb_glmm_slopes_terms (P > 64, K < 1, K > 4 or more than 128 nodes:
+ * LRVB_ERR_UNSUPPORTED), and an offset whose length is not n_obs: LRVB_ERR_STATE.  y is not validated here (the Python layer
+ * asks for finite y >= 1).                                                                                                    */
+int lrvb_glmm_ztpoisson_terms(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                              int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes, double* value_out,
+                              double* grad_global_out, double* H_blocks_out, double* group_sums_out, int32_t want_border);
+/* Streamed weight influence of the zero-truncated Poisson mixed model: lrvb_glmm_slopes_obs_influence with, per unit weight,
+ *   a1' = E A' - y_n = exp(rho_n + s_n / 2) + E r(t) - y_n,   a2' = E A'' / 2,   rho_n including the offset.
+ * Operand layouts, the row window, the output, "a window equals the same rows of the full result bitwise" and "no reduce-hook
+ * call" as there; errors as lrvb_glmm_ztpoisson_terms, and n0 > n1 or n1 > n_obs: LRVB_ERR_INVALID.                           */
+int lrvb_glmm_ztpoisson_obs_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                                      int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
+                                      const double* A_global, const double* A_local, int64_t Q, int64_t n0, int64_t n1, double* out);
+/* Group influence of that model: out[g][q] = sum over the rows n of group g of w_n * (the row of lrvb_glmm_ztpoisson_obs_influence)
+ * (G x Q, host), as lrvb_glmm_slopes_group_influence: a fixed-order sum of 2 K + 2 P columns per group, an exact zero row for
+ * an empty group, ONE reduce-hook call on the G x Q result.  Errors as lrvb_glmm_ztpoisson_obs_influence.                     */
+int lrvb_glmm_ztpoisson_group_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e,
+                                        const double* r, int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
+                                        const double* A_global, const double* A_local, int64_t Q, double* out);
+
 /* ---- group blocks of H^-1, fitted values and predictions with their linear-response variance ------------
  * For every mixed model with K <= 4 effects per group.  After a successful lrvb_glmm_slopes_schur (the factor L_g, U_g resident)
  * and a factored free Schur complement S on the caller's side, with
@@ -683,6 +719,12 @@ int lrvb_glmm_binomial_predict(lrvb_ctx* ctx, const double* mean, const double* 
                                int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes, const double* cov_beta,
                                int64_t n0, int64_t n1, const double* x_new, const double* z_new, const int32_t* gid_new,
                                const double* offset_new, const double* trials_new, int64_t n_new, double* out);
+/* The zero-truncated Poisson model: the arguments of lrvb_glmm_binomial_predict without trials_new; the
+ * response-scale mean is that of the TRUNCATED count, E A'(t) = exp(rho + . / 2) + E r(t), r = u / expm1(u) on the nodes.      */
+int lrvb_glmm_ztpoisson_predict(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                                int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes, const double* cov_beta,
+                                int64_t n0, int64_t n1, const double* x_new, const double* z_new, const int32_t* gid_new,
+                                const double* offset_new, int64_t n_new, double* out);
 
 /* ---- multinomial (softmax) regression ---------------------------------------------------------
  * K classes (2 <= K <= 17), labels y_n in {0 .. K-1}, class 0 the reference; coefficients beta ((K-1) x P, row-major, row a

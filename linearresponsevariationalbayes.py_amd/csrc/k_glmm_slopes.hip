@@ -3,6 +3,7 @@
 //   Poisson  (DESIGN.md section 26):  y_n ~ Poisson(exp(o_n + x_n . beta + z_n . u_g(n)))
 //   binomial:  y_n ~ Binomial(m_n, sigma(o_n + x_n . beta + z_n . u_g(n))), and through it NB2
 //   binomial with a probit or cloglog link:  p = Phi(.) or 1 - exp(-exp(.)) in the place of sigma(.)
+//   zero-truncated Poisson:  y_n >= 1,  P(y_n) = Poisson(y_n; lambda_n) / (1 - exp(-lambda_n)),  lambda_n as the Poisson one
 // Per observation rho_n = x_n . m + z_n . e_g, s_n = (x_n o x_n) . v + (z_n o z_n) . r_g and five coefficients a1, a2, c11, c12, c22.
 // Every kernel that walks the rows is written ONCE, as a template over a likelihood policy (k_glmm_walk.h, DESIGN.md sections 27 and
 // 31): LogisticLik (the quadrature k_glmm.hip runs too; with K = 1 and z = 1 this is that model) and PoissonLik
@@ -202,6 +203,7 @@ template <class F>
 static int gs_with_lik(const GlmmLik& lik, F&& f) {
     const LogisticLik::Args q{lik.gx, lik.gw, lik.n_nodes};
     if (lik.kind == GLMM_POISSON) return f(PoissonLik(), PoissonLik::Args(lik.off));
+    if (lik.kind == GLMM_ZTPOISSON) return f(TruncPoissonLik(), TruncPoissonLik::Args{q, lik.off});
     if (lik.kind == GLMM_BINOMIAL && lik.link == GLMM_LINK_PROBIT)
         return f(BinomialLinkLik<GLMM_LINK_PROBIT>(), BinomialLinkLik<GLMM_LINK_PROBIT>::Args{q, lik.off, lik.trials, lik.y});
     if (lik.kind == GLMM_BINOMIAL && lik.link == GLMM_LINK_CLOGLOG)
@@ -673,6 +675,17 @@ void glmm_link_infl_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* __re
     gsi_infl_rows<BinomialLinkLik<LINK>>(n0, R, P, Kz, X, Z, y, gid, m, vb, eg, rg, {{gx, gw, nq}, off, trials, y}, Ag, Al, Q, out);
 }
 
+// The zero-truncated Poisson model: the arguments of the binomial entry without the trials.
+__global__ __launch_bounds__(256)
+void glmm_ztpoisson_infl_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* __restrict__ X, const double* __restrict__ Z,
+                                     const double* __restrict__ off, const double* __restrict__ y, const int* __restrict__ gid,
+                                     const double* __restrict__ m, const double* __restrict__ vb, const double* __restrict__ eg,
+                                     const double* __restrict__ rg, const double* __restrict__ gx, const double* __restrict__ gw, int nq,
+                                     const double* __restrict__ Ag, const double* __restrict__ Al, int Q, double* __restrict__ out)
+{
+    gsi_infl_rows<TruncPoissonLik>(n0, R, P, Kz, X, Z, y, gid, m, vb, eg, rg, {{gx, gw, nq}, off}, Ag, Al, Q, out);
+}
+
 template <class Lik>
 static int gs_launch_infl_rows(lrvb_ctx* c, int Kz, const double* Z, typename Lik::Args la, i64 n0, i64 n1, const int* gid, const double* m,
                                const double* vb, const double* eg, const double* rg, const double* Ag, const double* Al, i64 Q,
@@ -687,6 +700,9 @@ static int gs_launch_infl_rows(lrvb_ctx* c, int Kz, const double* Z, typename Li
         hipLaunchKernelGGL(glmm_binomial_infl_rows_kernel, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
                            (const double*)la.off, (const double*)la.trials, (const double*)c->y.p, gid, m, vb, eg, rg, la.q.gx, la.q.gw,
                            la.q.nq, Ag, Al, (int)Q, out);
+    else if constexpr (std::is_same<Lik, TruncPoissonLik>::value)
+        hipLaunchKernelGGL(glmm_ztpoisson_infl_rows_kernel, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
+                           (const double*)la.off, (const double*)c->y.p, gid, m, vb, eg, rg, la.q.gx, la.q.gw, la.q.nq, Ag, Al, (int)Q, out);
     else if constexpr (gs_link_of<Lik>::value != GLMM_LINK_LOGIT)
         hipLaunchKernelGGL(glmm_link_infl_rows_kernel<gs_link_of<Lik>::value>, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz,
                            (const double*)c->X.p, Z, (const double*)la.off, (const double*)la.trials, (const double*)la.y, gid, m, vb, eg, rg,
@@ -1084,6 +1100,17 @@ void glmm_link_predict_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* _
     gsp_predict_rows<BinomialLinkLik<LINK>>(n0, R, P, Kz, X, Z, gid, m, vb, eg, rg, {{gx, gw, nq}, off, trials, nullptr}, Sbb, gcov, out, ldo);
 }
 
+// The zero-truncated Poisson model: the arguments of the binomial entry without the trials; the mean is E A' = exp(rho + . / 2) + E r.
+__global__ __launch_bounds__(256)
+void glmm_ztpoisson_predict_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* __restrict__ X, const double* __restrict__ Z,
+                                        const double* __restrict__ off, const int* __restrict__ gid, const double* __restrict__ m,
+                                        const double* __restrict__ vb, const double* __restrict__ eg, const double* __restrict__ rg,
+                                        const double* __restrict__ gx, const double* __restrict__ gw, int nq,
+                                        const double* __restrict__ Sbb, const double* __restrict__ gcov, double* __restrict__ out, i64 ldo)
+{
+    gsp_predict_rows<TruncPoissonLik>(n0, R, P, Kz, X, Z, gid, m, vb, eg, rg, {{gx, gw, nq}, off}, Sbb, gcov, out, ldo);
+}
+
 int launch_glmm_slopes_predict_rows(lrvb_ctx* c, const GlmmLik& lik, int Kz, const double* X, const double* Z, i64 n0, i64 n1,
                                     const int* gid, const double* m, const double* vb, const double* eg, const double* rg,
                                     const double* Sbb, const double* gcov, double* out, i64 ldo) {
@@ -1096,6 +1123,9 @@ int launch_glmm_slopes_predict_rows(lrvb_ctx* c, const GlmmLik& lik, int Kz, con
     if (lik.kind == GLMM_POISSON)
         hipLaunchKernelGGL(glmm_poisson_predict_rows_kernel, grid, block, 0, c->stream, n0, R, P, Kz, X, Z, lik.off, gid, m, vb, eg, rg, Sbb,
                            gcov, out, ldo);
+    else if (lik.kind == GLMM_ZTPOISSON)
+        hipLaunchKernelGGL(glmm_ztpoisson_predict_rows_kernel, grid, block, 0, c->stream, n0, R, P, Kz, X, Z, lik.off, gid, m, vb, eg, rg,
+                           lik.gx, lik.gw, lik.n_nodes, Sbb, gcov, out, ldo);
     else if (lik.kind == GLMM_BINOMIAL && lik.link == GLMM_LINK_PROBIT)
         hipLaunchKernelGGL(glmm_link_predict_rows_kernel<GLMM_LINK_PROBIT>, grid, block, 0, c->stream, n0, R, P, Kz, X, Z, lik.off, lik.trials, gid,
                            m, vb, eg, rg, lik.gx, lik.gw, lik.n_nodes, Sbb, gcov, out, ldo);

@@ -358,6 +358,109 @@ struct BinomialLinkLik {
     }
 };
 
+// Zero-truncated Poisson with a per-row offset: y in {1, 2, ..}, P(y | t) = e^{y t - u} / (y! (1 - e^{-u})),
+// u = e^t -- the count part of a hurdle model.  Canonical in t: -log P = A(t) - y t + log y! with the log-partition
+//   A(t) = log(e^u - 1) = u + log(-expm1(-u)),   A' = u + r (the response mean u / (1 - e^{-u})),   A^(k) = u + r^(k-1),  k >= 1,
+// r = u / expm1(u) and its derivatives by the recurrences of BinomialLinkLik<CLOGLOG>::h1 (A = e^t - h1 of that link).  The data
+// term is sum w [E A(t) - y rho], t ~ N(rho, s), rho including the offset; coefficients by Stein's identity in the logistic five-row
+// layout, as LogisticLik::coefs forms them:
+//   value = w (E A - y rho),  a1 = w (E A' - y),  a2 = w E A'' / 2,  c11 = w E A'',  c12 = w E A''' / 2,  c22 = w E A'''' / 4.
+// The e^t part of every E A^(k) is exp(rho + s / 2) EXACTLY: one exp per row, added behind the shuffles and not clamped -- where it
+// overflows the non-finite value reaches the sums and the entry refuses it, as for PoissonLik.  Only log(-expm1(-u)) and r^(k-1) go
+// on the nodes, which the four lanes of a row share as LogisticLik::moments does.  Past u = 700 (r < 1e-301) r is set to 0 and u
+// to 700 in the polynomials, a select; below t = -745 (u = 0) r is 0 / 0 and the row is refused in the same way.  Nodes AND a
+// staged offset, no trials, and y from the walk (MINUS_Y): the response mean E A' is infl's e1.  Fixed order, no atomics.
+struct TruncPoissonLik {
+    struct Args { LogisticLik::Args q; const double* __restrict__ off; };                      // off may be nullptr
+    struct Lds { LogisticLik::Lds q; double s_off[GLMM_T]; };               // the node tables; the offsets of the tile's rows
+    typedef LogisticLik::Moments Moments;
+    static constexpr const char* LIMITS = "zero-truncated Poisson mixed model: P <= 64, 1 <= K <= 4, at most 128 nodes";
+    static bool args_ok(const Args& a) { return LogisticLik::args_ok(a.q); }
+    static constexpr int NCF = 5, NB = 4, DK = 16;
+    static constexpr bool HAS_FACTOR = false;
+    static constexpr bool MINUS_Y = true;
+    static __device__ __forceinline__ int cf_row(int kind) { return kind; }
+    static __device__ __forceinline__ double cf_factor(int) { return 1.0; }
+    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return b * Kz + k; }
+    static __device__ __forceinline__ int d_stride(int) { return DK; }
+
+    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { LogisticLik::init(L.q, a.q, tid); }
+    static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
+    {
+        L.s_off[t] = (a.off && live) ? a.off[src] : 0.0;
+    }
+    static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_off[row]; }
+    static __device__ __forceinline__ int lane_row() { return (int)(threadIdx.x >> 2); }
+
+    // The node parts of A' and A'' at t (N = 2), or of A .. A'''' (N = 5), into g[5 - N ..]: g[0] = log(-expm1(-u)), g[k] = r^(k-1)
+    template <int N>
+    static __device__ __forceinline__ void node(double t, double* g)
+    {
+        const double u = exp(t), uc = fmin(u, 700.0);
+        const double r = u > 700.0 ? 0.0 : uc / expm1(uc);
+        const double q = 1.0 - uc - r, r1 = r * q;
+        g[1] = r; g[2] = r1;
+        if constexpr (N == 5) {
+            const double q1 = -uc - r1, r2 = r1 * q + r * q1, q2 = -uc - r2;
+            g[3] = r2; g[4] = r2 * q + 2.0 * r1 * q1 + r * q2;
+            g[0] = log(-expm1(-u));
+        }
+    }
+    // e1 = E A' (the response mean; the walk subtracts y) and e2 = E A'' = 2 psi_s, on all four lanes of a row
+    static __device__ __forceinline__ void infl(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& e1,
+                                                double& e2)
+    {
+        rho += o;
+        e1 = 0.0; e2 = 0.0;
+        if (live) {
+            const double sd = sqrt(fmax(s, 0.0));
+            for (int k = q4; k < a.q.nq; k += 4) {
+                const double t = rho + sd * L.q.sx[k], wk = L.q.sw[k];
+                double g[5];
+                node<2>(t, g);
+                e1 += wk * g[1]; e2 += wk * g[2];
+            }
+        }
+        e1 += __shfl_xor(e1, 1); e2 += __shfl_xor(e2, 1);
+        e1 += __shfl_xor(e1, 2); e2 += __shfl_xor(e2, 2);
+        const double eu = live ? exp(rho + 0.5 * s) : 0.0;
+        e1 += eu; e2 += eu;
+    }
+    static __device__ __forceinline__ void mean(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& mu)
+    {
+        double e2;
+        infl(L, a, o, live, q4, rho, s, mu, e2);
+    }
+    static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
+    {
+        rho += L.s_off[lane_row()];
+        double e[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        if (live) {
+            const double sd = sqrt(fmax(s, 0.0));
+            for (int k = q4; k < a.q.nq; k += 4) {
+                const double t = rho + sd * L.q.sx[k], wk = L.q.sw[k];
+                double g[5];
+                node<5>(t, g);
+#pragma unroll
+                for (int i = 0; i < 5; ++i) e[i] += wk * g[i];
+            }
+        }
+#pragma unroll
+        for (int off = 1; off <= 2; off <<= 1)
+#pragma unroll
+            for (int i = 0; i < 5; ++i) e[i] += __shfl_xor(e[i], off);
+        const double eu = live ? exp(rho + 0.5 * s) : 0.0;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) e[i] += eu;
+        return {e[0], e[1], e[2], e[3], e[4]};
+    }
+    static __device__ __forceinline__ double coefs(const Lds& L, int row, const Moments& mo, double wi, double yi, double rho, double s,
+                                                   double* k)
+    {
+        return LogisticLik::coefs(L.q, row, mo, wi, yi, rho + L.s_off[row], s, k);
+    }
+};
+
 // ---- what the kernels over group-sorted rows share ----------------------------------------------------------------------------------
 // The head of a tile of sorted rows: thread t < GLMM_T finds row t0 + t's original position, its group (the last g with
 // offs[g] <= i) and whether that group lies whole inside the tile; then the tile's rows of X and Z are gathered into xs (row

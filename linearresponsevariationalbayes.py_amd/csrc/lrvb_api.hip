@@ -2603,9 +2603,13 @@ static GlmmLik glmms_intercept(const double* gh_x, const double* gh_w, int32_t n
 static GlmmLik glmms_logistic(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_LOGISTIC, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false}; }
 static GlmmLik glmms_poisson() { return GlmmLik{GLMM_POISSON, nullptr, nullptr, 0, nullptr, nullptr, false}; }
 static GlmmLik glmms_binomial(const lrvb_ctx* c, const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_BINOMIAL, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, c->glmms_link, nullptr}; }
-static const char* glmms_name(const GlmmLik& lik) { return lik.kind == GLMM_POISSON ? "Poisson" : (lik.kind == GLMM_BINOMIAL ? "binomial" : "logistic"); }
+static GlmmLik glmms_ztpoisson(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_ZTPOISSON, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, LRVB_LINK_LOGIT, nullptr}; }
+static const char* glmms_name(const GlmmLik& lik) {
+    if (lik.kind == GLMM_ZTPOISSON) return "zero-truncated Poisson";
+    return lik.kind == GLMM_POISSON ? "Poisson" : (lik.kind == GLMM_BINOMIAL ? "binomial" : "logistic");
+}
 
-// The argument and state checks of all twelve entries over the rows, in one order (`other_null`: a required pointer of the entry's own is null).
+// The argument and state checks of every entry over the rows, in one order (`other_null`: a required pointer of the entry's own is null).
 // The unit design has no group design to check, and its length message names "e / r" as the intercept entries always have.
 static int glmms_check(lrvb_ctx* c, const GlmmLik& lik, const double* mean, const double* var, int64_t P_in, const double* e_loc,
                        const double* r_loc, int64_t G_in, int64_t K, bool other_null) {
@@ -2719,6 +2723,8 @@ static int glmms_terms(lrvb_ctx* c, GlmmLik lik, const double* mean, const doubl
         LRVB_FAIL(LRVB_ERR_INVALID, "the Poisson data term is not finite at this point: exp(rho + s / 2) overflows for some row (the kernel does not clamp)");
     if (lik.link == LRVB_LINK_CLOGLOG && !std::isfinite(*value_out))
         LRVB_FAIL(LRVB_ERR_INVALID, "the cloglog data term is not finite at this point: exp(rho + s / 2) overflows, or exp(t) underflows to 0, for some row (the kernel does not clamp)");
+    if (lik.kind == GLMM_ZTPOISSON && !std::isfinite(*value_out))
+        LRVB_FAIL(LRVB_ERR_INVALID, "the zero-truncated Poisson data term is not finite at this point: exp(rho + s / 2) overflows, or exp(t) underflows to 0, for some row (the kernel does not clamp)");
     c->glmms_valid = true; c->glmms_K = lik.unit ? 0 : (int)K;           // 0: the sums of lrvb_glmm_terms, for lrvb_glmm_schur only
     if (want_g) LRVB_TRY(d2h(c, grad_global_out, gred, (size_t)(2 * P)));
     if (want_H) LRVB_TRY(d2h(c, H_blocks_out, Hb, (size_t)(3 * P * P)));
@@ -3064,6 +3070,33 @@ extern "C" int lrvb_glmm_binomial_group_influence(lrvb_ctx* c, const double* mea
     return glmms_group_influence(c, glmms_binomial(c, gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out);
 }
 
+// ---- zero-truncated Poisson mixed model, the count part of a hurdle model ----------------------------------
+// The shared bodies with the TruncPoissonLik policy: the caller's nodes and the offset of lrvb_set_offset; neither the trials nor
+// the link of the binomial entries is read.
+extern "C" int lrvb_glmm_ztpoisson_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                         const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                         int32_t n_nodes, double* value_out, double* grad_global_out, double* H_blocks_out,
+                                         double* group_sums_out, int32_t want_border) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_terms(c, glmms_ztpoisson(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, value_out, grad_global_out,
+                       H_blocks_out, group_sums_out, want_border);
+}
+
+extern "C" int lrvb_glmm_ztpoisson_obs_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                                 const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                                 int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, int64_t n0,
+                                                 int64_t n1, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_obs_influence(c, glmms_ztpoisson(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, n0, n1, out);
+}
+
+extern "C" int lrvb_glmm_ztpoisson_group_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                                   const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                                   int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_group_influence(c, glmms_ztpoisson(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out);
+}
+
 // ---- group blocks of H^-1 and predictions with their linear-response variance (k_glmm_slopes.hip) ----------
 static int glmms_group_cov(lrvb_ctx* c, const double* W, const double* s, int64_t P_in, int64_t G_in, int64_t K, int64_t NC, bool arrow,
                            double* out) {
@@ -3176,6 +3209,16 @@ extern "C" int lrvb_glmm_binomial_predict(lrvb_ctx* c, const double* mean, const
     LRVB_TRY(ctx_bind(c));
     return glmms_predict(c, glmms_binomial(c, gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, Gp, K, cov_beta, n0, n1, x_new, z_new,
                          gid_new, offset_new, trials_new, n_new, out);
+}
+
+extern "C" int lrvb_glmm_ztpoisson_predict(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                           const double* r_loc, int64_t Gp, int64_t K, const double* gh_x, const double* gh_w,
+                                           int32_t n_nodes, const double* cov_beta, int64_t n0, int64_t n1, const double* x_new,
+                                           const double* z_new, const int32_t* gid_new, const double* offset_new, int64_t n_new,
+                                           double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_predict(c, glmms_ztpoisson(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, Gp, K, cov_beta, n0, n1, x_new, z_new,
+                         gid_new, offset_new, nullptr, n_new, out);
 }
 
 // ---- logistic regression with a full-covariance Gaussian posterior q(beta) = N(m, Sigma) ----------------------------------

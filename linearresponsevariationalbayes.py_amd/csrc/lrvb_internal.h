@@ -259,9 +259,10 @@ int  launch_glmm_infl_local(lrvb_ctx* c, i64 Q, const double* S, const double* A
 // k_glmm_slopes.hip (the logistic and the Poisson mixed model; P = n_cols <= 64, 1 <= K <= 4; groups and the group design set).
 // The three kernels over the rows are templates over a likelihood policy; GlmmLik picks the instantiation
 // and carries what only it reads: the Gauss-Hermite nodes (logistic, binomial), the per-row offset or nullptr (Poisson, binomial),
-// the per-row trials or nullptr (binomial).  `unit`: the unit group design of the random intercept (logistic,
+// the per-row trials or nullptr (binomial); the zero-truncated Poisson kind carries the
+// nodes and the offset.  `unit`: the unit group design of the random intercept (logistic,
 // K = 1, z = 1, nothing on the device): the host bodies hand the launchers Z = nullptr, and those launch the kernels of k_glmm.hip.
-enum GlmmKind { GLMM_LOGISTIC = 0, GLMM_POISSON = 1, GLMM_BINOMIAL = 2 };
+enum GlmmKind { GLMM_LOGISTIC = 0, GLMM_POISSON = 1, GLMM_BINOMIAL = 2, GLMM_ZTPOISSON = 3 };   // the last: nodes and an offset, no trials
 // `link` (binomial only, LRVB_LINK_*; 0 = logit: BinomialLik) picks the probit or cloglog policy of DESIGN.md section 35, and `y`
 // is the response those two stage themselves (the host bodies fill it in with the offset and the trials).
 struct GlmmLik { GlmmKind kind; const double* gx; const double* gw; int n_nodes; const double* off; const double* trials; bool unit;

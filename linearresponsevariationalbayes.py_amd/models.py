@@ -640,6 +640,26 @@ class DeviceContext(object):
         """G x Q group influence of the binomial mixed model, as `glmm_slopes_group_influence` (lrvb_glmm_binomial_group_influence)."""
         return self._glmm_group_influence(self._lib.lrvb_glmm_binomial_group_influence, True, True, mean, var, e, r, gh_x, gh_w, A)
 
+    # ---- zero-truncated Poisson mixed model (lrvb_glmm_ztpoisson_*): the layouts of the slopes entries, the offset of `set_offset` ----
+    def glmm_ztpoisson_terms(self, mean, var, e, r, gh_x, gh_w, want_grad=True, want_hess=True, want_border=True):
+        """Data term of the zero-truncated Poisson mixed model with K effects per group and the offset of `set_offset`
+        (lrvb_glmm_ztpoisson_terms): what `glmm_slopes_terms` returns, in its layouts.  The group sums stay resident for
+        `glmm_slopes_schur`.  A point at which exp(rho + s / 2) overflows, or e^t underflows to 0 on a node, is a ValueError."""
+        return self._glmm_terms(self._lib.lrvb_glmm_ztpoisson_terms, True, True, mean, var, e, r, gh_x, gh_w, want_grad, want_hess, want_border)
+
+    def glmm_ztpoisson_obs_influence(self, mean, var, e, r, gh_x, gh_w, A, n0=0, n1=None):
+        """(n1 - n0) x Q rows of the zero-truncated Poisson mixed model, as `glmm_slopes_obs_influence` (lrvb_glmm_ztpoisson_obs_influence)."""
+        return self._glmm_obs_influence(self._lib.lrvb_glmm_ztpoisson_obs_influence, True, True, mean, var, e, r, gh_x, gh_w, A, n0, n1)
+
+    def glmm_ztpoisson_group_influence(self, mean, var, e, r, gh_x, gh_w, A):
+        """G x Q group influence of the zero-truncated Poisson mixed model, as `glmm_slopes_group_influence`
+        (lrvb_glmm_ztpoisson_group_influence)."""
+        return self._glmm_group_influence(self._lib.lrvb_glmm_ztpoisson_group_influence, True, True, mean, var, e, r, gh_x, gh_w, A)
+
+    def glmm_ztpoisson_predict(self, mean, var, e, r, gh_x, gh_w, cov_beta, n0=0, n1=None, new=None):
+        """Fitted means of the truncated count (lrvb_glmm_ztpoisson_predict); new rows carry an offset."""
+        return self._glmm_predict(self._lib.lrvb_glmm_ztpoisson_predict, True, 1, mean, var, e, r, gh_x, gh_w, cov_beta, n0, n1, new)
+
     # ---- multinomial (softmax) regression: beta is (K - 1) x n_cols, D = (K - 1) n_cols (lrvb_softmax_*) --------------------
     def softmax_set_labels(self, labels, n_classes):
         y = np.ascontiguousarray(np.asarray(labels).ravel(), dtype=np.int32)

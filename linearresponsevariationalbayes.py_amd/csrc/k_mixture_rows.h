@@ -145,7 +145,12 @@ __device__ __forceinline__ double mx_half_max(double v) {
 #define MX_ST(sbase, voff, val, mask) asm volatile("s_mov_b64 exec, %3\n\tglobal_store_dwordx2 %0, %1, %2\n\ts_mov_b64 exec, -1" \
     :: "v"(voff), "v"(val), "s"(sbase), "s"(mask) : "memory")
 // (cache-policy bits on these stores -- nt, sc0, sc1, both, nt sc1 -- were measured in round 3: 1.148-1.18 ms, inside the noise)
-#define MX_ST16(sbase, voff, val, mask) asm volatile("s_mov_b64 exec, %3\n\tglobal_store_dwordx4 %0, %1, %2\n\ts_mov_b64 exec, -1" \
+// A store of more than 64 bits reads its data registers late: gfx940 and later need TWO wait states before a VALU instruction
+// may overwrite them, and hipcc cannot see the store inside the string.  With one state (the s_mov alone) the v_add that
+// follows the last segment of the first row of a pair overwrote the low dword of lanes 12..15 of each 16 now and then when
+// two workgroups shared a CU (more than 2048 rows), wherever those lanes are unmasked there: 22 of the 31 K, K = 32 not among
+// them.
+#define MX_ST16(sbase, voff, val, mask) asm volatile("s_mov_b64 exec, %3\n\tglobal_store_dwordx4 %0, %1, %2\n\ts_mov_b64 exec, -1\n\ts_nop 0" \
     :: "v"(voff), "v"(val), "s"(sbase), "s"(mask) : "memory")
 #define MX_DMA4(sbase, voff, ldsaddr, mask) asm volatile("s_mov_b32 m0, %2\n\ts_mov_b64 exec, %3\n\tglobal_load_lds_dword %0, %1\n\ts_mov_b64 exec, -1" \
     :: "v"(voff), "s"(sbase), "s"(ldsaddr), "s"(mask) : "memory")

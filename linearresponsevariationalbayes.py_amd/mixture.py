@@ -47,6 +47,13 @@ def _dirichlet_terms(alpha, d):
 
 
 class MixtureObjective(DeviceModel):
+    """The -ELBO of the module docstring with the N simplex rows eliminated on the device.
+
+    Weights.  A row with w_n = 0 counts for exactly nothing in `value`, `grad` and the sufficient statistics: its terms of
+    val2 and S64 are exactly zero and its K - 1 entries of the local gradient are exactly 0.0.  Its local Hessian block is the
+    zero matrix, which is not positive definite, so everything that needs the Schur complement (`global_hessian`,
+    `global_cov`, `global_sensitivity`, `local_stats`, `ctx.mixture_rows(want_schur=True)`) raises `numpy.linalg.LinAlgError`,
+    as it does for any row whose block is indefinite.  Drop such rows from the data instead."""
 
     def __init__(self, par, x, pi_prior=1.0, phi_prior=1.0, names=('pi', 'phi', 'z'), weights=None, device=0):
         self.par = par

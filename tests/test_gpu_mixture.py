@@ -121,6 +121,14 @@ def test_saturated_responsibilities(vb):
     o = om.mixture_rows(fz.ravel(), x, w, lam)
     assert rel_err(val2, o[0]) < 1e-12 and rel_err(gz, o[1]) < 1e-10 and rel_err(S64, o[3]) < 1e-12
     assert rel_err(R, o[4]) < 1e-6
+    # ... and against the row-by-row reference (tests/mixture_rows_reference.py), which does not share the
+    # oracle's conditioning: entry-wise bounds counted from the kernel text, R inside 8 unit_n of every row
+    import mixture_rows_reference as mr
+    ev = mr.evaluate(fz, x, w, lam)
+    assert np.all(np.abs(val2 - ev['val2']) <= ev['val2_bound'])
+    assert np.all(np.abs(gz - ev['gz']) <= ev['gz_bound']), mr.worst(gz, ev['gz'], ev['gz_bound'])
+    assert np.all(np.abs(S64 - ev['S64']) <= ev['S64_bound']), mr.worst(S64, ev['S64'], ev['S64_bound'])
+    assert np.all(np.abs(R - ev['R']) <= ev['R_bound']), mr.worst(R, ev['R'], ev['R_bound'])
     fz2 = fz.copy()
     fz2[::3] *= 200.0                                   # logits of +-1e3: exp underflows to exactly 0
     val2, gz, S64, R = fun.ctx.mixture_rows(K, fz2.ravel(), lam, want_schur=False)

@@ -9,9 +9,13 @@ The likelihood factorises: `HurdlePoissonGLMM` holds a `BinomialGLMMObjective` o
 models' value - log_norm_const() (-ELBO up to the same constants: the lower the better), the LRVB standard errors of beta and mu
 against the mean-field ones for both parts, and fitted means E y = p E [y | y > 0] next to the Poisson model's.
 
-    python examples/hurdle_poisson_glmm.py [--small] [--device-solve]
+    python examples/hurdle_poisson_glmm.py [--small] [--device-solve] [--dispersion PHI]
 
 --device-solve takes the Newton polish and the predictions through the device-resident block-arrow solve (`on_device=True`).
+--dispersion PHI draws the positive counts from the zero-truncated NB2 law with mean lambda_n and dispersion PHI (variance
+lambda + lambda^2 / PHI before truncation) and fits a third model, `HurdleNegBinomialGLMM` with that known PHI (DESIGN.md section
+39): its zero part is the hurdle Poisson model's, so only the count part, `TruncatedNegBinomialGLMMObjective`, is fitted again, and
+its value - log_norm_const() is printed next to the other two.
 """
 import os
 import sys
@@ -65,6 +69,7 @@ def standard_errors(par, fun, th, P, K):
 def main():
     small = '--small' in sys.argv
     device_solve = '--device-solve' in sys.argv
+    dispersion = float(sys.argv[sys.argv.index('--dispersion') + 1]) if '--dispersion' in sys.argv else None
     N, P, G = (20000, 8, 200) if small else (1000000, 64, 10000)
     K = 2
     rng = np.random.default_rng(0)
@@ -80,10 +85,16 @@ def main():
     u_c = mu_c[None, :] + rng.normal(size=(G, K)) / np.sqrt(tau)[None, :]
     p_pos = 1.0 / (1.0 + np.exp(-(x @ beta_z + (z * u_z[gid]).sum(1))))
     lam = np.exp(offset + x @ beta_c + (z * u_c[gid]).sum(1))
-    # zero-truncated Poisson draws by inversion on (P(0), 1)
-    from scipy.stats import poisson
-    p0 = np.exp(-lam)
-    y = np.where(rng.uniform(size=N) < p_pos, np.maximum(poisson.ppf(p0 + rng.uniform(size=N) * (1.0 - p0), lam), 1.0), 0.0)
+    # zero-truncated Poisson (or NB2) draws by inversion on (P(0), 1)
+    from scipy.stats import nbinom, poisson
+    if dispersion is None:
+        p0 = np.exp(-lam)
+        positive = poisson.ppf(p0 + rng.uniform(size=N) * (1.0 - p0), lam)
+    else:
+        pr = dispersion / (dispersion + lam)
+        p0 = pr ** dispersion
+        positive = nbinom.ppf(np.minimum(p0 + rng.uniform(size=N) * (1.0 - p0), 1.0 - 1e-12), dispersion, pr)
+    y = np.where(rng.uniform(size=N) < p_pos, np.maximum(positive, 1.0), 0.0)
     print('counts: %d rows, %.1f %% zeros (a Poisson law of the same mean would have %.1f %%), mean %.2f, variance %.2f'
           % (N, 100.0 * np.mean(y == 0), 100.0 * np.exp(-y.mean()), y.mean(), y.var()))
     names = ['beta[%d]' % j for j in range(P)] + ['mu[%d]' % k for k in range(K)]
@@ -117,6 +128,22 @@ def main():
     print('\nPoisson fit: %.2f s, max |free gradient| %.2e' % (time.perf_counter() - t0, np.max(np.abs(pois.grad(th_p, True)))))
     v_pois = pois.value(th_p, True) + float(np.sum(gammaln(y + 1.0)))     # its constant: -sum log y!
     print('\nvalue - log_norm_const (-ELBO up to common constants; lower is better): hurdle %.1f, Poisson %.1f' % (v_hurdle, v_pois))
+
+    # ---- the hurdle NB2 model: the same zero part, the count part with the known dispersion --------------------------------------
+    if dispersion is not None:
+        par_n = params(P, K, G)
+        hnb = vb.HurdleNegBinomialGLMM(params(P, K, G), par_n, x, y, z, gid, G, dispersion, offset=offset, zero_link='logit')
+        t0 = time.perf_counter()
+        th_n = fit(vb.Objective(par_n, hnb.count), hnb.count, th_c, device_solve)
+        print('\ncount part (zero-truncated NB2, phi = %g): %.2f s, max |free gradient| %.2e'
+              % (dispersion, time.perf_counter() - t0, np.max(np.abs(hnb.count.grad(th_n, True)))))
+        par_n.set_free(th_n)
+        print('beta[:4] fitted %s, simulated %s' % (np.array2string(par_n['beta']['mean'].get()[:4], precision=3), np.array2string(beta_c[:4], precision=3)))
+        v_nb = hnb.value(th_z, th_n) - hnb.log_norm_const()
+        print('value - log_norm_const: hurdle NB2 %.1f against hurdle Poisson %.1f (Poisson %.1f)' % (v_nb, v_hurdle, v_pois))
+        fn = hnb.predict(th_z, th_n, n0=0, n1=6, on_device=device_solve)
+        print('rows 0..5: hurdle NB2 E [y | y > 0] %s, E y %s' % (np.array2string(fn['mean_count_lrvb'], precision=3),
+                                                                 np.array2string(fn['mean_lrvb'], precision=3)))
 
     fitted = hur.predict(th_z, th_c, n0=0, n1=6, on_device=device_solve)
     fp = pois.predict(th_p, n0=0, n1=6, on_device=device_solve)

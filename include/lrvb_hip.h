@@ -667,6 +667,43 @@ int lrvb_glmm_ztpoisson_group_influence(lrvb_ctx* ctx, const double* mean, const
                                         const double* r, int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
                                         const double* A_global, const double* A_local, int64_t Q, double* out);
 
+/* ---- zero-truncated negative binomial (NB2) mixed model with K <= 4 independent random effects per group --
+ *   y_n in {1, 2, ..},  P(y_n | t_n) = NB2(y_n; mu_n = e^{t_n}, phi_n) / (1 - (1 + mu_n / phi_n)^{-phi_n}),  t_n = o_n + x_n . beta + z_n . u_g(n):
+ * the count part of a hurdle model for over-dispersed counts, with a KNOWN per-row dispersion phi_n > 0.
+ * lrvb_set_dispersion, a sibling of lrvb_set_trials: n_obs positive finite values in one device buffer of their own, or NULL to
+ * clear them; replaced by the next call.  Only the lrvb_glmm_ztnegbin_* entries read it.  The call drops the resident group sums,
+ * the factor and the group covariance.  A value that is not positive and finite: LRVB_ERR_INVALID, checked on the host ahead of
+ * everything else (the state is left as it was); n < 1 with a non-null pointer: LRVB_ERR_SIZE (the dispersion is then cleared, as
+ * lrvb_set_trials clears the trials); a length other than n_obs is found when an entry runs: LRVB_ERR_STATE.                    */
+int lrvb_set_dispersion(lrvb_ctx* ctx, const double* phi, int64_t n);
+/* Data term.  The offset of lrvb_set_offset is the SHIFTED one, o_n - log phi_n (as for the NB2 model on the binomial entries),
+ * so that eta = t - log phi ~ N(rho_n, s_n) with rho_n = offset_n + x_n . mean + z_n . e_g(n) and s_n as in lrvb_glmm_slopes_terms.
+ * With sp = softplus, v = phi sp(eta) and g = log(1 - exp(-v)) (the log of 1 - P(y = 0)):
+ *   H(eta) = (y + phi) sp(eta) - y eta + g(eta)                         (lgamma(y + phi) - lgamma(phi) - log y! is dropped)
+ *   value = sum_n w_n E H,  a1 = w E H',  a2 = w E H'' / 2,  c11 = w E H'',  c12 = w E H''' / 2,  c22 = w E H'''' / 4
+ * (Stein's identity on the caller's Gauss-Hermite nodes) in the five-row layout, the scratch sizes and the summation order of the
+ * logistic entries.  Past v = 700 the derivatives of g are exact zeros; where v underflows to 0 on a node (eta below about -745)
+ * the value is not finite after the reduction: the call returns LRVB_ERR_INVALID, the other outputs are then unspecified and no
+ * sums stay resident.  Arguments, outputs, the column layout of group_sums_out, want_border, the fixed summation order (two calls
+ * at one point are bitwise equal) and the reduce-hook contract are those of lrvb_glmm_slopes_terms; the group sums stay resident
+ * for lrvb_glmm_slopes_schur, lrvb_glmm_slopes_solve_forward, lrvb_glmm_slopes_solve_back and lrvb_glmm_slopes_group_cov.  The
+ * entries read neither lrvb_set_trials nor lrvb_set_link.  No dispersion set: LRVB_ERR_STATE ("no dispersion").  The other errors
+ * are those of lrvb_glmm_ztpoisson_terms.  y is not validated here (the Python layer asks for finite y >= 1).                   */
+int lrvb_glmm_ztnegbin_terms(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                             int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes, double* value_out,
+                             double* grad_global_out, double* H_blocks_out, double* group_sums_out, int32_t want_border);
+/* Streamed weight influence of that model: lrvb_glmm_slopes_obs_influence with, per unit weight,
+ *   a1' = (y_n + phi_n) E sigma(eta) + E g'(eta) - y_n,   a2' = E H'' / 2.
+ * Operand layouts, the row window, the output, "a window equals the same rows of the full result bitwise" and "no reduce-hook
+ * call" as there; errors as lrvb_glmm_ztnegbin_terms, and n0 > n1 or n1 > n_obs: LRVB_ERR_INVALID.                             */
+int lrvb_glmm_ztnegbin_obs_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                                     int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
+                                     const double* A_global, const double* A_local, int64_t Q, int64_t n0, int64_t n1, double* out);
+/* Group influence of that model, as lrvb_glmm_ztpoisson_group_influence.  Errors as lrvb_glmm_ztnegbin_obs_influence.          */
+int lrvb_glmm_ztnegbin_group_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e,
+                                       const double* r, int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
+                                       const double* A_global, const double* A_local, int64_t Q, double* out);
+
 /* ---- group blocks of H^-1, fitted values and predictions with their linear-response variance ------------
  * For every mixed model with K <= 4 effects per group.  After a successful lrvb_glmm_slopes_schur (the factor L_g, U_g resident)
  * and a factored free Schur complement S on the caller's side, with
@@ -725,6 +762,14 @@ int lrvb_glmm_ztpoisson_predict(lrvb_ctx* ctx, const double* mean, const double*
                                 int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes, const double* cov_beta,
                                 int64_t n0, int64_t n1, const double* x_new, const double* z_new, const int32_t* gid_new,
                                 const double* offset_new, int64_t n_new, double* out);
+/* The zero-truncated NB2 model: the arguments of lrvb_glmm_binomial_predict with the dispersion of the new
+ * rows (dispersion_new, n_new positive finite values, REQUIRED with new rows: LRVB_ERR_INVALID) in the place of trials_new;
+ * offset_new is the shifted offset o - log phi of the new rows.  The response-scale mean is that of the TRUNCATED count,
+ * E[e^t (1 + R(v))], R = 1 / expm1(v): phi exp(rho + . / 2) in closed form and not clamped, e^t R(v) on the nodes.               */
+int lrvb_glmm_ztnegbin_predict(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                               int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes, const double* cov_beta,
+                               int64_t n0, int64_t n1, const double* x_new, const double* z_new, const int32_t* gid_new,
+                               const double* offset_new, const double* dispersion_new, int64_t n_new, double* out);
 
 /* ---- multinomial (softmax) regression ---------------------------------------------------------
  * K classes (2 <= K <= 17), labels y_n in {0 .. K-1}, class 0 the reference; coefficients beta ((K-1) x P, row-major, row a

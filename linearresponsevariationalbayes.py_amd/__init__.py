@@ -52,7 +52,8 @@ from .glmm_slopes import LogisticGLMMSlopesObjective
 from .glmm_poisson import PoissonGLMMObjective
 from .glmm_binomial import BinomialGLMMObjective, NegBinomialGLMMObjective
 from .glmm_corr import LogisticGLMMCorrObjective, PoissonGLMMCorrObjective
-from .glmm_hurdle import TruncatedPoissonGLMMObjective, HurdlePoissonGLMM
+from .glmm_hurdle import (TruncatedPoissonGLMMObjective, HurdlePoissonGLMM, TruncatedNegBinomialGLMMObjective,
+                          HurdleNegBinomialGLMM)
 from .torch_closure import TorchObjective
 from . import regression as regression_utils
 from . import packing as ProjectionParams

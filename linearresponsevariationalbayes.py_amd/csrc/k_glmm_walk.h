@@ -461,6 +461,175 @@ struct TruncPoissonLik {
     }
 };
 
+// Zero-truncated negative binomial (NB2) with a known per-row dispersion phi and a per-row offset: y in
+// {1, 2, ..}, the count part of a hurdle model for over-dispersed counts.  With eta = t - log phi (the staged offset is the SHIFTED
+// one, o - log phi), sp = softplus and m = y + phi the row's term is, constants dropped,
+//   H(eta) = m sp(eta) - y eta + g(eta),   g = log(1 - exp(-v)),   v = phi sp(eta)      (P(y = 0) = (1 + e^eta)^-phi = exp(-v)):
+// the NB2 term of BinomialLik plus the log of 1 - P(0), which couples phi and eta inside a log and so is no binomial term.  The
+// data term is sum w [E H(eta)], eta ~ N(rho, s), rho including the shifted offset; coefficients by Stein's identity in the
+// logistic five-row layout, as LogisticLik::coefs forms them (MINUS_Y: infl returns e1 = m E sigma + E g', the walk subtracts y):
+//   value = w (E[m sp + g] - y rho),  a1 = w (E[m sigma + g'] - y),  a2 = w E H'' / 2,  c11 = w E H'',  c12 = w E H''' / 2,  c22 = w E H'''' / 4.
+// g by the chain rule in its FACTORED form, every intermediate O(1) down to eta = -745: with v_k = phi sp^(k), R = 1 / expm1(v),
+//   a = v_1 R, b = v_2 R, d = v_3 R, c = v_1 + a           (dR/d eta = -a (1 + R))
+//   g' = a,   g'' = b - a c,   b' = d - a (v_2 + b),   c' = v_2 + g'',   g''' = b' - g'' c - a c',
+//   d' = v_4 R - a (v_3 + d),   b'' = d' - g'' (v_2 + b) - a (v_3 + b'),   g'''' = b'' - g''' c - 2 g'' c' - a (v_3 + g''').
+// In the corner eta < log 1e-3, v < 0.01 the derivatives of order 2 to 4 come from two short series instead (at `node`).
+// Past v = 700 (R < 1e-304) R is 0 by a select (the TruncPoissonLik rule): a huge v gives exact zeros, not inf * 0.  Where v
+// underflows to 0 (eta below about -745) R is 1 / 0: the non-finite value reaches the sums and the entry refuses the point; no
+// clamp.  The response mean of the truncated count is E[mu / (1 - P0)] = E[e^t (1 + R(v))], e^t = phi e^eta: its e^t part is
+// phi exp(rho + s / 2) in closed form, one exp per row and not clamped; e^t R(v) goes on the nodes (-> 1 as t -> -inf, 0 by the
+// same select).  Nodes, offsets, phi and y are staged as BinomialLinkLik stages offset, trials and y (a null y -- the predict
+// walk -- stages zeros); the four lanes of a row share the nodes; five accumulators per lane, m sp^(k) + g^(k) per node, two xor
+// shuffles in fixed order, no atomics.
+struct TruncNegBinLik {
+    struct Args { LogisticLik::Args q; const double* __restrict__ off; const double* __restrict__ disp; const double* __restrict__ y; };   // off may be nullptr
+    struct Lds { LogisticLik::Lds q; double s_off[GLMM_T], s_phi[GLMM_T], s_y[GLMM_T]; };
+    typedef LogisticLik::Moments Moments;
+    static constexpr const char* LIMITS = "zero-truncated negative binomial mixed model: P <= 64, 1 <= K <= 4, at most 128 nodes";
+    static bool args_ok(const Args& a) { return LogisticLik::args_ok(a.q) && a.disp != nullptr; }
+    static constexpr int NCF = 5, NB = 4, DK = 16;
+    static constexpr bool HAS_FACTOR = false;
+    static constexpr bool MINUS_Y = true;
+    static __device__ __forceinline__ int cf_row(int kind) { return kind; }
+    static __device__ __forceinline__ double cf_factor(int) { return 1.0; }
+    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return b * Kz + k; }
+    static __device__ __forceinline__ int d_stride(int) { return DK; }
+
+    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { LogisticLik::init(L.q, a.q, tid); }
+    static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
+    {
+        L.s_off[t] = (a.off && live) ? a.off[src] : 0.0;
+        L.s_phi[t] = live ? a.disp[src] : 1.0;
+        L.s_y[t] = (a.y && live) ? a.y[src] : 0.0;
+    }
+    static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_off[row]; }
+    static __device__ __forceinline__ int lane_row() { return (int)(threadIdx.x >> 2); }
+
+    // 1 / expm1(v), 0 past v = 700 by a select
+    static __device__ __forceinline__ double recip_expm1(double v) { return v > 700.0 ? 0.0 : 1.0 / expm1(fmin(v, 700.0)); }
+
+    // The corner eta < log 1e-3 and v < 0.01: there g'', g''', g'''' are O(e^eta) while a, b, c are O(1), and b - a c keeps an absolute
+    // error of 2^-53 only -- 1e-3 of g'' at eta = -30.  With x = e^eta, g = log phi + eta + M(eta) + L(v),
+    //   M = log(sp / x) = -x / 2 + 5 x^2 / 24 - x^3 / 8 + 251 x^4 / 2880 - 19 x^5 / 288,   L = log((1 - e^-v) / v) = -v / 2 + v^2 / 24 - v^4 / 2880,
+    // and every term of g'' = M'' + L'' v_1^2 + L' v_2, g''' = M''' + L''' v_1^3 + 3 L'' v_1 v_2 + L' v_3,
+    // g'''' = M'''' + L'''' v_1^4 + 6 L''' v_1^2 v_2 + L'' (3 v_2^2 + 4 v_1 v_3) + L' v_4 has the sign and size of the result.  The terms
+    // left out are below 2e-13 (x^6) and 1e-15 (v^6) of it.  Outside the corner the factored form is good to 1e-13 of the result.
+    static constexpr double ETA_SMALL = -6.907755278982137, V_SMALL = 0.01;
+    // the J-th derivative in eta of M: sum_k c_k k^J x^k
+    template <int J>
+    static __device__ __forceinline__ double small_m(double x)
+    {
+        constexpr double p2 = J == 2 ? 4.0 : (J == 3 ? 8.0 : 16.0), p3 = J == 2 ? 9.0 : (J == 3 ? 27.0 : 81.0);
+        constexpr double p4 = J == 2 ? 16.0 : (J == 3 ? 64.0 : 256.0), p5 = J == 2 ? 25.0 : (J == 3 ? 125.0 : 625.0);
+        return x * (-0.5 + x * (p2 * (5.0 / 24.0) + x * (p3 * (-1.0 / 8.0) + x * (p4 * (251.0 / 2880.0) + x * (p5 * (-19.0 / 288.0))))));
+    }
+
+    // H' and H'' at eta = t (N = 2), or H + y eta, H' + y, H'' .. H'''' (N = 5), into h[5 - N ..]; mt = y + phi
+    template <int N>
+    static __device__ __forceinline__ void node(double t, double phi, double mt, double* h)
+    {
+        const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
+        const double sp = (t > 0.0 ? t : 0.0) + log1p(e);
+        const double sg = t >= 0.0 ? ie : e * ie;
+        const double g2 = e * ie * ie;
+        const double v = phi * sp, R = recip_expm1(v);
+        const double v1 = phi * sg, v2 = phi * g2;
+        const double a = v1 * R, b = v2 * R, c = v1 + a;
+        // the corner (see above): t < 0 there, so e = e^eta
+        const bool corner = t < ETA_SMALL && v < V_SMALL;
+        const double lp = -0.5 + v * (1.0 / 12.0 - v * v * (1.0 / 720.0)), lpp = 1.0 / 12.0 - v * v * (1.0 / 240.0);
+        const double gg2 = corner ? small_m<2>(e) + lpp * v1 * v1 + lp * v2 : b - a * c;
+        h[1] = mt * sg + a; h[2] = mt * g2 + gg2;
+        if constexpr (N == 5) {
+            const double om = (1.0 - e) * ie;                            // |1 - 2 sigma|
+            const double g3 = t >= 0.0 ? -g2 * om : g2 * om;
+            const double g4 = g2 * (1.0 - 6.0 * g2);
+            const double v3 = phi * g3, v4 = phi * g4;
+            double gg3, gg4;
+            if (corner) {
+                const double lppp = v * (-1.0 / 120.0);
+                gg3 = small_m<3>(e) + lppp * v1 * v1 * v1 + 3.0 * lpp * v1 * v2 + lp * v3;
+                gg4 = small_m<4>(e) - (1.0 / 120.0) * (v1 * v1) * (v1 * v1) + 6.0 * lppp * v1 * v1 * v2 + lpp * (3.0 * v2 * v2 + 4.0 * v1 * v3)
+                      + lp * v4;
+            } else {
+                const double d = v3 * R;
+                const double b1 = d - a * (v2 + b), c1 = v2 + gg2;
+                gg3 = b1 - gg2 * c - a * c1;
+                const double d1 = v4 * R - a * (v3 + d);
+                const double b2 = d1 - gg2 * (v2 + b) - a * (v3 + b1);
+                gg4 = b2 - gg3 * c - 2.0 * gg2 * c1 - a * (v3 + gg3);
+            }
+            h[0] = mt * sp + log(-expm1(-v)); h[3] = mt * g3 + gg3; h[4] = mt * g4 + gg4;
+        }
+    }
+    // e1 = m E sigma + E g' (the walk subtracts y) and e2 = E H'' = 2 psi_s, on all four lanes of a row
+    static __device__ __forceinline__ void infl(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& e1,
+                                                double& e2)
+    {
+        const int row = lane_row();
+        const double phi = L.s_phi[row], mt = L.s_y[row] + phi;
+        rho += o;
+        e1 = 0.0; e2 = 0.0;
+        if (live) {
+            const double sd = sqrt(fmax(s, 0.0));
+            for (int k = q4; k < a.q.nq; k += 4) {
+                const double t = rho + sd * L.q.sx[k], wk = L.q.sw[k];
+                double h[5];
+                node<2>(t, phi, mt, h);
+                e1 += wk * h[1]; e2 += wk * h[2];
+            }
+        }
+        e1 += __shfl_xor(e1, 1); e2 += __shfl_xor(e2, 1);
+        e1 += __shfl_xor(e1, 2); e2 += __shfl_xor(e2, 2);
+    }
+    // the response mean of the truncated count: phi exp(rho + s / 2) in closed form plus E[e^t R(v)] on the nodes
+    static __device__ __forceinline__ void mean(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& mu)
+    {
+        const double phi = L.s_phi[lane_row()];
+        rho += o;
+        double p = 0.0;
+        if (live) {
+            const double sd = sqrt(fmax(s, 0.0));
+            for (int k = q4; k < a.q.nq; k += 4) {
+                const double t = rho + sd * L.q.sx[k];
+                const double e = exp(-fabs(t));
+                const double v = phi * ((t > 0.0 ? t : 0.0) + log1p(e));
+                p += L.q.sw[k] * (v > 700.0 ? 0.0 : phi * exp(t) * recip_expm1(v));
+            }
+        }
+        p += __shfl_xor(p, 1);
+        p += __shfl_xor(p, 2);
+        mu = live ? phi * exp(rho + 0.5 * s) + p : 0.0;
+    }
+    static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
+    {
+        const int row = lane_row();
+        const double phi = L.s_phi[row], mt = L.s_y[row] + phi;
+        rho += L.s_off[row];
+        double e[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        if (live) {
+            const double sd = sqrt(fmax(s, 0.0));
+            for (int k = q4; k < a.q.nq; k += 4) {
+                const double t = rho + sd * L.q.sx[k], wk = L.q.sw[k];
+                double h[5];
+                node<5>(t, phi, mt, h);
+#pragma unroll
+                for (int i = 0; i < 5; ++i) e[i] += wk * h[i];
+            }
+        }
+#pragma unroll
+        for (int off = 1; off <= 2; off <<= 1)
+#pragma unroll
+            for (int i = 0; i < 5; ++i) e[i] += __shfl_xor(e[i], off);
+        return {e[0], e[1], e[2], e[3], e[4]};
+    }
+    static __device__ __forceinline__ double coefs(const Lds& L, int row, const Moments& mo, double wi, double yi, double rho, double s,
+                                                   double* k)
+    {
+        return LogisticLik::coefs(L.q, row, mo, wi, yi, rho + L.s_off[row], s, k);
+    }
+};
+
 // ---- what the kernels over group-sorted rows share ----------------------------------------------------------------------------------
 // The head of a tile of sorted rows: thread t < GLMM_T finds row t0 + t's original position, its group (the last g with
 // offs[g] <= i) and whether that group lies whole inside the tile; then the tile's rows of X and Z are gathered into xs (row

@@ -231,7 +231,7 @@ extern "C" int lrvb_ctx_destroy(lrvb_ctx* c) {
     DevBuf* all[] = { &c->X, &c->y, &c->w, &c->quadA, &c->quadM, &c->quadB, &c->theta, &c->eta, &c->j1, &c->j2,
                       &c->vtmp, &c->vtmp2, &c->vtmp3, &c->g_eta, &c->g_free, &c->lp, &c->cw, &c->zbuf,
                       &c->part_vec, &c->part_val, &c->stats, &c->tile_part, &c->Heta, &c->Hfree, &c->Jdense,
-                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn, &c->gz, &c->goff, &c->gtr, &c->glmms, &c->glmms_fac, &c->glmms_T, &c->glmms_gcov,
+                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn, &c->gz, &c->goff, &c->gtr, &c->gdisp, &c->glmms, &c->glmms_fac, &c->glmms_T, &c->glmms_gcov,
                       &c->sm.labels, &c->sm.p, &c->sm.wpad, &c->sm.work, &c->sm.col, &c->sm.tiles, &c->sm.rows };
     for (DevBuf* b : all) buf_free(*b);
     if (c->host_pinned) (void)hipHostFree(c->host_pinned);
@@ -2604,8 +2604,10 @@ static GlmmLik glmms_logistic(const double* gh_x, const double* gh_w, int32_t n_
 static GlmmLik glmms_poisson() { return GlmmLik{GLMM_POISSON, nullptr, nullptr, 0, nullptr, nullptr, false}; }
 static GlmmLik glmms_binomial(const lrvb_ctx* c, const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_BINOMIAL, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, c->glmms_link, nullptr}; }
 static GlmmLik glmms_ztpoisson(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_ZTPOISSON, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, LRVB_LINK_LOGIT, nullptr}; }
+static GlmmLik glmms_ztnegbin(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_ZTNEGBIN, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, LRVB_LINK_LOGIT, nullptr}; }
 static const char* glmms_name(const GlmmLik& lik) {
     if (lik.kind == GLMM_ZTPOISSON) return "zero-truncated Poisson";
+    if (lik.kind == GLMM_ZTNEGBIN) return "zero-truncated negative binomial";
     return lik.kind == GLMM_POISSON ? "Poisson" : (lik.kind == GLMM_BINOMIAL ? "binomial" : "logistic");
 }
 
@@ -2629,6 +2631,10 @@ static int glmms_check(lrvb_ctx* c, const GlmmLik& lik, const double* mean, cons
         LRVB_FAIL(LRVB_ERR_STATE, "the offset has %lld entries, the model has %lld observations", (long long)c->goff_n, (long long)c->N);
     if (lik.kind == GLMM_BINOMIAL && c->gtr_n != 0 && c->gtr_n != c->N)
         LRVB_FAIL(LRVB_ERR_STATE, "the trials have %lld entries, the model has %lld observations", (long long)c->gtr_n, (long long)c->N);
+    if (lik.kind == GLMM_ZTNEGBIN && c->gdisp_n == 0)
+        LRVB_FAIL(LRVB_ERR_STATE, "no dispersion: call lrvb_set_dispersion first");
+    if (lik.kind == GLMM_ZTNEGBIN && c->gdisp_n != c->N)
+        LRVB_FAIL(LRVB_ERR_STATE, "the dispersion has %lld entries, the model has %lld observations", (long long)c->gdisp_n, (long long)c->N);
     LRVB_TRY(check_len(P_in, c->P, "mean / var"));
     LRVB_TRY(check_len(G_in, c->n_groups, lik.unit ? "e / r" : "groups of e / r"));
     for (i64 j = 0; j < c->P; ++j) if (!(var[j] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "var[%lld] is not positive", (long long)j);
@@ -2649,6 +2655,7 @@ static int glmms_to_device(lrvb_ctx* c, GlmmLik& lik, double* g) {
     if (lik.kind != GLMM_LOGISTIC) lik.off = c->goff_n ? c->goff.p : nullptr;
     if (lik.kind == GLMM_BINOMIAL) lik.trials = c->gtr_n ? c->gtr.p : nullptr;
     if (lik.link != LRVB_LINK_LOGIT) lik.y = c->y.p;                      // the probit and cloglog policies stage y themselves
+    if (lik.kind == GLMM_ZTNEGBIN) { lik.trials = c->gdisp.p; lik.y = c->y.p; }   // phi rides in the trials slot; y is staged for y + phi
     if (lik.kind == GLMM_POISSON) return LRVB_OK;
     LRVB_TRY(h2d(c, g, lik.gx, (size_t)lik.n_nodes));
     LRVB_TRY(h2d(c, g + 128, lik.gw, (size_t)lik.n_nodes));
@@ -2725,6 +2732,8 @@ static int glmms_terms(lrvb_ctx* c, GlmmLik lik, const double* mean, const doubl
         LRVB_FAIL(LRVB_ERR_INVALID, "the cloglog data term is not finite at this point: exp(rho + s / 2) overflows, or exp(t) underflows to 0, for some row (the kernel does not clamp)");
     if (lik.kind == GLMM_ZTPOISSON && !std::isfinite(*value_out))
         LRVB_FAIL(LRVB_ERR_INVALID, "the zero-truncated Poisson data term is not finite at this point: exp(rho + s / 2) overflows, or exp(t) underflows to 0, for some row (the kernel does not clamp)");
+    if (lik.kind == GLMM_ZTNEGBIN && !std::isfinite(*value_out))
+        LRVB_FAIL(LRVB_ERR_INVALID, "the zero-truncated negative binomial data term is not finite at this point: phi softplus(eta) underflows to 0 on a node, or a moment overflows, for some row (the kernel does not clamp)");
     c->glmms_valid = true; c->glmms_K = lik.unit ? 0 : (int)K;           // 0: the sums of lrvb_glmm_terms, for lrvb_glmm_schur only
     if (want_g) LRVB_TRY(d2h(c, grad_global_out, gred, (size_t)(2 * P)));
     if (want_H) LRVB_TRY(d2h(c, H_blocks_out, Hb, (size_t)(3 * P * P)));
@@ -3097,6 +3106,42 @@ extern "C" int lrvb_glmm_ztpoisson_group_influence(lrvb_ctx* c, const double* me
     return glmms_group_influence(c, glmms_ztpoisson(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out);
 }
 
+// ---- zero-truncated NB2 mixed model, the count part of a hurdle model for over-dispersed counts -----------
+// The per-row dispersion phi: a sibling of lrvb_set_trials.  Checked here, on the host: the kernels divide by expm1(phi softplus).
+extern "C" int lrvb_set_dispersion(lrvb_ctx* c, const double* phi, int64_t n) {
+    LRVB_TRY(ctx_bind(c));
+    if (phi)
+        for (int64_t i = 0; i < n; ++i)
+            if (!(phi[i] > 0.0) || !std::isfinite(phi[i])) LRVB_FAIL(LRVB_ERR_INVALID, "dispersion[%lld] is not positive and finite", (long long)i);
+    return glmms_set_rows(c, c->gdisp, c->gdisp_n, phi, n, 1, "the dispersion needs at least one entry");
+}
+
+// The shared bodies with the TruncNegBinLik policy: the caller's nodes, the (shifted) offset of lrvb_set_offset and the dispersion
+// of lrvb_set_dispersion; neither the trials nor the link of the binomial entries is read.
+extern "C" int lrvb_glmm_ztnegbin_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                        const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                        int32_t n_nodes, double* value_out, double* grad_global_out, double* H_blocks_out,
+                                        double* group_sums_out, int32_t want_border) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_terms(c, glmms_ztnegbin(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, value_out, grad_global_out,
+                       H_blocks_out, group_sums_out, want_border);
+}
+
+extern "C" int lrvb_glmm_ztnegbin_obs_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                                const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                                int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, int64_t n0,
+                                                int64_t n1, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_obs_influence(c, glmms_ztnegbin(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, n0, n1, out);
+}
+
+extern "C" int lrvb_glmm_ztnegbin_group_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                                  const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                                  int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_group_influence(c, glmms_ztnegbin(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out);
+}
+
 // ---- group blocks of H^-1 and predictions with their linear-response variance (k_glmm_slopes.hip) ----------
 static int glmms_group_cov(lrvb_ctx* c, const double* W, const double* s, int64_t P_in, int64_t G_in, int64_t K, int64_t NC, bool arrow,
                            double* out) {
@@ -3149,6 +3194,11 @@ static int glmms_predict(lrvb_ctx* c, GlmmLik lik, const double* mean, const dou
     if (fresh) {
         if (!z_new || !gid_new || n_new < 0) LRVB_FAIL(LRVB_ERR_INVALID, "new rows need x, z, their groups and a count >= 0");
         n = n_new;
+        if (lik.kind == GLMM_ZTNEGBIN) {
+            if (!tr_new) LRVB_FAIL(LRVB_ERR_INVALID, "new rows of the zero-truncated negative binomial model need their dispersion");
+            for (i64 i = 0; i < n; ++i)
+                if (!(tr_new[i] > 0.0) || !std::isfinite(tr_new[i])) LRVB_FAIL(LRVB_ERR_INVALID, "dispersion of new row %lld is not positive and finite", (long long)i);
+        }
         gid_h.assign((size_t)(2 * ((n + 1) / 2)), 0);
         for (i64 i = 0; i < n; ++i) {                      // on the host, before anything is launched: an index outside is an out-of-bounds read
             if (gid_new[i] < 0 || gid_new[i] >= Gp)
@@ -3177,6 +3227,7 @@ static int glmms_predict(lrvb_ctx* c, GlmmLik lik, const double* mean, const dou
         lik.off = nullptr; lik.trials = nullptr;
         if (lik.kind != GLMM_LOGISTIC && off_new) { LRVB_TRY(h2d(c, on, off_new, (size_t)n)); lik.off = on; }
         if (lik.kind == GLMM_BINOMIAL && tr_new) { LRVB_TRY(h2d(c, tn, tr_new, (size_t)n)); lik.trials = tn; }
+        if (lik.kind == GLMM_ZTNEGBIN) { LRVB_TRY(h2d(c, tn, tr_new, (size_t)n)); lik.trials = tn; }      // the dispersion of the new rows, checked above
         X = xn; Z = zn; gid = reinterpret_cast<const int*>(gn); n0 = 0; n1 = n;
     } else gid = groups_ids(c);
     LRVB_TRY(launch_glmm_slopes_predict_rows(c, lik, (int)K, X, Z, n0, n1, gid, pt.m, pt.v, pt.e, pt.r, Sbb, c->glmms_gcov.p, od, n));
@@ -3219,6 +3270,16 @@ extern "C" int lrvb_glmm_ztpoisson_predict(lrvb_ctx* c, const double* mean, cons
     LRVB_TRY(ctx_bind(c));
     return glmms_predict(c, glmms_ztpoisson(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, Gp, K, cov_beta, n0, n1, x_new, z_new,
                          gid_new, offset_new, nullptr, n_new, out);
+}
+
+extern "C" int lrvb_glmm_ztnegbin_predict(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                          const double* r_loc, int64_t Gp, int64_t K, const double* gh_x, const double* gh_w,
+                                          int32_t n_nodes, const double* cov_beta, int64_t n0, int64_t n1, const double* x_new,
+                                          const double* z_new, const int32_t* gid_new, const double* offset_new,
+                                          const double* dispersion_new, int64_t n_new, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_predict(c, glmms_ztnegbin(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, Gp, K, cov_beta, n0, n1, x_new, z_new,
+                         gid_new, offset_new, dispersion_new, n_new, out);
 }
 
 // ---- logistic regression with a full-covariance Gaussian posterior q(beta) = N(m, Sigma) ----------------------------------

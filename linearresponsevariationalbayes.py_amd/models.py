@@ -660,6 +660,36 @@ class DeviceContext(object):
         """Fitted means of the truncated count (lrvb_glmm_ztpoisson_predict); new rows carry an offset."""
         return self._glmm_predict(self._lib.lrvb_glmm_ztpoisson_predict, True, 1, mean, var, e, r, gh_x, gh_w, cov_beta, n0, n1, new)
 
+    # ---- zero-truncated NB2 mixed model (lrvb_glmm_ztnegbin_*): the (shifted) offset of `set_offset`, the dispersion of `set_dispersion` ----
+    def set_dispersion(self, dispersion):
+        """The per-row dispersion phi > 0 of the zero-truncated negative binomial mixed model, or None to clear it
+        (lrvb_set_dispersion).  Only the `glmm_ztnegbin_*` entries read it; the resident group sums are dropped."""
+        if dispersion is None:
+            self._check(self._lib.lrvb_set_dispersion(self._h, None, 0))
+            return
+        d = _hip.as_f64(dispersion).ravel()
+        self._check(self._lib.lrvb_set_dispersion(self._h, _hip.ptr(d), d.size))
+
+    def glmm_ztnegbin_terms(self, mean, var, e, r, gh_x, gh_w, want_grad=True, want_hess=True, want_border=True):
+        """Data term of the zero-truncated NB2 mixed model with K effects per group, the shifted offset o - log phi of
+        `set_offset` and the dispersion of `set_dispersion` (lrvb_glmm_ztnegbin_terms): what `glmm_slopes_terms` returns, in its
+        layouts.  The group sums stay resident for `glmm_slopes_schur`.  A point at which phi softplus(eta) underflows to 0 on a
+        node is a ValueError."""
+        return self._glmm_terms(self._lib.lrvb_glmm_ztnegbin_terms, True, True, mean, var, e, r, gh_x, gh_w, want_grad, want_hess, want_border)
+
+    def glmm_ztnegbin_obs_influence(self, mean, var, e, r, gh_x, gh_w, A, n0=0, n1=None):
+        """(n1 - n0) x Q rows of the zero-truncated NB2 mixed model, as `glmm_slopes_obs_influence` (lrvb_glmm_ztnegbin_obs_influence)."""
+        return self._glmm_obs_influence(self._lib.lrvb_glmm_ztnegbin_obs_influence, True, True, mean, var, e, r, gh_x, gh_w, A, n0, n1)
+
+    def glmm_ztnegbin_group_influence(self, mean, var, e, r, gh_x, gh_w, A):
+        """G x Q group influence of the zero-truncated NB2 mixed model, as `glmm_slopes_group_influence`
+        (lrvb_glmm_ztnegbin_group_influence)."""
+        return self._glmm_group_influence(self._lib.lrvb_glmm_ztnegbin_group_influence, True, True, mean, var, e, r, gh_x, gh_w, A)
+
+    def glmm_ztnegbin_predict(self, mean, var, e, r, gh_x, gh_w, cov_beta, n0=0, n1=None, new=None):
+        """Fitted means of the truncated NB2 count (lrvb_glmm_ztnegbin_predict); new rows carry a shifted offset and their dispersion."""
+        return self._glmm_predict(self._lib.lrvb_glmm_ztnegbin_predict, True, 2, mean, var, e, r, gh_x, gh_w, cov_beta, n0, n1, new)
+
     # ---- multinomial (softmax) regression: beta is (K - 1) x n_cols, D = (K - 1) n_cols (lrvb_softmax_*) --------------------
     def softmax_set_labels(self, labels, n_classes):
         y = np.ascontiguousarray(np.asarray(labels).ravel(), dtype=np.int32)

@@ -671,7 +671,7 @@ int lrvb_glmm_ztpoisson_group_influence(lrvb_ctx* ctx, const double* mean, const
  *   y_n in {1, 2, ..},  P(y_n | t_n) = NB2(y_n; mu_n = e^{t_n}, phi_n) / (1 - (1 + mu_n / phi_n)^{-phi_n}),  t_n = o_n + x_n . beta + z_n . u_g(n):
  * the count part of a hurdle model for over-dispersed counts, with a KNOWN per-row dispersion phi_n > 0.
  * lrvb_set_dispersion, a sibling of lrvb_set_trials: n_obs positive finite values in one device buffer of their own, or NULL to
- * clear them; replaced by the next call.  Only the lrvb_glmm_ztnegbin_* entries read it.  The call drops the resident group sums,
+ * clear them; replaced by the next call.  Only the lrvb_glmm_ztnegbin_* and lrvb_glmm_beta_* entries read it.  The call drops the resident group sums,
  * the factor and the group covariance.  A value that is not positive and finite: LRVB_ERR_INVALID, checked on the host ahead of
  * everything else (the state is left as it was); n < 1 with a non-null pointer: LRVB_ERR_SIZE (the dispersion is then cleared, as
  * lrvb_set_trials clears the trials); a length other than n_obs is found when an entry runs: LRVB_ERR_STATE.                    */
@@ -703,6 +703,40 @@ int lrvb_glmm_ztnegbin_obs_influence(lrvb_ctx* ctx, const double* mean, const do
 int lrvb_glmm_ztnegbin_group_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e,
                                        const double* r, int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
                                        const double* A_global, const double* A_local, int64_t Q, double* out);
+
+/* ---- Beta mixed model with K <= 4 independent random effects per group ------------------------------------
+ *   0 < y_n < 1,  y_n ~ Beta(mu_n phi_n, (1 - mu_n) phi_n),  mu_n = sigma(t_n),  t_n = o_n + x_n . beta + z_n . u_g(n):
+ * continuous proportions with a KNOWN per-row precision phi_n > 0 (lrvb_set_dispersion) and the RAW offset of lrvb_set_offset
+ * (no log phi shift).  The context's y (LRVB_SLOT_Y) holds l_n = logit(y_n) = log y_n - log(1 - y_n).  With
+ *   h(t) = lgamma(phi sigma(t)) + lgamma(phi sigma(-t)) - phi l sigma(t)
+ *        = softplus(t) + softplus(-t) - 2 log phi + lgamma(1 + phi sigma(t)) + lgamma(1 + phi sigma(-t)) - phi l sigma(t)
+ * (the second form is the one evaluated; lgamma(phi) + (phi - 1) log(1 - y) - log y is dropped), t ~ N(rho_n, s_n) with
+ * rho_n = offset_n + x_n . mean + z_n . e_g(n) and s_n as in lrvb_glmm_slopes_terms:
+ *   value = sum_n w_n E h,  a1 = w E h',  a2 = w E h'' / 2,  c11 = w E h'',  c12 = w E h''' / 2,  c22 = w E h'''' / 4
+ * (Stein's identity on the caller's Gauss-Hermite nodes) in the five-row layout, the scratch sizes and the summation order of the
+ * logistic entries.  No finite point is refused: as |t| grows h grows like |t| and nothing overflows.  A value that is not finite
+ * after the reduction (a non-finite point, offset or l): LRVB_ERR_INVALID, the other outputs are then unspecified and no sums stay
+ * resident.  Arguments, outputs, the column layout of group_sums_out, want_border, the fixed summation order (two calls at one
+ * point are bitwise equal) and the reduce-hook contract are those of lrvb_glmm_slopes_terms; the group sums stay resident for
+ * lrvb_glmm_slopes_schur, lrvb_glmm_slopes_solve_forward, lrvb_glmm_slopes_solve_back and lrvb_glmm_slopes_group_cov.  The
+ * entries read neither lrvb_set_trials nor lrvb_set_link.  No dispersion set, or one of another length than n_obs:
+ * LRVB_ERR_STATE.  The other errors are those of lrvb_glmm_ztpoisson_terms.  y is not validated here (the Python layer asks for
+ * y strictly inside (0, 1)).  The fitted mean E sigma(t) does not depend on phi: lrvb_glmm_binomial_predict on a context without
+ * trials and with the logit link is the predict entry of this model.                                                          */
+int lrvb_glmm_beta_terms(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                         int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes, double* value_out,
+                         double* grad_global_out, double* H_blocks_out, double* group_sums_out, int32_t want_border);
+/* Streamed weight influence of that model: lrvb_glmm_slopes_obs_influence with, per unit weight, a1' = E h' (there is no "- y":
+ * the response sits inside h) and a2' = E h'' / 2.  Operand layouts, the row window, the output, "a window equals the same rows
+ * of the full result bitwise" and "no reduce-hook call" as there; errors as lrvb_glmm_beta_terms, and n0 > n1 or n1 > n_obs:
+ * LRVB_ERR_INVALID.                                                                                                            */
+int lrvb_glmm_beta_obs_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                                 int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
+                                 const double* A_global, const double* A_local, int64_t Q, int64_t n0, int64_t n1, double* out);
+/* Group influence of that model, as lrvb_glmm_ztpoisson_group_influence.  Errors as lrvb_glmm_beta_obs_influence.              */
+int lrvb_glmm_beta_group_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e,
+                                   const double* r, int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
+                                   const double* A_global, const double* A_local, int64_t Q, double* out);
 
 /* ---- group blocks of H^-1, fitted values and predictions with their linear-response variance ------------
  * For every mixed model with K <= 4 effects per group.  After a successful lrvb_glmm_slopes_schur (the factor L_g, U_g resident)

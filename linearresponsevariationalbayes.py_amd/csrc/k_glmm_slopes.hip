@@ -5,6 +5,7 @@
 //   binomial with a probit or cloglog link:  p = Phi(.) or 1 - exp(-exp(.)) in the place of sigma(.)
 //   zero-truncated Poisson:  y_n >= 1,  P(y_n) = Poisson(y_n; lambda_n) / (1 - exp(-lambda_n)),  lambda_n as the Poisson one
 //   zero-truncated NB2:  y_n >= 1,  P(y_n) = NB2(y_n; mu_n, phi_n) / (1 - (1 + mu_n / phi_n)^-phi_n),  mu_n as lambda_n
+//   Beta:  0 < y_n < 1,  y_n ~ Beta(mu_n phi_n, (1 - mu_n) phi_n),  mu_n = sigma(o_n + x_n . beta + z_n . u_g(n))
 // Per observation rho_n = x_n . m + z_n . e_g, s_n = (x_n o x_n) . v + (z_n o z_n) . r_g and five coefficients a1, a2, c11, c12, c22.
 // Every kernel that walks the rows is written ONCE, as a template over a likelihood policy (k_glmm_walk.h, DESIGN.md sections 27 and
 // 31): LogisticLik (the quadrature k_glmm.hip runs too; with K = 1 and z = 1 this is that model) and PoissonLik
@@ -206,6 +207,7 @@ static int gs_with_lik(const GlmmLik& lik, F&& f) {
     if (lik.kind == GLMM_POISSON) return f(PoissonLik(), PoissonLik::Args(lik.off));
     if (lik.kind == GLMM_ZTPOISSON) return f(TruncPoissonLik(), TruncPoissonLik::Args{q, lik.off});
     if (lik.kind == GLMM_ZTNEGBIN) return f(TruncNegBinLik(), TruncNegBinLik::Args{q, lik.off, lik.trials, lik.y});
+    if (lik.kind == GLMM_BETA) return f(BetaLik(), BetaLik::Args{q, lik.off, lik.trials, lik.y});
     if (lik.kind == GLMM_BINOMIAL && lik.link == GLMM_LINK_PROBIT)
         return f(BinomialLinkLik<GLMM_LINK_PROBIT>(), BinomialLinkLik<GLMM_LINK_PROBIT>::Args{q, lik.off, lik.trials, lik.y});
     if (lik.kind == GLMM_BINOMIAL && lik.link == GLMM_LINK_CLOGLOG)
@@ -700,6 +702,18 @@ void glmm_ztnegbin_infl_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* 
     gsi_infl_rows<TruncNegBinLik>(n0, R, P, Kz, X, Z, y, gid, m, vb, eg, rg, {{gx, gw, nq}, off, disp, y}, Ag, Al, Q, out);
 }
 
+// The Beta model: the arguments of the zero-truncated NB2 entry; y holds logit(y).
+__global__ __launch_bounds__(256)
+void glmm_beta_infl_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* __restrict__ X, const double* __restrict__ Z,
+                                const double* __restrict__ off, const double* __restrict__ disp, const double* __restrict__ y,
+                                const int* __restrict__ gid, const double* __restrict__ m, const double* __restrict__ vb,
+                                const double* __restrict__ eg, const double* __restrict__ rg, const double* __restrict__ gx,
+                                const double* __restrict__ gw, int nq, const double* __restrict__ Ag, const double* __restrict__ Al,
+                                int Q, double* __restrict__ out)
+{
+    gsi_infl_rows<BetaLik>(n0, R, P, Kz, X, Z, y, gid, m, vb, eg, rg, {{gx, gw, nq}, off, disp, y}, Ag, Al, Q, out);
+}
+
 template <class Lik>
 static int gs_launch_infl_rows(lrvb_ctx* c, int Kz, const double* Z, typename Lik::Args la, i64 n0, i64 n1, const int* gid, const double* m,
                                const double* vb, const double* eg, const double* rg, const double* Ag, const double* Al, i64 Q,
@@ -719,6 +733,10 @@ static int gs_launch_infl_rows(lrvb_ctx* c, int Kz, const double* Z, typename Li
                            (const double*)la.off, (const double*)c->y.p, gid, m, vb, eg, rg, la.q.gx, la.q.gw, la.q.nq, Ag, Al, (int)Q, out);
     else if constexpr (std::is_same<Lik, TruncNegBinLik>::value)
         hipLaunchKernelGGL(glmm_ztnegbin_infl_rows_kernel, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
+                           (const double*)la.off, (const double*)la.disp, (const double*)la.y, gid, m, vb, eg, rg, la.q.gx, la.q.gw, la.q.nq,
+                           Ag, Al, (int)Q, out);
+    else if constexpr (std::is_same<Lik, BetaLik>::value)
+        hipLaunchKernelGGL(glmm_beta_infl_rows_kernel, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
                            (const double*)la.off, (const double*)la.disp, (const double*)la.y, gid, m, vb, eg, rg, la.q.gx, la.q.gw, la.q.nq,
                            Ag, Al, (int)Q, out);
     else if constexpr (gs_link_of<Lik>::value != GLMM_LINK_LOGIT)

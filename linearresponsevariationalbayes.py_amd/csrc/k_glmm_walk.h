@@ -630,6 +630,167 @@ struct TruncNegBinLik {
     }
 };
 
+// Beta with a known per-row precision phi and a per-row offset: a proportion y strictly inside (0, 1),
+// y ~ Beta(mu phi, (1 - mu) phi), mu = sigma(t).  The staged y is l = logit(y); with it the row's term is, constants dropped,
+//   h(t) = lgamma(phi sigma(t)) + lgamma(phi sigma(-t)) - phi l sigma(t).
+// Differentiated as it stands that is useless in the tails: psi^(j)(phi mu) ~ (phi mu)^-(j+1) meets mu'^j ~ mu^j and O(1) terms
+// cancel to an O(mu) result.  Both arguments are therefore SHIFTED by one, lgamma(x) = lgamma(1 + x) - log x and
+// -log sigma(+-t) = softplus(-+t):
+//   h(t) = softplus(t) + softplus(-t) - 2 log phi + G(mu),   G(mu) = lgamma(1 + phi mu) + lgamma(1 + phi (1 - mu)) - phi l mu,
+// G smooth with every polygamma argument >= 1.  The softplus pair gives |t| + 2 log1p(e), +-|1 - 2 sigma| and 2 sigma', 2 sigma'',
+// 2 sigma''' (the g2, g3, g4 of LogisticLik::moments); G goes through Faa di Bruno with
+//   G_j = phi^j [psi^(j-1)(1 + phi mu) + (-1)^j psi^(j-1)(1 + phi (1 - mu))] - [j = 1] phi l,
+//   mu' = v,  mu'' = v (1 - 2 mu),  mu''' = v (1 - 6 v),  mu'''' = v (1 - 2 mu)(1 - 12 v),  v = mu (1 - mu),
+// mu and 1 - mu both from e = exp(-|t|), never 1 - sigma by subtraction.  The data term is sum w E h(t), t ~ N(rho, s), rho
+// including the offset; coefficients by Stein's identity in the logistic five-row layout.  Not canonical (the y-dependence sits
+// inside h): MINUS_Y is false and coefs ignores the walk's yi, as BinomialLinkLik does.  -2 log phi is added once per row behind
+// the shuffles (E of a constant).  NO finite point is refused: as |t| grows e underflows to 0, the arguments become 1 and 1 + phi
+// and h grows like |t| -- unlike the Poisson-type policies there is no exp of t that could overflow.  The response mean is
+// E sigma(t), the logistic one, whatever phi.  Nodes, offsets, phi and l are staged as TruncNegBinLik stages offset, dispersion and
+// y; the four lanes of a row share the nodes; five accumulators per lane, two xor shuffles in fixed order, no atomics.
+struct BetaLik {
+    struct Args { LogisticLik::Args q; const double* __restrict__ off; const double* __restrict__ disp; const double* __restrict__ y; };   // off may be nullptr; y holds logit(y)
+    struct Lds { LogisticLik::Lds q; double s_off[GLMM_T], s_phi[GLMM_T], s_y[GLMM_T]; };
+    typedef LogisticLik::Moments Moments;
+    static constexpr const char* LIMITS = "Beta mixed model: P <= 64, 1 <= K <= 4, at most 128 nodes";
+    static bool args_ok(const Args& a) { return LogisticLik::args_ok(a.q) && a.disp != nullptr; }
+    static constexpr int NCF = 5, NB = 4, DK = 16;
+    static constexpr bool HAS_FACTOR = false;
+    static constexpr bool MINUS_Y = false;
+    static __device__ __forceinline__ int cf_row(int kind) { return kind; }
+    static __device__ __forceinline__ double cf_factor(int) { return 1.0; }
+    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return b * Kz + k; }
+    static __device__ __forceinline__ int d_stride(int) { return DK; }
+
+    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { LogisticLik::init(L.q, a.q, tid); }
+    static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
+    {
+        L.s_off[t] = (a.off && live) ? a.off[src] : 0.0;
+        L.s_phi[t] = live ? a.disp[src] : 1.0;
+        L.s_y[t] = (a.y && live) ? a.y[src] : 0.0;
+    }
+    static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_off[row]; }
+    static __device__ __forceinline__ int lane_row() { return (int)(threadIdx.x >> 2); }
+
+    // lgamma (N = 5 only), psi, psi' (p[1], p[2]) and psi'', psi''' (N = 5: p[3], p[4]) at x >= 1: nine unrolled steps of the
+    // recurrence f(x) = f(x + 1) + .. wherever x is still below 10 -- selects, no data-dependent trip count and no indexed
+    // array -- and then the Stirling / Bernoulli series to B_16 at z >= 10 (the first term left out is below 3e-17 of the result).
+    template <int N>
+    static __device__ __forceinline__ void polygamma(double x, double* p)
+    {
+        double z = x, prod = 1.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            const bool lo = z < 10.0;
+            const double r = lo ? 1.0 / z : 0.0, r2 = r * r;
+            s1 += r; s2 += r2;
+            if constexpr (N == 5) { s3 += r2 * r; s4 += r2 * r2; prod *= lo ? z : 1.0; }
+            z = lo ? z + 1.0 : z;
+        }
+        const double w = 1.0 / z, w2 = w * w, lz = log(z);
+        // sum_k B_2k w^2k / (2k),  sum_k B_2k w^2k,  sum_k B_2k (2k + 1) w^2k,  sum_k B_2k (2k + 1)(2k + 2) w^2k,  k = 1 .. 8
+        p[1] = lz - 0.5 * w - s1
+               - w2 * (1.0 / 12.0 + w2 * (-1.0 / 120.0 + w2 * (1.0 / 252.0 + w2 * (-1.0 / 240.0 + w2 * (1.0 / 132.0 + w2 * (-691.0 / 32760.0
+                 + w2 * (1.0 / 12.0 + w2 * (-3617.0 / 8160.0))))))));
+        p[2] = s2 + w * (1.0 + 0.5 * w
+               + w2 * (1.0 / 6.0 + w2 * (-1.0 / 30.0 + w2 * (1.0 / 42.0 + w2 * (-1.0 / 30.0 + w2 * (5.0 / 66.0 + w2 * (-691.0 / 2730.0
+                 + w2 * (7.0 / 6.0 + w2 * (-3617.0 / 510.0)))))))));
+        if constexpr (N == 5) {
+            p[3] = -2.0 * s3 - w2 * (1.0 + w
+                   + w2 * (3.0 / 6.0 + w2 * (-5.0 / 30.0 + w2 * (7.0 / 42.0 + w2 * (-9.0 / 30.0 + w2 * (55.0 / 66.0 + w2 * (-13.0 * 691.0 / 2730.0
+                     + w2 * (15.0 * 7.0 / 6.0 + w2 * (-17.0 * 3617.0 / 510.0)))))))));
+            p[4] = 6.0 * s4 + w2 * w * (2.0 + 3.0 * w
+                   + w2 * (12.0 / 6.0 + w2 * (-30.0 / 30.0 + w2 * (56.0 / 42.0 + w2 * (-90.0 / 30.0 + w2 * (660.0 / 66.0
+                     + w2 * (-182.0 * 691.0 / 2730.0 + w2 * (240.0 * 7.0 / 6.0 + w2 * (-306.0 * 3617.0 / 510.0)))))))));
+            // sum_k B_2k w^(2k-1) / (2k (2k - 1))
+            p[0] = (z - 0.5) * lz - z + 0.9189385332046727 - log(prod)
+                   + w * (1.0 / 12.0 + w2 * (-1.0 / 360.0 + w2 * (1.0 / 1260.0 + w2 * (-1.0 / 1680.0 + w2 * (1.0 / 1188.0 + w2 * (-691.0 / 360360.0
+                     + w2 * (1.0 / 156.0 + w2 * (-3617.0 / 122400.0))))))));
+        }
+    }
+
+    // h' and h'' at t (N = 2), or h + 2 log phi, h', h'' .. h'''' (N = 5), into h[5 - N ..]; l = logit(y)
+    template <int N>
+    static __device__ __forceinline__ void node(double t, double phi, double l, double* h)
+    {
+        const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
+        const bool pos = t >= 0.0;
+        const double mu = pos ? ie : e * ie, nu = pos ? e * ie : ie;      // sigma(t) and sigma(-t)
+        const double g2 = e * ie * ie;                                   // v = mu (1 - mu)
+        const double om = (1.0 - e) * ie;                                // |1 - 2 sigma|
+        const double d = pos ? -om : om;                                 // 1 - 2 mu
+        double pa[5], pb[5];
+        polygamma<N>(1.0 + phi * mu, pa);
+        polygamma<N>(1.0 + phi * nu, pb);
+        const double G1 = phi * ((pa[1] - pb[1]) - l), G2 = phi * phi * (pa[2] + pb[2]);
+        const double m1 = g2, m2 = g2 * d;
+        h[1] = -d + G1 * m1;
+        h[2] = 2.0 * g2 + G2 * m1 * m1 + G1 * m2;
+        if constexpr (N == 5) {
+            const double p3 = phi * phi * phi;
+            const double G3 = p3 * (pa[3] - pb[3]), G4 = p3 * phi * (pa[4] + pb[4]);
+            const double g3 = g2 * d, g4 = g2 * (1.0 - 6.0 * g2);         // sigma'' and sigma'''
+            const double m3 = g4, m4 = g2 * d * (1.0 - 12.0 * g2);
+            h[0] = fabs(t) + 2.0 * log1p(e) + pa[0] + pb[0] - phi * l * mu;
+            h[3] = 2.0 * g3 + G3 * m1 * m1 * m1 + 3.0 * G2 * m1 * m2 + G1 * m3;
+            h[4] = 2.0 * g4 + G4 * (m1 * m1) * (m1 * m1) + 6.0 * G3 * m1 * m1 * m2 + G2 * (3.0 * m2 * m2 + 4.0 * m1 * m3) + G1 * m4;
+        }
+    }
+    // a1' = E h' and E h'' = 2 a2' per unit weight, on all four lanes of a row
+    static __device__ __forceinline__ void infl(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& e1,
+                                                double& e2)
+    {
+        const int row = lane_row();
+        const double phi = L.s_phi[row], l = L.s_y[row];
+        rho += o;
+        e1 = 0.0; e2 = 0.0;
+        if (live) {
+            const double sd = sqrt(fmax(s, 0.0));
+            for (int k = q4; k < a.q.nq; k += 4) {
+                const double t = rho + sd * L.q.sx[k], wk = L.q.sw[k];
+                double h[5];
+                node<2>(t, phi, l, h);
+                e1 += wk * h[1]; e2 += wk * h[2];
+            }
+        }
+        e1 += __shfl_xor(e1, 1); e2 += __shfl_xor(e2, 1);
+        e1 += __shfl_xor(e1, 2); e2 += __shfl_xor(e2, 2);
+    }
+    // the response mean E sigma(t) does not depend on phi: the logistic quadrature at rho + o
+    static __device__ __forceinline__ void mean(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& mu)
+    {
+        double e2;
+        LogisticLik::infl(L.q, a.q, 0.0, live, q4, rho + o, s, mu, e2);
+    }
+    static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
+    {
+        const int row = lane_row();
+        const double phi = L.s_phi[row], l = L.s_y[row];
+        rho += L.s_off[row];
+        double e[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        if (live) {
+            const double sd = sqrt(fmax(s, 0.0));
+            for (int k = q4; k < a.q.nq; k += 4) {
+                const double t = rho + sd * L.q.sx[k], wk = L.q.sw[k];
+                double h[5];
+                node<5>(t, phi, l, h);
+#pragma unroll
+                for (int i = 0; i < 5; ++i) e[i] += wk * h[i];
+            }
+        }
+#pragma unroll
+        for (int off = 1; off <= 2; off <<= 1)
+#pragma unroll
+            for (int i = 0; i < 5; ++i) e[i] += __shfl_xor(e[i], off);
+        return {live ? e[0] - 2.0 * log(phi) : 0.0, e[1], e[2], e[3], e[4]};
+    }
+    static __device__ __forceinline__ double coefs(const Lds&, int, const Moments& mo, double wi, double, double, double, double* k)
+    {
+        k[0] = wi * mo.e1; k[1] = wi * 0.5 * mo.e2; k[2] = wi * mo.e2; k[3] = wi * 0.5 * mo.e3; k[4] = wi * 0.25 * mo.e4;
+        return wi * mo.v;
+    }
+};
+
 // ---- what the kernels over group-sorted rows share ----------------------------------------------------------------------------------
 // The head of a tile of sorted rows: thread t < GLMM_T finds row t0 + t's original position, its group (the last g with
 // offs[g] <= i) and whether that group lies whole inside the tile; then the tile's rows of X and Z are gathered into xs (row

@@ -2605,9 +2605,11 @@ static GlmmLik glmms_poisson() { return GlmmLik{GLMM_POISSON, nullptr, nullptr, 
 static GlmmLik glmms_binomial(const lrvb_ctx* c, const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_BINOMIAL, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, c->glmms_link, nullptr}; }
 static GlmmLik glmms_ztpoisson(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_ZTPOISSON, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, LRVB_LINK_LOGIT, nullptr}; }
 static GlmmLik glmms_ztnegbin(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_ZTNEGBIN, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, LRVB_LINK_LOGIT, nullptr}; }
+static GlmmLik glmms_beta(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_BETA, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, LRVB_LINK_LOGIT, nullptr}; }
 static const char* glmms_name(const GlmmLik& lik) {
     if (lik.kind == GLMM_ZTPOISSON) return "zero-truncated Poisson";
     if (lik.kind == GLMM_ZTNEGBIN) return "zero-truncated negative binomial";
+    if (lik.kind == GLMM_BETA) return "Beta";
     return lik.kind == GLMM_POISSON ? "Poisson" : (lik.kind == GLMM_BINOMIAL ? "binomial" : "logistic");
 }
 
@@ -2631,9 +2633,10 @@ static int glmms_check(lrvb_ctx* c, const GlmmLik& lik, const double* mean, cons
         LRVB_FAIL(LRVB_ERR_STATE, "the offset has %lld entries, the model has %lld observations", (long long)c->goff_n, (long long)c->N);
     if (lik.kind == GLMM_BINOMIAL && c->gtr_n != 0 && c->gtr_n != c->N)
         LRVB_FAIL(LRVB_ERR_STATE, "the trials have %lld entries, the model has %lld observations", (long long)c->gtr_n, (long long)c->N);
-    if (lik.kind == GLMM_ZTNEGBIN && c->gdisp_n == 0)
+    const bool disp = lik.kind == GLMM_ZTNEGBIN || lik.kind == GLMM_BETA;
+    if (disp && c->gdisp_n == 0)
         LRVB_FAIL(LRVB_ERR_STATE, "no dispersion: call lrvb_set_dispersion first");
-    if (lik.kind == GLMM_ZTNEGBIN && c->gdisp_n != c->N)
+    if (disp && c->gdisp_n != c->N)
         LRVB_FAIL(LRVB_ERR_STATE, "the dispersion has %lld entries, the model has %lld observations", (long long)c->gdisp_n, (long long)c->N);
     LRVB_TRY(check_len(P_in, c->P, "mean / var"));
     LRVB_TRY(check_len(G_in, c->n_groups, lik.unit ? "e / r" : "groups of e / r"));
@@ -2656,6 +2659,7 @@ static int glmms_to_device(lrvb_ctx* c, GlmmLik& lik, double* g) {
     if (lik.kind == GLMM_BINOMIAL) lik.trials = c->gtr_n ? c->gtr.p : nullptr;
     if (lik.link != LRVB_LINK_LOGIT) lik.y = c->y.p;                      // the probit and cloglog policies stage y themselves
     if (lik.kind == GLMM_ZTNEGBIN) { lik.trials = c->gdisp.p; lik.y = c->y.p; }   // phi rides in the trials slot; y is staged for y + phi
+    if (lik.kind == GLMM_BETA) { lik.trials = c->gdisp.p; lik.y = c->y.p; }       // phi in the trials slot again; y holds logit(y)
     if (lik.kind == GLMM_POISSON) return LRVB_OK;
     LRVB_TRY(h2d(c, g, lik.gx, (size_t)lik.n_nodes));
     LRVB_TRY(h2d(c, g + 128, lik.gw, (size_t)lik.n_nodes));
@@ -2734,6 +2738,8 @@ static int glmms_terms(lrvb_ctx* c, GlmmLik lik, const double* mean, const doubl
         LRVB_FAIL(LRVB_ERR_INVALID, "the zero-truncated Poisson data term is not finite at this point: exp(rho + s / 2) overflows, or exp(t) underflows to 0, for some row (the kernel does not clamp)");
     if (lik.kind == GLMM_ZTNEGBIN && !std::isfinite(*value_out))
         LRVB_FAIL(LRVB_ERR_INVALID, "the zero-truncated negative binomial data term is not finite at this point: phi softplus(eta) underflows to 0 on a node, or a moment overflows, for some row (the kernel does not clamp)");
+    if (lik.kind == GLMM_BETA && !std::isfinite(*value_out))
+        LRVB_FAIL(LRVB_ERR_INVALID, "the Beta data term is not finite at this point: the point, the offset or logit(y) is not finite for some row (no finite point is refused)");
     c->glmms_valid = true; c->glmms_K = lik.unit ? 0 : (int)K;           // 0: the sums of lrvb_glmm_terms, for lrvb_glmm_schur only
     if (want_g) LRVB_TRY(d2h(c, grad_global_out, gred, (size_t)(2 * P)));
     if (want_H) LRVB_TRY(d2h(c, H_blocks_out, Hb, (size_t)(3 * P * P)));
@@ -3140,6 +3146,33 @@ extern "C" int lrvb_glmm_ztnegbin_group_influence(lrvb_ctx* c, const double* mea
                                                   int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, double* out) {
     LRVB_TRY(ctx_bind(c));
     return glmms_group_influence(c, glmms_ztnegbin(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out);
+}
+
+// ---- Beta mixed model: proportions strictly inside (0, 1) with a known precision --------------------------
+// The shared bodies with the BetaLik policy: the caller's nodes, the RAW offset of lrvb_set_offset and the precision of
+// lrvb_set_dispersion; the context's y holds logit(y).  Neither the trials nor the link of the binomial entries is read.
+extern "C" int lrvb_glmm_beta_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                    const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                    int32_t n_nodes, double* value_out, double* grad_global_out, double* H_blocks_out,
+                                    double* group_sums_out, int32_t want_border) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_terms(c, glmms_beta(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, value_out, grad_global_out,
+                       H_blocks_out, group_sums_out, want_border);
+}
+
+extern "C" int lrvb_glmm_beta_obs_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                            const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                            int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, int64_t n0,
+                                            int64_t n1, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_obs_influence(c, glmms_beta(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, n0, n1, out);
+}
+
+extern "C" int lrvb_glmm_beta_group_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                              const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                              int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_group_influence(c, glmms_beta(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out);
 }
 
 // ---- group blocks of H^-1 and predictions with their linear-response variance (k_glmm_slopes.hip) ----------

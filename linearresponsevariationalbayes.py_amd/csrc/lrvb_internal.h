@@ -149,7 +149,7 @@ struct lrvb_ctx {
     DevBuf gtr; i64 gtr_n = 0;
     // and the link of lrvb_set_link (LRVB_LINK_LOGIT = 0 by default); no other entry reads it
     int glmms_link = 0;
-    // lrvb_glmm_ztnegbin_* read the offset and the per-row dispersion of lrvb_set_dispersion, gdisp_n doubles (0 = none: refused)
+    // lrvb_glmm_ztnegbin_* and lrvb_glmm_beta_* read the offset and the per-row dispersion of lrvb_set_dispersion, gdisp_n doubles (0 = none: refused)
     DevBuf gdisp; i64 gdisp_n = 0;
     DevBuf opt;                    // trust-region Newton-CG: 12 D-vectors (+ the D x D preconditioner)
     DevBuf cgm[9];                 // blocked CG: B, X, R, P, Q, Z (Q x D), U, W (Q x V), R^T (P x Q)
@@ -265,7 +265,8 @@ int  launch_glmm_infl_local(lrvb_ctx* c, i64 Q, const double* S, const double* A
 // nodes and the offset.  `unit`: the unit group design of the random intercept (logistic,
 // K = 1, z = 1, nothing on the device): the host bodies hand the launchers Z = nullptr, and those launch the kernels of k_glmm.hip.
 enum GlmmKind { GLMM_LOGISTIC = 0, GLMM_POISSON = 1, GLMM_BINOMIAL = 2, GLMM_ZTPOISSON = 3,    // ZTPOISSON: nodes and an offset, no trials
-                GLMM_ZTNEGBIN = 4 };   // zero-truncated NB2: nodes, the shifted offset, the dispersion phi in `trials`, and `y`
+                GLMM_ZTNEGBIN = 4,     // zero-truncated NB2: nodes, the shifted offset, the dispersion phi in `trials`, and `y`
+                GLMM_BETA = 5 };       // Beta: nodes, the raw offset, the precision phi in `trials`, and logit(y) in `y`
 // `link` (binomial only, LRVB_LINK_*; 0 = logit: BinomialLik) picks the probit or cloglog policy of DESIGN.md section 35, and `y`
 // is the response those two stage themselves (the host bodies fill it in with the offset and the trials).
 struct GlmmLik { GlmmKind kind; const double* gx; const double* gw; int n_nodes; const double* off; const double* trials; bool unit;

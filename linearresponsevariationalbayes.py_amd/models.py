@@ -663,7 +663,7 @@ class DeviceContext(object):
     # ---- zero-truncated NB2 mixed model (lrvb_glmm_ztnegbin_*): the (shifted) offset of `set_offset`, the dispersion of `set_dispersion` ----
     def set_dispersion(self, dispersion):
         """The per-row dispersion phi > 0 of the zero-truncated negative binomial mixed model, or None to clear it
-        (lrvb_set_dispersion).  Only the `glmm_ztnegbin_*` entries read it; the resident group sums are dropped."""
+        (lrvb_set_dispersion) -- and the precision of the Beta one.  Only the `glmm_ztnegbin_*` and `glmm_beta_*` entries read it; the resident group sums are dropped."""
         if dispersion is None:
             self._check(self._lib.lrvb_set_dispersion(self._h, None, 0))
             return
@@ -689,6 +689,21 @@ class DeviceContext(object):
     def glmm_ztnegbin_predict(self, mean, var, e, r, gh_x, gh_w, cov_beta, n0=0, n1=None, new=None):
         """Fitted means of the truncated NB2 count (lrvb_glmm_ztnegbin_predict); new rows carry a shifted offset and their dispersion."""
         return self._glmm_predict(self._lib.lrvb_glmm_ztnegbin_predict, True, 2, mean, var, e, r, gh_x, gh_w, cov_beta, n0, n1, new)
+
+    # ---- Beta mixed model (lrvb_glmm_beta_*): the raw offset of `set_offset`, the precision of `set_dispersion`, logit(y) as y ----
+    def glmm_beta_terms(self, mean, var, e, r, gh_x, gh_w, want_grad=True, want_hess=True, want_border=True):
+        """Data term of the Beta mixed model with K effects per group, the offset of `set_offset` and the precision phi of
+        `set_dispersion` (lrvb_glmm_beta_terms); the context's y holds logit(y).  What `glmm_slopes_terms` returns, in its
+        layouts.  The group sums stay resident for `glmm_slopes_schur`.  No finite point is refused."""
+        return self._glmm_terms(self._lib.lrvb_glmm_beta_terms, True, True, mean, var, e, r, gh_x, gh_w, want_grad, want_hess, want_border)
+
+    def glmm_beta_obs_influence(self, mean, var, e, r, gh_x, gh_w, A, n0=0, n1=None):
+        """(n1 - n0) x Q rows of the Beta mixed model, as `glmm_slopes_obs_influence` (lrvb_glmm_beta_obs_influence)."""
+        return self._glmm_obs_influence(self._lib.lrvb_glmm_beta_obs_influence, True, True, mean, var, e, r, gh_x, gh_w, A, n0, n1)
+
+    def glmm_beta_group_influence(self, mean, var, e, r, gh_x, gh_w, A):
+        """G x Q group influence of the Beta mixed model, as `glmm_slopes_group_influence` (lrvb_glmm_beta_group_influence)."""
+        return self._glmm_group_influence(self._lib.lrvb_glmm_beta_group_influence, True, True, mean, var, e, r, gh_x, gh_w, A)
 
     # ---- multinomial (softmax) regression: beta is (K - 1) x n_cols, D = (K - 1) n_cols (lrvb_softmax_*) --------------------
     def softmax_set_labels(self, labels, n_classes):

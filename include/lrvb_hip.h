@@ -738,6 +738,32 @@ int lrvb_glmm_beta_group_influence(lrvb_ctx* ctx, const double* mean, const doub
                                    const double* r, int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
                                    const double* A_global, const double* A_local, int64_t Q, double* out);
 
+/* ---- the derivative in the log-dispersion of the Beta and the NB2 mixed model -----------------------------
+ * The dispersion of either model as phi_n = e^lambda phi0_n with ONE scalar lambda; d/d lambda = phi_n d/d phi_n at a fixed point.
+ * With h the row term of the family's terms entry (lrvb_glmm_beta_terms; lrvb_glmm_binomial_terms with the logit link, the
+ * trials y + phi and the offset o - log phi: NB2) and h_l, h_ll its first and second derivative in lambda at fixed t:
+ *   d_out[0] = sum_n w_n E h_l,   d_out[1] = sum_n w_n E h_ll                                   (data terms only: the constant that the
+ *                                                                                            value drops depends on phi too and is the caller's),
+ *   cross_global_out (2 P) = [sum_n d1_n x_n | sum_n d2_n x_n o x_n],   d1 = w E d_t h_l,  d2 = w E d_t^2 h_l / 2,
+ *   cross_local_out (G x 2 K, row-major) = per group [sum d1 z_k (K) | sum d2 z_k^2 (K)],
+ * the derivative in lambda of the gradient of the data term in the coordinates (mean, var, e, r) of the terms entries.  Beta:
+ *   h_l = a psi(1 + a) + b psi(1 + b) - l a - 2,  a = phi sigma(t), b = phi sigma(-t), l = logit y;  NB2, eta = t - log phi, m = y + phi:
+ *   h_l = phi softplus(eta) - m sigma(eta) + y.
+ * The context's state is that of the family's terms entry, and the dispersion of lrvb_set_dispersion for BOTH (the binomial
+ * entries themselves never read it: results of lrvb_glmm_binomial_* are unchanged by that call).  No dispersion, or one of another
+ * length than n_obs (NB2 also: no trials): LRVB_ERR_STATE.  P > 64, K outside 1..4, n_nodes outside 1..128, and for the NB2 entry a
+ * link other than logit: LRVB_ERR_UNSUPPORTED.  A result that is not finite after the reduction: LRVB_ERR_INVALID.  The other
+ * errors are those of lrvb_glmm_beta_terms.  One pass over the group-sorted rows; no atomics, a fixed summation order: two calls
+ * at one point are bitwise equal; an empty group's row is zero and a row of weight zero contributes exact zeros.  The entries
+ * write NEITHER the resident group sums NOR the factor NOR the group covariance of the context and drop none of them.  With a
+ * reduce hook installed the packed result [cross_local | cross_global | d] goes through it in ONE call.                        */
+int lrvb_glmm_beta_dispersion_terms(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                                    int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes, double* d_out,
+                                    double* cross_global_out, double* cross_local_out);
+int lrvb_glmm_negbin_dispersion_terms(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                                      int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes, double* d_out,
+                                      double* cross_global_out, double* cross_local_out);
+
 /* ---- group blocks of H^-1, fitted values and predictions with their linear-response variance ------------
  * For every mixed model with K <= 4 effects per group.  After a successful lrvb_glmm_slopes_schur (the factor L_g, U_g resident)
  * and a factored free Schur complement S on the caller's side, with

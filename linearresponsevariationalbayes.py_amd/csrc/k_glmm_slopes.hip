@@ -248,6 +248,121 @@ int launch_glmm_slopes_rows(lrvb_ctx* c, const GlmmLik& lik, int Kz, const doubl
 }
 int glmm_slopes_ncol(int P, int Kz) { return 2 * Kz + Kz * (2 * Kz + 1) + 4 * Kz * P; }
 
+// ---- the derivative in the log-dispersion (lrvb_glmm_beta_dispersion_terms / lrvb_glmm_negbin_dispersion_terms) ----
+// ONE pass over the rows in group-sorted order on the head of glmm_slopes_rows_kernel: the same tiles, the same staging
+// (gs_stage_sorted_tile), four lanes per row for rho and s by the same dot products, then DLik::dmoments.  Per row
+//   d1 = w E d_t h_l   (the derivative in rho of the row's h_l term),   d2 = w E d_t^2 h_l / 2   (the one in s),
+// written to the ORIGINAL row position (two coefficient rows: X^T d1 and (X o X)^T d2 are the library's weighted products) and to
+// LDS; per group the 2 K segmented sums [sum d1 z_k | sum d2 z_k^2], thread t < 2 K owning column t, the tile's rows walked in
+// order and flushed at every change of group as the rows kernel flushes (gs_flush_dst at ncol = 2 K; glmm_fixup_kernel adds the
+// partial rows in tile order); per tile the two partial scalars sum w E h_l and sum w E h_ll (vpart[tile], vpart[n_tiles + tile]),
+// finished in tile order by sum_partials_kernel.  No border, no local blocks, no products table.  No atomics: fixed-order sums,
+// bitwise reproducible.  Empty groups keep the zeros the caller wrote; a row of weight zero contributes w x = 0 exactly.
+template <class DLik>
+__global__ __launch_bounds__(256)
+void glmm_disp_rows_kernel(i64 N, int P, int Kz, i64 G, const double* __restrict__ X, const double* __restrict__ Z,
+                           const double* __restrict__ w, const i64* __restrict__ perm, const i64* __restrict__ offs,
+                           const double* __restrict__ m, const double* __restrict__ vb, const double* __restrict__ eg,
+                           const double* __restrict__ rg, typename DLik::Args la, double* __restrict__ coef, i64 NP,
+                           double* __restrict__ gsum, double* __restrict__ part, double* __restrict__ vpart)
+{
+    __shared__ double xs[GLMM_T * GS_XS], cf[2 * GLMM_T], ms[64], vs[64], red[8];
+    __shared__ typename DLik::Lds lik;
+    __shared__ i64 s_row[GLMM_T];
+    __shared__ int s_gid[GLMM_T], s_whole[GLMM_T];
+    const int tid = threadIdx.x;
+    const int ncol = 2 * Kz;
+    DLik::init(lik, la, tid);
+    if (tid < P) { ms[tid] = m[tid]; vs[tid] = vb[tid]; }
+    const i64 n_tiles = (N + GLMM_T - 1) / GLMM_T;
+    const int row = tid >> 2, q4 = tid & 3;
+    // the column of this thread (tid < 2 K): d1 z_k for tid < K, d2 z_k^2 behind them
+    const bool has_col = tid < ncol, c_sq = tid >= Kz;
+    const int c_z = P + (c_sq ? tid - Kz : tid), c_row = c_sq ? 1 : 0;
+    for (i64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const i64 t0 = tile * GLMM_T;
+        const int rows = (int)(N - t0 < GLMM_T ? N - t0 : GLMM_T);
+        __syncthreads();                                                 // the previous tile is consumed (and the nodes, m, v are in place)
+        gs_stage_sorted_tile<DLik, GS_XS>(tid, t0, rows, P, Kz, G, X, Z, perm, offs, la, lik, xs, s_row, s_gid, s_whole);
+        double rho = 0.0, s = 0.0;
+        if (row < rows) {
+            const double* xr = xs + row * GS_XS;
+            for (int j = q4; j < P; j += 4) { const double x = xr[j]; rho += x * ms[j]; s += x * x * vs[j]; }
+            if (q4 < Kz) {
+                const i64 gk = (i64)s_gid[row] * Kz + q4;
+                const double z = xr[P + q4];
+                rho += z * eg[gk]; s += z * z * rg[gk];
+            }
+        }
+        rho += __shfl_xor(rho, 1); s += __shfl_xor(s, 1);
+        rho += __shfl_xor(rho, 2); s += __shfl_xor(s, 2);
+        const DispMoments mo = DLik::dmoments(lik, la, row < rows, q4, rho, s);
+        double c1 = 0.0, c2 = 0.0;
+        if (q4 == 0) {
+            double d1 = 0.0, d2 = 0.0;
+            if (row < rows) {
+                const i64 pr = s_row[row];
+                const double wi = w[pr];
+                d1 = wi * mo.t1; d2 = wi * 0.5 * mo.t2;
+                c1 = wi * mo.hl; c2 = wi * mo.hll;
+                coef[pr] = d1; coef[NP + pr] = d2;
+            }
+            cf[row] = d1; cf[GLMM_T + row] = d2;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { c1 += __shfl_xor(c1, off); c2 += __shfl_xor(c2, off); }
+        if ((tid & 63) == 0) { red[tid >> 6] = c1; red[4 + (tid >> 6)] = c2; }
+        __syncthreads();
+        if (tid == 0) {
+            vpart[tile] = (red[0] + red[1]) + (red[2] + red[3]);
+            vpart[n_tiles + tile] = (red[4] + red[5]) + (red[6] + red[7]);
+        }
+        // segmented sums over the tile's rows, in row order
+        if (has_col) {
+            double acc = 0.0;
+            int run_start = 0;
+            for (int rr = 0; rr < rows; ++rr) {
+                double z = xs[rr * GS_XS + c_z];
+                if (c_sq) z *= z;
+                acc += cf[c_row * GLMM_T + rr] * z;
+                const int g = s_gid[rr];
+                if (rr == rows - 1 || s_gid[rr + 1] != g) {
+                    gs_flush_dst(s_whole[rr], g, tile, run_start, ncol, gsum, part)[tid] = acc;
+                    acc = 0.0; run_start = rr + 1;
+                }
+            }
+        }
+    }
+}
+
+template <class DLik>
+static int gs_launch_disp(lrvb_ctx* c, int Kz, typename DLik::Args la, const double* m, const double* vb, const double* eg, const double* rg,
+                          double* coef, i64 NP, double* gsum, double* part, double* vpart) {
+    const i64 N = c->N, G = c->n_groups;
+    if (c->P > 64 || !DLik::args_ok(la)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "%s", DLik::LIMITS);
+    const i64* gdev = reinterpret_cast<const i64*>(c->groups.p);
+    const double* Z = c->gz.p;
+    LRVB_TRY(gs_with_K(Kz, DLik::LIMITS, [&](auto) {
+        hipLaunchKernelGGL(glmm_disp_rows_kernel<DLik>, dim3(glmm_grid(N)), dim3(256), 0, c->stream, N, (int)c->P, Kz, G, (const double*)c->X.p, Z,
+                           (const double*)c->w.p, gdev, gdev + N, m, vb, eg, rg, la, coef, NP, gsum, part, vpart);
+    }));
+    hipLaunchKernelGGL(glmm_fixup_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, G, 2 * Kz, gdev + N, (const double*)part, gsum);
+    HIP_TRY(hipGetLastError());
+    return LRVB_OK;
+}
+
+// `lik` is the likelihood of the family's terms entry (GLMM_BETA, or GLMM_BINOMIAL with the logit link: NB2), `disp` the resident
+// dispersion; coef 2 x NP (zeroed by the caller), gsum G x 2 K (zeroed by the caller), part 2 x 2 K and vpart 2 doubles per tile.
+int launch_glmm_disp_rows(lrvb_ctx* c, const GlmmLik& lik, const double* disp, int Kz, const double* m, const double* vb, const double* eg,
+                          const double* rg, double* coef, i64 NP, double* gsum, double* part, double* vpart) {
+    const LogisticLik::Args q{lik.gx, lik.gw, lik.n_nodes};
+    if (lik.kind == GLMM_BETA)
+        return gs_launch_disp<BetaDispLik>(c, Kz, BetaDispLik::Args{q, lik.off, disp, lik.y}, m, vb, eg, rg, coef, NP, gsum, part, vpart);
+    if (lik.kind == GLMM_BINOMIAL && lik.link == GLMM_LINK_LOGIT)
+        return gs_launch_disp<NegBinDispLik>(c, Kz, NegBinDispLik::Args{q, lik.off, lik.trials, disp, lik.y}, m, vb, eg, rg, coef, NP, gsum, part, vpart);
+    LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the dispersion derivative is that of the Beta and the negative binomial mixed model");
+}
+
 // A = L L^T of one local block from its upper triangle a (row-major), L row-major into Ls; false where a pivot is not positive
 // (the factor then continues with 1 in its place).  One thread; shared by the elimination and by the two substitution kernels
 // of the solve below, so that all three see the same L bit for bit.

@@ -791,6 +791,121 @@ struct BetaLik {
     }
 };
 
+// ---- the dispersion-derivative policies ----------------------------------------------------------------------
+// The dispersion of the Beta and the NB2 model as phi_n = e^lambda phi0_n with ONE scalar lambda: every derivative below is in
+// lambda at fixed t, d/d lambda = phi d/d phi.  A policy of this kind serves glmm_disp_rows_kernel (k_glmm_slopes.hip) and supplies
+// the staging of its base policy and ONE function
+//   dmoments(lik, la, live, q4, rho, s) -> (E h_l, E d_t h_l, E d_t^2 h_l, E h_ll) per unit weight, t ~ N(rho + offset, s),
+// on all four lanes of a row: the nodes shared as LogisticLik::moments shares them, four accumulators per lane, two xor shuffles in
+// fixed order, no atomics.  By Stein's identity E d_t h_l is the derivative of E h_l in rho and E d_t^2 h_l / 2 the one in s: the two
+// coefficient rows of the cross Hessian d^2 F / d theta d lambda.
+struct DispMoments { double hl, t1, t2, hll; };
+
+// Beta (the shifted form of BetaLik): a = phi mu, b = phi (1 - mu), v = mu (1 - mu), d = 1 - 2 mu, l = logit y,
+//   h_l  = a psi(1 + a) + b psi(1 + b) - l a - 2,
+//   h_ll = a psi(1 + a) + a^2 psi'(1 + a) + b psi(1 + b) + b^2 psi'(1 + b) - l a,
+//   K1 = phi [psi(1 + a) + a psi'(1 + a) - psi(1 + b) - b psi'(1 + b) - l],   K2 = phi^2 [2 psi'(1 + a) + a psi''(1 + a) + 2 psi'(1 + b) + b psi''(1 + b)],
+//   d_t h_l = K1 v,   d_t^2 h_l = K2 v^2 + K1 v d.
+// mu and 1 - mu from e = exp(-|t|) as BetaLik::node forms them; psi, psi', psi'' from BetaLik::polygamma<5>, whose lgamma and psi'''
+// are not read here and fall to the compiler (the function is inlined).  Every polygamma argument is >= 1.  The -2 is E of a
+// constant: added once per row behind the shuffles.
+struct BetaDispLik {
+    typedef BetaLik::Args Args;
+    typedef BetaLik::Lds Lds;
+    static constexpr const char* LIMITS = BetaLik::LIMITS;
+    static bool args_ok(const Args& a) { return BetaLik::args_ok(a); }
+    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { BetaLik::init(L, a, tid); }
+    static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src) { BetaLik::stage_row(L, a, t, live, src); }
+    static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return BetaLik::row_shift(L, row); }
+    static __device__ __forceinline__ int lane_row() { return BetaLik::lane_row(); }
+
+    static __device__ __forceinline__ DispMoments dmoments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
+    {
+        const int row = lane_row();
+        const double phi = L.s_phi[row], l = L.s_y[row];
+        rho += L.s_off[row];
+        double e0 = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0;
+        if (live) {
+            const double sd = sqrt(fmax(s, 0.0));
+            for (int k = q4; k < a.q.nq; k += 4) {
+                const double t = rho + sd * L.q.sx[k], wk = L.q.sw[k];
+                const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
+                const bool pos = t >= 0.0;
+                const double mu = pos ? ie : e * ie, nu = pos ? e * ie : ie;  // sigma(t) and sigma(-t)
+                const double g2 = e * ie * ie;                               // v = mu (1 - mu)
+                const double om = (1.0 - e) * ie;
+                const double d = pos ? -om : om;                             // 1 - 2 mu
+                const double pa_ = phi * mu, pb_ = phi * nu;
+                double pa[5], pb[5];
+                BetaLik::polygamma<5>(1.0 + pa_, pa);
+                BetaLik::polygamma<5>(1.0 + pb_, pb);
+                const double first = pa_ * pa[1] + pb_ * pb[1] - l * pa_;    // h_l + 2
+                const double ta = pa_ * pa[2], tb = pb_ * pb[2];             // a psi'(1 + a), b psi'(1 + b)
+                const double K1 = phi * (((pa[1] + ta) - (pb[1] + tb)) - l);
+                const double K2 = phi * phi * ((2.0 * pa[2] + pa_ * pa[3]) + (2.0 * pb[2] + pb_ * pb[3]));
+                const double K1v = K1 * g2;
+                e0 += wk * first; e1 += wk * K1v; e2 += wk * (K2 * g2 * g2 + K1v * d); e3 += wk * (first + pa_ * ta + pb_ * tb);
+            }
+        }
+#pragma unroll
+        for (int off = 1; off <= 2; off <<= 1) {
+            e0 += __shfl_xor(e0, off); e1 += __shfl_xor(e1, off); e2 += __shfl_xor(e2, off); e3 += __shfl_xor(e3, off);
+        }
+        return {live ? e0 - 2.0 : 0.0, e1, e2, e3};
+    }
+};
+
+// NB2 through the binomial context: eta = t - log phi is what that context integrates over (its offset is o - log phi), m = y + phi
+// its trials.  On the logistic nodes, with sp = softplus(eta), sg = sigma(eta) and its derivatives g2, g3 (LogisticLik::moments),
+//   h_l  = phi sp - m sg + y,   h_ll = phi sp - 2 phi sg + m g2,   d_t h_l = phi sg - m g2,   d_t^2 h_l = phi g2 - m g3.
+// The shifted offset, the trials and phi ITSELF are staged (phi is never recovered as trials - y: at phi << y that loses it), and y
+// from the context's responses.  The E sums of sp, sg, g2, g3 are formed per lane and combined with phi, m and y behind the
+// shuffles (all four are linear in them).
+struct NegBinDispLik {
+    struct Args { LogisticLik::Args q; const double* __restrict__ off; const double* __restrict__ trials; const double* __restrict__ disp;
+                  const double* __restrict__ y; };                          // off may be nullptr
+    struct Lds { LogisticLik::Lds q; double s_off[GLMM_T], s_m[GLMM_T], s_phi[GLMM_T], s_y[GLMM_T]; };
+    static constexpr const char* LIMITS = "negative binomial mixed model: P <= 64, 1 <= K <= 4, at most 128 nodes";
+    static bool args_ok(const Args& a) { return LogisticLik::args_ok(a.q) && a.trials != nullptr && a.disp != nullptr && a.y != nullptr; }
+    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { LogisticLik::init(L.q, a.q, tid); }
+    static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
+    {
+        L.s_off[t] = (a.off && live) ? a.off[src] : 0.0;
+        L.s_m[t] = live ? a.trials[src] : 1.0;
+        L.s_phi[t] = live ? a.disp[src] : 1.0;
+        L.s_y[t] = live ? a.y[src] : 0.0;
+    }
+    static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_off[row]; }
+    static __device__ __forceinline__ int lane_row() { return (int)(threadIdx.x >> 2); }
+
+    static __device__ __forceinline__ DispMoments dmoments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
+    {
+        const int row = lane_row();
+        const double phi = L.s_phi[row], mt = L.s_m[row], yt = L.s_y[row];
+        rho += L.s_off[row];
+        double v = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0;
+        if (live) {
+            const double sd = sqrt(fmax(s, 0.0));
+            for (int k = q4; k < a.q.nq; k += 4) {
+                const double t = rho + sd * L.q.sx[k], wk = L.q.sw[k];
+                const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
+                const double sp = (t > 0.0 ? t : 0.0) + log1p(e);
+                const double sg = t >= 0.0 ? ie : e * ie;
+                const double g2 = e * ie * ie;
+                const double om = (1.0 - e) * ie;                        // |1 - 2 sigma|
+                const double g3 = t >= 0.0 ? -g2 * om : g2 * om;
+                v += wk * sp; e1 += wk * sg; e2 += wk * g2; e3 += wk * g3;
+            }
+        }
+#pragma unroll
+        for (int off = 1; off <= 2; off <<= 1) {
+            v += __shfl_xor(v, off); e1 += __shfl_xor(e1, off); e2 += __shfl_xor(e2, off); e3 += __shfl_xor(e3, off);
+        }
+        if (!live) return {0.0, 0.0, 0.0, 0.0};
+        return {(phi * v - mt * e1) + yt, phi * e1 - mt * e2, phi * e2 - mt * e3, phi * (v - 2.0 * e1) + mt * e2};
+    }
+};
+
 // ---- what the kernels over group-sorted rows share ----------------------------------------------------------------------------------
 // The head of a tile of sorted rows: thread t < GLMM_T finds row t0 + t's original position, its group (the last g with
 // offs[g] <= i) and whether that group lies whole inside the tile; then the tile's rows of X and Z are gathered into xs (row

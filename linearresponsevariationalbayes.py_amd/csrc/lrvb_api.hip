@@ -3175,6 +3175,68 @@ extern "C" int lrvb_glmm_beta_group_influence(lrvb_ctx* c, const double* mean, c
     return glmms_group_influence(c, glmms_beta(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out);
 }
 
+// ---- the derivative in the log-dispersion of the Beta and the NB2 mixed model (k_glmm_slopes.hip) ----------
+// The checks of the family's terms entry, in its order, then the dispersion (the binomial kind does not ask for one).  Everything
+// lives in c->work1, as the influence entries keep theirs:
+//   [nodes 256 | m, v | e, r | d1, d2 (2 NP, original order, zero past N) | tile partials (2 (2 K) per tile) | value partials (2 per tile) |
+//    local sums (G x 2 K) | global sums (2 P) | d (2)]
+// the last three adjacent, so that the packed result goes through the reduce hook in ONE piece.  Neither c->glmms nor the factor
+// nor the group covariance is written, and nothing is dropped: a resident solve after this entry rebuilds nothing.
+static int glmms_dispersion_terms(lrvb_ctx* c, GlmmLik lik, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                  const double* r_loc, int64_t G_in, int64_t K, double* d_out, double* cross_global_out,
+                                  double* cross_local_out) {
+    LRVB_TRY(glmms_check(c, lik, mean, var, P_in, e_loc, r_loc, G_in, K, !d_out || !cross_global_out || !cross_local_out));
+    if (c->gdisp_n == 0) LRVB_FAIL(LRVB_ERR_STATE, "no dispersion: call lrvb_set_dispersion first");
+    if (c->gdisp_n != c->N)
+        LRVB_FAIL(LRVB_ERR_STATE, "the dispersion has %lld entries, the model has %lld observations", (long long)c->gdisp_n, (long long)c->N);
+    if (lik.kind == GLMM_BINOMIAL && c->gtr_n == 0)
+        LRVB_FAIL(LRVB_ERR_STATE, "no trials: the negative binomial model keeps y + phi there (lrvb_set_trials)");
+    const i64 N = c->N, P = c->P, G = c->n_groups, GK = G * K, K2 = 2 * K;
+    DevBuf& X2 = c->mx_Xk;
+    if (!c->x2_ready || X2.n < (size_t)(N * P)) {
+        LRVB_TRY(buf_reserve(c, X2, (size_t)(N * P)));
+        EW(square_kernel, N * P, (const double*)c->X.p, X2.p);
+        c->x2_ready = true;
+    }
+    const i64 NP = up(N + 64), n_tiles = glmm_num_tiles(N), nres = G * K2 + 2 * P + 2;
+    GlmmPoint pt;
+    LRVB_TRY(glmms_point_upload(c, lik, mean, var, e_loc, r_loc, P, GK, (size_t)(2 * NP + up(n_tiles * 2 * K2) + up(2 * n_tiles) + nres), &pt));
+    if (lik.kind == GLMM_BINOMIAL) lik.y = c->y.p;                        // the counts: h_l = phi sp - m sigma + y
+    double* coef = pt.g + pt.doubles; double* part = coef + 2 * NP; double* vpart = part + up(n_tiles * 2 * K2);
+    double* gsum = vpart + up(2 * n_tiles); double* gred = gsum + G * K2; double* dred = gred + 2 * P;
+    HIP_TRY(hipMemsetAsync(coef, 0, (size_t)(2 * NP) * sizeof(double), c->stream));
+    HIP_TRY(hipMemsetAsync(gsum, 0, (size_t)nres * sizeof(double), c->stream));       // empty groups keep the zeros
+    LRVB_TRY(launch_glmm_disp_rows(c, lik, c->gdisp.p, (int)K, pt.m, pt.v, pt.e, pt.r, coef, NP, gsum, part, vpart));
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, c->stream, (const double*)vpart, n_tiles, dred);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, c->stream, (const double*)(vpart + n_tiles), n_tiles, dred + 1);
+    HIP_TRY(hipGetLastError());
+    LRVB_TRY(launch_gemv(c, true, N, P, 1.0, c->X.p, P, coef, 0.0, gred));
+    LRVB_TRY(launch_gemv(c, true, N, P, 1.0, X2.p, P, coef + NP, 0.0, gred + P));
+    LRVB_TRY(obs_reduce(c, gsum, nres));
+    LRVB_TRY(d2h(c, d_out, dred, 2));
+    if (!std::isfinite(d_out[0]) || !std::isfinite(d_out[1]))
+        LRVB_FAIL(LRVB_ERR_INVALID, "the dispersion derivative of the %s data term is not finite at this point", lik.kind == GLMM_BETA ? "Beta" : "negative binomial");
+    LRVB_TRY(d2h(c, cross_global_out, gred, (size_t)(2 * P)));
+    return d2h(c, cross_local_out, gsum, (size_t)(G * K2));
+}
+
+extern "C" int lrvb_glmm_beta_dispersion_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                               const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                               int32_t n_nodes, double* d_out, double* cross_global_out, double* cross_local_out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_dispersion_terms(c, glmms_beta(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, d_out, cross_global_out,
+                                  cross_local_out);
+}
+
+extern "C" int lrvb_glmm_negbin_dispersion_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                                 const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                                 int32_t n_nodes, double* d_out, double* cross_global_out, double* cross_local_out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_dispersion_terms(c, glmms_binomial(c, gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, d_out, cross_global_out,
+                                  cross_local_out);
+}
+
 // ---- group blocks of H^-1 and predictions with their linear-response variance (k_glmm_slopes.hip) ----------
 static int glmms_group_cov(lrvb_ctx* c, const double* W, const double* s, int64_t P_in, int64_t G_in, int64_t K, int64_t NC, bool arrow,
                            double* out) {

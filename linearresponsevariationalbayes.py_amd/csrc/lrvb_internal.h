@@ -277,6 +277,11 @@ int  launch_glmm_slopes_rows(lrvb_ctx* c, const GlmmLik& lik, int K, const doubl
                              double* coef /* original row order: 5 x NP (logistic, binomial), 2 x NP: a1 | h = w psi (Poisson) */, i64 NP,
                              double* gsum /* G x ncol, zeroed by the caller */,
                              double* part /* 2 ncol doubles per tile of glmm_num_tiles */, double* vpart);
+int  launch_glmm_disp_rows(lrvb_ctx* c, const GlmmLik& lik /* Beta, or binomial with the logit link (NB2) */, const double* disp /* phi, N */,
+                           int K, const double* m, const double* vb, const double* eg, const double* rg,
+                           double* coef /* original row order: 2 x NP, d1 | d2 */, i64 NP,
+                           double* gsum /* G x 2 K, zeroed by the caller */, double* part /* 2 (2 K) doubles per tile of glmm_num_tiles */,
+                           double* vpart /* 2 per tile */);
 int  launch_glmm_poisson_scale_blocks(lrvb_ctx* c, double* Hb /* 3 x P x P, all formed with h: blocks 1, 2 times 1/2, 1/4 */);
 int  launch_glmm_slopes_schur_rows(lrvb_ctx* c, int K, const double* gsum, const double* loc /* G x K (2 K + 1) */,
                                    const double* scale /* G x 2 K */, const double* closed /* G x 2 K x 3 */,

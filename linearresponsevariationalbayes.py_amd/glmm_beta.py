@@ -3,7 +3,8 @@ inside (0, 1) -- rates, shares, cover fractions -- glmmTMB's `beta_family(link =
 
     y_n ~ Beta(mu_n phi_n, (1 - mu_n) phi_n),   mu_n = sigma(t_n),   t_n = o_n + x_n . beta + z_n . u_{g(n)}
 
-with a KNOWN precision phi_n > 0 (a scalar or one value per row; fixed data, not estimated: Var y = mu (1 - mu) / (1 + phi)).
+with a precision phi_n = e^lambda phi0_n > 0 (phi0 a scalar or one value per row, Var y = mu (1 - mu) / (1 + phi)); lambda is ONE
+declared hyper-parameter, `log_dispersion_par`, 0 at construction, estimated by `fit_dispersion`.
 Priors, variational families, parameter layout, vector and free coordinates, n_global = 2 P + 4 K and the coupled rows are those of
 `LogisticGLMMSlopesObjective` (glmm_slopes.py).  With l = logit(y) the row's term is, constants dropped,
 
@@ -26,10 +27,10 @@ The O(N) work is `lrvb_glmm_beta_terms` (csrc/k_glmm_slopes.hip); everything aft
 unchanged.  The fitted mean E sigma(t) does not depend on phi: predictions go through the binomial predict entry with one trial.
 """
 import numpy as np
-from scipy.special import gammaln
+from scipy.special import digamma, gammaln, polygamma
 
 from . import _hip
-from .glmm_binomial import _nodes, _row_vector
+from .glmm_binomial import _LogDispersion, _nodes, _row_vector
 from .glmm_slopes import _LogisticMixedModel, _SlopesArrow
 
 # Stirling / Bernoulli series of BetaLik::polygamma at z >= 10, in w^2 = 1 / z^2, k = 1 .. 8
@@ -116,13 +117,47 @@ def beta_response_mean(rho, s, gh_x, gh_w):
     return (np.where(t >= 0.0, ie, e * ie) * wk).sum(-1)
 
 
-class BetaGLMMObjective(_SlopesArrow, _LogisticMixedModel):
+def beta_h_dispersion(t, phi, logit_y):
+    """[h_l, d_t h_l, d_t^2 h_l, h_ll] at t: the row term h of `beta_h` differentiated in lambda, phi = e^lambda phi0, at fixed t
+    (d/d lambda = phi d/d phi), by the formulas of the kernels (k_glmm_walk.h, BetaDispLik) on the shifted form: with a = phi mu,
+    b = phi (1 - mu), v = mu (1 - mu), d = 1 - 2 mu,
+        h_l = a psi(1 + a) + b psi(1 + b) - l a - 2,   h_ll = h_l + 2 + a^2 psi'(1 + a) + b^2 psi'(1 + b),
+        K1 = phi [psi(1 + a) + a psi'(1 + a) - psi(1 + b) - b psi'(1 + b) - l],
+        K2 = phi^2 [2 psi'(1 + a) + a psi''(1 + a) + 2 psi'(1 + b) + b psi''(1 + b)],   d_t h_l = K1 v,   d_t^2 h_l = K2 v^2 + K1 v d."""
+    t, phi, l = np.broadcast_arrays(np.asarray(t, dtype=np.float64), np.asarray(phi, dtype=np.float64),
+                                    np.asarray(logit_y, dtype=np.float64))
+    e = np.exp(-np.abs(t))
+    ie = 1.0 / (1.0 + e)
+    pos = t >= 0.0
+    mu, nu = np.where(pos, ie, e * ie), np.where(pos, e * ie, ie)
+    g2 = e * ie * ie
+    om = (1.0 - e) * ie
+    d = np.where(pos, -om, om)
+    a, b = phi * mu, phi * nu
+    pa, pb = polygamma_ge1(1.0 + a, 3), polygamma_ge1(1.0 + b, 3)
+    first = a * pa[1] + b * pb[1] - l * a
+    ta, tb = a * pa[2], b * pb[2]
+    K1 = phi * (((pa[1] + ta) - (pb[1] + tb)) - l)
+    K2 = phi * phi * ((2.0 * pa[2] + a * pa[3]) + (2.0 * pb[2] + b * pb[3]))
+    K1v = K1 * g2
+    return [first - 2.0, K1v, K2 * g2 * g2 + K1v * d, first + a * ta + b * tb]
+
+
+def beta_expected_h_dispersion(rho, s, logit_y, phi, gh_x, gh_w):
+    """(E h_l, E d_t h_l, E d_t^2 h_l, E h_ll), a 4 x ... array, t ~ N(rho, s) (rho including the offset), summed over the
+    Gauss-Hermite nodes as the kernels do.  d1 = w times row 1 and d2 = w times row 2 / 2 are the coefficient rows of the device."""
+    t, wk = _nodes(rho, s, gh_x, gh_w)
+    phi, l = np.asarray(phi, dtype=np.float64), np.asarray(logit_y, dtype=np.float64)
+    return np.stack([(a * wk).sum(-1) for a in beta_h_dispersion(t, phi[..., None], l[..., None])])
+
+
+class BetaGLMMObjective(_LogDispersion, _SlopesArrow, _LogisticMixedModel):
     _loss = 'logistic'
 
     def __init__(self, par, x, y, z, groups, n_groups, dispersion, offset=None, beta_prior_info=1.0, mu_prior=(0.0, 1.0),
                  tau_prior=(1.0, 1.0), gh_deg=20, names=('beta', 'mu', 'tau', 'u'), weights=None, device=0):
         """y: proportions, finite and STRICTLY inside (0, 1); exact zeros or ones are refused, not clipped.  dispersion: the
-        precision phi > 0, a scalar or N values, as in `NegBinomialGLMMObjective` -- fixed data, not estimated.  z: the N x K group
+        precision phi > 0, a scalar or N values, as in `NegBinomialGLMMObjective`: phi0 of phi = e^lambda phi0, lambda = `log_dispersion_par`.  z: the N x K group
         design, or None for one effect per group with the unit design.  offset: the N offsets o_n on the logit scale, or None for
         zero.  `value` is -ELBO up to the constant `log_norm_const()`.  All checks run before the device context is created."""
         y = _hip.as_f64(y).ravel()
@@ -146,6 +181,22 @@ class BetaGLMMObjective(_SlopesArrow, _LogisticMixedModel):
         self._y01, self._phi, self._offset = y.copy(), phi, offset
         self.ctx.set_offset(offset)
         self.ctx.set_dispersion(phi)
+        self._declare_dispersion(phi)
+
+    # ---- the precision as a hyper-parameter ----------------------------------------------------------------
+    def _push_dispersion(self, phi):
+        self.ctx.set_dispersion(phi)
+
+    def _dispersion_entry(self, point):
+        return self.ctx.glmm_beta_dispersion_terms(*point)
+
+    def log_norm_const_dispersion(self):
+        """(first, second) derivative in lambda of `log_norm_const()` at the current weights and precision:
+        sum w [phi psi(phi) + phi log(1 - y)], and that plus sum w phi^2 psi'(phi)."""
+        w = np.asarray(self.weights_par.get_vector(), dtype=np.float64).ravel()
+        phi = self._phi
+        c1 = float(np.sum(w * (phi * digamma(phi) + phi * np.log1p(-self._y01))))
+        return c1, c1 + float(np.sum(w * phi * phi * polygamma(1, phi)))
 
     # ---- the device entries -------------------------------------------------------------------------------------------------
     def _terms(self, *point, **want):

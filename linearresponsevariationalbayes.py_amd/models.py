@@ -705,6 +705,32 @@ class DeviceContext(object):
         """G x Q group influence of the Beta mixed model, as `glmm_slopes_group_influence` (lrvb_glmm_beta_group_influence)."""
         return self._glmm_group_influence(self._lib.lrvb_glmm_beta_group_influence, True, True, mean, var, e, r, gh_x, gh_w, A)
 
+    # ---- the derivative in the log-dispersion of the Beta and the NB2 mixed model (lrvb_glmm_*_dispersion_terms) ----------------
+    def _glmm_dispersion_terms(self, fn, mean, var, e, r, gh_x, gh_w):
+        m, v = _hip.as_f64(mean).ravel(), _hip.as_f64(var).ravel()
+        e, r = _hip.as_f64(e), _hip.as_f64(r)
+        gx, gw = _hip.as_f64(gh_x).ravel(), _hip.as_f64(gh_w).ravel()
+        P = self.n_cols
+        if e.ndim != 2 or r.shape != e.shape or m.size != P or v.size != P or gx.size != gw.size:
+            raise ValueError('expected mean and var of length {}, e and r of one shape G x K and as many weights as nodes'.format(P))
+        G, K = e.shape
+        d, cg, cl = np.empty(2), np.empty(2 * P), np.empty((G, 2 * max(K, 0)))
+        self._check(fn(self._h, _hip.ptr(m), _hip.ptr(v), P, _hip.ptr(e), _hip.ptr(r), G, K, _hip.ptr(gx), _hip.ptr(gw), gx.size,
+                       _hip.ptr(d), _hip.ptr(cg), _hip.ptr(cl)))
+        return d, cg, cl
+
+    def glmm_beta_dispersion_terms(self, mean, var, e, r, gh_x, gh_w):
+        """(d (2), cross_global (2 P), cross_local (G x 2 K)) of the Beta mixed model at the precision of `set_dispersion`
+        (lrvb_glmm_beta_dispersion_terms): the first and second derivative of the data term in the log-dispersion lambda,
+        phi = e^lambda phi0, and the derivative in lambda of its gradient in the coordinates (mean, var, e, r).  The resident group
+        sums and factor are not touched."""
+        return self._glmm_dispersion_terms(self._lib.lrvb_glmm_beta_dispersion_terms, mean, var, e, r, gh_x, gh_w)
+
+    def glmm_negbin_dispersion_terms(self, mean, var, e, r, gh_x, gh_w):
+        """As `glmm_beta_dispersion_terms` for the NB2 model on the binomial context: the trials y + phi of `set_trials`, the offset
+        o - log phi of `set_offset` and phi itself by `set_dispersion` (lrvb_glmm_negbin_dispersion_terms)."""
+        return self._glmm_dispersion_terms(self._lib.lrvb_glmm_negbin_dispersion_terms, mean, var, e, r, gh_x, gh_w)
+
     # ---- multinomial (softmax) regression: beta is (K - 1) x n_cols, D = (K - 1) n_cols (lrvb_softmax_*) --------------------
     def softmax_set_labels(self, labels, n_classes):
         y = np.ascontiguousarray(np.asarray(labels).ravel(), dtype=np.int32)

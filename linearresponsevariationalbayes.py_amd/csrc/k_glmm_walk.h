@@ -210,7 +210,7 @@ struct BinomialLik {
 //            -log1p(-erfc(t / sqrt 2) / 2) for t >= 0.
 //   cloglog  u = e^t, r = u / expm1(u):  h1' = -r,  r' = r q with q = 1 - u - r,  q' = -u - r', and so on by the product rule.
 //            Past u = 700 (r < 1e-301) r is set to 0 and u to 700 in the polynomials, a select: u = +inf gives exact zeros, not
-//            inf / inf.  h1 = -log(-expm1(-u)).  h0 = u EXACTLY integrable: E h0 and all its derivatives are exp(rho + s / 2), one
+//            inf / inf.  h1 = -log(-expm1(-u)) up to u = log 2, -log1p(-exp(-u)) past it.  h0 = u EXACTLY integrable: E h0 and all its derivatives are exp(rho + s / 2), one
 //            exp per row as in PoissonLik and not clamped -- where it overflows the non-finite value reaches the sums and the
 //            entry refuses it.  Below t = -745 (u = 0) r is 0 / 0 and the row is refused in the same way.
 // The products with y and m - y are formed per lane ahead of the xor shuffles; the four lanes of a row share the nodes as
@@ -243,14 +243,31 @@ struct BinomialLinkLik {
     static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_off[row]; }
     static __device__ __forceinline__ int lane_row() { return (int)(threadIdx.x >> 2); }
 
+    // Probit, left tail: below t = PROBIT_CF_BELOW the sum d = t + lambda cancels to -1 / t and carries t^2 times the error of erfcx, and
+    // 1 - w and w' behind it t^4 times.  There d comes from the continued fraction sqrt(2 / pi) / erfcx(x) = sqrt 2 (x + K(x)),
+    // K = (1/2) / (x + (2/2) / (x + (3/2) / (x + ..))), x = -t / sqrt 2: d = sqrt 2 K(x) without a cancellation and lambda = d - t.
+    // PROBIT_CF_TERMS terms (5e-16 of K at x = 3.5) from the tail as one ratio cn / cd -- one division; past x = 1e8, where cd would
+    // overflow, K = 1 / (2 x) to the last bit.  The cancellations of 1 - w and of w' themselves stay.
+    static constexpr double PROBIT_CF_BELOW = -5.0;
+    static constexpr int PROBIT_CF_TERMS = 24;
+
     // h1' and h1'' at t (N = 2), or h1 .. h1'''' (N = 5), into h[5 - N ..]: h[0] is the value wherever it is asked for
     template <int N>
     static __device__ __forceinline__ void h1(double t, double* h)
     {
         if constexpr (LINK == GLMM_LINK_PROBIT) {
             const double ex = erfcx(-0.7071067811865476 * t);
-            const double lam = 0.7978845608028654 / ex;                  // sqrt(2 / pi) / erfcx(-t / sqrt 2)
-            const double d = t + lam, w = lam * d;
+            double lam = 0.7978845608028654 / ex;                        // sqrt(2 / pi) / erfcx(-t / sqrt 2)
+            double d = t + lam;
+            if (t < PROBIT_CF_BELOW) {                                   // d = sqrt 2 K(x) from the continued fraction, lambda = d - t (above)
+                const double x0 = -0.7071067811865476 * t, x = fmin(x0, 1e8);
+                double cn = 0.5 * PROBIT_CF_TERMS, cd = x;
+#pragma unroll
+                for (int k = PROBIT_CF_TERMS - 1; k >= 1; --k) { const double nn = (0.5 * k) * cd; cd = x * cd + cn; cn = nn; }
+                d = 1.4142135623730951 * (x0 > 1e8 ? 0.5 / x0 : cn / cd);
+                lam = d - t;
+            }
+            const double w = lam * d;
             h[1] = -lam; h[2] = w;
             if constexpr (N == 5) {
                 const double w1 = lam * (1.0 - w) - w * d;
@@ -266,7 +283,8 @@ struct BinomialLinkLik {
             if constexpr (N == 5) {
                 const double q1 = -uc - r1, r2 = r1 * q + r * q1, q2 = -uc - r2;
                 h[3] = -r2; h[4] = -(r2 * q + 2.0 * r1 * q1 + r * q2);
-                h[0] = -log(-expm1(-u));
+                // past u = log 2 through log1p(-e^-u): 1 - e^-u rounds to 1 from u = 37 on and -log of it would lose e^-u whole
+                h[0] = u > 0.6931471805599453 ? -log1p(-exp(-u)) : -log(-expm1(-u));
             }
         }
     }

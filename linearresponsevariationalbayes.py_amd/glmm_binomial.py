@@ -43,6 +43,8 @@ def _row_vector(a, n, what):
 
 
 LINKS = {'logit': 0, 'probit': 1, 'cloglog': 2}                         # LRVB_LINK_* of the C ABI
+PROBIT_CF_BELOW, PROBIT_CF_TERMS = -5.0, 24                           # BinomialLinkLik<PROBIT>::h1: the continued fraction of t + lambda
+LOG2 = 0.6931471805599453                                               # where the cloglog value changes form (BinomialLinkLik::h1)
 
 
 def _h1_probit(t, order):
@@ -51,6 +53,18 @@ def _h1_probit(t, order):
         ex = erfcx(-t / np.sqrt(2.0))
         lam = np.sqrt(2.0 / np.pi) / ex
         d = t + lam
+        # Below t = PROBIT_CF_BELOW, d = t + lambda cancels to -1 / t and carries t^2 times the error of erfcx.  There it comes from the
+        # continued fraction sqrt(2 / pi) / erfcx(x) = sqrt 2 (x + K(x)), K = (1/2) / (x + (2/2) / (x + (3/2) / (x + ..))), x = -t / sqrt 2:
+        # d = sqrt 2 K(x) with no cancellation, lambda = d - t.  PROBIT_CF_TERMS terms (5e-16 of K at x = 3.5), evaluated from the tail
+        # as one ratio N / D; past x = 1e8, where D would overflow, K = 1 / (2 x) to the last bit.
+        far = t < PROBIT_CF_BELOW
+        x0 = -0.7071067811865476 * t
+        x = np.where(far, np.minimum(x0, 1e8), 6.0)
+        N, D = np.full_like(x, 0.5 * PROBIT_CF_TERMS), x.copy()
+        for k in range(PROBIT_CF_TERMS - 1, 0, -1):
+            N, D = 0.5 * k * D, x * D + N
+        d = np.where(far, 1.4142135623730951 * np.where(x0 > 1e8, 0.5 / np.where(far, x0, 1.0), N / D), d)
+        lam = np.where(far, d - t, lam)
         w = lam * d
         w1 = lam * (1.0 - w) - w * d
         h = [np.where(t < 0.0, 0.5 * t * t - np.log(0.5 * ex), -np.log1p(-0.5 * erfc(np.maximum(t, 0.0) / np.sqrt(2.0)))),
@@ -59,7 +73,8 @@ def _h1_probit(t, order):
 
 
 def _h1_cloglog(t, order):
-    """-log(1 - exp(-u)), u = e^t, and its derivatives in t through r = u / expm1(u): r' = r (1 - u - r)."""
+    """-log(1 - exp(-u)), u = e^t, and its derivatives in t through r = u / expm1(u): r' = r (1 - u - r).  The value is
+    -log(-expm1(-u)) up to u = log 2 and -log1p(-exp(-u)) past it: 1 - e^-u rounds to 1 from u = 37 on, and -log of it loses e^-u."""
     with np.errstate(over='ignore', divide='ignore', invalid='ignore'):
         u = np.exp(t)
         uc = np.minimum(u, 700.0)
@@ -69,7 +84,8 @@ def _h1_cloglog(t, order):
         q1 = -uc - r1
         r2 = r1 * q + r * q1
         q2 = -uc - r2
-        h = [-np.log(-np.expm1(-u)), -r, -r1, -r2, -(r2 * q + 2.0 * r1 * q1 + r * q2)]
+        h = [np.where(u > LOG2, -np.log1p(-np.exp(-u)), -np.log(-np.expm1(-np.minimum(u, LOG2)))), -r, -r1, -r2,
+             -(r2 * q + 2.0 * r1 * q1 + r * q2)]
     return h[:order + 1]
 
 

@@ -764,6 +764,44 @@ int lrvb_glmm_negbin_dispersion_terms(lrvb_ctx* ctx, const double* mean, const d
                                       int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes, double* d_out,
                                       double* cross_global_out, double* cross_local_out);
 
+/* ---- Gamma mixed model with a log link and K <= 4 independent random effects per group -------------------
+ *   y_n > 0,  y_n ~ Gamma(shape phi_n, mean mu_n),  mu_n = exp(t_n),  t_n = o_n + x_n . beta + z_n . u_g(n):
+ * positive continuous responses with a KNOWN per-row shape phi_n > 0 (lrvb_set_dispersion) and the RAW offset of lrvb_set_offset.
+ * The context's y (LRVB_SLOT_Y) holds log y_n.  With h(t) = phi (y e^{-t} + t) (phi log phi - lgamma(phi) + (phi - 1) log y is
+ * dropped), t ~ N(rho_n, s_n) with rho_n = offset_n + x_n . mean + z_n . e_g(n) and s_n as in lrvb_glmm_slopes_terms, the
+ * expectation is closed form, g = phi exp((log y - rho) + s / 2), ONE exp per row and no quadrature nodes:
+ *   value = sum_n w_n (g + phi rho),  a1 = w (phi - g),  a2 = w g / 2,  c11 = w g,  c12 = -w g / 2,  c22 = w g / 4
+ * in the two-row layout, the scratch sizes and the summation order of the Poisson entries (the sign of c12 rides on the factor of
+ * its sums).  The kernel does not clamp: where g overflows for some row the value is not finite after the reduction:
+ * LRVB_ERR_INVALID, the other outputs are then unspecified and no sums stay resident.  g underflowing to 0 is a legitimate point
+ * (the row's term is phi rho).  Arguments, outputs, the column layout of group_sums_out, want_border, the fixed summation order
+ * (two calls at one point are bitwise equal) and the reduce-hook contract are those of lrvb_glmm_poisson_terms; the group sums
+ * stay resident for lrvb_glmm_slopes_schur, lrvb_glmm_slopes_solve_forward, lrvb_glmm_slopes_solve_back and
+ * lrvb_glmm_slopes_group_cov.  The entries read neither lrvb_set_trials nor lrvb_set_link.  No dispersion set, or one of another
+ * length than n_obs: LRVB_ERR_STATE.  The other errors are those of lrvb_glmm_poisson_terms.  y is not validated here (the Python
+ * layer asks for finite y > 0).  The fitted mean E e^t = exp(rho + s / 2) does not depend on phi: lrvb_glmm_poisson_predict is
+ * the predict entry of this model (it reads the offset and never y).                                                            */
+int lrvb_glmm_gamma_terms(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                          int64_t G, int64_t K, double* value_out, double* grad_global_out, double* H_blocks_out,
+                          double* group_sums_out, int32_t want_border);
+/* Streamed weight influence of that model: lrvb_glmm_poisson_obs_influence with, per unit weight, a1' = phi - g (there is no
+ * "- y": the response sits inside g) and a2' = g / 2.  Operand layouts, the row window, the output, "a window equals the same
+ * rows of the full result bitwise" and "no reduce-hook call" as there; errors as lrvb_glmm_gamma_terms, and n0 > n1 or
+ * n1 > n_obs: LRVB_ERR_INVALID.                                                                                                 */
+int lrvb_glmm_gamma_obs_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                                  int64_t G, int64_t K, const double* A_global, const double* A_local, int64_t Q, int64_t n0,
+                                  int64_t n1, double* out);
+/* Group influence of that model, as lrvb_glmm_poisson_group_influence.  Errors as lrvb_glmm_gamma_obs_influence.                */
+int lrvb_glmm_gamma_group_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e,
+                                    const double* r, int64_t G, int64_t K, const double* A_global, const double* A_local, int64_t Q,
+                                    double* out);
+/* The derivative in the log-dispersion lambda (phi_n = e^lambda phi0_n) of that model, as lrvb_glmm_beta_dispersion_terms without
+ * the nodes.  h is linear in phi, so h_l = h_ll = h: d_out[0] = d_out[1] = the data term of lrvb_glmm_gamma_terms and the cross
+ * terms are its gradient, here formed by a kernel of their own.  Reads the state of lrvb_glmm_gamma_terms; writes NEITHER the
+ * resident group sums NOR the factor NOR the group covariance and drops none of them.  Errors as lrvb_glmm_gamma_terms.         */
+int lrvb_glmm_gamma_dispersion_terms(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                                     int64_t G, int64_t K, double* d_out, double* cross_global_out, double* cross_local_out);
+
 /* ---- group blocks of H^-1, fitted values and predictions with their linear-response variance ------------
  * For every mixed model with K <= 4 effects per group.  After a successful lrvb_glmm_slopes_schur (the factor L_g, U_g resident)
  * and a factored free Schur complement S on the caller's side, with

@@ -55,6 +55,7 @@ from .glmm_corr import LogisticGLMMCorrObjective, PoissonGLMMCorrObjective
 from .glmm_hurdle import (TruncatedPoissonGLMMObjective, HurdlePoissonGLMM, TruncatedNegBinomialGLMMObjective,
                           HurdleNegBinomialGLMM)
 from .glmm_beta import BetaGLMMObjective
+from .glmm_gamma import GammaGLMMObjective, HurdleGammaGLMM
 from .torch_closure import TorchObjective
 from . import regression as regression_utils
 from . import packing as ProjectionParams

@@ -126,6 +126,10 @@ _SIGNATURES = {
     'lrvb_glmm_beta_group_influence': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, c_i64, _VP],
     'lrvb_glmm_beta_dispersion_terms': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, _VP],
     'lrvb_glmm_negbin_dispersion_terms': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, _VP],
+    'lrvb_glmm_gamma_terms': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, _VP, _VP, ctypes.c_int32],
+    'lrvb_glmm_gamma_obs_influence': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, c_i64, c_i64, c_i64, _VP],
+    'lrvb_glmm_gamma_group_influence': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, c_i64, _VP],
+    'lrvb_glmm_gamma_dispersion_terms': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, _VP],
     'lrvb_softmax_set_labels': [_VP, _VP, c_i64, ctypes.c_int32],
     'lrvb_softmax_terms': [_VP, _VP, c_i64, c_i64, _VP, _VP, _VP, c_i64],
     'lrvb_softmax_hvp': [_VP, _VP, c_i64, c_i64, _VP, _VP],

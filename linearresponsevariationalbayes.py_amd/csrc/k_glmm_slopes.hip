@@ -6,6 +6,7 @@
 //   zero-truncated Poisson:  y_n >= 1,  P(y_n) = Poisson(y_n; lambda_n) / (1 - exp(-lambda_n)),  lambda_n as the Poisson one
 //   zero-truncated NB2:  y_n >= 1,  P(y_n) = NB2(y_n; mu_n, phi_n) / (1 - (1 + mu_n / phi_n)^-phi_n),  mu_n as lambda_n
 //   Beta:  0 < y_n < 1,  y_n ~ Beta(mu_n phi_n, (1 - mu_n) phi_n),  mu_n = sigma(o_n + x_n . beta + z_n . u_g(n))
+//   Gamma:  y_n > 0,  y_n ~ Gamma(shape phi_n, mean exp(o_n + x_n . beta + z_n . u_g(n)))
 // Per observation rho_n = x_n . m + z_n . e_g, s_n = (x_n o x_n) . v + (z_n o z_n) . r_g and five coefficients a1, a2, c11, c12, c22.
 // Every kernel that walks the rows is written ONCE, as a template over a likelihood policy (k_glmm_walk.h, DESIGN.md sections 27 and
 // 31): LogisticLik (the quadrature k_glmm.hip runs too; with K = 1 and z = 1 this is that model) and PoissonLik
@@ -208,6 +209,7 @@ static int gs_with_lik(const GlmmLik& lik, F&& f) {
     if (lik.kind == GLMM_ZTPOISSON) return f(TruncPoissonLik(), TruncPoissonLik::Args{q, lik.off});
     if (lik.kind == GLMM_ZTNEGBIN) return f(TruncNegBinLik(), TruncNegBinLik::Args{q, lik.off, lik.trials, lik.y});
     if (lik.kind == GLMM_BETA) return f(BetaLik(), BetaLik::Args{q, lik.off, lik.trials, lik.y});
+    if (lik.kind == GLMM_GAMMA) return f(GammaLik(), GammaLik::Args{lik.off, lik.trials, lik.y});
     if (lik.kind == GLMM_BINOMIAL && lik.link == GLMM_LINK_PROBIT)
         return f(BinomialLinkLik<GLMM_LINK_PROBIT>(), BinomialLinkLik<GLMM_LINK_PROBIT>::Args{q, lik.off, lik.trials, lik.y});
     if (lik.kind == GLMM_BINOMIAL && lik.link == GLMM_LINK_CLOGLOG)
@@ -351,16 +353,18 @@ static int gs_launch_disp(lrvb_ctx* c, int Kz, typename DLik::Args la, const dou
     return LRVB_OK;
 }
 
-// `lik` is the likelihood of the family's terms entry (GLMM_BETA, or GLMM_BINOMIAL with the logit link: NB2), `disp` the resident
+// `lik` is the likelihood of the family's terms entry (GLMM_BETA, GLMM_GAMMA, or GLMM_BINOMIAL with the logit link: NB2), `disp` the resident
 // dispersion; coef 2 x NP (zeroed by the caller), gsum G x 2 K (zeroed by the caller), part 2 x 2 K and vpart 2 doubles per tile.
 int launch_glmm_disp_rows(lrvb_ctx* c, const GlmmLik& lik, const double* disp, int Kz, const double* m, const double* vb, const double* eg,
                           const double* rg, double* coef, i64 NP, double* gsum, double* part, double* vpart) {
     const LogisticLik::Args q{lik.gx, lik.gw, lik.n_nodes};
     if (lik.kind == GLMM_BETA)
         return gs_launch_disp<BetaDispLik>(c, Kz, BetaDispLik::Args{q, lik.off, disp, lik.y}, m, vb, eg, rg, coef, NP, gsum, part, vpart);
+    if (lik.kind == GLMM_GAMMA)
+        return gs_launch_disp<GammaDispLik>(c, Kz, GammaDispLik::Args{lik.off, disp, lik.y}, m, vb, eg, rg, coef, NP, gsum, part, vpart);
     if (lik.kind == GLMM_BINOMIAL && lik.link == GLMM_LINK_LOGIT)
         return gs_launch_disp<NegBinDispLik>(c, Kz, NegBinDispLik::Args{q, lik.off, lik.trials, disp, lik.y}, m, vb, eg, rg, coef, NP, gsum, part, vpart);
-    LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the dispersion derivative is that of the Beta and the negative binomial mixed model");
+    LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the dispersion derivative is that of the Beta, the Gamma and the negative binomial mixed model");
 }
 
 // A = L L^T of one local block from its upper triangle a (row-major), L row-major into Ls; false where a pivot is not positive
@@ -829,6 +833,17 @@ void glmm_beta_infl_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* __re
     gsi_infl_rows<BetaLik>(n0, R, P, Kz, X, Z, y, gid, m, vb, eg, rg, {{gx, gw, nq}, off, disp, y}, Ag, Al, Q, out);
 }
 
+// The Gamma model: the arguments of the Beta entry without the nodes; y holds log(y).
+__global__ __launch_bounds__(256)
+void glmm_gamma_infl_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* __restrict__ X, const double* __restrict__ Z,
+                                 const double* __restrict__ off, const double* __restrict__ disp, const double* __restrict__ y,
+                                 const int* __restrict__ gid, const double* __restrict__ m, const double* __restrict__ vb,
+                                 const double* __restrict__ eg, const double* __restrict__ rg, const double* __restrict__ Ag,
+                                 const double* __restrict__ Al, int Q, double* __restrict__ out)
+{
+    gsi_infl_rows<GammaLik>(n0, R, P, Kz, X, Z, y, gid, m, vb, eg, rg, {off, disp, y}, Ag, Al, Q, out);
+}
+
 template <class Lik>
 static int gs_launch_infl_rows(lrvb_ctx* c, int Kz, const double* Z, typename Lik::Args la, i64 n0, i64 n1, const int* gid, const double* m,
                                const double* vb, const double* eg, const double* rg, const double* Ag, const double* Al, i64 Q,
@@ -854,6 +869,9 @@ static int gs_launch_infl_rows(lrvb_ctx* c, int Kz, const double* Z, typename Li
         hipLaunchKernelGGL(glmm_beta_infl_rows_kernel, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
                            (const double*)la.off, (const double*)la.disp, (const double*)la.y, gid, m, vb, eg, rg, la.q.gx, la.q.gw, la.q.nq,
                            Ag, Al, (int)Q, out);
+    else if constexpr (std::is_same<Lik, GammaLik>::value)
+        hipLaunchKernelGGL(glmm_gamma_infl_rows_kernel, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
+                           (const double*)la.off, (const double*)la.disp, (const double*)la.y, gid, m, vb, eg, rg, Ag, Al, (int)Q, out);
     else if constexpr (gs_link_of<Lik>::value != GLMM_LINK_LOGIT)
         hipLaunchKernelGGL(glmm_link_infl_rows_kernel<gs_link_of<Lik>::value>, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz,
                            (const double*)c->X.p, Z, (const double*)la.off, (const double*)la.trials, (const double*)la.y, gid, m, vb, eg, rg,
@@ -1278,12 +1296,13 @@ int launch_glmm_slopes_predict_rows(lrvb_ctx* c, const GlmmLik& lik, int Kz, con
                                     const int* gid, const double* m, const double* vb, const double* eg, const double* rg,
                                     const double* Sbb, const double* gcov, double* out, i64 ldo) {
     if (c->P > 64 || Kz < 1 || Kz > 4 || !X || !Z) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "mixed-model prediction: P <= 64, 1 <= K <= 4, a group design");
-    if (lik.kind != GLMM_POISSON && (lik.n_nodes < 1 || lik.n_nodes > 128)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 128 quadrature nodes");
+    const bool closed_form = lik.kind == GLMM_POISSON || lik.kind == GLMM_GAMMA;     // no nodes; E e^t = exp(rho + s / 2) for both
+    if (!closed_form && (lik.n_nodes < 1 || lik.n_nodes > 128)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 128 quadrature nodes");
     const i64 R = n1 - n0;
     if (R <= 0) return LRVB_OK;
     const dim3 grid(glmm_grid(R)), block(256);
     const int P = (int)c->P;
-    if (lik.kind == GLMM_POISSON)
+    if (closed_form)
         hipLaunchKernelGGL(glmm_poisson_predict_rows_kernel, grid, block, 0, c->stream, n0, R, P, Kz, X, Z, lik.off, gid, m, vb, eg, rg, Sbb,
                            gcov, out, ldo);
     else if (lik.kind == GLMM_ZTPOISSON)
@@ -1429,6 +1448,22 @@ __global__ void glmm_poisson_scale_blocks_kernel(i64 PP, double* __restrict__ Hb
     if (i >= PP) return;
     Hb[PP + i] *= 0.5;
     Hb[2 * PP + i] *= 0.25;
+}
+
+// The Gamma model's blocks likewise, with c12 = -g / 2: the cross block takes the sign with its factor (exact).
+__global__ void glmm_gamma_scale_blocks_kernel(i64 PP, double* __restrict__ Hb)
+{
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= PP) return;
+    Hb[PP + i] *= -0.5;
+    Hb[2 * PP + i] *= 0.25;
+}
+
+int launch_glmm_gamma_scale_blocks(lrvb_ctx* c, double* Hb) {
+    const i64 PP = c->P * c->P;
+    hipLaunchKernelGGL(glmm_gamma_scale_blocks_kernel, dim3((unsigned)((PP + 255) / 256)), dim3(256), 0, c->stream, PP, Hb);
+    HIP_TRY(hipGetLastError());
+    return LRVB_OK;
 }
 
 int launch_glmm_poisson_scale_blocks(lrvb_ctx* c, double* Hb) {

@@ -809,6 +809,70 @@ struct BetaLik {
     }
 };
 
+// Gamma with a log link, a per-row shape phi and a per-row offset: y > 0, mean mu = e^t, the row's term,
+// constants dropped,
+//   h(t) = phi (y e^{-t} + t).
+// The second likelihood after PoissonLik whose expectation under t ~ N(rho, s) is closed form: E h = g + phi rho with
+//   g = phi exp((log y - rho) + s / 2),
+// rho including the offset: ONE exp per row, no nodes.  The staged y is log y, so that g is one exp of a difference: a tiny or a huge
+// y never overflows a product that the exponent would not.  Every derivative of E h is a multiple of g:
+//   a1 = phi - g,  a2 = g / 2,  c11 = g,  c12 = -g / 2,  c22 = g / 4      (times w),
+// PoissonLik's two coefficient rows [a1 | g] with the SIGN of c12 carried by cf_factor(3) = -0.5 (the host's two-row branch puts
+// the same sign on the cross block).  Not canonical in the walk's sense (y sits inside g): MINUS_Y is false, coefs ignores the
+// walk's yi and infl returns e1 = phi - g whole.  No clamp: where g overflows the non-finite value reaches the sums and the entry
+// refuses the point, as for PoissonLik; where g underflows to 0 the row's term is phi rho, a legitimate point.  The response mean
+// E e^t = exp(rho + s / 2) does not depend on phi: the Poisson predict walk serves this model, and `mean` is PoissonLik's formula.
+// Offsets, phi and log y are staged as BetaLik stages offset, precision and logit y.  No shuffles, no atomics.
+struct GammaLik {
+    struct Args { const double* __restrict__ off; const double* __restrict__ disp; const double* __restrict__ y; };   // off may be nullptr; y holds log(y)
+    struct Lds { double s_off[GLMM_T], s_phi[GLMM_T], s_y[GLMM_T]; };
+    struct Moments {};
+    static constexpr const char* LIMITS = "Gamma mixed model: P <= 64, 1 <= K <= 4";
+    static bool args_ok(const Args& a) { return a.disp != nullptr && a.y != nullptr; }
+    static constexpr int NCF = 2, NB = 2, DK = 8;                        // coefficient rows [a1 | g]
+    static constexpr bool HAS_FACTOR = true;
+    static constexpr bool MINUS_Y = false;
+    static __device__ __forceinline__ int cf_row(int kind) { return kind == 0 ? 0 : 1; }
+    static __device__ __forceinline__ double cf_factor(int kind) { return kind == 4 ? 0.25 : (kind == 3 ? -0.5 : (kind == 1 ? 0.5 : 1.0)); }
+    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return (b & 1) * Kz + k; }
+    static __device__ __forceinline__ int d_stride(int Kz) { return 2 * Kz; }
+
+    static __device__ __forceinline__ void init(Lds&, const Args&, int) {}
+    static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
+    {
+        L.s_off[t] = (a.off && live) ? a.off[src] : 0.0;
+        L.s_phi[t] = live ? a.disp[src] : 1.0;
+        L.s_y[t] = live ? a.y[src] : 0.0;
+    }
+    static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_off[row]; }
+    static __device__ __forceinline__ int lane_row() { return (int)(threadIdx.x >> 2); }
+    // g = phi exp((log y - rho) + s / 2) at rho INCLUDING the offset
+    static __device__ __forceinline__ double g_of(double phi, double ly, double rho, double s) { return phi * exp((ly - rho) + 0.5 * s); }
+    // e1 = a1' = phi - g whole and e2 = E h'' = g, on all four lanes of a row
+    static __device__ __forceinline__ void infl(const Lds& L, const Args&, double o, bool live, int, double rho, double s, double& e1,
+                                                double& e2)
+    {
+        const int row = lane_row();
+        const double phi = L.s_phi[row];
+        const double g = live ? g_of(phi, L.s_y[row], rho + o, s) : 0.0;
+        e1 = live ? phi - g : 0.0; e2 = g;
+    }
+    // the response mean E e^t = exp(rho + s / 2), whatever phi
+    static __device__ __forceinline__ void mean(const Lds&, const Args&, double o, bool live, int, double rho, double s, double& mu)
+    {
+        mu = live ? exp((rho + o) + 0.5 * s) : 0.0;
+    }
+    static __device__ __forceinline__ Moments moments(const Lds&, const Args&, bool, int, double, double) { return {}; }
+    static __device__ __forceinline__ double coefs(const Lds& L, int row, const Moments&, double wi, double, double rho, double s, double* k)
+    {
+        rho += L.s_off[row];
+        const double phi = L.s_phi[row];
+        const double g = g_of(phi, L.s_y[row], rho, s);
+        k[0] = wi * (phi - g); k[1] = wi * g;
+        return wi * (g + phi * rho);
+    }
+};
+
 // ---- the dispersion-derivative policies ----------------------------------------------------------------------
 // The dispersion of the Beta and the NB2 model as phi_n = e^lambda phi0_n with ONE scalar lambda: every derivative below is in
 // lambda at fixed t, d/d lambda = phi d/d phi.  A policy of this kind serves glmm_disp_rows_kernel (k_glmm_slopes.hip) and supplies
@@ -921,6 +985,31 @@ struct NegBinDispLik {
         }
         if (!live) return {0.0, 0.0, 0.0, 0.0};
         return {(phi * v - mt * e1) + yt, phi * e1 - mt * e2, phi * e2 - mt * e3, phi * (v - 2.0 * e1) + mt * e2};
+    }
+};
+
+// Gamma: h = phi (y e^{-t} + t) is LINEAR in phi, so that in lambda = log(phi / phi0)
+//   h_l = h_ll = h,   d_t h_l = h',   d_t^2 h_l = h'':   (E h, phi - g, g, E h) with GammaLik's g and staging.
+// The derivative of the data term in lambda is the data term, the cross Hessian its gradient -- formed here by a kernel of its own.
+struct GammaDispLik {
+    typedef GammaLik::Args Args;
+    typedef GammaLik::Lds Lds;
+    static constexpr const char* LIMITS = GammaLik::LIMITS;
+    static bool args_ok(const Args& a) { return GammaLik::args_ok(a); }
+    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { GammaLik::init(L, a, tid); }
+    static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src) { GammaLik::stage_row(L, a, t, live, src); }
+    static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return GammaLik::row_shift(L, row); }
+    static __device__ __forceinline__ int lane_row() { return GammaLik::lane_row(); }
+
+    static __device__ __forceinline__ DispMoments dmoments(const Lds& L, const Args&, bool live, int, double rho, double s)
+    {
+        if (!live) return {0.0, 0.0, 0.0, 0.0};
+        const int row = lane_row();
+        const double phi = L.s_phi[row];
+        rho += L.s_off[row];
+        const double g = GammaLik::g_of(phi, L.s_y[row], rho, s);
+        const double eh = g + phi * rho;
+        return {eh, phi - g, g, eh};
     }
 };
 

@@ -2606,10 +2606,14 @@ static GlmmLik glmms_binomial(const lrvb_ctx* c, const double* gh_x, const doubl
 static GlmmLik glmms_ztpoisson(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_ZTPOISSON, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, LRVB_LINK_LOGIT, nullptr}; }
 static GlmmLik glmms_ztnegbin(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_ZTNEGBIN, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, LRVB_LINK_LOGIT, nullptr}; }
 static GlmmLik glmms_beta(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_BETA, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, LRVB_LINK_LOGIT, nullptr}; }
+static GlmmLik glmms_gamma() { return GlmmLik{GLMM_GAMMA, nullptr, nullptr, 0, nullptr, nullptr, false, LRVB_LINK_LOGIT, nullptr}; }
+// The likelihoods whose expectation is closed form: one exp per row, no nodes to check, upload or make room for.
+static bool glmms_closed_form(const GlmmLik& lik) { return lik.kind == GLMM_POISSON || lik.kind == GLMM_GAMMA; }
 static const char* glmms_name(const GlmmLik& lik) {
     if (lik.kind == GLMM_ZTPOISSON) return "zero-truncated Poisson";
     if (lik.kind == GLMM_ZTNEGBIN) return "zero-truncated negative binomial";
     if (lik.kind == GLMM_BETA) return "Beta";
+    if (lik.kind == GLMM_GAMMA) return "Gamma";
     return lik.kind == GLMM_POISSON ? "Poisson" : (lik.kind == GLMM_BINOMIAL ? "binomial" : "logistic");
 }
 
@@ -2617,9 +2621,9 @@ static const char* glmms_name(const GlmmLik& lik) {
 // The unit design has no group design to check, and its length message names "e / r" as the intercept entries always have.
 static int glmms_check(lrvb_ctx* c, const GlmmLik& lik, const double* mean, const double* var, int64_t P_in, const double* e_loc,
                        const double* r_loc, int64_t G_in, int64_t K, bool other_null) {
-    const bool poisson = lik.kind == GLMM_POISSON;
-    if (!mean || !var || !e_loc || !r_loc || (!poisson && (!lik.gx || !lik.gw)) || other_null) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
-    if (!poisson && (lik.n_nodes < 1 || lik.n_nodes > 128)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 128 quadrature nodes");
+    const bool closed_form = glmms_closed_form(lik);
+    if (!mean || !var || !e_loc || !r_loc || (!closed_form && (!lik.gx || !lik.gw)) || other_null) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    if (!closed_form && (lik.n_nodes < 1 || lik.n_nodes > 128)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 128 quadrature nodes");
     if (c->P > 64)
         LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the %s mixed model needs P <= 64 (got %lld)", glmms_name(lik), (long long)c->P);
     if (K < 1 || K > 4) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "1 to 4 random effects per group (got %lld)", (long long)K);
@@ -2633,7 +2637,7 @@ static int glmms_check(lrvb_ctx* c, const GlmmLik& lik, const double* mean, cons
         LRVB_FAIL(LRVB_ERR_STATE, "the offset has %lld entries, the model has %lld observations", (long long)c->goff_n, (long long)c->N);
     if (lik.kind == GLMM_BINOMIAL && c->gtr_n != 0 && c->gtr_n != c->N)
         LRVB_FAIL(LRVB_ERR_STATE, "the trials have %lld entries, the model has %lld observations", (long long)c->gtr_n, (long long)c->N);
-    const bool disp = lik.kind == GLMM_ZTNEGBIN || lik.kind == GLMM_BETA;
+    const bool disp = lik.kind == GLMM_ZTNEGBIN || lik.kind == GLMM_BETA || lik.kind == GLMM_GAMMA;
     if (disp && c->gdisp_n == 0)
         LRVB_FAIL(LRVB_ERR_STATE, "no dispersion: call lrvb_set_dispersion first");
     if (disp && c->gdisp_n != c->N)
@@ -2660,19 +2664,20 @@ static int glmms_to_device(lrvb_ctx* c, GlmmLik& lik, double* g) {
     if (lik.link != LRVB_LINK_LOGIT) lik.y = c->y.p;                      // the probit and cloglog policies stage y themselves
     if (lik.kind == GLMM_ZTNEGBIN) { lik.trials = c->gdisp.p; lik.y = c->y.p; }   // phi rides in the trials slot; y is staged for y + phi
     if (lik.kind == GLMM_BETA) { lik.trials = c->gdisp.p; lik.y = c->y.p; }       // phi in the trials slot again; y holds logit(y)
-    if (lik.kind == GLMM_POISSON) return LRVB_OK;
+    if (lik.kind == GLMM_GAMMA) { lik.trials = c->gdisp.p; lik.y = c->y.p; }      // the shape phi in the trials slot; y holds log(y)
+    if (glmms_closed_form(lik)) return LRVB_OK;
     LRVB_TRY(h2d(c, g, lik.gx, (size_t)lik.n_nodes));
     LRVB_TRY(h2d(c, g + 128, lik.gw, (size_t)lik.n_nodes));
     lik.gx = g; lik.gw = g + 128;
     return LRVB_OK;
 }
 
-// The point on the device, at the head of c->work1: [nodes 256 (not Poisson) | m, v (2 up(P)) | e, r (2 up(GK))], `doubles` in
+// The point on the device, at the head of c->work1: [nodes 256 (not the closed-form likelihoods) | m, v (2 up(P)) | e, r (2 up(GK))], `doubles` in
 // all; what a body keeps behind it (`tail` doubles) starts at g + doubles.  Reserves work1, uploads the likelihood and the point.
 struct GlmmPoint { double *g, *m, *v, *e, *r; i64 doubles; };
 static int glmms_point_upload(lrvb_ctx* c, GlmmLik& lik, const double* mean, const double* var, const double* e_loc, const double* r_loc,
                               i64 P, i64 GK, size_t tail, GlmmPoint* pt) {
-    const i64 nodes = lik.kind == GLMM_POISSON ? 0 : 256;
+    const i64 nodes = glmms_closed_form(lik) ? 0 : 256;
     pt->doubles = nodes + 2 * up(P) + 2 * up(GK);
     LRVB_TRY(buf_reserve(c, c->work1, (size_t)pt->doubles + tail));
     pt->g = c->work1.p; pt->m = pt->g + nodes; pt->v = pt->m + up(P); pt->e = pt->v + up(P); pt->r = pt->e + up(GK);
@@ -2685,13 +2690,14 @@ static int glmms_point_upload(lrvb_ctx* c, GlmmLik& lik, const double* mean, con
 
 // c->glmms: [H blocks (3 P^2) | group sums (G x ncol) | gradient (2 P) | value] -- every sum over observations of the call, adjacent,
 // so that the part that was formed goes through the reduce hook in one piece.  c->work1:
-// [nodes 256 (not Poisson) | m, v (2 up(P)) | e, r (2 up(G K)) | the coefficient vectors (original order, zero past N): five,
-// a1 a2 c11 c12 c22 (5 NP), or the Poisson model's two, a1 and h (2 NP) | tile partials]
+// [nodes 256 (not Poisson or Gamma) | m, v (2 up(P)) | e, r (2 up(G K)) | the coefficient vectors (original order, zero past N): five,
+// a1 a2 c11 c12 c22 (5 NP), or the two of the Poisson and the Gamma model, a1 and h (2 NP) | tile partials]
 static int glmms_terms(lrvb_ctx* c, GlmmLik lik, const double* mean, const double* var, int64_t P_in, const double* e_loc,
                        const double* r_loc, int64_t G_in, int64_t K, double* value_out, double* grad_global_out, double* H_blocks_out,
                        double* group_sums_out, int32_t want_border) {
     LRVB_TRY(glmms_check(c, lik, mean, var, P_in, e_loc, r_loc, G_in, K, !value_out));
-    const bool poisson = lik.kind == GLMM_POISSON;
+    // `poisson`: the two-row coefficient layout [a1 | h] of the closed-form likelihoods; the Gamma model's c12 = -h / 2 differs by a sign
+    const bool poisson = glmms_closed_form(lik), gamma = lik.kind == GLMM_GAMMA;
     const i64 N = c->N, P = c->P, G = c->n_groups, ncol = glmm_slopes_ncol((int)P, (int)K), nsc = ncol - 4 * K * P;
     c->glmms_drop();
     const bool want_g = grad_global_out != nullptr, want_H = H_blocks_out != nullptr;
@@ -2724,12 +2730,15 @@ static int glmms_terms(lrvb_ctx* c, GlmmLik lik, const double* mean, const doubl
         LRVB_TRY(weighted_tn(c, c->X.p, c->X.p, P, N, c11, Hb, c->mx_A));
         LRVB_TRY(weighted_tn(c, c->X.p, X2.p, P, N, c12, Hb + P * P, c->mx_A));
         LRVB_TRY(weighted_tn(c, X2.p, X2.p, P, N, c22, Hb + 2 * P * P, c->mx_A));
-        if (poisson) LRVB_TRY(launch_glmm_poisson_scale_blocks(c, Hb));
+        if (gamma) LRVB_TRY(launch_glmm_gamma_scale_blocks(c, Hb));
+        else if (poisson) LRVB_TRY(launch_glmm_poisson_scale_blocks(c, Hb));
     }
     double* first = want_H ? Hb : gsum;
     LRVB_TRY(obs_reduce(c, first, (i64)(vred + 1 - first)));
     if (lik.unit) { c->glmms_valid = true; c->glmms_K = 0; }             // the intercept entry marks its sums HERE, ahead of the copies, as it always has
     LRVB_TRY(d2h(c, value_out, vred, 1));
+    if (gamma && !std::isfinite(*value_out))
+        LRVB_FAIL(LRVB_ERR_INVALID, "the Gamma data term is not finite at this point: exp(log y - rho + s / 2) overflows for some row (the kernel does not clamp)");
     if (poisson && !std::isfinite(*value_out))
         LRVB_FAIL(LRVB_ERR_INVALID, "the Poisson data term is not finite at this point: exp(rho + s / 2) overflows for some row (the kernel does not clamp)");
     if (lik.link == LRVB_LINK_CLOGLOG && !std::isfinite(*value_out))
@@ -2939,7 +2948,7 @@ extern "C" int lrvb_glmm_arrow_solve_back(lrvb_ctx* c, const double* x_coupled, 
 
 // ---- weight influence of every mixed model (k_glmm.hip, k_glmm_slopes.hip) --------------------------------------------------------
 // The checks of glmms_terms, in its order, then the operand.  c->work1 holds
-//   [nodes 256 (not Poisson) | m, v (2 up(P)) | e, r (2 up(G K)) | A_global (Q x 2 P) | A_local (G x 2 K x Q) | call-specific scratch]
+//   [nodes 256 (not Poisson or Gamma) | m, v (2 up(P)) | e, r (2 up(G K)) | A_global (Q x 2 P) | A_local (G x 2 K x Q) | call-specific scratch]
 struct GlmmInflBufs { GlmmPoint pt; double *Ag, *Al, *extra; };
 static int glmms_infl_setup(lrvb_ctx* c, GlmmLik& lik, const double* mean, const double* var, int64_t P_in, const double* e_loc,
                             const double* r_loc, int64_t G_in, int64_t K, const double* A_global, const double* A_local, int64_t Q,
@@ -3175,6 +3184,31 @@ extern "C" int lrvb_glmm_beta_group_influence(lrvb_ctx* c, const double* mean, c
     return glmms_group_influence(c, glmms_beta(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out);
 }
 
+// ---- Gamma mixed model with a log link: positive responses with a known shape ------------------------------
+// The shared bodies with the GammaLik policy: no nodes, the RAW offset of lrvb_set_offset and the shape of lrvb_set_dispersion; the
+// context's y holds log(y).  Neither the trials nor the link of the binomial entries is read.
+extern "C" int lrvb_glmm_gamma_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                     const double* r_loc, int64_t G_in, int64_t K, double* value_out, double* grad_global_out,
+                                     double* H_blocks_out, double* group_sums_out, int32_t want_border) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_terms(c, glmms_gamma(), mean, var, P_in, e_loc, r_loc, G_in, K, value_out, grad_global_out, H_blocks_out,
+                       group_sums_out, want_border);
+}
+
+extern "C" int lrvb_glmm_gamma_obs_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                             const double* r_loc, int64_t G_in, int64_t K, const double* A_global,
+                                             const double* A_local, int64_t Q, int64_t n0, int64_t n1, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_obs_influence(c, glmms_gamma(), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, n0, n1, out);
+}
+
+extern "C" int lrvb_glmm_gamma_group_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                               const double* r_loc, int64_t G_in, int64_t K, const double* A_global,
+                                               const double* A_local, int64_t Q, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_group_influence(c, glmms_gamma(), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out);
+}
+
 // ---- the derivative in the log-dispersion of the Beta and the NB2 mixed model (k_glmm_slopes.hip) ----------
 // The checks of the family's terms entry, in its order, then the dispersion (the binomial kind does not ask for one).  Everything
 // lives in c->work1, as the influence entries keep theirs:
@@ -3216,7 +3250,7 @@ static int glmms_dispersion_terms(lrvb_ctx* c, GlmmLik lik, const double* mean, 
     LRVB_TRY(obs_reduce(c, gsum, nres));
     LRVB_TRY(d2h(c, d_out, dred, 2));
     if (!std::isfinite(d_out[0]) || !std::isfinite(d_out[1]))
-        LRVB_FAIL(LRVB_ERR_INVALID, "the dispersion derivative of the %s data term is not finite at this point", lik.kind == GLMM_BETA ? "Beta" : "negative binomial");
+        LRVB_FAIL(LRVB_ERR_INVALID, "the dispersion derivative of the %s data term is not finite at this point", lik.kind == GLMM_BETA ? "Beta" : (lik.kind == GLMM_GAMMA ? "Gamma" : "negative binomial"));
     LRVB_TRY(d2h(c, cross_global_out, gred, (size_t)(2 * P)));
     return d2h(c, cross_local_out, gsum, (size_t)(G * K2));
 }
@@ -3227,6 +3261,13 @@ extern "C" int lrvb_glmm_beta_dispersion_terms(lrvb_ctx* c, const double* mean, 
     LRVB_TRY(ctx_bind(c));
     return glmms_dispersion_terms(c, glmms_beta(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, d_out, cross_global_out,
                                   cross_local_out);
+}
+
+extern "C" int lrvb_glmm_gamma_dispersion_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                                const double* r_loc, int64_t G_in, int64_t K, double* d_out, double* cross_global_out,
+                                                double* cross_local_out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_dispersion_terms(c, glmms_gamma(), mean, var, P_in, e_loc, r_loc, G_in, K, d_out, cross_global_out, cross_local_out);
 }
 
 extern "C" int lrvb_glmm_negbin_dispersion_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
@@ -3271,7 +3312,7 @@ extern "C" int lrvb_glmm_arrow_group_cov(lrvb_ctx* c, const double* W, const dou
 }
 
 // The predict entries: the checks of glmms_terms in its order (e and r may carry the pseudo-group: Gp = G or G + 1 rows), the
-// resident group covariance, then the rows.  c->work1: [nodes 256 (not Poisson) | m, v (2 up(P)) | e, r (2 up(Gp K)) | Sigma_bb (P P)];
+// resident group covariance, then the rows.  c->work1: [nodes 256 (not Poisson or Gamma) | m, v (2 up(P)) | e, r (2 up(Gp K)) | Sigma_bb (P P)];
 // c->cgT: [out (5 n) | new rows: x (n P) | z (n K) | offset (n) | trials (n) | groups (n int32)].
 static int glmms_predict(lrvb_ctx* c, GlmmLik lik, const double* mean, const double* var, int64_t P_in, const double* e_loc,
                          const double* r_loc, int64_t Gp, int64_t K, const double* cov_beta, int64_t n0, int64_t n1, const double* x_new,

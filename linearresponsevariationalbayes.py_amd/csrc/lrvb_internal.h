@@ -266,7 +266,8 @@ int  launch_glmm_infl_local(lrvb_ctx* c, i64 Q, const double* S, const double* A
 // K = 1, z = 1, nothing on the device): the host bodies hand the launchers Z = nullptr, and those launch the kernels of k_glmm.hip.
 enum GlmmKind { GLMM_LOGISTIC = 0, GLMM_POISSON = 1, GLMM_BINOMIAL = 2, GLMM_ZTPOISSON = 3,    // ZTPOISSON: nodes and an offset, no trials
                 GLMM_ZTNEGBIN = 4,     // zero-truncated NB2: nodes, the shifted offset, the dispersion phi in `trials`, and `y`
-                GLMM_BETA = 5 };       // Beta: nodes, the raw offset, the precision phi in `trials`, and logit(y) in `y`
+                GLMM_BETA = 5,         // Beta: nodes, the raw offset, the precision phi in `trials`, and logit(y) in `y`
+                GLMM_GAMMA = 6 };      // Gamma, log link: NO nodes, the raw offset, the shape phi in `trials`, and log(y) in `y`
 // `link` (binomial only, LRVB_LINK_*; 0 = logit: BinomialLik) picks the probit or cloglog policy of DESIGN.md section 35, and `y`
 // is the response those two stage themselves (the host bodies fill it in with the offset and the trials).
 struct GlmmLik { GlmmKind kind; const double* gx; const double* gw; int n_nodes; const double* off; const double* trials; bool unit;
@@ -283,6 +284,7 @@ int  launch_glmm_disp_rows(lrvb_ctx* c, const GlmmLik& lik /* Beta, or binomial 
                            double* gsum /* G x 2 K, zeroed by the caller */, double* part /* 2 (2 K) doubles per tile of glmm_num_tiles */,
                            double* vpart /* 2 per tile */);
 int  launch_glmm_poisson_scale_blocks(lrvb_ctx* c, double* Hb /* 3 x P x P, all formed with h: blocks 1, 2 times 1/2, 1/4 */);
+int  launch_glmm_gamma_scale_blocks(lrvb_ctx* c, double* Hb /* 3 x P x P, all formed with g: blocks 1, 2 times -1/2, 1/4 */);
 int  launch_glmm_slopes_schur_rows(lrvb_ctx* c, int K, const double* gsum, const double* loc /* G x K (2 K + 1) */,
                                    const double* scale /* G x 2 K */, const double* closed /* G x 2 K x 3 */,
                                    double* U /* 2 K G x ldu */, int ldu, int* bad);

@@ -340,8 +340,7 @@ class _HurdleGLMM:
         x = _hip.as_f64(x)
         n = x.shape[0]
         y = _hip.as_f64(y).ravel()
-        if y.size != n or not np.all(np.isfinite(y)) or np.any(y < 0.0) or np.any((y > 0.0) & (y < 1.0)):
-            raise ValueError('y must hold {} finite counts: 0, or >= 1'.format(n))
+        self._check_y(y, n)
         z = np.ones((n, 1)) if z is None else _hip.as_f64(z)
         groups = np.asarray(groups).ravel()
         if offset is not None:
@@ -359,6 +358,11 @@ class _HurdleGLMM:
                                           weights=w, link=zero_link, **kw)
         self.count = self._make_count(par_count, x[pos], y[pos], z[pos], groups[pos],
                                       dict(kw, offset=None if offset is None else offset[pos], weights=None if w is None else w[pos]))
+
+    def _check_y(self, y, n):
+        """The responses of the composite (a subclass with a continuous positive part accepts what lies between 0 and 1)."""
+        if y.size != n or not np.all(np.isfinite(y)) or np.any(y < 0.0) or np.any((y > 0.0) & (y < 1.0)):
+            raise ValueError('y must hold {} finite counts: 0, or >= 1'.format(n))
 
     def value(self, x_zero, x_count, is_free=True):
         """The sum of the two parts' values: -ELBO of the hurdle model up to `log_norm_const()`."""

@@ -663,7 +663,7 @@ class DeviceContext(object):
     # ---- zero-truncated NB2 mixed model (lrvb_glmm_ztnegbin_*): the (shifted) offset of `set_offset`, the dispersion of `set_dispersion` ----
     def set_dispersion(self, dispersion):
         """The per-row dispersion phi > 0 of the zero-truncated negative binomial mixed model, or None to clear it
-        (lrvb_set_dispersion) -- and the precision of the Beta one.  Only the `glmm_ztnegbin_*` and `glmm_beta_*` entries read it; the resident group sums are dropped."""
+        (lrvb_set_dispersion) -- and the precision of the Beta one.  Only the `glmm_ztnegbin_*`, `glmm_beta_*` and `glmm_gamma_*` entries read it; the resident group sums are dropped."""
         if dispersion is None:
             self._check(self._lib.lrvb_set_dispersion(self._h, None, 0))
             return
@@ -706,7 +706,7 @@ class DeviceContext(object):
         return self._glmm_group_influence(self._lib.lrvb_glmm_beta_group_influence, True, True, mean, var, e, r, gh_x, gh_w, A)
 
     # ---- the derivative in the log-dispersion of the Beta and the NB2 mixed model (lrvb_glmm_*_dispersion_terms) ----------------
-    def _glmm_dispersion_terms(self, fn, mean, var, e, r, gh_x, gh_w):
+    def _glmm_dispersion_terms(self, fn, mean, var, e, r, gh_x, gh_w, nodes=True):
         m, v = _hip.as_f64(mean).ravel(), _hip.as_f64(var).ravel()
         e, r = _hip.as_f64(e), _hip.as_f64(r)
         gx, gw = _hip.as_f64(gh_x).ravel(), _hip.as_f64(gh_w).ravel()
@@ -715,8 +715,8 @@ class DeviceContext(object):
             raise ValueError('expected mean and var of length {}, e and r of one shape G x K and as many weights as nodes'.format(P))
         G, K = e.shape
         d, cg, cl = np.empty(2), np.empty(2 * P), np.empty((G, 2 * max(K, 0)))
-        self._check(fn(self._h, _hip.ptr(m), _hip.ptr(v), P, _hip.ptr(e), _hip.ptr(r), G, K, _hip.ptr(gx), _hip.ptr(gw), gx.size,
-                       _hip.ptr(d), _hip.ptr(cg), _hip.ptr(cl)))
+        quad = [_hip.ptr(gx), _hip.ptr(gw), gx.size] if nodes else []
+        self._check(fn(self._h, _hip.ptr(m), _hip.ptr(v), P, _hip.ptr(e), _hip.ptr(r), G, K, *quad, _hip.ptr(d), _hip.ptr(cg), _hip.ptr(cl)))
         return d, cg, cl
 
     def glmm_beta_dispersion_terms(self, mean, var, e, r, gh_x, gh_w):
@@ -730,6 +730,27 @@ class DeviceContext(object):
         """As `glmm_beta_dispersion_terms` for the NB2 model on the binomial context: the trials y + phi of `set_trials`, the offset
         o - log phi of `set_offset` and phi itself by `set_dispersion` (lrvb_glmm_negbin_dispersion_terms)."""
         return self._glmm_dispersion_terms(self._lib.lrvb_glmm_negbin_dispersion_terms, mean, var, e, r, gh_x, gh_w)
+
+    # ---- Gamma mixed model, log link (lrvb_glmm_gamma_*): the raw offset of `set_offset`, the shape of `set_dispersion`, log(y) as y; no quadrature ----
+    def glmm_gamma_terms(self, mean, var, e, r, want_grad=True, want_hess=True, want_border=True):
+        """Data term of the Gamma mixed model with K effects per group, the offset of `set_offset` and the shape phi of
+        `set_dispersion` (lrvb_glmm_gamma_terms); the context's y holds log(y).  What `glmm_poisson_terms` returns, in its
+        layouts.  The group sums stay resident for `glmm_slopes_schur`.  A point at which exp(log y - rho + s / 2) overflows is a
+        ValueError."""
+        return self._glmm_terms(self._lib.lrvb_glmm_gamma_terms, False, True, mean, var, e, r, (), (), want_grad, want_hess, want_border)
+
+    def glmm_gamma_obs_influence(self, mean, var, e, r, A, n0=0, n1=None):
+        """(n1 - n0) x Q rows of the Gamma mixed model, as `glmm_poisson_obs_influence` (lrvb_glmm_gamma_obs_influence)."""
+        return self._glmm_obs_influence(self._lib.lrvb_glmm_gamma_obs_influence, False, True, mean, var, e, r, (), (), A, n0, n1)
+
+    def glmm_gamma_group_influence(self, mean, var, e, r, A):
+        """G x Q group influence of the Gamma mixed model, as `glmm_poisson_group_influence` (lrvb_glmm_gamma_group_influence)."""
+        return self._glmm_group_influence(self._lib.lrvb_glmm_gamma_group_influence, False, True, mean, var, e, r, (), (), A)
+
+    def glmm_gamma_dispersion_terms(self, mean, var, e, r):
+        """As `glmm_beta_dispersion_terms` for the Gamma model (lrvb_glmm_gamma_dispersion_terms), without nodes: d[0] = d[1] = the
+        data term and the cross terms its gradient (the row term is linear in phi), formed by a kernel of their own."""
+        return self._glmm_dispersion_terms(self._lib.lrvb_glmm_gamma_dispersion_terms, mean, var, e, r, (), (), nodes=False)
 
     # ---- multinomial (softmax) regression: beta is (K - 1) x n_cols, D = (K - 1) n_cols (lrvb_softmax_*) --------------------
     def softmax_set_labels(self, labels, n_classes):

@@ -671,7 +671,7 @@ int lrvb_glmm_ztpoisson_group_influence(lrvb_ctx* ctx, const double* mean, const
  *   y_n in {1, 2, ..},  P(y_n | t_n) = NB2(y_n; mu_n = e^{t_n}, phi_n) / (1 - (1 + mu_n / phi_n)^{-phi_n}),  t_n = o_n + x_n . beta + z_n . u_g(n):
  * the count part of a hurdle model for over-dispersed counts, with a KNOWN per-row dispersion phi_n > 0.
  * lrvb_set_dispersion, a sibling of lrvb_set_trials: n_obs positive finite values in one device buffer of their own, or NULL to
- * clear them; replaced by the next call.  Only the lrvb_glmm_ztnegbin_* and lrvb_glmm_beta_* entries read it.  The call drops the resident group sums,
+ * clear them; replaced by the next call.  Only the lrvb_glmm_ztnegbin_*, lrvb_glmm_beta_*, lrvb_glmm_gamma_* and lrvb_glmm_censnormal_* entries read it.  The call drops the resident group sums,
  * the factor and the group covariance.  A value that is not positive and finite: LRVB_ERR_INVALID, checked on the host ahead of
  * everything else (the state is left as it was); n < 1 with a non-null pointer: LRVB_ERR_SIZE (the dispersion is then cleared, as
  * lrvb_set_trials clears the trials); a length other than n_obs is found when an entry runs: LRVB_ERR_STATE.                    */
@@ -802,6 +802,55 @@ int lrvb_glmm_gamma_group_influence(lrvb_ctx* ctx, const double* mean, const dou
 int lrvb_glmm_gamma_dispersion_terms(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
                                      int64_t G, int64_t K, double* d_out, double* cross_global_out, double* cross_local_out);
 
+/* ---- censored Gaussian (Tobit) mixed model with K <= 4 independent random effects per group --------------
+ *   y*_n ~ N(t_n, 1 / phi_n),  t_n = o_n + x_n . beta + z_n . u_g(n),  and a status delta_n per row: 0, y_n = y*_n is observed;
+ *   +1, right-censored (y*_n > y_n); -1, left-censored (y*_n < y_n).  On log-times it is the log-normal accelerated-failure-time
+ * model with shared frailties.  The precision phi_n > 0 is KNOWN per row (lrvb_set_dispersion), the offset the RAW one of
+ * lrvb_set_offset, and the context's y (LRVB_SLOT_Y) holds y_n.
+ * lrvb_set_censoring, a sibling of lrvb_set_dispersion: n_obs values in {-1, 0, +1}, kept in one device buffer of their own, or
+ * NULL to clear them; replaced by the next call.  Only the lrvb_glmm_censnormal_* entries read it.  The call drops the resident
+ * group sums, the factor and the group covariance.  Any other value: LRVB_ERR_INVALID, checked on the host ahead of everything else
+ * (the state is left as it was); n < 1 with a non-null pointer: LRVB_ERR_SIZE (the status is then cleared); a length other than
+ * n_obs is found when an entry runs: LRVB_ERR_STATE.                                                                            */
+int lrvb_set_censoring(lrvb_ctx* ctx, const int32_t* status, int64_t n);
+/* Data term.  With r = sqrt(phi), t ~ N(rho_n, s_n), rho_n = offset_n + x_n . mean + z_n . e_g(n) and s_n as in
+ * lrvb_glmm_slopes_terms, the row term is
+ *   observed   h(t) = phi (y - t)^2 / 2            (1/2 log phi - 1/2 log 2 pi is dropped): closed form, no nodes,
+ *              E h = phi ((y - rho)^2 + s) / 2,  E h' = -phi (y - rho),  E h'' = phi,  E h''' = E h'''' = 0;
+ *   censored   h(t) = -log Phi(a),  a = delta r (t - y): d_t^k h = (delta r)^k H^(k)(a), H = -log Phi, on the caller's Gauss-Hermite
+ *              nodes with the inverse-Mills evaluation of the probit link (lrvb_glmm_binomial_terms under LRVB_LINK_PROBIT);
+ *   value = sum_n w_n E h,  a1 = w E h',  a2 = w E h'' / 2,  c11 = w E h'',  c12 = w E h''' / 2,  c22 = w E h'''' / 4
+ * in the five-row layout, the scratch sizes and the summation order of the logistic entries.  The kernel does not clamp: a value
+ * that is not finite after the reduction (phi (rho - y)^2 overflows, or a^2 / 2 in the tail of a censored row): LRVB_ERR_INVALID,
+ * the other outputs are then unspecified and no sums stay resident.  Arguments, outputs, the column layout of group_sums_out,
+ * want_border, the fixed summation order (two calls at one point are bitwise equal) and the reduce-hook contract are those of
+ * lrvb_glmm_slopes_terms; the group sums stay resident for lrvb_glmm_slopes_schur, the two solves and lrvb_glmm_slopes_group_cov.
+ * The entries read neither lrvb_set_trials nor lrvb_set_link.  No dispersion or no status set, or one of another length than
+ * n_obs: LRVB_ERR_STATE.  The other errors are those of lrvb_glmm_ztpoisson_terms.  y is not validated here (the Python layer
+ * asks for finite y).                                                                                                           */
+int lrvb_glmm_censnormal_terms(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                               int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes, double* value_out,
+                               double* grad_global_out, double* H_blocks_out, double* group_sums_out, int32_t want_border);
+/* Streamed weight influence of that model: lrvb_glmm_slopes_obs_influence with, per unit weight, a1' = E h' (there is no "- y":
+ * the response sits inside h) and a2' = E h'' / 2.  Operand layouts, the row window, the output, "a window equals the same rows
+ * of the full result bitwise" and "no reduce-hook call" as there; errors as lrvb_glmm_censnormal_terms, and n0 > n1 or
+ * n1 > n_obs: LRVB_ERR_INVALID.                                                                                                 */
+int lrvb_glmm_censnormal_obs_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                                       int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
+                                       const double* A_global, const double* A_local, int64_t Q, int64_t n0, int64_t n1, double* out);
+/* Group influence of that model, as lrvb_glmm_ztpoisson_group_influence.  Errors as lrvb_glmm_censnormal_obs_influence.         */
+int lrvb_glmm_censnormal_group_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e,
+                                         const double* r, int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
+                                         const double* A_global, const double* A_local, int64_t Q, double* out);
+/* The derivative in the log-precision lambda (phi_n = e^lambda phi0_n, so d a / d lambda = a / 2) of that model, as
+ * lrvb_glmm_beta_dispersion_terms.  Observed rows are linear in phi: h_l = h_ll = h, d_t h_l = h', d_t^2 h_l = h''.  Censored rows:
+ *   h_l = a H' / 2,  h_ll = a (a H'' + H') / 4,  d_t h_l = delta r (a H'' + H') / 2,  d_t^2 h_l = phi (a H''' + 2 H'') / 2.
+ * Reads the state of lrvb_glmm_censnormal_terms; writes NEITHER the resident group sums NOR the factor NOR the group covariance
+ * and drops none of them.  Errors as lrvb_glmm_censnormal_terms.                                                                */
+int lrvb_glmm_censnormal_dispersion_terms(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e,
+                                          const double* r, int64_t G, int64_t K, const double* gh_x, const double* gh_w,
+                                          int32_t n_nodes, double* d_out, double* cross_global_out, double* cross_local_out);
+
 /* ---- group blocks of H^-1, fitted values and predictions with their linear-response variance ------------
  * For every mixed model with K <= 4 effects per group.  After a successful lrvb_glmm_slopes_schur (the factor L_g, U_g resident)
  * and a factored free Schur complement S on the caller's side, with
@@ -868,6 +917,13 @@ int lrvb_glmm_ztnegbin_predict(lrvb_ctx* ctx, const double* mean, const double* 
                                int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes, const double* cov_beta,
                                int64_t n0, int64_t n1, const double* x_new, const double* z_new, const int32_t* gid_new,
                                const double* offset_new, const double* dispersion_new, int64_t n_new, double* out);
+/* The censored Gaussian model: the arguments of lrvb_glmm_ztpoisson_predict.  The response-scale mean is the
+ * LATENT mean E y* = rho, whatever the precision and under either variance; neither y nor the status nor the precision of new
+ * rows is asked for.                                                                                                            */
+int lrvb_glmm_censnormal_predict(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                                 int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes, const double* cov_beta,
+                                 int64_t n0, int64_t n1, const double* x_new, const double* z_new, const int32_t* gid_new,
+                                 const double* offset_new, int64_t n_new, double* out);
 
 /* ---- multinomial (softmax) regression ---------------------------------------------------------
  * K classes (2 <= K <= 17), labels y_n in {0 .. K-1}, class 0 the reference; coefficients beta ((K-1) x P, row-major, row a

@@ -7,6 +7,7 @@
 //   zero-truncated NB2:  y_n >= 1,  P(y_n) = NB2(y_n; mu_n, phi_n) / (1 - (1 + mu_n / phi_n)^-phi_n),  mu_n as lambda_n
 //   Beta:  0 < y_n < 1,  y_n ~ Beta(mu_n phi_n, (1 - mu_n) phi_n),  mu_n = sigma(o_n + x_n . beta + z_n . u_g(n))
 //   Gamma:  y_n > 0,  y_n ~ Gamma(shape phi_n, mean exp(o_n + x_n . beta + z_n . u_g(n)))
+//   censored Gaussian:  y*_n ~ N(o_n + x_n . beta + z_n . u_g(n), 1 / phi_n), observed, left- or right-censored at y_n
 // Per observation rho_n = x_n . m + z_n . e_g, s_n = (x_n o x_n) . v + (z_n o z_n) . r_g and five coefficients a1, a2, c11, c12, c22.
 // Every kernel that walks the rows is written ONCE, as a template over a likelihood policy (k_glmm_walk.h, DESIGN.md sections 27 and
 // 31): LogisticLik (the quadrature k_glmm.hip runs too; with K = 1 and z = 1 this is that model) and PoissonLik
@@ -210,6 +211,7 @@ static int gs_with_lik(const GlmmLik& lik, F&& f) {
     if (lik.kind == GLMM_ZTNEGBIN) return f(TruncNegBinLik(), TruncNegBinLik::Args{q, lik.off, lik.trials, lik.y});
     if (lik.kind == GLMM_BETA) return f(BetaLik(), BetaLik::Args{q, lik.off, lik.trials, lik.y});
     if (lik.kind == GLMM_GAMMA) return f(GammaLik(), GammaLik::Args{lik.off, lik.trials, lik.y});
+    if (lik.kind == GLMM_CENSNORMAL) return f(CensNormalLik(), CensNormalLik::Args{q, lik.off, lik.trials, lik.y, lik.cens});
     if (lik.kind == GLMM_BINOMIAL && lik.link == GLMM_LINK_PROBIT)
         return f(BinomialLinkLik<GLMM_LINK_PROBIT>(), BinomialLinkLik<GLMM_LINK_PROBIT>::Args{q, lik.off, lik.trials, lik.y});
     if (lik.kind == GLMM_BINOMIAL && lik.link == GLMM_LINK_CLOGLOG)
@@ -353,7 +355,7 @@ static int gs_launch_disp(lrvb_ctx* c, int Kz, typename DLik::Args la, const dou
     return LRVB_OK;
 }
 
-// `lik` is the likelihood of the family's terms entry (GLMM_BETA, GLMM_GAMMA, or GLMM_BINOMIAL with the logit link: NB2), `disp` the resident
+// `lik` is the likelihood of the family's terms entry (GLMM_BETA, GLMM_GAMMA, GLMM_CENSNORMAL, or GLMM_BINOMIAL with the logit link: NB2), `disp` the resident
 // dispersion; coef 2 x NP (zeroed by the caller), gsum G x 2 K (zeroed by the caller), part 2 x 2 K and vpart 2 doubles per tile.
 int launch_glmm_disp_rows(lrvb_ctx* c, const GlmmLik& lik, const double* disp, int Kz, const double* m, const double* vb, const double* eg,
                           const double* rg, double* coef, i64 NP, double* gsum, double* part, double* vpart) {
@@ -362,9 +364,11 @@ int launch_glmm_disp_rows(lrvb_ctx* c, const GlmmLik& lik, const double* disp, i
         return gs_launch_disp<BetaDispLik>(c, Kz, BetaDispLik::Args{q, lik.off, disp, lik.y}, m, vb, eg, rg, coef, NP, gsum, part, vpart);
     if (lik.kind == GLMM_GAMMA)
         return gs_launch_disp<GammaDispLik>(c, Kz, GammaDispLik::Args{lik.off, disp, lik.y}, m, vb, eg, rg, coef, NP, gsum, part, vpart);
+    if (lik.kind == GLMM_CENSNORMAL)
+        return gs_launch_disp<CensNormalDispLik>(c, Kz, CensNormalDispLik::Args{q, lik.off, disp, lik.y, lik.cens}, m, vb, eg, rg, coef, NP, gsum, part, vpart);
     if (lik.kind == GLMM_BINOMIAL && lik.link == GLMM_LINK_LOGIT)
         return gs_launch_disp<NegBinDispLik>(c, Kz, NegBinDispLik::Args{q, lik.off, lik.trials, disp, lik.y}, m, vb, eg, rg, coef, NP, gsum, part, vpart);
-    LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the dispersion derivative is that of the Beta, the Gamma and the negative binomial mixed model");
+    LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the dispersion derivative is that of the Beta, the Gamma, the censored Gaussian and the negative binomial mixed model");
 }
 
 // A = L L^T of one local block from its upper triangle a (row-major), L row-major into Ls; false where a pivot is not positive
@@ -844,6 +848,18 @@ void glmm_gamma_infl_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* __r
     gsi_infl_rows<GammaLik>(n0, R, P, Kz, X, Z, y, gid, m, vb, eg, rg, {off, disp, y}, Ag, Al, Q, out);
 }
 
+// The censored Gaussian model: the arguments of the Beta entry, the status behind y; y holds the responses.
+__global__ __launch_bounds__(256)
+void glmm_censnormal_infl_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* __restrict__ X, const double* __restrict__ Z,
+                                      const double* __restrict__ off, const double* __restrict__ disp, const double* __restrict__ y,
+                                      const double* __restrict__ cens, const int* __restrict__ gid, const double* __restrict__ m,
+                                      const double* __restrict__ vb, const double* __restrict__ eg, const double* __restrict__ rg,
+                                      const double* __restrict__ gx, const double* __restrict__ gw, int nq, const double* __restrict__ Ag,
+                                      const double* __restrict__ Al, int Q, double* __restrict__ out)
+{
+    gsi_infl_rows<CensNormalLik>(n0, R, P, Kz, X, Z, y, gid, m, vb, eg, rg, {{gx, gw, nq}, off, disp, y, cens}, Ag, Al, Q, out);
+}
+
 template <class Lik>
 static int gs_launch_infl_rows(lrvb_ctx* c, int Kz, const double* Z, typename Lik::Args la, i64 n0, i64 n1, const int* gid, const double* m,
                                const double* vb, const double* eg, const double* rg, const double* Ag, const double* Al, i64 Q,
@@ -872,6 +888,10 @@ static int gs_launch_infl_rows(lrvb_ctx* c, int Kz, const double* Z, typename Li
     else if constexpr (std::is_same<Lik, GammaLik>::value)
         hipLaunchKernelGGL(glmm_gamma_infl_rows_kernel, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
                            (const double*)la.off, (const double*)la.disp, (const double*)la.y, gid, m, vb, eg, rg, Ag, Al, (int)Q, out);
+    else if constexpr (std::is_same<Lik, CensNormalLik>::value)
+        hipLaunchKernelGGL(glmm_censnormal_infl_rows_kernel, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
+                           (const double*)la.off, (const double*)la.disp, (const double*)la.y, (const double*)la.cens, gid, m, vb, eg, rg,
+                           la.q.gx, la.q.gw, la.q.nq, Ag, Al, (int)Q, out);
     else if constexpr (gs_link_of<Lik>::value != GLMM_LINK_LOGIT)
         hipLaunchKernelGGL(glmm_link_infl_rows_kernel<gs_link_of<Lik>::value>, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz,
                            (const double*)c->X.p, Z, (const double*)la.off, (const double*)la.trials, (const double*)la.y, gid, m, vb, eg, rg,
@@ -1292,6 +1312,18 @@ void glmm_ztnegbin_predict_rows_kernel(i64 n0, i64 R, int P, int Kz, const doubl
     gsp_predict_rows<TruncNegBinLik>(n0, R, P, Kz, X, Z, gid, m, vb, eg, rg, {{gx, gw, nq}, off, disp, nullptr}, Sbb, gcov, out, ldo);
 }
 
+// The censored Gaussian model: the arguments of the zero-truncated Poisson entry.  No y, no status and no
+// precision: the latent mean rho + o needs none of them, and new rows have none (the policy's staged fold o - y is then o).
+__global__ __launch_bounds__(256)
+void glmm_censnormal_predict_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* __restrict__ X, const double* __restrict__ Z,
+                                         const double* __restrict__ off, const int* __restrict__ gid, const double* __restrict__ m,
+                                         const double* __restrict__ vb, const double* __restrict__ eg, const double* __restrict__ rg,
+                                         const double* __restrict__ gx, const double* __restrict__ gw, int nq,
+                                         const double* __restrict__ Sbb, const double* __restrict__ gcov, double* __restrict__ out, i64 ldo)
+{
+    gsp_predict_rows<CensNormalLik>(n0, R, P, Kz, X, Z, gid, m, vb, eg, rg, {{gx, gw, nq}, off, nullptr, nullptr, nullptr}, Sbb, gcov, out, ldo);
+}
+
 int launch_glmm_slopes_predict_rows(lrvb_ctx* c, const GlmmLik& lik, int Kz, const double* X, const double* Z, i64 n0, i64 n1,
                                     const int* gid, const double* m, const double* vb, const double* eg, const double* rg,
                                     const double* Sbb, const double* gcov, double* out, i64 ldo) {
@@ -1307,6 +1339,9 @@ int launch_glmm_slopes_predict_rows(lrvb_ctx* c, const GlmmLik& lik, int Kz, con
                            gcov, out, ldo);
     else if (lik.kind == GLMM_ZTPOISSON)
         hipLaunchKernelGGL(glmm_ztpoisson_predict_rows_kernel, grid, block, 0, c->stream, n0, R, P, Kz, X, Z, lik.off, gid, m, vb, eg, rg,
+                           lik.gx, lik.gw, lik.n_nodes, Sbb, gcov, out, ldo);
+    else if (lik.kind == GLMM_CENSNORMAL)
+        hipLaunchKernelGGL(glmm_censnormal_predict_rows_kernel, grid, block, 0, c->stream, n0, R, P, Kz, X, Z, lik.off, gid, m, vb, eg, rg,
                            lik.gx, lik.gw, lik.n_nodes, Sbb, gcov, out, ldo);
     else if (lik.kind == GLMM_ZTNEGBIN) {
         if (!lik.trials) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "%s", TruncNegBinLik::LIMITS);

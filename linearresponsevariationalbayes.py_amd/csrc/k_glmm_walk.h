@@ -873,6 +873,130 @@ struct GammaLik {
     }
 };
 
+// Censored Gaussian (Tobit) with a per-row precision phi, a per-row offset and a per-row status: the latent
+// y* ~ N(t, 1 / phi), and the row says delta = 0 (y = y* observed), +1 (right-censored: y* > y) or -1 (left-censored: y* < y).  The
+// first policy that is closed form OR quadrature per row, by the row's status.  With r = sqrt(phi) and u = rho - y (rho including the
+// offset) the row's term under t ~ N(rho, s), constants dropped, is
+//   observed   h(t) = phi (y - t)^2 / 2:   E h = phi (u^2 + s) / 2,  E h' = phi u,  E h'' = phi,  E h''' = E h'''' = 0      (no nodes);
+//   censored   h(t) = H(a),  a = delta r (t - y),  H = -log Phi:   d_t^k h = (delta r)^k H^(k)(a) on the nodes t_k = rho + sqrt(s) x_k,
+//              H .. H'''' from BinomialLinkLik<PROBIT>::h1<5> as it stands (h1<2> in the influence walk).
+// What is STAGED is the fold d = o - y next to phi and delta (three arrays, the LDS of the probit policy): u = rho_x + d is one
+// addition, a shift of y and o by a common constant leaves d -- and with it every result -- unchanged wherever the shifted values are
+// exact, and the predict walk, which has no y (a null y stages zeros), reads d = o: `mean` is rho + d.  y, phi and delta are read
+// from the ORIGINAL row index, as every staged array; a null status is "every row observed".  Coefficients in the logistic five-row
+// layout as BinomialLinkLik forms them (MINUS_Y false: y sits inside u).  The four lanes of a row share the nodes and share the
+// row's status, so a quad never diverges; the shuffles stand outside the branch and run in fixed order; no atomics.  The powers of
+// delta r multiply the FINISHED sums, outside every fused multiply-add: with sqrt(phi) a power of two an all-censored data set is
+// the probit model on the design (r x, r z) with the offset r (o - y) to the last bit of a, and sum_k w_k H^(j)(a_k) is formed as the
+// probit policy forms it.  No clamp: an observed row overflows with phi u^2, a censored one with a^2 / 2 in the left tail; the
+// non-finite value reaches the sums and the entry refuses the point.
+struct CensNormalLik {
+    typedef BinomialLinkLik<GLMM_LINK_PROBIT> Probit;
+    struct Args { LogisticLik::Args q; const double* __restrict__ off; const double* __restrict__ disp; const double* __restrict__ y;
+                  const double* __restrict__ cens; };                       // off, y (predict) and cens (all observed) may be nullptr
+    struct Lds { LogisticLik::Lds q; double s_d[GLMM_T], s_phi[GLMM_T], s_st[GLMM_T]; };     // o - y, phi, delta as a double
+    typedef LogisticLik::Moments Moments;
+    static constexpr const char* LIMITS = "censored Gaussian mixed model: P <= 64, 1 <= K <= 4, at most 128 nodes";
+    static bool args_ok(const Args& a) { return LogisticLik::args_ok(a.q) && a.disp != nullptr && a.y != nullptr; }
+    static constexpr int NCF = 5, NB = 4, DK = 16;
+    static constexpr bool HAS_FACTOR = false;
+    static constexpr bool MINUS_Y = false;
+    static __device__ __forceinline__ int cf_row(int kind) { return kind; }
+    static __device__ __forceinline__ double cf_factor(int) { return 1.0; }
+    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return b * Kz + k; }
+    static __device__ __forceinline__ int d_stride(int) { return DK; }
+
+    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { LogisticLik::init(L.q, a.q, tid); }
+    static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
+    {
+        const double o = (a.off && live) ? a.off[src] : 0.0;
+        const double yy = (a.y && live) ? a.y[src] : 0.0;
+        L.s_d[t] = o - yy;
+        L.s_phi[t] = (a.disp && live) ? a.disp[src] : 1.0;
+        L.s_st[t] = (a.cens && live) ? a.cens[src] : 0.0;
+    }
+    static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_d[row]; }
+    static __device__ __forceinline__ int lane_row() { return (int)(threadIdx.x >> 2); }
+
+    // a1' = E h' and E h'' = 2 a2' per unit weight, on all four lanes of a row; o is the staged fold o - y
+    static __device__ __forceinline__ void infl(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& e1,
+                                                double& e2)
+    {
+        const int row = lane_row();
+        const double phi = L.s_phi[row], st = L.s_st[row];
+        const double u = rho + o;
+        const bool cens = live && st != 0.0;
+        e1 = 0.0; e2 = 0.0;
+        if (cens) {
+            const double dr = st * sqrt(phi), sd = sqrt(fmax(s, 0.0));
+            for (int k = q4; k < a.q.nq; k += 4) {
+                const double tu = u + sd * L.q.sx[k], wk = L.q.sw[k];
+                double av, h[5];
+                {
+#pragma clang fp contract(off)
+                    av = dr * tu;
+                }
+                Probit::h1<2>(av, h);
+                e1 += wk * h[1]; e2 += wk * h[2];
+            }
+        }
+        e1 += __shfl_xor(e1, 1); e2 += __shfl_xor(e2, 1);
+        e1 += __shfl_xor(e1, 2); e2 += __shfl_xor(e2, 2);
+        {
+#pragma clang fp contract(off)
+            if (cens) { e1 = e1 * (st * sqrt(phi)); e2 = e2 * phi; }
+            else if (live) { e1 = phi * u; e2 = phi; }
+        }
+    }
+    // the latent mean E y* = rho + o, whatever phi and whatever the variance (no y in the predict walk: the staged fold is o)
+    static __device__ __forceinline__ void mean(const Lds&, const Args&, double o, bool live, int, double rho, double, double& mu)
+    {
+        mu = live ? rho + o : 0.0;
+    }
+    static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
+    {
+        const int row = lane_row();
+        const double phi = L.s_phi[row], st = L.s_st[row];
+        const double u = rho + L.s_d[row];
+        const bool cens = live && st != 0.0;
+        double e[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        if (cens) {
+            const double dr = st * sqrt(phi), sd = sqrt(fmax(s, 0.0));
+            for (int k = q4; k < a.q.nq; k += 4) {
+                const double tu = u + sd * L.q.sx[k], wk = L.q.sw[k];
+                double av, h[5];
+                {
+#pragma clang fp contract(off)
+                    av = dr * tu;
+                }
+                Probit::h1<5>(av, h);
+#pragma unroll
+                for (int i = 0; i < 5; ++i) e[i] += wk * h[i];
+            }
+        }
+#pragma unroll
+        for (int off = 1; off <= 2; off <<= 1)
+#pragma unroll
+            for (int i = 0; i < 5; ++i) e[i] += __shfl_xor(e[i], off);
+        {
+#pragma clang fp contract(off)
+            if (cens) {
+                const double dr = st * sqrt(phi);
+                e[1] = e[1] * dr; e[2] = e[2] * phi; e[3] = e[3] * (dr * phi); e[4] = e[4] * (phi * phi);
+            } else if (live) {
+                const double q = u * u + s;
+                e[0] = 0.5 * (phi * q); e[1] = phi * u; e[2] = phi;
+            }
+        }
+        return {e[0], e[1], e[2], e[3], e[4]};
+    }
+    static __device__ __forceinline__ double coefs(const Lds&, int, const Moments& mo, double wi, double, double, double, double* k)
+    {
+        k[0] = wi * mo.e1; k[1] = wi * 0.5 * mo.e2; k[2] = wi * mo.e2; k[3] = wi * 0.5 * mo.e3; k[4] = wi * 0.25 * mo.e4;
+        return wi * mo.v;
+    }
+};
+
 // ---- the dispersion-derivative policies ----------------------------------------------------------------------
 // The dispersion of the Beta and the NB2 model as phi_n = e^lambda phi0_n with ONE scalar lambda: every derivative below is in
 // lambda at fixed t, d/d lambda = phi d/d phi.  A policy of this kind serves glmm_disp_rows_kernel (k_glmm_slopes.hip) and supplies
@@ -1010,6 +1134,59 @@ struct GammaDispLik {
         const double g = GammaLik::g_of(phi, L.s_y[row], rho, s);
         const double eh = g + phi * rho;
         return {eh, phi - g, g, eh};
+    }
+};
+
+// Censored Gaussian: the precision phi = e^lambda phi0, so r = sqrt(phi) and a = delta r (t - y) has d_l a = a / 2.
+//   observed   h is linear in phi, as the Gamma term:  h_l = h_ll = h,  d_t h_l = h',  d_t^2 h_l = h'':  (E h, phi u, phi, E h);
+//   censored   h_l = a H' / 2,   h_ll = a (a H'' + H') / 4,   d_t h_l = delta r (a H'' + H') / 2,   d_t^2 h_l = phi (a H''' + 2 H'') / 2
+// on the nodes, H', H'', H''' from the probit h1<5> (its value and fourth derivative are not read and fall to the compiler).  None of
+// the three sums cancels in a tail: as a -> -inf, a H'' + H' -> 2 a and a H''' + 2 H'' -> 2; as a -> +inf every term vanishes.  The
+// halves, delta r and phi multiply the finished sums.  Staging, the fold u = rho + (o - y) and the status are CensNormalLik's.
+struct CensNormalDispLik {
+    typedef CensNormalLik::Args Args;
+    typedef CensNormalLik::Lds Lds;
+    static constexpr const char* LIMITS = CensNormalLik::LIMITS;
+    static bool args_ok(const Args& a) { return CensNormalLik::args_ok(a); }
+    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { CensNormalLik::init(L, a, tid); }
+    static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src) { CensNormalLik::stage_row(L, a, t, live, src); }
+    static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return CensNormalLik::row_shift(L, row); }
+    static __device__ __forceinline__ int lane_row() { return CensNormalLik::lane_row(); }
+
+    static __device__ __forceinline__ DispMoments dmoments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
+    {
+        const int row = lane_row();
+        const double phi = L.s_phi[row], st = L.s_st[row];
+        const double u = rho + L.s_d[row];
+        const bool cens = live && st != 0.0;
+        double e0 = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0;
+        if (cens) {
+            const double dr = st * sqrt(phi), sd = sqrt(fmax(s, 0.0));
+            for (int k = q4; k < a.q.nq; k += 4) {
+                const double tu = u + sd * L.q.sx[k], wk = L.q.sw[k];
+                double av, h[5];
+                {
+#pragma clang fp contract(off)
+                    av = dr * tu;
+                }
+                CensNormalLik::Probit::h1<5>(av, h);
+                const double b1 = av * h[2] + h[1];                          // a H'' + H'
+                e0 += wk * (av * h[1]); e1 += wk * b1; e2 += wk * (av * h[3] + 2.0 * h[2]); e3 += wk * (av * b1);
+            }
+        }
+#pragma unroll
+        for (int off = 1; off <= 2; off <<= 1) {
+            e0 += __shfl_xor(e0, off); e1 += __shfl_xor(e1, off); e2 += __shfl_xor(e2, off); e3 += __shfl_xor(e3, off);
+        }
+        if (cens) return {0.5 * e0, (0.5 * (st * sqrt(phi))) * e1, (0.5 * phi) * e2, 0.25 * e3};
+        if (!live) return {0.0, 0.0, 0.0, 0.0};
+        double eh;
+        {
+#pragma clang fp contract(off)
+            const double q = u * u + s;
+            eh = 0.5 * (phi * q);
+        }
+        return {eh, phi * u, phi, eh};
     }
 };
 

@@ -231,7 +231,7 @@ extern "C" int lrvb_ctx_destroy(lrvb_ctx* c) {
     DevBuf* all[] = { &c->X, &c->y, &c->w, &c->quadA, &c->quadM, &c->quadB, &c->theta, &c->eta, &c->j1, &c->j2,
                       &c->vtmp, &c->vtmp2, &c->vtmp3, &c->g_eta, &c->g_free, &c->lp, &c->cw, &c->zbuf,
                       &c->part_vec, &c->part_val, &c->stats, &c->tile_part, &c->Heta, &c->Hfree, &c->Jdense,
-                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn, &c->gz, &c->goff, &c->gtr, &c->gdisp, &c->glmms, &c->glmms_fac, &c->glmms_T, &c->glmms_gcov,
+                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn, &c->gz, &c->goff, &c->gtr, &c->gdisp, &c->gcens, &c->glmms, &c->glmms_fac, &c->glmms_T, &c->glmms_gcov,
                       &c->sm.labels, &c->sm.p, &c->sm.wpad, &c->sm.work, &c->sm.col, &c->sm.tiles, &c->sm.rows };
     for (DevBuf* b : all) buf_free(*b);
     if (c->host_pinned) (void)hipHostFree(c->host_pinned);
@@ -2606,6 +2606,7 @@ static GlmmLik glmms_binomial(const lrvb_ctx* c, const double* gh_x, const doubl
 static GlmmLik glmms_ztpoisson(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_ZTPOISSON, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, LRVB_LINK_LOGIT, nullptr}; }
 static GlmmLik glmms_ztnegbin(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_ZTNEGBIN, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, LRVB_LINK_LOGIT, nullptr}; }
 static GlmmLik glmms_beta(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_BETA, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, LRVB_LINK_LOGIT, nullptr}; }
+static GlmmLik glmms_censnormal(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_CENSNORMAL, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, LRVB_LINK_LOGIT, nullptr, nullptr}; }
 static GlmmLik glmms_gamma() { return GlmmLik{GLMM_GAMMA, nullptr, nullptr, 0, nullptr, nullptr, false, LRVB_LINK_LOGIT, nullptr}; }
 // The likelihoods whose expectation is closed form: one exp per row, no nodes to check, upload or make room for.
 static bool glmms_closed_form(const GlmmLik& lik) { return lik.kind == GLMM_POISSON || lik.kind == GLMM_GAMMA; }
@@ -2614,6 +2615,7 @@ static const char* glmms_name(const GlmmLik& lik) {
     if (lik.kind == GLMM_ZTNEGBIN) return "zero-truncated negative binomial";
     if (lik.kind == GLMM_BETA) return "Beta";
     if (lik.kind == GLMM_GAMMA) return "Gamma";
+    if (lik.kind == GLMM_CENSNORMAL) return "censored Gaussian";
     return lik.kind == GLMM_POISSON ? "Poisson" : (lik.kind == GLMM_BINOMIAL ? "binomial" : "logistic");
 }
 
@@ -2637,11 +2639,15 @@ static int glmms_check(lrvb_ctx* c, const GlmmLik& lik, const double* mean, cons
         LRVB_FAIL(LRVB_ERR_STATE, "the offset has %lld entries, the model has %lld observations", (long long)c->goff_n, (long long)c->N);
     if (lik.kind == GLMM_BINOMIAL && c->gtr_n != 0 && c->gtr_n != c->N)
         LRVB_FAIL(LRVB_ERR_STATE, "the trials have %lld entries, the model has %lld observations", (long long)c->gtr_n, (long long)c->N);
-    const bool disp = lik.kind == GLMM_ZTNEGBIN || lik.kind == GLMM_BETA || lik.kind == GLMM_GAMMA;
+    const bool disp = lik.kind == GLMM_ZTNEGBIN || lik.kind == GLMM_BETA || lik.kind == GLMM_GAMMA || lik.kind == GLMM_CENSNORMAL;
     if (disp && c->gdisp_n == 0)
         LRVB_FAIL(LRVB_ERR_STATE, "no dispersion: call lrvb_set_dispersion first");
     if (disp && c->gdisp_n != c->N)
         LRVB_FAIL(LRVB_ERR_STATE, "the dispersion has %lld entries, the model has %lld observations", (long long)c->gdisp_n, (long long)c->N);
+    if (lik.kind == GLMM_CENSNORMAL && c->gcens_n == 0)
+        LRVB_FAIL(LRVB_ERR_STATE, "no censoring status: call lrvb_set_censoring first");
+    if (lik.kind == GLMM_CENSNORMAL && c->gcens_n != c->N)
+        LRVB_FAIL(LRVB_ERR_STATE, "the censoring status has %lld entries, the model has %lld observations", (long long)c->gcens_n, (long long)c->N);
     LRVB_TRY(check_len(P_in, c->P, "mean / var"));
     LRVB_TRY(check_len(G_in, c->n_groups, lik.unit ? "e / r" : "groups of e / r"));
     for (i64 j = 0; j < c->P; ++j) if (!(var[j] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "var[%lld] is not positive", (long long)j);
@@ -2665,6 +2671,7 @@ static int glmms_to_device(lrvb_ctx* c, GlmmLik& lik, double* g) {
     if (lik.kind == GLMM_ZTNEGBIN) { lik.trials = c->gdisp.p; lik.y = c->y.p; }   // phi rides in the trials slot; y is staged for y + phi
     if (lik.kind == GLMM_BETA) { lik.trials = c->gdisp.p; lik.y = c->y.p; }       // phi in the trials slot again; y holds logit(y)
     if (lik.kind == GLMM_GAMMA) { lik.trials = c->gdisp.p; lik.y = c->y.p; }      // the shape phi in the trials slot; y holds log(y)
+    if (lik.kind == GLMM_CENSNORMAL) { lik.trials = c->gdisp.p; lik.y = c->y.p; lik.cens = c->gcens.p; }   // the precision phi in the trials slot; y the responses
     if (glmms_closed_form(lik)) return LRVB_OK;
     LRVB_TRY(h2d(c, g, lik.gx, (size_t)lik.n_nodes));
     LRVB_TRY(h2d(c, g + 128, lik.gw, (size_t)lik.n_nodes));
@@ -2747,6 +2754,8 @@ static int glmms_terms(lrvb_ctx* c, GlmmLik lik, const double* mean, const doubl
         LRVB_FAIL(LRVB_ERR_INVALID, "the zero-truncated Poisson data term is not finite at this point: exp(rho + s / 2) overflows, or exp(t) underflows to 0, for some row (the kernel does not clamp)");
     if (lik.kind == GLMM_ZTNEGBIN && !std::isfinite(*value_out))
         LRVB_FAIL(LRVB_ERR_INVALID, "the zero-truncated negative binomial data term is not finite at this point: phi softplus(eta) underflows to 0 on a node, or a moment overflows, for some row (the kernel does not clamp)");
+    if (lik.kind == GLMM_CENSNORMAL && !std::isfinite(*value_out))
+        LRVB_FAIL(LRVB_ERR_INVALID, "the censored Gaussian data term is not finite at this point: phi (rho - y)^2 overflows for some observed row, or -log Phi in the tail of some censored row (the kernel does not clamp)");
     if (lik.kind == GLMM_BETA && !std::isfinite(*value_out))
         LRVB_FAIL(LRVB_ERR_INVALID, "the Beta data term is not finite at this point: the point, the offset or logit(y) is not finite for some row (no finite point is refused)");
     c->glmms_valid = true; c->glmms_K = lik.unit ? 0 : (int)K;           // 0: the sums of lrvb_glmm_terms, for lrvb_glmm_schur only
@@ -3209,6 +3218,49 @@ extern "C" int lrvb_glmm_gamma_group_influence(lrvb_ctx* c, const double* mean, 
     return glmms_group_influence(c, glmms_gamma(), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out);
 }
 
+// ---- censored Gaussian (Tobit) mixed model: observed, left- and right-censored rows with a known precision ----
+// The per-row status: a sibling of lrvb_set_dispersion.  Checked here, on the host, and kept as doubles (-1, 0, +1) so that the
+// kernels stage it next to the precision.
+extern "C" int lrvb_set_censoring(lrvb_ctx* c, const int32_t* status, int64_t n) {
+    LRVB_TRY(ctx_bind(c));
+    std::vector<double> st;
+    if (status) {
+        for (int64_t i = 0; i < n; ++i)
+            if (status[i] < -1 || status[i] > 1)
+                LRVB_FAIL(LRVB_ERR_INVALID, "censoring[%lld] is %d: the status is -1 (left-censored), 0 (observed) or +1 (right-censored)", (long long)i, (int)status[i]);
+        st.assign(status, status + (n > 0 ? n : 0));
+        st.push_back(0.0);                                               // never an empty vector: n < 1 is refused below, not read as "clear"
+    }
+    return glmms_set_rows(c, c->gcens, c->gcens_n, status ? st.data() : nullptr, n, 1, "the censoring status needs at least one entry");
+}
+
+// The shared bodies with the CensNormalLik policy: the caller's nodes, the RAW offset of lrvb_set_offset, the precision of
+// lrvb_set_dispersion and the status of lrvb_set_censoring; the context's y holds the responses (the censoring points of the
+// censored rows).  Neither the trials nor the link of the binomial entries is read.
+extern "C" int lrvb_glmm_censnormal_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                          const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                          int32_t n_nodes, double* value_out, double* grad_global_out, double* H_blocks_out,
+                                          double* group_sums_out, int32_t want_border) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_terms(c, glmms_censnormal(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, value_out, grad_global_out,
+                       H_blocks_out, group_sums_out, want_border);
+}
+
+extern "C" int lrvb_glmm_censnormal_obs_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                                  const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                                  int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, int64_t n0,
+                                                  int64_t n1, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_obs_influence(c, glmms_censnormal(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, n0, n1, out);
+}
+
+extern "C" int lrvb_glmm_censnormal_group_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                                    const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                                    int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_group_influence(c, glmms_censnormal(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out);
+}
+
 // ---- the derivative in the log-dispersion of the Beta and the NB2 mixed model (k_glmm_slopes.hip) ----------
 // The checks of the family's terms entry, in its order, then the dispersion (the binomial kind does not ask for one).  Everything
 // lives in c->work1, as the influence entries keep theirs:
@@ -3250,7 +3302,7 @@ static int glmms_dispersion_terms(lrvb_ctx* c, GlmmLik lik, const double* mean, 
     LRVB_TRY(obs_reduce(c, gsum, nres));
     LRVB_TRY(d2h(c, d_out, dred, 2));
     if (!std::isfinite(d_out[0]) || !std::isfinite(d_out[1]))
-        LRVB_FAIL(LRVB_ERR_INVALID, "the dispersion derivative of the %s data term is not finite at this point", lik.kind == GLMM_BETA ? "Beta" : (lik.kind == GLMM_GAMMA ? "Gamma" : "negative binomial"));
+        LRVB_FAIL(LRVB_ERR_INVALID, "the dispersion derivative of the %s data term is not finite at this point", lik.kind == GLMM_BETA ? "Beta" : (lik.kind == GLMM_GAMMA ? "Gamma" : (lik.kind == GLMM_CENSNORMAL ? "censored Gaussian" : "negative binomial")));
     LRVB_TRY(d2h(c, cross_global_out, gred, (size_t)(2 * P)));
     return d2h(c, cross_local_out, gsum, (size_t)(G * K2));
 }
@@ -3268,6 +3320,14 @@ extern "C" int lrvb_glmm_gamma_dispersion_terms(lrvb_ctx* c, const double* mean,
                                                 double* cross_local_out) {
     LRVB_TRY(ctx_bind(c));
     return glmms_dispersion_terms(c, glmms_gamma(), mean, var, P_in, e_loc, r_loc, G_in, K, d_out, cross_global_out, cross_local_out);
+}
+
+extern "C" int lrvb_glmm_censnormal_dispersion_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                                     const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                                     int32_t n_nodes, double* d_out, double* cross_global_out, double* cross_local_out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_dispersion_terms(c, glmms_censnormal(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, d_out, cross_global_out,
+                                  cross_local_out);
 }
 
 extern "C" int lrvb_glmm_negbin_dispersion_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
@@ -3416,6 +3476,17 @@ extern "C" int lrvb_glmm_ztnegbin_predict(lrvb_ctx* c, const double* mean, const
     LRVB_TRY(ctx_bind(c));
     return glmms_predict(c, glmms_ztnegbin(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, Gp, K, cov_beta, n0, n1, x_new, z_new,
                          gid_new, offset_new, dispersion_new, n_new, out);
+}
+
+// The censored Gaussian model: the latent mean rho + o under both variances; new rows carry an offset only.
+extern "C" int lrvb_glmm_censnormal_predict(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                            const double* r_loc, int64_t Gp, int64_t K, const double* gh_x, const double* gh_w,
+                                            int32_t n_nodes, const double* cov_beta, int64_t n0, int64_t n1, const double* x_new,
+                                            const double* z_new, const int32_t* gid_new, const double* offset_new, int64_t n_new,
+                                            double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_predict(c, glmms_censnormal(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, Gp, K, cov_beta, n0, n1, x_new, z_new,
+                         gid_new, offset_new, nullptr, n_new, out);
 }
 
 // ---- logistic regression with a full-covariance Gaussian posterior q(beta) = N(m, Sigma) ----------------------------------

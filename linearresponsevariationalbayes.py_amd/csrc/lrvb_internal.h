@@ -149,8 +149,10 @@ struct lrvb_ctx {
     DevBuf gtr; i64 gtr_n = 0;
     // and the link of lrvb_set_link (LRVB_LINK_LOGIT = 0 by default); no other entry reads it
     int glmms_link = 0;
-    // lrvb_glmm_ztnegbin_* and lrvb_glmm_beta_* read the offset and the per-row dispersion of lrvb_set_dispersion, gdisp_n doubles (0 = none: refused)
+    // lrvb_glmm_ztnegbin_*, lrvb_glmm_beta_*, lrvb_glmm_gamma_* and lrvb_glmm_censnormal_* read the offset and the per-row dispersion of lrvb_set_dispersion, gdisp_n doubles (0 = none: refused)
     DevBuf gdisp; i64 gdisp_n = 0;
+    // lrvb_glmm_censnormal_* also read the per-row censoring status of lrvb_set_censoring (-1 / 0 / +1 as doubles), gcens_n of them (0 = none: refused)
+    DevBuf gcens; i64 gcens_n = 0;
     DevBuf opt;                    // trust-region Newton-CG: 12 D-vectors (+ the D x D preconditioner)
     DevBuf cgm[9];                 // blocked CG: B, X, R, P, Q, Z (Q x D), U, W (Q x V), R^T (P x Q)
     DevBuf cgT;                    // N x Q products X U^T of the blocked HVP
@@ -267,11 +269,13 @@ int  launch_glmm_infl_local(lrvb_ctx* c, i64 Q, const double* S, const double* A
 enum GlmmKind { GLMM_LOGISTIC = 0, GLMM_POISSON = 1, GLMM_BINOMIAL = 2, GLMM_ZTPOISSON = 3,    // ZTPOISSON: nodes and an offset, no trials
                 GLMM_ZTNEGBIN = 4,     // zero-truncated NB2: nodes, the shifted offset, the dispersion phi in `trials`, and `y`
                 GLMM_BETA = 5,         // Beta: nodes, the raw offset, the precision phi in `trials`, and logit(y) in `y`
-                GLMM_GAMMA = 6 };      // Gamma, log link: NO nodes, the raw offset, the shape phi in `trials`, and log(y) in `y`
+                GLMM_GAMMA = 6,        // Gamma, log link: NO nodes, the raw offset, the shape phi in `trials`, and log(y) in `y`
+                GLMM_CENSNORMAL = 7 }; // censored Gaussian: nodes, the raw offset, the precision phi in `trials`, y in `y`, the status in `cens`
 // `link` (binomial only, LRVB_LINK_*; 0 = logit: BinomialLik) picks the probit or cloglog policy of DESIGN.md section 35, and `y`
 // is the response those two stage themselves (the host bodies fill it in with the offset and the trials).
 struct GlmmLik { GlmmKind kind; const double* gx; const double* gw; int n_nodes; const double* off; const double* trials; bool unit;
-                 int link; const double* y; };
+                 int link; const double* y;
+                 const double* cens; };   // censored Gaussian only: the per-row status -1 / 0 / +1 as doubles (device), or nullptr: every row observed
 int  glmm_slopes_ncol(int P, int K);      // columns of one group's sums: 2 K + K (2 K + 1) + 4 K P
 int  launch_glmm_slopes_rows(lrvb_ctx* c, const GlmmLik& lik, int K, const double* Z /* N x K; nullptr: the unit design */, const double* m, const double* vb,
                              const double* eg /* G x K */, const double* rg /* G x K */,

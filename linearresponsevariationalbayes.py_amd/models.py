@@ -663,7 +663,7 @@ class DeviceContext(object):
     # ---- zero-truncated NB2 mixed model (lrvb_glmm_ztnegbin_*): the (shifted) offset of `set_offset`, the dispersion of `set_dispersion` ----
     def set_dispersion(self, dispersion):
         """The per-row dispersion phi > 0 of the zero-truncated negative binomial mixed model, or None to clear it
-        (lrvb_set_dispersion) -- and the precision of the Beta one.  Only the `glmm_ztnegbin_*`, `glmm_beta_*` and `glmm_gamma_*` entries read it; the resident group sums are dropped."""
+        (lrvb_set_dispersion) -- and the precision of the Beta and the censored Gaussian one, the shape of the Gamma one.  Only the `glmm_ztnegbin_*`, `glmm_beta_*`, `glmm_gamma_*` and `glmm_censnormal_*` entries read it; the resident group sums are dropped."""
         if dispersion is None:
             self._check(self._lib.lrvb_set_dispersion(self._h, None, 0))
             return
@@ -751,6 +751,40 @@ class DeviceContext(object):
         """As `glmm_beta_dispersion_terms` for the Gamma model (lrvb_glmm_gamma_dispersion_terms), without nodes: d[0] = d[1] = the
         data term and the cross terms its gradient (the row term is linear in phi), formed by a kernel of their own."""
         return self._glmm_dispersion_terms(self._lib.lrvb_glmm_gamma_dispersion_terms, mean, var, e, r, (), (), nodes=False)
+
+    # ---- censored Gaussian mixed model (lrvb_glmm_censnormal_*): the raw offset, the precision of `set_dispersion`, the status of `set_censoring` ----
+    def set_censoring(self, status):
+        """The per-row status of the censored Gaussian mixed model, -1 (left-censored), 0 (observed) or +1 (right-censored), or None
+        to clear it (lrvb_set_censoring).  Only the `glmm_censnormal_*` entries read it; the resident group sums are dropped."""
+        if status is None:
+            self._check(self._lib.lrvb_set_censoring(self._h, None, 0))
+            return
+        st = np.ascontiguousarray(np.asarray(status).ravel(), dtype=np.int32)
+        self._check(self._lib.lrvb_set_censoring(self._h, st.ctypes.data, st.size))
+
+    def glmm_censnormal_terms(self, mean, var, e, r, gh_x, gh_w, want_grad=True, want_hess=True, want_border=True):
+        """Data term of the censored Gaussian mixed model with K effects per group, the offset of `set_offset`, the precision phi of
+        `set_dispersion` and the status of `set_censoring` (lrvb_glmm_censnormal_terms).  What `glmm_slopes_terms` returns, in its
+        layouts.  The group sums stay resident for `glmm_slopes_schur`.  A point at which a sum is not finite is a ValueError."""
+        return self._glmm_terms(self._lib.lrvb_glmm_censnormal_terms, True, True, mean, var, e, r, gh_x, gh_w, want_grad, want_hess, want_border)
+
+    def glmm_censnormal_obs_influence(self, mean, var, e, r, gh_x, gh_w, A, n0=0, n1=None):
+        """(n1 - n0) x Q rows of the censored Gaussian mixed model, as `glmm_slopes_obs_influence` (lrvb_glmm_censnormal_obs_influence)."""
+        return self._glmm_obs_influence(self._lib.lrvb_glmm_censnormal_obs_influence, True, True, mean, var, e, r, gh_x, gh_w, A, n0, n1)
+
+    def glmm_censnormal_group_influence(self, mean, var, e, r, gh_x, gh_w, A):
+        """G x Q group influence of the censored Gaussian mixed model, as `glmm_slopes_group_influence`
+        (lrvb_glmm_censnormal_group_influence)."""
+        return self._glmm_group_influence(self._lib.lrvb_glmm_censnormal_group_influence, True, True, mean, var, e, r, gh_x, gh_w, A)
+
+    def glmm_censnormal_dispersion_terms(self, mean, var, e, r, gh_x, gh_w):
+        """As `glmm_beta_dispersion_terms` for the censored Gaussian model (lrvb_glmm_censnormal_dispersion_terms): the derivatives in
+        the log-precision lambda, phi = e^lambda phi0."""
+        return self._glmm_dispersion_terms(self._lib.lrvb_glmm_censnormal_dispersion_terms, mean, var, e, r, gh_x, gh_w)
+
+    def glmm_censnormal_predict(self, mean, var, e, r, gh_x, gh_w, cov_beta, n0=0, n1=None, new=None):
+        """The latent mean of the censored Gaussian mixed model (lrvb_glmm_censnormal_predict); new rows carry an offset."""
+        return self._glmm_predict(self._lib.lrvb_glmm_censnormal_predict, True, 1, mean, var, e, r, gh_x, gh_w, cov_beta, n0, n1, new)
 
     # ---- multinomial (softmax) regression: beta is (K - 1) x n_cols, D = (K - 1) n_cols (lrvb_softmax_*) --------------------
     def softmax_set_labels(self, labels, n_classes):

@@ -11,20 +11,67 @@
 
 constexpr int GLMM_T = 64;               // sorted rows per tile, for every walk, glmm_fixup_kernel and glmm_num_tiles
 
-// ---- the likelihood policies -------------------------------------------------------------------------------------------------------
-// `kind` names one of the five coefficients: 0 = a1, 1 = a2, 2 = c11, 3 = c12, 4 = c22.
-struct LogisticLik {
-    struct Args { const double* gx; const double* gw; int nq; };         // Gauss-Hermite nodes and weights (device), 1 <= nq <= 128
-    struct Lds { double sx[128], sw[128]; };                             // sqrt(2) x_k, w_k / sqrt(pi)
-    struct Moments { double v, e1, e2, e3, e4; };
-    static constexpr const char* LIMITS = "logistic mixed model with slopes: P <= 64, 1 <= K <= 4, at most 128 nodes";
-    static bool args_ok(const Args& a) { return a.nq >= 1 && a.nq <= 128; }
+// ---- what the likelihood policies share ------------------------------------------------------------------------
+// Neither infl nor moments is handed its row: in every kernel the four lanes of staged row r are the threads 4 r .. 4 r + 3.
+__device__ __forceinline__ int gs_lane_row() { return (int)(threadIdx.x >> 2); }
+
+// The Gauss-Hermite walk of a row: the four lanes of a row share the nodes, lane q4 takes the nodes q4, q4 + 4, .. of the tables
+// q.sx, q.sw (LogisticLik::Lds) at t = rho + sqrt(max(s, 0)) x_k and hands (t, w_k) to f.  f accumulates in expressions of its
+// own -- its sums, and how they contract, belong to the policy.  A lane that is not `on` (a dead row of the tile; an observed row of
+// the censored policy) walks nothing and keeps its zeros.
+template <class Q, class F>
+__device__ __forceinline__ void gh_nodes(const Q& q, int nq, bool on, int q4, double rho, double s, F f)
+{
+    if (on) {
+        const double sd = sqrt(fmax(s, 0.0));
+        for (int k = q4; k < nq; k += 4) f(rho + sd * q.sx[k], q.sw[k]);
+    }
+}
+
+// The N accumulators of a lane summed over the four lanes of its row, on all four: two xor shuffles in fixed order, no atomics.
+// Stands outside every branch on the row's data, so that a quad never diverges around it.
+template <int N>
+__device__ __forceinline__ void gh_lane_sum(double* e)
+{
+#pragma unroll
+    for (int off = 1; off <= 2; off <<= 1)
+#pragma unroll
+        for (int i = 0; i < N; ++i) e[i] += __shfl_xor(e[i], off);
+}
+// the pair of an influence walk, which its caller holds in two variables
+__device__ __forceinline__ void gh_lane_sum(double& e1, double& e2)
+{
+    double e[2] = {e1, e2};
+    gh_lane_sum<2>(e);
+    e1 = e[0]; e2 = e[1];
+}
+
+// The two coefficient layouts.  `kind` names one of the five coefficients: 0 = a1, 1 = a2, 2 = c11, 3 = c12, 4 = c22.
+// Five rows, one per coefficient: every policy that integrates on the nodes.
+struct FiveRowLayout {
     static constexpr int NCF = 5, NB = 4, DK = 16;
     static constexpr bool HAS_FACTOR = false;
     static __device__ __forceinline__ int cf_row(int kind) { return kind; }
     static __device__ __forceinline__ double cf_factor(int) { return 1.0; }                      // HAS_FACTOR is false: no flush multiplies by it
     static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return b * Kz + k; }
     static __device__ __forceinline__ int d_stride(int) { return DK; }
+};
+// Two rows [a1 | h], every other coefficient a multiple cf_factor(kind) of h: the closed forms.  cf_factor is the policy's own.
+struct TwoRowLayout {
+    static constexpr int NCF = 2, NB = 2, DK = 8;
+    static constexpr bool HAS_FACTOR = true;
+    static __device__ __forceinline__ int cf_row(int kind) { return kind == 0 ? 0 : 1; }
+    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return (b & 1) * Kz + k; }
+    static __device__ __forceinline__ int d_stride(int Kz) { return 2 * Kz; }
+};
+
+// ---- the likelihood policies -------------------------------------------------------------------------------------------------------
+struct LogisticLik : FiveRowLayout {
+    struct Args { const double* gx; const double* gw; int nq; };         // Gauss-Hermite nodes and weights (device), 1 <= nq <= 128
+    struct Lds { double sx[128], sw[128]; };                             // sqrt(2) x_k, w_k / sqrt(pi)
+    struct Moments { double v, e1, e2, e3, e4; };
+    static constexpr const char* LIMITS = "logistic mixed model with slopes: P <= 64, 1 <= K <= 4, at most 128 nodes";
+    static bool args_ok(const Args& a) { return a.nq >= 1 && a.nq <= 128; }
 
     static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid)
     {
@@ -38,17 +85,12 @@ struct LogisticLik {
                                                 double& e2)
     {
         e1 = 0.0; e2 = 0.0;
-        if (live) {
-            const double sd = sqrt(fmax(s, 0.0));
-            for (int k = q4; k < a.nq; k += 4) {
-                const double t = rho + sd * L.sx[k], wk = L.sw[k];
-                const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
-                const double sg = t >= 0.0 ? ie : e * ie;
-                e1 += wk * sg; e2 += wk * e * ie * ie;
-            }
-        }
-        e1 += __shfl_xor(e1, 1); e2 += __shfl_xor(e2, 1);
-        e1 += __shfl_xor(e1, 2); e2 += __shfl_xor(e2, 2);
+        gh_nodes(L, a.nq, live, q4, rho, s, [&](double t, double wk) {
+            const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
+            const double sg = t >= 0.0 ? ie : e * ie;
+            e1 += wk * sg; e2 += wk * e * ie * ie;
+        });
+        gh_lane_sum(e1, e2);
     }
     // What the walk asks of a canonical likelihood: the influence kernels subtract y from e1, and the
     // response-scale mean of the predict walk is infl's e1.
@@ -60,26 +102,18 @@ struct LogisticLik {
     }
     static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
     {
-        double v = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0, e4 = 0.0;
-        if (live) {
-            const double sd = sqrt(fmax(s, 0.0));
-            for (int k = q4; k < a.nq; k += 4) {
-                const double t = rho + sd * L.sx[k], wk = L.sw[k];
-                const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
-                const double sp = (t > 0.0 ? t : 0.0) + log1p(e);
-                const double sg = t >= 0.0 ? ie : e * ie;
-                const double g2 = e * ie * ie;
-                const double om = (1.0 - e) * ie;                        // |1 - 2 sigma|
-                const double g3 = t >= 0.0 ? -g2 * om : g2 * om;
-                v += wk * sp; e1 += wk * sg; e2 += wk * g2; e3 += wk * g3; e4 += wk * g2 * (1.0 - 6.0 * g2);
-            }
-        }
-#pragma unroll
-        for (int off = 1; off <= 2; off <<= 1) {
-            v += __shfl_xor(v, off); e1 += __shfl_xor(e1, off); e2 += __shfl_xor(e2, off);
-            e3 += __shfl_xor(e3, off); e4 += __shfl_xor(e4, off);
-        }
-        return {v, e1, e2, e3, e4};
+        double m[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        gh_nodes(L, a.nq, live, q4, rho, s, [&](double t, double wk) {
+            const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
+            const double sp = (t > 0.0 ? t : 0.0) + log1p(e);
+            const double sg = t >= 0.0 ? ie : e * ie;
+            const double g2 = e * ie * ie;
+            const double om = (1.0 - e) * ie;                            // |1 - 2 sigma|
+            const double g3 = t >= 0.0 ? -g2 * om : g2 * om;
+            m[0] += wk * sp; m[1] += wk * sg; m[2] += wk * g2; m[3] += wk * g3; m[4] += wk * g2 * (1.0 - 6.0 * g2);
+        });
+        gh_lane_sum<5>(m);
+        return {m[0], m[1], m[2], m[3], m[4]};
     }
     static __device__ __forceinline__ double coefs(const Lds&, int, const Moments& mo, double wi, double yi, double rho, double,
                                                    double* k)
@@ -89,18 +123,27 @@ struct LogisticLik {
     }
 };
 
-struct PoissonLik {
+// A policy that integrates on LogisticLik's nodes next to staged per-row data: its Args and its Lds begin with the node tables `q`.
+struct NodeTableLik : FiveRowLayout {
+    typedef LogisticLik::Moments Moments;
+    template <class L, class A>
+    static __device__ __forceinline__ void init(L& l, const A& a, int tid) { LogisticLik::init(l.q, a.q, tid); }
+    // The coefficients of a likelihood that is not canonical, by Stein's identity from its finished moments (E H, E H', .. E H''''):
+    // no "- y rho" and no "- y", y sits inside H.  A canonical one delegates to LogisticLik::coefs.
+    static __device__ __forceinline__ double stein_coefs(const Moments& mo, double wi, double* k)
+    {
+        k[0] = wi * mo.e1; k[1] = wi * 0.5 * mo.e2; k[2] = wi * mo.e2; k[3] = wi * 0.5 * mo.e3; k[4] = wi * 0.25 * mo.e4;
+        return wi * mo.v;
+    }
+};
+
+struct PoissonLik : TwoRowLayout {
     typedef const double* __restrict__ Args;                             // the per-row offset (device, original row order) or nullptr
     struct Lds { double s_off[GLMM_T]; };                                  // the offsets of the tile's rows
     struct Moments {};
     static constexpr const char* LIMITS = "Poisson mixed model: P <= 64, 1 <= K <= 4";
     static bool args_ok(const Args&) { return true; }
-    static constexpr int NCF = 2, NB = 2, DK = 8;                        // coefficient rows [a1 | h]
-    static constexpr bool HAS_FACTOR = true;
-    static __device__ __forceinline__ int cf_row(int kind) { return kind == 0 ? 0 : 1; }
-    static __device__ __forceinline__ double cf_factor(int kind) { return kind == 4 ? 0.25 : ((kind & 1) ? 0.5 : 1.0); }
-    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return (b & 1) * Kz + k; }
-    static __device__ __forceinline__ int d_stride(int Kz) { return 2 * Kz; }
+    static __device__ __forceinline__ double cf_factor(int kind) { return kind == 4 ? 0.25 : ((kind & 1) ? 0.5 : 1.0); }   // rows [a1 | h]
 
     static __device__ __forceinline__ void init(Lds&, const Args&, int) {}
     static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
@@ -139,32 +182,22 @@ struct PoissonLik {
 // layout is the logistic one.  m = 1 and o = 0 (either pointer null, or the values themselves) give the logistic instantiation
 // bit for bit: x * 1.0 and x + 0.0 are exact, and the products with m are kept out of every fused multiply-add, so that the
 // sums behind them are contracted as LogisticLik's are.
-struct BinomialLik {
+struct BinomialLik : NodeTableLik {
     struct Args { LogisticLik::Args q; const double* __restrict__ off; const double* __restrict__ trials; };   // either may be nullptr
     struct Lds { LogisticLik::Lds q; double s_off[GLMM_T], s_m[GLMM_T]; };   // the node tables; the offsets and trials of the tile's rows
-    typedef LogisticLik::Moments Moments;
     static constexpr const char* LIMITS = "binomial mixed model: P <= 64, 1 <= K <= 4, at most 128 nodes";
     static bool args_ok(const Args& a) { return LogisticLik::args_ok(a.q); }
-    static constexpr int NCF = 5, NB = 4, DK = 16;
-    static constexpr bool HAS_FACTOR = false;
-    static __device__ __forceinline__ int cf_row(int kind) { return kind; }
-    static __device__ __forceinline__ double cf_factor(int) { return 1.0; }
-    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return b * Kz + k; }
-    static __device__ __forceinline__ int d_stride(int) { return DK; }
 
-    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { LogisticLik::init(L.q, a.q, tid); }
     static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
     {
         L.s_off[t] = (a.off && live) ? a.off[src] : 0.0;
         L.s_m[t] = (a.trials && live) ? a.trials[src] : 1.0;
     }
     static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_off[row]; }
-    // Neither infl nor moments is handed its row: in all three kernels the four lanes of staged row r are the threads 4 r .. 4 r + 3.
-    static __device__ __forceinline__ int lane_row() { return (int)(threadIdx.x >> 2); }
     static __device__ __forceinline__ void infl(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& e1,
                                                 double& e2)
     {
-        const double mt = L.s_m[lane_row()];
+        const double mt = L.s_m[gs_lane_row()];
         LogisticLik::infl(L.q, a.q, 0.0, live, q4, rho + o, s, e1, e2);
         {
 #pragma clang fp contract(off)
@@ -180,7 +213,7 @@ struct BinomialLik {
     }
     static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
     {
-        const int row = lane_row();
+        const int row = gs_lane_row();
         const double mt = L.s_m[row];
         Moments mo = LogisticLik::moments(L.q, a.q, live, q4, rho + L.s_off[row], s);
         {
@@ -213,27 +246,18 @@ struct BinomialLik {
 //            inf / inf.  h1 = -log(-expm1(-u)) up to u = log 2, -log1p(-exp(-u)) past it.  h0 = u EXACTLY integrable: E h0 and all its derivatives are exp(rho + s / 2), one
 //            exp per row as in PoissonLik and not clamped -- where it overflows the non-finite value reaches the sums and the
 //            entry refuses it.  Below t = -745 (u = 0) r is 0 / 0 and the row is refused in the same way.
-// The products with y and m - y are formed per lane ahead of the xor shuffles; the four lanes of a row share the nodes as
-// LogisticLik::moments does.  Fixed order, no atomics.
+// The products with y and m - y are formed per lane, inside the node function.
 constexpr int GLMM_LINK_LOGIT = 0, GLMM_LINK_PROBIT = 1, GLMM_LINK_CLOGLOG = 2;     // LRVB_LINK_* of the C ABI
 
 template <int LINK>
-struct BinomialLinkLik {
+struct BinomialLinkLik : NodeTableLik {
     static_assert(LINK == GLMM_LINK_PROBIT || LINK == GLMM_LINK_CLOGLOG, "the logit link is BinomialLik");
     struct Args { LogisticLik::Args q; const double* __restrict__ off; const double* __restrict__ trials; const double* __restrict__ y; };
     struct Lds { LogisticLik::Lds q; double s_off[GLMM_T], s_m[GLMM_T], s_y[GLMM_T]; };
-    typedef LogisticLik::Moments Moments;
     static constexpr const char* LIMITS = "binomial mixed model: P <= 64, 1 <= K <= 4, at most 128 nodes";
     static bool args_ok(const Args& a) { return LogisticLik::args_ok(a.q); }
-    static constexpr int NCF = 5, NB = 4, DK = 16;
-    static constexpr bool HAS_FACTOR = false;
     static constexpr bool MINUS_Y = false;
-    static __device__ __forceinline__ int cf_row(int kind) { return kind; }
-    static __device__ __forceinline__ double cf_factor(int) { return 1.0; }
-    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return b * Kz + k; }
-    static __device__ __forceinline__ int d_stride(int) { return DK; }
 
-    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { LogisticLik::init(L.q, a.q, tid); }
     static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
     {
         L.s_off[t] = (a.off && live) ? a.off[src] : 0.0;
@@ -241,7 +265,6 @@ struct BinomialLinkLik {
         L.s_y[t] = (a.y && live) ? a.y[src] : 0.0;
     }
     static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_off[row]; }
-    static __device__ __forceinline__ int lane_row() { return (int)(threadIdx.x >> 2); }
 
     // Probit, left tail: below t = PROBIT_CF_BELOW the sum d = t + lambda cancels to -1 / t and carries t^2 times the error of erfcx, and
     // 1 - w and w' behind it t^4 times.  There d comes from the continued fraction sqrt(2 / pi) / erfcx(x) = sqrt 2 (x + K(x)),
@@ -292,26 +315,21 @@ struct BinomialLinkLik {
     static __device__ __forceinline__ void infl(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& e1,
                                                 double& e2)
     {
-        const int row = lane_row();
+        const int row = gs_lane_row();
         const double yt = L.s_y[row], ft = L.s_m[row] - yt;
         rho += o;
         e1 = 0.0; e2 = 0.0;
-        if (live) {
-            const double sd = sqrt(fmax(s, 0.0));
-            for (int k = q4; k < a.q.nq; k += 4) {
-                const double t = rho + sd * L.q.sx[k], wk = L.q.sw[k];
-                double h[5];
-                h1<2>(t, h);
-                double g1 = yt * h[1], g2 = yt * h[2];
-                if constexpr (LINK == GLMM_LINK_PROBIT) {
-                    h1<2>(-t, h);
-                    g1 -= ft * h[1]; g2 += ft * h[2];
-                }
-                e1 += wk * g1; e2 += wk * g2;
+        gh_nodes(L.q, a.q.nq, live, q4, rho, s, [&](double t, double wk) {
+            double h[5];
+            h1<2>(t, h);
+            double g1 = yt * h[1], g2 = yt * h[2];
+            if constexpr (LINK == GLMM_LINK_PROBIT) {
+                h1<2>(-t, h);
+                g1 -= ft * h[1]; g2 += ft * h[2];
             }
-        }
-        e1 += __shfl_xor(e1, 1); e2 += __shfl_xor(e2, 1);
-        e1 += __shfl_xor(e1, 2); e2 += __shfl_xor(e2, 2);
+            e1 += wk * g1; e2 += wk * g2;
+        });
+        gh_lane_sum(e1, e2);
         if constexpr (LINK == GLMM_LINK_CLOGLOG) {
             const double eh = live ? ft * exp(rho + 0.5 * s) : 0.0;
             e1 += eh; e2 += eh;
@@ -320,48 +338,37 @@ struct BinomialLinkLik {
     // the response-scale mean m p: probit in closed form, E Phi(t) = Phi(rho / sqrt(1 + s)); cloglog on the nodes
     static __device__ __forceinline__ void mean(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& mu)
     {
-        const double mt = L.s_m[lane_row()];
+        const double mt = L.s_m[gs_lane_row()];
         rho += o;
         if constexpr (LINK == GLMM_LINK_PROBIT) {
             mu = live ? mt * (0.5 * erfc(-rho / sqrt(2.0 * (1.0 + fmax(s, 0.0))))) : 0.0;
         } else {
             double p = 0.0;
-            if (live) {
-                const double sd = sqrt(fmax(s, 0.0));
-                for (int k = q4; k < a.q.nq; k += 4) p += L.q.sw[k] * -expm1(-exp(rho + sd * L.q.sx[k]));
-            }
-            p += __shfl_xor(p, 1);
-            p += __shfl_xor(p, 2);
+            gh_nodes(L.q, a.q.nq, live, q4, rho, s, [&](double t, double wk) { p += wk * -expm1(-exp(t)); });
+            gh_lane_sum<1>(&p);
             mu = mt * p;
         }
     }
     static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
     {
-        const int row = lane_row();
+        const int row = gs_lane_row();
         const double yt = L.s_y[row], ft = L.s_m[row] - yt;
         rho += L.s_off[row];
         double e[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-        if (live) {
-            const double sd = sqrt(fmax(s, 0.0));
-            for (int k = q4; k < a.q.nq; k += 4) {
-                const double t = rho + sd * L.q.sx[k], wk = L.q.sw[k];
-                double h[5], g[5];
-                h1<5>(t, h);
+        gh_nodes(L.q, a.q.nq, live, q4, rho, s, [&](double t, double wk) {
+            double h[5], g[5];
+            h1<5>(t, h);
 #pragma unroll
-                for (int i = 0; i < 5; ++i) g[i] = yt * h[i];
-                if constexpr (LINK == GLMM_LINK_PROBIT) {
-                    h1<5>(-t, h);
+            for (int i = 0; i < 5; ++i) g[i] = yt * h[i];
+            if constexpr (LINK == GLMM_LINK_PROBIT) {
+                h1<5>(-t, h);
 #pragma unroll
-                    for (int i = 0; i < 5; ++i) g[i] += ft * ((i & 1) ? -h[i] : h[i]);
-                }
-#pragma unroll
-                for (int i = 0; i < 5; ++i) e[i] += wk * g[i];
+                for (int i = 0; i < 5; ++i) g[i] += ft * ((i & 1) ? -h[i] : h[i]);
             }
-        }
 #pragma unroll
-        for (int off = 1; off <= 2; off <<= 1)
-#pragma unroll
-            for (int i = 0; i < 5; ++i) e[i] += __shfl_xor(e[i], off);
+            for (int i = 0; i < 5; ++i) e[i] += wk * g[i];
+        });
+        gh_lane_sum<5>(e);
         if constexpr (LINK == GLMM_LINK_CLOGLOG) {
             const double eh = live ? ft * exp(rho + 0.5 * s) : 0.0;
 #pragma unroll
@@ -371,8 +378,7 @@ struct BinomialLinkLik {
     }
     static __device__ __forceinline__ double coefs(const Lds&, int, const Moments& mo, double wi, double, double, double, double* k)
     {
-        k[0] = wi * mo.e1; k[1] = wi * 0.5 * mo.e2; k[2] = wi * mo.e2; k[3] = wi * 0.5 * mo.e3; k[4] = wi * 0.25 * mo.e4;
-        return wi * mo.v;
+        return stein_coefs(mo, wi, k);
     }
 };
 
@@ -385,30 +391,21 @@ struct BinomialLinkLik {
 //   value = w (E A - y rho),  a1 = w (E A' - y),  a2 = w E A'' / 2,  c11 = w E A'',  c12 = w E A''' / 2,  c22 = w E A'''' / 4.
 // The e^t part of every E A^(k) is exp(rho + s / 2) EXACTLY: one exp per row, added behind the shuffles and not clamped -- where it
 // overflows the non-finite value reaches the sums and the entry refuses it, as for PoissonLik.  Only log(-expm1(-u)) and r^(k-1) go
-// on the nodes, which the four lanes of a row share as LogisticLik::moments does.  Past u = 700 (r < 1e-301) r is set to 0 and u
+// on the nodes.  Past u = 700 (r < 1e-301) r is set to 0 and u
 // to 700 in the polynomials, a select; below t = -745 (u = 0) r is 0 / 0 and the row is refused in the same way.  Nodes AND a
-// staged offset, no trials, and y from the walk (MINUS_Y): the response mean E A' is infl's e1.  Fixed order, no atomics.
-struct TruncPoissonLik {
+// staged offset, no trials, and y from the walk (MINUS_Y): the response mean E A' is infl's e1.
+struct TruncPoissonLik : NodeTableLik {
     struct Args { LogisticLik::Args q; const double* __restrict__ off; };                      // off may be nullptr
     struct Lds { LogisticLik::Lds q; double s_off[GLMM_T]; };               // the node tables; the offsets of the tile's rows
-    typedef LogisticLik::Moments Moments;
     static constexpr const char* LIMITS = "zero-truncated Poisson mixed model: P <= 64, 1 <= K <= 4, at most 128 nodes";
     static bool args_ok(const Args& a) { return LogisticLik::args_ok(a.q); }
-    static constexpr int NCF = 5, NB = 4, DK = 16;
-    static constexpr bool HAS_FACTOR = false;
     static constexpr bool MINUS_Y = true;
-    static __device__ __forceinline__ int cf_row(int kind) { return kind; }
-    static __device__ __forceinline__ double cf_factor(int) { return 1.0; }
-    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return b * Kz + k; }
-    static __device__ __forceinline__ int d_stride(int) { return DK; }
 
-    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { LogisticLik::init(L.q, a.q, tid); }
     static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
     {
         L.s_off[t] = (a.off && live) ? a.off[src] : 0.0;
     }
     static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_off[row]; }
-    static __device__ __forceinline__ int lane_row() { return (int)(threadIdx.x >> 2); }
 
     // The node parts of A' and A'' at t (N = 2), or of A .. A'''' (N = 5), into g[5 - N ..]: g[0] = log(-expm1(-u)), g[k] = r^(k-1)
     template <int N>
@@ -430,17 +427,12 @@ struct TruncPoissonLik {
     {
         rho += o;
         e1 = 0.0; e2 = 0.0;
-        if (live) {
-            const double sd = sqrt(fmax(s, 0.0));
-            for (int k = q4; k < a.q.nq; k += 4) {
-                const double t = rho + sd * L.q.sx[k], wk = L.q.sw[k];
-                double g[5];
-                node<2>(t, g);
-                e1 += wk * g[1]; e2 += wk * g[2];
-            }
-        }
-        e1 += __shfl_xor(e1, 1); e2 += __shfl_xor(e2, 1);
-        e1 += __shfl_xor(e1, 2); e2 += __shfl_xor(e2, 2);
+        gh_nodes(L.q, a.q.nq, live, q4, rho, s, [&](double t, double wk) {
+            double g[5];
+            node<2>(t, g);
+            e1 += wk * g[1]; e2 += wk * g[2];
+        });
+        gh_lane_sum(e1, e2);
         const double eu = live ? exp(rho + 0.5 * s) : 0.0;
         e1 += eu; e2 += eu;
     }
@@ -451,22 +443,15 @@ struct TruncPoissonLik {
     }
     static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
     {
-        rho += L.s_off[lane_row()];
+        rho += L.s_off[gs_lane_row()];
         double e[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-        if (live) {
-            const double sd = sqrt(fmax(s, 0.0));
-            for (int k = q4; k < a.q.nq; k += 4) {
-                const double t = rho + sd * L.q.sx[k], wk = L.q.sw[k];
-                double g[5];
-                node<5>(t, g);
+        gh_nodes(L.q, a.q.nq, live, q4, rho, s, [&](double t, double wk) {
+            double g[5];
+            node<5>(t, g);
 #pragma unroll
-                for (int i = 0; i < 5; ++i) e[i] += wk * g[i];
-            }
-        }
-#pragma unroll
-        for (int off = 1; off <= 2; off <<= 1)
-#pragma unroll
-            for (int i = 0; i < 5; ++i) e[i] += __shfl_xor(e[i], off);
+            for (int i = 0; i < 5; ++i) e[i] += wk * g[i];
+        });
+        gh_lane_sum<5>(e);
         const double eu = live ? exp(rho + 0.5 * s) : 0.0;
 #pragma unroll
         for (int i = 0; i < 5; ++i) e[i] += eu;
@@ -497,23 +482,14 @@ struct TruncPoissonLik {
 // clamp.  The response mean of the truncated count is E[mu / (1 - P0)] = E[e^t (1 + R(v))], e^t = phi e^eta: its e^t part is
 // phi exp(rho + s / 2) in closed form, one exp per row and not clamped; e^t R(v) goes on the nodes (-> 1 as t -> -inf, 0 by the
 // same select).  Nodes, offsets, phi and y are staged as BinomialLinkLik stages offset, trials and y (a null y -- the predict
-// walk -- stages zeros); the four lanes of a row share the nodes; five accumulators per lane, m sp^(k) + g^(k) per node, two xor
-// shuffles in fixed order, no atomics.
-struct TruncNegBinLik {
+// walk -- stages zeros); m sp^(k) + g^(k) per node.
+struct TruncNegBinLik : NodeTableLik {
     struct Args { LogisticLik::Args q; const double* __restrict__ off; const double* __restrict__ disp; const double* __restrict__ y; };   // off may be nullptr
     struct Lds { LogisticLik::Lds q; double s_off[GLMM_T], s_phi[GLMM_T], s_y[GLMM_T]; };
-    typedef LogisticLik::Moments Moments;
     static constexpr const char* LIMITS = "zero-truncated negative binomial mixed model: P <= 64, 1 <= K <= 4, at most 128 nodes";
     static bool args_ok(const Args& a) { return LogisticLik::args_ok(a.q) && a.disp != nullptr; }
-    static constexpr int NCF = 5, NB = 4, DK = 16;
-    static constexpr bool HAS_FACTOR = false;
     static constexpr bool MINUS_Y = true;
-    static __device__ __forceinline__ int cf_row(int kind) { return kind; }
-    static __device__ __forceinline__ double cf_factor(int) { return 1.0; }
-    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return b * Kz + k; }
-    static __device__ __forceinline__ int d_stride(int) { return DK; }
 
-    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { LogisticLik::init(L.q, a.q, tid); }
     static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
     {
         L.s_off[t] = (a.off && live) ? a.off[src] : 0.0;
@@ -521,7 +497,6 @@ struct TruncNegBinLik {
         L.s_y[t] = (a.y && live) ? a.y[src] : 0.0;
     }
     static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_off[row]; }
-    static __device__ __forceinline__ int lane_row() { return (int)(threadIdx.x >> 2); }
 
     // 1 / expm1(v), 0 past v = 700 by a select
     static __device__ __forceinline__ double recip_expm1(double v) { return v > 700.0 ? 0.0 : 1.0 / expm1(fmin(v, 700.0)); }
@@ -584,61 +559,44 @@ struct TruncNegBinLik {
     static __device__ __forceinline__ void infl(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& e1,
                                                 double& e2)
     {
-        const int row = lane_row();
+        const int row = gs_lane_row();
         const double phi = L.s_phi[row], mt = L.s_y[row] + phi;
         rho += o;
         e1 = 0.0; e2 = 0.0;
-        if (live) {
-            const double sd = sqrt(fmax(s, 0.0));
-            for (int k = q4; k < a.q.nq; k += 4) {
-                const double t = rho + sd * L.q.sx[k], wk = L.q.sw[k];
-                double h[5];
-                node<2>(t, phi, mt, h);
-                e1 += wk * h[1]; e2 += wk * h[2];
-            }
-        }
-        e1 += __shfl_xor(e1, 1); e2 += __shfl_xor(e2, 1);
-        e1 += __shfl_xor(e1, 2); e2 += __shfl_xor(e2, 2);
+        gh_nodes(L.q, a.q.nq, live, q4, rho, s, [&](double t, double wk) {
+            double h[5];
+            node<2>(t, phi, mt, h);
+            e1 += wk * h[1]; e2 += wk * h[2];
+        });
+        gh_lane_sum(e1, e2);
     }
     // the response mean of the truncated count: phi exp(rho + s / 2) in closed form plus E[e^t R(v)] on the nodes
     static __device__ __forceinline__ void mean(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& mu)
     {
-        const double phi = L.s_phi[lane_row()];
+        const double phi = L.s_phi[gs_lane_row()];
         rho += o;
         double p = 0.0;
-        if (live) {
-            const double sd = sqrt(fmax(s, 0.0));
-            for (int k = q4; k < a.q.nq; k += 4) {
-                const double t = rho + sd * L.q.sx[k];
-                const double e = exp(-fabs(t));
-                const double v = phi * ((t > 0.0 ? t : 0.0) + log1p(e));
-                p += L.q.sw[k] * (v > 700.0 ? 0.0 : phi * exp(t) * recip_expm1(v));
-            }
-        }
-        p += __shfl_xor(p, 1);
-        p += __shfl_xor(p, 2);
+        gh_nodes(L.q, a.q.nq, live, q4, rho, s, [&](double t, double wk) {
+            const double e = exp(-fabs(t));
+            const double v = phi * ((t > 0.0 ? t : 0.0) + log1p(e));
+            p += wk * (v > 700.0 ? 0.0 : phi * exp(t) * recip_expm1(v));
+        });
+        gh_lane_sum<1>(&p);
         mu = live ? phi * exp(rho + 0.5 * s) + p : 0.0;
     }
     static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
     {
-        const int row = lane_row();
+        const int row = gs_lane_row();
         const double phi = L.s_phi[row], mt = L.s_y[row] + phi;
         rho += L.s_off[row];
         double e[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-        if (live) {
-            const double sd = sqrt(fmax(s, 0.0));
-            for (int k = q4; k < a.q.nq; k += 4) {
-                const double t = rho + sd * L.q.sx[k], wk = L.q.sw[k];
-                double h[5];
-                node<5>(t, phi, mt, h);
+        gh_nodes(L.q, a.q.nq, live, q4, rho, s, [&](double t, double wk) {
+            double h[5];
+            node<5>(t, phi, mt, h);
 #pragma unroll
-                for (int i = 0; i < 5; ++i) e[i] += wk * h[i];
-            }
-        }
-#pragma unroll
-        for (int off = 1; off <= 2; off <<= 1)
-#pragma unroll
-            for (int i = 0; i < 5; ++i) e[i] += __shfl_xor(e[i], off);
+            for (int i = 0; i < 5; ++i) e[i] += wk * h[i];
+        });
+        gh_lane_sum<5>(e);
         return {e[0], e[1], e[2], e[3], e[4]};
     }
     static __device__ __forceinline__ double coefs(const Lds& L, int row, const Moments& mo, double wi, double yi, double rho, double s,
@@ -665,22 +623,14 @@ struct TruncNegBinLik {
 // the shuffles (E of a constant).  NO finite point is refused: as |t| grows e underflows to 0, the arguments become 1 and 1 + phi
 // and h grows like |t| -- unlike the Poisson-type policies there is no exp of t that could overflow.  The response mean is
 // E sigma(t), the logistic one, whatever phi.  Nodes, offsets, phi and l are staged as TruncNegBinLik stages offset, dispersion and
-// y; the four lanes of a row share the nodes; five accumulators per lane, two xor shuffles in fixed order, no atomics.
-struct BetaLik {
+// y.
+struct BetaLik : NodeTableLik {
     struct Args { LogisticLik::Args q; const double* __restrict__ off; const double* __restrict__ disp; const double* __restrict__ y; };   // off may be nullptr; y holds logit(y)
     struct Lds { LogisticLik::Lds q; double s_off[GLMM_T], s_phi[GLMM_T], s_y[GLMM_T]; };
-    typedef LogisticLik::Moments Moments;
     static constexpr const char* LIMITS = "Beta mixed model: P <= 64, 1 <= K <= 4, at most 128 nodes";
     static bool args_ok(const Args& a) { return LogisticLik::args_ok(a.q) && a.disp != nullptr; }
-    static constexpr int NCF = 5, NB = 4, DK = 16;
-    static constexpr bool HAS_FACTOR = false;
     static constexpr bool MINUS_Y = false;
-    static __device__ __forceinline__ int cf_row(int kind) { return kind; }
-    static __device__ __forceinline__ double cf_factor(int) { return 1.0; }
-    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return b * Kz + k; }
-    static __device__ __forceinline__ int d_stride(int) { return DK; }
 
-    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { LogisticLik::init(L.q, a.q, tid); }
     static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
     {
         L.s_off[t] = (a.off && live) ? a.off[src] : 0.0;
@@ -688,7 +638,6 @@ struct BetaLik {
         L.s_y[t] = (a.y && live) ? a.y[src] : 0.0;
     }
     static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_off[row]; }
-    static __device__ __forceinline__ int lane_row() { return (int)(threadIdx.x >> 2); }
 
     // lgamma (N = 5 only), psi, psi' (p[1], p[2]) and psi'', psi''' (N = 5: p[3], p[4]) at x >= 1: nine unrolled steps of the
     // recurrence f(x) = f(x + 1) + .. wherever x is still below 10 -- selects, no data-dependent trip count and no indexed
@@ -758,21 +707,16 @@ struct BetaLik {
     static __device__ __forceinline__ void infl(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& e1,
                                                 double& e2)
     {
-        const int row = lane_row();
+        const int row = gs_lane_row();
         const double phi = L.s_phi[row], l = L.s_y[row];
         rho += o;
         e1 = 0.0; e2 = 0.0;
-        if (live) {
-            const double sd = sqrt(fmax(s, 0.0));
-            for (int k = q4; k < a.q.nq; k += 4) {
-                const double t = rho + sd * L.q.sx[k], wk = L.q.sw[k];
-                double h[5];
-                node<2>(t, phi, l, h);
-                e1 += wk * h[1]; e2 += wk * h[2];
-            }
-        }
-        e1 += __shfl_xor(e1, 1); e2 += __shfl_xor(e2, 1);
-        e1 += __shfl_xor(e1, 2); e2 += __shfl_xor(e2, 2);
+        gh_nodes(L.q, a.q.nq, live, q4, rho, s, [&](double t, double wk) {
+            double h[5];
+            node<2>(t, phi, l, h);
+            e1 += wk * h[1]; e2 += wk * h[2];
+        });
+        gh_lane_sum(e1, e2);
     }
     // the response mean E sigma(t) does not depend on phi: the logistic quadrature at rho + o
     static __device__ __forceinline__ void mean(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& mu)
@@ -782,30 +726,22 @@ struct BetaLik {
     }
     static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
     {
-        const int row = lane_row();
+        const int row = gs_lane_row();
         const double phi = L.s_phi[row], l = L.s_y[row];
         rho += L.s_off[row];
         double e[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-        if (live) {
-            const double sd = sqrt(fmax(s, 0.0));
-            for (int k = q4; k < a.q.nq; k += 4) {
-                const double t = rho + sd * L.q.sx[k], wk = L.q.sw[k];
-                double h[5];
-                node<5>(t, phi, l, h);
+        gh_nodes(L.q, a.q.nq, live, q4, rho, s, [&](double t, double wk) {
+            double h[5];
+            node<5>(t, phi, l, h);
 #pragma unroll
-                for (int i = 0; i < 5; ++i) e[i] += wk * h[i];
-            }
-        }
-#pragma unroll
-        for (int off = 1; off <= 2; off <<= 1)
-#pragma unroll
-            for (int i = 0; i < 5; ++i) e[i] += __shfl_xor(e[i], off);
+            for (int i = 0; i < 5; ++i) e[i] += wk * h[i];
+        });
+        gh_lane_sum<5>(e);
         return {live ? e[0] - 2.0 * log(phi) : 0.0, e[1], e[2], e[3], e[4]};
     }
     static __device__ __forceinline__ double coefs(const Lds&, int, const Moments& mo, double wi, double, double, double, double* k)
     {
-        k[0] = wi * mo.e1; k[1] = wi * 0.5 * mo.e2; k[2] = wi * mo.e2; k[3] = wi * 0.5 * mo.e3; k[4] = wi * 0.25 * mo.e4;
-        return wi * mo.v;
+        return stein_coefs(mo, wi, k);
     }
 };
 
@@ -823,19 +759,14 @@ struct BetaLik {
 // refuses the point, as for PoissonLik; where g underflows to 0 the row's term is phi rho, a legitimate point.  The response mean
 // E e^t = exp(rho + s / 2) does not depend on phi: the Poisson predict walk serves this model, and `mean` is PoissonLik's formula.
 // Offsets, phi and log y are staged as BetaLik stages offset, precision and logit y.  No shuffles, no atomics.
-struct GammaLik {
+struct GammaLik : TwoRowLayout {
     struct Args { const double* __restrict__ off; const double* __restrict__ disp; const double* __restrict__ y; };   // off may be nullptr; y holds log(y)
     struct Lds { double s_off[GLMM_T], s_phi[GLMM_T], s_y[GLMM_T]; };
     struct Moments {};
     static constexpr const char* LIMITS = "Gamma mixed model: P <= 64, 1 <= K <= 4";
     static bool args_ok(const Args& a) { return a.disp != nullptr && a.y != nullptr; }
-    static constexpr int NCF = 2, NB = 2, DK = 8;                        // coefficient rows [a1 | g]
-    static constexpr bool HAS_FACTOR = true;
     static constexpr bool MINUS_Y = false;
-    static __device__ __forceinline__ int cf_row(int kind) { return kind == 0 ? 0 : 1; }
-    static __device__ __forceinline__ double cf_factor(int kind) { return kind == 4 ? 0.25 : (kind == 3 ? -0.5 : (kind == 1 ? 0.5 : 1.0)); }
-    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return (b & 1) * Kz + k; }
-    static __device__ __forceinline__ int d_stride(int Kz) { return 2 * Kz; }
+    static __device__ __forceinline__ double cf_factor(int kind) { return kind == 4 ? 0.25 : (kind == 3 ? -0.5 : (kind == 1 ? 0.5 : 1.0)); }   // rows [a1 | g]
 
     static __device__ __forceinline__ void init(Lds&, const Args&, int) {}
     static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
@@ -845,14 +776,13 @@ struct GammaLik {
         L.s_y[t] = live ? a.y[src] : 0.0;
     }
     static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_off[row]; }
-    static __device__ __forceinline__ int lane_row() { return (int)(threadIdx.x >> 2); }
     // g = phi exp((log y - rho) + s / 2) at rho INCLUDING the offset
     static __device__ __forceinline__ double g_of(double phi, double ly, double rho, double s) { return phi * exp((ly - rho) + 0.5 * s); }
     // e1 = a1' = phi - g whole and e2 = E h'' = g, on all four lanes of a row
     static __device__ __forceinline__ void infl(const Lds& L, const Args&, double o, bool live, int, double rho, double s, double& e1,
                                                 double& e2)
     {
-        const int row = lane_row();
+        const int row = gs_lane_row();
         const double phi = L.s_phi[row];
         const double g = live ? g_of(phi, L.s_y[row], rho + o, s) : 0.0;
         e1 = live ? phi - g : 0.0; e2 = g;
@@ -884,29 +814,21 @@ struct GammaLik {
 // addition, a shift of y and o by a common constant leaves d -- and with it every result -- unchanged wherever the shifted values are
 // exact, and the predict walk, which has no y (a null y stages zeros), reads d = o: `mean` is rho + d.  y, phi and delta are read
 // from the ORIGINAL row index, as every staged array; a null status is "every row observed".  Coefficients in the logistic five-row
-// layout as BinomialLinkLik forms them (MINUS_Y false: y sits inside u).  The four lanes of a row share the nodes and share the
-// row's status, so a quad never diverges; the shuffles stand outside the branch and run in fixed order; no atomics.  The powers of
+// layout as BinomialLinkLik forms them (MINUS_Y false: y sits inside u).  The four lanes of a row share the
+// row's status, so a quad never diverges; gh_lane_sum stands outside the branch.  The powers of
 // delta r multiply the FINISHED sums, outside every fused multiply-add: with sqrt(phi) a power of two an all-censored data set is
 // the probit model on the design (r x, r z) with the offset r (o - y) to the last bit of a, and sum_k w_k H^(j)(a_k) is formed as the
 // probit policy forms it.  No clamp: an observed row overflows with phi u^2, a censored one with a^2 / 2 in the left tail; the
 // non-finite value reaches the sums and the entry refuses the point.
-struct CensNormalLik {
+struct CensNormalLik : NodeTableLik {
     typedef BinomialLinkLik<GLMM_LINK_PROBIT> Probit;
     struct Args { LogisticLik::Args q; const double* __restrict__ off; const double* __restrict__ disp; const double* __restrict__ y;
                   const double* __restrict__ cens; };                       // off, y (predict) and cens (all observed) may be nullptr
     struct Lds { LogisticLik::Lds q; double s_d[GLMM_T], s_phi[GLMM_T], s_st[GLMM_T]; };     // o - y, phi, delta as a double
-    typedef LogisticLik::Moments Moments;
     static constexpr const char* LIMITS = "censored Gaussian mixed model: P <= 64, 1 <= K <= 4, at most 128 nodes";
     static bool args_ok(const Args& a) { return LogisticLik::args_ok(a.q) && a.disp != nullptr && a.y != nullptr; }
-    static constexpr int NCF = 5, NB = 4, DK = 16;
-    static constexpr bool HAS_FACTOR = false;
     static constexpr bool MINUS_Y = false;
-    static __device__ __forceinline__ int cf_row(int kind) { return kind; }
-    static __device__ __forceinline__ double cf_factor(int) { return 1.0; }
-    static __device__ __forceinline__ int o_d(int b, int k, int Kz) { return b * Kz + k; }
-    static __device__ __forceinline__ int d_stride(int) { return DK; }
 
-    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { LogisticLik::init(L.q, a.q, tid); }
     static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
     {
         const double o = (a.off && live) ? a.off[src] : 0.0;
@@ -916,18 +838,17 @@ struct CensNormalLik {
         L.s_st[t] = (a.cens && live) ? a.cens[src] : 0.0;
     }
     static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_d[row]; }
-    static __device__ __forceinline__ int lane_row() { return (int)(threadIdx.x >> 2); }
 
     // a1' = E h' and E h'' = 2 a2' per unit weight, on all four lanes of a row; o is the staged fold o - y
     static __device__ __forceinline__ void infl(const Lds& L, const Args& a, double o, bool live, int q4, double rho, double s, double& e1,
                                                 double& e2)
     {
-        const int row = lane_row();
+        const int row = gs_lane_row();
         const double phi = L.s_phi[row], st = L.s_st[row];
         const double u = rho + o;
         const bool cens = live && st != 0.0;
         e1 = 0.0; e2 = 0.0;
-        if (cens) {
+        if (cens) {                                                      // the walk in its own text: see `moments`
             const double dr = st * sqrt(phi), sd = sqrt(fmax(s, 0.0));
             for (int k = q4; k < a.q.nq; k += 4) {
                 const double tu = u + sd * L.q.sx[k], wk = L.q.sw[k];
@@ -940,8 +861,7 @@ struct CensNormalLik {
                 e1 += wk * h[1]; e2 += wk * h[2];
             }
         }
-        e1 += __shfl_xor(e1, 1); e2 += __shfl_xor(e2, 1);
-        e1 += __shfl_xor(e1, 2); e2 += __shfl_xor(e2, 2);
+        gh_lane_sum(e1, e2);
         {
 #pragma clang fp contract(off)
             if (cens) { e1 = e1 * (st * sqrt(phi)); e2 = e2 * phi; }
@@ -955,11 +875,14 @@ struct CensNormalLik {
     }
     static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
     {
-        const int row = lane_row();
+        const int row = gs_lane_row();
         const double phi = L.s_phi[row], st = L.s_st[row];
         const double u = rho + L.s_d[row];
         const bool cens = live && st != 0.0;
         double e[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        // The walks of this policy and of CensNormalDispLik stand in their own text, not as calls of gh_nodes: through the helper
+        // glmm_slopes_rows_kernel<CensNormalLik> measured 3 to 5 % slower at K = 4, outside the margin of DESIGN.md section 46, and
+        // with delta r formed ahead of the helper every observed row paid its square root (2 % of the dispersion walk).
         if (cens) {
             const double dr = st * sqrt(phi), sd = sqrt(fmax(s, 0.0));
             for (int k = q4; k < a.q.nq; k += 4) {
@@ -974,10 +897,7 @@ struct CensNormalLik {
                 for (int i = 0; i < 5; ++i) e[i] += wk * h[i];
             }
         }
-#pragma unroll
-        for (int off = 1; off <= 2; off <<= 1)
-#pragma unroll
-            for (int i = 0; i < 5; ++i) e[i] += __shfl_xor(e[i], off);
+        gh_lane_sum<5>(e);
         {
 #pragma clang fp contract(off)
             if (cens) {
@@ -992,8 +912,7 @@ struct CensNormalLik {
     }
     static __device__ __forceinline__ double coefs(const Lds&, int, const Moments& mo, double wi, double, double, double, double* k)
     {
-        k[0] = wi * mo.e1; k[1] = wi * 0.5 * mo.e2; k[2] = wi * mo.e2; k[3] = wi * 0.5 * mo.e3; k[4] = wi * 0.25 * mo.e4;
-        return wi * mo.v;
+        return stein_coefs(mo, wi, k);
     }
 };
 
@@ -1002,8 +921,7 @@ struct CensNormalLik {
 // lambda at fixed t, d/d lambda = phi d/d phi.  A policy of this kind serves glmm_disp_rows_kernel (k_glmm_slopes.hip) and supplies
 // the staging of its base policy and ONE function
 //   dmoments(lik, la, live, q4, rho, s) -> (E h_l, E d_t h_l, E d_t^2 h_l, E h_ll) per unit weight, t ~ N(rho + offset, s),
-// on all four lanes of a row: the nodes shared as LogisticLik::moments shares them, four accumulators per lane, two xor shuffles in
-// fixed order, no atomics.  By Stein's identity E d_t h_l is the derivative of E h_l in rho and E d_t^2 h_l / 2 the one in s: the two
+// on all four lanes of a row, by gh_nodes and gh_lane_sum<4>.  By Stein's identity E d_t h_l is the derivative of E h_l in rho and E d_t^2 h_l / 2 the one in s: the two
 // coefficient rows of the cross Hessian d^2 F / d theta d lambda.
 struct DispMoments { double hl, t1, t2, hll; };
 
@@ -1023,41 +941,33 @@ struct BetaDispLik {
     static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { BetaLik::init(L, a, tid); }
     static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src) { BetaLik::stage_row(L, a, t, live, src); }
     static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return BetaLik::row_shift(L, row); }
-    static __device__ __forceinline__ int lane_row() { return BetaLik::lane_row(); }
 
     static __device__ __forceinline__ DispMoments dmoments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
     {
-        const int row = lane_row();
+        const int row = gs_lane_row();
         const double phi = L.s_phi[row], l = L.s_y[row];
         rho += L.s_off[row];
-        double e0 = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0;
-        if (live) {
-            const double sd = sqrt(fmax(s, 0.0));
-            for (int k = q4; k < a.q.nq; k += 4) {
-                const double t = rho + sd * L.q.sx[k], wk = L.q.sw[k];
-                const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
-                const bool pos = t >= 0.0;
-                const double mu = pos ? ie : e * ie, nu = pos ? e * ie : ie;  // sigma(t) and sigma(-t)
-                const double g2 = e * ie * ie;                               // v = mu (1 - mu)
-                const double om = (1.0 - e) * ie;
-                const double d = pos ? -om : om;                             // 1 - 2 mu
-                const double pa_ = phi * mu, pb_ = phi * nu;
-                double pa[5], pb[5];
-                BetaLik::polygamma<5>(1.0 + pa_, pa);
-                BetaLik::polygamma<5>(1.0 + pb_, pb);
-                const double first = pa_ * pa[1] + pb_ * pb[1] - l * pa_;    // h_l + 2
-                const double ta = pa_ * pa[2], tb = pb_ * pb[2];             // a psi'(1 + a), b psi'(1 + b)
-                const double K1 = phi * (((pa[1] + ta) - (pb[1] + tb)) - l);
-                const double K2 = phi * phi * ((2.0 * pa[2] + pa_ * pa[3]) + (2.0 * pb[2] + pb_ * pb[3]));
-                const double K1v = K1 * g2;
-                e0 += wk * first; e1 += wk * K1v; e2 += wk * (K2 * g2 * g2 + K1v * d); e3 += wk * (first + pa_ * ta + pb_ * tb);
-            }
-        }
-#pragma unroll
-        for (int off = 1; off <= 2; off <<= 1) {
-            e0 += __shfl_xor(e0, off); e1 += __shfl_xor(e1, off); e2 += __shfl_xor(e2, off); e3 += __shfl_xor(e3, off);
-        }
-        return {live ? e0 - 2.0 : 0.0, e1, e2, e3};
+        double m[4] = {0.0, 0.0, 0.0, 0.0};
+        gh_nodes(L.q, a.q.nq, live, q4, rho, s, [&](double t, double wk) {
+            const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
+            const bool pos = t >= 0.0;
+            const double mu = pos ? ie : e * ie, nu = pos ? e * ie : ie;      // sigma(t) and sigma(-t)
+            const double g2 = e * ie * ie;                                   // v = mu (1 - mu)
+            const double om = (1.0 - e) * ie;
+            const double d = pos ? -om : om;                                 // 1 - 2 mu
+            const double pa_ = phi * mu, pb_ = phi * nu;
+            double pa[5], pb[5];
+            BetaLik::polygamma<5>(1.0 + pa_, pa);
+            BetaLik::polygamma<5>(1.0 + pb_, pb);
+            const double first = pa_ * pa[1] + pb_ * pb[1] - l * pa_;        // h_l + 2
+            const double ta = pa_ * pa[2], tb = pb_ * pb[2];                 // a psi'(1 + a), b psi'(1 + b)
+            const double K1 = phi * (((pa[1] + ta) - (pb[1] + tb)) - l);
+            const double K2 = phi * phi * ((2.0 * pa[2] + pa_ * pa[3]) + (2.0 * pb[2] + pb_ * pb[3]));
+            const double K1v = K1 * g2;
+            m[0] += wk * first; m[1] += wk * K1v; m[2] += wk * (K2 * g2 * g2 + K1v * d); m[3] += wk * (first + pa_ * ta + pb_ * tb);
+        });
+        gh_lane_sum<4>(m);
+        return {live ? m[0] - 2.0 : 0.0, m[1], m[2], m[3]};
     }
 };
 
@@ -1082,33 +992,25 @@ struct NegBinDispLik {
         L.s_y[t] = live ? a.y[src] : 0.0;
     }
     static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return L.s_off[row]; }
-    static __device__ __forceinline__ int lane_row() { return (int)(threadIdx.x >> 2); }
 
     static __device__ __forceinline__ DispMoments dmoments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
     {
-        const int row = lane_row();
+        const int row = gs_lane_row();
         const double phi = L.s_phi[row], mt = L.s_m[row], yt = L.s_y[row];
         rho += L.s_off[row];
-        double v = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0;
-        if (live) {
-            const double sd = sqrt(fmax(s, 0.0));
-            for (int k = q4; k < a.q.nq; k += 4) {
-                const double t = rho + sd * L.q.sx[k], wk = L.q.sw[k];
-                const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
-                const double sp = (t > 0.0 ? t : 0.0) + log1p(e);
-                const double sg = t >= 0.0 ? ie : e * ie;
-                const double g2 = e * ie * ie;
-                const double om = (1.0 - e) * ie;                        // |1 - 2 sigma|
-                const double g3 = t >= 0.0 ? -g2 * om : g2 * om;
-                v += wk * sp; e1 += wk * sg; e2 += wk * g2; e3 += wk * g3;
-            }
-        }
-#pragma unroll
-        for (int off = 1; off <= 2; off <<= 1) {
-            v += __shfl_xor(v, off); e1 += __shfl_xor(e1, off); e2 += __shfl_xor(e2, off); e3 += __shfl_xor(e3, off);
-        }
+        double m[4] = {0.0, 0.0, 0.0, 0.0};                                  // E sp, E sg, E g2, E g3
+        gh_nodes(L.q, a.q.nq, live, q4, rho, s, [&](double t, double wk) {
+            const double e = exp(-fabs(t)), ie = 1.0 / (1.0 + e);
+            const double sp = (t > 0.0 ? t : 0.0) + log1p(e);
+            const double sg = t >= 0.0 ? ie : e * ie;
+            const double g2 = e * ie * ie;
+            const double om = (1.0 - e) * ie;                            // |1 - 2 sigma|
+            const double g3 = t >= 0.0 ? -g2 * om : g2 * om;
+            m[0] += wk * sp; m[1] += wk * sg; m[2] += wk * g2; m[3] += wk * g3;
+        });
+        gh_lane_sum<4>(m);
         if (!live) return {0.0, 0.0, 0.0, 0.0};
-        return {(phi * v - mt * e1) + yt, phi * e1 - mt * e2, phi * e2 - mt * e3, phi * (v - 2.0 * e1) + mt * e2};
+        return {(phi * m[0] - mt * m[1]) + yt, phi * m[1] - mt * m[2], phi * m[2] - mt * m[3], phi * (m[0] - 2.0 * m[1]) + mt * m[2]};
     }
 };
 
@@ -1123,12 +1025,11 @@ struct GammaDispLik {
     static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { GammaLik::init(L, a, tid); }
     static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src) { GammaLik::stage_row(L, a, t, live, src); }
     static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return GammaLik::row_shift(L, row); }
-    static __device__ __forceinline__ int lane_row() { return GammaLik::lane_row(); }
 
     static __device__ __forceinline__ DispMoments dmoments(const Lds& L, const Args&, bool live, int, double rho, double s)
     {
         if (!live) return {0.0, 0.0, 0.0, 0.0};
-        const int row = lane_row();
+        const int row = gs_lane_row();
         const double phi = L.s_phi[row];
         rho += L.s_off[row];
         const double g = GammaLik::g_of(phi, L.s_y[row], rho, s);
@@ -1151,16 +1052,15 @@ struct CensNormalDispLik {
     static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid) { CensNormalLik::init(L, a, tid); }
     static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src) { CensNormalLik::stage_row(L, a, t, live, src); }
     static __device__ __forceinline__ double row_shift(const Lds& L, int row) { return CensNormalLik::row_shift(L, row); }
-    static __device__ __forceinline__ int lane_row() { return CensNormalLik::lane_row(); }
 
     static __device__ __forceinline__ DispMoments dmoments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
     {
-        const int row = lane_row();
+        const int row = gs_lane_row();
         const double phi = L.s_phi[row], st = L.s_st[row];
         const double u = rho + L.s_d[row];
         const bool cens = live && st != 0.0;
-        double e0 = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0;
-        if (cens) {
+        double m[4] = {0.0, 0.0, 0.0, 0.0};
+        if (cens) {                                                      // the walk in its own text: see CensNormalLik::moments
             const double dr = st * sqrt(phi), sd = sqrt(fmax(s, 0.0));
             for (int k = q4; k < a.q.nq; k += 4) {
                 const double tu = u + sd * L.q.sx[k], wk = L.q.sw[k];
@@ -1171,14 +1071,11 @@ struct CensNormalDispLik {
                 }
                 CensNormalLik::Probit::h1<5>(av, h);
                 const double b1 = av * h[2] + h[1];                          // a H'' + H'
-                e0 += wk * (av * h[1]); e1 += wk * b1; e2 += wk * (av * h[3] + 2.0 * h[2]); e3 += wk * (av * b1);
+                m[0] += wk * (av * h[1]); m[1] += wk * b1; m[2] += wk * (av * h[3] + 2.0 * h[2]); m[3] += wk * (av * b1);
             }
         }
-#pragma unroll
-        for (int off = 1; off <= 2; off <<= 1) {
-            e0 += __shfl_xor(e0, off); e1 += __shfl_xor(e1, off); e2 += __shfl_xor(e2, off); e3 += __shfl_xor(e3, off);
-        }
-        if (cens) return {0.5 * e0, (0.5 * (st * sqrt(phi))) * e1, (0.5 * phi) * e2, 0.25 * e3};
+        gh_lane_sum<4>(m);
+        if (cens) return {0.5 * m[0], (0.5 * (st * sqrt(phi))) * m[1], (0.5 * phi) * m[2], 0.25 * m[3]};
         if (!live) return {0.0, 0.0, 0.0, 0.0};
         double eh;
         {

@@ -422,3 +422,141 @@ def test_recorded_predictions_agree_with_the_dense_inverse(sfixture, case):
                         continue
                     own = float(abs(mpmath.mpf(float(a)) - ex) / abs(ex))
                     assert abs(d - a) <= max(8.0 * own, 16.0 * U53) * abs(a)
+
+
+# ---- tests/golden/glmm_policies_parent.npz: the likelihood policies behind the shared node loop ------------
+import torch                                                             # noqa: E402
+
+P_IDS = [c['name'] for c in mg.POLICY_CASES]
+TERMS_FAMILIES = [f for f in mg.POLICY_FAMILIES if f.get('terms', True)]
+
+
+@pytest.fixture(scope='module')
+def pfixture():
+    with np.load(mg.POLICY_FIXTURE) as f:
+        return {k: f[k] for k in f.files}
+
+
+def test_policy_fixture_names_its_parent_and_is_complete(pfixture):
+    assert os.path.getsize(mg.POLICY_FIXTURE) < 1024 * 1024
+    assert re.fullmatch(r'[0-9a-f]{40}', str(pfixture['parent_commit']))
+    assert 'HIP version' in str(pfixture['hipcc_version'])
+    assert [f['name'] for f in TERMS_FAMILIES] == ['binomial', 'probit', 'cloglog', 'ztpoisson', 'ztnegbin', 'beta', 'gamma', 'censnormal']
+    assert [f['name'] for f in mg.POLICY_FAMILIES if f.get('predict')] == ['binomial', 'probit', 'cloglog', 'ztpoisson', 'ztnegbin', 'censnormal']
+    assert [f['name'] for f in mg.POLICY_FAMILIES if f.get('dispersion')] == ['beta', 'gamma', 'censnormal', 'negbin']
+    for case in mg.POLICY_CASES:
+        N, P, K, G = case['shape']
+        n0, n1 = mg.window(N)
+        for fam in mg.POLICY_FAMILIES:
+            head = '%s/%s/' % (case['name'], fam['name'])
+            for name in mg.policy_outputs(fam):
+                key = head + name
+                raw = key in pfixture
+                assert raw != (key + ':sha256' in pfixture and key + ':shape' in pfixture), key
+                if raw:
+                    assert pfixture[key].size <= mg.RAW_MAX and np.all(np.isfinite(pfixture[key]))
+                else:
+                    assert np.prod(pfixture[key + ':shape']) > mg.RAW_MAX
+            if fam.get('terms', True):
+                assert pfixture[head + 'value'].tobytes() == pfixture[head + 'value_only'].tobytes()
+                assert pfixture[head + 'grad'].shape == (2 * P,)
+                assert pfixture[head + 'scalar_columns'].shape == (G, 2 * K + K * (2 * K + 1))
+            if fam.get('predict'):
+                assert pfixture[head + 'predict_window'].shape == (5, n1 - n0) and pfixture[head + 'predict_new'].shape == (5, mg.N_NEW)
+            if fam.get('dispersion'):
+                assert pfixture[head + 'dispersion_d'].shape == (2,) and pfixture[head + 'dispersion_cross_global'].shape == (2 * P,)
+                assert pfixture[head + 'dispersion_cross_local'].shape == (G, 2 * K)
+    assert len(pfixture) == 2 + len(mg.POLICY_CASES) + sum(
+        (1 if '%s/%s/%s' % (c['name'], f['name'], o) in pfixture else 2)
+        for c in mg.POLICY_CASES for f in mg.POLICY_FAMILIES for o in mg.policy_outputs(f))
+
+
+@pytest.mark.parametrize('case', mg.POLICY_CASES, ids=P_IDS)
+def test_policy_cases_rebuild_from_their_seeds(pfixture, case):
+    a, b = mg.build_policy_case(case), mg.build_policy_case(case)
+    assert mg.policy_inputs_digest(a) == mg.policy_inputs_digest(b) == str(pfixture[case['name'] + ':inputs'])
+
+
+def test_policy_cases_are_the_witnesses_they_are_meant_to_be():
+    built = {c['name']: (c, mg.build_policy_case(c)) for c in mg.POLICY_CASES}
+    assert [(c['shape'], c['deg']) for c in mg.POLICY_CASES] == [((1, 1, 1, 1), 1), ((65, 5, 2, 3), 5), ((37, 3, 1, 5), 128), ((130, 64, 4, 2), 20)]
+    owned = lambda deg: [len(range(q4, deg, 4)) for q4 in range(4)]     # the nodes of the four lanes of a row
+    assert owned(1) == [1, 0, 0, 0] and owned(5) == [2, 1, 1, 1] and owned(128) == [32] * 4 and mg.GLMM_TILE - 1 == 63
+    assert built['one_node'][1]['fam']['censnormal']['censoring'][0] != 0                  # the single row is censored
+    c, b = built['cut_group']
+    s = np.bincount(b['gid'], minlength=3)                               # group 1 is cut by the boundary at row 64; group 2 is empty
+    assert 0 < s[0] < 64 < s[0] + s[1] == 65 and s[2] == 0 and np.sum(b['w'] == 0.0) >= 3
+    c, b = built['all_columns']
+    assert tuple(np.bincount(b['gid'], minlength=2)) == (30, 100) and c['shape'][1] == 64
+    for name, (c, b) in built.items():
+        f = b['fam']
+        assert np.any(f['binomial']['trials'] != 1.0) or c['shape'][0] == 1
+        assert np.all(f['ztpoisson']['y'] >= 1.0) and np.all(f['ztnegbin']['y'] >= 1.0) and np.all(f['gamma']['y'] > 0.0)
+        assert np.all((f['beta']['y'] > 0.0) & (f['beta']['y'] < 1.0)) and np.any(b['o'] != 0.0)
+        cov = mg.policy_coverage(c, b)
+        if c['shape'][0] >= 64:                                          # statuses -1, 0, +1 as neighbours inside one tile
+            assert cov['statuses_mixed']
+    assert built['cut_group'][0]['deg'] == 5 and all(mg.policy_coverage(*built['cut_group']).values())   # every branch on nodes of weight >= 0.011
+    assert all(mg.coverage_of_all_cases().values())
+    assert np.any(built['cut_group'][1]['new']['groups'] == -1)
+
+
+import contextlib                                                        # noqa: E402
+
+
+@contextlib.contextmanager
+def _reference_nodes(r, deg):
+    """The binomial reference reads its node count from the module and the link reference binds it as a default, in the forward
+    pass and again in the backward one: both are set to the case's for as long as the reference is evaluated AND differentiated."""
+    keep = r['bref'].GH_DEG, r['lref'].expected_dk
+    r['bref'].GH_DEG = deg
+    r['lref'].expected_dk = lambda link, which, mu, s, k: keep[1](link, which, mu, s, k, deg)
+    try:
+        yield
+    finally:
+        r['bref'].GH_DEG, r['lref'].expected_dk = keep
+
+
+def _policy_reference(r, case, b, name):
+    """eta -> the data term of the family by its torch reference, at the case's number of nodes (inside `_reference_nodes`)."""
+    N, P, K, G = case['shape']
+    x, z, w, o, gid, deg, d = b['x'], b['z'], b['w'], b['o'], b['gid'], b['deg'], b['fam'][name]
+    if name == 'binomial':
+        ta = r['bref'].targs(x, d['y'], z, w, o, d['trials'], gid, G)
+        return lambda eta: r['bref'].kl_vec(eta, *ta) - r['bref']._priors(eta, ta[0], ta[1], ta[2], ta[3], ta[6], G, ta[8])
+    if name in ('probit', 'cloglog'):
+        ta = r['lref'].targs(x, d['y'], z, w, o, d['trials'], gid, G, name)
+        return lambda eta: r['lref'].data(eta, *ta[:8], name)
+    if name == 'ztpoisson':
+        ta = r['ztp'].targs(x, d['y'], z, w, o, gid, G)
+        return lambda eta: r['ztp'].data(eta, *ta[:7], deg)
+    if name == 'censnormal':
+        ta = r['cens'].targs(x, d['y'], z, w, o, d['dispersion'], gid, G, d['censoring'])
+        return lambda eta: r['cens'].data(eta, *ta[:8], ta[9], deg)
+    mod = r[{'ztnegbin': 'ztnb', 'beta': 'beta', 'gamma': 'gamma'}[name]]
+    ta = mod.targs(x, d['y'], z, w, o, d['dispersion'], gid, G)
+    return lambda eta: mod.data(eta, *ta[:8], mod.GH_DEG if name == 'gamma' else deg)
+
+
+@pytest.mark.parametrize('case', mg.POLICY_CASES, ids=P_IDS)
+def test_recorded_policy_values_and_gradients_agree_with_the_references(pfixture, case):
+    """Value 1e-11 and gradients 1e-10 relative, the tolerances of `_check_against_reference` (tests/test_gpu_glmm_binomial.py) that
+    the `test_reference_parity` of every one of these families runs.  The gradient of the reference is taken in eta by autograd and
+    moved to the coordinates of the entry: v = 1 / i_beta and r = 1 / i, so d/dv = -i^2 d/di."""
+    N, P, K, G = case['shape']
+    b = mg.build_policy_case(case)
+    eta, ng, GK = b['eta'], 2 * P + 4 * K, G * K
+    r = mg._policy_refs()
+    for fam in TERMS_FAMILIES:
+        t = torch.tensor(eta, requires_grad=True)
+        with _reference_nodes(r, b['deg']):
+            val = _policy_reference(r, case, b, fam['name'])(t)
+            g = torch.autograd.grad(val, t)[0].numpy()
+        val = float(val.detach())
+        g_glob = np.concatenate([g[:P], -eta[P:2 * P] ** 2 * g[P:2 * P]])
+        g_loc = np.concatenate([g[ng:ng + GK].reshape(G, K), (-eta[ng + GK:] ** 2 * g[ng + GK:]).reshape(G, K)], axis=1)
+        head = '%s/%s/' % (case['name'], fam['name'])
+        e = [abs(float(pfixture[head + 'value'][0]) - val) / abs(val), rel_err(pfixture[head + 'grad'], g_glob),
+             rel_err(pfixture[head + 'scalar_columns'][:, :2 * K], g_loc)]
+        print(case['name'], fam['name'], e)
+        assert e[0] < 1e-11 and e[1] < 1e-10 and e[2] < 1e-10

@@ -851,6 +851,56 @@ int lrvb_glmm_censnormal_dispersion_terms(lrvb_ctx* ctx, const double* mean, con
                                           const double* r, int64_t G, int64_t K, const double* gh_x, const double* gh_w,
                                           int32_t n_nodes, double* d_out, double* cross_global_out, double* cross_local_out);
 
+/* ---- ordinal mixed model, cumulative logit link, K <= 4 independent random effects per group --------------
+ *   y_n in {0 .. T},  P(y_n <= j | t_n) = sigma(alpha_{j+1} - t_n),  t_n = o_n + x_n . beta + z_n . u_g(n),
+ * with T cut points alpha_1 < .. < alpha_T (2 <= T + 1 <= 16 ordered categories).  The offset is the RAW one of lrvb_set_offset and the
+ * context's y (LRVB_SLOT_Y) holds the categories as doubles.
+ * lrvb_set_thresholds: T finite, strictly increasing values, 1 <= T <= 15, kept with both sentinels -inf and +inf in one device
+ * table of 17 doubles; replaced by the next call, which touches nothing of length n_obs.  Only the lrvb_glmm_ordinal_* entries read
+ * it.  The call drops the resident group sums, the factor and the group covariance.  A null pointer, a T outside 1 .. 15, a value that
+ * is not finite or not above the one before it: LRVB_ERR_INVALID, checked on the host ahead of everything else (the state is left as
+ * it was).                                                                                                                       */
+int lrvb_set_thresholds(lrvb_ctx* ctx, const double* alpha, int64_t T);
+/* Data term.  With lo = alpha_y, hi = alpha_{y+1} (alpha_0 = -inf, alpha_{T+1} = +inf), D = hi - lo, t ~ N(rho_n, s_n),
+ * rho_n = offset_n + x_n . mean + z_n . e_g(n) and s_n as in lrvb_glmm_slopes_terms, the row term is
+ *   h(t) = -log[sigma(hi - t) - sigma(lo - t)] = softplus(t - hi) + softplus(lo - t) - log(1 - e^-D)
+ * whole (nothing is dropped: the last term depends on the thresholds), the two softplus terms on the caller's Gauss-Hermite nodes with
+ * the expressions of the logistic entries, the third in closed form per row;
+ *   value = sum_n w_n E h,  a1 = w E h',  a2 = w E h'' / 2,  c11 = w E h'',  c12 = w E h''' / 2,  c22 = w E h'''' / 4
+ * in the five-row layout, the scratch sizes and the summation order of the logistic entries.  The kernel does not clamp values: one
+ * that is not finite after the reduction: LRVB_ERR_INVALID, the other outputs are then unspecified and no sums stay resident.
+ * Arguments, outputs, the column layout of group_sums_out, want_border, the fixed summation order (two calls at one point are bitwise
+ * equal) and the reduce-hook contract are those of lrvb_glmm_slopes_terms; the group sums stay resident for lrvb_glmm_slopes_schur,
+ * the two solves and lrvb_glmm_slopes_group_cov.  The entries read neither trials, link, dispersion nor censoring status.  No
+ * thresholds set: LRVB_ERR_STATE.  A y that is not an integer in 0 .. T: LRVB_ERR_INVALID, found on the host before any kernel over
+ * the rows is launched (y is read back once per lrvb_set_data and T; the kernels clamp the table index besides).  The other errors
+ * are those of lrvb_glmm_ztpoisson_terms.                                                                                        */
+int lrvb_glmm_ordinal_terms(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                            int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes, double* value_out,
+                            double* grad_global_out, double* H_blocks_out, double* group_sums_out, int32_t want_border);
+/* Streamed weight influence of that model: lrvb_glmm_slopes_obs_influence with, per unit weight, a1' = E h' (there is no "- y":
+ * the response picks the cut points) and a2' = E h'' / 2.  Errors as lrvb_glmm_ordinal_terms, and n0 > n1 or n1 > n_obs:
+ * LRVB_ERR_INVALID.                                                                                                              */
+int lrvb_glmm_ordinal_obs_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                                    int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
+                                    const double* A_global, const double* A_local, int64_t Q, int64_t n0, int64_t n1, double* out);
+/* Group influence of that model, as lrvb_glmm_ztpoisson_group_influence.  Errors as lrvb_glmm_ordinal_obs_influence.             */
+int lrvb_glmm_ordinal_group_influence(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                                      int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes,
+                                      const double* A_global, const double* A_local, int64_t Q, double* out);
+/* The derivatives of that data term in the thresholds alpha at fixed (mean, var, e, r): one pass over the rows, which forms its
+ * products with x and z itself (a row touches two of the T thresholds).  With r = 1 / expm1(D), c = e^-D / expm1(-D)^2 (0 on an end
+ * category) a row adds, times w, -E sigma(t - hi) - r to g[hi], E sigma(lo - t) + r to g[lo], E sigma'(t - hi) + c and
+ * E sigma'(lo - t) + c to the diagonal and -c to the off-diagonal entry of (lo, hi): the Hessian in alpha is tridiagonal.
+ *   g_out (T), h_diag_out (T), h_off_out (T - 1: entry j couples alpha_j+1 and alpha_j+2; untouched where T = 1),
+ *   cross_global_out (T x 2 P, row j = [d/d mean | d/d var] of g[j]),  cross_local_out (G x T x 2 K, [d/d e | d/d r] of g[j]).
+ * Fixed summation order for a given n_obs, no atomics: two calls at one point are bitwise equal.  Reads the state of
+ * lrvb_glmm_ordinal_terms; writes NEITHER the resident group sums NOR the factor NOR the group covariance and drops none of them.
+ * A sum that is not finite: LRVB_ERR_INVALID.  The other errors as lrvb_glmm_ordinal_terms.                                      */
+int lrvb_glmm_ordinal_threshold_terms(lrvb_ctx* ctx, const double* mean, const double* var, int64_t P, const double* e, const double* r,
+                                      int64_t G, int64_t K, const double* gh_x, const double* gh_w, int32_t n_nodes, double* g_out,
+                                      double* h_diag_out, double* h_off_out, double* cross_global_out, double* cross_local_out);
+
 /* ---- group blocks of H^-1, fitted values and predictions with their linear-response variance ------------
  * For every mixed model with K <= 4 effects per group.  After a successful lrvb_glmm_slopes_schur (the factor L_g, U_g resident)
  * and a factored free Schur complement S on the caller's side, with

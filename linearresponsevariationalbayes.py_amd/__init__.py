@@ -57,6 +57,7 @@ from .glmm_hurdle import (TruncatedPoissonGLMMObjective, HurdlePoissonGLMM, Trun
 from .glmm_beta import BetaGLMMObjective
 from .glmm_gamma import GammaGLMMObjective, HurdleGammaGLMM
 from .glmm_censored import CensoredNormalGLMMObjective
+from .glmm_ordinal import OrdinalGLMMObjective
 from .torch_closure import TorchObjective
 from . import regression as regression_utils
 from . import packing as ProjectionParams

@@ -136,6 +136,11 @@ _SIGNATURES = {
     'lrvb_glmm_censnormal_group_influence': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, c_i64, _VP],
     'lrvb_glmm_censnormal_dispersion_terms': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, _VP],
     'lrvb_glmm_censnormal_predict': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, ctypes.c_int32, _VP, c_i64, c_i64, _VP, _VP, _VP, _VP, c_i64, _VP],
+    'lrvb_set_thresholds': [_VP, _VP, c_i64],
+    'lrvb_glmm_ordinal_terms': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, _VP, _VP, ctypes.c_int32],
+    'lrvb_glmm_ordinal_obs_influence': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, c_i64, c_i64, c_i64, _VP],
+    'lrvb_glmm_ordinal_group_influence': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, c_i64, _VP],
+    'lrvb_glmm_ordinal_threshold_terms': [_VP, _VP, _VP, c_i64, _VP, _VP, c_i64, c_i64, _VP, _VP, ctypes.c_int32, _VP, _VP, _VP, _VP, _VP],
     'lrvb_softmax_set_labels': [_VP, _VP, c_i64, ctypes.c_int32],
     'lrvb_softmax_terms': [_VP, _VP, c_i64, c_i64, _VP, _VP, _VP, c_i64],
     'lrvb_softmax_hvp': [_VP, _VP, c_i64, c_i64, _VP, _VP],

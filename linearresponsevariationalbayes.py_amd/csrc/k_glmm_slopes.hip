@@ -8,6 +8,7 @@
 //   Beta:  0 < y_n < 1,  y_n ~ Beta(mu_n phi_n, (1 - mu_n) phi_n),  mu_n = sigma(o_n + x_n . beta + z_n . u_g(n))
 //   Gamma:  y_n > 0,  y_n ~ Gamma(shape phi_n, mean exp(o_n + x_n . beta + z_n . u_g(n)))
 //   censored Gaussian:  y*_n ~ N(o_n + x_n . beta + z_n . u_g(n), 1 / phi_n), observed, left- or right-censored at y_n
+//   ordinal, cumulative logit:  P(y_n <= j) = sigma(alpha_j+1 - o_n - x_n . beta - z_n . u_g(n)),  y_n in {0 .. T}
 // Per observation rho_n = x_n . m + z_n . e_g, s_n = (x_n o x_n) . v + (z_n o z_n) . r_g and five coefficients a1, a2, c11, c12, c22.
 // Every kernel that walks the rows is written ONCE, as a template over a likelihood policy (k_glmm_walk.h, DESIGN.md sections 27 and
 // 31): LogisticLik (the quadrature k_glmm.hip runs too; with K = 1 and z = 1 this is that model) and PoissonLik
@@ -212,6 +213,7 @@ static int gs_with_lik(const GlmmLik& lik, F&& f) {
     if (lik.kind == GLMM_BETA) return f(BetaLik(), BetaLik::Args{q, lik.off, lik.trials, lik.y});
     if (lik.kind == GLMM_GAMMA) return f(GammaLik(), GammaLik::Args{lik.off, lik.trials, lik.y});
     if (lik.kind == GLMM_CENSNORMAL) return f(CensNormalLik(), CensNormalLik::Args{q, lik.off, lik.trials, lik.y, lik.cens});
+    if (lik.kind == GLMM_ORDINAL) return f(OrdinalLik(), OrdinalLik::Args{q, lik.off, lik.y, lik.thr, lik.T});
     if (lik.kind == GLMM_BINOMIAL && lik.link == GLMM_LINK_PROBIT)
         return f(BinomialLinkLik<GLMM_LINK_PROBIT>(), BinomialLinkLik<GLMM_LINK_PROBIT>::Args{q, lik.off, lik.trials, lik.y});
     if (lik.kind == GLMM_BINOMIAL && lik.link == GLMM_LINK_CLOGLOG)
@@ -369,6 +371,165 @@ int launch_glmm_disp_rows(lrvb_ctx* c, const GlmmLik& lik, const double* disp, i
     if (lik.kind == GLMM_BINOMIAL && lik.link == GLMM_LINK_LOGIT)
         return gs_launch_disp<NegBinDispLik>(c, Kz, NegBinDispLik::Args{q, lik.off, lik.trials, disp, lik.y}, m, vb, eg, rg, coef, NP, gsum, part, vpart);
     LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "the dispersion derivative is that of the Beta, the Gamma, the censored Gaussian and the negative binomial mixed model");
+}
+
+// ---- the derivatives in the thresholds of the ordinal model (lrvb_glmm_ordinal_threshold_terms) -------------
+// ONE pass over the rows in group-sorted order on the head of glmm_disp_rows_kernel: the same tiles, the same staging, four lanes per
+// row for rho and s by the same dot products, then OrdinalLik::thr_moments: E sigma, E sigma', E sigma'' at t - hi and at lo - t.
+// A row of category y touches TWO of the T thresholds, its hi (index y, where y < T) and its lo (index y - 1, where y >= 1).  With
+// r = 1 / expm1(D) and c = e^-D / expm1(-D)^2 (both 0 at the sentinel D = +inf of an end category) the row holds, times its weight,
+//   g_hi = -E sigma(t - hi) - r,  g_lo = E sigma(lo - t) + r,  H_hi,hi = E sigma'(t - hi) + c,  H_lo,lo = E sigma'(lo - t) + c,  H_lo,hi = -c,
+//   d1_hi = -E sigma'(t - hi),  d2_hi = -E sigma''(t - hi) / 2,  d1_lo = -E sigma'(lo - t),  d2_lo = +E sigma''(lo - t) / 2
+// (d1 the derivative in rho of the row's threshold gradient, d2 the one in s, by Stein's identity).  Unlike a scalar dispersion there is
+// no coefficient VECTOR per threshold to hand to the library's products: the products with x are formed here.
+//   cross_global  T x 2 P accumulators per workgroup in LDS, [sum d1 x | sum d2 x o x] per threshold.  Thread c < 2 P owns column c of
+//                 all T rows: it walks the tile's rows in order and adds to the rows of the two thresholds the row touches -- the
+//                 threads of a wave write consecutive words of ONE accumulator row, whichever row the data picks.  The accumulators
+//                 persist over the workgroup's tiles; each workgroup writes one block, glmm_thr_finish_kernel adds them in block order.
+//   cross_local   per group the T x 2 K segmented sums [sum d1 z | sum d2 z o z], thread 128 + u owning column u = j 2 K + c, flushed
+//                 at every change of group through gs_flush_dst at ncol = 2 K T, the partial rows added by glmm_fixup_kernel.
+//   g, H          per tile 3 T partial scalars (g | H diagonal | H off-diagonal, the last slot of the third unused), thread q < 3 T
+//                 summing the tile's rows in order; vpart[q n_tiles + tile], finished in tile order by sum_partials_kernel.
+// No atomics: every sum has a fixed order for a given grid, bitwise reproducible.  A row of weight zero contributes exact zeros.
+__global__ __launch_bounds__(256)
+void glmm_thr_rows_kernel(i64 N, int P, int Kz, i64 G, const double* __restrict__ X, const double* __restrict__ Z,
+                          const double* __restrict__ w, const i64* __restrict__ perm, const i64* __restrict__ offs,
+                          const double* __restrict__ m, const double* __restrict__ vb, const double* __restrict__ eg,
+                          const double* __restrict__ rg, OrdinalLik::Args la, double* __restrict__ gsum, double* __restrict__ part,
+                          double* __restrict__ vpart, double* __restrict__ cpart)
+{
+    __shared__ double xs[GLMM_T * GS_XS], rv[9 * GLMM_T], acc[OrdinalLik::MAX_T * 128], ms[64], vs[64];
+    __shared__ OrdinalLik::Lds lik;
+    __shared__ i64 s_row[GLMM_T];
+    __shared__ int s_gid[GLMM_T], s_whole[GLMM_T];
+    const int tid = threadIdx.x;
+    const int T = la.T, P2 = 2 * P, K2 = 2 * Kz, ncl = K2 * T;
+    OrdinalLik::init(lik, la, tid);
+    if (tid < P) { ms[tid] = m[tid]; vs[tid] = vb[tid]; }
+    for (int e = tid; e < T * P2; e += 256) acc[e] = 0.0;
+    const i64 n_tiles = (N + GLMM_T - 1) / GLMM_T;
+    const int row = tid >> 2, q4 = tid & 3;
+    // thread c < 2 P: column c of cross_global (x_c for c < P, x_{c-P}^2 behind them)
+    const bool g_col = tid < P2, g_sq = tid >= P;
+    const int g_x = g_sq ? tid - P : tid;
+    // thread 128 + u, u < 2 K T: column u = j 2 K + c of cross_local (z_c for c < K, z_{c-K}^2 behind them)
+    const int lu = tid - 128;
+    const bool l_col = lu >= 0 && lu < ncl;
+    const int l_j = l_col ? lu / K2 : 0, l_c = l_col ? lu - l_j * K2 : 0;
+    const bool l_sq = l_c >= Kz;
+    const int l_z = P + (l_sq ? l_c - Kz : l_c);
+    // thread q < 3 T: scalar slot q = b T + j
+    const int s_b = tid / T, s_j = tid - s_b * T;
+    for (i64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const i64 t0 = tile * GLMM_T;
+        const int rows = (int)(N - t0 < GLMM_T ? N - t0 : GLMM_T);
+        __syncthreads();                                                 // the previous tile is consumed (and the nodes, the table, m, v are in place)
+        gs_stage_sorted_tile<OrdinalLik, GS_XS>(tid, t0, rows, P, Kz, G, X, Z, perm, offs, la, lik, xs, s_row, s_gid, s_whole);
+        double rho = 0.0, s = 0.0;
+        if (row < rows) {
+            const double* xr = xs + row * GS_XS;
+            for (int j = q4; j < P; j += 4) { const double x = xr[j]; rho += x * ms[j]; s += x * x * vs[j]; }
+            if (q4 < Kz) {
+                const i64 gk = (i64)s_gid[row] * Kz + q4;
+                const double z = xr[P + q4];
+                rho += z * eg[gk]; s += z * z * rg[gk];
+            }
+        }
+        rho += __shfl_xor(rho, 1); s += __shfl_xor(s, 1);
+        rho += __shfl_xor(rho, 2); s += __shfl_xor(s, 2);
+        const OrdinalLik::ThrMoments mo = OrdinalLik::thr_moments(lik, la, row < rows, q4, rho, s);
+        if (q4 == 0) {
+            double v[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            if (row < rows) {
+                const double wi = w[s_row[row]];
+                const double D = OrdinalLik::row_delta(lik, row);         // +inf on an end category: r = c = 0
+                const double em = exp(-D), dm = expm1(-D);
+                const double r = 1.0 / expm1(D), c = em / (dm * dm);      // in e^-D: e^D overflows at D = 710
+                v[0] = -(wi * mo.a1); v[1] = -(wi * 0.5 * mo.a2); v[2] = -(wi * mo.b1); v[3] = wi * 0.5 * mo.b2;
+                v[4] = wi * (-mo.a0 - r); v[5] = wi * (mo.b0 + r); v[6] = wi * (mo.a1 + c); v[7] = wi * (mo.b1 + c); v[8] = -(wi * c);
+            }
+#pragma unroll
+            for (int i = 0; i < 9; ++i) rv[i * GLMM_T + row] = v[i];
+        }
+        __syncthreads();
+        if (g_col) {
+            const double* dh = rv + (g_sq ? 1 : 0) * GLMM_T;
+            const double* dl = rv + (g_sq ? 3 : 2) * GLMM_T;
+            for (int rr = 0; rr < rows; ++rr) {
+                double x = xs[rr * GS_XS + g_x];
+                if (g_sq) x *= x;
+                const int j = lik.s_cat[rr];                              // in [0, T]: clamped where it was staged
+                if (j < T) acc[j * P2 + tid] += dh[rr] * x;
+                if (j >= 1) acc[(j - 1) * P2 + tid] += dl[rr] * x;
+            }
+        } else if (l_col) {
+            const double* dh = rv + (l_sq ? 1 : 0) * GLMM_T;
+            const double* dl = rv + (l_sq ? 3 : 2) * GLMM_T;
+            double a = 0.0;
+            int run_start = 0;
+            for (int rr = 0; rr < rows; ++rr) {
+                double z = xs[rr * GS_XS + l_z];
+                if (l_sq) z *= z;
+                const int j = lik.s_cat[rr];
+                if (j == l_j) a += dh[rr] * z;
+                if (j == l_j + 1) a += dl[rr] * z;
+                const int g = s_gid[rr];
+                if (rr == rows - 1 || s_gid[rr + 1] != g) {
+                    gs_flush_dst(s_whole[rr], g, tile, run_start, ncl, gsum, part)[lu] = a;
+                    a = 0.0; run_start = rr + 1;
+                }
+            }
+        }
+        if (tid < 3 * T) {
+            const double* vh = rv + (s_b == 0 ? 4 : 6) * GLMM_T;
+            const double* vl = rv + (s_b == 0 ? 5 : 7) * GLMM_T;
+            const double* vo = rv + 8 * GLMM_T;
+            double a = 0.0;
+            for (int rr = 0; rr < rows; ++rr) {
+                const int j = lik.s_cat[rr];
+                if (s_b < 2) {
+                    if (j == s_j) a += vh[rr];
+                    if (j == s_j + 1) a += vl[rr];
+                } else if (j == s_j + 1 && j < T) a += vo[rr];           // the pair (alpha_j, alpha_j+1) of an interior category
+            }
+            vpart[(i64)tid * n_tiles + tile] = a;
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < T * P2; e += 256) cpart[(i64)blockIdx.x * (T * P2) + e] = acc[e];
+}
+
+// out[i] = sum over the nblk workgroup blocks, in block order
+__global__ __launch_bounds__(256)
+void glmm_thr_finish_kernel(int nblk, int n, const double* __restrict__ cpart, double* __restrict__ out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double a = 0.0;
+    for (int b = 0; b < nblk; ++b) a += cpart[(i64)b * n + i];
+    out[i] = a;
+}
+
+unsigned glmm_thr_grid(i64 N) { return glmm_grid(N); }
+
+// `lik` is the ordinal likelihood on the device (nodes, offset, y, the table); gsum G x 2 K T (zeroed by the caller), part 2 x 2 K T
+// per tile, vpart 3 T per tile, cpart T x 2 P per workgroup of glmm_thr_grid(N), cross T x 2 P.
+int launch_glmm_thr_rows(lrvb_ctx* c, const GlmmLik& lik, int Kz, const double* m, const double* vb, const double* eg, const double* rg,
+                         double* gsum, double* part, double* vpart, double* cpart, double* cross) {
+    const i64 N = c->N, G = c->n_groups;
+    const OrdinalLik::Args la{{lik.gx, lik.gw, lik.n_nodes}, lik.off, lik.y, lik.thr, lik.T};
+    if (lik.kind != GLMM_ORDINAL || c->P > 64 || Kz < 1 || Kz > 4 || !OrdinalLik::args_ok(la)) LRVB_FAIL(LRVB_ERR_UNSUPPORTED, "%s", OrdinalLik::LIMITS);
+    const i64* gdev = reinterpret_cast<const i64*>(c->groups.p);
+    const unsigned grid = glmm_thr_grid(N);
+    const int ncl = 2 * Kz * lik.T, ncg = lik.T * 2 * (int)c->P;
+    hipLaunchKernelGGL(glmm_thr_rows_kernel, dim3(grid), dim3(256), 0, c->stream, N, (int)c->P, Kz, G, (const double*)c->X.p, (const double*)c->gz.p,
+                       (const double*)c->w.p, gdev, gdev + N, m, vb, eg, rg, la, gsum, part, vpart, cpart);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(glmm_fixup_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, G, ncl, gdev + N, (const double*)part, gsum);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(glmm_thr_finish_kernel, dim3((unsigned)((ncg + 255) / 256)), dim3(256), 0, c->stream, (int)grid, ncg, (const double*)cpart, cross);
+    HIP_TRY(hipGetLastError());
+    return LRVB_OK;
 }
 
 // A = L L^T of one local block from its upper triangle a (row-major), L row-major into Ls; false where a pivot is not positive
@@ -860,6 +1021,18 @@ void glmm_censnormal_infl_rows_kernel(i64 n0, i64 R, int P, int Kz, const double
     gsi_infl_rows<CensNormalLik>(n0, R, P, Kz, X, Z, y, gid, m, vb, eg, rg, {{gx, gw, nq}, off, disp, y, cens}, Ag, Al, Q, out);
 }
 
+// The ordinal model: the offset, the categories (y) and the table of T + 2 cut points behind Z.
+__global__ __launch_bounds__(256)
+void glmm_ordinal_infl_rows_kernel(i64 n0, i64 R, int P, int Kz, const double* __restrict__ X, const double* __restrict__ Z,
+                                   const double* __restrict__ off, const double* __restrict__ y, const double* __restrict__ thr, int T,
+                                   const int* __restrict__ gid, const double* __restrict__ m, const double* __restrict__ vb,
+                                   const double* __restrict__ eg, const double* __restrict__ rg, const double* __restrict__ gx,
+                                   const double* __restrict__ gw, int nq, const double* __restrict__ Ag, const double* __restrict__ Al,
+                                   int Q, double* __restrict__ out)
+{
+    gsi_infl_rows<OrdinalLik>(n0, R, P, Kz, X, Z, y, gid, m, vb, eg, rg, {{gx, gw, nq}, off, y, thr, T}, Ag, Al, Q, out);
+}
+
 template <class Lik>
 static int gs_launch_infl_rows(lrvb_ctx* c, int Kz, const double* Z, typename Lik::Args la, i64 n0, i64 n1, const int* gid, const double* m,
                                const double* vb, const double* eg, const double* rg, const double* Ag, const double* Al, i64 Q,
@@ -892,6 +1065,10 @@ static int gs_launch_infl_rows(lrvb_ctx* c, int Kz, const double* Z, typename Li
         hipLaunchKernelGGL(glmm_censnormal_infl_rows_kernel, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
                            (const double*)la.off, (const double*)la.disp, (const double*)la.y, (const double*)la.cens, gid, m, vb, eg, rg,
                            la.q.gx, la.q.gw, la.q.nq, Ag, Al, (int)Q, out);
+    else if constexpr (std::is_same<Lik, OrdinalLik>::value)
+        hipLaunchKernelGGL(glmm_ordinal_infl_rows_kernel, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz, (const double*)c->X.p, Z,
+                           (const double*)la.off, (const double*)la.y, (const double*)la.thr, la.T, gid, m, vb, eg, rg, la.q.gx, la.q.gw,
+                           la.q.nq, Ag, Al, (int)Q, out);
     else if constexpr (gs_link_of<Lik>::value != GLMM_LINK_LOGIT)
         hipLaunchKernelGGL(glmm_link_infl_rows_kernel<gs_link_of<Lik>::value>, dim3(glmm_grid(R)), dim3(256), 0, c->stream, n0, R, (int)c->P, Kz,
                            (const double*)c->X.p, Z, (const double*)la.off, (const double*)la.trials, (const double*)la.y, gid, m, vb, eg, rg,

@@ -916,6 +916,113 @@ struct CensNormalLik : NodeTableLik {
     }
 };
 
+// Ordinal response with a cumulative logit link: y in {0 .. T}, cut points -inf = a_0 < a_1 < .. < a_T < a_T+1 = +inf,
+//   P(y = j | t) = sigma(a_j+1 - t) - sigma(a_j - t) = sigma(hi - t) sigma(t - lo) (1 - e^-D),   hi = a_y+1, lo = a_y, D = hi - lo,
+//   h(t) = -log P = softplus(t - hi) + softplus(lo - t) - log(-expm1(-D)):
+// two logistic node functions at two shifts plus a term without t, no cancellation anywhere.  The node expressions are
+// LogisticLik::moments' at a = t - hi and at b = lo - t (d/dt b = -1: the odd derivatives of the lo term are negated); a missing cut
+// point of an end category is a sentinel +-inf, at which e = exp(-inf) = 0 and every expression is an exact zero -- no branch.  The
+// D term is one closed form per LIVE row behind the shuffles, in the value only; at D = +inf it is -log1p(-0) = -0.
+// The table of T + 2 cut points (both sentinels) is copied to LDS once per workgroup; per row the category, clamped to [0, T] as an
+// INTEGER (a bound on an address: the host entries refuse such data before any walk), and the folds hi - o and lo - o are staged from
+// the row's ORIGINAL index, so that t - hi = rho_x - (hi - o) is one subtraction and a common shift of the cut points and the offset
+// changes nothing wherever the shifted values are exact.  Not canonical in the walk's sense (y picks the cut points): MINUS_Y is
+// false, coefficients by Stein's identity in the five-row layout.  No clamp of values: a non-finite sum reaches the entry, which
+// refuses it.  The predict walk is not instantiated for this policy (no `mean`): P(y <= j) is the binomial entry's at offset o - a_j+1.
+struct OrdinalLik : NodeTableLik {
+    static constexpr int MAX_T = 15;
+    struct Args { LogisticLik::Args q; const double* __restrict__ off; const double* __restrict__ y; const double* __restrict__ thr; int T; };   // off may be nullptr; thr: T + 2 doubles
+    struct Lds { LogisticLik::Lds q; double tab[MAX_T + 2], s_hi[GLMM_T], s_lo[GLMM_T]; int s_cat[GLMM_T]; };
+    struct ThrMoments { double a0, a1, a2, b0, b1, b2; };                  // E sigma, E sigma', E sigma'' at t - hi and at lo - t
+    static constexpr const char* LIMITS = "ordinal mixed model: P <= 64, 1 <= K <= 4, at most 128 nodes, 1 to 15 thresholds";
+    static bool args_ok(const Args& a) { return LogisticLik::args_ok(a.q) && a.y != nullptr && a.thr != nullptr && a.T >= 1 && a.T <= MAX_T; }
+    static constexpr bool MINUS_Y = false;
+
+    static __device__ __forceinline__ void init(Lds& L, const Args& a, int tid)
+    {
+        LogisticLik::init(L.q, a.q, tid);
+        if (tid < a.T + 2) L.tab[tid] = a.thr[tid];
+    }
+    // after the barrier that follows init: reads the table
+    static __device__ __forceinline__ void stage_row(Lds& L, const Args& a, int t, bool live, i64 src)
+    {
+        const double o = (a.off && live) ? a.off[src] : 0.0;
+        const double yy = live ? a.y[src] : 0.0;
+        const int j = yy >= 0.0 ? (yy <= (double)a.T ? (int)yy : a.T) : 0;   // a NaN compares false: 0
+        L.s_cat[t] = j; L.s_hi[t] = L.tab[j + 1] - o; L.s_lo[t] = L.tab[j] - o;
+    }
+    static __device__ __forceinline__ double row_shift(const Lds&, int) { return 0.0; }   // the folds are read by gs_lane_row()
+    // D = hi - lo from the TABLE, not from the two folds: those carry the rounding of a - o, which at a small D would be most of it
+    static __device__ __forceinline__ double row_delta(const Lds& L, int row) { const int j = L.s_cat[row]; return L.tab[j + 1] - L.tab[j]; }
+
+    // softplus, sigma, sigma' (N = 2: g[1], g[2] only) and sigma'', sigma''' (N = 5) at x, as LogisticLik::moments forms them
+    template <int N>
+    static __device__ __forceinline__ void node(double x, double* g)
+    {
+        const double e = exp(-fabs(x)), ie = 1.0 / (1.0 + e);
+        const double g2 = e * ie * ie;
+        g[1] = x >= 0.0 ? ie : e * ie; g[2] = g2;
+        if constexpr (N == 5) {
+            const double om = (1.0 - e) * ie;                            // |1 - 2 sigma|
+            g[0] = (x > 0.0 ? x : 0.0) + log1p(e);
+            g[3] = x >= 0.0 ? -g2 * om : g2 * om; g[4] = g2 * (1.0 - 6.0 * g2);
+        }
+    }
+    // -log(1 - e^-D), D > 0: past log 2 through log1p (1 - e^-D rounds to 1 from D = 37 on)
+    static __device__ __forceinline__ double delta_term(double D) { return D > 0.6931471805599453 ? -log1p(-exp(-D)) : -log(-expm1(-D)); }
+
+    // a1' = E h' and E h'' = 2 a2' per unit weight, on all four lanes of a row
+    static __device__ __forceinline__ void infl(const Lds& L, const Args& a, double, bool live, int q4, double rho, double s, double& e1,
+                                                double& e2)
+    {
+        const int row = gs_lane_row();
+        const double hi = L.s_hi[row], lo = L.s_lo[row];
+        e1 = 0.0; e2 = 0.0;
+        gh_nodes(L.q, a.q.nq, live, q4, rho, s, [&](double t, double wk) {
+            double ga[5], gb[5];
+            node<2>(t - hi, ga);
+            node<2>(lo - t, gb);
+            e1 += wk * (ga[1] - gb[1]); e2 += wk * (ga[2] + gb[2]);
+        });
+        gh_lane_sum(e1, e2);
+    }
+    static __device__ __forceinline__ Moments moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
+    {
+        const int row = gs_lane_row();
+        const double hi = L.s_hi[row], lo = L.s_lo[row];
+        double e[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        gh_nodes(L.q, a.q.nq, live, q4, rho, s, [&](double t, double wk) {
+            double ga[5], gb[5];
+            node<5>(t - hi, ga);
+            node<5>(lo - t, gb);
+#pragma unroll
+            for (int i = 0; i < 5; ++i) e[i] += wk * ((i & 1) ? ga[i] - gb[i] : ga[i] + gb[i]);
+        });
+        gh_lane_sum<5>(e);
+        return {live ? e[0] + delta_term(row_delta(L, row)) : 0.0, e[1], e[2], e[3], e[4]};
+    }
+    static __device__ __forceinline__ double coefs(const Lds&, int, const Moments& mo, double wi, double, double, double, double* k)
+    {
+        return stein_coefs(mo, wi, k);
+    }
+    // the six node sums of the threshold pass (glmm_thr_rows_kernel), on all four lanes of a row
+    static __device__ __forceinline__ ThrMoments thr_moments(const Lds& L, const Args& a, bool live, int q4, double rho, double s)
+    {
+        const int row = gs_lane_row();
+        const double hi = L.s_hi[row], lo = L.s_lo[row];
+        double e[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        gh_nodes(L.q, a.q.nq, live, q4, rho, s, [&](double t, double wk) {
+            double ga[5], gb[5];
+            node<5>(t - hi, ga);                                         // the value and sigma''' are not read and fall to the compiler
+            node<5>(lo - t, gb);
+            e[0] += wk * ga[1]; e[1] += wk * ga[2]; e[2] += wk * ga[3];
+            e[3] += wk * gb[1]; e[4] += wk * gb[2]; e[5] += wk * gb[3];
+        });
+        gh_lane_sum<6>(e);
+        return {e[0], e[1], e[2], e[3], e[4], e[5]};
+    }
+};
+
 // ---- the dispersion-derivative policies ----------------------------------------------------------------------
 // The dispersion of the Beta and the NB2 model as phi_n = e^lambda phi0_n with ONE scalar lambda: every derivative below is in
 // lambda at fixed t, d/d lambda = phi d/d phi.  A policy of this kind serves glmm_disp_rows_kernel (k_glmm_slopes.hip) and supplies

@@ -231,7 +231,7 @@ extern "C" int lrvb_ctx_destroy(lrvb_ctx* c) {
     DevBuf* all[] = { &c->X, &c->y, &c->w, &c->quadA, &c->quadM, &c->quadB, &c->theta, &c->eta, &c->j1, &c->j2,
                       &c->vtmp, &c->vtmp2, &c->vtmp3, &c->g_eta, &c->g_free, &c->lp, &c->cw, &c->zbuf,
                       &c->part_vec, &c->part_val, &c->stats, &c->tile_part, &c->Heta, &c->Hfree, &c->Jdense,
-                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn, &c->gz, &c->goff, &c->gtr, &c->gdisp, &c->gcens, &c->glmms, &c->glmms_fac, &c->glmms_T, &c->glmms_gcov,
+                      &c->Tdense, &c->work1, &c->chol, &c->cholW, &c->hprog, &c->cgH, &c->groups, &c->mx_theta, &c->mx_lam, &c->mx_A, &c->mx_U, &c->mx_g, &c->mx_Xk, &c->mx_R, &c->cgT, &c->ones, &c->cgm[0], &c->cgm[1], &c->cgm[2], &c->cgm[3], &c->cgm[4], &c->cgm[5], &c->cgm[6], &c->cgm[7], &c->cgm[8], &c->rhs, &c->cgx, &c->cgr, &c->cgp, &c->cgq, &c->cgz, &c->scal, &c->opt, &c->dkw, &c->cyv, &c->rvec, &c->red_scratch, &c->gstats, &c->Zs, &c->ws, &c->bpart, &c->gpad, &c->boxmap, &c->jtmap, &c->qg_Mt, &c->qg_T1, &c->qg_Av, &c->hres.H, &c->hres.theta_dev, &c->qstats, &c->lmvn, &c->gz, &c->goff, &c->gtr, &c->gdisp, &c->gcens, &c->gthr, &c->glmms, &c->glmms_fac, &c->glmms_T, &c->glmms_gcov,
                       &c->sm.labels, &c->sm.p, &c->sm.wpad, &c->sm.work, &c->sm.col, &c->sm.tiles, &c->sm.rows };
     for (DevBuf* b : all) buf_free(*b);
     if (c->host_pinned) (void)hipHostFree(c->host_pinned);
@@ -325,7 +325,7 @@ extern "C" int lrvb_set_data(lrvb_ctx* c, int slot, const double* host, int64_t 
     LRVB_TRY(buf_reserve(c, *b, n));
     LRVB_TRY(h2d(c, b->p, host, n));
     if (slot == LRVB_SLOT_X) { c->have_X = true; c->x2_ready = false; c->gstats_valid = false; c->zs_valid = false; }
-    if (slot == LRVB_SLOT_Y) c->have_y = true;
+    if (slot == LRVB_SLOT_Y) { c->have_y = true; c->ord_y_T = -1; }
     invalidate_caches(c, true);
     return LRVB_OK;
 }
@@ -338,7 +338,7 @@ extern "C" int lrvb_set_data_dev(lrvb_ctx* c, int slot, const double* data_dev, 
     if (b->p && b->owned) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(b->p)); }
     b->p = const_cast<double*>(data_dev); b->n = n; b->owned = false; ++c->buf_epoch;
     if (slot == LRVB_SLOT_X) { c->have_X = true; c->x2_ready = false; c->gstats_valid = false; c->zs_valid = false; }
-    if (slot == LRVB_SLOT_Y) c->have_y = true;
+    if (slot == LRVB_SLOT_Y) { c->have_y = true; c->ord_y_T = -1; }
     invalidate_caches(c, true);
     return LRVB_OK;
 }
@@ -2607,6 +2607,7 @@ static GlmmLik glmms_ztpoisson(const double* gh_x, const double* gh_w, int32_t n
 static GlmmLik glmms_ztnegbin(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_ZTNEGBIN, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, LRVB_LINK_LOGIT, nullptr}; }
 static GlmmLik glmms_beta(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_BETA, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, LRVB_LINK_LOGIT, nullptr}; }
 static GlmmLik glmms_censnormal(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_CENSNORMAL, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, LRVB_LINK_LOGIT, nullptr, nullptr}; }
+static GlmmLik glmms_ordinal(const double* gh_x, const double* gh_w, int32_t n_nodes) { return GlmmLik{GLMM_ORDINAL, gh_x, gh_w, (int)n_nodes, nullptr, nullptr, false, LRVB_LINK_LOGIT, nullptr, nullptr, nullptr, 0}; }
 static GlmmLik glmms_gamma() { return GlmmLik{GLMM_GAMMA, nullptr, nullptr, 0, nullptr, nullptr, false, LRVB_LINK_LOGIT, nullptr}; }
 // The likelihoods whose expectation is closed form: one exp per row, no nodes to check, upload or make room for.
 static bool glmms_closed_form(const GlmmLik& lik) { return lik.kind == GLMM_POISSON || lik.kind == GLMM_GAMMA; }
@@ -2616,7 +2617,22 @@ static const char* glmms_name(const GlmmLik& lik) {
     if (lik.kind == GLMM_BETA) return "Beta";
     if (lik.kind == GLMM_GAMMA) return "Gamma";
     if (lik.kind == GLMM_CENSNORMAL) return "censored Gaussian";
+    if (lik.kind == GLMM_ORDINAL) return "ordinal";
     return lik.kind == GLMM_POISSON ? "Poisson" : (lik.kind == GLMM_BINOMIAL ? "binomial" : "logistic");
+}
+
+// The categories of the ordinal model are integers in 0 .. T: anything else is refused here, on the host, before a walk is launched
+// (the kernels clamp the table index besides).  y is read back once per (y, T): lrvb_set_data forgets the verdict, a smaller T too.
+static int glmms_ordinal_check_y(lrvb_ctx* c) {
+    if (c->ord_y_T == c->gthr_T) return LRVB_OK;
+    std::vector<double> yh((size_t)c->N);
+    LRVB_TRY(d2h(c, yh.data(), c->y.p, (size_t)c->N));
+    const double top = (double)c->gthr_T;
+    for (i64 i = 0; i < c->N; ++i)
+        if (!(yh[i] >= 0.0 && yh[i] <= top && yh[i] == std::floor(yh[i])))
+            LRVB_FAIL(LRVB_ERR_INVALID, "y[%lld] is %g: with %d thresholds the categories are the integers 0 .. %d", (long long)i, yh[i], c->gthr_T, c->gthr_T);
+    c->ord_y_T = c->gthr_T;
+    return LRVB_OK;
 }
 
 // The argument and state checks of every entry over the rows, in one order (`other_null`: a required pointer of the entry's own is null).
@@ -2648,10 +2664,13 @@ static int glmms_check(lrvb_ctx* c, const GlmmLik& lik, const double* mean, cons
         LRVB_FAIL(LRVB_ERR_STATE, "no censoring status: call lrvb_set_censoring first");
     if (lik.kind == GLMM_CENSNORMAL && c->gcens_n != c->N)
         LRVB_FAIL(LRVB_ERR_STATE, "the censoring status has %lld entries, the model has %lld observations", (long long)c->gcens_n, (long long)c->N);
+    if (lik.kind == GLMM_ORDINAL && c->gthr_T == 0)
+        LRVB_FAIL(LRVB_ERR_STATE, "no thresholds: call lrvb_set_thresholds first");
     LRVB_TRY(check_len(P_in, c->P, "mean / var"));
     LRVB_TRY(check_len(G_in, c->n_groups, lik.unit ? "e / r" : "groups of e / r"));
     for (i64 j = 0; j < c->P; ++j) if (!(var[j] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "var[%lld] is not positive", (long long)j);
     for (i64 g = 0; g < c->n_groups * K; ++g) if (!(r_loc[g] > 0.0)) LRVB_FAIL(LRVB_ERR_INVALID, "r[%lld] is not positive", (long long)g);
+    if (lik.kind == GLMM_ORDINAL) LRVB_TRY(glmms_ordinal_check_y(c));
     return LRVB_OK;
 }
 
@@ -2672,6 +2691,7 @@ static int glmms_to_device(lrvb_ctx* c, GlmmLik& lik, double* g) {
     if (lik.kind == GLMM_BETA) { lik.trials = c->gdisp.p; lik.y = c->y.p; }       // phi in the trials slot again; y holds logit(y)
     if (lik.kind == GLMM_GAMMA) { lik.trials = c->gdisp.p; lik.y = c->y.p; }      // the shape phi in the trials slot; y holds log(y)
     if (lik.kind == GLMM_CENSNORMAL) { lik.trials = c->gdisp.p; lik.y = c->y.p; lik.cens = c->gcens.p; }   // the precision phi in the trials slot; y the responses
+    if (lik.kind == GLMM_ORDINAL) { lik.y = c->y.p; lik.thr = c->gthr.p; lik.T = c->gthr_T; }   // y the categories; the table with both sentinels
     if (glmms_closed_form(lik)) return LRVB_OK;
     LRVB_TRY(h2d(c, g, lik.gx, (size_t)lik.n_nodes));
     LRVB_TRY(h2d(c, g + 128, lik.gw, (size_t)lik.n_nodes));
@@ -2756,6 +2776,8 @@ static int glmms_terms(lrvb_ctx* c, GlmmLik lik, const double* mean, const doubl
         LRVB_FAIL(LRVB_ERR_INVALID, "the zero-truncated negative binomial data term is not finite at this point: phi softplus(eta) underflows to 0 on a node, or a moment overflows, for some row (the kernel does not clamp)");
     if (lik.kind == GLMM_CENSNORMAL && !std::isfinite(*value_out))
         LRVB_FAIL(LRVB_ERR_INVALID, "the censored Gaussian data term is not finite at this point: phi (rho - y)^2 overflows for some observed row, or -log Phi in the tail of some censored row (the kernel does not clamp)");
+    if (lik.kind == GLMM_ORDINAL && !std::isfinite(*value_out))
+        LRVB_FAIL(LRVB_ERR_INVALID, "the ordinal data term is not finite at this point: the point or the offset is not finite, or a softplus overflows, for some row (the kernel does not clamp)");
     if (lik.kind == GLMM_BETA && !std::isfinite(*value_out))
         LRVB_FAIL(LRVB_ERR_INVALID, "the Beta data term is not finite at this point: the point, the offset or logit(y) is not finite for some row (no finite point is refused)");
     c->glmms_valid = true; c->glmms_K = lik.unit ? 0 : (int)K;           // 0: the sums of lrvb_glmm_terms, for lrvb_glmm_schur only
@@ -3259,6 +3281,99 @@ extern "C" int lrvb_glmm_censnormal_group_influence(lrvb_ctx* c, const double* m
                                                     int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, double* out) {
     LRVB_TRY(ctx_bind(c));
     return glmms_group_influence(c, glmms_censnormal(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out);
+}
+
+// ---- ordinal mixed model: cumulative logit rows with estimated thresholds -----------------------------------
+// The cut points: T finite, strictly increasing values, kept as the table [-inf, alpha_1 .. alpha_T, +inf] on the
+// device (17 doubles at most; nothing of length N is touched).  Checked ahead of everything else: a refusal leaves the state as it was.
+extern "C" int lrvb_set_thresholds(lrvb_ctx* c, const double* alpha, int64_t T) {
+    LRVB_TRY(ctx_bind(c));
+    if (!alpha) LRVB_FAIL(LRVB_ERR_INVALID, "null argument");
+    if (T < 1 || T > 15) LRVB_FAIL(LRVB_ERR_INVALID, "1 to 15 thresholds (got %lld): 2 to 16 ordered categories", (long long)T);
+    for (int64_t j = 0; j < T; ++j) {
+        if (!std::isfinite(alpha[j])) LRVB_FAIL(LRVB_ERR_INVALID, "thresholds[%lld] is not finite", (long long)j);
+        if (j > 0 && !(alpha[j] > alpha[j - 1]))
+            LRVB_FAIL(LRVB_ERR_INVALID, "the thresholds must increase strictly: thresholds[%lld] = %g is not above thresholds[%lld] = %g", (long long)j, alpha[j], (long long)(j - 1), alpha[j - 1]);
+    }
+    double tab[17];
+    tab[0] = -INFINITY;
+    for (int64_t j = 0; j < T; ++j) tab[j + 1] = alpha[j];
+    tab[T + 1] = INFINITY;
+    LRVB_TRY(buf_reserve(c, c->gthr, 17));
+    c->glmms_drop();
+    c->gthr_T = 0;
+    LRVB_TRY(h2d(c, c->gthr.p, tab, (size_t)(T + 2)));
+    c->gthr_T = (int)T;
+    return LRVB_OK;
+}
+
+// The shared bodies with the OrdinalLik policy: the caller's nodes, the RAW offset of lrvb_set_offset and the table of
+// lrvb_set_thresholds; the context's y holds the categories.  Neither trials, link, dispersion nor status is read.
+extern "C" int lrvb_glmm_ordinal_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                       const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                       int32_t n_nodes, double* value_out, double* grad_global_out, double* H_blocks_out,
+                                       double* group_sums_out, int32_t want_border) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_terms(c, glmms_ordinal(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, value_out, grad_global_out,
+                       H_blocks_out, group_sums_out, want_border);
+}
+
+extern "C" int lrvb_glmm_ordinal_obs_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                               const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                               int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, int64_t n0,
+                                               int64_t n1, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_obs_influence(c, glmms_ordinal(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, n0, n1, out);
+}
+
+extern "C" int lrvb_glmm_ordinal_group_influence(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                                 const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                                 int32_t n_nodes, const double* A_global, const double* A_local, int64_t Q, double* out) {
+    LRVB_TRY(ctx_bind(c));
+    return glmms_group_influence(c, glmms_ordinal(gh_x, gh_w, n_nodes), mean, var, P_in, e_loc, r_loc, G_in, K, A_global, A_local, Q, out);
+}
+
+// The derivatives in the thresholds (glmm_thr_rows_kernel).  The checks of the terms entry, in its order.  Everything lives in
+// c->work1, as the dispersion entry keeps its own:
+//   [nodes 256 | m, v | e, r | tile partials (2 (2 K T) per tile) | scalar partials (3 T per tile) | workgroup blocks (T 2 P each) |
+//    local sums (G x 2 K T) | global sums (T x 2 P) | g, H diagonal, H off-diagonal (3 T)]
+// the last three adjacent, so that the packed result goes through the reduce hook in ONE piece.  Neither c->glmms nor the factor nor
+// the group covariance is written, and nothing is dropped.
+extern "C" int lrvb_glmm_ordinal_threshold_terms(lrvb_ctx* c, const double* mean, const double* var, int64_t P_in, const double* e_loc,
+                                                 const double* r_loc, int64_t G_in, int64_t K, const double* gh_x, const double* gh_w,
+                                                 int32_t n_nodes, double* g_out, double* h_diag_out, double* h_off_out,
+                                                 double* cross_global_out, double* cross_local_out) {
+    LRVB_TRY(ctx_bind(c));
+    GlmmLik lik = glmms_ordinal(gh_x, gh_w, n_nodes);
+    LRVB_TRY(glmms_check(c, lik, mean, var, P_in, e_loc, r_loc, G_in, K, !g_out || !h_diag_out || !h_off_out || !cross_global_out || !cross_local_out));
+    const i64 N = c->N, P = c->P, G = c->n_groups, GK = G * K, T = c->gthr_T, ncl = 2 * K * T, ncg = T * 2 * P;
+    const i64 n_tiles = glmm_num_tiles(N), nblk = (i64)glmm_thr_grid(N), nres = G * ncl + ncg + 3 * T;
+    GlmmPoint pt;
+    LRVB_TRY(glmms_point_upload(c, lik, mean, var, e_loc, r_loc, P, GK, (size_t)(up(n_tiles * 2 * ncl) + up(3 * T * n_tiles) + up(nblk * ncg) + nres), &pt));
+    double* part = pt.g + pt.doubles; double* vpart = part + up(n_tiles * 2 * ncl); double* cpart = vpart + up(3 * T * n_tiles);
+    double* gsum = cpart + up(nblk * ncg); double* gred = gsum + G * ncl; double* sred = gred + ncg;
+    HIP_TRY(hipMemsetAsync(gsum, 0, (size_t)nres * sizeof(double), c->stream));       // empty groups keep the zeros
+    LRVB_TRY(launch_glmm_thr_rows(c, lik, (int)K, pt.m, pt.v, pt.e, pt.r, gsum, part, vpart, cpart, gred));
+    for (i64 q = 0; q < 3 * T; ++q) {
+        hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, c->stream, (const double*)(vpart + q * n_tiles), n_tiles, sred + q);
+        HIP_TRY(hipGetLastError());
+    }
+    LRVB_TRY(obs_reduce(c, gsum, nres));
+    std::vector<double> sh((size_t)(3 * T));
+    LRVB_TRY(d2h(c, sh.data(), sred, (size_t)(3 * T)));
+    for (i64 q = 0; q < 3 * T; ++q)
+        if (!std::isfinite(sh[q]))
+            LRVB_FAIL(LRVB_ERR_INVALID, "the threshold derivative of the ordinal data term is not finite at this point");
+    for (i64 j = 0; j < T; ++j) { g_out[j] = sh[j]; h_diag_out[j] = sh[T + j]; if (j + 1 < T) h_off_out[j] = sh[2 * T + j]; }
+    LRVB_TRY(d2h(c, cross_global_out, gred, (size_t)ncg));
+    LRVB_TRY(d2h(c, cross_local_out, gsum, (size_t)(G * ncl)));
+    // the node sums behind the cross blocks are bounded, so only a NaN of the point or the offset reaches them -- on rows of an end
+    // category it can miss g and H (the sentinel's entries are not summed), hence the blocks are looked at themselves
+    for (i64 i = 0; i < ncg; ++i)
+        if (!std::isfinite(cross_global_out[i])) LRVB_FAIL(LRVB_ERR_INVALID, "the threshold derivative of the ordinal data term is not finite at this point");
+    for (i64 i = 0; i < G * ncl; ++i)
+        if (!std::isfinite(cross_local_out[i])) LRVB_FAIL(LRVB_ERR_INVALID, "the threshold derivative of the ordinal data term is not finite at this point");
+    return LRVB_OK;
 }
 
 // ---- the derivative in the log-dispersion of the Beta and the NB2 mixed model (k_glmm_slopes.hip) ----------

@@ -153,6 +153,9 @@ struct lrvb_ctx {
     DevBuf gdisp; i64 gdisp_n = 0;
     // lrvb_glmm_censnormal_* also read the per-row censoring status of lrvb_set_censoring (-1 / 0 / +1 as doubles), gcens_n of them (0 = none: refused)
     DevBuf gcens; i64 gcens_n = 0;
+    // lrvb_glmm_ordinal_* read the cut points of lrvb_set_thresholds: gthr holds -inf, the gthr_T values (0 = none: refused), +inf.
+    // ord_y_T: the T for which the categories in y were found to lie in 0 .. T (-1: not checked since y was set)
+    DevBuf gthr; int gthr_T = 0; int ord_y_T = -1;
     DevBuf opt;                    // trust-region Newton-CG: 12 D-vectors (+ the D x D preconditioner)
     DevBuf cgm[9];                 // blocked CG: B, X, R, P, Q, Z (Q x D), U, W (Q x V), R^T (P x Q)
     DevBuf cgT;                    // N x Q products X U^T of the blocked HVP
@@ -270,12 +273,14 @@ enum GlmmKind { GLMM_LOGISTIC = 0, GLMM_POISSON = 1, GLMM_BINOMIAL = 2, GLMM_ZTP
                 GLMM_ZTNEGBIN = 4,     // zero-truncated NB2: nodes, the shifted offset, the dispersion phi in `trials`, and `y`
                 GLMM_BETA = 5,         // Beta: nodes, the raw offset, the precision phi in `trials`, and logit(y) in `y`
                 GLMM_GAMMA = 6,        // Gamma, log link: NO nodes, the raw offset, the shape phi in `trials`, and log(y) in `y`
-                GLMM_CENSNORMAL = 7 }; // censored Gaussian: nodes, the raw offset, the precision phi in `trials`, y in `y`, the status in `cens`
+                GLMM_CENSNORMAL = 7,   // censored Gaussian: nodes, the raw offset, the precision phi in `trials`, y in `y`, the status in `cens`
+                GLMM_ORDINAL = 8 };    // ordinal, cumulative logit: nodes, the raw offset, the categories in `y`, the table of cut points in `thr`
 // `link` (binomial only, LRVB_LINK_*; 0 = logit: BinomialLik) picks the probit or cloglog policy of DESIGN.md section 35, and `y`
 // is the response those two stage themselves (the host bodies fill it in with the offset and the trials).
 struct GlmmLik { GlmmKind kind; const double* gx; const double* gw; int n_nodes; const double* off; const double* trials; bool unit;
                  int link; const double* y;
-                 const double* cens; };   // censored Gaussian only: the per-row status -1 / 0 / +1 as doubles (device), or nullptr: every row observed
+                 const double* cens;      // censored Gaussian only: the per-row status -1 / 0 / +1 as doubles (device), or nullptr: every row observed
+                 const double* thr; int T; };   // ordinal only: -inf, the T cut points, +inf (device, T + 2 doubles); null and 0 for every other kind
 int  glmm_slopes_ncol(int P, int K);      // columns of one group's sums: 2 K + K (2 K + 1) + 4 K P
 int  launch_glmm_slopes_rows(lrvb_ctx* c, const GlmmLik& lik, int K, const double* Z /* N x K; nullptr: the unit design */, const double* m, const double* vb,
                              const double* eg /* G x K */, const double* rg /* G x K */,
@@ -287,6 +292,11 @@ int  launch_glmm_disp_rows(lrvb_ctx* c, const GlmmLik& lik /* Beta, or binomial 
                            double* coef /* original row order: 2 x NP, d1 | d2 */, i64 NP,
                            double* gsum /* G x 2 K, zeroed by the caller */, double* part /* 2 (2 K) doubles per tile of glmm_num_tiles */,
                            double* vpart /* 2 per tile */);
+unsigned glmm_thr_grid(i64 N);            // workgroups of glmm_thr_rows_kernel: one block of cpart each
+int  launch_glmm_thr_rows(lrvb_ctx* c, const GlmmLik& lik /* ordinal, on the device */, int K, const double* m, const double* vb,
+                          const double* eg, const double* rg, double* gsum /* G x 2 K T, zeroed by the caller */,
+                          double* part /* 2 (2 K T) doubles per tile of glmm_num_tiles */, double* vpart /* 3 T per tile: slot q at q n_tiles */,
+                          double* cpart /* T x 2 P per workgroup of glmm_thr_grid */, double* cross /* T x 2 P */);
 int  launch_glmm_poisson_scale_blocks(lrvb_ctx* c, double* Hb /* 3 x P x P, all formed with h: blocks 1, 2 times 1/2, 1/4 */);
 int  launch_glmm_gamma_scale_blocks(lrvb_ctx* c, double* Hb /* 3 x P x P, all formed with g: blocks 1, 2 times -1/2, 1/4 */);
 int  launch_glmm_slopes_schur_rows(lrvb_ctx* c, int K, const double* gsum, const double* loc /* G x K (2 K + 1) */,

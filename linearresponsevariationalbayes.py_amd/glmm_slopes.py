@@ -199,6 +199,7 @@ class _LogisticMixedModel(DeviceModel):
     `_solve_on_device` where it has a device-resident block-arrow solve."""
     _stats_at_point = True
     _loss = 'logistic'                               # the loss the device context is created with
+    _minus_y = True                                  # `cross_hessian` subtracts y from `_row_psi_derivs`' first value (False: a1' comes whole)
 
     def __init__(self, par, x, y, z, groups, n_groups, beta_prior_info, mu_prior, tau_prior, gh_deg, names, weights, device):
         """z: the N x K group design, or None for one effect per group with the unit design (nothing is sent to the device).
@@ -589,7 +590,8 @@ class _LogisticMixedModel(DeviceModel):
         rho = x @ eta[:P] + np.sum(z * e[gid], axis=1)
         s = (x * x) @ v + np.sum(z * z * r[gid], axis=1)
         p_rho, p_s = self._row_psi_derivs(rho, s)
-        p_rho = p_rho - self._y
+        if self._minus_y:
+            p_rho = p_rho - self._y
         C = np.zeros((N, ng + 2 * GK))
         C[:, :P] = p_rho[:, None] * x
         C[:, P:2 * P] = p_s[:, None] * (x * x) * (-v * v)[None, :]

@@ -786,6 +786,49 @@ class DeviceContext(object):
         """The latent mean of the censored Gaussian mixed model (lrvb_glmm_censnormal_predict); new rows carry an offset."""
         return self._glmm_predict(self._lib.lrvb_glmm_censnormal_predict, True, 1, mean, var, e, r, gh_x, gh_w, cov_beta, n0, n1, new)
 
+    # ---- ordinal mixed model, cumulative logit (lrvb_glmm_ordinal_*): the raw offset, the cut points of `set_thresholds`, the categories as y ----
+    def set_thresholds(self, thresholds):
+        """The T strictly increasing finite cut points of the ordinal mixed model, 1 <= T <= 15 (lrvb_set_thresholds): T doubles go
+        to the device, nothing of length N.  Only the `glmm_ordinal_*` entries read them; the resident group sums are dropped."""
+        a = _hip.as_f64(thresholds).ravel()
+        self._check(self._lib.lrvb_set_thresholds(self._h, _hip.ptr(a), a.size))
+        self._n_thresholds = int(a.size)                                    # the sizes of `glmm_ordinal_threshold_terms`
+
+    def glmm_ordinal_terms(self, mean, var, e, r, gh_x, gh_w, want_grad=True, want_hess=True, want_border=True):
+        """Data term of the ordinal mixed model with K effects per group, the offset of `set_offset` and the cut points of
+        `set_thresholds` (lrvb_glmm_ordinal_terms).  What `glmm_slopes_terms` returns, in its layouts.  The group sums stay resident
+        for `glmm_slopes_schur`.  A category outside 0 .. T or a point at which a sum is not finite is a ValueError."""
+        return self._glmm_terms(self._lib.lrvb_glmm_ordinal_terms, True, True, mean, var, e, r, gh_x, gh_w, want_grad, want_hess, want_border)
+
+    def glmm_ordinal_obs_influence(self, mean, var, e, r, gh_x, gh_w, A, n0=0, n1=None):
+        """(n1 - n0) x Q rows of the ordinal mixed model, as `glmm_slopes_obs_influence` (lrvb_glmm_ordinal_obs_influence)."""
+        return self._glmm_obs_influence(self._lib.lrvb_glmm_ordinal_obs_influence, True, True, mean, var, e, r, gh_x, gh_w, A, n0, n1)
+
+    def glmm_ordinal_group_influence(self, mean, var, e, r, gh_x, gh_w, A):
+        """G x Q group influence of the ordinal mixed model, as `glmm_slopes_group_influence` (lrvb_glmm_ordinal_group_influence)."""
+        return self._glmm_group_influence(self._lib.lrvb_glmm_ordinal_group_influence, True, True, mean, var, e, r, gh_x, gh_w, A)
+
+    def glmm_ordinal_threshold_terms(self, mean, var, e, r, gh_x, gh_w):
+        """(g (T), h_diag (T), h_off (T - 1), cross_global (T x 2 P), cross_local (G x T x 2 K)) of the ordinal mixed model at the cut
+        points of `set_thresholds` (lrvb_glmm_ordinal_threshold_terms): gradient and tridiagonal Hessian of the data term in the
+        thresholds alpha, and the derivative in alpha of its gradient in the coordinates (mean, var, e, r).  The resident group sums
+        and factor are not touched."""
+        m, v = _hip.as_f64(mean).ravel(), _hip.as_f64(var).ravel()
+        e, r = _hip.as_f64(e), _hip.as_f64(r)
+        gx, gw = _hip.as_f64(gh_x).ravel(), _hip.as_f64(gh_w).ravel()
+        P, T = self.n_cols, getattr(self, '_n_thresholds', 0)
+        if T < 1:
+            raise ValueError('no thresholds: call set_thresholds first')
+        if e.ndim != 2 or r.shape != e.shape or m.size != P or v.size != P or gx.size != gw.size:
+            raise ValueError('expected mean and var of length {}, e and r of one shape G x K and as many weights as nodes'.format(P))
+        G, K = e.shape
+        g, hd, ho = np.empty(T), np.empty(T), np.zeros(max(T - 1, 1))
+        cg, cl = np.empty((T, 2 * P)), np.empty((G, T, 2 * max(K, 0)))
+        self._check(self._lib.lrvb_glmm_ordinal_threshold_terms(self._h, _hip.ptr(m), _hip.ptr(v), P, _hip.ptr(e), _hip.ptr(r), G, K,
+                                                               _hip.ptr(gx), _hip.ptr(gw), gx.size, _hip.ptr(g), _hip.ptr(hd),
+                                                               _hip.ptr(ho), _hip.ptr(cg), _hip.ptr(cl)))
+        return g, hd, ho[:T - 1], cg, cl
+
     # ---- multinomial (softmax) regression: beta is (K - 1) x n_cols, D = (K - 1) n_cols (lrvb_softmax_*) --------------------
     def softmax_set_labels(self, labels, n_classes):
         y = np.ascontiguousarray(np.asarray(labels).ravel(), dtype=np.int32)
